@@ -13,6 +13,10 @@ factorised exchange of divshot_amd/parallel.py (all-reduce of the 11 geometry fl
 SH rows rebuilt locally; 56 B/splat on the wire instead of 236), or with --exchange allreduce one sum-all-reduce of all rows.
 value = 8 * K / time (whole job). `--views-per-step V` instead fixes V views per GPU per step (weak scaling, the round-1 shape).
 Rank 0 prints ONE JSON line.  Inputs are resident in HBM before the timed region starts.
+A plain run sets up, warms up, times the K steps and prints the headline (value, ms_per_step, step spread, exposed exchange);
+`--full` adds every side measurement after it (other gradient mode, collective microbenchmarks, strict single-view figure, kernel
+probes, per-stage timing, roofline, interactions, CPU baseline, parity against the CPU oracle). `--dump-outputs DIR` writes the last
+timed step's rendered views and gradient rows as DIR/<name>.npy (float32; seeded samples of the larger arrays, 64 MB at most).
 """
 import argparse
 import datetime
@@ -213,6 +217,30 @@ def scaling_model(n, world, views_per_rank, per_rank_compute_ms, measured_ms_per
                 "pipelined_ms_per_iteration": step_p, "pipelined_views_per_s": world * views_per_rank / (step_p * 1e-3)}}
 
 
+DUMP_BUDGET_BYTES = 60_000_000      # float data of --dump-outputs; with the .npy headers the folder stays under 64 MB
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """Write each float32 device tensor of `arrays` as out_dir/<name>.npy. The arrays share DUMP_BUDGET_BYTES evenly; one larger than
+    its share is written as a 1-D sample of its flattened elements: one element per equal stratum, at an offset drawn from a
+    generator seeded with `seed` and the array's size, so that two runs (or two builds) with the same arguments sample the same
+    elements."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() <= cap:
+            a = t.detach().float().cpu().numpy()
+        else:
+            stride = flat.numel() // cap
+            rng = np.random.default_rng([seed, flat.numel()])
+            idx = np.arange(cap, dtype=np.int64) * stride + rng.integers(0, stride, cap)
+            a = flat.index_select(0, torch.from_numpy(idx).to(flat.device)).float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def watchdog_seconds():
     try:
         return max(30.0, float(os.environ.get("DVS_BENCH_WATCHDOG_S", "900")))
@@ -293,8 +321,15 @@ def main():
     ap.add_argument("--tight-tiles", type=int, default=0,
                     help="1: dvs_opts.tile_bounds = DVS_TILES_TIGHT (opt-in: only the tiles the alpha >= 1/255 ellipse reaches; same images and "
                          "gradients, shorter lists). The headline (default 0) runs the canonical 3-sigma rectangles")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-iters", type=int, default=10, help="extra iterations with per-stage hipEvent timing")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every side measurement: the other gradient mode, collective microbenchmarks, "
+                         "the strict single-view figure, kernel probes, per-stage timing, roofline, interactions, CPU baseline and "
+                         "parity against the oracle. Off by default: a plain run sets up, warms up, times --steps steps and reports")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rendered images, gradient rows) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all: an array above its share as a fixed, seeded sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check against the oracle")
+    ap.add_argument("--profile-iters", type=int, default=10, help="--full: extra iterations with per-stage hipEvent timing")
     args = ap.parse_args()
 
     # `python bench.py --gpus N` with N > 1 and no launcher around it: start the N ranks ourselves (one process per GPU under
@@ -562,7 +597,74 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     elapsed = max_over_ranks(elapsed)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's results, before anything below reuses the buffers: its rendered views (group by group) and the
+        # gradient rows it accumulated (after the exchange, when there is one)
+        last = {"rgb": outs[0]} if K == 1 else {f"rgb_group{gi}": outs[gi % n_ctx] for gi in range(K - n_ctx, K)}
+        last.update({"grad_" + k: v for k, v in grads.items()})
+        dump_outputs(args.dump_outputs, last)
+    for r_ in rasts:
+        r_.get_num_rendered()         # raises if an asynchronous forward of the timed region overflowed its instance arena
 
+    ms_per_step = elapsed / args.steps * 1e3
+    value = GLOBAL_VIEWS * args.steps / elapsed
+    exchange_info = None
+    if multi:
+        exchange_info = {
+            "impl": args.exchange_impl + (": include/dvs_comm.h, the calls of libgstrain.so's train_step" if comm is not None else ": torch.distributed"),
+            "backend": comm.backend if comm is not None else ("torch.distributed/" + dist.get_backend()),
+            # what the COMMUNICATOR itself reports (ncclCommCount through dvs_comm_backend_ranks), not the launcher's WORLD_SIZE
+            "rccl_nranks": comm.backend_ranks if comm is not None else dist.get_world_size(),
+            "world_size_env": world, "exchange": exchange, "early_gather": bool(early), "a9_chunks": len(a9_chunks) if a9_chunks else 1,
+            "choreography": ("colour all-gather on the communication stream behind dvs_raster_backward_dcolor (under A9); "
+                             + ("A9 in %d splat chunks, each chunk's geometry groups as ONE grouped launch behind it; " % len(a9_chunks) if a9_chunks else "geometry all-reduce behind A9; ")
+                             + "SH rows rebuilt on the compute stream when the gather has landed, under the geometry all-reduce") if factorised else "one all-reduce of the flat gradient buffer",
+        }
+    headline = None
+    if rank == 0:
+        # what every run reports: the timed region itself (step durations and the exposed exchange from its own events)
+        step_ms = sorted(marks[i_].elapsed_time(marks[i_ + 1]) for i_ in range(args.steps))
+        step_spread = [step_ms[int(q * (len(step_ms) - 1))] for q in (0.1, 0.5, 0.9)] if step_ms else None
+        comm_ms = None
+        if comm_marks:
+            cm = sorted(a_.elapsed_time(b_) for a_, b_ in comm_marks)
+            comm_ms = {"mean": float(np.mean(cm)), "p50": cm[len(cm) // 2], "p90": cm[int(0.9 * (len(cm) - 1))],
+                       "note": "rank 0, main stream: from 'last view's backward done' to 'exchange complete' (the gathers of earlier views "
+                               "run under compute and are not in this figure)"}
+        headline = {
+            "metric": "train views/sec (fwd+bwd raster) at 1M splats 1920x1080" if args.workload == "C3" else f"train views/sec (fwd+bwd raster), workload {args.workload}",
+            "value": value, "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak" if weak else "strong", "vs_baseline": None,
+            "t_raster_ms_per_step": (ms_per_step - comm_ms["mean"]) if comm_ms else ms_per_step, "t_comm_exposed_ms_per_step": comm_ms,
+            "exchange": exchange_info, "rccl_nranks": exchange_info["rccl_nranks"] if exchange_info else None,
+            "step_ms_p10_p50_p90": step_spread, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{args.workload}: {n} splats, {W}x{H}, SH degree {deg}, {GLOBAL_VIEWS} views per iteration "
+                                   + ("(weak scaling: fixed per GPU), " if weak else f"sharded over {world} GPU(s) (BASELINE config C4), ") + f"{VPS} view(s) per GPU per step"
+                                   + (f" as {K} multi-view pass(es) of {G} view(s) (dvs_raster_forward_views / dvs_raster_backward_*)"
+                                      + (" software-pipelined over two contexts/streams, gradients accumulated" if K > 1 else ""))
+                                   + ((", RCCL exchange of the gradient rows: " + exchange) if world > 1 else ""),
+                       "views_per_step": world * VPS, "views_per_gpu_per_step": VPS, "ms_per_view": ms_per_step / VPS, "absgrad": bool(args.absgrad), "mode": args.mode, "stagger": bool(args.stagger), "groups": K, "views_per_group": G, "early_gather": bool(early), "a9_chunks": len(a9_chunks) if a9_chunks else 1, "async_forward": bool(args.async_forward), "hip_graph": bool(args.graph), "bwd_variant": args.bwd_variant, "fwd_variant": args.fwd_variant, "grad_mode": args.grad_mode, "tile_bounds": "tight (opt-in)" if args.tight_tiles else "canonical", "shN_layout": "tiled[N/64][45][64]" if tiled else "rows[N][45]"},
+            "full": bool(args.full),
+        }
+
+    def finish():
+        for r_ in rasts:
+            r_.close()
+        barrier()
+        if dist is not None:
+            dist.destroy_process_group()
+        if comm is not None:
+            comm.close()
+        if watchdog is not None:
+            watchdog.cancel()
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline), flush=True)
+        finish()
+        return
+
+    # ---- --full: everything below measures or checks beside the headline ----
     # the same step in the other gradient mode (libgstrain.so runs DVS_GRAD_LINEAGE, the headline DVS_GRAD_TRUE): a short timed
     # side loop, so that "same cost" is a measured statement
     other_mode = None
@@ -694,18 +796,6 @@ def main():
         stage_ms = {k: float(np.mean(v)) for k, v in acc.items()}
     barrier()
 
-    exchange_info = None
-    if multi:
-        exchange_info = {
-            "impl": args.exchange_impl + (": include/dvs_comm.h, the calls of libgstrain.so's train_step" if comm is not None else ": torch.distributed"),
-            "backend": comm.backend if comm is not None else ("torch.distributed/" + dist.get_backend()),
-            # what the COMMUNICATOR itself reports (ncclCommCount through dvs_comm_backend_ranks), not the launcher's WORLD_SIZE
-            "rccl_nranks": comm.backend_ranks if comm is not None else dist.get_world_size(),
-            "world_size_env": world, "exchange": exchange, "early_gather": bool(early), "a9_chunks": len(a9_chunks) if a9_chunks else 1,
-            "choreography": ("colour all-gather on the communication stream behind dvs_raster_backward_dcolor (under A9); "
-                             + ("A9 in %d splat chunks, each chunk's geometry groups as ONE grouped launch behind it; " % len(a9_chunks) if a9_chunks else "geometry all-reduce behind A9; ")
-                             + "SH rows rebuilt on the compute stream when the gather has landed, under the geometry all-reduce") if factorised else "one all-reduce of the flat gradient buffer",
-        }
     if rank == 0:
         st = rast1.state
         V = int((torch.from_numpy(rast1._d2h(st.radii, (n,), np.int32)) > 0).sum())
@@ -714,7 +804,6 @@ def main():
         tiles = st.tiles_x * st.tiles_y
         ab, p = algorithmic_bytes(n, V, T, Ppix, tiles, deg, bool(args.absgrad))
         total_bytes = sum(ab.values())
-        ms_per_step = elapsed / args.steps * 1e3
         try:
             pr = torch.cuda.get_device_properties(dev)
             device_info = {"name": pr.name, "gcn_arch": getattr(pr, "gcnArchName", None), "compute_units": pr.multi_processor_count,
@@ -722,15 +811,6 @@ def main():
                            "memory_gb": round(pr.total_memory / 2 ** 30, 1), "host_cores": os.cpu_count()}
         except Exception:      # noqa: BLE001
             device_info = None
-        step_ms = sorted(marks[i_].elapsed_time(marks[i_ + 1]) for i_ in range(args.steps))
-        step_spread = [step_ms[int(q * (len(step_ms) - 1))] for q in (0.1, 0.5, 0.9)] if step_ms else None
-        value = GLOBAL_VIEWS * args.steps / elapsed
-        comm_ms = None
-        if comm_marks:
-            cm = sorted(a_.elapsed_time(b_) for a_, b_ in comm_marks)
-            comm_ms = {"mean": float(np.mean(cm)), "p50": cm[len(cm) // 2], "p90": cm[int(0.9 * (len(cm) - 1))],
-                       "note": "rank 0, main stream: from 'last view's backward done' to 'exchange complete' (the gathers of earlier views "
-                               "run under compute and are not in this figure)"}
         # dominant kernel = the longest single-kernel stage
         single = {k: stage_ms[k] for k in ("render_bwd", "render_fwd", "preprocess_fwd", "preprocess_bwd", "duplicate") if k in stage_ms}
         roofline = None
@@ -908,25 +988,11 @@ def main():
             if k in stage_table:
                 stage_table[k]["algorithmic_bytes"] = ab[k]
         raster_ms = sum(v for k, v in stage_ms.items()) if stage_ms else None
-        rec = {
-            "metric": "train views/sec (fwd+bwd raster) at 1M splats 1920x1080" if args.workload == "C3" else f"train views/sec (fwd+bwd raster), workload {args.workload}",
-            "value": value, "unit": "views/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak" if weak else "strong", "vs_baseline": None,
-            "other_grad_mode": other_mode,
-            "strict_single_view": strict, "t_raster_ms_per_step": (ms_per_step - comm_ms["mean"]) if comm_ms else ms_per_step,
-            "t_comm_exposed_ms_per_step": comm_ms, "comm_microbench": comm_micro, "clocks": clocks,
-            "exchange": exchange_info, "rccl_nranks": exchange_info["rccl_nranks"] if exchange_info else None,
+        rec = dict(headline, config=dict(headline["config"], N=n, V=V, T=T, P=Ppix, tiles=tiles, sort_passes_p=p))
+        rec.update({
+            "other_grad_mode": other_mode, "strict_single_view": strict, "comm_microbench": comm_micro, "clocks": clocks,
             "per_rank_compute_ms": per_rank_compute_ms, "scaling_model": scaling_model(n, world, VPS, per_rank_compute_ms, ms_per_step),
-            "step_ms_p10_p50_p90": step_spread,
             "device": device_info,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.workload}: {n} splats, {W}x{H}, SH degree {deg}, {GLOBAL_VIEWS} views per iteration "
-                                   + ("(weak scaling: fixed per GPU), " if weak else f"sharded over {world} GPU(s) (BASELINE config C4), ") + f"{VPS} view(s) per GPU per step"
-                                   + (f" as {K} multi-view pass(es) of {G} view(s) (dvs_raster_forward_views / dvs_raster_backward_*)"
-                                      + (" software-pipelined over two contexts/streams, gradients accumulated" if K > 1 else ""))
-                                   + ((", RCCL exchange of the gradient rows: " + exchange) if world > 1 else ""),
-                       "views_per_step": world * VPS, "views_per_gpu_per_step": VPS, "ms_per_view": ms_per_step / VPS, "absgrad": bool(args.absgrad), "mode": args.mode, "stagger": bool(args.stagger), "groups": K, "views_per_group": G, "early_gather": bool(early), "a9_chunks": len(a9_chunks) if a9_chunks else 1, "async_forward": bool(args.async_forward), "hip_graph": bool(args.graph), "bwd_variant": args.bwd_variant, "fwd_variant": args.fwd_variant, "grad_mode": args.grad_mode, "tile_bounds": "tight (opt-in)" if args.tight_tiles else "canonical", "shN_layout": "tiled[N/64][45][64]" if tiled else "rows[N][45]",
-                       "N": n, "V": V, "T": T, "P": Ppix, "tiles": tiles, "sort_passes_p": p},
             "grad_l2_after_exchange": grad_norms,
             "roofline": roofline,
             "pipeline": {"algorithmic_bytes_per_view": total_bytes,
@@ -939,7 +1005,7 @@ def main():
                          "frac_of_hbm_peak_by_counters": (counter_bytes_step / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBPS)
                                                          if (roofline is not None and counter_bytes_step) else None,
                          "sum_of_stage_ms": raster_ms, "stages": stage_table},
-        }
+        })
         # compute-side figure of SURVEY.md §8(d): pixel-splat interactions I = sum over tiles of (list entries walked before all 256
         # pixels of the tile terminate) x 256, from the saved n_contrib of the last profiled view
         try:
@@ -994,15 +1060,7 @@ def main():
                     rec["parity_vs_oracle"] = {"error": repr(e)}
         print(json.dumps(rec), flush=True)
     rast1.close()
-    for r_ in rasts:
-        r_.close()
-    barrier()
-    if dist is not None:
-        dist.destroy_process_group()
-    if comm is not None:
-        comm.close()
-    if watchdog is not None:
-        watchdog.cancel()
+    finish()
 
 
 if __name__ == "__main__":

@@ -16,7 +16,7 @@ def _run(exchange, port, vps=1, impl="torch", extra=()):
     include/dvs_comm.h (RCCL needs one device per rank)"""
     env = dict(os.environ, DVS_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", DVS_COMM_BACKEND="tcp")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
            "--workload", "C2", "--no-cpu-baseline", "--profile-iters", "0", "--exchange", exchange, "--views-per-step", str(vps),
            "--exchange-impl", impl] + list(extra)
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
@@ -26,14 +26,14 @@ def _run(exchange, port, vps=1, impl="torch", extra=()):
 
 
 def test_bench_self_launch_two_ranks(gpu_device):
-    """`python bench.py --gpus 2 --steps 3` exactly as the driver types it (no launcher around it): bench.py starts its two ranks itself
+    """`python bench.py --gpus 2 --steps 3 --full` as the driver types it (no launcher around it): bench.py starts its two ranks itself
     under torch.distributed.run and exchanges through the product's layer (include/dvs_comm.h); here the two ranks share the one GPU of
     the test box, so the communicator is the test-only TCP backend (on a node with two GPUs the same command runs RCCL). Rank 0 prints the
     one JSON line of BASELINE config C4 (8 views per iteration, 4 per rank, strong scaling), which says who ran the collectives."""
     env = dict(os.environ, DVS_COMM_BACKEND="tcp")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"], capture_output=True,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], capture_output=True,
                        text=True, timeout=900, env=env, cwd=ROOT)
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -83,7 +83,7 @@ def test_pipelined_views_accumulate_like_sequential(gpu_device):
     """N=1: a step of 4 pipelined views leaves the same accumulated gradient as 4 sequential single-view steps would."""
     import subprocess as sp
     def run(vps):
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--workload", "C2", "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--full", "--workload", "C2", "--no-cpu-baseline",
                "--profile-iters", "0", "--views-per-step", str(vps)]
         p = sp.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
         assert p.returncode == 0, p.stderr[-2000:]
@@ -106,7 +106,7 @@ def test_bench_step_over_rccl_one_rank(gpu_device):
             env["DVS_FORCE_COLLECTIVES"] = "1"
         else:
             env.pop("DVS_FORCE_COLLECTIVES", None)
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--workload", "C2", "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--workload", "C2", "--no-cpu-baseline",
                "--profile-iters", "0", "--global-views", "2", "--exchange", exchange, "--exchange-impl", impl]
         env.pop("DVS_COMM_BACKEND", None)                                  # RCCL itself
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)

@@ -5,6 +5,8 @@ mkdir -p gpurun_out
 export TMPDIR=/tmp
 timeout 1200 python -m pytest tests -m gpu -x -q > gpurun_out/pytest_gpu.log 2>&1; echo "pytest rc=$?"; tail -4 gpurun_out/pytest_gpu.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
+# the summary below reads the side measurements (roofline, strict single view, parity): those come with --full
+BENCH_ARGS="--full ${BENCH_ARGS:---steps 50 --warmup 10}"
 timeout 600 python bench.py ${BENCH_ARGS:---steps 50 --warmup 10} > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err; echo "bench rc=$?"
 python - <<'PY'
 import json
