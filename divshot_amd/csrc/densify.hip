@@ -96,8 +96,9 @@ __device__ __forceinline__ int d_action(int i, const float* opacity, const float
     if (!(avg >= p.grad_threshold)) return DVS_DENSIFY_KEEP;
     return smax > p.scale_threshold ? DVS_DENSIFY_SPLIT : DVS_DENSIFY_CLONE;
 }
-__device__ __forceinline__ uint32_t d_count(int a) { return a == DVS_DENSIFY_PRUNE ? 0u : (a == DVS_DENSIFY_KEEP ? 1u : 2u); }
+__device__ __forceinline__ bool d_grows(int a) { return a == DVS_DENSIFY_CLONE || a == DVS_DENSIFY_SPLIT; }
 
+// per block: (surviving splats) | (growth candidates << 16), both <= DB
 __global__ void __launch_bounds__(DB)
 k_densify_blocksum(int n, const float* __restrict__ opacity, const float* __restrict__ scale, const float* __restrict__ grad_accum,
                    const float* __restrict__ denom, const int* __restrict__ max_radii, dvs_densify_params p, uint8_t* __restrict__ action,
@@ -107,34 +108,62 @@ k_densify_blocksum(int n, const float* __restrict__ opacity, const float* __rest
     int a = DVS_DENSIFY_PRUNE;
     if (i < n) { a = d_action(i, opacity, scale, grad_accum, denom, max_radii, p); action[i] = (uint8_t)a; }
     uint32_t tot;
-    (void)d_block_excl_scan(i < n ? d_count(a) : 0u, tmp, &tot);
+    (void)d_block_excl_scan((a != DVS_DENSIFY_PRUNE ? 1u : 0u) | (d_grows(a) ? 1u << 16 : 0u), tmp, &tot);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
 }
-// single workgroup: exclusive scan of the block sums; growth beyond cap_max is cut by demoting CLONE/SPLIT to KEEP later (k_offsets)
+// single workgroup over the nb packed block sums, DB blocks per chunk with a running carry. Pass 1: totals S (survivors) and G (growth
+// candidates); the growth budget is G, or min(G, cap_max - S) (>= 0) when cap_max > 0, and the new count is S + budget. Pass 2: block
+// offsets = survivors before the block + accepted growth before it, where growth is accepted in splat order until the budget is spent.
+// The one block in which the budget runs out ("cut" block) and what is left of the budget there (< its candidates, so < DB) go to the
+// word after the block offsets: block_sums[nb] = cut << 8 | left (cut = nb: every candidate is accepted).
 __global__ void __launch_bounds__(DB)
-k_densify_scan_blocks(uint32_t* __restrict__ block_sums, uint32_t nb, uint64_t* __restrict__ total) {
+k_densify_scan_blocks(uint32_t* __restrict__ block_sums, uint32_t nb, int cap_max, uint64_t* __restrict__ total) {
     __shared__ uint32_t tmp[DB / 64 + 1];
-    uint64_t carry = 0;
+    __shared__ uint32_t cut_word;
+    uint64_t S = 0, G = 0;
     for (uint32_t base = 0; base < nb; base += DB) {
         const uint32_t idx = base + threadIdx.x;
         const uint32_t v = idx < nb ? block_sums[idx] : 0u;
-        uint32_t tot;
-        const uint32_t ex = d_block_excl_scan(v, tmp, &tot);
-        if (idx < nb) block_sums[idx] = (uint32_t)(carry + ex);
-        carry += tot;
+        uint32_t ts, tg;
+        (void)d_block_excl_scan(v & 0xffffu, tmp, &ts);
+        (void)d_block_excl_scan(v >> 16, tmp, &tg);
+        S += ts; G += tg;
     }
-    if (threadIdx.x == 0) *total = carry;
+    const uint64_t budget = cap_max > 0 ? ((uint64_t)cap_max > S ? min(G, (uint64_t)cap_max - S) : 0ull) : G;
+    if (threadIdx.x == 0) cut_word = nb << 8;
+    __syncthreads();
+    uint64_t cs = 0, cg = 0;
+    for (uint32_t base = 0; base < nb; base += DB) {
+        const uint32_t idx = base + threadIdx.x;
+        const uint32_t v = idx < nb ? block_sums[idx] : 0u;
+        uint32_t ts, tg;
+        const uint64_t es = cs + d_block_excl_scan(v & 0xffffu, tmp, &ts);
+        const uint64_t eg = cg + d_block_excl_scan(v >> 16, tmp, &tg);
+        if (idx < nb) {
+            block_sums[idx] = (uint32_t)(es + min(eg, budget));
+            if (eg <= budget && budget < eg + (v >> 16)) cut_word = idx << 8 | (uint32_t)(budget - eg);     // (one block at most)
+        }
+        cs += ts; cg += tg;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        *total = S + budget;
+        if (nb) block_sums[nb] = cut_word;
+    }
 }
+// growth candidates past the budget are demoted to KEEP (action rewritten); offsets = exclusive scan of the final output counts
 __global__ void __launch_bounds__(DB)
-k_densify_offsets(int n, uint8_t* __restrict__ action, const uint32_t* __restrict__ block_offsets, uint32_t* __restrict__ offsets,
-                  int cap_max, uint64_t* __restrict__ total) {
+k_densify_offsets(int n, uint8_t* __restrict__ action, const uint32_t* __restrict__ block_offsets, uint32_t* __restrict__ offsets) {
     __shared__ uint32_t tmp[DB / 64 + 1];
     const int i = blockIdx.x * DB + threadIdx.x;
-    const int a = i < n ? action[i] : DVS_DENSIFY_PRUNE;
+    int a = i < n ? action[i] : DVS_DENSIFY_PRUNE;
+    const uint32_t cut = block_offsets[gridDim.x];
+    const uint32_t quota = blockIdx.x < (cut >> 8) ? (uint32_t)DB : (blockIdx.x == (cut >> 8) ? (cut & 0xffu) : 0u);
     uint32_t tot;
-    const uint32_t off = d_block_excl_scan(i < n ? d_count(a) : 0u, tmp, &tot) + block_offsets[blockIdx.x];
-    if (i < n) offsets[i] = off;
-    (void)cap_max; (void)total;
+    const uint32_t ex = d_block_excl_scan((a != DVS_DENSIFY_PRUNE ? 1u : 0u) | (d_grows(a) ? 1u << 16 : 0u), tmp, &tot);
+    const uint32_t rank = ex >> 16;                                  // growth candidates before i in this block
+    if (d_grows(a) && rank >= quota) { a = DVS_DENSIFY_KEEP; action[i] = (uint8_t)a; }
+    if (i < n) offsets[i] = block_offsets[blockIdx.x] + (ex & 0xffffu) + min(rank, quota);
 }
 
 // mode 0: parameters; mode 1: optimizer moments
@@ -235,8 +264,8 @@ int dvs_densify_plan(void* stream, int n, const float* opacity, const float* sca
     hipStream_t st = (hipStream_t)stream;
     const uint32_t nb = (uint32_t)((n + DB - 1) / DB);
     if (nb) hipLaunchKernelGGL(k_densify_blocksum, dim3(nb), dim3(DB), 0, st, n, opacity, scale, grad_accum, denom, max_radii, *prm, action, scratch);
-    hipLaunchKernelGGL(k_densify_scan_blocks, dim3(1), dim3(DB), 0, st, scratch, nb, new_count);
-    if (nb) hipLaunchKernelGGL(k_densify_offsets, dim3(nb), dim3(DB), 0, st, n, action, scratch, offsets, prm->cap_max, new_count);
+    hipLaunchKernelGGL(k_densify_scan_blocks, dim3(1), dim3(DB), 0, st, scratch, nb, prm->cap_max, new_count);
+    if (nb) hipLaunchKernelGGL(k_densify_offsets, dim3(nb), dim3(DB), 0, st, n, action, scratch, offsets);
     return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
 }
 int dvs_densify_apply(void* stream, int n, const uint8_t* action, const uint32_t* offsets, const dvs_densify_params* prm, int mode,

@@ -425,7 +425,7 @@ void GaussianTrainerScene::Impl::densify(int it) {
     prm.max_world_scale = after_reset ? cfg.pruneScale3d * extent : 0.f;                     // `pruneScale3d` (fraction of the scene extent)
     prm.max_screen_radius = after_reset && it < cfg.refineScale2dStopIter                    // `pruneScale2d` (fraction of the image size)
                                 ? std::max(1, (int)(cfg.pruneScale2d * (float)std::max(W, H))) : 0;
-    prm.cap_max = cap; prm.seed = (uint32_t)it; prm.shn_layout = DVS_SHN_TILED;
+    prm.cap_max = 0; prm.seed = (uint32_t)it; prm.shn_layout = DVS_SHN_TILED;  // no kernel cap: over capMax, the loop below re-plans prune-only
     prm.revised_opacity = (cfg.revisedOpacity || cfg.densifyStrategy == 2) ? 1 : 0;      // ADC+ always uses the revised opacity of the copies
     uint64_t new_n = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -471,7 +471,7 @@ void GaussianTrainerScene::Impl::prune_light(int it) {
     prm.min_opacity = std::max(cfg.pruneOpacity, cfg.min_opacity);       // --minOpacity is the only opacity threshold the CLI exposes
     prm.max_world_scale = cfg.pruneScale3d * extent;
     prm.max_screen_radius = 0;
-    prm.cap_max = cap; prm.seed = (uint32_t)it; prm.shn_layout = DVS_SHN_TILED; prm.revised_opacity = 0;
+    prm.cap_max = 0; prm.seed = (uint32_t)it; prm.shn_layout = DVS_SHN_TILED; prm.revised_opacity = 0;   // (no growth: nothing to cap)
     HIP_OR_THROW(hipMemsetAsync(d_grad_accum, 0, (size_t)cap * 4, stream));
     HIP_OR_THROW(hipMemsetAsync(d_denom, 0, (size_t)cap * 4, stream));
     HIP_OR_THROW(hipMemsetAsync(d_max_radii, 0, (size_t)cap * 4, stream));

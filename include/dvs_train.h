@@ -83,7 +83,12 @@ int dvs_adam_step_groups(void* stream, const dvs_adam_group* groups, int n_group
  *                          above the limits;  SPLIT  avg >= grad_threshold and max exp(scale) > scale_threshold (replaced by 2
  *                          samples, scale / 1.6);  CLONE  avg >= grad_threshold otherwise (kept + 1 copy);  KEEP.
  *                          Writes action[n], the exclusive scan of the output counts offsets[n] and the new count (device + pinned host
- *                          copy is the caller's business). Growth is cut off deterministically (by splat index) at cap_max.
+ *                          copy is the caller's business). Growth is cut off deterministically (by splat index) at cap_max:
+ *                          with S surviving (non-PRUNE) splats, only the first max(0, cap_max - S) CLONE / SPLIT candidates in
+ *                          splat order keep their action, the others are demoted to KEEP in action[], and
+ *                          new_count = min(uncapped count, max(cap_max, S)). PRUNE is never changed by the cap. When S alone exceeds
+ *                          cap_max, new_count = S (> cap_max): what to do then (prune harder, or grow the arrays) is the caller's
+ *                          decision. cap_max <= 0 = no cap.
  *   dvs_densify_apply      scatters ONE attribute set old -> new at the planned offsets. mode 0 = parameters (split samples drawn
  *                          from the splat's own Gaussian with a counter-based hash RNG), mode 1 = optimizer moments (kept rows copied,
  *                          rows of new splats zero). shN arrays may be in either layout (shn_layout).
@@ -95,7 +100,7 @@ typedef struct dvs_densify_params {
     float min_opacity;         /* prune below (activated opacity) */
     float max_world_scale;     /* prune if max exp(scale) exceeds it; 0 = off */
     int32_t max_screen_radius; /* prune if max_radii exceeds it; 0 = off */
-    int32_t cap_max;           /* hard cap on the new count */
+    int32_t cap_max;           /* cap on the new count (growth only, see dvs_densify_plan); <= 0 = no cap */
     uint32_t seed;             /* RNG stream for split samples (use the step number) */
     int32_t shn_layout;        /* DVS_SHN_ROWS / DVS_SHN_TILED for the shN arrays passed to dvs_densify_apply */
     int32_t revised_opacity;   /* config `revisedOpacity`: both results of a clone / split take opacity 1 - sqrt(1 - o), so that

@@ -2,22 +2,9 @@
 restatement (and, for SSIM, fp64 finite differences of that restatement)."""
 import numpy as np
 import pytest
+from util import gauss_window, conv_same, relocation_np as _relocation_np  # noqa: F401  (shared with test_gpu_train_ops_scale.py)
 
 pytestmark = pytest.mark.gpu
-
-
-def gauss_window():
-    x = np.arange(11) - 5.0
-    g = np.exp(-x * x / (2 * 1.5 ** 2))
-    return g / g.sum()
-
-
-def conv_same(img, g):
-    """separable 11-tap convolution with zero padding, img [H,W] float64"""
-    H, W = img.shape
-    p = np.pad(img, 5)
-    t = sum(g[k] * p[:, k:k + W] for k in range(11))
-    return sum(g[k] * t[k:k + H, :] for k in range(11))
 
 
 def ssim_np(x, y):
@@ -267,14 +254,6 @@ def test_densify_plan_and_apply(gpu_device, tiled):
     torch.cuda.synchronize()
     np.testing.assert_allclose(op_d.cpu().numpy(), np.minimum(A["opacity"], np.log(0.01 / 0.99)), rtol=1e-6)
     assert not m.any() and not v.any()
-
-
-def _relocation_np(o, ratio, min_opacity):
-    """numpy restatement of the MCMC relocation rule (opacity / scale of the c+1 copies of a splat drawn c times)."""
-    from math import comb, sqrt
-    no = 1.0 - (1.0 - o) ** (1.0 / ratio)
-    denom = sum(comb(i - 1, k) * (-1) ** k * no ** (k + 1) / sqrt(k + 1) for i in range(1, ratio + 1) for k in range(i))
-    return min(max(no, min_opacity), 1.0 - 1.1920929e-7), o / denom
 
 
 @pytest.mark.parametrize("tiled", [False, True])
