@@ -34,6 +34,9 @@
 namespace {
 const int kWidth[6] = {3, 3, 45, 1, 3, 4};          // pos sh0 shN opacity scale rot
 enum { P_POS = 0, P_SH0, P_SHN, P_OPA, P_SCALE, P_ROT };
+const int kAllGroups[6] = {P_POS, P_SH0, P_SHN, P_OPA, P_SCALE, P_ROT};
+const int kGeomGroups[4] = {P_POS, P_OPA, P_SCALE, P_ROT};                // what the factorised exchange all-reduces
+constexpr float kAdamBeta1 = 0.9f, kAdamBeta2 = 0.999f, kAdamEps = 1e-15f;
 
 void logf_(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
 void logf_(const char* fmt, ...) {
@@ -117,7 +120,6 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     int vpi = 1;                                                             // views per trainStep and GPU, one multi-view pass (cfg.viewsPerIter / DVS_VIEWS_PER_ITER)
     bool sequential_views = false;                                           // DVS_VIEWS_MODE=sequential: the same views one pass at a time, accumulating (the reference shape)
     int* d_vis_radius = nullptr;                                             // visibleAdam with vpi > 1: max radius over the step's views
-    int loss_views = 1;                                                      // views whose loss sums d_loss holds
     std::vector<dvs_camera> cams;
     std::vector<float*> d_targets;
     float* d_out = nullptr; float* d_dL = nullptr; float* d_loss = nullptr;     // d_loss[0..63] = (1-w) L1 partial sums, d_loss[64..127] = SSIM partial sums
@@ -206,6 +208,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         HIP_OR_THROW(hipMemsetAsync(d_denom, 0, (size_t)cap * 4, stream));
         HIP_OR_THROW(hipMemsetAsync(d_max_radii, 0, (size_t)cap * 4, stream));
     }
+    void apply_plan(const dvs_densify_params& prm, int new_n, bool zero_moments);
     void densify(int it);
     void densify_mcmc(int it);
     void prune_light(int it);
@@ -213,6 +216,48 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     void sync_stats();
     const float* target_for(int ci);
     bool mcmc() const { return cfg.densifyStrategy == 1; }
+    bool exchange_factorised() const { return comm && factorised; }
+    bool visible_adam() const { return cfg.visibleAdam && world == 1; }     // per-rank visibility would let the replicas drift apart
+    int sh_degree_at(int s) const { return cfg.progressiveTrain ? std::min(sh_max, s / 1000) : sh_max; }   // SH bands unlocked every 1000 steps
+    void setup_exchange();
+    // cameras: one xorshift stream shared by all ranks; an iteration draws world x vpi views and rank r renders views r vpi .. r vpi + vpi - 1
+    // (vpi = 1: one view per GPU and iteration, as the reference's trainStep renders one camera; vpi = 8 on one GPU: BASELINE config C4)
+    void draw_cameras(std::vector<int>& ci) {
+        ci.assign((size_t)world * vpi, 0);                  // every rank knows every rank's cameras: the SH rows are rebuilt from them
+        for (int& c : ci) {
+            cam_rng ^= cam_rng << 13; cam_rng ^= cam_rng >> 7; cam_rng ^= cam_rng << 17;
+            c = cfg.singleCamera ? 0 : (int)(cam_rng % cams.size());
+        }
+    }
+    std::vector<dvs_camera> rank_cameras(const std::vector<int>& ci_all) const {     // this rank's views of an iteration's draw
+        std::vector<dvs_camera> v((size_t)vpi);
+        for (int k = 0; k < vpi; ++k) v[(size_t)k] = cams[(size_t)ci_all[(size_t)rank * vpi + k]];
+        return v;
+    }
+    const int* any_view_radii() {                            // max radius over the step's views (view-major fwd.radii of the multi-view pass)
+        if (!d_vis_radius) HIP_OR_THROW(hipMalloc((void**)&d_vis_radius, (size_t)cap * sizeof(int) + 16));
+        DVS_OR_THROW(dvs_any_view_radius(stream, n, vpi, fwd.radii, d_vis_radius));
+        return d_vis_radius;
+    }
+    // ---- the phases of one trainStep ----
+    struct Step {                                                            // one iteration, carried through its phases
+        int it = 0, deg = 0;                                                 // the iteration being computed, its SH degree
+        std::vector<int> ci_all;                                             // the iteration's cameras, [rank][local view]
+        std::vector<dvs_camera> vcams;                                       // this rank's views
+        dvs_opts opts{};
+        bool mcmc = false, absgrad = false, want_stats = false;
+        bool refine_now = false, reset_now = false, prune_now = false;
+        float lr_pos = 0.f;
+        dvs_adam_group adam[6] = {};                                         // Adam groups over the whole arrays
+        const int* adam_gate = nullptr;                                      // (render_backward) visible-only Adam: radius > 0 in the step's views
+        int chunk_per = 0, n_chunks = 0;                                     // (render_backward) > 0: the geometry gradients left behind A9 in chunks
+    };
+    Step plan_step();                                                        // decides the step; launches nothing
+    void loss_of_view(const Step& s, int v);
+    void render_backward(Step& s);
+    void exchange(const Step& s, bool pipelined);
+    void finish_range(const Step& s, int first, int count, const int* groups, int n_groups, const int* gate);
+    void finish_pipelined(const Step& s);
     dvs_splats splats() const {
         dvs_splats s{};
         s.pos = d_param[P_POS]; s.sh0 = d_param[P_SH0]; s.shN = d_param[P_SHN]; s.opacity = d_param[P_OPA];
@@ -394,7 +439,41 @@ bool GaussianTrainerScene::Impl::load_synthetic(const std::string& spec_str) {
     for (int g = 0; g < 6; ++g) { upload(g, init[g]); init_host[g] = init[g]; }
     report_config();
     if (cfg.verbose) logf_("synthetic scene: %d splats, %d cameras @ %dx%d, SH degree %d%s", spec.n, spec.n_cams, W, H, sh_max, resumed ? " (resumed)" : "");
+    if (exchange_factorised()) setup_exchange();
     return true;
+}
+
+// factorised exchange: the SH rows are not written by the backward, only each view's colour gradient, which leaves right after
+// the composite backward (dvs_raster_backward_dcolor) so that its all-gather runs on the communication stream while A9 computes
+void GaussianTrainerScene::Impl::setup_exchange() {
+    HIP_OR_THROW(hipMalloc((void**)&d_dcolor_local, (size_t)vpi * cap * 3 * sizeof(float) + 16));
+    HIP_OR_THROW(hipMalloc((void**)&d_dcolor_scratch, (size_t)vpi * cap * 3 * sizeof(float) + 16));
+    HIP_OR_THROW(hipMalloc((void**)&d_dcolor_all, (size_t)world * vpi * cap * 3 * sizeof(float) + 16));
+    HIP_OR_THROW(hipStreamCreateWithFlags(&comm_stream, hipStreamNonBlocking));
+    for (hipEvent_t* e : {&ev_dcolor, &ev_bwd, &ev_comm, &ev_gather}) HIP_OR_THROW(hipEventCreateWithFlags(e, hipEventDisableTiming));
+    if (const char* e = getenv("DVS_A9_CHUNKS")) a9_chunks = std::max(1, std::min(64, atoi(e)));
+    if (const char* e = getenv("DVS_EXCHANGE_PIPELINE")) pipeline = e[0] == '1' && a9_chunks > 1;
+    ev_chunk.resize((size_t)a9_chunks); ev_ar.resize((size_t)a9_chunks);
+    for (hipEvent_t& e : ev_chunk) HIP_OR_THROW(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    for (hipEvent_t& e : ev_ar) HIP_OR_THROW(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    if (rank == 0 && a9_chunks > 1)
+        logf_("gradient exchange: A9 in %d splat chunks, each chunk's geometry all-reduce behind it%s", a9_chunks,
+              pipeline ? "; PIPELINED across the iteration boundary: Adam and the next iteration's projection run chunk by chunk as the all-reduces land "
+                         "(DVS_EXCHANGE_PIPELINE=1)" : "");
+}
+
+// applies the plan to the parameter, m and v sets (old -> new) and swaps the sets. The SH tile pads of every new set are zeroed
+// first; with zero_moments (densify) the whole new m and v groups are
+void GaussianTrainerScene::Impl::apply_plan(const dvs_densify_params& prm, int new_n, bool zero_moments) {
+    for (int set = 0; set < 3; ++set) {
+        float** src = set == 0 ? d_param : (set == 1 ? d_m : d_v);
+        float** dst = set == 0 ? d_param2 : (set == 1 ? d_m2 : d_v2);
+        const float* s6[6] = {src[0], src[1], src[2], src[3], src[4], src[5]};
+        for (int g = 0; g < 6; ++g)
+            if (g == P_SHN || (set > 0 && zero_moments)) HIP_OR_THROW(hipMemsetAsync(dst[g], 0, dev_floats_for(g, new_n) * sizeof(float), stream));
+        DVS_OR_THROW(dvs_densify_apply(stream, n, d_action, d_offsets, &prm, set == 0 ? 0 : 1, s6, dst, new_n));
+        for (int g = 0; g < 6; ++g) std::swap(src[g], dst[g]);
+    }
 }
 
 // densifyStrategy 1 (MCMC): dead splats are relocated onto live ones drawn ~ opacity, then the model grows by 5 % up to the cap.
@@ -437,16 +516,7 @@ void GaussianTrainerScene::Impl::densify(int it) {
         prm.grad_threshold = 3.0e38f;                            // at the cap: prune only, no growth this round
     }
     if (new_n == 0 || new_n > (uint64_t)cap) { reset_stats(); return; }
-    for (int set = 0; set < 3; ++set) {
-        float** src = set == 0 ? d_param : (set == 1 ? d_m : d_v);
-        float** dst = set == 0 ? d_param2 : (set == 1 ? d_m2 : d_v2);
-        const float* s6[6] = {src[0], src[1], src[2], src[3], src[4], src[5]};
-        if (set > 0)
-            for (int g = 0; g < 6; ++g) HIP_OR_THROW(hipMemsetAsync(dst[g], 0, dev_floats_for(g, (int)new_n) * sizeof(float), stream));
-        else HIP_OR_THROW(hipMemsetAsync(dst[P_SHN], 0, dev_floats_for(P_SHN, (int)new_n) * sizeof(float), stream));   // tile pads
-        DVS_OR_THROW(dvs_densify_apply(stream, n, d_action, d_offsets, &prm, set == 0 ? 0 : 1, s6, dst, (int)new_n));
-        for (int g = 0; g < 6; ++g) std::swap(src[g], dst[g]);
-    }
+    apply_plan(prm, (int)new_n, true);
     if (cfg.verbose) {
         logf_("densify @%d: %d -> %llu splats", it, n, (unsigned long long)new_n);
         uint64_t cap_ = 0, grows_ = 0, lastT_ = 0, over_ = 0;        // the rasterizer's instance arena at this point (HBM pressure of big scenes)
@@ -472,23 +542,14 @@ void GaussianTrainerScene::Impl::prune_light(int it) {
     prm.max_world_scale = cfg.pruneScale3d * extent;
     prm.max_screen_radius = 0;
     prm.cap_max = 0; prm.seed = (uint32_t)it; prm.shn_layout = DVS_SHN_TILED; prm.revised_opacity = 0;   // (no growth: nothing to cap)
-    HIP_OR_THROW(hipMemsetAsync(d_grad_accum, 0, (size_t)cap * 4, stream));
-    HIP_OR_THROW(hipMemsetAsync(d_denom, 0, (size_t)cap * 4, stream));
-    HIP_OR_THROW(hipMemsetAsync(d_max_radii, 0, (size_t)cap * 4, stream));
+    reset_stats();
     uint64_t new_n = 0;
     DVS_OR_THROW(dvs_densify_plan(stream, n, d_param[P_OPA], d_param[P_SCALE], d_grad_accum, d_denom, d_max_radii, &prm, d_action,
                                   d_offsets, d_dscratch, d_newcount));
     HIP_OR_THROW(hipMemcpyAsync(&new_n, d_newcount, 8, hipMemcpyDeviceToHost, stream));
     HIP_OR_THROW(hipStreamSynchronize(stream));
     if (new_n > 0 && new_n < (uint64_t)n) {
-        for (int set = 0; set < 3; ++set) {
-            float** src = set == 0 ? d_param : (set == 1 ? d_m : d_v);
-            float** dst = set == 0 ? d_param2 : (set == 1 ? d_m2 : d_v2);
-            const float* s6[6] = {src[0], src[1], src[2], src[3], src[4], src[5]};
-            HIP_OR_THROW(hipMemsetAsync(dst[P_SHN], 0, dev_floats_for(P_SHN, (int)new_n) * sizeof(float), stream));
-            DVS_OR_THROW(dvs_densify_apply(stream, n, d_action, d_offsets, &prm, set == 0 ? 0 : 1, s6, dst, (int)new_n));
-            for (int g = 0; g < 6; ++g) std::swap(src[g], dst[g]);
-        }
+        apply_plan(prm, (int)new_n, false);
         if (cfg.verbose && rank == 0) logf_("light prune @%d: %d -> %llu splats", it, n, (unsigned long long)new_n);
         n = (int)new_n;
         HIP_OR_THROW(hipMemsetAsync(d_grad_flat, 0, grad_floats * sizeof(float), stream));
@@ -549,285 +610,223 @@ void GaussianTrainerScene::trainSetup() {
     curIteration = impl_->step;
 }
 
+GaussianTrainerScene::Impl::Step GaussianTrainerScene::Impl::plan_step() {
+    Step s;
+    if (next_ci.size() == (size_t)world * vpi) { s.ci_all = next_ci; next_ci.clear(); }   // (drawn by the previous, pipelined step: the same stream)
+    else draw_cameras(s.ci_all);
+    s.vcams = rank_cameras(s.ci_all);
+    s.it = step + 1;
+    s.deg = sh_degree_at(step);
+    s.mcmc = mcmc();
+    s.absgrad = cfg.useAbsGrad || cfg.densifyStrategy == 2;                  // ADC+ always splits on the abs-grad statistic
+    const bool refining = s.it < cfg.refineStopIter;
+    // densification statistics of the step's views (SURVEY.md §8(f) row 1), summed over the ranks in densify(): per view and visible
+    // splat  grad_accum += |abs-grad|, denom += 1, max_radii = max
+    s.want_stats = refining && !s.mcmc;
+    s.refine_now = refining && s.it > cfg.warmupLength && cfg.refineEvery > 0 && s.it % cfg.refineEvery == 0;
+    s.reset_now = refining && !s.mcmc && cfg.resetAlphaEvery > 0 && s.it % cfg.resetAlphaEvery == 0;
+    s.prune_now = !refining && cfg.pruneStrategy > 0 && cfg.pruneInterval > 0 && s.it % cfg.pruneInterval == 0;
+    s.opts.sh_degree = s.deg; s.opts.antialias = cfg.mipAntiliased ? 1 : 0; s.opts.absgrad = s.absgrad ? 1 : 0; s.opts.accumulate = 0;
+    s.opts.shn_layout = DVS_SHN_TILED;
+    s.opts.grad_mode = DVS_GRAD_LINEAGE;        // the backward of the lineage the reference credits (README.md:95)
+    static const bool tight_tiles = [] { const char* e = getenv("DVS_TIGHT_TILES"); return e && e[0] == '1'; }();
+    s.opts.tile_bounds = tight_tiles ? DVS_TILES_TIGHT : DVS_TILES_CANONICAL;   // opt-in: same images and gradients, shorter tile lists (dvs_raster.h)
+    // Adam, per-group learning rates (names gs_train.cpp:52-57; position lr decays exponentially init -> final, scaled by the scene extent)
+    const float t = std::min(1.0f, (float)step / (float)std::max(1, cfg.numIters));
+    s.lr_pos = extent * std::exp((1.f - t) * std::log(cfg.poslrInit) + t * std::log(cfg.poslrFinal));
+    const float lr[6] = {s.lr_pos, cfg.featurelr, cfg.featurelr / 20.f, cfg.opacitylr, cfg.scalinglr, cfg.rotationlr};
+    // one launch per set of groups; shN chunks above the active SH degree have g = m = v = 0 (Adam is the identity there)
+    for (int k = 0; k < 6; ++k)
+        s.adam[k] = dvs_adam_group{d_param[k], d_grad[k], d_m[k], d_v[k], (uint64_t)dev_floats(k), lr[k], kWidth[k],
+                                   k == P_SHN ? DVS_SHN_TILED : DVS_SHN_ROWS, 0};
+    s.adam[P_SHN].active_chunks = s.deg >= 3 ? 0 : (3 * ((s.deg + 1) * (s.deg + 1) - 1) + 3) / 4;
+    if (s.deg == 0) s.adam[P_SHN].count = 0;
+    return s;
+}
+
+// photometric loss (1-w) L1 + w (1 - SSIM), w = --ssim (main.cpp:24-25), of view v: its gradient goes straight into d_dL[v]; the loss
+// sums of the step's views add up in d_loss (getCurrentLoss reports their mean)
+void GaussianTrainerScene::Impl::loss_of_view(const Step& s, int v) {
+    const int ci = s.ci_all[(size_t)rank * vpi + v];
+    const size_t img = 3 * (size_t)W * H;
+    const float* target = target_for(ci);
+    const float* out = d_out + (size_t)v * img;
+    float* dL = d_dL + (size_t)v * img;
+    const float w_ssim = d_ssim_maps[0] ? cfg.ssimWeight : 0.f;
+    if (w_ssim > 0.f) {     // SSIM maps, then the L1 and SSIM gradients in one pass over the image
+        DVS_OR_THROW(dvs_ssim_forward(stream, out, target, W, H, d_ssim_maps[0], d_ssim_maps[1], d_ssim_maps[2], d_loss + DVS_SSIM_SLOTS));
+        DVS_OR_THROW(dvs_loss_l1_ssim_backward(stream, out, target, W, H, d_ssim_maps[0], d_ssim_maps[1], d_ssim_maps[2], w_ssim, dL, d_loss));
+    } else {
+        DVS_OR_THROW(dvs_l1_loss_grad_w(stream, out, target, img, 1.f, dL, d_loss));
+    }
+    if (cfg.useMask && !d_masks.empty()) {
+        const size_t P = (size_t)W * H;
+        hipLaunchKernelGGL(k_mask_mul, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, stream, dL, d_masks[(size_t)ci], P);
+    }
+}
+
+// forward, loss, composite backward, statistics and A9 of the step's views: ONE multi-view pass (parameters read once, one depth sort /
+// scan / (view, tile) sort / composite launch for all V views, the gradient rows written once: their sum over the views), or with
+// DVS_VIEWS_MODE=sequential one pass per view, gradients accumulating (the reference shape, kept as the check of the multi-view pass)
+void GaussianTrainerScene::Impl::render_backward(Step& s) {
+    const bool fact = exchange_factorised(), seq = sequential_views;
+    const int passes = seq ? vpi : 1, views = seq ? 1 : vpi;                 // views per pass
+    const dvs_splats sp = splats();
+    const size_t img = 3 * (size_t)W * H;
+    dvs_opts opts = s.opts;
+    dvs_splat_grads g{};
+    g.pos = d_grad[P_POS]; g.sh0 = d_grad[P_SH0]; g.shN = d_grad[P_SHN]; g.opacity = d_grad[P_OPA];
+    g.scale = d_grad[P_SCALE]; g.rot = d_grad[P_ROT]; g.absgrad2d = s.absgrad ? d_absgrad : nullptr;
+    g.mean2d = (s.want_stats && !s.absgrad) ? d_mean2d : nullptr;          // ADC without abs-grad: the norm of dL/dmean2D is the statistic
+    if (fact) { g.sh0 = nullptr; g.shN = nullptr; }                          // (the SH rows are rebuilt after the exchange)
+    for (int v = 0; v < passes; ++v) {                                      // v: the first view of the pass
+        const dvs_camera* cam = &s.vcams[(size_t)v];
+        opts.accumulate = v > 0 ? 1 : 0;
+        if (seq) {
+            DVS_OR_THROW(dvs_raster_forward(ctx, stream, &sp, cam, &opts, d_out + (size_t)v * img, &fwd, nullptr));
+        } else {
+            DVS_OR_THROW(dvs_raster_forward_views(ctx, stream, &sp, cam, views, &opts, d_out));
+            DVS_OR_THROW(dvs_get_view_state(ctx, 0, &fwd));                   // (view-major arrays: fwd.radii = [V][n])
+        }
+        for (int u = v; u < v + views; ++u) loss_of_view(s, u);
+        DVS_OR_THROW(dvs_raster_backward_composite(ctx, stream, cam, &opts, d_dL + (size_t)v * img));
+        if (fact) {
+            g.dcolor = d_dcolor_scratch + (size_t)v * n * 3;                 // A9's own copy of the colour gradient
+            DVS_OR_THROW(dvs_raster_backward_dcolor(ctx, stream, d_dcolor_local + (size_t)v * n * 3));
+        }
+        if (fact && v == passes - 1) {      // all local views' colour gradients leave in ONE all-gather, under the last pass's A9
+            HIP_OR_THROW(hipEventRecord(ev_dcolor, stream));
+            HIP_OR_THROW(hipStreamWaitEvent(comm_stream, ev_dcolor, 0));
+            DVS_OR_THROW(dvs_comm_all_gather_f32(comm, comm_stream, d_dcolor_local, d_dcolor_all, (size_t)vpi * n * 3));
+        }
+        if (s.want_stats && s.absgrad) {    // per view, from the composite backward's rows (before A9 consumes them): the exact single-view rule
+            const float* rows = nullptr; int rf = 0;
+            DVS_OR_THROW(dvs_get_bwd_intermediates(ctx, &rows, &rf));
+            DVS_OR_THROW(dvs_densify_accumulate_rows(stream, n, views, fwd.radii, rows, W, H, d_grad_accum, d_denom, d_max_radii));
+        }
+        if (fact && !seq && a9_chunks > 1 && n >= 256 * a9_chunks) {
+            // A9 in splat chunks: as soon as chunk k is queued its 44 B/splat of geometry gradients (four ranges of the flat buffer, one
+            // grouped collective) start their all-reduce on the communication stream, under the A9 of the chunks behind it (SURVEY §8(e))
+            HIP_OR_THROW(hipEventRecord(ev_gather, comm_stream));            // (behind the colour all-gather queued above)
+            s.chunk_per = ((n + a9_chunks - 1) / a9_chunks + 255) / 256 * 256;
+            for (int first = 0; first < n; first += s.chunk_per, ++s.n_chunks) {
+                const int count = std::min(s.chunk_per, n - first);
+                const size_t k = (size_t)s.n_chunks;
+                DVS_OR_THROW(dvs_raster_backward_project_chunk(ctx, stream, &sp, cam, &opts, &g, first, count));
+                HIP_OR_THROW(hipEventRecord(ev_chunk[k], stream));
+                HIP_OR_THROW(hipStreamWaitEvent(comm_stream, ev_chunk[k], 0));
+                DVS_OR_THROW(dvs_comm_group_start(comm));
+                DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, comm_stream, d_grad[P_POS] + 3 * (size_t)first, 3 * (size_t)count));
+                DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, comm_stream, d_grad[P_SCALE] + 3 * (size_t)first, 3 * (size_t)count));
+                DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, comm_stream, d_grad[P_ROT] + 4 * (size_t)first, 4 * (size_t)count));
+                DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, comm_stream, d_grad[P_OPA] + (size_t)first, (size_t)count));
+                DVS_OR_THROW(dvs_comm_group_end(comm));
+                HIP_OR_THROW(hipEventRecord(ev_ar[k], comm_stream));
+            }
+        } else {
+            DVS_OR_THROW(dvs_raster_backward_project(ctx, stream, &sp, cam, &opts, &g));
+        }
+        if (s.want_stats && !s.absgrad) {
+            // the standard rule: |dL/dmean2D| of the view, threshold growGrad2d (0.0002). The multi-view pass hands out the SUM over the
+            // views of dL/dmean2D: its norm is accumulated once per step for splats visible in at least one view (for V = 1 the reference
+            // rule; documented difference for V > 1)
+            if (v > 0) throw std::runtime_error("gstrain: DVS_VIEWS_MODE=sequential with useAbsGrad off needs per-view mean2d rows (use the multi-view pass)");
+            const int* radii = seq ? fwd.radii : any_view_radii();
+            hipLaunchKernelGGL(k_norm2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_mean2d, d_mean2d, n);
+            DVS_OR_THROW(dvs_densify_accumulate(stream, n, radii, d_mean2d, W, H, d_grad_accum, d_denom, d_max_radii));
+        }
+    }
+    if (visible_adam()) s.adam_gate = seq || vpi == 1 ? fwd.radii : any_view_radii();   // (sequential: the last view's — a single-view notion there)
+}
+
+// data parallel, over RCCL / xGMI: all-gather of the views' colour gradients + all-reduce of the geometry groups, then every
+// replica rebuilds the summed SH rows from all views (factorised) — or ONE sum-all-reduce of all six groups (they share a buffer)
+void GaussianTrainerScene::Impl::exchange(const Step& s, bool pipelined) {
+    if (!comm) return;
+    if (!factorised) { DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, stream, d_grad_flat, grad_floats)); return; }
+    if (s.n_chunks == 0) {          // (all collectives on the communication stream, in the same order on every rank)
+        HIP_OR_THROW(hipEventRecord(ev_gather, comm_stream));                // (behind the colour all-gather)
+        HIP_OR_THROW(hipEventRecord(ev_bwd, stream));
+        HIP_OR_THROW(hipStreamWaitEvent(comm_stream, ev_bwd, 0));
+        DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, comm_stream, d_grad_flat, geom_floats));
+    }
+    HIP_OR_THROW(hipEventRecord(ev_comm, comm_stream));
+    // The SH rows need only the colour all-gather: they are rebuilt and their Adam step (sh0 + shN: 192 of the 236 B per splat) runs
+    // WHILE the geometry all-reduce is still on the links; the geometry groups follow when it has landed.
+    HIP_OR_THROW(hipStreamWaitEvent(stream, ev_gather, 0));
+    std::vector<float> campos(s.ci_all.size() * 3);             // slot order of the all-gather: [rank][local view]
+    for (size_t q = 0; q < s.ci_all.size(); ++q) for (int k = 0; k < 3; ++k) campos[q * 3 + k] = cams[(size_t)s.ci_all[q]].campos[k];
+    DVS_OR_THROW(dvs_sh_grad_combine(ctx, stream, n, d_param[P_POS], s.deg, (int)s.ci_all.size(), campos.data(), d_dcolor_all,
+                                     d_grad[P_SH0], d_grad[P_SHN], 0, DVS_SHN_TILED));
+    const dvs_adam_group sh_groups[2] = {s.adam[P_SH0], s.adam[P_SHN]};
+    DVS_OR_THROW(dvs_adam_step_groups(stream, sh_groups, 2, kAdamBeta1, kAdamBeta2, kAdamEps, s.it, s.adam_gate, n));
+    if (!pipelined) HIP_OR_THROW(hipStreamWaitEvent(stream, ev_comm, 0));
+}
+
+// the optimizer tail on the splats [first, first + count): MCMC regularisers, Adam on the given groups, exploration noise. All are
+// element-wise, so a range is bit-identical to the whole-array calls.
+void GaussianTrainerScene::Impl::finish_range(const Step& s, int first, int count, const int* groups, int n_groups, const int* gate) {
+    if (s.mcmc)        // opacity and scale regularisers of the MCMC strategy (0.01 each in the published rule): a function of the replicated
+                       // parameters, added once (after the exchange) on every rank
+        DVS_OR_THROW(dvs_mcmc_regularize_range(stream, n, first, count, d_param[P_OPA], d_param[P_SCALE], d_grad[P_OPA], d_grad[P_SCALE], 0.01f, 0.01f));
+    dvs_adam_group ag[6];
+    for (int k = 0; k < n_groups; ++k) {
+        ag[k] = s.adam[groups[k]];
+        if (ag[k].layout != DVS_SHN_ROWS) continue;                      // (the tiled shN group is only ever stepped whole: first 0, count n)
+        const size_t off = (size_t)ag[k].width * (size_t)first;
+        ag[k].param += off; ag[k].grad += off; ag[k].m += off; ag[k].v += off; ag[k].count = (uint64_t)ag[k].width * (uint64_t)count;
+    }
+    DVS_OR_THROW(dvs_adam_step_groups(stream, ag, n_groups, kAdamBeta1, kAdamBeta2, kAdamEps, s.it, gate ? gate + first : nullptr, count));
+    if (s.mcmc && cfg.noiselr > 0.f)      // exploration noise, scaled by the position learning rate (`noiselr`, gs_train.cpp:97)
+        DVS_OR_THROW(dvs_mcmc_add_noise_range(stream, n, first, count, d_param[P_POS], d_param[P_SCALE], d_param[P_ROT], d_param[P_OPA],
+                                              cfg.noiselr * s.lr_pos, (uint32_t)s.it));
+}
+
+// PIPELINED exchange (round 6; SURVEY 8(e) "Overlap"; DVS_EXCHANGE_PIPELINE=1, off by default until it has run on real links): the
+// geometry gradients left in chunks behind A9. Here every chunk is finished as soon as ITS all-reduce has landed — regulariser,
+// Adam on the four geometry groups, exploration noise, each on the chunk's splat range (all element-wise: bit-identical to the
+// whole-array calls) — and then the NEXT iteration's projection (A2) of that chunk is queued: A2 is per splat, and the chunk's
+// parameters are final (the SH groups were stepped in exchange(), under the all-reduces). Only the last chunk's all-reduce is exposed;
+// the all-reduces of the chunks before it run under the Adam / A2 of their predecessors. Iterations that refine, reset or prune
+// change the parameters after Adam: no early projection there (the next forward projects everything itself).
+void GaussianTrainerScene::Impl::finish_pipelined(const Step& s) {
+    const bool early = !s.refine_now && !s.reset_now && !s.prune_now && s.it < cfg.numIters;
+    if (early) draw_cameras(next_ci);
+    const std::vector<dvs_camera> ncams = early ? rank_cameras(next_ci) : std::vector<dvs_camera>();
+    dvs_opts nopts = s.opts;
+    nopts.sh_degree = sh_degree_at(s.it);                               // (what the next trainStep will compute from step = it)
+    const dvs_splats sp = splats();
+    for (int k = 0; k < s.n_chunks; ++k) {
+        const int first = k * s.chunk_per, count = std::min(s.chunk_per, n - first);
+        HIP_OR_THROW(hipStreamWaitEvent(stream, ev_ar[(size_t)k], 0));
+        finish_range(s, first, count, kGeomGroups, 4, nullptr);        // ungated Adam, unlike the unpipelined tail (s.adam_gate)
+        if (early) DVS_OR_THROW(dvs_raster_forward_views_prepare(ctx, stream, &sp, ncams.data(), vpi, &nopts, first, count));
+    }
+}
+
 void GaussianTrainerScene::trainStep() {
     Impl& m = *impl_;
     if (!m.ctx || m.cams.empty()) throw std::runtime_error("trainStep before loadTrainData");
     HIP_OR_THROW(hipSetDevice(m.device));
-    // cameras: one xorshift stream shared by all ranks; an iteration draws world x vpi views and rank r renders views r vpi .. r vpi + vpi - 1
-    // (vpi = 1: one view per GPU and iteration, as the reference's trainStep renders one camera; vpi = 8 on one GPU: BASELINE config C4)
-    const int V = m.vpi;
-    std::vector<int> ci_all((size_t)m.world * V, 0);                // every rank knows every rank's cameras: the SH rows are rebuilt from them
-    auto draw_cameras = [&](std::vector<int>& ci) {
-        for (size_t k = 0; k < ci.size(); ++k) {
-            m.cam_rng ^= m.cam_rng << 13; m.cam_rng ^= m.cam_rng >> 7; m.cam_rng ^= m.cam_rng << 17;
-            ci[k] = m.cfg.singleCamera ? 0 : (int)(m.cam_rng % m.cams.size());
-        }
-    };
-    if (m.next_ci.size() == ci_all.size()) { ci_all = m.next_ci; m.next_ci.clear(); }      // (drawn by the previous, pipelined step: the same stream)
-    else draw_cameras(ci_all);
-    const int* ci_mine = &ci_all[(size_t)m.rank * V];
-    std::vector<dvs_camera> vcams((size_t)V);
-    for (int v = 0; v < V; ++v) vcams[(size_t)v] = m.cams[(size_t)ci_mine[v]];
-    const int it = m.step + 1;
-    const int deg = m.cfg.progressiveTrain ? std::min(m.sh_max, m.step / 1000) : m.sh_max;   // SH bands unlocked every 1000 steps
-    const bool mcmc = m.mcmc();
-    const bool adc_plus = m.cfg.densifyStrategy == 2;
-    const bool absgrad = m.cfg.useAbsGrad || adc_plus;                                        // ADC+ always splits on the abs-grad statistic
-    const bool refining = it < m.cfg.refineStopIter;
-    dvs_opts opts{};
-    opts.sh_degree = deg; opts.antialias = m.cfg.mipAntiliased ? 1 : 0; opts.absgrad = absgrad ? 1 : 0; opts.accumulate = 0;
-    opts.shn_layout = DVS_SHN_TILED;
-    opts.grad_mode = DVS_GRAD_LINEAGE;          // the backward of the lineage the reference credits (README.md:95)
-    static const bool tight_tiles = [] { const char* e = getenv("DVS_TIGHT_TILES"); return e && e[0] == '1'; }();
-    opts.tile_bounds = tight_tiles ? DVS_TILES_TIGHT : DVS_TILES_CANONICAL;     // opt-in: same images and gradients, shorter tile lists (dvs_raster.h)
-    const dvs_splats sp = m.splats();
-    const size_t img = 3 * (size_t)m.W * m.H;
-    const float w_ssim = m.d_ssim_maps[0] ? m.cfg.ssimWeight : 0.f;
-    // photometric loss (1-w) L1 + w (1 - SSIM), w = --ssim (main.cpp:24-25), of view v: its gradient goes straight into d_dL[v]; the loss
-    // sums of the step's views add up in d_loss (getCurrentLoss reports their mean)
-    auto loss_of_view = [&](int v) {
-        const float* target = m.target_for(ci_mine[v]);
-        const float* out = m.d_out + (size_t)v * img;
-        float* dL = m.d_dL + (size_t)v * img;
-        if (w_ssim > 0.f) {     // SSIM maps, then the L1 and SSIM gradients in one pass over the image
-            DVS_OR_THROW(dvs_ssim_forward(m.stream, out, target, m.W, m.H, m.d_ssim_maps[0], m.d_ssim_maps[1], m.d_ssim_maps[2],
-                                          m.d_loss + DVS_SSIM_SLOTS));
-            DVS_OR_THROW(dvs_loss_l1_ssim_backward(m.stream, out, target, m.W, m.H, m.d_ssim_maps[0], m.d_ssim_maps[1],
-                                                   m.d_ssim_maps[2], w_ssim, dL, m.d_loss));
-        } else {
-            DVS_OR_THROW(dvs_l1_loss_grad_w(m.stream, out, target, img, 1.f, dL, m.d_loss));
-        }
-        if (m.cfg.useMask && !m.d_masks.empty()) {
-            const size_t P = (size_t)m.W * m.H;
-            hipLaunchKernelGGL(k_mask_mul, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, m.stream, dL, m.d_masks[(size_t)ci_mine[v]], P);
-        }
-    };
+    Impl::Step s = m.plan_step();
     HIP_OR_THROW(hipMemsetAsync(m.d_loss, 0, 2 * DVS_SSIM_SLOTS * sizeof(float), m.stream));
-    m.loss_views = V;
-    dvs_splat_grads g{};
-    g.pos = m.d_grad[P_POS]; g.sh0 = m.d_grad[P_SH0]; g.shN = m.d_grad[P_SHN]; g.opacity = m.d_grad[P_OPA];
-    g.scale = m.d_grad[P_SCALE]; g.rot = m.d_grad[P_ROT]; g.absgrad2d = absgrad ? m.d_absgrad : nullptr;
-    g.mean2d = (!absgrad && !mcmc && refining) ? m.d_mean2d : nullptr;      // ADC without abs-grad: the norm of dL/dmean2D is the statistic
-    const bool fact = m.comm && m.factorised;
-    if (fact && !m.d_dcolor_local) {
-        // factorised exchange: the SH rows are not written by the backward, only each view's colour gradient, which leaves right after
-        // the composite backward (dvs_raster_backward_dcolor) so that its all-gather runs on the communication stream while A9 computes
-        HIP_OR_THROW(hipMalloc((void**)&m.d_dcolor_local, (size_t)V * m.cap * 3 * sizeof(float) + 16));
-        HIP_OR_THROW(hipMalloc((void**)&m.d_dcolor_scratch, (size_t)V * m.cap * 3 * sizeof(float) + 16));
-        HIP_OR_THROW(hipMalloc((void**)&m.d_dcolor_all, (size_t)m.world * V * m.cap * 3 * sizeof(float) + 16));
-        HIP_OR_THROW(hipStreamCreateWithFlags(&m.comm_stream, hipStreamNonBlocking));
-        for (hipEvent_t* e : {&m.ev_dcolor, &m.ev_bwd, &m.ev_comm, &m.ev_gather}) HIP_OR_THROW(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        if (const char* e = getenv("DVS_A9_CHUNKS")) m.a9_chunks = std::max(1, std::min(64, atoi(e)));
-        if (const char* e = getenv("DVS_EXCHANGE_PIPELINE")) m.pipeline = e[0] == '1' && m.a9_chunks > 1;
-        m.ev_chunk.resize((size_t)m.a9_chunks); m.ev_ar.resize((size_t)m.a9_chunks);
-        for (hipEvent_t& e : m.ev_chunk) HIP_OR_THROW(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        for (hipEvent_t& e : m.ev_ar) HIP_OR_THROW(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        if (m.rank == 0 && m.a9_chunks > 1)
-            logf_("gradient exchange: A9 in %d splat chunks, each chunk's geometry all-reduce behind it%s", m.a9_chunks,
-                  m.pipeline ? "; PIPELINED across the iteration boundary: Adam and the next iteration's projection run chunk by chunk as the all-reduces land "
-                               "(DVS_EXCHANGE_PIPELINE=1)" : "");
-    }
-    bool geom_reduced = false;                  // the geometry gradients already left chunk by chunk behind A9
-    int chunk_per = 0, n_chunks = 0;            // ... in n_chunks chunks of chunk_per splats (the last one shorter)
-    // densification statistics of the step's views (SURVEY.md §8(f) row 1), summed over the ranks in densify(): per view and visible
-    // splat  grad_accum += |abs-grad|, denom += 1, max_radii = max
-    const bool want_stats = refining && !mcmc;
-    const int* vis_radii = nullptr;                                   // visible-only Adam: radius > 0 in any of the step's views
-    if (m.sequential_views) {
-        // one pass per view, gradients accumulating over the views (DVS_VIEWS_MODE=sequential: the reference shape, kept as the check of the multi-view pass)
-        for (int v = 0; v < V; ++v) {
-            opts.accumulate = v > 0 ? 1 : 0;
-            DVS_OR_THROW(dvs_raster_forward(m.ctx, m.stream, &sp, &vcams[(size_t)v], &opts, m.d_out + (size_t)v * img, &m.fwd, nullptr));
-            loss_of_view(v);
-            const float* dLv = m.d_dL + (size_t)v * img;
-            if (fact) {
-                g.sh0 = nullptr; g.shN = nullptr; g.dcolor = m.d_dcolor_scratch + (size_t)v * m.n * 3;
-                DVS_OR_THROW(dvs_raster_backward_composite(m.ctx, m.stream, &vcams[(size_t)v], &opts, dLv));
-                DVS_OR_THROW(dvs_raster_backward_dcolor(m.ctx, m.stream, m.d_dcolor_local + (size_t)v * m.n * 3));
-            } else {
-                DVS_OR_THROW(dvs_raster_backward_composite(m.ctx, m.stream, &vcams[(size_t)v], &opts, dLv));
-            }
-            if (want_stats && absgrad) {
-                const float* rows = nullptr; int rf = 0;
-                DVS_OR_THROW(dvs_get_bwd_intermediates(m.ctx, &rows, &rf));
-                DVS_OR_THROW(dvs_densify_accumulate_rows(m.stream, m.n, 1, m.fwd.radii, rows, m.W, m.H, m.d_grad_accum, m.d_denom, m.d_max_radii));
-            }
-            if (fact && v == V - 1) {           // all local views' colour gradients leave in ONE all-gather, under the last view's A9
-                HIP_OR_THROW(hipEventRecord(m.ev_dcolor, m.stream));
-                HIP_OR_THROW(hipStreamWaitEvent(m.comm_stream, m.ev_dcolor, 0));
-                DVS_OR_THROW(dvs_comm_all_gather_f32(m.comm, m.comm_stream, m.d_dcolor_local, m.d_dcolor_all, (size_t)V * m.n * 3));
-            }
-            DVS_OR_THROW(dvs_raster_backward_project(m.ctx, m.stream, &sp, &vcams[(size_t)v], &opts, &g));
-            if (want_stats && !absgrad) {       // the standard rule: |dL/dmean2D| of the view, threshold growGrad2d (0.0002)
-                if (v > 0) throw std::runtime_error("gstrain: DVS_VIEWS_MODE=sequential with useAbsGrad off needs per-view mean2d rows (use the multi-view pass)");
-                hipLaunchKernelGGL(k_norm2, dim3((unsigned)((m.n + 255) / 256)), dim3(256), 0, m.stream, m.d_mean2d, m.d_mean2d, m.n);
-                DVS_OR_THROW(dvs_densify_accumulate(m.stream, m.n, m.fwd.radii, m.d_mean2d, m.W, m.H, m.d_grad_accum, m.d_denom, m.d_max_radii));
-            }
-        }
-        vis_radii = m.fwd.radii;                // (the last view's — visibleAdam is a single-view notion in this mode)
-    } else {
-        // ONE multi-view pass: parameters read once, one depth sort / scan / (view, tile) sort / composite launch for all V views, the
-        // gradient rows written once (their sum over the views)
-        DVS_OR_THROW(dvs_raster_forward_views(m.ctx, m.stream, &sp, vcams.data(), V, &opts, m.d_out));
-        DVS_OR_THROW(dvs_get_view_state(m.ctx, 0, &m.fwd));                       // (view-major arrays: fwd.radii = [V][n])
-        for (int v = 0; v < V; ++v) loss_of_view(v);
-        if (fact) { g.sh0 = nullptr; g.shN = nullptr; g.dcolor = m.d_dcolor_scratch; }
-        DVS_OR_THROW(dvs_raster_backward_composite(m.ctx, m.stream, vcams.data(), &opts, m.d_dL));
-        if (fact) {
-            DVS_OR_THROW(dvs_raster_backward_dcolor(m.ctx, m.stream, m.d_dcolor_local));
-            HIP_OR_THROW(hipEventRecord(m.ev_dcolor, m.stream));
-            HIP_OR_THROW(hipStreamWaitEvent(m.comm_stream, m.ev_dcolor, 0));
-            DVS_OR_THROW(dvs_comm_all_gather_f32(m.comm, m.comm_stream, m.d_dcolor_local, m.d_dcolor_all, (size_t)V * m.n * 3));
-        }
-        if (want_stats && absgrad) {            // per view, from the composite backward's rows (before A9 consumes them): the exact single-view rule
-            const float* rows = nullptr; int rf = 0;
-            DVS_OR_THROW(dvs_get_bwd_intermediates(m.ctx, &rows, &rf));
-            DVS_OR_THROW(dvs_densify_accumulate_rows(m.stream, m.n, V, m.fwd.radii, rows, m.W, m.H, m.d_grad_accum, m.d_denom, m.d_max_radii));
-        }
-        if (fact && m.a9_chunks > 1 && m.n >= 256 * m.a9_chunks) {
-            // A9 in splat chunks: as soon as chunk k is queued its 44 B/splat of geometry gradients (four ranges of the flat buffer, one
-            // grouped collective) start their all-reduce on the communication stream, under the A9 of the chunks behind it (SURVEY §8(e))
-            HIP_OR_THROW(hipEventRecord(m.ev_gather, m.comm_stream));            // (behind the colour all-gather queued above)
-            const int per = ((m.n + m.a9_chunks - 1) / m.a9_chunks + 255) / 256 * 256;
-            int k = 0;
-            for (int first = 0; first < m.n; first += per, ++k) {
-                const int count = std::min(per, m.n - first);
-                DVS_OR_THROW(dvs_raster_backward_project_chunk(m.ctx, m.stream, &sp, vcams.data(), &opts, &g, first, count));
-                HIP_OR_THROW(hipEventRecord(m.ev_chunk[(size_t)k], m.stream));
-                HIP_OR_THROW(hipStreamWaitEvent(m.comm_stream, m.ev_chunk[(size_t)k], 0));
-                DVS_OR_THROW(dvs_comm_group_start(m.comm));
-                DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(m.comm, m.comm_stream, m.d_grad[P_POS] + 3 * (size_t)first, 3 * (size_t)count));
-                DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(m.comm, m.comm_stream, m.d_grad[P_SCALE] + 3 * (size_t)first, 3 * (size_t)count));
-                DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(m.comm, m.comm_stream, m.d_grad[P_ROT] + 4 * (size_t)first, 4 * (size_t)count));
-                DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(m.comm, m.comm_stream, m.d_grad[P_OPA] + (size_t)first, (size_t)count));
-                DVS_OR_THROW(dvs_comm_group_end(m.comm));
-                HIP_OR_THROW(hipEventRecord(m.ev_ar[(size_t)k], m.comm_stream));
-            }
-            geom_reduced = true;
-            chunk_per = per; n_chunks = k;
-        } else {
-            DVS_OR_THROW(dvs_raster_backward_project(m.ctx, m.stream, &sp, vcams.data(), &opts, &g));
-        }
-        if (want_stats && !absgrad) {
-            // without abs-grad the multi-view pass hands out the SUM over the views of dL/dmean2D: its norm is accumulated once per step
-            // for splats visible in at least one view (for V = 1 the reference rule; documented difference for V > 1)
-            if (!m.d_vis_radius) HIP_OR_THROW(hipMalloc((void**)&m.d_vis_radius, (size_t)m.cap * sizeof(int) + 16));
-            DVS_OR_THROW(dvs_any_view_radius(m.stream, m.n, V, m.fwd.radii, m.d_vis_radius));
-            hipLaunchKernelGGL(k_norm2, dim3((unsigned)((m.n + 255) / 256)), dim3(256), 0, m.stream, m.d_mean2d, m.d_mean2d, m.n);
-            DVS_OR_THROW(dvs_densify_accumulate(m.stream, m.n, m.d_vis_radius, m.d_mean2d, m.W, m.H, m.d_grad_accum, m.d_denom, m.d_max_radii));
-        }
-        if (V == 1) {
-            vis_radii = m.fwd.radii;
-        } else if (m.cfg.visibleAdam && m.world == 1) {
-            if (!m.d_vis_radius) HIP_OR_THROW(hipMalloc((void**)&m.d_vis_radius, (size_t)m.cap * sizeof(int) + 16));
-            DVS_OR_THROW(dvs_any_view_radius(m.stream, m.n, V, m.fwd.radii, m.d_vis_radius));
-            vis_radii = m.d_vis_radius;
-        }
-    }
-    // Adam, per-group learning rates (names gs_train.cpp:52-57; position lr decays exponentially init -> final, scaled by the scene extent)
-    const float t = std::min(1.0f, (float)m.step / (float)std::max(1, m.cfg.numIters));
-    const float lr_pos = m.extent * std::exp((1.f - t) * std::log(m.cfg.poslrInit) + t * std::log(m.cfg.poslrFinal));
-    const float lr[6] = {lr_pos, m.cfg.featurelr, m.cfg.featurelr / 20.f, m.cfg.opacitylr, m.cfg.scalinglr, m.cfg.rotationlr};
-    // one launch per set of groups; shN chunks above the active SH degree have g = m = v = 0 (Adam is the identity there)
-    static const int width[6] = {3, 3, 45, 1, 3, 4};
-    dvs_adam_group ag[6];
-    for (int k = 0; k < 6; ++k) {
-        ag[k] = dvs_adam_group{m.d_param[k], m.d_grad[k], m.d_m[k], m.d_v[k], (uint64_t)m.dev_floats(k), lr[k], width[k],
-                               k == P_SHN ? DVS_SHN_TILED : DVS_SHN_ROWS, 0};
-        if (k == P_SHN) ag[k].active_chunks = deg >= 3 ? 0 : (3 * ((deg + 1) * (deg + 1) - 1) + 3) / 4;
-    }
-    if (deg == 0) ag[P_SHN].count = 0;
-    const bool visible_only = m.cfg.visibleAdam && m.world == 1 && vis_radii;       // per-rank visibility would let the replicas drift apart
-    const int* adam_gate = visible_only ? vis_radii : nullptr;
-    bool sh_adam_done = false;
-    // data parallel, over RCCL / xGMI: all-gather of the views' colour gradients + all-reduce of the geometry groups, then every
-    // replica rebuilds the summed SH rows from all views (factorised) — or ONE sum-all-reduce of all six groups (they share a buffer)
-    if (fact) {             // (all collectives on the communication stream, in the same order on every rank)
-        if (!geom_reduced) {
-            HIP_OR_THROW(hipEventRecord(m.ev_gather, m.comm_stream));            // (behind the colour all-gather)
-            HIP_OR_THROW(hipEventRecord(m.ev_bwd, m.stream));
-            HIP_OR_THROW(hipStreamWaitEvent(m.comm_stream, m.ev_bwd, 0));
-            DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(m.comm, m.comm_stream, m.d_grad_flat, m.geom_floats));
-        }
-        HIP_OR_THROW(hipEventRecord(m.ev_comm, m.comm_stream));
-        // The SH rows need only the colour all-gather: they are rebuilt and their Adam step (sh0 + shN: 192 of the 236 B per splat) runs
-        // WHILE the geometry all-reduce is still on the links; the geometry groups follow when it has landed.
-        HIP_OR_THROW(hipStreamWaitEvent(m.stream, m.ev_gather, 0));
-        std::vector<float> campos(ci_all.size() * 3);               // slot order of the all-gather: [rank][local view]
-        for (size_t q = 0; q < ci_all.size(); ++q) for (int k = 0; k < 3; ++k) campos[q * 3 + k] = m.cams[(size_t)ci_all[q]].campos[k];
-        DVS_OR_THROW(dvs_sh_grad_combine(m.ctx, m.stream, m.n, m.d_param[P_POS], deg, (int)ci_all.size(), campos.data(), m.d_dcolor_all,
-                                         m.d_grad[P_SH0], m.d_grad[P_SHN], 0, DVS_SHN_TILED));
-        dvs_adam_group sh_groups[2] = {ag[P_SH0], ag[P_SHN]};
-        DVS_OR_THROW(dvs_adam_step_groups(m.stream, sh_groups, 2, 0.9f, 0.999f, 1e-15f, it, adam_gate, m.n));
-        sh_adam_done = true;
-        if (!(m.pipeline && geom_reduced)) HIP_OR_THROW(hipStreamWaitEvent(m.stream, m.ev_comm, 0));
-    } else if (m.comm) {
-        DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(m.comm, m.stream, m.d_grad_flat, m.grad_floats));
-    }
-    const bool refine_now = refining && it > m.cfg.warmupLength && m.cfg.refineEvery > 0 && it % m.cfg.refineEvery == 0;
-    const bool reset_now = refining && !mcmc && m.cfg.resetAlphaEvery > 0 && it % m.cfg.resetAlphaEvery == 0;
-    const bool prune_now = !refining && m.cfg.pruneStrategy > 0 && m.cfg.pruneInterval > 0 && it % m.cfg.pruneInterval == 0;
-    const bool pipelined_tail = m.pipeline && geom_reduced && sh_adam_done;
-    if (pipelined_tail) {
-        // PIPELINED exchange (round 6; SURVEY 8(e) "Overlap"; DVS_EXCHANGE_PIPELINE=1, off by default until it has run on real links): the
-        // geometry gradients left in chunks behind A9. Here every chunk is finished as soon as ITS all-reduce has landed — regulariser,
-        // Adam on the four geometry groups, exploration noise, each on the chunk's splat range (all element-wise: bit-identical to the
-        // whole-array calls) — and then the NEXT iteration's projection (A2) of that chunk is queued: A2 is per splat, and the chunk's
-        // parameters are final (the SH groups were stepped above, under the all-reduces). Only the last chunk's all-reduce is exposed;
-        // the all-reduces of the chunks before it run under the Adam / A2 of their predecessors. Iterations that refine, reset or prune
-        // change the parameters after Adam: no early projection there (the next forward projects everything itself).
-        const bool early = !refine_now && !reset_now && !prune_now && it < m.cfg.numIters && !m.sequential_views;
-        std::vector<dvs_camera> ncams;
-        dvs_opts nopts = opts;
-        if (early) {
-            m.next_ci.assign(ci_all.size(), 0);
-            draw_cameras(m.next_ci);
-            ncams.resize((size_t)V);
-            for (int v = 0; v < V; ++v) ncams[(size_t)v] = m.cams[(size_t)m.next_ci[(size_t)m.rank * V + v]];
-            nopts.sh_degree = m.cfg.progressiveTrain ? std::min(m.sh_max, it / 1000) : m.sh_max;       // (what the next trainStep will compute from m.step = it)
-            nopts.accumulate = 0;
-        }
-        for (int k = 0; k < n_chunks; ++k) {
-            const int first = k * chunk_per, count = std::min(chunk_per, m.n - first);
-            HIP_OR_THROW(hipStreamWaitEvent(m.stream, m.ev_ar[(size_t)k], 0));
-            if (mcmc)
-                DVS_OR_THROW(dvs_mcmc_regularize_range(m.stream, m.n, first, count, m.d_param[P_OPA], m.d_param[P_SCALE], m.d_grad[P_OPA], m.d_grad[P_SCALE], 0.01f, 0.01f));
-            dvs_adam_group geo[4] = {ag[P_POS], ag[P_OPA], ag[P_SCALE], ag[P_ROT]};
-            for (dvs_adam_group& q : geo) {
-                const size_t off = (size_t)q.width * (size_t)first;
-                q.param += off; q.grad += off; q.m += off; q.v += off; q.count = (uint64_t)q.width * (uint64_t)count;
-            }
-            DVS_OR_THROW(dvs_adam_step_groups(m.stream, geo, 4, 0.9f, 0.999f, 1e-15f, it, nullptr, count));
-            if (mcmc && m.cfg.noiselr > 0.f)
-                DVS_OR_THROW(dvs_mcmc_add_noise_range(m.stream, m.n, first, count, m.d_param[P_POS], m.d_param[P_SCALE], m.d_param[P_ROT], m.d_param[P_OPA],
-                                                      m.cfg.noiselr * lr_pos, (uint32_t)it));
-            if (early) DVS_OR_THROW(dvs_raster_forward_views_prepare(m.ctx, m.stream, &sp, ncams.data(), V, &nopts, first, count));
-        }
-    } else {
-        if (mcmc)      // opacity and scale regularisers of the MCMC strategy (0.01 each in the published rule): a function of the replicated
-                       // parameters, added once (after the exchange) on every rank
-            DVS_OR_THROW(dvs_mcmc_regularize(m.stream, m.n, m.d_param[P_OPA], m.d_param[P_SCALE], m.d_grad[P_OPA], m.d_grad[P_SCALE], 0.01f, 0.01f));
-        if (sh_adam_done) {
-            dvs_adam_group geo_groups[4] = {ag[P_POS], ag[P_OPA], ag[P_SCALE], ag[P_ROT]};
-            DVS_OR_THROW(dvs_adam_step_groups(m.stream, geo_groups, 4, 0.9f, 0.999f, 1e-15f, it, adam_gate, m.n));
-        } else {
-            DVS_OR_THROW(dvs_adam_step_groups(m.stream, ag, 6, 0.9f, 0.999f, 1e-15f, it, adam_gate, m.n));
-        }
-        if (mcmc && m.cfg.noiselr > 0.f)      // exploration noise, scaled by the position learning rate (`noiselr`, gs_train.cpp:97)
-            DVS_OR_THROW(dvs_mcmc_add_noise(m.stream, m.n, m.d_param[P_POS], m.d_param[P_SCALE], m.d_param[P_ROT], m.d_param[P_OPA],
-                                            m.cfg.noiselr * lr_pos, (uint32_t)it));
-    }
-    if (refine_now) { if (mcmc) m.densify_mcmc(it); else m.densify(it); }
-    if (reset_now)
+    m.render_backward(s);
+    const bool pipelined = m.pipeline && s.n_chunks > 0;
+    m.exchange(s, pipelined);
+    if (pipelined) m.finish_pipelined(s);
+    else if (m.exchange_factorised()) m.finish_range(s, 0, m.n, kGeomGroups, 4, s.adam_gate);     // (the SH groups were stepped in exchange())
+    else m.finish_range(s, 0, m.n, kAllGroups, 6, s.adam_gate);
+    if (s.refine_now) { if (s.mcmc) m.densify_mcmc(s.it); else m.densify(s.it); }
+    if (s.reset_now)
         DVS_OR_THROW(dvs_reset_opacity(m.stream, m.n, m.d_param[P_OPA], 0.01f, m.d_m[P_OPA], m.d_v[P_OPA]));
-    if (prune_now) {
-        m.prune_light(it);
-        pruenIteraions.push_back(it);
+    if (s.prune_now) {
+        m.prune_light(s.it);
+        pruenIteraions.push_back(s.it);
     }
     if (m.cfg.verbose && m.rank == 0 && (m.step % 100 == 0))          // same line the editor logs (application/editor/source/editor.cpp:1554)
         logf_("Iteraions %d, loss : %f", m.step, (double)getCurrentLoss());
-    m.step = it;
-    curIteration = it;
+    m.step = s.it;
+    curIteration = s.it;
     m.host_valid = false;
     if (m.step >= m.cfg.numIters) m.status = TrainingStatus::Training_Done;
 }
@@ -970,7 +969,7 @@ float GaussianTrainerScene::getCurrentLoss() {
         const float w = m.d_ssim_maps[0] ? m.cfg.ssimWeight : 0.f;
         double l1 = 0, ssim_sum = 0;
         for (int k = 0; k < DVS_SSIM_SLOTS; ++k) { l1 += h[k]; ssim_sum += h[DVS_SSIM_SLOTS + k]; }
-        const double nv = (double)std::max(1, m.loss_views);             // the sums cover the step's views: report their mean
+        const double nv = (double)m.vpi;                                  // the sums cover the step's views: report their mean
         m.last_loss = (float)(l1 / nv) + (w > 0.f ? w * (1.f - (float)(ssim_sum / nv / (3.0 * m.W * m.H))) : 0.f);
     }
     return m.last_loss;
