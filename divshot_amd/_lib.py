@@ -3,7 +3,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("DVS_RASTER_LIB") or os.path.join(_HERE, "lib", "libdvsraster.so")     # override: experiment builds (tools/)
+LIB_PATH = os.environ.get("DVS_RASTER_LIB") or os.path.join(_HERE, "lib", "libdvsraster.so")     # override: another build of the library (tools/lib_ab.sh A/Bs two builds)
 
 
 class DvsError(RuntimeError):

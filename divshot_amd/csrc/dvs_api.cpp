@@ -48,10 +48,6 @@ struct Buf {
         if (e != hipSuccess) { e = hipMalloc(&p, need); want = need; }
         if (e != hipSuccess) { set_error("hipMalloc", e, __FILE__, __LINE__); p = nullptr; return DVS_ERR_HIP; }
         bytes = want;
-#ifdef DVS_EXPERIMENT
-        // timing-only ablation builds (tools/xbuild.sh) may skip stores: zeroed arenas keep every index a later kernel gathers through valid
-        (void)hipMemset(p, 0, want);
-#endif
         return DVS_OK;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
@@ -117,7 +113,6 @@ struct dvs_ctx {
         dvs_camera cams[DVS_MAX_VIEWS];
     } prep;
     int bwd_variant = DVS_BWD_TR;        // which A8 kernel (dvs_set_backward_variant; env DVS_BWD_VARIANT at create): the measured winner
-    int fwd_variant = DVS_FWD_QUADRANT;  // which A7 kernel (dvs_set_forward_variant; env DVS_FWD_VARIANT at create)
     // stage timing: `timing` = every stage, synchronising per call (profiling iterations); `probe` = hipEvent pairs around the
     // composite kernels only, never synchronising — they are read back once, so the kernels are timed under the concurrency of
     // the real (pipelined) step
@@ -239,12 +234,8 @@ dvs_ctx* dvs_create_views(int device, size_t max_splats, int max_w, int max_h, i
     if ((e = hipSetDevice(device)) != hipSuccess) { set_error("hipSetDevice", e, __FILE__, __LINE__); return nullptr; }
     dvs_ctx* c = new dvs_ctx();
     c->device = device; c->max_splats = max_splats; c->max_w = max_w; c->max_h = max_h; c->max_views = max_views;
-    // (A/B runs; the retired kernels exist in experiment builds only — elsewhere the request falls back to the default)
-    if (const char* v = getenv("DVS_BWD_VARIANT")) {
-        c->bwd_variant = v[0] == '0' ? DVS_BWD_BLOCKS : v[0] == '1' ? DVS_BWD_REDUCE : v[0] == '2' ? DVS_BWD_MM : DVS_BWD_TR;
-        if ((c->bwd_variant == DVS_BWD_REDUCE || c->bwd_variant == DVS_BWD_MM) && !dvs_launch_render_bwd) c->bwd_variant = DVS_BWD_TR;
-    }
-    if (const char* v = getenv("DVS_FWD_VARIANT")) c->fwd_variant = (v[0] == '0' && dvs_launch_render_fwd_blocks) ? DVS_FWD_BLOCKS : DVS_FWD_QUADRANT;
+    // (A/B runs; a request for one of the retired kernels, 1 or 2, falls back to the default)
+    if (const char* v = getenv("DVS_BWD_VARIANT")) c->bwd_variant = v[0] == '0' ? DVS_BWD_BLOCKS : DVS_BWD_TR;
     if (const char* v = getenv("DVS_LIVE_LISTS")) c->live_lists = v[0] != '0';
     if (hipMalloc((void**)&c->total_dev, 32) != hipSuccess || hipHostMalloc((void**)&c->total_host, 32, hipHostMallocDefault) != hipSuccess ||
         hipMemset(c->total_dev, 0, 32) != hipSuccess) {
@@ -297,13 +288,18 @@ void dvs_destroy(dvs_ctx* c) {
     delete c;
 }
 
+// tile-rectangle record format of a forward (DVS_TILES_TIGHT is opt-in: only the tiles the alpha >= 1/255 ellipse reaches, dvs_raster.h)
+static int rect_format(const dvs_opts* opts, int tiles_x, int tiles_y) {
+    if (opts->tile_bounds == DVS_TILES_TIGHT) return DVS_FE_RECT_TIGHT;
+    return (tiles_x <= 255 && tiles_y <= 255) ? DVS_FE_RECT_U8 : DVS_FE_RECT_U16;
+}
+
 // A2 for the splats [first, first + count) of all views (begin: the front end's zeroed state first — the key-range slots and super sums of
 // frontend.hip and the tile ranges behind them, ONE memset)
 static int run_a2(dvs_ctx* c, hipStream_t st, const dvs_splats* p, const dvs_camera* cams, int V, const dvs_opts* opts, int64_t first, int64_t count, bool begin) {
     const int n = p->n, W = cams[0].width, H = cams[0].height;
     const int tiles_x = (W + DVS_TILE - 1) / DVS_TILE, tiles_y = (H + DVS_TILE - 1) / DVS_TILE, tiles = tiles_x * tiles_y;
-    const int tight = opts->tile_bounds == DVS_TILES_TIGHT ? 1 : 0;
-    const int rect_fmt = tight ? DVS_FE_RECT_TIGHT : (tiles_x <= 255 && tiles_y <= 255) ? DVS_FE_RECT_U8 : DVS_FE_RECT_U16;
+    const int rect_fmt = rect_format(opts, tiles_x, tiles_y);
     DvsCams dcams;
     for (int v = 0; v < V; ++v) dcams.c[v] = to_dev_cam(cams[v]);
     if (begin) HIPCHECK(hipMemsetAsync(c->ranges.p, 0, c->fe_zero_bytes + (size_t)tiles * V * 8, st));
@@ -330,14 +326,12 @@ static int forward_views(dvs_ctx* c, hipStream_t st, const dvs_splats* p, const 
     const int n = p->n, W = cam->width, H = cam->height;
     const int tiles_x = (W + DVS_TILE - 1) / DVS_TILE, tiles_y = (H + DVS_TILE - 1) / DVS_TILE, tiles = tiles_x * tiles_y;
     const size_t nV = (size_t)n * V;
-    DvsCams dcams;
     float bgs[DVS_MAX_VIEWS * 3];
-    for (int v = 0; v < V; ++v) { dcams.c[v] = to_dev_cam(cams[v]); for (int k = 0; k < 3; ++k) bgs[3 * v + k] = cams[v].bg[k]; }
+    for (int v = 0; v < V; ++v) for (int k = 0; k < 3; ++k) bgs[3 * v + k] = cams[v].bg[k];
     c->have_fwd = false;
     c->rows_pending = false;
     timing_reset(c);
     StageTimer tm(c, st);
-    const int tight = opts->tile_bounds == DVS_TILES_TIGHT ? 1 : 0;      // opt-in: only the tiles the alpha >= 1/255 ellipse reaches (dvs_raster.h)
 
     uint64_t T = 0, T_expected = 0;
     const uint64_t* T_dev = nullptr;           // async: the kernels over instances read T on the device, grids sized for the capacity
@@ -370,7 +364,7 @@ static int forward_views(dvs_ctx* c, hipStream_t st, const dvs_splats* p, const 
     }
     {
         // ---- the segmented front end (frontend.hip): every view is a segment of the sorts, workgroup b works for view b % V ----
-        const int rect_fmt = tight ? DVS_FE_RECT_TIGHT : (tiles_x <= 255 && tiles_y <= 255) ? DVS_FE_RECT_U8 : DVS_FE_RECT_U16;
+        const int rect_fmt = rect_format(opts, tiles_x, tiles_y);
         // A2 — unless dvs_raster_forward_views_prepare already ran it, chunk by chunk, for exactly these inputs (a data-parallel step
         // projects the next iteration's splats behind the optimizer's chunks while the gradient exchange is still on the links)
         const bool prepared = prep_matches(c, p, cams, V, opts) && c->prep.next == (int64_t)n;
@@ -418,10 +412,10 @@ static int forward_views(dvs_ctx* c, hipStream_t st, const dvs_splats* p, const 
                                             c->inst_splat[0].as<uint32_t>(), key16));
         size_t e5 = tm.mark(); tm.span("duplicate", e4, e5);
         // A5 (high key bits): every view's instances by tile id; the last pass hands out view * tiles + tile
-        // A6 rides on the last pass (a range boundary is where the scattered tile id changes) whenever k_render_fwd composites (it decodes
-        // the ranges). An asynchronous forward does not even write the sorted tile ids: nothing on the device reads them, and
+        // A6 rides on the last pass (a range boundary is where the scattered tile id changes): k_render_fwd decodes the ranges
+        // (DVS_FE_NO_FUSE_A6=1: A6 as its own kernel, a cross-check). An asynchronous forward does not even write the sorted tile ids: nothing on the device reads them, and
         // dvs_fwd_state.sorted_tile is then NULL (dvs_raster.h).
-        const bool fuse_a6 = (c->fwd_variant == DVS_FWD_QUADRANT || V > 1) && !fe_no_fuse();
+        const bool fuse_a6 = !fe_no_fuse();
         const bool write_keys = !(fuse_a6 && c->async_T) || c->export_tiles;
         if (n > 0) {
             const uint64_t cap = c->async_T ? c->inst_cap : T;
@@ -442,23 +436,18 @@ static int forward_views(dvs_ctx* c, hipStream_t st, const dvs_splats* p, const 
     // the live lists of A7 (entries that reach their tile, compacted) go into the sort's other pair of instance arrays, free by now
     c->live_splat = nullptr; c->live_pos = nullptr;
     uint64_t* rec_masks = nullptr; uint64_t rec_cap = 0;          // dvs_debug_record_decisions (parity tests): one view, synchronous T
-    if (c->rec_masks && V == 1 && !c->async_T && (c->fwd_variant == DVS_FWD_QUADRANT)) {
+    if (c->rec_masks && V == 1 && !c->async_T) {
         rec_masks = c->rec_masks; rec_cap = c->rec_cap;
         HIPCHECK(hipMemsetAsync(rec_masks, 0, (size_t)(T < rec_cap ? T : rec_cap) * 32, st));
     }
-    if (c->fwd_variant == DVS_FWD_QUADRANT || V > 1) {
-        // Only the "tr" composite backward walks them (the other variants ignore them), and they cost the forward two 4-B stores per
-        // instance: none for an inference-only context (dvs_set_live_lists(ctx, 0)) or another backward. The spare pair of the tile
-        // sort's ping-pong buffers is RESERVED for them until the next forward on this context: nothing after the sort may reuse
-        // inst_*[icur ^ 1].
-        if (c->live_lists && c->bwd_variant == DVS_BWD_TR) { c->live_splat = c->inst_splat[icur ^ 1].as<uint32_t>(); c->live_pos = c->inst_tile[icur ^ 1].as<uint32_t>(); }
-        HIPCHECK(dvs_launch_render_fwd(st, W, H, tiles_x, tiles_y, V, ranges_ptr(c), c->inst_splat[icur].as<uint32_t>(),
-                                       c->splat2d.as<float>(), bgs, out_rgb, c->final_T.as<float>(), c->n_contrib.as<uint32_t>(),
-                                       c->live_splat, c->live_pos, rec_masks, rec_cap, ranges_encoded ? c->ranges_canon.as<uint32_t>() : nullptr));
-    } else
-        HIPCHECK(dvs_launch_render_fwd_blocks(st, W, H, tiles_x, tiles_y, ranges_ptr(c), c->inst_splat[icur].as<uint32_t>(),
-                                              c->splat2d.as<float>(), cam->bg, out_rgb,
-                                              c->final_T.as<float>(), c->n_contrib.as<uint32_t>()));
+    // Only the "tr" composite backward walks them (the other variant ignores them), and they cost the forward two 4-B stores per
+    // instance: none for an inference-only context (dvs_set_live_lists(ctx, 0)) or the other backward. The spare pair of the tile
+    // sort's ping-pong buffers is RESERVED for them until the next forward on this context: nothing after the sort may reuse
+    // inst_*[icur ^ 1].
+    if (c->live_lists && c->bwd_variant == DVS_BWD_TR) { c->live_splat = c->inst_splat[icur ^ 1].as<uint32_t>(); c->live_pos = c->inst_tile[icur ^ 1].as<uint32_t>(); }
+    HIPCHECK(dvs_launch_render_fwd(st, W, H, tiles_x, tiles_y, V, ranges_ptr(c), c->inst_splat[icur].as<uint32_t>(),
+                                   c->splat2d.as<float>(), bgs, out_rgb, c->final_T.as<float>(), c->n_contrib.as<uint32_t>(),
+                                   c->live_splat, c->live_pos, rec_masks, rec_cap, ranges_encoded ? c->ranges_canon.as<uint32_t>() : nullptr));
     if (c->probe) (void)probe_event(c, st);
     size_t e8 = tm.mark(); tm.span("render_fwd", e7, e8);
 
@@ -575,15 +564,9 @@ static int bwd_composite(dvs_ctx* c, hipStream_t st, const dvs_camera* cams, con
     if (c->bwd_variant == DVS_BWD_TR)
         HIPCHECK(dvs_launch_render_bwd_tr(st, s.width, s.height, s.tiles_x, s.tiles_y, V, s.ranges, s.sorted_splat, s.splat2d, bgs, s.final_T,
                                           s.n_contrib, dL_drgb, c->g_rows.as<float>(), opts->absgrad, opts->grad_mode, c->live_splat, c->live_pos));
-    else if (c->bwd_variant == DVS_BWD_BLOCKS)
+    else                                                   // DVS_BWD_BLOCKS: the setter and dvs_create_views admit nothing else
         HIPCHECK(dvs_launch_render_bwd_blocks(st, s.width, s.height, s.tiles_x, s.tiles_y, V, s.ranges, s.sorted_splat, s.splat2d,
                                               bgs, s.final_T, s.n_contrib, dL_drgb, c->g_rows.as<float>(), opts->absgrad, opts->grad_mode));
-    else {                                                 // experiment builds: the retired kernels (the mm experiment renders one view)
-        if (!dvs_launch_render_bwd) { g_last_error = "dvs_raster_backward: this build does not contain the selected composite-backward variant"; return DVS_ERR_INVALID; }
-        HIPCHECK(dvs_launch_render_bwd(st, s.width, s.height, s.tiles_x, s.tiles_y, V, s.ranges, s.sorted_splat, s.splat2d,
-                                       bgs, s.final_T, s.n_contrib, dL_drgb, c->g_rows.as<float>(), opts->absgrad, opts->grad_mode,
-                                       V > 1 ? DVS_BWD_REDUCE : c->bwd_variant));
-    }
     if (c->probe) (void)probe_event(c, st);
     if (tm) { size_t e2 = tm->mark(); tm->span("render_bwd", e1, e2); }
     c->rows_pending = true;
@@ -896,9 +879,8 @@ int dvs_debug_record_decisions(dvs_ctx* c, uint64_t* take_masks, uint64_t capaci
 
 int dvs_set_backward_variant(dvs_ctx* c, int variant) {
     if (!c || variant < DVS_BWD_BLOCKS || variant > DVS_BWD_TR) { g_last_error = "dvs_set_backward_variant: bad argument"; return DVS_ERR_INVALID; }
-    if ((variant == DVS_BWD_REDUCE || variant == DVS_BWD_MM) && !dvs_launch_render_bwd) {
-        g_last_error = "dvs_set_backward_variant: the 'reduce' and 'mm' kernels are retired — this library contains 'tr' (default) and 'blocks' only "
-                       "(an experiment build, tools/xbuild.sh, brings them back)";
+    if (variant == DVS_BWD_REDUCE || variant == DVS_BWD_MM) {
+        g_last_error = "dvs_set_backward_variant: the 'reduce' and 'mm' kernels are retired — this library contains 'tr' (default) and 'blocks' only";
         return DVS_ERR_UNSUPPORTED;
     }
     c->bwd_variant = variant;
@@ -910,12 +892,12 @@ int dvs_set_live_lists(dvs_ctx* c, int enable) {
     return DVS_OK;
 }
 int dvs_set_forward_variant(dvs_ctx* c, int variant) {
-    if (!c || (variant != DVS_FWD_BLOCKS && variant != DVS_FWD_QUADRANT)) { g_last_error = "dvs_set_forward_variant: bad argument"; return DVS_ERR_INVALID; }
-    if (variant == DVS_FWD_BLOCKS && !dvs_launch_render_fwd_blocks) {
-        g_last_error = "dvs_set_forward_variant: the per-block forward is retired — this library contains the quadrant forward only (tools/xbuild.sh brings it back)";
+    // 0 = the per-block forward (retired), 1 = the quadrant forward, the only one there is (dvs_raster.h)
+    if (!c || (variant != 0 && variant != 1)) { g_last_error = "dvs_set_forward_variant: bad argument"; return DVS_ERR_INVALID; }
+    if (variant == 0) {
+        g_last_error = "dvs_set_forward_variant: the per-block forward is retired — this library contains the quadrant forward only";
         return DVS_ERR_UNSUPPORTED;
     }
-    c->fwd_variant = variant;
     return DVS_OK;
 }
 

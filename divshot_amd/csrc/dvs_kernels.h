@@ -92,20 +92,12 @@ hipError_t dvs_launch_render_fwd(hipStream_t st, int W, int H, int tiles_x, int 
                                  position -> number of such entries before it in its tile*/,
                                  uint64_t* take_masks /*test hook (or null): [take_cap][4] zeroed by the caller — per list position and 8x8 quadrant, the pixels that took the entry*/,
                                  uint64_t take_cap, uint32_t* ranges_out = nullptr /*where k_render_fwd leaves (start, end) when `ranges` is encoded*/);
-// EXPERIMENT BUILDS ONLY (-DDVS_EXPERIMENT): the retired A8 kernels "reduce" and "mm". Declared weak: the release library does not
-// define it, dvs_set_backward_variant refuses those variants there.
-hipError_t dvs_launch_render_bwd(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, const uint32_t* ranges,
-                                 const uint32_t* sorted_splat, const float* splat2d, const float* bgs, const float* final_T, const uint32_t* n_contrib,
-                                 const float* dL_dout, float* grad_rows /*[n,12] zero-initialised*/, int absgrad, int grad_mode,
-                                 int variant /*DVS_BWD_*: which A8 kernel (the mm experiment renders one view)*/) __attribute__((weak));
 // A8 kernel variants (dvs_set_backward_variant): same inputs, same 48-B row contract, results equal to fp32 roundoff
 enum { DVS_BWD_BLOCKS = 0 /*per-4x4-block lists, four cursors per wave, 12-value group reduction per step (round 2): kept in the release library as
        the independent-summation-order cross-check of the parity tests*/, DVS_BWD_REDUCE = 1 /*per-quadrant masks, wave-wide reduction tree per visit
-       (round 1; experiment builds only)*/, DVS_BWD_MM = 2 /*per-quadrant masks, sums contracted on the fp32 matrix pipe (experiment builds only)*/,
+       (round 1; retired, refused by the setter)*/, DVS_BWD_MM = 2 /*per-quadrant masks, sums contracted on the fp32 matrix pipe (retired, refused)*/,
        DVS_BWD_TR = 3 /*per-4x4-block lists; (v5, w) pairs transposed through LDS and accumulated serially per (block, slot, pixel row):
        render_tr.hip (default since round 3)*/ };
-// A7 kernel variants (dvs_set_forward_variant): bit-identical results
-enum { DVS_FWD_BLOCKS = 0 /*per-4x4-block lists (experiment builds only)*/, DVS_FWD_QUADRANT = 1 /*per-quadrant masks walked by the scalar unit (default)*/ };
 
 // render_tr.hip
 hipError_t dvs_launch_render_bwd_tr(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, const uint32_t* ranges,
@@ -115,9 +107,6 @@ hipError_t dvs_launch_render_bwd_tr(hipStream_t st, int W, int H, int tiles_x, i
                                     const uint32_t* live_pos);
 
 // render_blocks.hip
-hipError_t dvs_launch_render_fwd_blocks(hipStream_t st, int W, int H, int tiles_x, int tiles_y, const uint32_t* ranges,
-                                        const uint32_t* sorted_splat, const float* splat2d, const float bg[3], float* out_color,
-                                        float* final_T, uint32_t* n_contrib) __attribute__((weak));      // experiment builds only
 hipError_t dvs_launch_render_bwd_blocks(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, const uint32_t* ranges,
                                         const uint32_t* sorted_splat, const float* splat2d, const float* bgs /*[n_views][3]*/, const float* final_T,
                                         const uint32_t* n_contrib, const float* dL_dout, float* grad_rows, int absgrad, int grad_mode);

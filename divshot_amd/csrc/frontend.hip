@@ -821,7 +821,7 @@ hipError_t dvs_launch_seg_init(hipStream_t st, int n, int V, uint32_t rows_per_v
     return hipGetLastError();
 }
 
-// ---- A6 as its own kernel: only when k_render_fwd does not composite (experiment builds' per-block forward) or DVS_FE_NO_FUSE_A6=1;
+// ---- A6 as its own kernel: only with DVS_FE_NO_FUSE_A6=1 (a cross-check switch of the parity tests);
 // normally the tile sort's last pass builds the ranges (k_seg_scatter) ---------------------------------------------------------------
 __global__ void __launch_bounds__(FE_BLOCK)
 k_tile_ranges(uint64_t T_host, const uint64_t* __restrict__ T_dev, const uint32_t* __restrict__ sorted_tile, uint2* __restrict__ ranges) {

@@ -509,8 +509,8 @@ __device__ __forceinline__ void a9_sigma_to_params(float in_s0, float in_s1, flo
 // dL/d(unit direction) of a view's colour: gdir[d] = sum_k d(basis_k)/d(dir_d) * s_k with s_k = sum_ch shN[k][ch] * gc[ch] (the colour
 // gradient folded into the coefficients FIRST: 45 + 33 fused multiply-adds per (view, splat) instead of the 45 x 3 x 3 multiply-multiply-add
 // triples of rounds 1-5a — k_preprocess_bwd_views is 60 % vector-ALU-busy by the counters, profiles/r05b_pmc_sq.txt). Only the structurally
-// non-zero derivative entries are read (dvs_sh_basis_grad, dvs_device.h:211). Both A9 kernels use this one form, so a batch stays
-// bit-identical to its views run one by one.
+// non-zero derivative entries are read (dvs_sh_basis_grad, dvs_device.h:211). Both A9 kernels use this one form, so the per-view
+// contributions of a batch are the ones its views produce one by one (the sums over the views are not: see k_preprocess_bwd_views).
 __device__ __forceinline__ void a9_dir_grad(int deg, float x, float y, float z, const float s[16], float g[3]) {
     float db[16][3];
     dvs_sh_basis_grad(deg, x, y, z, db);
@@ -703,8 +703,10 @@ k_preprocess_bwd(int n, const float* __restrict__ pos, const float* __restrict__
 // gradient rows per view. The SH rows are rank-1 in the per-view colour gradient, so this kernel only emits that (dcolor, 12 B per
 // splat and view) and k_sh_grad_combine builds sh0 / shN from it afterwards — on one GPU right away, in data-parallel runs after the
 // all-gather of dcolor (the factorised exchange), with the same kernel. Per view the same expressions in the same order as
-// k_preprocess_bwd, so the geometry gradients of a batch are bit-identical to its views run one by one with opts.accumulate.
-template <bool ACCUM, bool NOHOIST, bool FUSE_SH /*build the SH rows here instead of emitting per-view colour gradients (below)*/>
+// k_preprocess_bwd, so the pos and opacity gradients of a batch are bit-identical to its views run one by one with opts.accumulate.
+// The scale and rot gradients are not: a9_sigma_to_params runs once on dL/dSigma summed over the views (contraction allowed there), not
+// once per view — equal to fp32 roundoff.
+template <bool ACCUM, bool FUSE_SH /*build the SH rows here instead of emitting per-view colour gradients (below)*/>
 __global__ void __launch_bounds__(PP_BLOCK) __attribute__((amdgpu_waves_per_eu(2, 2)))
 k_preprocess_bwd_views(DvsCams cams_arg /* MUST stay the first parameter: read through dvs_load_cam() */, int n_views, int n,
                        const float* __restrict__ pos, const float* __restrict__ shN, const float* __restrict__ opacity,
@@ -773,16 +775,12 @@ k_preprocess_bwd_views(DvsCams cams_arg /* MUST stay the first parameter: read t
             n0 = grad_rows[3 * on]; n1 = grad_rows[3 * on + 1]; n2 = grad_rows[3 * on + 2];
             nfl = flags[on];
         }
-        // NOHOIST: keep the view-independent intermediates (exp of the scales, rotation, 3D covariance) from being hoisted out of the
-        // loop — they are cheap to recompute and would otherwise stay live across it
-        float s0_ = in_s0, s1_ = in_s1, s2_ = in_s2, q0_ = in_q.x, q1_ = in_q.y, q2_ = in_q.z, q3_ = in_q.w, op_ = in_op;
-        if (NOHOIST) asm volatile("" : "+v"(s0_), "+v"(s1_), "+v"(s2_), "+v"(q0_), "+v"(q1_), "+v"(q2_), "+v"(q3_), "+v"(op_));
         float gcol[3] = {0.f, 0.f, 0.f};
         if ((vis >> view) & 1u) {
             if (rezero) { grad_rows[3 * o] = z4; grad_rows[3 * o + 1] = z4; grad_rows[3 * o + 2] = z4; }
             float gpv[3] = {0.f, 0.f, 0.f}, g_opv;
             float2 dmv;
-            a9_geometry(cam, px, py, pz, s0_, s1_, s2_, make_float4(q0_, q1_, q2_, q3_), op_, fl, r0, r1, antialias, grad_mode, gpv, Gs, g_opv, dmv);
+            a9_geometry(cam, px, py, pz, in_s0, in_s1, in_s2, in_q, in_op, fl, r0, r1, antialias, grad_mode, gpv, Gs, g_opv, dmv);
             const float dL_dcol[3] = {r1.z, r1.w, r2.x};
             // colour -> view direction (the SH rows themselves: k_sh_grad_combine)
             const float dxw = px - cam.campos[0], dyw = py - cam.campos[1], dzw = pz - cam.campos[2];
@@ -1089,16 +1087,11 @@ hipError_t dvs_launch_preprocess_bwd_views(hipStream_t st, int n, int n_views, c
     const int grid = (i1 - i0 + PP_BLOCK - 1) / PP_BLOCK;
     const bool fuse = g_sh0 && g_shN;               // the SH rows are built in the kernel's epilogue; out_dcolor is not written
     const size_t lds = (size_t)PP_BLOCK * (6 + (fuse ? 6 * n_views : 0)) * sizeof(float);
-#ifdef DVS_EXPERIMENT
-    static const bool nohoist = getenv("DVS_A9V_NOHOIST") && getenv("DVS_A9V_NOHOIST")[0] == '1';      // experiment builds only
-#else
-    constexpr bool nohoist = false;
-#endif
-#define DVS_PPV1(A, N, F)                                                                                                        \
-    hipLaunchKernelGGL((k_preprocess_bwd_views<A, N, F>), dim3(grid), dim3(PP_BLOCK), lds, st, cams, n_views, n, pos, shN, opacity, scale, rot, \
+#define DVS_PPV1(A, F)                                                                                                        \
+    hipLaunchKernelGGL((k_preprocess_bwd_views<A, F>), dim3(grid), dim3(PP_BLOCK), lds, st, cams, n_views, n, pos, shN, opacity, scale, rot, \
                        deg, antialias, radii, flags, (float4*)grad_rows, g_pos, g_opacity, g_scale, g_rot,                         \
                        (float2*)out_absgrad2d, (float2*)out_mean2d, out_dcolor, g_sh0, g_shN, rezero, grad_mode, i0, i1)
-#define DVS_PPV(A) do { if (fuse) DVS_PPV1(A, false, true); else if (nohoist) DVS_PPV1(A, true, false); else DVS_PPV1(A, false, false); } while (0)
+#define DVS_PPV(A) do { if (fuse) DVS_PPV1(A, true); else DVS_PPV1(A, false); } while (0)
     if (accumulate) DVS_PPV(true); else DVS_PPV(false);
 #undef DVS_PPV
 #undef DVS_PPV1

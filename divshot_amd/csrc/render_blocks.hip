@@ -1,6 +1,6 @@
-// render_blocks.hip — A7 / A8 with per-4x4-block splat lists. The A8 kernel here was the default composite backward of round 2 (variant
-// "blocks"; round 3's default, render_tr.hip, keeps its lists and tables and replaces its per-step reduction); the A7 kernel is a
-// measured experiment (not faster than render.hip's, see the end of this header).
+// render_blocks.hip — A8 with per-4x4-block splat lists. The kernel here was the default composite backward of round 2 (variant
+// "blocks"; round 3's default, render_tr.hip, keeps its lists and tables and replaces its per-step reduction) and is kept as the
+// parity tests' cross-check with a different summation order.
 //
 // The round-1 composite kernels walk, per 8x8 quadrant (= one wave), every splat whose alpha >= 1/255 ellipse reaches the quadrant;
 // on the bench scene a visit has 21 of 64 lanes contributing (a footprint of ~40 px inside the tile against a 64-px quadrant), and
@@ -9,8 +9,7 @@
 // tile's sixteen blocks and the survivors are compacted, by ballot + mbcnt, into sixteen per-block index lists. A wave still owns an
 // 8x8 quadrant, but its 64 lanes form FOUR interleaved groups of 16 (group = lane & 3 = one 4x4 block) and every group walks its own
 // list with its own cursor: in one iteration the four groups evaluate four different splats. A wave needs max(list length of its
-// four blocks) iterations instead of one per quadrant visit (0.74x the iterations at 44 % lane utilisation with batches of 64), and
-// the scalar bit-walk of the round-1 forward is gone (the cursor is a vector register).
+// four blocks) iterations instead of one per quadrant visit (0.74x the iterations at 44 % lane utilisation with batches of 64).
 //
 // Backward: the 12 per-pixel partials are still reduced across lanes, but only over a group (lanes with equal lane & 3): the two
 // packing swaps (v_permlane32_swap, v_permlane16_swap) fold the four 16-lane rows, two ds_swizzle steps (xor 4, xor 8) finish —
@@ -24,28 +23,19 @@
 // Batches of 64 entries keep the tables at 12 KB (8 workgroups per CU; with 128 the kernel loses 30 % to occupancy).
 //
 // Same inputs, same 48-B row contract (moments about the mean), same alpha rule and thresholds as render.hip; selected by
-// dvs_set_backward_variant / dvs_set_forward_variant (DVS_*_BLOCKS). Reference anchors as in render.hip.
+// dvs_set_backward_variant (DVS_BWD_BLOCKS). Reference anchors as in render.hip.
 //
 // MEASURED (C3, 1 MI355X, profiles/r02_variants.md):
 //   backward 0.46-0.48 ms per view against 0.51 ms (round-1 kernel, same box); inside the 8-view launch 3.35 vs 3.90 ms.
 //            Earlier forms of the merge: ds_add_f32 into one table per tile 0.83 ms (the LDS float atomic costs ~12 cycles per
 //            active lane, tools/ubench/lds_atomic.hip: the LDS was busy 100 % of the kernel); global atomics per group 1.60 ms.
 //            Ranking the sixteen lists by length per batch and dealing them to the waves in that order: -1.3 % instructions only.
-//   forward  0.22 ms vs 0.18 ms: fewer iterations, but 39 instead of 28 vector instructions per iteration (per-lane cursor and
-//            addresses) plus the sixteen block tests and the list compaction per staged entry (+25 M instructions): same total.
-#include <cstdlib>
+//            A per-block forward on the same lists measured 0.22 ms against 0.18 ms for render.hip's and was removed.
 #include "dvs_device.h"
 #include "dvs_kernels.h"
 #include "render_common.h"
 
-#ifndef BK_RB
 #define BK_RB 64                        // list entries staged per batch (the four per-wave tables of A8 take 4 x BK_RB x 48 B)
-#endif
-#ifndef BK_STAGE_NT
-// A8 staging threads. RB: four threads per entry, four blocks each. BK_RB: one thread per entry (the per-entry set-up is not repeated:
-// 40 % fewer staging instructions), but the staging phase then runs in ONE wave — measured 1 % slower end to end (1185 vs 1195 views/s).
-#define BK_STAGE_NT RB
-#endif
 #define BK_SW (BK_RB / 64)              // staging waves per block subset
 
 struct __attribute__((aligned(16))) BlockLds {
@@ -58,15 +48,17 @@ struct __attribute__((aligned(16))) BlockLds {
     uint32_t wcnt[BK_SW][16];     // per staging wave
 };
 
-// Stage entries [first, first + cnt) and build the sixteen block lists. Thread t handles entry t % BK_RB and the blocks
-// [BK_GPT * (t / BK_RB), +BK_GPT). `blast` (backward only): per block the deepest contributor of any of its pixels — entries at or
-// beyond it can never contribute there and are left out of that block's list.
-template <bool USE_LAST, int NT /*staging threads: RB, or BK_RB = one per entry (no per-entry set-up repeated by several threads)*/>
+// Stage entries [first, first + cnt) and build the sixteen block lists. All RB threads stage: thread t handles entry t % BK_RB and the
+// blocks [GPT * (t / BK_RB), +GPT), i.e. four threads per entry, one block row each. (One thread per entry repeats no per-entry set-up
+// — 40 % fewer staging instructions — but runs the staging phase in ONE wave: measured 1 % slower end to end, 1185 vs 1195 views/s.)
+// `blast`: per block the deepest contributor of any of its pixels — entries at or beyond it can never contribute there and are left
+// out of that block's list.
 __device__ __forceinline__ void stage_blocks(BlockLds& L, const uint32_t* __restrict__ sorted_splat, uint32_t first, int cnt, int base,
                                              const float4* __restrict__ splat2d, float tile_x0, float tile_y0, const uint32_t* blast) {
-    constexpr int GPT = 16 * BK_RB / NT, ROWS = GPT / 4;        // blocks / block rows per staging thread
+    constexpr int GPT = 16 * BK_RB / RB, ROWS = GPT / 4;        // blocks / block rows per staging thread
     const int t = threadIdx.x, e = t % BK_RB, sub = t / BK_RB, lane = t & 63, ws = e >> 6;
-    const bool stager = t < NT;
+    const bool stager = t < RB;           // every thread of the workgroup; the tests below are kept because the compiler schedules
+                                          // k_render_bwd_blocks differently without them, and this kernel is a fixed cross-check
     uint32_t hits = 0;                    // bit i: block GPT * sub + i
     if (stager && e < cnt) {
         const uint32_t id = sorted_splat[first + e];
@@ -118,24 +110,12 @@ __device__ __forceinline__ void stage_blocks(BlockLds& L, const uint32_t* __rest
             const float ev = __builtin_fmaf(c * ty_, ty_, vbase[col]), eh = __builtin_fmaf(a * tx_, tx_, hbase[r]);
             const float qm = (vin[col] && hin[r]) ? 0.f : fminf(ev, eh);
             bool h = !(qm > bound);                                       // NaN-safe: a failed comparison keeps the entry
-            if (USE_LAST) h = h && ((uint32_t)(base + e) < blast[GPT * sub + i]);
+            h = h && ((uint32_t)(base + e) < blast[GPT * sub + i]);
             hits |= h ? (1u << i) : 0u;
         }
     }
-    if (NT == 64 && BK_RB == 64) {        // one staging wave: ranks and list lengths come straight from its ballots, no second phase
-        if (stager) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const uint64_t m = __ballot((hits >> i) & 1u);
-                const uint32_t rk = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                if ((hits >> i) & 1u) L.list[i][rk] = (uint8_t)e;
-                if (lane == 0) L.cnt[i] = (uint32_t)__popcll(m);
-            }
-        }
-        return;                           // (the caller's barrier publishes the lists)
-    }
     uint32_t rank[GPT];
-    if (stager) {                         // (whole waves: NT is a multiple of 64)
+    if (stager) {
 #pragma unroll
         for (int i = 0; i < GPT; ++i) {
             const uint64_t m = __ballot((hits >> i) & 1u);
@@ -172,78 +152,14 @@ __device__ __forceinline__ int wave_max4(int v) {
     return max(max(a, b), max(c, d));
 }
 
-// (the per-block forward is an experiment of round 2 — same image bits as k_render_fwd, not faster: experiment builds only)
-#ifdef DVS_EXPERIMENT
-// ---- A7 -------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(RB)
-k_render_fwd_blocks(int W, int H, int tiles_x, int num_tiles, const uint2* __restrict__ ranges,
-                    const uint32_t* __restrict__ sorted_splat, const float4* __restrict__ splat2d, float bg0, float bg1, float bg2,
-                    float* __restrict__ out_color, float* __restrict__ final_T, uint32_t* __restrict__ n_contrib) {
-    __shared__ BlockLds L;
-    const int tile = tile_of_block(blockIdx.x, num_tiles);
-    if (tile >= num_tiles) return;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int block, lx, ly;
-    lane_pixel(wave, lane, block, lx, ly);
-    const int px = tx * DVS_TILE + lx, py = ty * DVS_TILE + ly;
-    const bool inside = px < W && py < H;
-    const float pxf = (float)px, pyf = (float)py;
-    const uint2 range = ranges[tile];
-    const int total = (int)(range.y - range.x);
-    bool done = !inside;
-    float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
-    uint32_t last = 0;
-    const uint8_t* lp = &L.list[block][0];
-
-    for (int base = 0; base < total; base += BK_RB) {
-        if (__syncthreads_and(done)) break;
-        const int cnt = min(BK_RB, total - base);
-        stage_blocks<false, RB>(L, sorted_splat, range.x + base, cnt, base, splat2d, (float)(tx * DVS_TILE), (float)(ty * DVS_TILE), nullptr);
-        __syncthreads();
-        if (__all(done)) continue;
-        const int len = (int)L.cnt[block];
-        const int nmax = wave_max4(len);
-        int jn = len > 0 ? (int)lp[0] : 0;
-#pragma unroll 1
-        for (int it = 0; it < nmax; ++it) {
-            const bool act = it < len;
-            const int j = jn;
-            jn = it + 1 < len ? (int)lp[it + 1] : 0;                       // next cursor value, requested one iteration ahead
-            const float4 xy = L.xyc[j];
-            const float4 zo = L.zoir[j];
-            const float dx = xy.x - pxf, dy = xy.y - pyf;
-            const float p2 = __builtin_fmaf(zo.x * dy, dy, __builtin_fmaf(xy.w, dy, xy.z * dx) * dx);
-            const float alpha = fminf(DVS_ALPHA_MAX, zo.y * __builtin_amdgcn_exp2f(p2));
-            const bool valid = act && !done && !(p2 > 0.f) && !(alpha < DVS_ALPHA_MIN);
-            const float aT = alpha * T;
-            const float test_T = T - aT;
-            const bool stop = valid && (test_T < DVS_T_STOP);
-            const bool take = valid && !stop;
-            done = done || stop;
-            const float w = take ? aT : 0.f;
-            C0 = __builtin_fmaf(zo.w, w, C0); C1 = __builtin_fmaf(L.cog[j].w, w, C1); C2 = __builtin_fmaf(zo.z, w, C2);
-            T = T - w;
-            last = take ? (uint32_t)(base + j + 1) : last;
-            if ((it & 15) == 15 && __all(done)) break;
-        }
-    }
-    if (inside) {
-        const size_t P = (size_t)W * H, pix = (size_t)py * W + px;
-        final_T[pix] = T;
-        n_contrib[pix] = last;
-        out_color[pix] = C0 + T * bg0;
-        out_color[P + pix] = C1 + T * bg1;
-        out_color[2 * P + pix] = C2 + T * bg2;
-    }
-}
-
 // ---- A8 -------------------------------------------------------------------------------------------
-// 12 per-lane partials -> per-GROUP totals (group = lanes with equal lane & 3). As wave_reduce12 (render_common.h) but the
-// butterfly stops after the column bits 2 and 3: q[k] holds, in lane (row r, column c), the total over the lanes of group c & 3 of
+// 12 per-lane partials -> per-GROUP totals (group = lanes with equal lane & 3). NV = number of live values (11 with abs-grad, 9
+// without). Two halving steps with the gfx950 swap instructions fold the four 16-lane rows while packing 4 values per register
+// (v_permlane32_swap: lanes 32-63 of A <-> lanes 0-31 of B; v_permlane16_swap: odd 16-lane rows of A <-> even rows of B); the odd
+// value out has no partner to be packed with and is folded across the two wave halves with ds_bpermute_b32 (`xaddr` = (lane ^ 32) * 4)
+// + one v_add instead. Two ds_swizzle butterfly steps (LDS crossbar, no LDS memory) over the column bits 2 and 3 finish: q[k] holds,
+// in lane (row r, column c), the total over the lanes of group c & 3 of
 // value index  q[0]: v0,v2,v1,v3   q[1]: v4,v6,v5,v7   q[2]: v8,v10,v9,v11  (by row r).
-#endif  // DVS_EXPERIMENT
-
 template <int NV>
 __device__ __forceinline__ void group_reduce12(const float v[12], float q[3], int xaddr) {
     const float h0 = swap32_add(v[0], v[1]), h1 = swap32_add(v[2], v[3]), h2 = swap32_add(v[4], v[5]);
@@ -272,7 +188,7 @@ k_render_bwd_blocks(ViewBg bg_arg /* MUST stay the first parameter: read through
                     int num_tiles /* = views * tiles_per_view */, const uint2* __restrict__ ranges,
                     const uint32_t* __restrict__ sorted_splat, const float4* __restrict__ splat2d,
                     const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dout /*[views,3,H,W]*/,
-                    float* __restrict__ grow /*[n,12], same row contract as k_render_bwd*/, int lineage) {
+                    float* __restrict__ grow /*[n,12], same row contract as k_render_bwd_tr*/, int lineage) {
     __shared__ BlockLds L;
     __shared__ float s_tab[4][BK_RB * 12];                  // per wave and batch entry: the 12-float row, summed over the wave's blocks
     __shared__ uint32_t s_blast[16];
@@ -319,14 +235,14 @@ k_render_bwd_blocks(ViewBg bg_arg /* MUST stay the first parameter: read through
     if (todo == 0) return;
 
     float T = T_final;
-    float D = T_final * bg_dot;          // see k_render_bwd: one scalar of "colour behind" state suffices
+    float D = T_final * bg_dot;          // see k_render_bwd_tr: one scalar of "colour behind" state suffices
     const uint8_t* lp = &L.list[block][0];
     const int nbatch = (int)((todo + BK_RB - 1) / BK_RB);
     for (int b = nbatch - 1; b >= 0; --b) {
         const int base = b * BK_RB;
         const int cnt = min(BK_RB, (int)todo - base);
         __syncthreads();                                    // previous batch published and consumed
-        stage_blocks<true, BK_STAGE_NT>(L, sorted_splat, range.x + base, cnt, base, splat2d, (float)(tx * DVS_TILE), (float)(ty * DVS_TILE), s_blast);
+        stage_blocks(L, sorted_splat, range.x + base, cnt, base, splat2d, (float)(tx * DVS_TILE), (float)(ty * DVS_TILE), s_blast);
         __syncthreads();
         const int len = (int)L.cnt[block];
         const int nmax = __builtin_amdgcn_readfirstlane(wave_max4(len));
@@ -400,19 +316,6 @@ k_render_bwd_blocks(ViewBg bg_arg /* MUST stay the first parameter: read through
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------
-#ifdef DVS_EXPERIMENT
-hipError_t dvs_launch_render_fwd_blocks(hipStream_t st, int W, int H, int tiles_x, int tiles_y, const uint32_t* ranges,
-                                        const uint32_t* sorted_splat, const float* splat2d, const float bg[3], float* out_color,
-                                        float* final_T, uint32_t* n_contrib) {
-    const int num_tiles = tiles_x * tiles_y;
-    if (num_tiles <= 0) return hipSuccess;
-    const int grid = ((num_tiles + 7) >> 3) << 3;
-    hipLaunchKernelGGL(k_render_fwd_blocks, dim3(grid), dim3(RB), 0, st, W, H, tiles_x, num_tiles, (const uint2*)ranges, sorted_splat,
-                       (const float4*)splat2d, bg[0], bg[1], bg[2], out_color, final_T, n_contrib);
-    return hipGetLastError();
-}
-#endif  // DVS_EXPERIMENT
-
 hipError_t dvs_launch_render_bwd_blocks(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, const uint32_t* ranges,
                                         const uint32_t* sorted_splat, const float* splat2d, const float* bgs, const float* final_T,
                                         const uint32_t* n_contrib, const float* dL_dout, float* grad_rows, int absgrad, int grad_mode) {
@@ -420,9 +323,8 @@ hipError_t dvs_launch_render_bwd_blocks(hipStream_t st, int W, int H, int tiles_
     if (num_tiles <= 0) return hipSuccess;
     const int grid = ((num_tiles + 7) >> 3) << 3;
     const int lineage = grad_mode == 1 ? 1 : 0;
-    const size_t extra_lds = dvs_experiment_extra_lds();
-#define DVS_RBB(KERNEL)                                                                                                             \
-    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(RB), extra_lds, st, make_view_bg(n_views, bgs), W, H, tiles_x, tiles_pv, num_tiles, \
+#define DVS_RBB(KERNEL)                                                                                                     \
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(RB), 0, st, make_view_bg(n_views, bgs), W, H, tiles_x, tiles_pv, num_tiles, \
                        (const uint2*)ranges, sorted_splat, (const float4*)splat2d, final_T, n_contrib, dL_dout, grad_rows, lineage)
     if (absgrad) DVS_RBB(k_render_bwd_blocks<true>); else DVS_RBB(k_render_bwd_blocks<false>);
 #undef DVS_RBB

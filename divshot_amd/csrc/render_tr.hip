@@ -29,9 +29,6 @@
 // Same inputs and the same 48-B row contract (moments about the mean, see dvs_get_bwd_intermediates) as the other A8 kernels; the
 // opacity factor of the moment / abs-grad sums is applied once per (tile, splat) when the tables are published.
 // Reference anchors as in render.hip (alpha rule gsplat_ps.hlsl:60-65, 16x16 groups gaussian_common.hlsl:162-163, abs-grad main.cpp:44).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include "dvs_device.h"
 #include "dvs_kernels.h"
 #include "render_common.h"
@@ -39,16 +36,13 @@
 #define TR_SLOTS 4
 #define TR_SS 136          // floats per slot of the transposition buffer: two planes of 64 + 8 pad — with the phase-2 lane map below the
                            // ds_read_b128 of a wave hit 16 distinct 16-B bank groups per service group (brute-forced over the gfx950 lane groups)
-#ifndef TR_SKIP_EMPTY_STEPS
-#define TR_SKIP_EMPTY_STEPS 0      // a step in which no lane contributes could skip its second half — measured: 450 of 2.78 M steps per C3 view
-#endif                             // (the block test + per-block deepest contributor leave no empty steps); the branch only splits the schedule
+// (A step in which no lane contributes could skip its second half — measured: 450 of 2.78 M steps per C3 view: the block test + per-block
+// deepest contributor leave no empty steps, and the branch only splits the schedule. Not done.)
 // (Round 4 measured two more variants of this kernel and dropped them — the next batch's records touched ahead of their gather, and an
 // owner byte per table row that lets conflict-free pairs update in one pass (code in the history at commit cb18e80) — and a wave-autonomous
 // form of the whole kernel, one wave per workgroup without any workgroup barrier (commit 7484d16; 25 % slower): DESIGN.md section 5.3,
 // profiles/r04_a8_variants_ab.txt, r04_a8_autonomous_ab.txt.)
-#ifndef TR_MINW
 #define TR_MINW 6          // waves per SIMD the kernel is compiled for (register cap 80; the LDS footprint allows six workgroups per CU)
-#endif
 
 template <int BK>
 struct __attribute__((aligned(16))) TrLds {
@@ -60,9 +54,6 @@ struct __attribute__((aligned(16))) TrLds {
     uint8_t list[(BK + 1) * 16];  // element k (1-based, list order) of block b at k * 16 + b; row 0 = sentinels (BK)
     uint32_t cnt[16];             // list lengths
     uint32_t blast[16];           // per block: deepest contributor of any of its pixels
-#ifdef TR_STATS
-    uint32_t live[BK];            // entry reaches at least one block
-#endif
 };
 
 // The gather of a batch: splat ids (requested before the previous batch is published, so that round trip runs under the publish), then
@@ -78,8 +69,7 @@ __device__ __forceinline__ uint32_t tr_load_id(const uint32_t* __restrict__ sort
 // holding one block sit in one wave (BK = 64) or one half wave (BK = 32), so ranks and lengths come straight from that wave's ballots.
 template <int BK>
 __device__ __forceinline__ void tr_stage(TrLds<BK>& L, const float4* __restrict__ splat2d, uint32_t id, int cnt, int base, int parity,
-                                         float tile_x0, float tile_y0 DVS_DBG_PARAM) {
-    const int dbg = DVS_DBG_VALUE;
+                                         float tile_x0, float tile_y0) {
     constexpr int GPT = 16 * BK / RB;
     static_assert(GPT == 4 || GPT == 2, "BK must be 64 or 32");
     const int t = threadIdx.x, e = t % BK, sub = t / BK, lane = t & 63;
@@ -102,8 +92,6 @@ __device__ __forceinline__ void tr_stage(TrLds<BK>& L, const float4* __restrict_
         const bool hin = y0 <= 0.f && y1 >= 0.f;
         const float ye = y0 > 0.f ? y0 : y1;
         const float hx = nb_a * ye, hbase = hin ? __builtin_inff() : ye * ye * det_a;
-        if (dbg & 16384) hits = 0xFu;                       // timing only (with dbg 8: no list loop): staging without the ellipse-vs-block tests
-        else
 #pragma unroll
         for (int i = 0; i < GPT; ++i) {
             const float x0 = ox + 4.f * (float)i, x1 = x0 + 3.f;
@@ -132,31 +120,24 @@ __device__ __forceinline__ void tr_stage(TrLds<BK>& L, const float4* __restrict_
             rk = up ? __builtin_amdgcn_mbcnt_hi(hi, 0u) : __builtin_amdgcn_mbcnt_lo(lo, 0u);
             len = (uint32_t)__popc(up ? hi : lo);
         }
-#ifdef TR_STATS
-        if (i == 0 && hits) atomicOr(&L.live[e], 1u);
-#endif
         if (hit) L.list[(rk + 1u) * 16u + (uint32_t)(b0 + i)] = (uint8_t)e;
         if (e == 0) L.cnt[b0 + i] = len;
     }
 }
 
-#ifdef TR_STATS
-__device__ unsigned long long tr_stats[8];
-#endif
 template <bool ABSGRAD, bool LINEAGE, int BK>
 __global__ void __launch_bounds__(RB, TR_MINW)
 k_render_bwd_tr(ViewBg bg_arg /* MUST stay the first parameter: read through dvs_load_bg() */, int W, int H, int tiles_x, int tiles_per_view,
                 int num_tiles /* = views * tiles_per_view */, const uint2* __restrict__ ranges,
                 const uint32_t* __restrict__ sorted_splat, const float4* __restrict__ splat2d,
                 const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dout /*[views,3,H,W]*/,
-                float* __restrict__ grow /*[n,12], same row contract as k_render_bwd*/ DVS_DBG_PARAM,
+                float* __restrict__ grow /*[n,12]: Sx Sy Sxx Sxy Syy So r g b |mx| |my| pad (moments about the mean)*/,
                 const uint32_t* __restrict__ live_splat /*k_render_fwd's compacted lists (entries that reach the tile), or null*/,
                 const uint32_t* __restrict__ live_pos /*list position -> position in the compacted list*/) {
     __shared__ TrLds<BK> L;
     __shared__ __attribute__((aligned(16))) float s_tab[4][(BK + 1) * 12];   // per wave and batch entry: the 12-float row; row BK = sink of the dummy entry
     __shared__ __attribute__((aligned(16))) float s_tb[4][TR_SLOTS * TR_SS];  // per wave: slot, plane (v5 | w), phase-1 lane
     (void)bg_arg;
-    const int dbg = DVS_DBG_VALUE;                          // release builds: 0, every `dbg &` test below folds away
     const int tile_g = tile_of_block(blockIdx.x, num_tiles);
     if (tile_g >= num_tiles) return;
     const int view = tile_g / tiles_per_view, tile = tile_g - view * tiles_per_view;
@@ -219,18 +200,18 @@ k_render_bwd_tr(ViewBg bg_arg /* MUST stay the first parameter: read through dvs
     if (pi == 0) L.blast[blk1] = bmax;
     for (int e = threadIdx.x; e < (BK + 1) * 12; e += RB) reinterpret_cast<float4*>(&s_tab[0][0])[e] = make_float4(0.f, 0.f, 0.f, 0.f);      // (4 tables x (BK + 1) x 12 floats = (BK + 1) x 12 16-B words)
     if (threadIdx.x < 16) L.list[threadIdx.x] = (uint8_t)BK;
-#ifdef TR_STATS
-    if (threadIdx.x < BK) L.live[threadIdx.x] = 0u;
-#endif
     if (threadIdx.x == 0) { L.ea[BK] = make_float4(0.f, 0.f, 0.f, 0.f); L.eb[BK] = make_float4(0.f, 0.f, 0.f, 0.f); L.ec[BK] = make_float4(0.f, 0.f, 0.f, 0.f); }
     __syncthreads();
     uint32_t todo = 0;
 #pragma unroll
     for (int g = 0; g < 16; ++g) todo = max(todo, L.blast[g]);
-    if (todo == 0 || (dbg & 64)) return;
+    if (todo == 0) return;
 
+    // Back-to-front state per pixel: T = transmittance in front of the current splat, and ONE scalar
+    // D = sum over the splats behind of (c_k . dL/dC) alpha_k T_k + T_final (bg . dL/dC): because the upstream pixel
+    // gradient is constant along the list, dL/dalpha_j = (c_j . dL/dC) T_j - D / (1 - alpha_j) needs no per-channel state.
     float T = T_final;
-    float D = T_final * bg_dot;          // see k_render_bwd: one scalar of "colour behind" state suffices
+    float D = T_final * bg_dot;
     const uint32_t tb_m0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)&s_tb[wave][0]);   // LDS byte offset of the wave's buffer (low half of the flat address), wave-uniform:
                                                                           // phase 1 writes (v5, w) of slot s, lane l at floats [TR_SS s + l], [TR_SS s + 64 + l]
     // LDS byte addresses kept as opaque 32-bit values (the low half of a flat LDS address is the LDS offset): the compiler otherwise
@@ -245,7 +226,6 @@ k_render_bwd_tr(ViewBg bg_arg /* MUST stay the first parameter: read through dvs
 
     // phase 2: the wave's TR_SLOTS x 4 (slot, block) pairs, four lanes (pixel rows) per pair
     auto flush = [&](uint32_t jpack) {
-        if (dbg & 4) return;
         const uint32_t jp = (uint32_t)__builtin_amdgcn_ds_bpermute(jaddr, (int)jpack);
         const int j = (int)((jp >> jshift) & 0xffu);
         const tr_v4f V_ = *(lds_cv4f*)tbr_a, W_ = *(lds_cv4f*)(tbr_a + 256u);
@@ -255,21 +235,6 @@ k_render_bwd_tr(ViewBg bg_arg /* MUST stay the first parameter: read through dvs
         asm("" : : "v"(cq.x));                                            // (keeps the read ONE ds_read_b128: without a use of .x it is split into
                                                                           //  two reads whose offsets need an extra address add)
         const float Dx = mean.x - X0f, Dy = mean.y - Y0f;                 // d = mean - pixel for the row's first pixel; pixel x: Dx - x
-        if (dbg & 1024) {                                                 // timing only: a round without its arithmetic (what a matrix-pipe version could at best save)
-            const float h0 = swap32_add(V.x, V.y), h1 = swap32_add(V.z, V.w), h2 = swap32_add(Wv.x, Wv.y), h3 = swap32_add(Wv.z, Wv.w);
-            const float h4 = swap32_add(Dx, Dy), h5 = Dx + __int_as_float(__builtin_amdgcn_ds_bpermute(xaddr, __float_as_int(Dy)));
-            const float q0 = swap16_add(h0, h1), q1 = swap16_add(h2, h3), q2 = swap16_add(h4, h5);
-            uint32_t slot_a;
-            asm("v_mad_u32_u24 %0, %1, 48, %2" : "=v"(slot_a) : "v"(j), "v"(tabw_a));
-            lds_float* const slot = (lds_float*)slot_a;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                if (g2 == g) { slot[0] += q0; slot[4] += q1; slot[8] += q2; }
-                __builtin_amdgcn_wave_barrier();
-                asm volatile("" ::: "memory");
-            }
-            return;
-        }
         const float A0 = (V.x + V.y) + (V.z + V.w);
         const float B0 = __builtin_fmaf(3.f, V.w, __builtin_fmaf(2.f, V.z, V.y));
         const float C0 = __builtin_fmaf(9.f, V.w, __builtin_fmaf(4.f, V.z, V.y));
@@ -294,10 +259,6 @@ k_render_bwd_tr(ViewBg bg_arg /* MUST stay the first parameter: read through dvs
         v[11] = 0.f;
         // fold the four pixel rows (the four 16-lane rows of the wave) with the packing swaps: afterwards row r holds, in q[k], the
         // total of value 4 k + perm(r) of its (block, slot) pair
-        float q0, q1, q2;
-        if (dbg & 4096) {                                                 // timing only: the round without its packing swaps
-            q0 = (v[0] + v[1]) + (v[2] + v[3]); q1 = (v[4] + v[5]) + (v[6] + v[7]); q2 = (v[8] + v[9]) + v[10];
-        } else {
         const float h0 = swap32_add(v[0], v[1]), h1 = swap32_add(v[2], v[3]), h2 = swap32_add(v[4], v[5]);
         const float h3 = swap32_add(v[6], v[7]);
         float h4, h5;
@@ -308,15 +269,12 @@ k_render_bwd_tr(ViewBg bg_arg /* MUST stay the first parameter: read through dvs
             h4 = v[8] + __int_as_float(__builtin_amdgcn_ds_bpermute(xaddr, __float_as_int(v[8])));
             h5 = 0.f;
         }
-        q0 = swap16_add(h0, h1); q1 = swap16_add(h2, h3); q2 = swap16_add(h4, h5);
-        }
+        const float q0 = swap16_add(h0, h1), q1 = swap16_add(h2, h3), q2 = swap16_add(h4, h5);
         // one block group at a time: two groups may hold the same entry (measured: in nearly every round); LDS operations of one wave
         // execute in order, so a later group sees an earlier group's write
         uint32_t slot_a;                                                  // = tabw_a + 48 j
         asm("v_mad_u32_u24 %0, %1, 48, %2" : "=v"(slot_a) : "v"(j), "v"(tabw_a));
         lds_float* const slot = (lds_float*)slot_a;
-        if (dbg & 2048) { asm volatile("" : : "v"(q0), "v"(q1), "v"(q2), "v"(slot_a)); return; }     // timing only: no table update
-        if (dbg & 8192) { slot[0] += q0; slot[4] += q1; slot[8] += q2; return; }                      // timing only: ONE read-add-write for all four groups (conflicts ignored)
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             if (g2 == g) { slot[0] += q0; slot[4] += q1; slot[8] += q2; }
@@ -332,33 +290,13 @@ k_render_bwd_tr(ViewBg bg_arg /* MUST stay the first parameter: read through dvs
         const int base = b * BK;
         const int cnt = min(BK, (int)todo - base);
         // (no barrier here: the publish of batch b + 1, which other threads may still be in, reads the tables and idop[(b + 1) & 1] only)
-        tr_stage<BK>(L, splat2d, id_stage, cnt, base, b & 1, tile_x0, tile_y0 DVS_DBG_PASS(dbg));
-        if (!(dbg & 256)) __syncthreads();                  // batch staged; the tables are zero again        (dbg 256: timing of a barrier-free batch loop — wrong results)
+        tr_stage<BK>(L, splat2d, id_stage, cnt, base, b & 1, tile_x0, tile_y0);
+        __syncthreads();                                    // batch staged; the tables are zero again
         const int len = (int)L.cnt[blk1];
         int nmax = len;
         nmax = max(nmax, __shfl_xor(nmax, 16, 64));
         nmax = max(nmax, __shfl_xor(nmax, 32, 64));
         nmax = __builtin_amdgcn_readfirstlane(nmax);
-#ifdef TR_STATS                                             // tools/xbuild.sh stats -DTR_STATS: step / imbalance counters of a launch on stderr
-        if (threadIdx.x == 0) {
-            uint32_t sum = 0, wmx = 0, wsum = 0;
-            for (int w = 0; w < 4; ++w) {                   // wave w owns the blocks (2 (w & 1) + {0, 1}, 2 (w >> 1) + {0, 1})
-                uint32_t m = 0;
-                for (int g = 0; g < 4; ++g) { const uint32_t c = L.cnt[(2 * (w >> 1) + (g >> 1)) * 4 + 2 * (w & 1) + (g & 1)]; m = max(m, c); sum += c; }
-                wmx = max(wmx, m); wsum += m;
-            }
-            atomicAdd(&tr_stats[0], (unsigned long long)wsum);          // list steps summed over the waves
-            atomicAdd(&tr_stats[1], (unsigned long long)(4 * wmx));     // the same if every wave took as many as the batch's slowest (what the barrier costs)
-            atomicAdd(&tr_stats[2], (unsigned long long)sum);           // (block, entry) pairs
-            atomicAdd(&tr_stats[3], 1ull);                              // batches
-            atomicAdd(&tr_stats[4], (unsigned long long)cnt);           // staged entries
-            uint32_t lv = 0;
-            for (int e2 = 0; e2 < cnt; ++e2) lv += L.live[e2];
-            atomicAdd(&tr_stats[5], (unsigned long long)lv);            // ... that reach at least one block of the tile
-        }
-        __syncthreads();
-        if (threadIdx.x < BK) L.live[threadIdx.x] = 0u;
-#endif
         const int lastb = (int)min(last, (uint32_t)(base + BK)) - base;          // entries of this batch below the pixel's last contributor
         uint32_t p = (uint32_t)len * 16u + (uint32_t)blk1;                         // byte offset of the list's last element
         uint32_t jn = lbase[p];                                                    // (32 bits behind an opaque copy: the compiler narrows the loop
@@ -366,7 +304,7 @@ k_render_bwd_tr(ViewBg bg_arg /* MUST stay the first parameter: read through dvs
         uint32_t jpack = 0;
         int nslot = 0;
 #pragma unroll 1
-        for (int it = 0; it < ((dbg & 8) ? 0 : nmax); ++it) {
+        for (int it = 0; it < nmax; ++it) {
             const int j = (int)jn;
             jpack = (jpack << 8) | (uint32_t)j;                                    // (here: every use of j ahead of the next element's load)
             const bool below_last = j < lastb;
@@ -381,9 +319,6 @@ k_render_bwd_tr(ViewBg bg_arg /* MUST stay the first parameter: read through dvs
             const float oa = eb.y * G;
             const float alpha = fminf(DVS_ALPHA_MAX, oa);
             const bool contrib = below_last && !(p2 > 0.f) && !(alpha < DVS_ALPHA_MIN);
-#if TR_SKIP_EMPTY_STEPS
-            if (__builtin_amdgcn_ballot_w64(contrib) == 0) continue;
-#endif
             const float2 rg = make_float2(eb.z, eb.w);
             const float cb = L.ec[j].x;
             const float al = contrib ? alpha : 0.f;
@@ -402,7 +337,7 @@ k_render_bwd_tr(ViewBg bg_arg /* MUST stay the first parameter: read through dvs
                          : : "v"(v5), "v"(w), "s"(tb_m0 + (uint32_t)(TR_SS * 4) * (uint32_t)nslot) : "memory", "m0");
             if (++nslot == TR_SLOTS) { flush(jpack); nslot = 0; }
         }
-        if (nslot > 0 && !(dbg & 512)) {                    // pad the unfinished round with the dummy entry (zero pairs, sink row)   (dbg 512: timing without the padded rounds — wrong results)
+        if (nslot > 0) {                                    // pad the unfinished round with the dummy entry (zero pairs, sink row)
             for (; nslot < TR_SLOTS; ++nslot) {
                 float* const tbw = &s_tb[wave][lane];
                 tbw[TR_SS * nslot] = 0.f; tbw[TR_SS * nslot + 64] = 0.f;
@@ -410,17 +345,17 @@ k_render_bwd_tr(ViewBg bg_arg /* MUST stay the first parameter: read through dvs
             }
             flush(jpack);
         }
-        if (!(dbg & 256)) __syncthreads();                  // tables complete; nobody reads the staged entries or lists any more
+        __syncthreads();                                    // tables complete; nobody reads the staged entries or lists any more
         if (b > 0) id_stage = tr_load_id<BK>(sorted_splat, range.x + (b - 1) * BK, BK);     // the next batch's ids arrive under the publish
         // the tile's total per touched (entry, value): ONE global atomic each — consecutive threads add consecutive floats of a row.
         // The moment and abs-grad sums were taken over v5 = G dL/dalpha; the row contract wants them over opacity * v5.
-        for (int e = threadIdx.x; e < ((dbg & 128) ? 0 : cnt * 12); e += RB) {
+        for (int e = threadIdx.x; e < cnt * 12; e += RB) {
             const float val = (s_tab[0][e] + s_tab[1][e]) + (s_tab[2][e] + s_tab[3][e]);
             if (val != 0.f) {
                 const int ent = e / 12, comp = e - 12 * ent;
                 const uint2 io = L.idop[b & 1][ent];
                 const float sc = (comp == 5 || (comp >= 6 && comp <= 8)) ? 1.f : __uint_as_float(io.y);
-                if (comp < 11 && !(dbg & 1)) atomicAdd(&grow[(size_t)io.x * 12 + comp], val * sc);
+                if (comp < 11) atomicAdd(&grow[(size_t)io.x * 12 + comp], val * sc);
             }
             s_tab[0][e] = 0.f; s_tab[1][e] = 0.f; s_tab[2][e] = 0.f; s_tab[3][e] = 0.f;
         }
@@ -436,29 +371,15 @@ hipError_t dvs_launch_render_bwd_tr(hipStream_t st, int W, int H, int tiles_x, i
     if (num_tiles <= 0) return hipSuccess;
     const int grid = ((num_tiles + 7) >> 3) << 3;
     const int lineage = grad_mode == 1 ? 1 : 0;
-#ifdef DVS_EXPERIMENT
-    static const int dbg = dvs_experiment_int("DVS_TR_DEBUG");      // ablation bits of tools/bwd_probe.py (timing only; experiment builds)
-#endif
-    const size_t extra_lds = dvs_experiment_extra_lds();
-#define DVS_TR(A, LN, BKV)                                                                                                          \
-    hipLaunchKernelGGL((k_render_bwd_tr<A, LN, BKV>), dim3(grid), dim3(RB), extra_lds, st, make_view_bg(n_views, bgs), W, H, tiles_x, tiles_pv, \
-                       num_tiles, (const uint2*)ranges, sorted_splat, (const float4*)splat2d, final_T, n_contrib, dL_dout, grad_rows DVS_DBG_PASS(dbg), live_splat, live_pos)
+#define DVS_TR(A, LN, BKV)                                                                                                              \
+    hipLaunchKernelGGL((k_render_bwd_tr<A, LN, BKV>), dim3(grid), dim3(RB), 0, st, make_view_bg(n_views, bgs), W, H, tiles_x, tiles_pv, \
+                       num_tiles, (const uint2*)ranges, sorted_splat, (const float4*)splat2d, final_T, n_contrib, dL_dout, grad_rows, live_splat, live_pos)
 #define DVS_TR_B(BKV)                                                                                   \
     do {                                                                                                \
         if (absgrad) { if (lineage) DVS_TR(true, true, BKV); else DVS_TR(true, false, BKV); }           \
         else { if (lineage) DVS_TR(false, true, BKV); else DVS_TR(false, false, BKV); }                 \
     } while (0)
     DVS_TR_B(64);
-#ifdef TR_STATS
-    {
-        unsigned long long h[8];
-        hipStreamSynchronize(st);
-        hipMemcpyFromSymbol(h, HIP_SYMBOL(tr_stats), sizeof(h));
-        fprintf(stderr, "TR_STATS views %d: wave_steps %llu  if_lockstep %llu  block_pairs %llu  batches %llu  entries %llu  live_entries %llu\n", n_views, h[0], h[1], h[2], h[3], h[4], h[5]);
-        memset(h, 0, sizeof(h));
-        hipMemcpyToSymbol(HIP_SYMBOL(tr_stats), h, sizeof(h));
-    }
-#endif
 #undef DVS_TR_B
 #undef DVS_TR
     return hipGetLastError();

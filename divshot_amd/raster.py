@@ -98,12 +98,13 @@ class Rasterizer:
         return self.num_rendered
 
     def set_backward_variant(self, variant):
-        """A8 kernel: 3 / "tr" (default, render_tr.hip), 0 / "blocks" (round 2), 1 / "reduce" (round 1), 2 / "mm" — see dvs_raster.h."""
+        """A8 kernel: 3 / "tr" (default, render_tr.hip), 0 / "blocks" (round 2, the parity tests' cross-check). 1 / "reduce" and 2 / "mm" name
+        retired kernels: they are passed through and the library refuses them (DVS_ERR_UNSUPPORTED) — see dvs_raster.h."""
         v = {"blocks": 0, "reduce": 1, "mm": 2, "tr": 3}.get(variant, variant)
         check(lib.dvs_set_backward_variant(self.ctx, int(v)), "dvs_set_backward_variant")
 
     def set_forward_variant(self, variant):
-        """A7 kernel: 1 / "quadrant" (default), 0 / "blocks" (experiment); bit-identical results."""
+        """A7 kernel: 1 / "quadrant", the only one. 0 / "blocks" names the retired per-block forward: passed through, refused by the library."""
         v = {"blocks": 0, "quadrant": 1}.get(variant, variant)
         check(lib.dvs_set_forward_variant(self.ctx, int(v)), "dvs_set_forward_variant")
 

@@ -300,8 +300,9 @@ int dvs_debug_sort_depth_keys(dvs_ctx* ctx, void* stream, const uint32_t* keys, 
 
 /* The library ships ONE composite forward (A7, "quadrant") and ONE composite backward (A8, "tr"), plus the round-2 backward "blocks" as
  * the independent-summation-order cross-check of the parity tests. The other measured alternatives of DESIGN.md §5 — backward "reduce"
- * (round 1) and "mm" (matrix-pipe experiment), forward "blocks" — are retired: their source stays in csrc/ behind -DDVS_EXPERIMENT
- * (tools/xbuild.sh builds such a library for A/B runs) and the release library answers DVS_ERR_UNSUPPORTED when they are asked for.
+ * (round 1) and "mm" (matrix-pipe experiment), forward "blocks" — are retired and their source is gone from the tree (the last commit
+ * that contains it is 263b613; their measurements are in profiles/ and DESIGN.md §5): the library answers DVS_ERR_UNSUPPORTED when
+ * they are asked for.
  * Backward (A8), results equal to fp32 roundoff:
  *   3 "tr"      (default since round 3) per-4x4-pixel-block splat lists; a list step ends when the pair's two per-pixel scalars
  *               (G dL/dalpha, alpha T) are known: they cross an LDS transposition buffer, and every four steps each lane sums one
@@ -311,7 +312,7 @@ int dvs_debug_sort_depth_keys(dvs_ctx* ctx, void* stream, const uint32_t* keys, 
  *   1 "reduce"  (retired) per-8x8-quadrant cull masks, a 12-value wave-wide reduction tree and one atomic row update per (wave, splat) visit
  *   2 "mm"      (retired) per-quadrant masks, the per-splat sums contracted on the fp32 matrix pipe; one view per launch only
  * Forward (A7), bit-identical results:  1 "quadrant" (default) / 0 "blocks" (retired).
- * The environment variables DVS_BWD_VARIANT / DVS_FWD_VARIANT (digits) set the defaults of new contexts (a retired variant is ignored). */
+ * The environment variable DVS_BWD_VARIANT (a digit) sets the default of new contexts (a retired variant is ignored). */
 int dvs_set_backward_variant(dvs_ctx* ctx, int variant);
 int dvs_set_forward_variant(dvs_ctx* ctx, int variant);
 /* Live lists (default on; DVS_LIVE_LISTS=0 sets the default of new contexts off): the "quadrant" forward writes, per tile, the

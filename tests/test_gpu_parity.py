@@ -60,22 +60,10 @@ def _run_gpu(rast, P, cam, tgt, deg, aa, absgrad=True, variants=None):
     import torch
     from divshot_amd.raster import params_to_device
     Pd = params_to_device(P, rast.tdev)
-    # experiment libraries (DVS_RASTER_LIB=tools/xlib/..., DVS_TEST_ALL_VARIANTS=1) also carry the retired per-block A7 kernel: bit-identical
-    # (same per-pixel sequence of contributing splats, same expressions). The release library has ONE forward.
-    img_q = saved_q = None
-    if ALL_VARIANTS:
-        rast.set_forward_variant("blocks")
-        img_q = rast.forward(Pd, cam, sh_degree=deg, antialias=aa, absgrad=absgrad).clone()
-        torch.cuda.synchronize()
-        saved_q = rast.saved()
-        rast.set_forward_variant("quadrant")
     img = rast.forward(Pd, cam, sh_degree=deg, antialias=aa, absgrad=absgrad)
     torch.cuda.synchronize()
     img_h = img.cpu().numpy()
     saved = rast.saved()
-    if img_q is not None:
-        assert torch.equal(img, img_q), "A7 variants differ in the image"
-        assert np.array_equal(saved["final_T"].view(np.uint32), saved_q["final_T"].view(np.uint32)) and np.array_equal(saved["n_contrib"], saved_q["n_contrib"])
     keys = rast.sorted_keys()
     dL = torch.from_numpy((img_h - tgt) / tgt[0].size).to(rast.tdev)
     runs = {}
@@ -92,11 +80,9 @@ def _run_gpu(rast, P, cam, tgt, deg, aa, absgrad=True, variants=None):
 
 
 # The matrix checks the shipped A8 kernel ("tr") and its round-2 predecessor ("blocks": the cross-check with a different summation order,
-# the only other A8 kernel in the release library). The retired experiments ("reduce", round 1; "mm", the MFMA contraction; the per-block
-# A7) exist in experiment builds only (tools/xbuild.sh): DVS_TEST_ALL_VARIANTS=1 together with DVS_RASTER_LIB=<such a library> brings
-# them back into the matrix.
-ALL_VARIANTS = os.environ.get("DVS_TEST_ALL_VARIANTS") == "1"
-BWD_VARIANTS = ("reduce", "blocks", "mm", "tr") if ALL_VARIANTS else ("blocks", "tr")
+# the only other A8 kernel in the library). The retired experiments ("reduce", round 1; "mm", the MFMA contraction; the per-block A7)
+# are no longer in the source.
+BWD_VARIANTS = ("blocks", "tr")
 REPORT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "parity_report.jsonl")
 
 
@@ -917,7 +903,7 @@ def test_hip_graph_replay_of_the_pass(gpu_device):
     r.close()
 
 
-@pytest.mark.parametrize("tiled,bwd", [(True, "tr"), (False, "tr"), (True, "blocks")] + ([(True, "reduce")] if os.environ.get("DVS_TEST_ALL_VARIANTS") == "1" else []))
+@pytest.mark.parametrize("tiled,bwd", [(True, "tr"), (False, "tr"), (True, "blocks")])
 def test_multi_view_batch_equals_single_views(gpu_device, tiled, bwd):
     """dvs_raster_forward_views / _backward_views (BASELINE config C4: several cameras per iteration in ONE pass — parameters read once,
     one depth sort / scan / (view, tile) sort / composite launch, gradients written once) against the same views run one by one with

@@ -62,7 +62,7 @@ def test_lineage_fp32_oracle_close_to_fp64(oracle_mod):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("variant", ["reduce", "blocks", "mm", "tr"] if os.environ.get("DVS_TEST_ALL_VARIANTS") == "1" else ["blocks", "tr"])
+@pytest.mark.parametrize("variant", ["blocks", "tr"])
 def test_hip_lineage_mode_on_saturating_scene(gpu_device, oracle_mod, variant):
     """The HIP path in both gradient modes on the scene that really exercises them (pixels on the 0.99 cap, splats on the clamped
     Jacobian branch — the seeded configurations of test_gpu_parity.py hardly do: their measured lineage-vs-true difference is 0 to 1.6e-4),
