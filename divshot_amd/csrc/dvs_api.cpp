@@ -306,9 +306,7 @@ static int run_a2(dvs_ctx* c, hipStream_t st, const dvs_splats* p, const dvs_cam
     HIPCHECK(dvs_launch_preprocess_fwd(st, n, p->pos, p->sh0, p->shN, p->opacity, p->scale, p->rot, dcams, V, opts->sh_degree,
                                        opts->antialias, tiles_x, tiles_y, c->radii.as<int>(), c->splat2d.as<float>(),
                                        c->depth.as<float>(), c->flags.as<uint32_t>(), c->tiles_touched.as<uint32_t>(), c->key[0].as<uint32_t>(),
-                                       nullptr, opts->shn_layout, rect_fmt == DVS_FE_RECT_U16 ? c->rect.as<uint32_t>() : nullptr,
-                                       rect_fmt == DVS_FE_RECT_TIGHT ? c->rect.as<uint32_t>() : nullptr,
-                                       rect_fmt == DVS_FE_RECT_U8 ? c->rect.as<uint32_t>() : nullptr, fe_kred(c), (int)first, (int)count));
+                                       opts->shn_layout, c->rect.as<uint32_t>(), rect_fmt, fe_kred(c), (int)first, (int)count));
     return DVS_OK;
 }
 static bool prep_matches(const dvs_ctx* c, const dvs_splats* p, const dvs_camera* cams, int V, const dvs_opts* opts) {
@@ -427,7 +425,7 @@ static int forward_views(dvs_ctx* c, hipStream_t st, const dvs_splats* p, const 
         }
         size_t e6 = tm.mark(); tm.span("tile_sort", e5, e6);
         if (fuse_a6) ranges_encoded = n > 0 ? 1 : 0;
-        else HIPCHECK(dvs_launch_tile_ranges(st, T, c->inst_tile[icur].as<uint32_t>(), ranges_ptr(c), tiles * V, T_dev, T_expected, false));     // (cleared by the memset above)
+        else HIPCHECK(dvs_launch_tile_ranges(st, T, c->inst_tile[icur].as<uint32_t>(), ranges_ptr(c), T_dev, T_expected));     // (cleared by the memset above)
         keys_written = write_keys;
         e7 = tm.mark(); tm.span("tile_ranges", e6, e7);
     }

@@ -9,11 +9,10 @@ hipError_t dvs_launch_preprocess_fwd(hipStream_t st, int n, const float* pos, co
                                      const float* opacity, const float* scale, const float* rot, const DvsCams& cams, int n_views,
                                      int deg, int antialias, int tiles_x, int tiles_y, int* radii /*per-view outputs are [n_views][n]*/, float* splat2d,
                                      float* depth, uint32_t* flags,
-                                     uint32_t* tiles_touched, uint32_t* depth_key, uint32_t* ids, int shn_tiled, uint32_t* rect /*[n,2]: 4 x u16*/,
-                                     uint32_t* rect16 /*DVS_TILES_TIGHT: [n,4] = rectangle + 64-bit tile mask, written instead of rect; null = canonical*/,
-                                     uint32_t* rect8 = nullptr /*DVS_FE_RECT_U8: [n] 4 x u8 (minx, miny, width, height) instead of rect*/,
-                                     uint32_t* kred = nullptr /*segmented front end: the views' key ranges [n_views][64][16] (zeroed by the caller); ids may then be null*/,
-                                     int first = 0, int count = -1 /*splat range of this launch: [first, first + count), count < 0 = up to n*/);
+                                     uint32_t* tiles_touched, uint32_t* depth_key, int shn_tiled,
+                                     uint32_t* rect /*[n_views][n] tile-rectangle records of format rect_fmt*/, int rect_fmt /*DVS_FE_RECT_* (below)*/,
+                                     uint32_t* kred /*segmented front end: the views' key ranges [n_views][64][16] (zeroed by the caller)*/,
+                                     int first, int count /*splat range of this launch: [first, first + count), count < 0 = up to n*/);
 hipError_t dvs_launch_preprocess_bwd(hipStream_t st, int n, const float* pos, const float* shN, const float* opacity,
                                      const float* scale, const float* rot, const DvsCam& cam, int deg, int antialias,
                                      const int* radii, const uint32_t* flags, float* grad_rows /*[n,12], read then re-zeroed*/,
@@ -48,8 +47,48 @@ struct DvsSeg {
     uint32_t _r0, _r1, _r2;
 };
 // tile-rectangle record formats (A2 writes, A3 gathers, A4 streams)
-enum { DVS_FE_RECT_U8 = 0 /*4 B: minx | miny << 8 | width << 16 | height << 24 (tiles_x, tiles_y <= 255)*/, DVS_FE_RECT_U16 = 1 /*8 B: 4 x u16*/,
-       DVS_FE_RECT_TIGHT = 2 /*16 B: 4 x u16 + the 64-bit tile mask of DVS_TILES_TIGHT*/ };
+enum { DVS_FE_RECT_U8 = 0 /*4 B: minx | miny << 8 | width << 16 | height << 24 (tiles_x, tiles_y <= 255: up to 4080 x 4080 pixels)*/,
+       DVS_FE_RECT_U16 = 1 /*8 B: [minx | maxx << 16, miny | maxy << 16] (larger images)*/,
+       DVS_FE_RECT_TIGHT = 2 /*16 B: the 8-B rectangle + the 64-bit tile mask of DVS_TILES_TIGHT*/ };
+// The record of each format: `pack` is what A2 writes (tiles [minx, maxx) x [miny, maxy); `mask` is read by TIGHT alone), the
+// accessors are what A3 / A4 read; zero() is the record of a culled splat (count 0).
+template <int FMT> struct FeRect;
+template <> struct FeRect<DVS_FE_RECT_U8> {
+    typedef uint32_t T;
+    static __device__ __forceinline__ T pack(uint32_t minx, uint32_t miny, uint32_t maxx, uint32_t maxy, unsigned long long) {
+        return minx | (miny << 8) | ((maxx - minx) << 16) | ((maxy - miny) << 24);
+    }
+    static __device__ __forceinline__ uint32_t count(T r) { return ((r >> 16) & 0xFFu) * (r >> 24); }
+    static __device__ __forceinline__ uint32_t minx(T r) { return r & 0xFFu; }
+    static __device__ __forceinline__ uint32_t miny(T r) { return (r >> 8) & 0xFFu; }
+    static __device__ __forceinline__ uint32_t width(T r) { return (r >> 16) & 0xFFu; }
+    static __device__ __forceinline__ T zero() { return 0u; }
+};
+template <> struct FeRect<DVS_FE_RECT_U16> {
+    typedef uint2 T;
+    static __device__ __forceinline__ T pack(uint32_t minx, uint32_t miny, uint32_t maxx, uint32_t maxy, unsigned long long) {
+        return make_uint2(minx | (maxx << 16), miny | (maxy << 16));
+    }
+    static __device__ __forceinline__ uint32_t count(T r) { return ((r.x >> 16) - (r.x & 0xFFFFu)) * ((r.y >> 16) - (r.y & 0xFFFFu)); }
+    static __device__ __forceinline__ uint32_t minx(T r) { return r.x & 0xFFFFu; }
+    static __device__ __forceinline__ uint32_t miny(T r) { return r.y & 0xFFFFu; }
+    static __device__ __forceinline__ uint32_t width(T r) { return (r.x >> 16) - (r.x & 0xFFFFu); }
+    static __device__ __forceinline__ T zero() { return make_uint2(0u, 0u); }
+};
+template <> struct FeRect<DVS_FE_RECT_TIGHT> {
+    typedef uint4 T;
+    static __device__ __forceinline__ T pack(uint32_t minx, uint32_t miny, uint32_t maxx, uint32_t maxy, unsigned long long mask) {
+        return make_uint4(minx | (maxx << 16), miny | (maxy << 16), (uint32_t)mask, (uint32_t)(mask >> 32));
+    }
+    static __device__ __forceinline__ uint32_t count(T r) {
+        const uint32_t both = r.z & r.w;
+        return both == 0xFFFFFFFFu ? ((r.x >> 16) - (r.x & 0xFFFFu)) * ((r.y >> 16) - (r.y & 0xFFFFu)) : (uint32_t)(__popc(r.z) + __popc(r.w));
+    }
+    static __device__ __forceinline__ uint32_t minx(T r) { return r.x & 0xFFFFu; }
+    static __device__ __forceinline__ uint32_t miny(T r) { return r.y & 0xFFFFu; }
+    static __device__ __forceinline__ uint32_t width(T r) { return (r.x >> 16) - (r.x & 0xFFFFu); }
+    static __device__ __forceinline__ T zero() { return make_uint4(0u, 0u, 0u, 0u); }
+};
 #define DVS_FE_KRED_WORDS (DVS_MAX_VIEWS * 64 * 16)        /* key-range slots: [view][64][16 words] */
 #define DVS_FE_MAXBINS 2048
 #define DVS_FE_SUPER_STRIDE 32                                  /* u64 words between two super-sum counters (256 B: own memory channel) */
@@ -77,8 +116,8 @@ hipError_t dvs_launch_seg_binning(hipStream_t st, int n, int V, int rect_fmt, co
 
 // frontend.hip, continued
 // A6: per-tile [start,end) from the sorted tile ids. T_dev (nullable): device-side count, T sizes the grid.
-hipError_t dvs_launch_tile_ranges(hipStream_t st, uint64_t T, const uint32_t* sorted_tile, uint32_t* ranges, int tiles,
-                                  const uint64_t* T_dev = nullptr, uint64_t T_expected = 0, bool clear = true /*false: the caller has zeroed `ranges`*/);
+hipError_t dvs_launch_tile_ranges(hipStream_t st, uint64_t T, const uint32_t* sorted_tile, uint32_t* ranges /*zeroed by the caller*/,
+                                  const uint64_t* T_dev = nullptr, uint64_t T_expected = 0);
 // canonical 64-bit keys of the sorted list (parity export)
 hipError_t dvs_launch_export_keys(hipStream_t st, uint64_t T, const uint32_t* sorted_tile, const uint32_t* sorted_splat,
                                   const float* depth, uint64_t* out_keys);

@@ -555,39 +555,6 @@ hipError_t dvs_fe_probe_rank_atomic(hipStream_t st, uint32_t* bad_dev /*one zero
     return hipGetLastError();
 }
 
-// ---- tile rectangles: three record formats -----------------------------------------------------------------------------------------
-//   FE_RECT_U8   4 B  minx | miny << 8 | width << 16 | height << 24            (tiles_x, tiles_y <= 255: up to 4080 x 4080 pixels)
-//   FE_RECT_U16  8 B  [minx | maxx << 16, miny | maxy << 16]                    (larger images)
-//   FE_RECT_TIGHT 16 B the 8-B rectangle + the 64-bit tile mask of DVS_TILES_TIGHT
-template <int FMT> struct FeRect;
-template <> struct FeRect<DVS_FE_RECT_U8> {
-    typedef uint32_t T;
-    static __device__ __forceinline__ uint32_t count(T r) { return ((r >> 16) & 0xFFu) * (r >> 24); }
-    static __device__ __forceinline__ uint32_t minx(T r) { return r & 0xFFu; }
-    static __device__ __forceinline__ uint32_t miny(T r) { return (r >> 8) & 0xFFu; }
-    static __device__ __forceinline__ uint32_t width(T r) { return (r >> 16) & 0xFFu; }
-    static __device__ __forceinline__ T zero() { return 0u; }
-};
-template <> struct FeRect<DVS_FE_RECT_U16> {
-    typedef uint2 T;
-    static __device__ __forceinline__ uint32_t count(T r) { return ((r.x >> 16) - (r.x & 0xFFFFu)) * ((r.y >> 16) - (r.y & 0xFFFFu)); }
-    static __device__ __forceinline__ uint32_t minx(T r) { return r.x & 0xFFFFu; }
-    static __device__ __forceinline__ uint32_t miny(T r) { return r.y & 0xFFFFu; }
-    static __device__ __forceinline__ uint32_t width(T r) { return (r.x >> 16) - (r.x & 0xFFFFu); }
-    static __device__ __forceinline__ T zero() { return make_uint2(0u, 0u); }
-};
-template <> struct FeRect<DVS_FE_RECT_TIGHT> {
-    typedef uint4 T;
-    static __device__ __forceinline__ uint32_t count(T r) {
-        const uint32_t both = r.z & r.w;
-        return both == 0xFFFFFFFFu ? ((r.x >> 16) - (r.x & 0xFFFFu)) * ((r.y >> 16) - (r.y & 0xFFFFu)) : (uint32_t)(__popc(r.z) + __popc(r.w));
-    }
-    static __device__ __forceinline__ uint32_t minx(T r) { return r.x & 0xFFFFu; }
-    static __device__ __forceinline__ uint32_t miny(T r) { return r.y & 0xFFFFu; }
-    static __device__ __forceinline__ uint32_t width(T r) { return (r.x >> 16) - (r.x & 0xFFFFu); }
-    static __device__ __forceinline__ T zero() { return make_uint4(0u, 0u, 0u, 0u); }
-};
-
 // ---- A3: tile counts in depth order ---------------------------------------------------------------------------------------------------
 // Workgroup (view, block): 256 consecutive elements of the view's depth-sorted list. The ONE random gather of the stage —
 // rect[view][sorted id] — is done here and the rectangles are re-emitted in depth order, so that A4 streams. With FE_RECT_U8 a view's
@@ -850,10 +817,8 @@ k_tile_ranges(uint64_t T_host, const uint64_t* __restrict__ T_dev, const uint32_
     }
 }
 
-hipError_t dvs_launch_tile_ranges(hipStream_t st, uint64_t T, const uint32_t* sorted_tile, uint32_t* ranges, int tiles, const uint64_t* T_dev,
-                                  uint64_t T_expected, bool clear) {
-    hipError_t e = clear ? hipMemsetAsync(ranges, 0, (size_t)tiles * 2 * sizeof(uint32_t), st) : hipSuccess;
-    if (e != hipSuccess) return e;
+hipError_t dvs_launch_tile_ranges(hipStream_t st, uint64_t T, const uint32_t* sorted_tile, uint32_t* ranges, const uint64_t* T_dev,
+                                  uint64_t T_expected) {
     if (T == 0) return hipSuccess;
     const uint64_t T_grid = (T_dev && T_expected > 0 && T_expected < T) ? T_expected : T;
     const uint32_t nb = (uint32_t)((T_grid + 4 * FE_BLOCK - 1) / (4 * FE_BLOCK));

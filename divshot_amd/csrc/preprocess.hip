@@ -66,7 +66,87 @@ __device__ __forceinline__ void stage_rows_out(float* __restrict__ g, const floa
 // (and no LDS-bound occupancy). Element e of splat i: float4 index ((i>>6)*12 + e/4)*64 + (i&63), component e%4.
 __device__ __forceinline__ int64_t shn_tiled_f4(int i, int c) { return ((int64_t)(i >> 6) * 12 + c) * 64 + (i & 63); }
 
+// ---- the chains A2 and A9 must agree on, bit for bit: each is written here once ------------------
+// A9 recomputes the forward's intermediates (they feed nothing but floats there, but the conic must be the one the forward composited
+// with), so both directions call these. Nothing in them contracts (-ffp-contract=off): operation order is the oracle's.
+// View-independent: activated scales, normalised quaternion, rotation, 3D covariance.
+struct PpFrame { float s[3], qn, inv_qn, qr, qx, qy, qz /*normalised*/, R[9], c3[6]; };
+__device__ __forceinline__ PpFrame pp_frame(float in_s0, float in_s1, float in_s2, float4 in_q) {
+    PpFrame f;
+    f.s[0] = dvs_exp_det(in_s0); f.s[1] = dvs_exp_det(in_s1); f.s[2] = dvs_exp_det(in_s2);
+    f.qn = dvs_sqrt_rn(((in_q.x * in_q.x + in_q.y * in_q.y) + in_q.z * in_q.z) + in_q.w * in_q.w);
+    f.inv_qn = 1.0f / f.qn;
+    f.qr = in_q.x * f.inv_qn; f.qx = in_q.y * f.inv_qn; f.qy = in_q.z * f.inv_qn; f.qz = in_q.w * f.inv_qn;
+    dvs_quat_to_rot(f.qr, f.qx, f.qy, f.qz, f.R);
+    dvs_cov3d(f.s, f.R, f.c3);
+    return f;
+}
+// View-dependent: view / clip transform, FOV clamp, Jacobian rows T0 T1 (of J W), Sigma T, cov2D, low-pass, determinant, conic.
+struct PpProj {
+    float tx, ty, tz, hx, hy, hw, pw, cl_x, cl_y, txc, tyc, T0[3], T1[3], v0[3], v1[3], cxx, cxy, cyy, a, b, c, det, det_inv;
+    float cA, cB, cC;   // the conic: the inverse of the low-passed cov2D
+    uint32_t clamp;     // DVS_FLAG_CLAMP_X | _Y as the forward publishes them
+};
+__device__ __forceinline__ PpProj pp_project(const DvsCam& cam, float px, float py, float pz, const float c3[6]) {
+    PpProj p;
+    p.tx = dvs_xform(cam.view, px, py, pz, 0);
+    p.ty = dvs_xform(cam.view, px, py, pz, 1);
+    p.tz = dvs_xform(cam.view, px, py, pz, 2);
+    p.hx = dvs_xform(cam.proj, px, py, pz, 0);
+    p.hy = dvs_xform(cam.proj, px, py, pz, 1);
+    p.hw = dvs_xform(cam.proj, px, py, pz, 3);
+    p.pw = 1.0f / (p.hw + 0.0000001f);
+    const float limx = DVS_FOV_GUARD * cam.tan_fovx, limy = DVS_FOV_GUARD * cam.tan_fovy;
+    const float txtz = p.tx / p.tz, tytz = p.ty / p.tz;
+    p.clamp = 0;
+    if (txtz < -limx || txtz > limx) p.clamp |= DVS_FLAG_CLAMP_X;
+    if (tytz < -limy || tytz > limy) p.clamp |= DVS_FLAG_CLAMP_Y;
+    p.cl_x = fminf(limx, fmaxf(-limx, txtz)); p.cl_y = fminf(limy, fmaxf(-limy, tytz));
+    p.txc = p.cl_x * p.tz; p.tyc = p.cl_y * p.tz;
+    const float fx = cam.focal_x, fy = cam.focal_y;
+    const float J00 = fx / p.tz, J02 = -(fx * p.txc) / (p.tz * p.tz);
+    const float J11 = fy / p.tz, J12 = -(fy * p.tyc) / (p.tz * p.tz);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        p.T0[k] = J00 * cam.view[k * 4 + 0] + J02 * cam.view[k * 4 + 2];
+        p.T1[k] = J11 * cam.view[k * 4 + 1] + J12 * cam.view[k * 4 + 2];
+    }
+    const float* T0 = p.T0, *T1 = p.T1;
+    p.v0[0] = (c3[0] * T0[0] + c3[1] * T0[1]) + c3[2] * T0[2];
+    p.v0[1] = (c3[1] * T0[0] + c3[3] * T0[1]) + c3[4] * T0[2];
+    p.v0[2] = (c3[2] * T0[0] + c3[4] * T0[1]) + c3[5] * T0[2];
+    p.v1[0] = (c3[0] * T1[0] + c3[1] * T1[1]) + c3[2] * T1[2];
+    p.v1[1] = (c3[1] * T1[0] + c3[3] * T1[1]) + c3[4] * T1[2];
+    p.v1[2] = (c3[2] * T1[0] + c3[4] * T1[1]) + c3[5] * T1[2];
+    p.cxx = (T0[0] * p.v0[0] + T0[1] * p.v0[1]) + T0[2] * p.v0[2];
+    p.cxy = (T0[0] * p.v1[0] + T0[1] * p.v1[1]) + T0[2] * p.v1[2];
+    p.cyy = (T1[0] * p.v1[0] + T1[1] * p.v1[1]) + T1[2] * p.v1[2];
+    p.a = p.cxx + DVS_LOWPASS; p.b = p.cxy; p.c = p.cyy + DVS_LOWPASS;
+    p.det = p.a * p.c - p.b * p.b;
+    p.det_inv = 1.0f / p.det;
+    p.cA = p.c * p.det_inv; p.cB = -p.b * p.det_inv; p.cC = p.a * p.det_inv;
+    return p;
+}
+// Unit view direction (p - campos) / |.|; `campos` is a pointer in any address space (a DvsCam member, a kernarg table row).
+struct PpDir { float ux, uy, uz, inv_dl; };
+template <typename P>
+__device__ __forceinline__ PpDir pp_view_dir(float px, float py, float pz, P campos) {
+    const float dx = px - campos[0], dy = py - campos[1], dz = pz - campos[2];
+    const float dl = dvs_sqrt_rn((dx * dx + dy * dy) + dz * dz);
+    PpDir d;
+    d.inv_dl = 1.0f / dl;
+    d.ux = dx * d.inv_dl; d.uy = dy * d.inv_dl; d.uz = dz * d.inv_dl;
+    return d;
+}
+
 // ---- A2 ---------------------------------------------------------------------------------------
+template <int FMT>
+__device__ __forceinline__ void a2_write_rect(void* __restrict__ rect, int64_t o, bool ok, int minx, int miny, int maxx, int maxy,
+                                              unsigned long long mask) {
+    typedef FeRect<FMT> F;
+    reinterpret_cast<typename F::T*>(rect)[o] = ok ? F::pack((uint32_t)minx, (uint32_t)miny, (uint32_t)maxx, (uint32_t)maxy, mask) : F::zero();
+}
+
 template <bool TILED, bool MULTI /*more than one view: the parameter registers stay live across the view loop*/>
 __global__ void __launch_bounds__(PP_BLOCK)
 k_preprocess_fwd(DvsCams cams_arg /* MUST stay the first parameter: read through dvs_load_cam() */, int n_views, int n,
@@ -75,12 +155,11 @@ k_preprocess_fwd(DvsCams cams_arg /* MUST stay the first parameter: read through
                  int deg, int antialias, int tiles_x, int tiles_y,
                  int* __restrict__ radii, float4* __restrict__ splat2d /*[n] 64-B records, DVS_S2D_* */, float* __restrict__ depth,
                  uint32_t* __restrict__ flags,
-                 uint32_t* __restrict__ tiles_touched, uint32_t* __restrict__ depth_key, uint32_t* __restrict__ ids,
-                 uint2* __restrict__ rect /*tile rectangle [minx | maxx << 16, miny | maxy << 16]; empty for culled splats*/,
-                 uint4* __restrict__ rect16 /*DVS_TILES_TIGHT: {rectangle, tile mask lo, hi} instead of `rect` (null: canonical rectangles)*/,
-                 uint32_t* __restrict__ rect8 /*DVS_FE_RECT_U8: minx | miny << 8 | width << 16 | height << 24 instead of `rect` (null: 16-bit fields)*/,
+                 uint32_t* __restrict__ tiles_touched, uint32_t* __restrict__ depth_key,
+                 void* __restrict__ rect /*tile-rectangle records FeRect<rect_fmt>::T (dvs_kernels.h); the zero record for culled splats*/,
+                 int rect_fmt /*DVS_FE_RECT_*: uniform, tested once per view*/,
                  uint32_t* __restrict__ kred /*segmented front end (frontend.hip): [view][64 slots][16 words], word 0 = max(~key), word 1 = max(key)
-                 over the view's visible splats, zeroed by the caller; null = the batch-wide sort of rounds 1-4, which wants `ids`*/,
+                 over the view's visible splats, zeroed by the caller*/,
                  int i0, int i1 /*this launch covers the splats [i0, i1): all of them, or one chunk of a data-parallel step that projects the
                  next iteration's splats chunk by chunk behind the optimizer (dvs_raster_forward_views_prepare); n stays the view-major stride*/) {
     extern __shared__ __attribute__((aligned(16))) float lds[];   // [PP_BLOCK*45] when deg>0
@@ -133,65 +212,21 @@ k_preprocess_fwd(DvsCams cams_arg /* MUST stay the first parameter: read through
     // wave practically never has all 64 splats culled, so the exits saved nothing.) Same expressions in the same order for the lanes that
     // survive: bit-identical outputs; culled lanes compute on whatever they hold (NaN / inf are harmless, nothing is stored from them).
     const float px = in_px, py = in_py, pz = in_pz;
-    const float tx = dvs_xform(cam.view, px, py, pz, 0);
-    const float ty = dvs_xform(cam.view, px, py, pz, 1);
-    const float tz = dvs_xform(cam.view, px, py, pz, 2);
+    const PpFrame fr = pp_frame(in_s0, in_s1, in_s2, in_q);
+    const PpProj pj = pp_project(cam, px, py, pz, fr.c3);
+    const float tz = pj.tz, a = pj.a, b = pj.b, c = pj.c, det = pj.det;
     // a NaN log-scale or opacity logit culls the splat (the clamps inside dvs_exp_det would otherwise turn it into a number)
     bool ok = (tz > DVS_NEAR) && (in_s0 == in_s0) && (in_s1 == in_s1) && (in_s2 == in_s2) && (in_op == in_op);
-    const float hx = dvs_xform(cam.proj, px, py, pz, 0);
-    const float hy = dvs_xform(cam.proj, px, py, pz, 1);
-    const float hw = dvs_xform(cam.proj, px, py, pz, 3);
-    const float pw = 1.0f / (hw + 0.0000001f);
-    const float ndc_x = hx * pw, ndc_y = hy * pw;
-
-    const float s[3] = {dvs_exp_det(in_s0), dvs_exp_det(in_s1), dvs_exp_det(in_s2)};
-    const float4 q4 = in_q;
-    const float qr = q4.x, qx = q4.y, qy = q4.z, qz = q4.w;
-    const float qn = dvs_sqrt_rn(((qr * qr + qx * qx) + qy * qy) + qz * qz);
-    ok = ok && (qn > 0.f);
-    const float inv_qn = 1.0f / qn;
-    float R[9];
-    dvs_quat_to_rot(qr * inv_qn, qx * inv_qn, qy * inv_qn, qz * inv_qn, R);
-    float c3[6];
-    dvs_cov3d(s, R, c3);
-
-    const float limx = DVS_FOV_GUARD * cam.tan_fovx, limy = DVS_FOV_GUARD * cam.tan_fovy;
-    const float txtz = tx / tz, tytz = ty / tz;
-    uint32_t fl = 0;
-    if (txtz < -limx || txtz > limx) fl |= DVS_FLAG_CLAMP_X;
-    if (tytz < -limy || tytz > limy) fl |= DVS_FLAG_CLAMP_Y;
-    const float txc = fminf(limx, fmaxf(-limx, txtz)) * tz;
-    const float tyc = fminf(limy, fmaxf(-limy, tytz)) * tz;
-    const float fx = cam.focal_x, fy = cam.focal_y;
-    const float J00 = fx / tz, J02 = -(fx * txc) / (tz * tz);
-    const float J11 = fy / tz, J12 = -(fy * tyc) / (tz * tz);
-    float T0[3], T1[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        T0[k] = J00 * cam.view[k * 4 + 0] + J02 * cam.view[k * 4 + 2];
-        T1[k] = J11 * cam.view[k * 4 + 1] + J12 * cam.view[k * 4 + 2];
-    }
-    const float v0x = (c3[0] * T0[0] + c3[1] * T0[1]) + c3[2] * T0[2];
-    const float v0y = (c3[1] * T0[0] + c3[3] * T0[1]) + c3[4] * T0[2];
-    const float v0z = (c3[2] * T0[0] + c3[4] * T0[1]) + c3[5] * T0[2];
-    const float v1x = (c3[0] * T1[0] + c3[1] * T1[1]) + c3[2] * T1[2];
-    const float v1y = (c3[1] * T1[0] + c3[3] * T1[1]) + c3[4] * T1[2];
-    const float v1z = (c3[2] * T1[0] + c3[4] * T1[1]) + c3[5] * T1[2];
-    const float cxx = (T0[0] * v0x + T0[1] * v0y) + T0[2] * v0z;
-    const float cxy = (T0[0] * v1x + T0[1] * v1y) + T0[2] * v1z;
-    const float cyy = (T1[0] * v1x + T1[1] * v1y) + T1[2] * v1z;
-
-    const float a = cxx + DVS_LOWPASS, b = cxy, c = cyy + DVS_LOWPASS;
-    const float det = a * c - b * b;
-    ok = ok && (det > 0.f);
+    ok = ok && (fr.qn > 0.f) && (det > 0.f);
+    const float ndc_x = pj.hx * pj.pw, ndc_y = pj.hy * pj.pw;
+    uint32_t fl = pj.clamp;
     float opac = dvs_sigmoid_det(in_op);
     if (antialias) {
-        const float det_orig = cxx * cyy - b * b;
+        const float det_orig = pj.cxx * pj.cyy - b * b;
         const float aa = dvs_sqrt_rn(fmaxf(0.f, det_orig / det));
         opac = opac * aa;
     }
     ok = ok && (opac > DVS_ALPHA_MIN);
-    const float det_inv = 1.0f / det;
     const float mid = 0.5f * (a + c);
     const float lam = mid + dvs_sqrt_rn(fmaxf(0.1f, mid * mid - det));
     const float radf = ceilf(3.0f * dvs_sqrt_rn(lam));
@@ -205,11 +240,9 @@ k_preprocess_fwd(DvsCams cams_arg /* MUST stay the first parameter: read through
     const int touched = (rmaxx - rminx) * (rmaxy - rminy);
     ok = ok && (touched > 0);
 
-    const float dx = px - cam.campos[0], dy = py - cam.campos[1], dz = pz - cam.campos[2];
-    const float dl = dvs_sqrt_rn((dx * dx + dy * dy) + dz * dz);
-    const float inv_dl = 1.0f / dl;
+    const PpDir dir = pp_view_dir(px, py, pz, cam.campos);
     float bas[16];
-    dvs_sh_basis(deg, dx * inv_dl, dy * inv_dl, dz * inv_dl, bas);
+    dvs_sh_basis(deg, dir.ux, dir.uy, dir.uz, bas);
     const int ncoef = (deg + 1) * (deg + 1);
     const float in_dc[3] = {in_dc0, in_dc1, in_dc2};
     float colr[3] = {bas[0] * in_dc[0], bas[0] * in_dc[1], bas[0] * in_dc[2]};
@@ -244,13 +277,12 @@ k_preprocess_fwd(DvsCams cams_arg /* MUST stay the first parameter: read through
     const float2 out_mean = ok ? make_float2(m2x, m2y) : make_float2(0.f, 0.f);
     const float out_depth = ok ? tz : 0.f;
     const uint32_t out_key = ok ? __float_as_uint(tz) : 0xFFFFFFFFu;
-    const float4 out_co = ok ? make_float4(c * det_inv, -b * det_inv, a * det_inv, opac) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 out_co = ok ? make_float4(pj.cA, pj.cB, pj.cC, opac) : make_float4(0.f, 0.f, 0.f, 0.f);
     const float out_rgb[3] = {ok ? rgb_c[0] : 0.f, ok ? rgb_c[1] : 0.f, ok ? rgb_c[2] : 0.f};
     const uint32_t out_flags = ok ? fl : 0u;
     uint32_t out_tiles = ok ? (uint32_t)touched : 0u;
-    const uint2 out_rect = ok ? make_uint2((uint32_t)rminx | ((uint32_t)rmaxx << 16), (uint32_t)rminy | ((uint32_t)rmaxy << 16)) : make_uint2(0u, 0u);
     unsigned long long out_mask = 0ull;
-    if (rect16 && ok) {    // DVS_TILES_TIGHT: only the tiles the alpha >= 1/255 ellipse reaches (rectangles of more than 64 tiles stay whole)
+    if (rect_fmt == DVS_FE_RECT_TIGHT && ok) {    // DVS_TILES_TIGHT: only the tiles the alpha >= 1/255 ellipse reaches (rectangles of more than 64 tiles stay whole)
         out_mask = ~0ull;
         if (touched <= 64) {
             out_mask = dvs_tight_tile_mask(out_co.x, out_co.y, out_co.z, opac, m2x, m2y, rminx, rminy, rmaxx, rmaxy);
@@ -292,33 +324,27 @@ k_preprocess_fwd(DvsCams cams_arg /* MUST stay the first parameter: read through
     }
     flags[o] = out_flags;
     tiles_touched[o] = out_tiles;
-    if (rect16) rect16[o] = make_uint4(out_rect.x, out_rect.y, (uint32_t)out_mask, (uint32_t)(out_mask >> 32));
-    else if (rect8) {
-        const uint32_t x0 = out_rect.x & 0xFFFFu, y0 = out_rect.y & 0xFFFFu;
-        rect8[o] = x0 | (y0 << 8) | (((out_rect.x >> 16) - x0) << 16) | (((out_rect.y >> 16) - y0) << 24);
-    } else rect[o] = out_rect;
+    if (rect_fmt == DVS_FE_RECT_TIGHT) a2_write_rect<DVS_FE_RECT_TIGHT>(rect, o, ok, rminx, rminy, rmaxx, rmaxy, out_mask);
+    else if (rect_fmt == DVS_FE_RECT_U8) a2_write_rect<DVS_FE_RECT_U8>(rect, o, ok, rminx, rminy, rmaxx, rmaxy, out_mask);
+    else a2_write_rect<DVS_FE_RECT_U16>(rect, o, ok, rminx, rminy, rmaxx, rmaxy, out_mask);
     depth_key[o] = out_key;
-    if (ids) ids[o] = (uint32_t)o;
-    if (kred) {
-        // the view's key range for the range-adaptive depth sort: one pair of atomics per wave into one of 64 slots (64 B apart)
-        uint32_t knm = ~out_key, kmx = out_radius > 0 ? out_key : 0u;         // both are max reductions with identity 0 (culled: ~0xFFFFFFFF = 0)
-        uint32_t* slot = kred + ((size_t)view * 64 + (blockIdx.x & 63u)) * 16;
-        if (wave_base + 64 <= i1) {
-            // wave64 max in six DPP steps (row_shr 1, 2, 4, 8, row_bcast 15, 31): lane 63 ends with the wave's maximum
+    // the view's key range for the range-adaptive depth sort: one pair of atomics per wave into one of 64 slots (64 B apart)
+    uint32_t knm = ~out_key, kmx = out_radius > 0 ? out_key : 0u;         // both are max reductions with identity 0 (culled: ~0xFFFFFFFF = 0)
+    uint32_t* slot = kred + ((size_t)view * 64 + (blockIdx.x & 63u)) * 16;
+    if (wave_base + 64 <= i1) {
+        // wave64 max in six DPP steps (row_shr 1, 2, 4, 8, row_bcast 15, 31): lane 63 ends with the wave's maximum
 #define A2_DPP_MAX(v, ctrl, rmask) { const uint32_t o_ = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rmask, 0xF, false); v = o_ > v ? o_ : v; }
-            A2_DPP_MAX(knm, 0x111, 0xF) A2_DPP_MAX(kmx, 0x111, 0xF) A2_DPP_MAX(knm, 0x112, 0xF) A2_DPP_MAX(kmx, 0x112, 0xF)
-            A2_DPP_MAX(knm, 0x114, 0xF) A2_DPP_MAX(kmx, 0x114, 0xF) A2_DPP_MAX(knm, 0x118, 0xF) A2_DPP_MAX(kmx, 0x118, 0xF)
-            A2_DPP_MAX(knm, 0x142, 0xA) A2_DPP_MAX(kmx, 0x142, 0xA) A2_DPP_MAX(knm, 0x143, 0xC) A2_DPP_MAX(kmx, 0x143, 0xC)
+        A2_DPP_MAX(knm, 0x111, 0xF) A2_DPP_MAX(kmx, 0x111, 0xF) A2_DPP_MAX(knm, 0x112, 0xF) A2_DPP_MAX(kmx, 0x112, 0xF)
+        A2_DPP_MAX(knm, 0x114, 0xF) A2_DPP_MAX(kmx, 0x114, 0xF) A2_DPP_MAX(knm, 0x118, 0xF) A2_DPP_MAX(kmx, 0x118, 0xF)
+        A2_DPP_MAX(knm, 0x142, 0xA) A2_DPP_MAX(kmx, 0x142, 0xA) A2_DPP_MAX(knm, 0x143, 0xC) A2_DPP_MAX(kmx, 0x143, 0xC)
 #undef A2_DPP_MAX
-            if ((threadIdx.x & 63) == 63 && knm != 0u) { atomicMax(slot, knm); atomicMax(slot + 1, kmx); }
-        } else if (out_radius > 0) { atomicMax(slot, knm); atomicMax(slot + 1, kmx); }
-    }
+        if ((threadIdx.x & 63) == 63 && knm != 0u) { atomicMax(slot, knm); atomicMax(slot + 1, kmx); }
+    } else if (out_radius > 0) { atomicMax(slot, knm); atomicMax(slot + 1, kmx); }
     }   // views
 }
 
 // The geometry part of A9. Round 6 splits it where the chain stops depending on the view:
-//   a9_geometry   per (splat, view): recomputes the forward intermediates (same expressions as k_preprocess_fwd: these feed nothing but
-//                 floats here, but the conic must be the one the forward composited with), turns the A8 moments into dL/dmean2D and
+//   a9_geometry   per (splat, view): recomputes the forward intermediates (pp_frame, pp_project), turns the A8 moments into dL/dmean2D and
 //                 dL/dconic, walks back through conic -> cov2D -> (J, W) and through the projection to the position, and ADDS the
 //                 view's symmetrised dL/dSigma (Gm + Gm^T, six values) to `Gs`;
 //   a9_sigma_to_params   once per splat: Sigma = M M^T, M = R S  ->  dL/dscale, dL/drot. The 3D covariance does not depend on the view
@@ -330,50 +356,16 @@ k_preprocess_fwd(DvsCams cams_arg /* MUST stay the first parameter: read through
 __device__ __forceinline__ void a9_geometry(const DvsCam& cam, float px, float py, float pz, float in_s0, float in_s1, float in_s2, float4 in_q,
                                             float in_op, uint32_t fl, float4 r0, float4 r1, int antialias, int grad_mode, float gp[3],
                                             float Gs[6] /* += : 00 01 02 11 12 22 of Gm + Gm^T */, float& g_op, float2& dm_out) {
-        const float tx = dvs_xform(cam.view, px, py, pz, 0);
-        const float ty = dvs_xform(cam.view, px, py, pz, 1);
-        const float tz = dvs_xform(cam.view, px, py, pz, 2);
-        const float hx = dvs_xform(cam.proj, px, py, pz, 0);
-        const float hy = dvs_xform(cam.proj, px, py, pz, 1);
-        const float hw = dvs_xform(cam.proj, px, py, pz, 3);
-        const float pw = 1.0f / (hw + 0.0000001f);
-        const float s[3] = {dvs_exp_det(in_s0), dvs_exp_det(in_s1), dvs_exp_det(in_s2)};
-        const float4 q4 = in_q;
-        const float qn = dvs_sqrt_rn(((q4.x * q4.x + q4.y * q4.y) + q4.z * q4.z) + q4.w * q4.w);
-        const float inv_qn = 1.0f / qn;
-        const float qr = q4.x * inv_qn, qx = q4.y * inv_qn, qy = q4.z * inv_qn, qz = q4.w * inv_qn;
-        float R[9];
-        dvs_quat_to_rot(qr, qx, qy, qz, R);
-        float c3[6];
-        dvs_cov3d(s, R, c3);
-        const float limx = DVS_FOV_GUARD * cam.tan_fovx, limy = DVS_FOV_GUARD * cam.tan_fovy;
-        const float txtz = tx / tz, tytz = ty / tz;
-        const float cl_x = fminf(limx, fmaxf(-limx, txtz)), cl_y = fminf(limy, fmaxf(-limy, tytz));
-        const float txc = cl_x * tz, tyc = cl_y * tz;
+        const PpFrame fr = pp_frame(in_s0, in_s1, in_s2, in_q);
+        const PpProj pj = pp_project(cam, px, py, pz, fr.c3);
+        const float tz = pj.tz, hx = pj.hx, hy = pj.hy, pw = pj.pw, cl_x = pj.cl_x, cl_y = pj.cl_y, txc = pj.txc, tyc = pj.tyc;
+        const float* T0 = pj.T0, *T1 = pj.T1, *v0 = pj.v0, *v1 = pj.v1;
+        const float cxx = pj.cxx, cyy = pj.cyy, a = pj.a, b = pj.b, c = pj.c, det = pj.det, det_inv = pj.det_inv;
         const float fx = cam.focal_x, fy = cam.focal_y;
-        const float J00 = fx / tz, J02 = -(fx * txc) / (tz * tz);
-        const float J11 = fy / tz, J12 = -(fy * tyc) / (tz * tz);
-        float T0[3], T1[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            T0[k] = J00 * cam.view[k * 4 + 0] + J02 * cam.view[k * 4 + 2];
-            T1[k] = J11 * cam.view[k * 4 + 1] + J12 * cam.view[k * 4 + 2];
-        }
-        const float v0[3] = {(c3[0] * T0[0] + c3[1] * T0[1]) + c3[2] * T0[2], (c3[1] * T0[0] + c3[3] * T0[1]) + c3[4] * T0[2],
-                             (c3[2] * T0[0] + c3[4] * T0[1]) + c3[5] * T0[2]};
-        const float v1[3] = {(c3[0] * T1[0] + c3[1] * T1[1]) + c3[2] * T1[2], (c3[1] * T1[0] + c3[3] * T1[1]) + c3[4] * T1[2],
-                             (c3[2] * T1[0] + c3[4] * T1[1]) + c3[5] * T1[2]};
-        const float cxx = (T0[0] * v0[0] + T0[1] * v0[1]) + T0[2] * v0[2];
-        const float cxy = (T0[0] * v1[0] + T0[1] * v1[1]) + T0[2] * v1[2];
-        const float cyy = (T1[0] * v1[0] + T1[1] * v1[1]) + T1[2] * v1[2];
-        const float a = cxx + DVS_LOWPASS, b = cxy, c = cyy + DVS_LOWPASS;
-        const float det = a * c - b * b;
-        const float det_inv = 1.0f / det;
-        // A8 publishes moments of s = dL/dG * G about the mean (S_x S_y | S_xx S_xy S_yy | S_o); with the conic (A, B, C) — the same
-        // expressions, hence the same bits, as the forward wrote — they become the gradients of the 2D mean and of the conic
-        const float cA = c * det_inv, cB = -b * det_inv, cC = a * det_inv;
+        // A8 publishes moments of s = dL/dG * G about the mean (S_x S_y | S_xx S_xy S_yy | S_o); with the conic (A, B, C) — the
+        // forward's own bits — they become the gradients of the 2D mean and of the conic
+        const float cA = pj.cA, cB = pj.cB, cC = pj.cC;
         const float sig = dvs_sigmoid_det(in_op);
-        (void)ty;
     {
 #pragma clang fp contract(fast)
         const float2 dL_dm = make_float2(-(cA * r0.x + cB * r0.y), -(cC * r0.y + cB * r0.x));
@@ -463,12 +455,9 @@ __device__ __forceinline__ void a9_geometry(const DvsCam& cam, float px, float p
 // gradient is projected off the quaternion and divided by its norm). `Gs` = the symmetrised dL/dSigma summed over the views.
 __device__ __forceinline__ void a9_sigma_to_params(float in_s0, float in_s1, float in_s2, float4 in_q, const float Gs[6], float gsc[3],
                                                    float gq_out[4]) {
-    const float s[3] = {dvs_exp_det(in_s0), dvs_exp_det(in_s1), dvs_exp_det(in_s2)};
-    const float qn = dvs_sqrt_rn(((in_q.x * in_q.x + in_q.y * in_q.y) + in_q.z * in_q.z) + in_q.w * in_q.w);
-    const float inv_qn = 1.0f / qn;
-    const float qr = in_q.x * inv_qn, qx = in_q.y * inv_qn, qy = in_q.z * inv_qn, qz = in_q.w * inv_qn;
-    float R[9];
-    dvs_quat_to_rot(qr, qx, qy, qz, R);
+    const PpFrame fr = pp_frame(in_s0, in_s1, in_s2, in_q);       // (its cov3D is not read here and folds away)
+    const float* s = fr.s, *R = fr.R;
+    const float inv_qn = fr.inv_qn, qr = fr.qr, qx = fr.qx, qy = fr.qy, qz = fr.qz;
     {
 #pragma clang fp contract(fast)
         const float G[9] = {Gs[0], Gs[1], Gs[2], Gs[1], Gs[3], Gs[4], Gs[2], Gs[4], Gs[5]};
@@ -526,6 +515,79 @@ __device__ __forceinline__ void a9_dir_grad(int deg, float x, float y, float z, 
 #undef A9_T
 }
 
+// dL/d(colour) of a (view, splat) from its A8 row, zero where the forward clamped the channel (DVS_FLAG_CLAMP_R/G/B): what A9 uses, what
+// it emits as dcolor, and what k_dcolor_from_rows publishes ahead of it.
+__device__ __forceinline__ void a9_masked_dcolor(uint32_t fl, float4 r1, float r2x, float gc[3]) {
+    const float dL_dcol[3] = {r1.z, r1.w, r2x};
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) gc[ch] = (fl & (1u << ch)) ? 0.f : dL_dcol[ch];
+}
+__device__ __forceinline__ bool a9_dcolor_is_zero(const float gc[3]) { return gc[0] == 0.f && gc[1] == 0.f && gc[2] == 0.f; }
+
+// s_k += shN[k][ch] * gc[ch] over the four elements e = 4c .. 4c + 3 of chunk c of a tiled row (compile-time after unrolling:
+// coefficient k = e/3 + 1, channel e%3; element 44 is the last, coefficients from `ncoef` up are skipped)
+__device__ __forceinline__ void a9_sk_chunk(int c, float4 q, const float gc[3], int ncoef, float sk[16]) {
+    const float qv[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int e = c * 4 + u;
+        if (e < 45 && e / 3 + 1 < ncoef) sk[e / 3 + 1] = __builtin_fmaf(qv[u], gc[e % 3], sk[e / 3 + 1]);
+    }
+}
+// s_k -> dL/d(unit direction) -> projected off the direction, through the normalisation, added to dL/dpos
+__device__ __forceinline__ void a9_dir_to_pos(int deg, const PpDir& d, const float sk[16], float gp[3]) {
+    float gdir[3] = {0.f, 0.f, 0.f};
+    a9_dir_grad(deg, d.ux, d.uy, d.uz, sk, gdir);
+    const float ug = (d.ux * gdir[0] + d.uy * gdir[1]) + d.uz * gdir[2];
+    gp[0] += (gdir[0] - d.ux * ug) * d.inv_dl; gp[1] += (gdir[1] - d.uy * ug) * d.inv_dl; gp[2] += (gdir[2] - d.uz * ug) * d.inv_dl;
+}
+
+// One view's rank-1 contribution to a splat's SH rows held in registers: dL/dsh0 += bas_0 gc, dL/dshN[k] += bas_k gc (basis entries above
+// the degree are zero; explicit FMAs: this file is compiled without contraction for A2's sake, and both users are vector-ALU-bound)
+__device__ __forceinline__ void sh_rows_accumulate(const float bas[16], const float gc[3], float acc0[3], float acc[48]) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) acc0[ch] = __builtin_fmaf(bas[0], gc[ch], acc0[ch]);
+#pragma unroll
+    for (int k = 1; k < 16; ++k)
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) acc[(k - 1) * 3 + ch] = __builtin_fmaf(bas[k], gc[ch], acc[(k - 1) * 3 + ch]);
+}
+// ... and the row of splat i leaves as its twelve float4 chunks (chunk 11 holds element 44 and three pads)
+template <bool ACCUM>
+__device__ __forceinline__ void sh_rows_store_tiled(float* __restrict__ g_shN, int i, const float acc[48]) {
+    float4* d4 = reinterpret_cast<float4*>(g_shN);
+#pragma unroll
+    for (int c = 0; c < 12; ++c) {
+        float4 o = c == 11 ? make_float4(acc[44], 0.f, 0.f, 0.f) : make_float4(acc[c * 4], acc[c * 4 + 1], acc[c * 4 + 2], acc[c * 4 + 3]);
+        const int64_t idx = shn_tiled_f4(i, c);
+        if (ACCUM) { const float4 p = d4[idx]; o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w; }
+        d4[idx] = o;
+    }
+}
+
+// What a lane of either A9 kernel stores itself (the 3-float groups leave through LDS): the optional densification statistics, opacity, rot.
+template <bool ACCUM>
+__device__ __forceinline__ void a9_store_lane(int i, float2 ag, float2 dm, float g_op, const float gq[4], float2* __restrict__ out_absgrad2d,
+                                              float2* __restrict__ out_mean2d, float* __restrict__ g_opacity, float* __restrict__ g_rot) {
+    if (out_absgrad2d) {
+        if (ACCUM) { const float2 o = out_absgrad2d[i]; ag.x += o.x; ag.y += o.y; }
+        out_absgrad2d[i] = ag;
+    }
+    if (out_mean2d) {
+        if (ACCUM) { const float2 o = out_mean2d[i]; dm.x += o.x; dm.y += o.y; }
+        out_mean2d[i] = dm;
+    }
+    if (ACCUM) {
+        g_opacity[i] += g_op;
+        float4 o = reinterpret_cast<float4*>(g_rot)[i];
+        o.x += gq[0]; o.y += gq[1]; o.z += gq[2]; o.w += gq[3];
+        reinterpret_cast<float4*>(g_rot)[i] = o;
+    } else {
+        g_opacity[i] = g_op;
+        reinterpret_cast<float4*>(g_rot)[i] = make_float4(gq[0], gq[1], gq[2], gq[3]);
+    }
+}
+
 template <bool ACCUM, bool TILED>
 __global__ void __launch_bounds__(PP_BLOCK)
 k_preprocess_bwd(int n, const float* __restrict__ pos, const float* __restrict__ shN, const float* __restrict__ opacity,
@@ -571,28 +633,20 @@ k_preprocess_bwd(int n, const float* __restrict__ pos, const float* __restrict__
             const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
             grad_rows[3 * (int64_t)i] = z4; grad_rows[3 * (int64_t)i + 1] = z4; grad_rows[3 * (int64_t)i + 2] = z4;
         }
-        const float dL_dcol[3] = {r1.z, r1.w, r2.x};
         const float px = in_px, py = in_py, pz = in_pz;
         const uint32_t fl = in_fl;
         // 1. colour / SH
-        const float dxw = px - cam.campos[0], dyw = py - cam.campos[1], dzw = pz - cam.campos[2];
-        const float dl = dvs_sqrt_rn((dxw * dxw + dyw * dyw) + dzw * dzw);
-        const float inv_dl = 1.0f / dl;
-        const float ux = dxw * inv_dl, uy = dyw * inv_dl, uz = dzw * inv_dl;
+        const PpDir dir = pp_view_dir(px, py, pz, cam.campos);
         float bas[16];
-        dvs_sh_basis(deg, ux, uy, uz, bas);
+        dvs_sh_basis(deg, dir.ux, dir.uy, dir.uz, bas);
         const int ncoef = (deg + 1) * (deg + 1);
-        float gdir[3] = {0.f, 0.f, 0.f};
         float sk[16];                                        // s_k = sum_ch shN[k][ch] * gc[ch] (a9_dir_grad)
 #pragma unroll
         for (int k = 0; k < 16; ++k) sk[k] = 0.f;
         float gc[3];
+        a9_masked_dcolor(fl, r1, r2.x, gc);
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            gc[ch] = (fl & (1u << ch)) ? 0.f : dL_dcol[ch];
-            gcol[ch] = gc[ch];
-            gs0[ch] = bas[0] * gc[ch];
-        }
+        for (int ch = 0; ch < 3; ++ch) { gcol[ch] = gc[ch]; gs0[ch] = bas[0] * gc[ch]; }
         if (TILED) {
             // twelve float4 chunks: load the parameters of chunk c, emit its four gradient elements, store — nothing is staged
 #pragma unroll
@@ -600,16 +654,11 @@ k_preprocess_bwd(int n, const float* __restrict__ pos, const float* __restrict__
                 const int64_t idx = shn_tiled_f4(i, c);
                 float gv[4] = {0.f, 0.f, 0.f, 0.f};
                 if (c * 4 < (ncoef - 1) * 3) {
-                    const float4 q = p4[idx];
-                    const float qv[4] = {q.x, q.y, q.z, q.w};
+                    a9_sk_chunk(c, p4[idx], gc, ncoef, sk);
 #pragma unroll
                     for (int u = 0; u < 4; ++u) {
                         const int e = c * 4 + u;                     // compile-time: coefficient k = e/3 + 1, channel e%3
-                        if (e < 45 && e / 3 + 1 < ncoef) {
-                            const int k = e / 3 + 1, ch = e % 3;
-                            gv[u] = bas[k] * gc[ch];
-                            sk[k] = __builtin_fmaf(qv[u], gc[ch], sk[k]);
-                        }
+                        if (e < 45 && e / 3 + 1 < ncoef) gv[u] = bas[e / 3 + 1] * gc[e % 3];
                     }
                 }
                 if (g4) {
@@ -632,11 +681,7 @@ k_preprocess_bwd(int n, const float* __restrict__ pos, const float* __restrict__
             }
             for (int e = (ncoef - 1) * 3; e < 45; ++e) row[e] = 0.f;
         }
-        {
-            a9_dir_grad(deg, ux, uy, uz, sk, gdir);
-            const float ug = (ux * gdir[0] + uy * gdir[1]) + uz * gdir[2];
-            gp[0] += (gdir[0] - ux * ug) * inv_dl; gp[1] += (gdir[1] - uy * ug) * inv_dl; gp[2] += (gdir[2] - uz * ug) * inv_dl;
-        }
+        a9_dir_to_pos(deg, dir, sk, gp);
 
         float Gs[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         a9_geometry(cam, px, py, pz, in_s0, in_s1, in_s2, in_q, in_op, fl, r0, r1, antialias, grad_mode, gp, Gs, g_op, dm_out);
@@ -652,27 +697,7 @@ k_preprocess_bwd(int n, const float* __restrict__ pos, const float* __restrict__
         }
     }
 
-    if (valid) {
-        if (out_absgrad2d) {
-            float2 a = make_float2(r2.y, r2.z);
-            if (ACCUM) { const float2 o = out_absgrad2d[i]; a.x += o.x; a.y += o.y; }
-            out_absgrad2d[i] = a;
-        }
-        if (out_mean2d) {
-            float2 mm = dm_out;
-            if (ACCUM) { const float2 o = out_mean2d[i]; mm.x += o.x; mm.y += o.y; }
-            out_mean2d[i] = mm;
-        }
-        if (ACCUM) {
-            g_opacity[i] += g_op;
-            float4 o = reinterpret_cast<float4*>(g_rot)[i];
-            o.x += gq_out[0]; o.y += gq_out[1]; o.z += gq_out[2]; o.w += gq_out[3];
-            reinterpret_cast<float4*>(g_rot)[i] = o;
-        } else {
-            g_opacity[i] = g_op;
-            reinterpret_cast<float4*>(g_rot)[i] = make_float4(gq_out[0], gq_out[1], gq_out[2], gq_out[3]);
-        }
-    }
+    if (valid) a9_store_lane<ACCUM>(i, make_float2(r2.y, r2.z), dm_out, g_op, gq_out, out_absgrad2d, out_mean2d, g_opacity, g_rot);
     // shN gradient rows leave through LDS as coalesced 16-B stores (zero rows when deg == 0); skipped entirely in the
     // factorised multi-GPU mode (g_shN == nullptr: peers rebuild the rows from dcolor, dvs_sh_grad_combine)
     if (!TILED && g_shN) {
@@ -702,8 +727,9 @@ k_preprocess_bwd(int n, const float* __restrict__ pos, const float* __restrict__
 // accumulators, and the geometry gradients (pos, scale, rot, opacity: 44 B) are written once — instead of a read-modify-write of the
 // gradient rows per view. The SH rows are rank-1 in the per-view colour gradient, so this kernel only emits that (dcolor, 12 B per
 // splat and view) and k_sh_grad_combine builds sh0 / shN from it afterwards — on one GPU right away, in data-parallel runs after the
-// all-gather of dcolor (the factorised exchange), with the same kernel. Per view the same expressions in the same order as
-// k_preprocess_bwd, so the pos and opacity gradients of a batch are bit-identical to its views run one by one with opts.accumulate.
+// all-gather of dcolor (the factorised exchange), with the same kernel. Per view it calls what k_preprocess_bwd calls (a9_geometry,
+// a9_masked_dcolor, a9_sk_chunk, a9_dir_to_pos), so the pos and opacity gradients of a batch are bit-identical to its views run one
+// by one with opts.accumulate.
 // The scale and rot gradients are not: a9_sigma_to_params runs once on dL/dSigma summed over the views (contraction allowed there), not
 // once per view — equal to fp32 roundoff.
 template <bool ACCUM, bool FUSE_SH /*build the SH rows here instead of emitting per-view colour gradients (below)*/>
@@ -781,41 +807,23 @@ k_preprocess_bwd_views(DvsCams cams_arg /* MUST stay the first parameter: read t
             float gpv[3] = {0.f, 0.f, 0.f}, g_opv;
             float2 dmv;
             a9_geometry(cam, px, py, pz, in_s0, in_s1, in_s2, in_q, in_op, fl, r0, r1, antialias, grad_mode, gpv, Gs, g_opv, dmv);
-            const float dL_dcol[3] = {r1.z, r1.w, r2.x};
             // colour -> view direction (the SH rows themselves: k_sh_grad_combine)
-            const float dxw = px - cam.campos[0], dyw = py - cam.campos[1], dzw = pz - cam.campos[2];
-            const float dl = dvs_sqrt_rn((dxw * dxw + dyw * dyw) + dzw * dzw);
-            const float inv_dl = 1.0f / dl;
-            const float ux = dxw * inv_dl, uy = dyw * inv_dl, uz = dzw * inv_dl;
-            float gdir[3] = {0.f, 0.f, 0.f};
+            const PpDir dir = pp_view_dir(px, py, pz, cam.campos);
             float sk[16];                                    // s_k = sum_ch shN[k][ch] * gc[ch] (a9_dir_grad)
 #pragma unroll
             for (int k = 0; k < 16; ++k) sk[k] = 0.f;
             float gc[3];
+            a9_masked_dcolor(fl, r1, r2.x, gc);
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) { gc[ch] = (fl & (1u << ch)) ? 0.f : dL_dcol[ch]; gcol[ch] = gc[ch]; }
+            for (int ch = 0; ch < 3; ++ch) gcol[ch] = gc[ch];
             // (a9_dir_grad does not read the sums of the bands above `deg`; with deg == 0 the coefficient registers hold zeros)
 #pragma unroll
-            for (int c = 0; c < 12; ++c) {
-                const float qv[4] = {q4[c].x, q4[c].y, q4[c].z, q4[c].w};
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int e = c * 4 + u;                                 // compile-time: coefficient k = e/3 + 1, channel e%3
-                    if (e < 45) {
-                        const int k = e / 3 + 1, ch = e % 3;
-                        sk[k] = __builtin_fmaf(qv[u], gc[ch], sk[k]);
-                    }
-                }
-            }
+            for (int c = 0; c < 12; ++c) a9_sk_chunk(c, q4[c], gc, 16, sk);
             if (FUSE_SH) {              // the epilogue builds the SH rows from these: what k_sh_grad_combine would re-read and recompute
                 float* lv = l_view + (size_t)view * (6 * PP_BLOCK) + threadIdx.x;
-                lv[0] = gc[0]; lv[PP_BLOCK] = gc[1]; lv[2 * PP_BLOCK] = gc[2]; lv[3 * PP_BLOCK] = ux; lv[4 * PP_BLOCK] = uy; lv[5 * PP_BLOCK] = uz;
+                lv[0] = gc[0]; lv[PP_BLOCK] = gc[1]; lv[2 * PP_BLOCK] = gc[2]; lv[3 * PP_BLOCK] = dir.ux; lv[4 * PP_BLOCK] = dir.uy; lv[5 * PP_BLOCK] = dir.uz;
             }
-            {
-                a9_dir_grad(deg, ux, uy, uz, sk, gdir);
-                const float ug = (ux * gdir[0] + uy * gdir[1]) + uz * gdir[2];
-                gpv[0] += (gdir[0] - ux * ug) * inv_dl; gpv[1] += (gdir[1] - uy * ug) * inv_dl; gpv[2] += (gdir[2] - uz * ug) * inv_dl;
-            }
+            a9_dir_to_pos(deg, dir, sk, gpv);
 #pragma unroll
             for (int k = 0; k < 3; ++k) gp[k] += gpv[k];
             g_op += g_opv;
@@ -834,8 +842,9 @@ k_preprocess_bwd_views(DvsCams cams_arg /* MUST stay the first parameter: read t
     if (vis) a9_sigma_to_params(in_s0, in_s1, in_s2, in_q, Gs, gsc, gq);       // once per splat: linear in the summed dL/dSigma
     // FUSE_SH (round 6; the one-GPU path, where nobody else needs the per-view colour gradients): dL/dsh0 = sum_v SH_C0 gc_v and
     // dL/dshN[k] = sum_v basis_k(dir_v) gc_v are built HERE, after the view loop — its registers are free by now — from the (gc, dir)
-    // pairs the loop left in LDS, with the expressions and the view order of k_sh_grad_combine (bit-identical rows). Saved against the
-    // two-kernel form: 12 B per (view, splat) written and read back, the positions read again, a launch.
+    // pairs the loop left in LDS, in the view order of k_sh_grad_combine<., true>, with its skip test and its row store; the sums are
+    // sh_rows_accumulate, which that kernel has to spell out (see there) — bit-identical rows. Saved against the two-kernel form:
+    // 12 B per (view, splat) written and read back, the positions read again, a launch.
     float acc0[3] = {0.f, 0.f, 0.f};
     if (FUSE_SH) {
         float acc[48];
@@ -845,48 +854,14 @@ k_preprocess_bwd_views(DvsCams cams_arg /* MUST stay the first parameter: read t
             if (!((vis >> view) & 1u)) continue;
             const float* lv = l_view + (size_t)view * (6 * PP_BLOCK) + threadIdx.x;
             const float gc[3] = {lv[0], lv[PP_BLOCK], lv[2 * PP_BLOCK]};
-            if (gc[0] == 0.f && gc[1] == 0.f && gc[2] == 0.f) continue;              // fully clamped in this view
+            if (a9_dcolor_is_zero(gc)) continue;                                     // fully clamped in this view
             float bas[16];
             dvs_sh_basis(deg, lv[3 * PP_BLOCK], lv[4 * PP_BLOCK], lv[5 * PP_BLOCK], bas);
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch) acc0[ch] = __builtin_fmaf(bas[0], gc[ch], acc0[ch]);
-#pragma unroll
-            for (int k = 1; k < 16; ++k)
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch) acc[(k - 1) * 3 + ch] = __builtin_fmaf(bas[k], gc[ch], acc[(k - 1) * 3 + ch]);
+            sh_rows_accumulate(bas, gc, acc0, acc);
         }
-        if (valid) {
-            float4* d4 = reinterpret_cast<float4*>(g_shN);
-#pragma unroll
-            for (int c = 0; c < 12; ++c) {
-                float4 o = c == 11 ? make_float4(acc[44], 0.f, 0.f, 0.f) : make_float4(acc[c * 4], acc[c * 4 + 1], acc[c * 4 + 2], acc[c * 4 + 3]);
-                const int64_t idx = shn_tiled_f4(i, c);
-                if (ACCUM) { const float4 p = d4[idx]; o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w; }
-                d4[idx] = o;
-            }
-        }
+        if (valid) sh_rows_store_tiled<ACCUM>(g_shN, i, acc);
     }
-    if (valid) {
-        if (out_absgrad2d) {
-            float2 a = ag;
-            if (ACCUM) { const float2 q = out_absgrad2d[i]; a.x += q.x; a.y += q.y; }
-            out_absgrad2d[i] = a;
-        }
-        if (out_mean2d) {
-            float2 mm = dm;
-            if (ACCUM) { const float2 q = out_mean2d[i]; mm.x += q.x; mm.y += q.y; }
-            out_mean2d[i] = mm;
-        }
-        if (ACCUM) {
-            g_opacity[i] += g_op;
-            float4 q = reinterpret_cast<float4*>(g_rot)[i];
-            q.x += gq[0]; q.y += gq[1]; q.z += gq[2]; q.w += gq[3];
-            reinterpret_cast<float4*>(g_rot)[i] = q;
-        } else {
-            g_opacity[i] = g_op;
-            reinterpret_cast<float4*>(g_rot)[i] = make_float4(gq[0], gq[1], gq[2], gq[3]);
-        }
-    }
+    if (valid) a9_store_lane<ACCUM>(i, ag, dm, g_op, gq, out_absgrad2d, out_mean2d, g_opacity, g_rot);
     __syncthreads();
     float* l_pos = lds, *l_scl = lds + PP_BLOCK * 3;
 #pragma unroll
@@ -910,6 +885,19 @@ k_preprocess_bwd_views(DvsCams cams_arg /* MUST stay the first parameter: read t
 #define COMBINE_MAX_VIEWS 64
 struct CombineViews { float campos[COMBINE_MAX_VIEWS][3]; };
 
+// One view of a splat in k_sh_grad_combine: its colour gradient dcolor[o] and the SH basis of its view direction.
+// false: the view contributes nothing (the splat is culled or fully clamped there).
+template <typename P>
+__device__ __forceinline__ bool combine_view(const float* __restrict__ dcolor, int64_t o, float px, float py, float pz, P campos, int deg,
+                                             float gc[3], float bas[16]) {
+    const float* gcp = dcolor + o * 3;
+    gc[0] = gcp[0]; gc[1] = gcp[1]; gc[2] = gcp[2];
+    if (a9_dcolor_is_zero(gc)) return false;
+    const PpDir d = pp_view_dir(px, py, pz, campos);
+    dvs_sh_basis(deg, d.ux, d.uy, d.uz, bas);
+    return true;
+}
+
 template <bool ACCUM, bool TILED>
 __global__ void __launch_bounds__(PP_BLOCK)
 k_sh_grad_combine(CombineViews views_arg /* MUST stay the first parameter: read through the kernarg pointer below */, int n,
@@ -920,66 +908,38 @@ k_sh_grad_combine(CombineViews views_arg /* MUST stay the first parameter: read 
     // read-only memory: address it directly (scalar loads with a dynamic offset).
     (void)views_arg;
     typedef const __attribute__((address_space(4))) CombineViews* KernargViews;
-    const KernargViews vp = (KernargViews)__builtin_amdgcn_kernarg_segment_ptr();
-#define views (*vp)
+    const KernargViews views = (KernargViews)__builtin_amdgcn_kernarg_segment_ptr();
     extern __shared__ __attribute__((aligned(16))) float lds[];   // ROWS: [PP_BLOCK*45] + [PP_BLOCK*3]; TILED: [PP_BLOCK*3]
     const int64_t base = (int64_t)blockIdx.x * PP_BLOCK;
     const int i = (int)(base + threadIdx.x);
     float* l_sh0 = TILED ? lds : lds + PP_BLOCK * 45;
     float acc0[3] = {0.f, 0.f, 0.f};
+    // Where the 45 sums live is all that differs. TILED: in registers (an LDS row per lane made this kernel LDS-bound: one
+    // read-modify-write per FMA), the k loop fully unrolled, and the twelve float4 chunks leave straight from registers.
+    // ROWS: in the lane's LDS row, which leaves through stage_rows_out.
+    float acc[48];
+    float* row = lds + threadIdx.x * 45;
     if (TILED) {
-        // the 45 sums stay in registers (an LDS row per lane made this kernel LDS-bound: one read-modify-write per FMA), the
-        // k loop is fully unrolled (basis entries above `deg` are zero), and the twelve float4 chunks leave straight from registers
-        float acc[48];
 #pragma unroll
         for (int e = 0; e < 48; ++e) acc[e] = 0.f;
-        if (i < n) {
-            const float px = pos[3 * (int64_t)i], py = pos[3 * (int64_t)i + 1], pz = pos[3 * (int64_t)i + 2];
-            for (int v = 0; v < n_views; ++v) {
-                const float* gcp = dcolor + ((int64_t)v * n + i) * 3;
-                const float gc[3] = {gcp[0], gcp[1], gcp[2]};
-                if (gc[0] == 0.f && gc[1] == 0.f && gc[2] == 0.f) continue;          // culled / fully clamped in this view
-                const float dxw = px - views.campos[v][0], dyw = py - views.campos[v][1], dzw = pz - views.campos[v][2];
-                const float dl = dvs_sqrt_rn((dxw * dxw + dyw * dyw) + dzw * dzw);
-                const float inv_dl = 1.0f / dl;
-                float bas[16];
-                dvs_sh_basis(deg, dxw * inv_dl, dyw * inv_dl, dzw * inv_dl, bas);
-                // (explicit FMAs: this file is compiled without contraction for A2's sake, and the kernel is 60 % vector-ALU-busy)
+    } else {
+        for (int e = 0; e < 45; ++e) row[e] = 0.f;
+    }
+    if (i < n) {
+        const float px = pos[3 * (int64_t)i], py = pos[3 * (int64_t)i + 1], pz = pos[3 * (int64_t)i + 2];
+        const int ncoef = (deg + 1) * (deg + 1);
+        for (int v = 0; v < n_views; ++v) {
+            float gc[3], bas[16];
+            if (!combine_view(dcolor, (int64_t)v * n + i, px, py, pz, views->campos[v], deg, gc, bas)) continue;
+            if (TILED) {
+                // sh_rows_accumulate, written out: through the call the SLP vectoriser carries every sum twice (128 VGPRs instead of 84 / 96, a wave less)
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) acc0[ch] = __builtin_fmaf(bas[0], gc[ch], acc0[ch]);
 #pragma unroll
                 for (int k = 1; k < 16; ++k)
 #pragma unroll
                     for (int ch = 0; ch < 3; ++ch) acc[(k - 1) * 3 + ch] = __builtin_fmaf(bas[k], gc[ch], acc[(k - 1) * 3 + ch]);
-            }
-            float4* d4 = reinterpret_cast<float4*>(g_shN);
-#pragma unroll
-            for (int c = 0; c < 12; ++c) {
-                float4 o = c == 11 ? make_float4(acc[44], 0.f, 0.f, 0.f)          // chunk 11 holds element 44 and three pads
-                                   : make_float4(acc[c * 4], acc[c * 4 + 1], acc[c * 4 + 2], acc[c * 4 + 3]);
-                const int64_t idx = shn_tiled_f4(i, c);
-                if (ACCUM) { const float4 p = d4[idx]; o.x += p.x; o.y += p.y; o.z += p.z; o.w += p.w; }
-                d4[idx] = o;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) l_sh0[threadIdx.x * 3 + k] = acc0[k];
-        __syncthreads();
-    } else {
-        float* row = lds + threadIdx.x * 45;
-        for (int e = 0; e < 45; ++e) row[e] = 0.f;
-        if (i < n) {
-            const float px = pos[3 * (int64_t)i], py = pos[3 * (int64_t)i + 1], pz = pos[3 * (int64_t)i + 2];
-            const int ncoef = (deg + 1) * (deg + 1);
-            for (int v = 0; v < n_views; ++v) {
-                const float* gcp = dcolor + ((int64_t)v * n + i) * 3;
-                const float gc[3] = {gcp[0], gcp[1], gcp[2]};
-                if (gc[0] == 0.f && gc[1] == 0.f && gc[2] == 0.f) continue;
-                const float dxw = px - views.campos[v][0], dyw = py - views.campos[v][1], dzw = pz - views.campos[v][2];
-                const float dl = dvs_sqrt_rn((dxw * dxw + dyw * dyw) + dzw * dzw);
-                const float inv_dl = 1.0f / dl;
-                float bas[16];
-                dvs_sh_basis(deg, dxw * inv_dl, dyw * inv_dl, dzw * inv_dl, bas);
+            } else {
 #pragma unroll
                 for (int ch = 0; ch < 3; ++ch) acc0[ch] += bas[0] * gc[ch];
                 for (int k = 1; k < ncoef; ++k)
@@ -987,13 +947,13 @@ k_sh_grad_combine(CombineViews views_arg /* MUST stay the first parameter: read 
                     for (int ch = 0; ch < 3; ++ch) row[(k - 1) * 3 + ch] += bas[k] * gc[ch];
             }
         }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) l_sh0[threadIdx.x * 3 + k] = acc0[k];
-        __syncthreads();
-        stage_rows_out<45, ACCUM>(g_shN, lds, base, n);
+        if (TILED) sh_rows_store_tiled<ACCUM>(g_shN, i, acc);
     }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) l_sh0[threadIdx.x * 3 + k] = acc0[k];
+    __syncthreads();
+    if (!TILED) stage_rows_out<45, ACCUM>(g_shN, lds, base, n);
     stage_rows_out<3, ACCUM>(g_sh0, l_sh0, base, n);
-#undef views
 }
 
 // ---- relayout between the reference rows [n][45] and the tiled layout --------------------------------------------------
@@ -1033,20 +993,26 @@ k_shn_relayout(int n, const float* __restrict__ src, float* __restrict__ dst, in
 }
 
 // ---- launchers -----------------------------------------------------------------------------------
+// The splats [i0, i1) of a chunk-capable launch — [first, first + count) clipped to [0, n), count < 0 = up to n — and its
+// workgroups (0: nothing to do).
+static int pp_chunk_grid(int n, int first, int count, int* i0, int* i1) {
+    *i0 = first < 0 ? 0 : first;
+    *i1 = count < 0 ? n : (first + count < n ? first + count : n);
+    return (n <= 0 || *i1 <= *i0) ? 0 : (*i1 - *i0 + PP_BLOCK - 1) / PP_BLOCK;
+}
 hipError_t dvs_launch_preprocess_fwd(hipStream_t st, int n, const float* pos, const float* sh0, const float* shN,
                                      const float* opacity, const float* scale, const float* rot, const DvsCams& cams, int n_views,
                                      int deg, int antialias, int tiles_x, int tiles_y, int* radii, float* splat2d,
                                      float* depth, uint32_t* flags,
-                                     uint32_t* tiles_touched, uint32_t* depth_key, uint32_t* ids, int shn_tiled, uint32_t* rect, uint32_t* rect16,
-                                     uint32_t* rect8, uint32_t* kred, int first, int count) {
-    if (n <= 0) return hipSuccess;
-    const int i0 = first < 0 ? 0 : first, i1 = count < 0 ? n : (first + count < n ? first + count : n);
-    if (i1 <= i0) return hipSuccess;
-    const int grid = (i1 - i0 + PP_BLOCK - 1) / PP_BLOCK;
+                                     uint32_t* tiles_touched, uint32_t* depth_key, int shn_tiled, uint32_t* rect, int rect_fmt,
+                                     uint32_t* kred, int first, int count) {
+    int i0, i1;
+    const int grid = pp_chunk_grid(n, first, count, &i0, &i1);
+    if (grid == 0) return hipSuccess;
     if (shn_tiled) {
 #define DVS_A2(T, M, LDS) hipLaunchKernelGGL((k_preprocess_fwd<T, M>), dim3(grid), dim3(PP_BLOCK), LDS, st, cams, n_views, n, pos, sh0, shN, opacity, \
                                              scale, rot, deg, antialias, tiles_x, tiles_y, radii, (float4*)splat2d, depth, flags,          \
-                                             tiles_touched, depth_key, ids, (uint2*)rect, (uint4*)rect16, rect8, kred, i0, i1)
+                                             tiles_touched, depth_key, (void*)rect, rect_fmt, kred, i0, i1)
         if (n_views > 1) DVS_A2(true, true, 0); else DVS_A2(true, false, 0);
     } else {
         const size_t lds = deg > 0 ? (size_t)PP_BLOCK * 45 * sizeof(float) : 0;
@@ -1081,10 +1047,10 @@ hipError_t dvs_launch_preprocess_bwd_views(hipStream_t st, int n, int n_views, c
                                            const int* radii, const uint32_t* flags, float* grad_rows, float* g_pos, float* g_opacity,
                                            float* g_scale, float* g_rot, float* out_absgrad2d, float* out_mean2d, float* out_dcolor,
                                            int accumulate, int rezero, int grad_mode, int first, int count, float* g_sh0, float* g_shN) {
-    if (n <= 0 || n_views <= 0) return hipSuccess;
-    const int i0 = first < 0 ? 0 : first, i1 = count < 0 ? n : (first + count < n ? first + count : n);
-    if (i1 <= i0) return hipSuccess;
-    const int grid = (i1 - i0 + PP_BLOCK - 1) / PP_BLOCK;
+    if (n_views <= 0) return hipSuccess;
+    int i0, i1;
+    const int grid = pp_chunk_grid(n, first, count, &i0, &i1);
+    if (grid == 0) return hipSuccess;
     const bool fuse = g_sh0 && g_shN;               // the SH rows are built in the kernel's epilogue; out_dcolor is not written
     const size_t lds = (size_t)PP_BLOCK * (6 + (fuse ? 6 * n_views : 0)) * sizeof(float);
 #define DVS_PPV1(A, F)                                                                                                        \
@@ -1119,7 +1085,7 @@ hipError_t dvs_launch_sh_grad_combine(hipStream_t st, int n, const float* pos, i
 }
 
 // ---- colour gradients straight from the A8 rows (before A9) ----------------------------------------------------------------
-// dcolor[o] = dL/d(colour) of (view, splat) o with the clamped channels masked — exactly what A9 emits — so that a data-parallel
+// dcolor[o] = dL/d(colour) of (view, splat) o with the clamped channels masked — what A9 emits (a9_masked_dcolor) — so that a data-parallel
 // trainer can start the all-gather of the colour gradients while A9 is still running.
 __global__ void __launch_bounds__(PP_BLOCK)
 k_dcolor_from_rows(int64_t total, const int* __restrict__ radii, const uint32_t* __restrict__ flags, const float4* __restrict__ rows,
@@ -1132,7 +1098,7 @@ k_dcolor_from_rows(int64_t total, const int* __restrict__ radii, const uint32_t*
         const float4 r1 = rows[3 * o + 1];
         const float r2x = rows[3 * o + 2].x;
         const uint32_t fl = flags[o];
-        g[0] = (fl & 1u) ? 0.f : r1.z; g[1] = (fl & 2u) ? 0.f : r1.w; g[2] = (fl & 4u) ? 0.f : r2x;
+        a9_masked_dcolor(fl, r1, r2x, g);
     }
 #pragma unroll
     for (int k = 0; k < 3; ++k) l_col[threadIdx.x * 3 + k] = g[k];
