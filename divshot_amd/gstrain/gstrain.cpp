@@ -677,7 +677,7 @@ void GaussianTrainerScene::Impl::render_backward(Step& s) {
     dvs_splat_grads g{};
     g.pos = d_grad[P_POS]; g.sh0 = d_grad[P_SH0]; g.shN = d_grad[P_SHN]; g.opacity = d_grad[P_OPA];
     g.scale = d_grad[P_SCALE]; g.rot = d_grad[P_ROT]; g.absgrad2d = s.absgrad ? d_absgrad : nullptr;
-    g.mean2d = (s.want_stats && !s.absgrad) ? d_mean2d : nullptr;          // ADC without abs-grad: the norm of dL/dmean2D is the statistic
+    g.mean2d = (s.want_stats && !s.absgrad) ? d_mean2d : nullptr;          // ADC without abs-grad: dL/dmean2D feeds the statistic
     if (fact) { g.sh0 = nullptr; g.shN = nullptr; }                          // (the SH rows are rebuilt after the exchange)
     for (int v = 0; v < passes; ++v) {                                      // v: the first view of the pass
         const dvs_camera* cam = &s.vcams[(size_t)v];
@@ -727,12 +727,14 @@ void GaussianTrainerScene::Impl::render_backward(Step& s) {
             DVS_OR_THROW(dvs_raster_backward_project(ctx, stream, &sp, cam, &opts, &g));
         }
         if (s.want_stats && !s.absgrad) {
-            // the standard rule: |dL/dmean2D| of the view, threshold growGrad2d (0.0002). The multi-view pass hands out the SUM over the
-            // views of dL/dmean2D: its norm is accumulated once per step for splats visible in at least one view (for V = 1 the reference
-            // rule; documented difference for V > 1)
+            // the standard rule, threshold growGrad2d (0.0002): hypot(gx W/2, gy H/2) of the view's dL/dmean2D (pixel units) per visible
+            // splat. One view per step: the signed components go to dvs_densify_accumulate as they are — it scales each by (W/2, H/2)
+            // and takes the norm. The multi-view pass hands out the SUM over the views of dL/dmean2D: its norm is taken FIRST (k_norm2:
+            // (|g|, 0)), so that what is accumulated, once per step for splats visible in at least one view, is |sum g| W/2 — both
+            // components scaled by W/2 (documented difference for V > 1)
             if (v > 0) throw std::runtime_error("gstrain: DVS_VIEWS_MODE=sequential with useAbsGrad off needs per-view mean2d rows (use the multi-view pass)");
-            const int* radii = seq ? fwd.radii : any_view_radii();
-            hipLaunchKernelGGL(k_norm2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_mean2d, d_mean2d, n);
+            const int* radii = seq || vpi == 1 ? fwd.radii : any_view_radii();
+            if (vpi > 1) hipLaunchKernelGGL(k_norm2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_mean2d, d_mean2d, n);
             DVS_OR_THROW(dvs_densify_accumulate(stream, n, radii, d_mean2d, W, H, d_grad_accum, d_denom, d_max_radii));
         }
     }

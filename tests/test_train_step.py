@@ -104,14 +104,15 @@ def _run(args, timeout=600, env=None):
     return p
 
 
-def _hip_targets(spec, cams, sh):
-    """The plugin's training views: the generating scene rendered by the HIP forward (same call, same options as load_synthetic)."""
+def _hip_targets(spec, cams, sh, antialias=False):
+    """The plugin's training views: the generating scene rendered by the HIP forward (same call, same options as load_synthetic:
+    --mipAntiliased applies to them too)."""
     import torch
     from divshot_amd.raster import Rasterizer, params_to_device
     gt = dv.synth_splats(spec)
     r = Rasterizer(0, max_splats=spec.n, max_w=spec.width, max_h=spec.height)
     P = params_to_device(gt, torch.device("cuda", 0))
-    out = [r.forward(P, c, sh_degree=sh).detach().cpu().numpy().copy() for c in cams]
+    out = [r.forward(P, c, sh_degree=sh, antialias=antialias).detach().cpu().numpy().copy() for c in cams]
     r.close()
     return out
 

@@ -8,7 +8,13 @@ this build's plugin defines (divshot_amd/gstrain/gstrain.cpp trainStep) from ind
   ((1 - w) sign(out - target) / (3 W H) - w dSSIM/dout; w = --ssim, 0 = L1 only; the SSIM and its gradient restated analytically below)
   -> oracle backward in DVS_GRAD_LINEAGE -> per-group Adam in numpy (beta 0.9 / 0.999, eps 1e-15, bias-corrected) with the learning
   rates of gaussian_trainer_scene.hpp (position: extent x exponential decay) -> abs-grad densification statistics
-  (sqrt((|gx| W/2)^2 + (|gy| H/2)^2) per visible splat, denominator + 1).
+  (sqrt((|gx| W/2)^2 + (|gy| H/2)^2) per visible splat, denominator + 1), and the statistic of `--absgrad 0`, the same expression on the
+  signed dL/dmean2D.
+
+Options of the step, each off by default (the host flags of gstrain.cpp plan_step / loss_of_view / trainStep): start_step (a resume
+through --load_itr), progressive (SH degree min(sh, step // 1000)), antialias, pack_u8 (8-bit training views), mask (the synthetic
+inscribed-ellipse mask on the photometric gradient), reset_alpha_every (the opacity reset inside the step) and the light prune
+(prune_decisions / apply_prune).
 
 dtype float32 mirrors the arithmetic the plugin performs; float64 is the ground truth of the same recurrences. The parity test compares
 the plugin with the float64 trajectory on every element where the float32 restatement itself stays within tolerance of it: Adam with
@@ -77,6 +83,33 @@ def camera_stream(n_cams, count, single_camera=False):
     return out
 
 
+def pack_unpack_u8(t):
+    """--packLevel 1 (k_pack_u8 then k_unpack_u8): a view stored as 8 bits per channel and expanded again, in the kernels' float32
+    operation order — float32(rint(clip(t * 255, 0, 255))) * float32(1 / 255); rint rounds half to even."""
+    q = np.rint(np.clip(np.asarray(t, np.float32) * np.float32(255.0), np.float32(0.0), np.float32(255.0))).astype(np.float32)
+    return q * np.float32(1.0 / 255.0)
+
+
+def ellipse_mask(W, H):
+    """--useMask on a synthetic scene (gstrain.cpp load_synthetic): 1 inside the ellipse inscribed in the image, 0 outside; pixel
+    centres u = (x + 0.5) / W * 2 - 1, v likewise, u^2 + v^2 <= 1, evaluated in float32 as the plugin does. -> [H, W] float32"""
+    f = np.float32
+    u = (np.arange(W, dtype=np.float32) + f(0.5)) / f(W) * f(2.0) - f(1.0)
+    v = (np.arange(H, dtype=np.float32) + f(0.5)) / f(H) * f(2.0) - f(1.0)
+    return (u[None, :] * u[None, :] + v[:, None] * v[:, None] <= f(1.0)).astype(np.float32)
+
+
+def sh_degree_at(step, sh_degree, progressive=True):
+    """the SH degree a step trains at: one more band every 1000 steps with --progressTrain 1 (gstrain.cpp sh_degree_at)"""
+    return min(sh_degree, step // 1000) if progressive else sh_degree
+
+
+def shn_active_chunks(deg):
+    """float4 chunks of a splat's 45 (+3 pad) higher-order SH floats that hold the bands up to `deg`: ceil(3 ((deg + 1)^2 - 1) / 4)
+    (what plan_step hands the Adam kernel; at degree 3 the product passes 0 = all twelve)"""
+    return -(-3 * ((deg + 1) ** 2 - 1) // 4)
+
+
 def scene_extent(cams):
     """1.1 x the largest distance of a camera centre from their mean; tiny rigs fall back to 5 (gstrain.cpp load_synthetic)."""
     c = np.array([[cam.campos[0], cam.campos[1], cam.campos[2]] for cam in cams], np.float64)
@@ -86,13 +119,20 @@ def scene_extent(cams):
 
 class TrainStepRef:
     def __init__(self, oracle_cls, cams, targets, init, sh_degree, num_iters, dtype=np.float32, views_per_step=1, world=1, lr=None,
-                 ssim_weight=0.0, mcmc_reg=None):
+                 ssim_weight=0.0, mcmc_reg=None, start_step=0, progressive=False, antialias=False, pack_u8=False, mask=False,
+                 reset_alpha_every=0):
         """ssim_weight: w of L = (1 - w) mean|x - y| + w (1 - mean SSIM) (--ssim, main.cpp:24: 0.2; 0 = L1 only).
-        mcmc_reg: (opacity_reg, scale_reg) of densifyStrategy 1 (gstrain.cpp: 0.01, 0.01), added to the summed gradients once per step."""
+        mcmc_reg: (opacity_reg, scale_reg) of densifyStrategy 1 (gstrain.cpp: 0.01, 0.01), added to the summed gradients once per step.
+        start_step: a resume through --load_itr — the step number (Adam bias correction, position-rate schedule, SH degree) starts there,
+        the moments at zero and the camera stream at its seed. progressive: --progressTrain 1. antialias: --mipAntiliased 1.
+        pack_u8: --packLevel 1, the targets go through 8 bits. mask: --useMask 1, the photometric gradient (not the reported loss) is
+        multiplied by ellipse_mask. reset_alpha_every: --resetAlphaEvery, applied after the Adam step of iterations it % r == 0."""
         self.w_ssim, self.mcmc_reg = float(ssim_weight), mcmc_reg
         self.dt = np.dtype(dtype)
         self.orc = oracle_cls(self.dt)
-        self.cams, self.targets = cams, [np.asarray(t, self.dt) for t in targets]
+        self.progressive, self.antialias, self.reset_every = bool(progressive), bool(antialias), int(reset_alpha_every)
+        self.cams, self.targets = cams, [np.asarray(pack_unpack_u8(t) if pack_u8 else t, self.dt) for t in targets]
+        self.mask = [np.asarray(ellipse_mask(c.width, c.height), self.dt) for c in cams] if mask else None
         self.P = {k: np.array(init[k], self.dt) for k in KEYS}
         self.P["shN"] = self.P["shN"].reshape(-1, 15, 3)
         self.M = {k: np.zeros_like(v) for k, v in self.P.items()}
@@ -101,11 +141,15 @@ class TrainStepRef:
         self.views, self.world = views_per_step, world
         self.extent = scene_extent(cams)
         self.lr = dict(LR, **(lr or {}))
-        self.step = 0
+        self.step = self.start = int(start_step)
         n = self.P["pos"].shape[0]
         self.order = camera_stream(len(cams), 4096 * views_per_step * world)
         self.grad_accum, self.denom, self.max_radii = np.zeros(n, self.dt), np.zeros(n, self.dt), np.zeros(n, np.int32)
+        self.grad_accum_mean2d = np.zeros(n, self.dt)         # the statistic of --absgrad 0
         self.losses = []
+
+    def degree(self):
+        return sh_degree_at(self.step, self.deg, self.progressive)
 
     def learning_rates(self):
         f = self.dt.type
@@ -118,12 +162,13 @@ class TrainStepRef:
         """Sum over the step's views (all ranks' views: the exchange sums them) of the L1 loss gradient; also the statistics."""
         f = self.dt.type
         n_views = self.views * self.world
-        draws = self.order[self.step * n_views:(self.step + 1) * n_views]
+        k = self.step - self.start                              # the camera stream restarts with the process
+        draws = self.order[k * n_views:(k + 1) * n_views]
         G = {k: np.zeros_like(v) for k, v in self.P.items()}
         loss = 0.0
         for ci in draws:
             cam, tgt = self.cams[ci], self.targets[ci]
-            out = self.orc.forward(self.P, cam, sh_degree=self.deg, antialias=False, absgrad=True, grad_mode=1)
+            out = self.orc.forward(self.P, cam, sh_degree=self.degree(), antialias=self.antialias, absgrad=True, grad_mode=1)
             d = out - tgt
             scale = f(1.0) / f(d.size)
             w = f(self.w_ssim)
@@ -133,14 +178,17 @@ class TrainStepRef:
                 val, gs = ssim_and_grad(np.ascontiguousarray(out, self.dt), tgt)
                 dL = (dL - w * gs).astype(self.dt)
                 loss += self.w_ssim * (1.0 - val)
+            if self.mask is not None:                       # after the L1 / SSIM mix; the loss above stays unmasked (k_mask_mul: dL only)
+                dL = (dL * self.mask[ci][None]).astype(self.dt)
             g = self.orc.backward(dL, grad_mode=1)
             for k in KEYS:
                 G[k] += g[k].reshape(G[k].shape)
             radii = self.orc.get("radii")
-            ag = self.orc.get("absgrad")
+            ag, gm = self.orc.get("absgrad"), self.orc.get("dL_dmean2d")
             vis = radii > 0
             W, H = cam.width, cam.height
             self.grad_accum += np.where(vis, np.hypot(ag[:, 0] * f(0.5 * W), ag[:, 1] * f(0.5 * H)), 0).astype(self.dt)
+            self.grad_accum_mean2d += np.where(vis, np.hypot(gm[:, 0] * f(0.5 * W), gm[:, 1] * f(0.5 * H)), 0).astype(self.dt)
             self.denom += vis.astype(self.dt)
             self.max_radii = np.maximum(self.max_radii, np.where(vis, radii, 0))
         self.losses.append(loss / len(draws))
@@ -158,11 +206,14 @@ class TrainStepRef:
         b1, b2, eps = f(0.9), f(0.999), f(1e-15)
         bc1, bc2 = f(1.0) / (f(1.0) - b1 ** f(it)), f(1.0) / (f(1.0) - b2 ** f(it))
         lr = self.learning_rates()
+        deg = self.degree()
         for k in KEYS:
             g = G[k]
             if k == "shN":                                   # only the float4 chunks of the active SH bands are stepped (zero gradient above them anyway)
+                if deg == 0:                                 # no shN step at all at degree 0 (plan_step: count = 0)
+                    continue
                 g = g.copy()
-                g[:, (self.deg + 1) ** 2 - 1:, :] = 0
+                g[:, (deg + 1) ** 2 - 1:, :] = 0
             self.M[k] = b1 * self.M[k] + (f(1.0) - b1) * g
             self.V[k] = b2 * self.V[k] + (f(1.0) - b2) * g * g
             self.P[k] = (self.P[k] - lr[k] * (self.M[k] * bc1) / (np.sqrt(self.V[k] * bc2) + eps)).astype(self.dt)
@@ -171,14 +222,39 @@ class TrainStepRef:
         G = self.gradients()
         self.adam(G)
         self.step += 1
+        if self.reset_every > 0 and self.step % self.reset_every == 0:      # trainStep reset_now -> dvs_reset_opacity(0.01)
+            f = self.dt.type
+            self.P["opacity"] = np.minimum(self.P["opacity"], np.log(f(0.01) / (f(1.0) - f(0.01)))).astype(self.dt)
+            self.M["opacity"][:] = 0
+            self.V["opacity"][:] = 0
         return G
 
-    # ---- ADC refinement decision of gstrain.cpp densify() / densify.hip d_action (before any opacity reset) --------------------------
-    def adc_actions(self, grow_grad2d, min_opacity=0.005):
-        """0 keep, 1 clone, 2 split, 3 prune — and the margin of each decision (relative distance to its nearest threshold)."""
+    # ---- light prune of gstrain.cpp prune_light() (pruneStrategy > 0, after refinement has stopped) ----------------------------------
+    def prune_decisions(self, prune_opacity=0.005, min_opacity=0.005, prune_scale3d=0.1):
+        """-> (prune [n] bool, margin [n]): a splat goes when sigmoid(opacity) < max(pruneOpacity, min_opacity) or max exp(scale) >
+        pruneScale3d x extent; margin = relative distance to the nearer threshold."""
         op = 1.0 / (1.0 + np.exp(-self.P["opacity"].astype(np.float64)))
         smax = np.exp(self.P["scale"].max(1).astype(np.float64))
-        avg = np.where(self.denom > 0, self.grad_accum.astype(np.float64) / np.maximum(self.denom, 1), 0.0)
+        thr_o, thr_s = max(prune_opacity, min_opacity), prune_scale3d * self.extent
+        return (op < thr_o) | (smax > thr_s), np.minimum(np.abs(op - thr_o) / thr_o, np.abs(smax - thr_s) / thr_s)
+
+    def apply_prune(self, keep):
+        """compacts the parameters and both Adam moments of all six groups in order (apply_plan with zero_moments = false)"""
+        keep = np.asarray(keep, bool)
+        for D in (self.P, self.M, self.V):
+            for k in KEYS:
+                D[k] = np.ascontiguousarray(D[k][keep])
+        self.grad_accum, self.denom, self.max_radii = (np.zeros(int(keep.sum()), a.dtype) for a in (self.grad_accum, self.denom, self.max_radii))
+        self.grad_accum_mean2d = np.zeros(int(keep.sum()), self.dt)
+
+    # ---- ADC refinement decision of gstrain.cpp densify() / densify.hip d_action (before any opacity reset) --------------------------
+    def adc_actions(self, grow_grad2d, min_opacity=0.005, stat="absgrad"):
+        """0 keep, 1 clone, 2 split, 3 prune — and the margin of each decision (relative distance to its nearest threshold).
+        stat: "absgrad" (--absgrad 1) or "mean2d" (--absgrad 0: hypot(gx W/2, gy H/2) of the signed dL/dmean2D)."""
+        accum = {"absgrad": self.grad_accum, "mean2d": self.grad_accum_mean2d}[stat]
+        op = 1.0 / (1.0 + np.exp(-self.P["opacity"].astype(np.float64)))
+        smax = np.exp(self.P["scale"].max(1).astype(np.float64))
+        avg = np.where(self.denom > 0, accum.astype(np.float64) / np.maximum(self.denom, 1), 0.0)
         thr_s = 0.01 * self.extent
         act = np.where(op < min_opacity, 3, np.where(avg >= grow_grad2d, np.where(smax > thr_s, 2, 1), 0))
         margin = np.minimum(np.abs(op - min_opacity) / min_opacity, np.abs(avg - grow_grad2d) / grow_grad2d)
