@@ -20,15 +20,15 @@ hipError_t dvs_launch_preprocess_bwd(hipStream_t st, int n, const float* pos, co
                                      float* g_rot, float* out_absgrad2d /*nullable*/, float* out_mean2d /*nullable*/,
                                      float* out_dcolor /*nullable*/, int accumulate, int rezero_rows, int shn_tiled, int grad_mode);
 // A9 for all views of a batch in one pass (DVS_SHN_TILED layout only): radii / flags / grad_rows are [n_views][n]; writes the
-// geometry gradients (sums over the views) and out_dcolor [n_views][n][3]; the SH rows follow from dcolor (dvs_launch_sh_grad_combine)
+// geometry gradients (sums over the views) and out_dcolor [n_views][n][3]; the SH rows follow from dcolor (dvs_launch_sh_grad_combine).
+// [first, first + count) is the splat range of this launch (A9 can run in chunks). g_sh0 / g_shN both given: the kernel builds the SH
+// rows itself (tiled layout) from the views' colour gradients and does NOT write out_dcolor — the one-GPU path.
 hipError_t dvs_launch_preprocess_bwd_views(hipStream_t st, int n, int n_views, const float* pos, const float* shN, const float* opacity,
                                            const float* scale, const float* rot, const DvsCams& cams, int deg, int antialias,
                                            const int* radii, const uint32_t* flags, float* grad_rows, float* g_pos, float* g_opacity,
                                            float* g_scale, float* g_rot, float* out_absgrad2d, float* out_mean2d, float* out_dcolor,
-                                           int accumulate, int rezero_rows, int grad_mode, int first = 0, int count = -1 /*splat range of this
-                                           launch: [first, first + count), count < 0 = up to n*/,
-                                           float* g_sh0 = nullptr, float* g_shN = nullptr /*both given: the kernel builds the SH rows itself
-                                           (tiled layout) from the views' colour gradients and does NOT write out_dcolor — the one-GPU path*/);
+                                           int accumulate, int rezero_rows, int grad_mode, int first, int count, float* g_sh0 /*nullable*/,
+                                           float* g_shN /*nullable*/);
 // g_sh0 / g_shN may be nullptr in dvs_launch_preprocess_bwd (factorised exchange); this rebuilds them from dcolor[n_views,n,3].
 hipError_t dvs_launch_sh_grad_combine(hipStream_t st, int n, const float* pos, int deg, int n_views, const float* campos_host,
                                       const float* dcolor, float* g_sh0, float* g_shN, int accumulate, int shn_tiled);
@@ -90,7 +90,7 @@ template <> struct FeRect<DVS_FE_RECT_TIGHT> {
     static __device__ __forceinline__ T zero() { return make_uint4(0u, 0u, 0u, 0u); }
 };
 #define DVS_FE_KRED_WORDS (DVS_MAX_VIEWS * 64 * 16)        /* key-range slots: [view][64][16 words] */
-#define DVS_FE_MAXBINS 2048
+#define DVS_FE_MAXBINS 2048                                     /* 11-bit digits: 3 x 11 >= 31 bits, every positive float's range */
 #define DVS_FE_SUPER_STRIDE 32                                  /* u64 words between two super-sum counters (256 B: own memory channel) */
 size_t dvs_fe_hist_words(uint64_t max_elems, int n_views, int max_bins);       // histogram table words for sorts of up to max_elems elements in n_views segments
 uint32_t dvs_depth_sort_rows_per_view(int n, int V);

@@ -28,7 +28,7 @@
 
 #define FE_BLOCK 256
 #define FE_WAVES (FE_BLOCK / 64)
-#define FE_MAXBINS 2048           // 11-bit digits: 3 x 11 >= 31 bits, every positive float's range
+#define FE_MAXBINS DVS_FE_MAXBINS // (dvs_kernels.h: the host sizes the totals table with it)
 #define FE_REORDER_BITS 9         // digits up to this width are re-ordered in LDS before the global stores
 #define FE_CULLED 0xFFFFFFFFu
 

@@ -1086,6 +1086,45 @@ def test_forward_prepared_in_chunks_equals_forward(gpu_device):
     r.close()
 
 
+def test_depth_sort_hook_drops_a_prepared_forward(gpu_device):
+    """dvs_debug_sort_depth_keys overwrites A2's outputs (the depth keys and the key-range slots): a complete preparation made before
+    it no longer describes the arenas. The forward that follows, with the prepared inputs, must project by itself again — image and
+    saved integer arrays are those of the plain forward, not a sort of the hook's keys."""
+    import torch
+    from divshot_amd.raster import Rasterizer, params_to_device
+    from divshot_amd import _lib as _l
+    n, W, H, V = 6007, 208, 120, 3
+    spec = dv.make_spec(n, W, H, sh_degree=3, n_cams=4, seed=61)
+    P = dv.synth_splats(spec)
+    cams = [dv.synth_camera(spec, i + 1) for i in range(V)]
+    r = Rasterizer(0, max_splats=n, max_w=W, max_h=H, max_views=V)
+    Pd = params_to_device(P, r.tdev)
+    Pd["shN"] = r.shn_relayout(Pd["shN"], n, to_tiled=True)
+    ref = r.forward_views(Pd, cams, sh_degree=3, absgrad=True, shn_tiled=True).clone()
+    ref_saved = [r.view_saved(v) for v in range(V)]
+    sp = r._splats(Pd, tiled=True)
+    carr = (_l.Camera * V)(*cams)
+    opts = _l.Opts(); opts.sh_degree = 3; opts.absgrad = 1; opts.shn_layout = 1
+    torch.cuda.synchronize()
+    for first, count in ((0, 2048), (2048, n - 2048)):                    # 1. a complete preparation
+        assert dv.lib.dvs_raster_forward_views_prepare(r.ctx, None, C.byref(sp), carr, V, C.byref(opts), first, count) == 0, dv.lib.dvs_last_error()
+    m = 9001                                                              # 2. the hook, on keys of its own
+    keys = np.random.default_rng(7).integers(1 << 10, 1 << 24, m, dtype=np.uint64).astype(np.uint32)
+    k_d = torch.from_numpy(keys.view(np.int32).copy()).to(r.tdev)
+    out = torch.empty(m, dtype=torch.int32, device=r.tdev)
+    cnt = C.c_uint32(0)
+    assert dv.lib.dvs_debug_sort_depth_keys(r.ctx, None, k_d.data_ptr(), m, out.data_ptr(), C.byref(cnt), None) == 0, dv.lib.dvs_last_error()
+    assert cnt.value == m
+    img = r.forward_views(Pd, cams, sh_degree=3, absgrad=True, shn_tiled=True)      # 3. the forward with the prepared inputs
+    torch.cuda.synchronize()
+    assert torch.equal(img, ref), "the forward after the hook used the stale preparation"
+    for v in range(V):
+        sv = r.view_saved(v)
+        for k in ("radii", "flags", "tiles_touched", "vals", "ranges", "n_contrib"):
+            np.testing.assert_array_equal(sv[k], ref_saved[v][k], err_msg=f"view {v} {k}")
+    r.close()
+
+
 def test_live_lists_give_the_same_gradients(gpu_device):
     """dvs_set_live_lists: the "tr" backward over the forward's compacted lists (entries that reach their tile) against the same
     kernel over the full lists — one view and a 3-view pass, a scene with many entries that miss their tiles (small, faint splats) and
