@@ -56,6 +56,10 @@ class AdamGroup(C.Structure):
                 ("lr", C.c_float), ("width", C.c_int32), ("layout", C.c_int32), ("active_chunks", C.c_int32)]
 
 
+class MetricsView(C.Structure):
+    _fields_ = [("img", C.c_void_p), ("target", C.c_void_p), ("mask", C.c_void_p)]
+
+
 class McmcSets(C.Structure):
     _fields_ = [("param", C.c_void_p * 6), ("m", C.c_void_p * 6), ("v", C.c_void_p * 6)]
 
@@ -139,6 +143,8 @@ _PROTOS = {
                                     C.c_void_p, C.c_int]),
     "dvs_loss_l1_ssim_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                             C.c_void_p, C.c_void_p]),
+    "dvs_image_metrics_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dvs_image_metrics_views": (C.c_int, [C.c_void_p, C.POINTER(MetricsView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "dvs_densify_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dvs_densify_accumulate_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dvs_any_view_radius": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

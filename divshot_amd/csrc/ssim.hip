@@ -11,24 +11,7 @@
 #include <climits>
 #include "../../include/dvs_train.h"
 #include "../../include/dvs_raster.h"
-
-#define ST 16
-#define HALO 5
-#define SP (ST + 2 * HALO)        // 26
-#define SSIM_C1 0.0001f
-#define SSIM_C2 0.0009f
-
-__constant__ float c_gauss[11] = {0.001028380123898387f, 0.0075987582094967365f, 0.036000773310661316f, 0.10936068743467331f,
-                                  0.21300552785396576f,  0.26601171493530273f,   0.21300552785396576f,  0.10936068743467331f,
-                                  0.036000773310661316f, 0.0075987582094967365f, 0.001028380123898387f};
-
-__device__ __forceinline__ float block_sum256(float v, float* tmp) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    if ((threadIdx.x & 63) == 0) tmp[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return tmp[0] + tmp[1] + tmp[2] + tmp[3];
-}
+#include "ssim_common.h"
 
 // load the 26x26 patches of NP planes (zero outside the image) into LDS. All 3*NP global loads are issued before the first
 // LDS write (clamped address + select instead of a branch): with a branch per element the loads serialise and the kernel

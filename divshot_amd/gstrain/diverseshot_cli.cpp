@@ -26,7 +26,10 @@ static std::map<std::string, std::string> g_opts = {
     {"refineStopIter", "15000"}, {"refineScale2dStopIter", "15000"}, {"minOpacity", "0.005"}, {"pruneEvery", "70000"},
     {"pruneStrategy", "1"}, {"revisedOpacity", "1"}, {"mipAntiliased", "0"}, {"packLevel", "1"}, {"exportMesh", "0"},
     {"noiselr", "100000"}, {"useMask", "0"}, {"eval", "0"},
-    {"viewsPerIter", "1"}};       // extension of this build: cameras per train_step as one multi-view pass (BASELINE config C4: 8)
+    {"viewsPerIter", "1"},        // extension of this build: cameras per train_step as one multi-view pass (BASELINE config C4: 8)
+    // extensions of this build: --eval holds out every 8th camera (0, 8, ...) as the test set; --evalHoldout K chooses the modulus
+    // (-1 = not given; it wins over --eval), --evalEvery N also scores the test set every N steps (it is always scored at a save)
+    {"evalHoldout", "-1"}, {"evalEvery", "0"}};
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
 
@@ -97,6 +100,8 @@ int main(int argc, const char* argv[]) {
     train_config.useMask = as_bool(g_opts["useMask"]);
     train_config.numIters = max_iteraion;
     if (g_opts.count("viewsPerIter")) train_config.viewsPerIter = atoi(g_opts["viewsPerIter"].c_str());   // extension of this build (config C4)
+    train_config.evalHoldout = atoi(g_opts["evalHoldout"].c_str()) >= 0 ? atoi(g_opts["evalHoldout"].c_str()) : (as_bool(g_opts["eval"]) ? 8 : 0);
+    train_config.evalEvery = atoi(g_opts["evalEvery"].c_str());
     train_config.normalConsistencyLoss = false;
     if (train_config.exportMesh) { train_config.normalConsistencyLoss = true; train_config.useMask = true; }
     train_config.verbose = true;

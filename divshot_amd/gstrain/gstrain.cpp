@@ -130,6 +130,16 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     std::vector<float> host[6];
     bool host_valid = false;
+    // held-out evaluation (cfg.evalHoldout / evalEvery): camera i is a test camera iff i % eval_holdout == 0. Both lists are empty when
+    // evaluation is off — the draw is then the reference's, over all cameras. The test views are rendered by a context of their own:
+    // the training context's saved forward state, pending backward rows and prepared projection are never touched by an evaluation.
+    int eval_holdout = 0, eval_every = 0;
+    std::vector<int> train_idx, test_idx;
+    dvs_ctx* eval_ctx = nullptr; int eval_views = 0;                         // created at the first evaluation: min(n_test, 8) views per pass
+    float* d_eval_out = nullptr; void* d_eval_scratch = nullptr; double* d_eval_res = nullptr;
+    std::vector<double> eval_res;                                            // [n_test][4] = {mse, l1, ssim, psnr} of the last evaluation
+    double eval_mean[4] = {NAN, NAN, NAN, NAN};
+    int eval_it = -1;
 
     ~Impl() { release(); }
     void release() {
@@ -156,6 +166,8 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         for (float* t : d_targets) (void)hipFree(t);
         d_targets.clear();
         for (float** p : {&d_absgrad, &d_out, &d_dL, &d_loss, &d_ssim_maps[0], &d_ssim_maps[1], &d_ssim_maps[2]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        for (void** p : {(void**)&d_eval_out, &d_eval_scratch, (void**)&d_eval_res}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        if (eval_ctx) { dvs_destroy(eval_ctx); eval_ctx = nullptr; }
         if (ctx) { dvs_destroy(ctx); ctx = nullptr; }
         if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; }
     }
@@ -226,9 +238,14 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         ci.assign((size_t)world * vpi, 0);                  // every rank knows every rank's cameras: the SH rows are rebuilt from them
         for (int& c : ci) {
             cam_rng ^= cam_rng << 13; cam_rng ^= cam_rng >> 7; cam_rng ^= cam_rng << 17;
-            c = cfg.singleCamera ? 0 : (int)(cam_rng % cams.size());
+            if (train_idx.empty()) c = cfg.singleCamera ? 0 : (int)(cam_rng % cams.size());
+            else c = train_idx[cfg.singleCamera ? 0 : (size_t)(cam_rng % train_idx.size())];     // held-out cameras are never trained on
         }
     }
+    void setup_split();
+    bool evaluate(bool write_json, bool force = false);
+    void run_evaluation();
+    void write_eval_json() const;
     std::vector<dvs_camera> rank_cameras(const std::vector<int>& ci_all) const {     // this rank's views of an iteration's draw
         std::vector<dvs_camera> v((size_t)vpi);
         for (int k = 0; k < vpi; ++k) v[(size_t)k] = cams[(size_t)ci_all[(size_t)rank * vpi + k]];
@@ -305,6 +322,12 @@ void GaussianTrainerScene::Impl::report_config() const {
           cfg.capMax, cfg.packLevel, (cfg.packLevel & PackF32ToU8) ? "PackF32ToU8: 8-bit training views" : "fp32 training views",
           (cfg.packLevel & PackTileID) ? ", PackTileID: always on here (the tile sort's keys are tile ids inside a view, written as 16-bit words while a view has <= 65536 tiles)" : "",
           (int)cfg.useMask, (int)cfg.useAbsGrad, (int)cfg.mipAntiliased, (int)cfg.visibleAdam, (int)cfg.singleCamera, (int)cfg.progressiveTrain, world);
+    if (!test_idx.empty()) {
+        std::string idx;
+        for (int c : test_idx) idx += " " + std::to_string(c);
+        logf_("config: evaluation: %zu of %zu cameras held out of training (evalHoldout %d: cameras%s), scored at every save%s", test_idx.size(),
+              cams.size(), eval_holdout, idx.c_str(), eval_every > 0 ? (" and every " + std::to_string(eval_every) + " steps").c_str() : "");
+    }
     std::string ign;
     if (cfg.modelType != 0) ign += " modelType(only 3DGS)";
     if (cfg.cullSH) ign += " cullSH";
@@ -320,6 +343,90 @@ void GaussianTrainerScene::Impl::report_config() const {
     if (!cfg.cameraPosePath.empty() || !cfg.pointCloudPath.empty()) ign += " cameraPosePath/pointCloudPath(dataset ingestion)";
     if (cfg.visibleAdam && world > 1) ign += " visibleAdam(off with WORLD_SIZE > 1: the visible set differs per rank)";
     if (!ign.empty()) logf_("config: IGNORED by this build:%s", ign.c_str());
+}
+
+// the train / test split of cfg.evalHoldout (DVS_EVAL_HOLDOUT): a function of the camera index alone, so every rank derives the same one
+void GaussianTrainerScene::Impl::setup_split() {
+    eval_holdout = cfg.evalHoldout; eval_every = cfg.evalEvery;
+    if (const char* e = getenv("DVS_EVAL_HOLDOUT")) eval_holdout = atoi(e);
+    if (const char* e = getenv("DVS_EVAL_EVERY")) eval_every = atoi(e);
+    train_idx.clear(); test_idx.clear();
+    if (eval_holdout <= 0) { eval_holdout = 0; return; }
+    for (int c = 0; c < (int)cams.size(); ++c) (c % eval_holdout == 0 ? test_idx : train_idx).push_back(c);
+    if (train_idx.empty() || test_idx.empty()) {
+        if (rank == 0)
+            logf_("evaluation is OFF: evalHoldout %d over %zu cameras leaves %zu to train on and %zu to test on; training on every camera",
+                  eval_holdout, cams.size(), train_idx.size(), test_idx.size());
+        train_idx.clear(); test_idx.clear(); eval_holdout = 0;
+    }
+}
+
+// Held-out evaluation, on the training stream: the test cameras rendered from the current parameters at the full SH degree (what a
+// viewer shows from the saved PLY), min(n_test, 8) views per multi-view pass of a SEPARATE context, each pass scored by one
+// dvs_image_metrics_views call against the stored targets (8-bit ones as they are, the camera's mask when useMask), then ONE copy of
+// the [n_test][4] doubles to the host. Only rank 0 evaluates (the replicas are identical). -> false when evaluation is off.
+// A save right after the step that was just scored (evalEvery divides the iteration) writes that result: the parameters are the same.
+bool GaussianTrainerScene::Impl::evaluate(bool write_json, bool force) {
+    if (test_idx.empty() || rank != 0 || !ctx) return false;
+    HIP_OR_THROW(hipSetDevice(device));
+    if (force || eval_it != step) run_evaluation();
+    if (write_json) write_eval_json();
+    return true;
+}
+void GaussianTrainerScene::Impl::run_evaluation() {
+    const int nt = (int)test_idx.size();
+    const size_t img = 3 * (size_t)W * H;
+    if (!eval_ctx) {
+        eval_views = std::min(nt, 8);
+        eval_ctx = dvs_create_views(device, (size_t)cap, W, H, eval_views);
+        if (!eval_ctx) throw std::runtime_error(std::string("dvs_create_views (evaluation): ") + dvs_last_error());
+        HIP_OR_THROW(hipMalloc((void**)&d_eval_out, (size_t)eval_views * img * sizeof(float)));
+        HIP_OR_THROW(hipMalloc(&d_eval_scratch, dvs_image_metrics_scratch_bytes(W, H, eval_views)));
+        HIP_OR_THROW(hipMalloc((void**)&d_eval_res, (size_t)nt * 4 * sizeof(double)));
+    }
+    dvs_opts opts{};
+    opts.sh_degree = sh_max; opts.antialias = cfg.mipAntiliased ? 1 : 0; opts.shn_layout = DVS_SHN_TILED; opts.tile_bounds = DVS_TILES_CANONICAL;
+    const dvs_splats sp = splats();
+    const bool u8 = (cfg.packLevel & PackF32ToU8) != 0;
+    for (int first = 0; first < nt; first += eval_views) {
+        const int nb = std::min(eval_views, nt - first);
+        std::vector<dvs_camera> bc((size_t)nb);
+        dvs_metrics_view mv[DVS_METRICS_MAX_VIEWS] = {};
+        for (int k = 0; k < nb; ++k) {
+            const size_t ci = (size_t)test_idx[(size_t)(first + k)];
+            bc[(size_t)k] = cams[ci];
+            mv[k].img = d_eval_out + (size_t)k * img;
+            mv[k].target = u8 ? (const void*)d_targets_u8[ci] : (const void*)d_targets[ci];
+            mv[k].mask = cfg.useMask && !d_masks.empty() ? d_masks[ci] : nullptr;
+        }
+        DVS_OR_THROW(dvs_raster_forward_views(eval_ctx, stream, &sp, bc.data(), nb, &opts, d_eval_out));
+        DVS_OR_THROW(dvs_image_metrics_views(stream, mv, nb, W, H, u8 ? 1 : 0, d_eval_scratch, d_eval_res + (size_t)first * 4));
+    }
+    eval_res.assign((size_t)nt * 4, 0.0);
+    HIP_OR_THROW(hipMemcpyAsync(eval_res.data(), d_eval_res, eval_res.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
+    HIP_OR_THROW(hipStreamSynchronize(stream));
+    for (int k = 0; k < 4; ++k) {
+        double a = 0.0;
+        for (int v = 0; v < nt; ++v) a += eval_res[(size_t)v * 4 + k];
+        eval_mean[k] = a / nt;
+    }
+    eval_it = step;
+    logf_("eval @%d: %d views, PSNR %.17g dB, SSIM %.17g, L1 %.17g", step, nt, eval_mean[3], eval_mean[2], eval_mean[1]);
+}
+// <modelPath>_<it>_eval.json: the last evaluation, every double with 17 significant digits (they read back bit for bit)
+void GaussianTrainerScene::Impl::write_eval_json() const {
+    const int nt = (int)test_idx.size();
+    const std::string file = cfg.modelPath + "_" + std::to_string(step) + "_eval.json";
+    FILE* f = fopen(file.c_str(), "w");
+    if (!f) { logf_("evaluation: cannot write %s", file.c_str()); return; }
+    fprintf(f, "{\n  \"iteration\": %d,\n  \"n_splats\": %d,\n  \"sh_degree\": %d,\n  \"holdout\": %d,\n  \"views\": [\n", step, n, sh_max, eval_holdout);
+    for (int v = 0; v < nt; ++v) {
+        const double* r = &eval_res[(size_t)v * 4];
+        fprintf(f, "    {\"camera\": %d, \"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}%s\n", test_idx[(size_t)v], r[3], r[2], r[1], r[0],
+                v + 1 < nt ? "," : "");
+    }
+    fprintf(f, "  ],\n  \"mean\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}\n}\n", eval_mean[3], eval_mean[2], eval_mean[1], eval_mean[0]);
+    fclose(f);
 }
 
 // data parallel: the densification statistics are per-view sums / maxima — make them global before a refinement decision
@@ -405,6 +512,7 @@ bool GaussianTrainerScene::Impl::load_synthetic(const std::string& spec_str) {
     }
     if (cfg.packLevel & PackF32ToU8) HIP_OR_THROW(hipMalloc((void**)&d_target_f32, img * sizeof(float)));
     HIP_OR_THROW(hipStreamSynchronize(stream));
+    setup_split();
     {   // scene extent = 1.1 x the largest distance of a camera centre from their mean (the usual "cameras_extent"); a single
         // camera or a tiny rig falls back to half the depth range of the synthetic slab
         double mean[3] = {0, 0, 0};
@@ -831,6 +939,7 @@ void GaussianTrainerScene::trainStep() {
     curIteration = s.it;
     m.host_valid = false;
     if (m.step >= m.cfg.numIters) m.status = TrainingStatus::Training_Done;
+    if (m.eval_every > 0 && m.step % m.eval_every == 0) m.evaluate(false);
 }
 
 void GaussianTrainerScene::saveGaussianModel() {
@@ -849,6 +958,7 @@ void GaussianTrainerScene::saveGaussianModel() {
                           m.host[5].data(), m.cfg.mipAntiliased, &err))
         logf_("save_splat_model: %s", err.c_str());
     else if (m.cfg.verbose) logf_("saved %d splats to %s", m.n, file.c_str());
+    m.evaluate(true);                                                       // <modelPath>_<it>_eval.json beside the PLY (rank 0, evaluation on)
 }
 void GaussianTrainerScene::exportMesh(const std::string&) { logf_("export_mesh: mesh extraction is outside this build's scope"); }
 void GaussianTrainerScene::exportSparsePointCloud(const std::string& path) {
@@ -889,6 +999,7 @@ void GaussianTrainerScene::resetGaussian() {
     HIP_OR_THROW(hipMemset(m.d_grad_flat, 0, m.grad_floats * sizeof(float)));
     m.reset_stats();
     m.step = 0; curIteration = 0; pruenIteraions.clear();
+    m.eval_it = -1;
     m.host_valid = false;
     (void)dvs_raster_forward_cancel_prepared(m.ctx);          // (a pipelined step may have projected the next iteration's splats already)
     m.status = TrainingStatus::Training;
@@ -985,6 +1096,11 @@ double GaussianTrainerScene::getTrainingElpasedTime() const {
 }
 int GaussianTrainerScene::getNumGaussians() const { return impl_->n; }
 int GaussianTrainerScene::getNumCameras() const { return (int)impl_->cams.size(); }
+int GaussianTrainerScene::getNumTestCameras() const { return (int)impl_->test_idx.size(); }
+bool GaussianTrainerScene::evaluateTestSet() { return impl_->evaluate(false, true); }
+double GaussianTrainerScene::getTestPSNR() const { return impl_->eval_mean[3]; }
+double GaussianTrainerScene::getTestSSIM() const { return impl_->eval_mean[2]; }
+double GaussianTrainerScene::getTestL1() const { return impl_->eval_mean[1]; }
 const std::vector<float>& GaussianTrainerScene::getGaussianPositionCpu() { impl_->fetch_host(); return impl_->host[P_POS]; }
 const std::vector<float>& GaussianTrainerScene::getGaussianSH0Cpu() { impl_->fetch_host(); return impl_->host[P_SH0]; }
 const std::vector<float>& GaussianTrainerScene::getGaussianSHNCpu() { impl_->fetch_host(); return impl_->host[P_SHN]; }

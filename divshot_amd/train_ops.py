@@ -1,7 +1,7 @@
 """ctypes wrappers of include/dvs_train.h (loss gradient, SSIM, fused Adam) on torch CUDA tensors."""
 import ctypes as C
 import torch
-from ._lib import lib, check, AdamGroup
+from ._lib import lib, check, AdamGroup, MetricsView
 
 
 def _st():
@@ -47,6 +47,33 @@ class Ssim:
                                     self.maps[1].data_ptr(), self.maps[2].data_ptr(), float(scale), dL.data_ptr(), int(accumulate)),
               "dvs_ssim_backward")
         return dL
+
+
+def image_metrics(imgs, targets, masks=None):
+    """Image metrics of V views in one call (dvs_image_metrics_views) -> torch.float64 [V, 4], rows {mse, l1, ssim, psnr} (asynchronous).
+    imgs: V float32 [3,H,W] tensors (or one [V,3,H,W]); targets: likewise, all float32 or all uint8; masks: None, or V entries each None
+    or a float32 [H,W] tensor. The rendered view is clamped to [0, 1] and both images are multiplied by the mask (include/dvs_train.h)."""
+    imgs, targets = list(imgs), list(targets)
+    V = len(imgs)
+    masks = [None] * V if masks is None else list(masks)
+    if len(targets) != V or len(masks) != V:
+        raise ValueError("image_metrics: imgs, targets and masks must have one entry per view")
+    H, W = (int(d) for d in imgs[0].shape[-2:]) if V else (0, 0)
+    u8 = V > 0 and targets[0].dtype == torch.uint8
+    arr = (MetricsView * max(V, 1))()
+    for a, x, y, m in zip(arr, imgs, targets, masks):
+        if x.dtype != torch.float32 or tuple(x.shape) != (3, H, W) or not x.is_contiguous():
+            raise ValueError("image_metrics: every img must be a contiguous float32 [3,H,W] tensor of one size")
+        if y.dtype != (torch.uint8 if u8 else torch.float32) or tuple(y.shape) != (3, H, W) or not y.is_contiguous():
+            raise ValueError("image_metrics: every target must be a contiguous [3,H,W] tensor, all float32 or all uint8")
+        if m is not None and (m.dtype != torch.float32 or tuple(m.shape) != (H, W) or not m.is_contiguous()):
+            raise ValueError("image_metrics: a mask must be a contiguous float32 [H,W] tensor")
+        a.img, a.target, a.mask = x.data_ptr(), y.data_ptr(), m.data_ptr() if m is not None else None
+    dev = imgs[0].device if V else torch.device("cuda")
+    scratch = torch.empty(max(4, lib.dvs_image_metrics_scratch_bytes(W, H, V)), dtype=torch.uint8, device=dev)
+    out = torch.empty((max(V, 1), 4), dtype=torch.float64, device=dev)
+    check(lib.dvs_image_metrics_views(_st(), arr, V, W, H, int(u8), scratch.data_ptr(), out.data_ptr()), "dvs_image_metrics_views")
+    return out[:V]
 
 
 def adam_step(param, grad, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-15):

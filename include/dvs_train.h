@@ -41,6 +41,32 @@ int dvs_ssim_backward(void* stream, const float* img, const float* target, int w
 int dvs_loss_l1_ssim_backward(void* stream, const float* img, const float* target, int width, int height, const float* dm_dmu1,
                               const float* dm_dsigma1_sq, const float* dm_dsigma12, float ssim_weight, float* dL_dimg, float* l1_sum);
 
+/* ---- image metrics of a batch of views (held-out evaluation) ---------------------------------------------------------------------
+ * out[v] = {mse, l1, ssim, psnr} of view v, with m = the pixel's mask value (1 when mask is NULL),
+ *   x = min(1, max(0, img)) * m,   y = target * m   (an 8-bit target is expanded as (float)u * (1.0f/255.0f), the operation of the
+ *   trainer's packLevel PackF32ToU8 views),
+ *   mse = sum (x-y)^2 / (3HW),   l1 = sum |x-y| / (3HW),   ssim = the mean SSIM of x and y exactly as the loss kernels above define it,
+ *   psnr = -10 log10(max(mse, 1e-10)) in fp64 (100 dB for identical images).
+ * ONE launch over the tiles of all views plus a small finalising launch; no per-pixel output, 8-bit targets are read as bytes. Every
+ * workgroup writes its fp32 partial sums to its own slot of `scratch` and the finalising kernel adds a view's slots in a fixed order
+ * in fp64: no atomics, so two calls on the same inputs return bit-identical rows and a view's row does not depend on which other views
+ * share the call.
+ *   views     HOST array [n_views] (1..DVS_METRICS_MAX_VIEWS) of DEVICE pointers, all views width x height; copied before the call returns
+ *   alignment img / target / mask need only the natural alignment of their element (4 bytes for fp32, 1 for uint8) — NOT the 16 bytes
+ *             of the rasterizer's interface: the kernel reads scalars (rows of an odd width cannot be 16-byte aligned anyway)
+ *   scratch   DEVICE, dvs_image_metrics_scratch_bytes(width, height, n_views) bytes, 4-byte aligned, no initialisation needed
+ *   out       DEVICE double [n_views][4]
+ * DVS_ERR_INVALID for n_views outside 1..16, a NULL img / target / scratch / out, non-positive sizes. Asynchronous on `stream`. */
+#define DVS_METRICS_MAX_VIEWS 16
+typedef struct dvs_metrics_view {   /* DEVICE pointers */
+    const float* img;      /* [3,H,W] planar fp32, the rendered view */
+    const void*  target;   /* [3,H,W] planar: fp32, or uint8 when target_u8 */
+    const float* mask;     /* [H,W] or NULL */
+} dvs_metrics_view;
+size_t dvs_image_metrics_scratch_bytes(int width, int height, int n_views);
+int dvs_image_metrics_views(void* stream, const dvs_metrics_view* views /* HOST [n_views] */, int n_views,
+                            int width, int height, int target_u8, void* scratch, double* out /* DEVICE [n_views][4] */);
+
 /* Fused Adam over one parameter array (count floats): m, v are the moment arrays (same size, DEVICE).
  * step is 1-based. Asynchronous. */
 int dvs_adam_step(void* stream, float* param, const float* grad, float* m, float* v, size_t count, float lr, float beta1,

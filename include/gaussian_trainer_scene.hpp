@@ -67,6 +67,13 @@ struct GaussianTrainConfig {
     // optimizer step per trainStep, as after that many accumulated single-view steps. The environment variable DVS_VIEWS_PER_ITER
     // overrides it (the reference's hosts do not know the field).
     int viewsPerIter = 1;
+    // extension of this build, appended the same way (0 / 0 = the reference's behaviour: every camera trains, nothing is evaluated).
+    // evalHoldout = K > 0: camera i is a TEST camera iff i % K == 0 (K = 8 is the lineage's usual hold-out); trainStep draws from the
+    // other cameras only, and the test cameras are rendered and scored (PSNR / SSIM / L1, include/dvs_train.h dvs_image_metrics_views)
+    // after every saveGaussianModel() and every evalEvery steps (0 = only when saving). The environment variables DVS_EVAL_HOLDOUT /
+    // DVS_EVAL_EVERY override them (the reference's hosts do not know the fields).
+    int evalHoldout = 0;
+    int evalEvery = 0;
 };
 
 class GSTRAIN_API GaussianTrainerScene {
@@ -110,7 +117,13 @@ public:
     void setTrainingStatus(TrainingStatus s);
     double getTrainingElpasedTime() const;
     int getNumGaussians() const;
-    int getNumCameras() const;
+    int getNumCameras() const;                        // all cameras, held-out ones included
+    // held-out evaluation (extension of this build; config evalHoldout / evalEvery)
+    int getNumTestCameras() const;                    // 0 when evaluation is off
+    bool evaluateTestSet();                           // renders and scores the test cameras now, synchronises; false when evaluation is off
+    double getTestPSNR() const;                       // means over the test cameras of the last evaluation, NaN before the first
+    double getTestSSIM() const;
+    double getTestL1() const;
     // trainer -> viewer hand-off (editor.cpp:1459-1473 -> GaussianModel::update_from_cpu, gaussian_model.cpp:43-68)
     const std::vector<float>& getGaussianPositionCpu();
     const std::vector<float>& getGaussianSH0Cpu();
