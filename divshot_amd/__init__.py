@@ -6,7 +6,7 @@ tests and bench.py; torch is only used for device memory, streams and torch.dist
 There is no CPU fallback: everything here fails loudly when the HIP library is missing.
 """
 from ._lib import lib, Camera, Opts, Splats, FwdState, SplatGrads, SceneSpec, DvsError, LIB_PATH  # noqa: F401
-from .scene import synth_splats, synth_camera, synth_target, make_spec  # noqa: F401
+from .scene import synth_splats, synth_camera, synth_target, make_spec, camera_downscale  # noqa: F401
 
 __all__ = ["lib", "Camera", "Opts", "Splats", "FwdState", "SplatGrads", "SceneSpec", "DvsError",
-           "synth_splats", "synth_camera", "synth_target", "make_spec", "LIB_PATH"]
+           "synth_splats", "synth_camera", "synth_target", "make_spec", "camera_downscale", "LIB_PATH"]

@@ -60,6 +60,10 @@ class MetricsView(C.Structure):
     _fields_ = [("img", C.c_void_p), ("target", C.c_void_p), ("mask", C.c_void_p)]
 
 
+class DownsampleView(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p)]
+
+
 class McmcSets(C.Structure):
     _fields_ = [("param", C.c_void_p * 6), ("m", C.c_void_p * 6), ("v", C.c_void_p * 6)]
 
@@ -135,6 +139,7 @@ _PROTOS = {
     "dvs_synth_camera": (C.c_int, [C.POINTER(SceneSpec), C.c_int, C.POINTER(Camera)]),
     "dvs_synth_target": (C.c_int, [C.POINTER(SceneSpec), C.c_int, C.c_void_p]),
     "dvs_make_camera": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.POINTER(Camera)]),
+    "dvs_camera_downscale": (C.c_int, [C.POINTER(Camera), C.c_int, C.POINTER(Camera)]),
     "dvs_l1_loss_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "dvs_l1_loss_grad_w": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
     "dvs_l2_loss_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
@@ -145,6 +150,7 @@ _PROTOS = {
                                             C.c_void_p, C.c_void_p]),
     "dvs_image_metrics_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "dvs_image_metrics_views": (C.c_int, [C.c_void_p, C.POINTER(MetricsView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "dvs_downsample_views": (C.c_int, [C.c_void_p, C.POINTER(DownsampleView), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "dvs_densify_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dvs_densify_accumulate_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dvs_any_view_radius": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

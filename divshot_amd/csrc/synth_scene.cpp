@@ -62,6 +62,24 @@ int dvs_make_camera(const float* R, const float* t, float fov_x_deg, int width, 
     return DVS_OK;
 }
 
+int dvs_camera_downscale(const dvs_camera* in, int factor, dvs_camera* out) {
+    if (!in || !out || in == out || (factor != 1 && factor != 2 && factor != 4 && factor != 8)) return DVS_ERR_INVALID;
+    const int wd = in->width / factor, hd = in->height / factor;
+    if (wd <= 0 || hd <= 0) return DVS_ERR_INVALID;
+    *out = *in;
+    if (factor == 1) return DVS_OK;
+    out->width = wd; out->height = hd;
+    out->focal_x = in->focal_x / (float)factor; out->focal_y = in->focal_y / (float)factor;       // a power of two: exact
+    const double s[2] = {(double)in->width / ((double)factor * wd), (double)in->height / ((double)factor * hd)};
+    for (int r = 0; r < 2; ++r) {
+        if (s[r] == 1.0) continue;                          // nothing cropped: the row and tan_fov stay as they are, bit for bit
+        for (int k = 0; k < 4; ++k) out->proj[k * 4 + r] = (float)(s[r] * (double)in->proj[k * 4 + r] + (s[r] - 1.0) * (double)in->proj[k * 4 + 3]);
+        float& tan_fov = r == 0 ? out->tan_fovx : out->tan_fovy;
+        tan_fov = (float)((double)tan_fov / s[r]);
+    }
+    return DVS_OK;
+}
+
 int dvs_synth_camera(const dvs_scene_spec* s, int index, dvs_camera* out) {
     if (!s || !out || index < 0 || index >= (s->n_cams > 0 ? s->n_cams : 1)) return DVS_ERR_INVALID;
     double eye[3] = {0, 0, 0};

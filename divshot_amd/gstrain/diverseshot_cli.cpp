@@ -29,7 +29,10 @@ static std::map<std::string, std::string> g_opts = {
     {"viewsPerIter", "1"},        // extension of this build: cameras per train_step as one multi-view pass (BASELINE config C4: 8)
     // extensions of this build: --eval holds out every 8th camera (0, 8, ...) as the test set; --evalHoldout K chooses the modulus
     // (-1 = not given; it wins over --eval), --evalEvery N also scores the test set every N steps (it is always scored at a save)
-    {"evalHoldout", "-1"}, {"evalEvery", "0"}};
+    {"evalHoldout", "-1"}, {"evalEvery", "0"},
+    // the reference's config field resolutionSchedule (its CLI has no flag for it; the editor sets 3000) and this build's numDownscales:
+    // coarse-to-fine training, start at 1/2^K of the image size and double every N steps (0 = off)
+    {"resolutionSchedule", "0"}, {"numDownscales", "2"}};
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
 
@@ -102,6 +105,8 @@ int main(int argc, const char* argv[]) {
     if (g_opts.count("viewsPerIter")) train_config.viewsPerIter = atoi(g_opts["viewsPerIter"].c_str());   // extension of this build (config C4)
     train_config.evalHoldout = atoi(g_opts["evalHoldout"].c_str()) >= 0 ? atoi(g_opts["evalHoldout"].c_str()) : (as_bool(g_opts["eval"]) ? 8 : 0);
     train_config.evalEvery = atoi(g_opts["evalEvery"].c_str());
+    train_config.resolutionSchedule = atoi(g_opts["resolutionSchedule"].c_str());
+    train_config.numDownscales = atoi(g_opts["numDownscales"].c_str());
     train_config.normalConsistencyLoss = false;
     if (train_config.exportMesh) { train_config.normalConsistencyLoss = true; train_config.useMask = true; }
     train_config.verbose = true;

@@ -11,6 +11,7 @@
 // data parallel: every rank holds a replica, renders its own camera of the iteration, the gradient rows are summed
 // with ONE RCCL all-reduce over xGMI (include/dvs_comm.h), the densification statistics likewise before each refinement, and the
 // optimizer / densifier run replicated and deterministic so that the replicas stay bit-identical.
+// With resolutionSchedule > 0 the first steps train coarse to fine: on box-filtered views of 1/2^k the size, through level cameras.
 // Out of scope: COLMAP / image ingestion, mesh export, the 2DGS model type. load_train_data accepts a
 // synthetic-scene spec instead of a dataset path. Every GaussianTrainConfig field the hosts set is either honoured
 // or named in the one-time "ignored" line of report_config().
@@ -140,6 +141,17 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     std::vector<double> eval_res;                                            // [n_test][4] = {mse, l1, ssim, psnr} of the last evaluation
     double eval_mean[4] = {NAN, NAN, NAN, NAN};
     int eval_it = -1;
+    // coarse-to-fine training (cfg.resolutionSchedule = S, cfg.numDownscales = K; both 0 here when the schedule is off): the step with
+    // `step` completed steps before it trains at level k = max(K - step / S, 0), on images of W / 2^k x H / 2^k — the stored views
+    // box-filtered by ONE dvs_downsample_views call per step into d_level_targets, the cameras those of dvs_camera_downscale. The
+    // level is a function of the step number alone (every rank derives the same one; a resume lands on the right one). Everything
+    // per pixel of the step (d_out, d_dL, the loss, the densification statistics) has the level's size; the arenas keep the full one.
+    int res_every = 0, res_levels = 0;
+    std::vector<std::vector<dvs_camera>> level_cams;                        // [k - 1][camera], k = 1..K (level 0: cams)
+    float* d_level_targets = nullptr; float* d_level_masks = nullptr;       // [vpi,3,H/2,W/2] / [vpi,H/2,W/2]: room for the largest level below full size
+    int cur_level = -1;                                                      // level of the last step (-1: none yet)
+    int lw = 0, lh = 0;                                                      // image size of the last step (W x H when the schedule is off)
+    int level_first_step = 0; std::chrono::steady_clock::time_point level_t0;
 
     ~Impl() { release(); }
     void release() {
@@ -152,7 +164,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         d_targets_u8.clear();
         for (float* t : d_masks) (void)hipFree(t);
         d_masks.clear();
-        for (float** p : {&d_grad_flat, &d_mean2d, &d_target_f32, &d_dcolor_local, &d_dcolor_all, &d_dcolor_scratch}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        for (float** p : {&d_grad_flat, &d_mean2d, &d_target_f32, &d_level_targets, &d_level_masks, &d_dcolor_local, &d_dcolor_all, &d_dcolor_scratch}) { if (*p) (void)hipFree(*p); *p = nullptr; }
         if (d_vis_radius) { (void)hipFree(d_vis_radius); d_vis_radius = nullptr; }
         for (hipEvent_t* e : {&ev_dcolor, &ev_bwd, &ev_comm, &ev_gather}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
         for (hipEvent_t e : ev_chunk) (void)hipEventDestroy(e);
@@ -246,11 +258,16 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     bool evaluate(bool write_json, bool force = false);
     void run_evaluation();
     void write_eval_json() const;
-    std::vector<dvs_camera> rank_cameras(const std::vector<int>& ci_all) const {     // this rank's views of an iteration's draw
+    std::vector<dvs_camera> rank_cameras(const std::vector<int>& ci_all, int level) const {     // this rank's views of an iteration's draw, at a level
         std::vector<dvs_camera> v((size_t)vpi);
-        for (int k = 0; k < vpi; ++k) v[(size_t)k] = cams[(size_t)ci_all[(size_t)rank * vpi + k]];
+        for (int k = 0; k < vpi; ++k) {
+            const size_t ci = (size_t)ci_all[(size_t)rank * vpi + k];
+            v[(size_t)k] = level > 0 ? level_cams[(size_t)level - 1][ci] : cams[ci];
+        }
         return v;
     }
+    int level_of(int s) const { return res_every > 0 ? std::max(res_levels - s / res_every, 0) : 0; }   // s: completed steps before the step
+    void setup_levels();
     const int* any_view_radii() {                            // max radius over the step's views (view-major fwd.radii of the multi-view pass)
         if (!d_vis_radius) HIP_OR_THROW(hipMalloc((void**)&d_vis_radius, (size_t)cap * sizeof(int) + 16));
         DVS_OR_THROW(dvs_any_view_radius(stream, n, vpi, fwd.radii, d_vis_radius));
@@ -259,6 +276,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     // ---- the phases of one trainStep ----
     struct Step {                                                            // one iteration, carried through its phases
         int it = 0, deg = 0;                                                 // the iteration being computed, its SH degree
+        int level = 0, div = 1, Wd = 0, Hd = 0;                              // resolution level of the step, 2^level, the level's image size
         std::vector<int> ci_all;                                             // the iteration's cameras, [rank][local view]
         std::vector<dvs_camera> vcams;                                       // this rank's views
         dvs_opts opts{};
@@ -270,6 +288,9 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         int chunk_per = 0, n_chunks = 0;                                     // (render_backward) > 0: the geometry gradients left behind A9 in chunks
     };
     Step plan_step();                                                        // decides the step; launches nothing
+    void enter_level(const Step& s);
+    void close_level();
+    void level_targets(const Step& s);
     void loss_of_view(const Step& s, int v);
     void render_backward(Step& s);
     void exchange(const Step& s, bool pipelined);
@@ -328,6 +349,10 @@ void GaussianTrainerScene::Impl::report_config() const {
         logf_("config: evaluation: %zu of %zu cameras held out of training (evalHoldout %d: cameras%s), scored at every save%s", test_idx.size(),
               cams.size(), eval_holdout, idx.c_str(), eval_every > 0 ? (" and every " + std::to_string(eval_every) + " steps").c_str() : "");
     }
+    if (res_every > 0)
+        logf_("config: resolutionSchedule %d, numDownscales %d: coarse-to-fine training, the step after s completed ones renders 1/2^max(%d - s/%d, 0) of "
+              "%dx%d (targets box-filtered per step, cameras of dvs_camera_downscale); full resolution from iteration %d; evaluation always at full size",
+              res_every, res_levels, res_levels, res_every, W, H, res_levels * res_every + 1);
     std::string ign;
     if (cfg.modelType != 0) ign += " modelType(only 3DGS)";
     if (cfg.cullSH) ign += " cullSH";
@@ -338,7 +363,6 @@ void GaussianTrainerScene::Impl::report_config() const {
     if (cfg.enableFocusRegion) ign += " enableFocusRegion";
     if (cfg.exportMesh) ign += " exportMesh";
     if (cfg.outputSparsePoints) ign += " outputSparsePoints";
-    if (cfg.resolutionSchedule) ign += " resolutionSchedule";
     if (cfg.maxImageCount) ign += " maxImageCount";
     if (!cfg.cameraPosePath.empty() || !cfg.pointCloudPath.empty()) ign += " cameraPosePath/pointCloudPath(dataset ingestion)";
     if (cfg.visibleAdam && world > 1) ign += " visibleAdam(off with WORLD_SIZE > 1: the visible set differs per rank)";
@@ -429,6 +453,65 @@ void GaussianTrainerScene::Impl::write_eval_json() const {
     fclose(f);
 }
 
+// cfg.resolutionSchedule / numDownscales (DVS_RESOLUTION_SCHEDULE / DVS_NUM_DOWNSCALES): K clamped once to the largest value that leaves
+// min(W, H) >> K >= 16 (and to the factor 8 of dvs_downsample_views); level cameras of every (camera, level) and the staging buffers
+void GaussianTrainerScene::Impl::setup_levels() {
+    res_every = cfg.resolutionSchedule; res_levels = cfg.numDownscales;
+    if (const char* e = getenv("DVS_RESOLUTION_SCHEDULE")) res_every = atoi(e);
+    if (const char* e = getenv("DVS_NUM_DOWNSCALES")) res_levels = atoi(e);
+    lw = W; lh = H; cur_level = -1;
+    if (res_every <= 0) { res_every = 0; res_levels = 0; return; }
+    int k = std::max(0, std::min(res_levels, 3));
+    while (k > 0 && (std::min(W, H) >> k) < 16) --k;
+    if (k != res_levels && rank == 0)
+        logf_("resolutionSchedule: numDownscales %d clamped to %d (levels 1/2 .. 1/8, the smaller side of %dx%d stays >= 16 pixels)", res_levels, k, W, H);
+    res_levels = k;
+    level_cams.assign((size_t)res_levels, std::vector<dvs_camera>(cams.size()));
+    for (int l = 1; l <= res_levels; ++l)
+        for (size_t c = 0; c < cams.size(); ++c) DVS_OR_THROW(dvs_camera_downscale(&cams[c], 1 << l, &level_cams[(size_t)l - 1][c]));
+    if (res_levels == 0) return;
+    const size_t P = (size_t)(W / 2) * (size_t)(H / 2);
+    HIP_OR_THROW(hipMalloc((void**)&d_level_targets, (size_t)vpi * 3 * P * sizeof(float) + 16));
+    if (cfg.useMask) HIP_OR_THROW(hipMalloc((void**)&d_level_masks, (size_t)vpi * P * sizeof(float) + 16));
+}
+
+// A step at another level than the one before it (the first step included): ONE stream synchronisation closes the finished level's
+// wall time and opens the new one's. max_radii is in pixels of its level and starts again; grad_accum / denom are in NDC units and carry over.
+void GaussianTrainerScene::Impl::enter_level(const Step& s) {
+    if (s.level == cur_level) return;
+    if (cur_level >= 0) {
+        close_level();
+        HIP_OR_THROW(hipMemsetAsync(d_max_radii, 0, (size_t)cap * 4, stream));
+    } else {
+        HIP_OR_THROW(hipStreamSynchronize(stream));
+    }
+    cur_level = s.level; level_first_step = step; level_t0 = std::chrono::steady_clock::now();
+    if (rank == 0) logf_("resolution @%d: %dx%d (1/%d)", s.it, s.Wd, s.Hd, s.div);
+}
+void GaussianTrainerScene::Impl::close_level() {                            // (also when training ends)
+    if (cur_level < 0) return;
+    HIP_OR_THROW(hipStreamSynchronize(stream));
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - level_t0).count();
+    const int steps = step - level_first_step;
+    if (rank == 0 && steps > 0) logf_("resolution: %d steps at %dx%d: %.4f ms/step", steps, W >> cur_level, H >> cur_level, ms / steps);
+    cur_level = -1;
+}
+
+// the step's views at its level (level > 0): ONE launch for the images, one more for the masks
+void GaussianTrainerScene::Impl::level_targets(const Step& s) {
+    const bool u8 = (cfg.packLevel & PackF32ToU8) != 0, masked = cfg.useMask && !d_masks.empty();
+    const size_t P = (size_t)s.Wd * s.Hd;
+    dvs_downsample_view tv[DVS_DOWNSAMPLE_MAX_VIEWS] = {}, mv[DVS_DOWNSAMPLE_MAX_VIEWS] = {};
+    for (int v = 0; v < vpi; ++v) {
+        const size_t ci = (size_t)s.ci_all[(size_t)rank * vpi + v];
+        tv[v].src = u8 ? (const void*)d_targets_u8[ci] : (const void*)d_targets[ci];
+        tv[v].dst = d_level_targets + (size_t)v * 3 * P;
+        if (masked) { mv[v].src = d_masks[ci]; mv[v].dst = d_level_masks + (size_t)v * P; }
+    }
+    DVS_OR_THROW(dvs_downsample_views(stream, tv, vpi, 3, W, H, s.div, u8 ? 1 : 0));
+    if (masked) DVS_OR_THROW(dvs_downsample_views(stream, mv, vpi, 1, W, H, s.div, 0));   // fractional weights at the ellipse's edge: they scale the gradient
+}
+
 // data parallel: the densification statistics are per-view sums / maxima — make them global before a refinement decision
 void GaussianTrainerScene::Impl::sync_stats() {
     if (!comm) return;
@@ -513,6 +596,7 @@ bool GaussianTrainerScene::Impl::load_synthetic(const std::string& spec_str) {
     if (cfg.packLevel & PackF32ToU8) HIP_OR_THROW(hipMalloc((void**)&d_target_f32, img * sizeof(float)));
     HIP_OR_THROW(hipStreamSynchronize(stream));
     setup_split();
+    setup_levels();
     {   // scene extent = 1.1 x the largest distance of a camera centre from their mean (the usual "cameras_extent"); a single
         // camera or a tiny rig falls back to half the depth range of the synthetic slab
         double mean[3] = {0, 0, 0};
@@ -611,7 +695,7 @@ void GaussianTrainerScene::Impl::densify(int it) {
     const bool after_reset = it > cfg.resetAlphaEvery;
     prm.max_world_scale = after_reset ? cfg.pruneScale3d * extent : 0.f;                     // `pruneScale3d` (fraction of the scene extent)
     prm.max_screen_radius = after_reset && it < cfg.refineScale2dStopIter                    // `pruneScale2d` (fraction of the image size)
-                                ? std::max(1, (int)(cfg.pruneScale2d * (float)std::max(W, H))) : 0;
+                                ? std::max(1, (int)(cfg.pruneScale2d * (float)std::max(lw, lh))) : 0;   // (max_radii is in pixels of the level)
     prm.cap_max = 0; prm.seed = (uint32_t)it; prm.shn_layout = DVS_SHN_TILED;  // no kernel cap: over capMax, the loop below re-plans prune-only
     prm.revised_opacity = (cfg.revisedOpacity || cfg.densifyStrategy == 2) ? 1 : 0;      // ADC+ always uses the revised opacity of the copies
     uint64_t new_n = 0;
@@ -722,7 +806,8 @@ GaussianTrainerScene::Impl::Step GaussianTrainerScene::Impl::plan_step() {
     Step s;
     if (next_ci.size() == (size_t)world * vpi) { s.ci_all = next_ci; next_ci.clear(); }   // (drawn by the previous, pipelined step: the same stream)
     else draw_cameras(s.ci_all);
-    s.vcams = rank_cameras(s.ci_all);
+    s.level = level_of(step); s.div = 1 << s.level; s.Wd = W / s.div; s.Hd = H / s.div;
+    s.vcams = rank_cameras(s.ci_all, s.level);
     s.it = step + 1;
     s.deg = sh_degree_at(step);
     s.mcmc = mcmc();
@@ -756,8 +841,9 @@ GaussianTrainerScene::Impl::Step GaussianTrainerScene::Impl::plan_step() {
 // sums of the step's views add up in d_loss (getCurrentLoss reports their mean)
 void GaussianTrainerScene::Impl::loss_of_view(const Step& s, int v) {
     const int ci = s.ci_all[(size_t)rank * vpi + v];
+    const int W = s.Wd, H = s.Hd;                                            // the step's level: everything below is per pixel of it
     const size_t img = 3 * (size_t)W * H;
-    const float* target = target_for(ci);
+    const float* target = s.level > 0 ? d_level_targets + (size_t)v * img : target_for(ci);
     const float* out = d_out + (size_t)v * img;
     float* dL = d_dL + (size_t)v * img;
     const float w_ssim = d_ssim_maps[0] ? cfg.ssimWeight : 0.f;
@@ -769,7 +855,8 @@ void GaussianTrainerScene::Impl::loss_of_view(const Step& s, int v) {
     }
     if (cfg.useMask && !d_masks.empty()) {
         const size_t P = (size_t)W * H;
-        hipLaunchKernelGGL(k_mask_mul, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, stream, dL, d_masks[(size_t)ci], P);
+        hipLaunchKernelGGL(k_mask_mul, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, stream, dL,
+                           s.level > 0 ? d_level_masks + (size_t)v * P : d_masks[(size_t)ci], P);
     }
 }
 
@@ -780,7 +867,9 @@ void GaussianTrainerScene::Impl::render_backward(Step& s) {
     const bool fact = exchange_factorised(), seq = sequential_views;
     const int passes = seq ? vpi : 1, views = seq ? 1 : vpi;                 // views per pass
     const dvs_splats sp = splats();
+    const int W = s.Wd, H = s.Hd;                                            // the step's level
     const size_t img = 3 * (size_t)W * H;
+    if (s.level > 0) level_targets(s);
     dvs_opts opts = s.opts;
     dvs_splat_grads g{};
     g.pos = d_grad[P_POS]; g.sh0 = d_grad[P_SH0]; g.shN = d_grad[P_SHN]; g.opacity = d_grad[P_OPA];
@@ -902,7 +991,7 @@ void GaussianTrainerScene::Impl::finish_range(const Step& s, int first, int coun
 void GaussianTrainerScene::Impl::finish_pipelined(const Step& s) {
     const bool early = !s.refine_now && !s.reset_now && !s.prune_now && s.it < cfg.numIters;
     if (early) draw_cameras(next_ci);
-    const std::vector<dvs_camera> ncams = early ? rank_cameras(next_ci) : std::vector<dvs_camera>();
+    const std::vector<dvs_camera> ncams = early ? rank_cameras(next_ci, level_of(s.it)) : std::vector<dvs_camera>();   // (the NEXT step's level)
     dvs_opts nopts = s.opts;
     nopts.sh_degree = sh_degree_at(s.it);                               // (what the next trainStep will compute from step = it)
     const dvs_splats sp = splats();
@@ -919,6 +1008,8 @@ void GaussianTrainerScene::trainStep() {
     if (!m.ctx || m.cams.empty()) throw std::runtime_error("trainStep before loadTrainData");
     HIP_OR_THROW(hipSetDevice(m.device));
     Impl::Step s = m.plan_step();
+    if (m.res_every > 0) m.enter_level(s);
+    m.lw = s.Wd; m.lh = s.Hd;
     HIP_OR_THROW(hipMemsetAsync(m.d_loss, 0, 2 * DVS_SSIM_SLOTS * sizeof(float), m.stream));
     m.render_backward(s);
     const bool pipelined = m.pipeline && s.n_chunks > 0;
@@ -938,7 +1029,7 @@ void GaussianTrainerScene::trainStep() {
     m.step = s.it;
     curIteration = s.it;
     m.host_valid = false;
-    if (m.step >= m.cfg.numIters) m.status = TrainingStatus::Training_Done;
+    if (m.step >= m.cfg.numIters) { m.status = TrainingStatus::Training_Done; m.close_level(); }
     if (m.eval_every > 0 && m.step % m.eval_every == 0) m.evaluate(false);
 }
 
@@ -1000,6 +1091,7 @@ void GaussianTrainerScene::resetGaussian() {
     m.reset_stats();
     m.step = 0; curIteration = 0; pruenIteraions.clear();
     m.eval_it = -1;
+    m.cur_level = -1; m.lw = m.W; m.lh = m.H;
     m.host_valid = false;
     (void)dvs_raster_forward_cancel_prepared(m.ctx);          // (a pipelined step may have projected the next iteration's splats already)
     m.status = TrainingStatus::Training;
@@ -1083,7 +1175,7 @@ float GaussianTrainerScene::getCurrentLoss() {
         double l1 = 0, ssim_sum = 0;
         for (int k = 0; k < DVS_SSIM_SLOTS; ++k) { l1 += h[k]; ssim_sum += h[DVS_SSIM_SLOTS + k]; }
         const double nv = (double)m.vpi;                                  // the sums cover the step's views: report their mean
-        m.last_loss = (float)(l1 / nv) + (w > 0.f ? w * (1.f - (float)(ssim_sum / nv / (3.0 * m.W * m.H))) : 0.f);
+        m.last_loss = (float)(l1 / nv) + (w > 0.f ? w * (1.f - (float)(ssim_sum / nv / (3.0 * m.lw * m.lh))) : 0.f);
     }
     return m.last_loss;
 }
@@ -1096,6 +1188,7 @@ double GaussianTrainerScene::getTrainingElpasedTime() const {
 }
 int GaussianTrainerScene::getNumGaussians() const { return impl_->n; }
 int GaussianTrainerScene::getNumCameras() const { return (int)impl_->cams.size(); }
+int GaussianTrainerScene::getCurrentDownscale() const { return 1 << impl_->level_of(impl_->step); }
 int GaussianTrainerScene::getNumTestCameras() const { return (int)impl_->test_idx.size(); }
 bool GaussianTrainerScene::evaluateTestSet() { return impl_->evaluate(false, true); }
 double GaussianTrainerScene::getTestPSNR() const { return impl_->eval_mean[3]; }

@@ -30,3 +30,10 @@ def synth_target(spec, index=0):
     t = np.empty((3, spec.height, spec.width), np.float32)
     check(lib.dvs_synth_target(C.byref(spec), index, t.ctypes.data), "dvs_synth_target")
     return t
+
+
+def camera_downscale(cam, factor):
+    """The level camera of `cam` for its image box-downsampled by factor 1, 2, 4 or 8 (dvs_camera_downscale)."""
+    out = Camera()
+    check(lib.dvs_camera_downscale(C.byref(cam), int(factor), C.byref(out)), "dvs_camera_downscale")
+    return out

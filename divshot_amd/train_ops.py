@@ -1,7 +1,7 @@
 """ctypes wrappers of include/dvs_train.h (loss gradient, SSIM, fused Adam) on torch CUDA tensors."""
 import ctypes as C
 import torch
-from ._lib import lib, check, AdamGroup, MetricsView
+from ._lib import lib, check, AdamGroup, MetricsView, DownsampleView
 
 
 def _st():
@@ -74,6 +74,24 @@ def image_metrics(imgs, targets, masks=None):
     out = torch.empty((max(V, 1), 4), dtype=torch.float64, device=dev)
     check(lib.dvs_image_metrics_views(_st(), arr, V, W, H, int(u8), scratch.data_ptr(), out.data_ptr()), "dvs_image_metrics_views")
     return out[:V]
+
+
+def downsample_views(srcs, factor):
+    """Box downsample of V views by factor 1, 2, 4 or 8 in one call (dvs_downsample_views) -> list of V float32 [planes, H // f, W // f]
+    tensors (asynchronous). srcs: V contiguous [planes, H, W] tensors of one shape, all float32 or all uint8; any element alignment."""
+    srcs = list(srcs)
+    V = len(srcs)
+    planes, H, W = (int(d) for d in srcs[0].shape)
+    u8 = srcs[0].dtype == torch.uint8
+    for x in srcs:
+        if x.dtype != (torch.uint8 if u8 else torch.float32) or tuple(x.shape) != (planes, H, W) or not x.is_contiguous():
+            raise ValueError("downsample_views: every source must be a contiguous [planes,H,W] tensor of one shape, all float32 or all uint8")
+    outs = [torch.empty((planes, H // factor, W // factor), dtype=torch.float32, device=x.device) for x in srcs]
+    arr = (DownsampleView * max(V, 1))()
+    for a, x, o in zip(arr, srcs, outs):
+        a.src, a.dst = x.data_ptr(), o.data_ptr()
+    check(lib.dvs_downsample_views(_st(), arr, V, planes, W, H, int(factor), int(u8)), "dvs_downsample_views")
+    return outs
 
 
 def adam_step(param, grad, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-15):

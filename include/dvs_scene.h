@@ -33,6 +33,16 @@ int dvs_synth_camera(const dvs_scene_spec* spec, int index, dvs_camera* out);
 int dvs_synth_target(const dvs_scene_spec* spec, int index, float* target);
 /* Build a camera from pose (world->camera rotation R row-major [9], translation t[3]) and pinhole fov. */
 int dvs_make_camera(const float* R, const float* t, float fov_x_deg, int width, int height, dvs_camera* out);
+/* The camera of `in` for its image box-downsampled by `factor` (1, 2, 4 or 8; dvs_downsample_views, include/dvs_train.h): the level
+ * camera of coarse-to-fine training. view, campos, bg unchanged; width = W / d, height = H / d (floor); focal_{x,y} /= d (exact).
+ * With s_x = W / (d W_d), s_y = H / (d H_d) in double (1 when d divides the size, > 1 when columns / rows are cropped):
+ *   proj'[k*4+0] = s_x proj[k*4+0] + (s_x - 1) proj[k*4+3],   proj'[k*4+1] likewise with s_y (k = 0..3),   rows 2 and 3 unchanged,
+ *   tan_fov' = tan_fov / s    (s == 1: proj and tan_fov come out bit-identical to the input).
+ * A splat at pixel x of the full image (pixel i has its centre at i) then lands at (x + 0.5) / d - 0.5 of the level image, the
+ * centre of mass of the box filter. The cropped principal point is no longer the image centre, which moves the 1.3 tan_fov guard
+ * of the covariance clamp by less than half a level pixel; that is left as it is.
+ * DVS_ERR_INVALID for a NULL argument, in == out, another factor, or a size that would become 0. Factor 1 is a copy. */
+int dvs_camera_downscale(const dvs_camera* in, int factor, dvs_camera* out);
 
 #ifdef __cplusplus
 }

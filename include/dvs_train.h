@@ -67,6 +67,23 @@ size_t dvs_image_metrics_scratch_bytes(int width, int height, int n_views);
 int dvs_image_metrics_views(void* stream, const dvs_metrics_view* views /* HOST [n_views] */, int n_views,
                             int width, int height, int target_u8, void* scratch, double* out /* DEVICE [n_views][4] */);
 
+/* ---- box downsample of a batch of views (coarse-to-fine training: the level targets and masks of resolutionSchedule) -----------------
+ * dst(x, y) = mean of the source block [x f, x f + f) x [y f, y f + f), per plane; dst is [planes, height/f, width/f] (floor): the
+ * width - (width/f) f rightmost columns and the matching bottom rows of the source are not used. ALL views in ONE launch; no atomics,
+ * no scratch. The result is defined bit for bit, whatever path the kernel takes for a view:
+ *   uint8 source   ((float)S * (1.0f/255.0f)) * (1.0f/(f*f)), S the exact integer sum of the block (f = 1: the trainer's 8-bit expansion)
+ *   fp32 source    the block's values added in fp32 in row-major order, starting from the first one, then * (1.0f/(f*f))
+ *   views     HOST array [n_views] (1..DVS_DOWNSAMPLE_MAX_VIEWS) of DEVICE pointers, all views the same size; copied before the call returns
+ *   planes    3 for images, 1 for masks;  factor 1, 2, 4 or 8;  src_u8: the sources are uint8, not fp32
+ *   alignment only the natural alignment of the element (4 bytes for fp32, 1 for uint8). A view whose src and dst are 16-byte aligned
+ *             and whose widths allow it (width % 16 == 0 for uint8, % 4 for fp32; (width/f) % 4 == 0) is moved as 16-byte words.
+ * DVS_ERR_INVALID for NULL views / src / dst, n_views outside 1..16, planes < 1, another factor, width/f == 0 or height/f == 0.
+ * Asynchronous on `stream`. */
+#define DVS_DOWNSAMPLE_MAX_VIEWS 16
+typedef struct dvs_downsample_view { const void* src; float* dst; } dvs_downsample_view;   /* DEVICE pointers */
+int dvs_downsample_views(void* stream, const dvs_downsample_view* views /* HOST [n_views] */, int n_views,
+                         int planes, int width, int height, int factor, int src_u8);
+
 /* Fused Adam over one parameter array (count floats): m, v are the moment arrays (same size, DEVICE).
  * step is 1-based. Asynchronous. */
 int dvs_adam_step(void* stream, float* param, const float* grad, float* m, float* v, size_t count, float lr, float beta1,

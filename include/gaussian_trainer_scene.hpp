@@ -74,6 +74,13 @@ struct GaussianTrainConfig {
     // DVS_EVAL_EVERY override them (the reference's hosts do not know the fields).
     int evalHoldout = 0;
     int evalEvery = 0;
+    // extension of this build, appended the same way: the number of levels of the coarse-to-fine schedule that the reference's field
+    // resolutionSchedule (above; 0 = off, the editor's dataset import sets 3000: editor.cpp:2016) turns on. With S = resolutionSchedule > 0
+    // and K = numDownscales the step after `step` completed ones trains at level k = max(K - step / S, 0): on the training views
+    // box-filtered by 2^k (W / 2^k x H / 2^k, floor) through the cameras of dvs_camera_downscale — the published rule of the lineage:
+    // start at 1/2^K, double every S steps. K is clamped at load to 3 and so that the smaller image side stays >= 16 pixels. Saved
+    // models and the held-out evaluation are always at full resolution. DVS_RESOLUTION_SCHEDULE / DVS_NUM_DOWNSCALES override the two.
+    int numDownscales = 2;
 };
 
 class GSTRAIN_API GaussianTrainerScene {
@@ -118,6 +125,7 @@ public:
     double getTrainingElpasedTime() const;
     int getNumGaussians() const;
     int getNumCameras() const;                        // all cameras, held-out ones included
+    int getCurrentDownscale() const;                  // 1, 2, 4 or 8: the divisor of the image size the next trainStep() trains at (1 when resolutionSchedule is 0)
     // held-out evaluation (extension of this build; config evalHoldout / evalEvery)
     int getNumTestCameras() const;                    // 0 when evaluation is off
     bool evaluateTestSet();                           // renders and scores the test cameras now, synchronises; false when evaluation is off
