@@ -171,7 +171,14 @@ _PROTOS = {
     "dvs_adam_step_groups": (C.c_int, [C.c_void_p, C.POINTER(AdamGroup), C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p,
                                        C.c_int32]),
 }
-for _name, (_res, _args) in _PROTOS.items():
+# include/dvs_export.h: the model export packers (a table of their own: _PROTOS is the list of the four headers above)
+_EXPORT_PROTOS = {
+    "dvs_pack_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "dvs_pack_compressed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
+    "dvs_pack_splat32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+for _name, (_res, _args) in list(_PROTOS.items()) + list(_EXPORT_PROTOS.items()):
     _f = getattr(lib, _name)          # AttributeError here = the .so does not export a declared symbol
     _f.restype = _res
     _f.argtypes = _args

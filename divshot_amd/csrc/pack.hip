@@ -1,0 +1,264 @@
+// pack.hip — model export packers (include/dvs_export.h): the device-resident splats into the payload of DIVSHOT's chunked, quantised
+// .compressed.ply (external/tinygsplat/tiny_gsplat.cpp:293-396, tiny_gsplat.hpp:342-468) and into 32-byte .splat records
+// (tiny_gsplat.cpp:243-291). A per-splat streaming job over 56 B of input per splat; shN is never read.
+//   (a) k_pack_bounds / k_pack_bounds_final: min / max of pos per axis. Every workgroup writes its partial result to its own slot, one
+//       small workgroup combines the slots: no float atomics, the result does not depend on the schedule.
+//   (b) k_pack_morton: one 30-bit Morton key (10 bits per axis over the model's box) and the splat index per splat.
+//   (c) the stable segmented LSD radix sort of frontend.hip (dvs_launch_seg_sort, one segment, four passes, ballot ranking): equal
+//       keys stay in index order.
+//   (d) k_pack_chunks: one workgroup of 256 lanes per chunk of 256 consecutive sorted entries (the last may be partial). A lane gathers
+//       its splat by sorted index; the chunk's bounds of pos and of the raw scale are taken over the chunk's OWN members (the reference's
+//       calcMinMax seeds them with p[start] instead of p[indices[start]], tiny_gsplat.hpp:332, which can only widen the box: not
+//       reproduced); a lane leaves ONE 16-byte record, so a wavefront stores 1 KiB contiguously; lanes 0-11 write the chunk row.
+//   (e) k_pack_splat32: one 32-byte record per splat in the model's order, two 16-byte stores per lane.
+// Results are defined bit for bit (tests/compressed_ply_ref.py restates them in numpy): compiled without contraction (EXACT), IEEE
+// division and square root, min / max are order-independent. No atomics, no inline assembly, plain vector stores.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include "dvs_device.h"
+#include "dvs_kernels.h"
+#include "../../include/dvs_raster.h"
+#include "../../include/dvs_export.h"
+
+namespace {
+constexpr int PK_BLOCK = 256, PK_WAVES = PK_BLOCK / 64;
+constexpr int PK_BOUNDS_BLOCKS = 512;                      // at most this many partial slots; the workgroups stride over the splats
+constexpr int PK_CHUNK = 256;                              // splats per chunk of the format
+
+__device__ __forceinline__ float pk_wave_min(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
+    return v;
+}
+__device__ __forceinline__ float pk_wave_max(float v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
+    return v;
+}
+
+// workgroup-wide min of lo[0..K) and max of hi[0..K): every lane returns with the results. lds = [PK_WAVES][2 K] floats.
+template <int K>
+__device__ __forceinline__ void pk_block_minmax(float (&lo)[K], float (&hi)[K], float* lds) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < K; ++k) { lo[k] = pk_wave_min(lo[k]); hi[k] = pk_wave_max(hi[k]); }
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) { lds[wave * 2 * K + k] = lo[k]; lds[wave * 2 * K + K + k] = hi[k]; }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        float a = lds[k], b = lds[K + k];
+#pragma unroll
+        for (int w = 1; w < PK_WAVES; ++w) { a = fminf(a, lds[w * 2 * K + k]); b = fmaxf(b, lds[w * 2 * K + K + k]); }
+        lo[k] = a; hi[k] = b;
+    }
+}
+// the same result for ONE of the 2 K values, chosen by a lane-dependent index t (0 .. K - 1: minima, K .. 2 K - 1: maxima), read from
+// what pk_block_minmax left in LDS: no dynamically indexed register array
+template <int K>
+__device__ __forceinline__ float pk_block_result(const float* lds, int t) {
+    float r = lds[t];
+#pragma unroll
+    for (int w = 1; w < PK_WAVES; ++w) { const float o = lds[w * 2 * K + t]; r = t < K ? fminf(r, o) : fmaxf(r, o); }
+    return r;
+}
+
+// (a) slots[block] = {min xyz, max xyz} over the splats block * 256 + tid, + gridDim * 256, ...
+__global__ void __launch_bounds__(PK_BLOCK)
+k_pack_bounds(int n, const float* __restrict__ pos, float* __restrict__ slots) {
+    __shared__ float lds[PK_WAVES * 6];
+    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    for (int64_t i = (int64_t)blockIdx.x * PK_BLOCK + threadIdx.x; i < n; i += (int64_t)gridDim.x * PK_BLOCK) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { const float p = pos[3 * i + k]; lo[k] = fminf(lo[k], p); hi[k] = fmaxf(hi[k], p); }
+    }
+    pk_block_minmax<3>(lo, hi, lds);
+    if (threadIdx.x < 6) slots[blockIdx.x * 6 + threadIdx.x] = pk_block_result<3>(lds, (int)threadIdx.x);
+}
+// one workgroup: bounds[0..6) = the slots combined
+__global__ void __launch_bounds__(PK_BLOCK)
+k_pack_bounds_final(int n_slots, const float* __restrict__ slots, float* __restrict__ bounds) {
+    __shared__ float lds[PK_WAVES * 6];
+    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()}, hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    for (int s = threadIdx.x; s < n_slots; s += PK_BLOCK) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], slots[s * 6 + k]); hi[k] = fmaxf(hi[k], slots[s * 6 + 3 + k]); }
+    }
+    pk_block_minmax<3>(lo, hi, lds);
+    if (threadIdx.x < 6) bounds[threadIdx.x] = pk_block_result<3>(lds, (int)threadIdx.x);
+}
+
+// bits 0..9 of q spread to every third bit
+__device__ __forceinline__ uint32_t pk_spread3(uint32_t q) {
+    uint32_t r = 0;
+#pragma unroll
+    for (int i = 0; i < 10; ++i) r |= ((q >> i) & 1u) << (3 * i);
+    return r;
+}
+
+// (b) keys[i] = 30-bit Morton code of pos[i] in the model's box, vals[i] = i
+__global__ void __launch_bounds__(PK_BLOCK)
+k_pack_morton(int n, const float* __restrict__ pos, const float* __restrict__ bounds, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
+    const int64_t i = (int64_t)blockIdx.x * PK_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    uint32_t key = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float mn = bounds[k], ext = bounds[3 + k] - mn;
+        const float rel = ext < 1e-5f ? 0.0f : (pos[3 * i + k] - mn) / ext;
+        const float s = fminf(fmaxf(rel * 1023.0f, 0.0f), 1023.0f);       // rel is in [0, 1] already; a NaN position lands in cell 0
+        key |= pk_spread3((uint32_t)s) << k;
+    }
+    keys[i] = key;
+    vals[i] = (uint32_t)i;
+}
+
+__device__ __forceinline__ float pk_norm(float x, float mn, float mx) { const float e = mx - mn; return e < 0.00001f ? 0.0f : (x - mn) / e; }
+// tiny_gsplat.hpp:342-346: the product in fp32, the rounding in fp64
+__device__ __forceinline__ uint32_t pk_unorm(float v, int bits) {
+    const int t = (1 << bits) - 1;
+    const double r = floor((double)(v * (float)t) + 0.5);
+    return (uint32_t)fmin(fmax(r, 0.0), (double)t);                        // (fmax(NaN, 0) = 0)
+}
+__device__ __forceinline__ uint32_t pk_111011(float x, float y, float z) { return pk_unorm(x, 11) << 21 | pk_unorm(y, 10) << 11 | pk_unorm(z, 11); }
+
+// q = rot / |rot| with correctly rounded sqrt and divisions; a squared norm of 0 or not finite gives (1, 0, 0, 0)
+__device__ __forceinline__ void pk_quat(const float4 r, float q[4]) {
+    const float ss = ((r.x * r.x + r.y * r.y) + r.z * r.z) + r.w * r.w;
+    if (!(ss > 0.0f) || !(ss < __builtin_inff())) { q[0] = 1.0f; q[1] = q[2] = q[3] = 0.0f; return; }
+    const float len = dvs_sqrt_rn(ss);
+    q[0] = r.x / len; q[1] = r.y / len; q[2] = r.z / len; q[3] = r.w / len;
+}
+__device__ __forceinline__ uint32_t pk_rot(const float4 r) {
+    float q[4];
+    pk_quat(r, q);
+    int largest = 0;
+    float ql = q[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) if (fabsf(q[k]) > fabsf(ql)) { largest = k; ql = q[k]; }      // the first of equal magnitudes stays
+    const float sgn = ql < 0.0f ? -1.0f : 1.0f;
+    uint32_t result = (uint32_t)largest;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k != largest) result = (result << 10) | pk_unorm((sgn * q[k]) * 0.70710678f + 0.5f, 10);
+    return result;
+}
+
+// (d) chunk c = sorted entries [256 c, min(n, 256 c + 256))
+__global__ void __launch_bounds__(PK_BLOCK)
+k_pack_chunks(int n, const uint32_t* __restrict__ sorted, const float* __restrict__ pos, const float* __restrict__ sh0,
+              const float* __restrict__ opacity, const float* __restrict__ scale, const float* __restrict__ rot,
+              float* __restrict__ chunks, uint4* __restrict__ verts, uint32_t* __restrict__ order) {
+    __shared__ float lds[PK_WAVES * 12];
+    const int64_t j = (int64_t)blockIdx.x * PK_CHUNK + threadIdx.x;
+    const bool valid = j < n;
+    const uint32_t id = valid ? sorted[j] : 0u;
+    float p[3], s[3], lo[6], hi[6];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        p[k] = pos[3 * (size_t)id + k]; s[k] = scale[3 * (size_t)id + k];
+        lo[k] = valid ? p[k] : __builtin_inff(); hi[k] = valid ? p[k] : -__builtin_inff();
+        lo[3 + k] = valid ? s[k] : __builtin_inff(); hi[3 + k] = valid ? s[k] : -__builtin_inff();
+    }
+    pk_block_minmax<6>(lo, hi, lds);
+    if (threadIdx.x < 12) {                                                // {pmin, pmax, smin, smax} from the LDS order {pmin, smin, pmax, smax}
+        const int t = threadIdx.x;
+        chunks[(size_t)blockIdx.x * 12 + t] = pk_block_result<6>(lds, t < 3 ? t : t < 6 ? t + 3 : t < 9 ? t - 3 : t);
+    }
+    if (!valid) return;
+    const float c0 = sh0[3 * (size_t)id], c1 = sh0[3 * (size_t)id + 1], c2 = sh0[3 * (size_t)id + 2];
+    const float4 r = reinterpret_cast<const float4*>(rot)[id];
+    uint4 w;
+    w.x = pk_111011(pk_norm(p[0], lo[0], hi[0]), pk_norm(p[1], lo[1], hi[1]), pk_norm(p[2], lo[2], hi[2]));
+    w.y = pk_rot(r);
+    w.z = pk_111011(pk_norm(s[0], lo[3], hi[3]), pk_norm(s[1], lo[4], hi[4]), pk_norm(s[2], lo[5], hi[5]));
+    w.w = pk_unorm(c0 * DVS_SH_C0 + 0.5f, 8) << 24 | pk_unorm(c1 * DVS_SH_C0 + 0.5f, 8) << 16 | pk_unorm(c2 * DVS_SH_C0 + 0.5f, 8) << 8 |
+          pk_unorm(dvs_sigmoid_det(opacity[id]), 8);
+    verts[j] = w;
+    if (order) order[j] = id;
+}
+
+__device__ __forceinline__ uint32_t pk_trunc_u8(float v) { return (uint32_t)fminf(fmaxf(v, 0.0f), 255.0f); }
+
+// (e) one 32-byte record per splat
+__global__ void __launch_bounds__(PK_BLOCK)
+k_pack_splat32(int n, const float* __restrict__ pos, const float* __restrict__ sh0, const float* __restrict__ opacity,
+               const float* __restrict__ scale, const float* __restrict__ rot, uint4* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * PK_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    float q[4];
+    pk_quat(reinterpret_cast<const float4*>(rot)[i], q);
+    uint4 a, b;
+    a.x = __float_as_uint(pos[3 * i]); a.y = __float_as_uint(pos[3 * i + 1]); a.z = __float_as_uint(pos[3 * i + 2]);
+    a.w = __float_as_uint(dvs_exp_det(scale[3 * i]));
+    b.x = __float_as_uint(dvs_exp_det(scale[3 * i + 1])); b.y = __float_as_uint(dvs_exp_det(scale[3 * i + 2]));
+    b.z = pk_trunc_u8((0.5f + DVS_SH_C0 * sh0[3 * i]) * 255.0f) | pk_trunc_u8((0.5f + DVS_SH_C0 * sh0[3 * i + 1]) * 255.0f) << 8 |
+          pk_trunc_u8((0.5f + DVS_SH_C0 * sh0[3 * i + 2]) * 255.0f) << 16 | pk_trunc_u8(dvs_sigmoid_det(opacity[i]) * 255.0f) << 24;
+    b.w = pk_trunc_u8(q[0] * 128.0f + 128.0f) | pk_trunc_u8(q[1] * 128.0f + 128.0f) << 8 | pk_trunc_u8(q[2] * 128.0f + 128.0f) << 16 |
+          pk_trunc_u8(q[3] * 128.0f + 128.0f) << 24;
+    out[2 * i] = a;
+    out[2 * i + 1] = b;
+}
+
+// the scratch of dvs_pack_compressed: byte offsets of its parts, each on a 256-byte boundary
+struct PackScratch { size_t slots, bounds, seg, totals, hist, key[2], val[2], total; };
+PackScratch pack_layout(int n) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    PackScratch L;
+    size_t o = 0;
+    L.slots = o; o += up((size_t)PK_BOUNDS_BLOCKS * 6 * sizeof(float));
+    L.bounds = o; o += up(6 * sizeof(float));
+    L.seg = o; o += up(sizeof(DvsSeg));
+    L.totals = o; o += up((size_t)DVS_FE_MAXBINS * sizeof(uint32_t));
+    L.hist = o; o += up(dvs_fe_hist_words((uint64_t)n, 1, 512) * sizeof(uint32_t));
+    for (int k = 0; k < 2; ++k) { L.key[k] = o; o += up((size_t)n * 4); L.val[k] = o; o += up((size_t)n * 4); }
+    L.total = o;
+    return L;
+}
+bool off16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
+}  // namespace
+
+extern "C" size_t dvs_pack_scratch_bytes(int n) { return n > 0 ? pack_layout(n).total : 0; }
+
+extern "C" int dvs_pack_compressed(void* stream, int n, const float* pos, const float* sh0, const float* opacity, const float* scale,
+                                   const float* rot, void* scratch, float* chunks, uint32_t* verts, uint32_t* order) {
+    if (n <= 0 || !pos || !sh0 || !opacity || !scale || !rot || !scratch || !chunks || !verts) return DVS_ERR_INVALID;
+    if (off16(pos) || off16(sh0) || off16(opacity) || off16(scale) || off16(rot) || off16(scratch) || off16(chunks) || off16(verts) || off16(order))
+        return DVS_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const PackScratch L = pack_layout(n);
+    char* const base = (char*)scratch;
+    float* const slots = (float*)(base + L.slots);
+    float* const bounds = (float*)(base + L.bounds);
+    DvsSeg* const seg = (DvsSeg*)(base + L.seg);
+    uint32_t* key[2] = {(uint32_t*)(base + L.key[0]), (uint32_t*)(base + L.key[1])};
+    uint32_t* val[2] = {(uint32_t*)(base + L.val[0]), (uint32_t*)(base + L.val[1])};
+    const unsigned nblocks = (unsigned)(((int64_t)n + PK_BLOCK - 1) / PK_BLOCK);
+    const unsigned bblocks = nblocks < (unsigned)PK_BOUNDS_BLOCKS ? nblocks : (unsigned)PK_BOUNDS_BLOCKS;
+    hipLaunchKernelGGL(k_pack_bounds, dim3(bblocks), dim3(PK_BLOCK), 0, st, n, pos, slots);
+    hipLaunchKernelGGL(k_pack_bounds_final, dim3(1), dim3(PK_BLOCK), 0, st, (int)bblocks, (const float*)slots, bounds);
+    hipLaunchKernelGGL(k_pack_morton, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, pos, (const float*)bounds, key[0], val[0]);
+    if (hipGetLastError() != hipSuccess) return DVS_ERR_HIP;
+    // one segment [0, n); ballot ranking (rank_atomic = 0): correct by construction, no probe of the device needed
+    const uint32_t part = dvs_fe_part_for((uint64_t)n);
+    int cur = 0;
+    if (dvs_launch_seg_init(st, n, 1, 0, seg) != hipSuccess) return DVS_ERR_HIP;
+    if (dvs_launch_seg_sort(st, 1, key[0], val[0], key[1], val[1], seg, 0, 30, (uint64_t)n, part, (uint32_t)((uint32_t)n / part) + 3u,
+                            (uint32_t*)(base + L.hist), (uint32_t*)(base + L.totals), 0u, &cur, nullptr, 1, 0, 0) != hipSuccess)
+        return DVS_ERR_HIP;
+    const unsigned nchunks = (unsigned)(((int64_t)n + PK_CHUNK - 1) / PK_CHUNK);
+    hipLaunchKernelGGL(k_pack_chunks, dim3(nchunks), dim3(PK_BLOCK), 0, st, n, (const uint32_t*)val[cur], pos, sh0, opacity, scale, rot, chunks,
+                       (uint4*)verts, order);
+    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+}
+
+extern "C" int dvs_pack_splat32(void* stream, int n, const float* pos, const float* sh0, const float* opacity, const float* scale,
+                                const float* rot, uint8_t* out) {
+    if (n <= 0 || !pos || !sh0 || !opacity || !scale || !rot || !out) return DVS_ERR_INVALID;
+    if (off16(pos) || off16(sh0) || off16(opacity) || off16(scale) || off16(rot) || off16(out)) return DVS_ERR_INVALID;
+    const unsigned nblocks = (unsigned)(((int64_t)n + PK_BLOCK - 1) / PK_BLOCK);
+    hipLaunchKernelGGL(k_pack_splat32, dim3(nblocks), dim3(PK_BLOCK), 0, (hipStream_t)stream, n, pos, sh0, opacity, scale, rot, (uint4*)out);
+    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+}

@@ -8,6 +8,7 @@
 // The reference's own gs_train.cpp cannot be compiled here (it needs the closed header and <format>);
 // CLI11 / indicators / spdlog are replaced by a few lines of standard C++.
 #include <dlfcn.h>
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -32,7 +33,10 @@ static std::map<std::string, std::string> g_opts = {
     {"evalHoldout", "-1"}, {"evalEvery", "0"},
     // the reference's config field resolutionSchedule (its CLI has no flag for it; the editor sets 3000) and this build's numDownscales:
     // coarse-to-fine training, start at 1/2^K of the image size and double every N steps (0 = off)
-    {"resolutionSchedule", "0"}, {"numDownscales", "2"}};
+    {"resolutionSchedule", "0"}, {"numDownscales", "2"},
+    // extension of this build: compact formats every save writes beside the full PLY: compressed | splat | compressed,splat
+    // (<outputPath>_<it>.compressed.ply / .splat); empty = none, unless --outputPath itself ends in .compressed.ply / .splat
+    {"exportFormat", ""}};
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
 
@@ -107,6 +111,15 @@ int main(int argc, const char* argv[]) {
     train_config.evalEvery = atoi(g_opts["evalEvery"].c_str());
     train_config.resolutionSchedule = atoi(g_opts["resolutionSchedule"].c_str());
     train_config.numDownscales = atoi(g_opts["numDownscales"].c_str());
+    for (size_t at = 0; at < g_opts["exportFormat"].size();) {
+        const std::string& v = g_opts["exportFormat"];
+        const size_t comma = std::min(v.find(',', at), v.size());
+        const std::string tok = v.substr(at, comma - at);
+        if (tok == "compressed") train_config.exportFormats |= 1;
+        else if (tok == "splat") train_config.exportFormats |= 2;
+        else { std::cout << "Command Line Error: --exportFormat takes compressed, splat or compressed,splat, not '" << tok << "'\n"; return 1; }
+        at = comma + 1;
+    }
     train_config.normalConsistencyLoss = false;
     if (train_config.exportMesh) { train_config.normalConsistencyLoss = true; train_config.useMask = true; }
     train_config.verbose = true;

@@ -30,6 +30,7 @@
 #include "../../include/dvs_scene.h"
 #include "../../include/dvs_train.h"
 #include "../../include/dvs_comm.h"
+#include "../../include/dvs_export.h"
 #include "ply_io.hpp"
 
 namespace {
@@ -152,6 +153,10 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     int cur_level = -1;                                                      // level of the last step (-1: none yet)
     int lw = 0, lh = 0;                                                      // image size of the last step (W x H when the schedule is off)
     int level_first_step = 0; std::chrono::steady_clock::time_point level_t0;
+    // compact exports beside the full PLY (cfg.exportFormats / DVS_EXPORT_FORMATS / the suffix of modelPath): the packers' scratch, the
+    // packed payload on the device and its host copy. Nothing is allocated until a save exports; the buffers only grow.
+    void* d_export_scratch = nullptr; uint8_t* d_export_out = nullptr; size_t export_scratch_cap = 0, export_out_cap = 0;
+    std::vector<uint8_t> export_host;
 
     ~Impl() { release(); }
     void release() {
@@ -179,6 +184,8 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         d_targets.clear();
         for (float** p : {&d_absgrad, &d_out, &d_dL, &d_loss, &d_ssim_maps[0], &d_ssim_maps[1], &d_ssim_maps[2]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
         for (void** p : {(void**)&d_eval_out, &d_eval_scratch, (void**)&d_eval_res}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        for (void** p : {&d_export_scratch, (void**)&d_export_out}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        export_scratch_cap = export_out_cap = 0;
         if (eval_ctx) { dvs_destroy(eval_ctx); eval_ctx = nullptr; }
         if (ctx) { dvs_destroy(ctx); ctx = nullptr; }
         if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; }
@@ -303,6 +310,20 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         return s;
     }
     std::string model_file(int it) const { return cfg.modelPath + "_" + std::to_string(it) + ".ply"; }
+    bool model_path_ends(const char* suffix) const {
+        const size_t k = strlen(suffix);
+        return cfg.modelPath.size() >= k && cfg.modelPath.compare(cfg.modelPath.size() - k, k, suffix) == 0;
+    }
+    // EXPORT_* bits of the compact formats a save writes; decided at every use, since the editor sets modelPath after construction
+    enum { EXPORT_COMPRESSED = 1, EXPORT_SPLAT = 2 };
+    int suffix_formats() const { return model_path_ends(".compressed.ply") ? EXPORT_COMPRESSED : model_path_ends(".splat") ? EXPORT_SPLAT : 0; }
+    int export_formats() const {
+        int f = cfg.exportFormats;
+        if (const char* e = getenv("DVS_EXPORT_FORMATS")) f = atoi(e);
+        if (f == 0) f = suffix_formats();
+        return f & (EXPORT_COMPRESSED | EXPORT_SPLAT);
+    }
+    void export_model(int format);
     void fetch_host() {
         if (host_valid) return;
         HIP_OR_THROW(hipStreamSynchronize(stream));
@@ -353,7 +374,12 @@ void GaussianTrainerScene::Impl::report_config() const {
         logf_("config: resolutionSchedule %d, numDownscales %d: coarse-to-fine training, the step after s completed ones renders 1/2^max(%d - s/%d, 0) of "
               "%dx%d (targets box-filtered per step, cameras of dvs_camera_downscale); full resolution from iteration %d; evaluation always at full size",
               res_every, res_levels, res_levels, res_every, W, H, res_levels * res_every + 1);
+    if (const int fmts = export_formats())
+        logf_("config: exportFormats %d: every save also writes%s%s beside the full PLY, packed on the device%s", fmts,
+              (fmts & EXPORT_COMPRESSED) ? " <modelPath>_<it>.compressed.ply" : "", (fmts & EXPORT_SPLAT) ? " <modelPath>_<it>.splat" : "",
+              (cfg.exportFormats == 0 && !getenv("DVS_EXPORT_FORMATS")) ? " (turned on by the suffix of modelPath)" : "");
     std::string ign;
+    if (model_path_ends(".spz")) ign += " modelPath suffix .spz(spz export: the full PLY is written)";
     if (cfg.modelType != 0) ign += " modelType(only 3DGS)";
     if (cfg.cullSH) ign += " cullSH";
     if (cfg.pixelGradScale) ign += " pixelGradScale";
@@ -1039,6 +1065,7 @@ void GaussianTrainerScene::saveGaussianModel() {
     // is how the two-rank test checks that they ARE identical, bit for bit
     static const bool all_ranks = [] { const char* e = getenv("DVS_SAVE_ALL_RANKS"); return e && e[0] == '1'; }();
     if (m.rank != 0 && !all_ranks) return;
+    const auto t_save = std::chrono::steady_clock::now();
     m.fetch_host();
     const std::string file = m.model_file(m.step) + (m.rank != 0 ? ".rank" + std::to_string(m.rank) : std::string());
     std::error_code ec;
@@ -1049,7 +1076,58 @@ void GaussianTrainerScene::saveGaussianModel() {
                           m.host[5].data(), m.cfg.mipAntiliased, &err))
         logf_("save_splat_model: %s", err.c_str());
     else if (m.cfg.verbose) logf_("saved %d splats to %s", m.n, file.c_str());
+    if (m.rank == 0 && m.export_formats()) {                                // the comparison for the compact exports' lines below
+        std::error_code fec;
+        const auto ply_bytes = std::filesystem::file_size(file, fec);
+        logf_("export @%d: ply %d splats, %llu bytes, %.2f ms", m.step, m.n, (unsigned long long)(fec ? 0 : ply_bytes),
+              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_save).count());
+    }
+    if (m.rank == 0)
+        for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT})
+            if (m.export_formats() & format) m.export_model(format);
     m.evaluate(true);                                                       // <modelPath>_<it>_eval.json beside the PLY (rank 0, evaluation on)
+}
+
+// One compact export of the current model: packed on the training stream from the device arrays (shN is not read, so its tiled layout
+// does not matter), the packed payload alone copied to the host and written to <modelPath>_<step>.compressed.ply / .splat.
+void GaussianTrainerScene::Impl::export_model(int format) {
+    const auto t_start = std::chrono::steady_clock::now();
+    const bool compressed = format == EXPORT_COMPRESSED;
+    const size_t n_chunks = ((size_t)n + 255) / 256;
+    const size_t chunk_bytes = n_chunks * 12 * sizeof(float);              // (a multiple of 16: the vertex records follow on a 16-byte boundary)
+    const size_t bytes = compressed ? chunk_bytes + (size_t)n * 16 : (size_t)n * 32;
+    if (bytes > export_out_cap) {
+        if (d_export_out) { (void)hipFree(d_export_out); d_export_out = nullptr; export_out_cap = 0; }
+        HIP_OR_THROW(hipMalloc((void**)&d_export_out, bytes));
+        export_out_cap = bytes;
+    }
+    if (export_host.size() < bytes) export_host.resize(bytes);
+    int status;
+    if (compressed) {
+        const size_t need = dvs_pack_scratch_bytes(n);
+        if (need > export_scratch_cap) {
+            if (d_export_scratch) { (void)hipFree(d_export_scratch); d_export_scratch = nullptr; export_scratch_cap = 0; }
+            HIP_OR_THROW(hipMalloc(&d_export_scratch, need));
+            export_scratch_cap = need;
+        }
+        status = dvs_pack_compressed(stream, n, d_param[P_POS], d_param[P_SH0], d_param[P_OPA], d_param[P_SCALE], d_param[P_ROT], d_export_scratch,
+                                     (float*)d_export_out, (uint32_t*)(d_export_out + chunk_bytes), nullptr);
+    } else {
+        status = dvs_pack_splat32(stream, n, d_param[P_POS], d_param[P_SH0], d_param[P_OPA], d_param[P_SCALE], d_param[P_ROT], d_export_out);
+    }
+    if (status != DVS_OK) throw std::runtime_error(std::string(compressed ? "dvs_pack_compressed" : "dvs_pack_splat32") + ": status " + std::to_string(status));
+    HIP_OR_THROW(hipMemcpyAsync(export_host.data(), d_export_out, bytes, hipMemcpyDeviceToHost, stream));
+    HIP_OR_THROW(hipStreamSynchronize(stream));
+    const std::string file = cfg.modelPath + "_" + std::to_string(step) + (compressed ? ".compressed.ply" : ".splat");
+    std::string err;
+    const bool ok = compressed ? gsply::write_compressed_ply(file, (size_t)n, (const float*)export_host.data(),
+                                                             (const uint32_t*)(export_host.data() + chunk_bytes), cfg.mipAntiliased, &err)
+                               : gsply::write_splat(file, (size_t)n, export_host.data(), &err);
+    if (!ok) { logf_("export @%d: %s", step, err.c_str()); return; }
+    std::error_code ec;
+    const auto file_bytes = std::filesystem::file_size(file, ec);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    logf_("export @%d: %s %d splats, %llu bytes, %.2f ms", step, compressed ? "compressed.ply" : "splat", n, (unsigned long long)(ec ? bytes : file_bytes), ms);
 }
 void GaussianTrainerScene::exportMesh(const std::string&) { logf_("export_mesh: mesh extraction is outside this build's scope"); }
 void GaussianTrainerScene::exportSparsePointCloud(const std::string& path) {
@@ -1098,7 +1176,11 @@ void GaussianTrainerScene::resetGaussian() {
     m.t0 = std::chrono::steady_clock::now();
 }
 void GaussianTrainerScene::setDensifyStrategy(int strategy) { impl_->cfg.densifyStrategy = std::min(2, std::max(0, strategy)); impl_->report_config(); }
-void GaussianTrainerScene::setModelPath(const std::string& path) { impl_->cfg.modelPath = path; }
+void GaussianTrainerScene::setModelPath(const std::string& path) {
+    const int before = impl_->export_formats();
+    impl_->cfg.modelPath = path;
+    if (impl_->export_formats() != before) impl_->report_config();         // the editor's "Splat Format" arrives as the suffix of the path
+}
 void GaussianTrainerScene::updateFocusRegion(const dvs_types::Vec3& position, const dvs_types::Vec3& rotation, const dvs_types::Vec3& scale) {
     focus_region_position = position; focus_region_rotation = rotation; focus_region_scale = scale;     // stored; enableFocusRegion is not used by the trainer
 }

@@ -4,6 +4,7 @@
 // with f_rest CHANNEL-major on disk ([c*15 + j], tiny_gsplat.cpp:231-236) while the in-memory shN block is
 // coefficient-major [j*3 + c] (gaussian_model.cpp:163-167) — the writer/reader transposes.
 #pragma once
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -12,4 +13,10 @@ bool write_ply(const std::string& path, size_t n, const float* pos, const float*
                const float* scale, const float* rot, bool antialiased, std::string* err);
 bool read_ply(const std::string& path, std::vector<float>& pos, std::vector<float>& sh0, std::vector<float>& shN,
               std::vector<float>& opacity, std::vector<float>& scale, std::vector<float>& rot, std::string* err);
+// The viewer's two compact formats, written from payloads packed on the device (include/dvs_export.h):
+// the chunked, quantised PLY with the header of tiny_gsplat.cpp:371-391 — `element chunk` ceil(n / 256) rows of 12 floats, then
+// `element vertex` n records of 4 uints (packed_position, packed_rotation, packed_scale, packed_color) — read by load_compress_ply
+// (tiny_gsplat.cpp:766-815); and the headerless .splat file of 32-byte records (tiny_gsplat.cpp:243-291).
+bool write_compressed_ply(const std::string& path, size_t n, const float* chunks, const uint32_t* verts, bool antialiased, std::string* err);
+bool write_splat(const std::string& path, size_t n, const uint8_t* bytes, std::string* err);
 }
