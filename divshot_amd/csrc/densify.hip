@@ -86,8 +86,12 @@ __global__ void __launch_bounds__(DB) k_any_view_radius(int n, int n_views, cons
 
 __device__ __forceinline__ int d_action(int i, const float* opacity, const float* scale, const float* grad_accum, const float* denom,
                                         const int* max_radii, const dvs_densify_params& p) {
-    const float op = 1.0f / (1.0f + __expf(-opacity[i]));
-    const float smax = __expf(fmaxf(scale[3 * (int64_t)i], fmaxf(scale[3 * (int64_t)i + 1], scale[3 * (int64_t)i + 2])));
+    const float lo = opacity[i], s0 = scale[3 * (int64_t)i], s1 = scale[3 * (int64_t)i + 1], s2 = scale[3 * (int64_t)i + 2];
+    // a splat with a non-finite opacity or scale is culled by every forward and would otherwise be KEEP for ever (NaN fails `<`,
+    // fmaxf drops a NaN scale, an infinite one never gathers statistics): it goes, whatever the limits and the cap
+    if (!(isfinite(lo) && isfinite(s0) && isfinite(s1) && isfinite(s2))) return DVS_DENSIFY_PRUNE;
+    const float op = 1.0f / (1.0f + __expf(-lo));
+    const float smax = __expf(fmaxf(s0, fmaxf(s1, s2)));
     if (op < p.min_opacity) return DVS_DENSIFY_PRUNE;
     if (p.max_world_scale > 0.f && smax > p.max_world_scale) return DVS_DENSIFY_PRUNE;
     if (p.max_screen_radius > 0 && max_radii[i] > p.max_screen_radius) return DVS_DENSIFY_PRUNE;

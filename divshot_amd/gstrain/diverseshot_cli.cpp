@@ -36,7 +36,10 @@ static std::map<std::string, std::string> g_opts = {
     {"resolutionSchedule", "0"}, {"numDownscales", "2"},
     // extension of this build: compact formats every save writes beside the full PLY: compressed | splat | compressed,splat
     // (<outputPath>_<it>.compressed.ply / .splat); empty = none, unless --outputPath itself ends in .compressed.ply / .splat
-    {"exportFormat", ""}};
+    {"exportFormat", ""},
+    // the config fields pruneScale3d / pruneScale2d (the reference's CLI has no flag for them): after the first opacity reset a refinement
+    // also prunes splats larger than this fraction of the scene extent / whose screen radius exceeds this fraction of the image size
+    {"pruneScale3d", "0.1"}, {"pruneScale2d", "0.15"}};
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
 
@@ -100,6 +103,8 @@ int main(int argc, const char* argv[]) {
     train_config.useAbsGrad = as_bool(g_opts["absgrad"]);
     train_config.pruneInterval = atoi(g_opts["pruneEvery"].c_str());
     train_config.pruneStrategy = atoi(g_opts["pruneStrategy"].c_str());
+    train_config.pruneScale3d = (float)atof(g_opts["pruneScale3d"].c_str());
+    train_config.pruneScale2d = (float)atof(g_opts["pruneScale2d"].c_str());
     train_config.mipAntiliased = as_bool(g_opts["mipAntiliased"]);
     train_config.maxImageHeight = atoi(g_opts["maxImageHeight"].c_str());
     train_config.maxImageWidth = atoi(g_opts["maxImageWidth"].c_str());

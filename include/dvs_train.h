@@ -123,7 +123,10 @@ int dvs_adam_step_groups(void* stream, const dvs_adam_group* groups, int n_group
  *   dvs_densify_accumulate after every backward: for visible splats  grad_accum += |g| (g = abs-grad of the 2D mean in NDC units:
  *                          pixel-unit gradient x 0.5*(W,H)),  denom += 1,  max_radii = max(max_radii, radius).
  *   dvs_densify_plan       action per splat from avg = grad_accum/denom:   PRUNE  sigmoid(opacity) < min_opacity, or world/screen size
- *                          above the limits;  SPLIT  avg >= grad_threshold and max exp(scale) > scale_threshold (replaced by 2
+ *                          above the limits (max exp(scale) > max_world_scale, max_radii > max_screen_radius, both strict; a splat that
+ *                          was never visible has max_radii 0 and stays), or an opacity or scale that is NaN or +-inf (no forward
+ *                          renders such a splat, so nothing else would ever remove it) — every prune rule is decided before any
+ *                          growth, whatever avg;  SPLIT  avg >= grad_threshold and max exp(scale) > scale_threshold (replaced by 2
  *                          samples, scale / 1.6);  CLONE  avg >= grad_threshold otherwise (kept + 1 copy);  KEEP.
  *                          Writes action[n], the exclusive scan of the output counts offsets[n] and the new count (device + pinned host
  *                          copy is the caller's business). Growth is cut off deterministically (by splat index) at cap_max:

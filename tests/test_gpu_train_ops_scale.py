@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 from util import gauss_window, conv_same, relocation_np, rel_close
+from densify_ref import capped as _capped_want      # the documented cap, restated once (tests/densify_ref.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -157,16 +158,6 @@ def test_densify_plan_apply_across_scan_chunks(gpu_device, n, tiled):
     assert np.array_equal(offs, _excl_cumsum(cnt)) and new_n == int(cnt.sum())
     for mode in (0, 1):
         _check_apply(A, act, offs, new_n, d.apply(prm, mode, new_n), mode)
-
-
-def _capped_want(act0, cap):
-    """the documented cap: the first max(0, cap - S) growth candidates in splat order keep CLONE / SPLIT, the rest become KEEP"""
-    S = int((act0 != PRUNE).sum())
-    grow = np.nonzero((act0 == CLONE) | (act0 == SPLIT))[0]
-    budget = len(grow) if cap <= 0 else min(len(grow), max(cap - S, 0))
-    want = act0.copy()
-    want[grow[budget:]] = KEEP
-    return want, S, len(grow)
 
 
 def test_densify_cap_max(gpu_device):

@@ -1,6 +1,6 @@
 """`train_step` at step level with the options the reference CLI turns on by default, and the other host flags of the step: progressive
 SH (--progressTrain 1), 8-bit training views (--packLevel 1), --useMask, --mipAntiliased, the opacity reset inside the step, the light
-prune, and ADC on the statistic of --absgrad 0. The kernel-level suites pin the ops; these pin how gstrain.cpp wires them: on which step
+prune, ADC on the statistic of --absgrad 0, and the ADC refinement after an opacity reset (both size limits on). The kernel-level suites pin the ops; these pin how gstrain.cpp wires them: on which step
 they run, with which arguments, and what state they leave for the next Adam step.
 
 CPU part (not marked gpu): the restatement's own pieces (pack formula, mask, degree schedule), and for every GPU case below
@@ -38,6 +38,7 @@ CASES = {
     "reset": dict(n=2000, W=64, H=64, cams=4, sh=1, seed=34, every=6),
     "prune": dict(n=1500, W=256, H=256, cams=4, sh=2, seed=35, K=10, more=2),      # n is not a multiple of 64: the last shN tile is partial
     "adc": dict(n=3000, W=96, H=48, cams=4, sh=1, seed=12, K=10),                # clearly non-square
+    "adc_limits": dict(n=3000, W=96, H=48, cams=4, sh=1, seed=12, K=10, every=4),  # resets at 4 and 8, ONE refinement at 10 > 4
 }
 BASE = ["--ssim", "0", "--packLevel", "0", "--densifyStrategy", "0", "--progressTrain", "0", "--absgrad", "1", "--warmupLength", "100000"]
 
@@ -383,6 +384,45 @@ def test_adc_mean2d_case_discriminates():
     assert (norm_first >= avg * r.denom * (1 - 1e-12)).all()          # W > H: scaling both components by W/2 can only be larger
 
 
+def _adc_limits(r, W):
+    """the flags of the post-reset refinement case, from the restated state after its ten steps: growGrad2d at the median of the
+    abs-grad statistic, pruneScale3d at the 0.9 quantile of max exp(scale) / extent, pruneScale2d so that the radius limit is the 0.97
+    quantile of max_radii (in the middle between two pixels) -> (grow, pruneScale3d, pruneScale2d, max_world_scale, max_screen_radius),
+    the last two as gstrain.cpp densify() computes them in float32 from the flags"""
+    f = np.float32
+    avg = r.grad_accum / np.maximum(r.denom, 1)
+    grow = float(f(np.median(avg[r.denom > 0])))
+    ps3 = f(np.quantile(np.exp(r.P["scale"].max(1)), 0.9) / r.extent)
+    ps2 = f((int(np.quantile(r.max_radii, 0.97)) + 0.5) / W)
+    return grow, float(ps3), float(ps2), float(ps3 * f(r.extent)), max(1, int(ps2 * f(W)))
+
+
+def test_adc_after_reset_case_discriminates():
+    """measured (oracle targets, 96x48, opacity resets at 4 and 8, the refinement at 10): the limits are 0.677 x extent = 0.372 and 14
+    pixels; with them 336 splats are pruned instead of 6, 90.7 % of the decisions have a 5 % margin under both rules, and on those 239
+    splats change action against the limits-off rule: 126 that would have split and 113 that would have been kept; 183 by the world
+    limit alone, 17 by the screen limit alone, 39 by both — the GPU test sees either limit being ignored, or checked after the growth."""
+    c, spec, cams = _case("adc_limits")
+    tg = _oracle_targets(spec, cams, c["sh"])
+    init = _start_model(spec, c["seed"])
+    r = _r64(cams, tg, init, c["sh"], c["K"], c["K"], reset_alpha_every=c["every"])
+    grow, ps3, ps2, mws, lim = _adc_limits(r, c["W"])
+    off, m_off = r.adc_actions(grow)
+    on, m_on = r.adc_actions(grow, max_world_scale=mws, max_screen_radius=lim)
+    legacy, m_legacy = r.adc_actions(grow, 0.005, "absgrad")
+    assert np.array_equal(off, legacy) and np.array_equal(m_off, m_legacy)           # the defaults are the rule before any reset
+    firm = (m_on > 0.05) & (m_off > 0.05)
+    changed = (on != off) & firm
+    world, screen = np.exp(r.P["scale"].max(1)) > mws, r.max_radii > lim
+    counts = dict(firm=float(firm.mean()), changed=int(changed.sum()), were_split=int((changed & (off == 2)).sum()),
+                  were_kept=int((changed & (off == 0)).sum()), world_only=int((changed & world & ~screen).sum()),
+                  screen_only=int((changed & screen & ~world).sum()))
+    print(grow, ps3, ps2, mws, lim, np.bincount(off, minlength=4), np.bincount(on, minlength=4), counts)
+    assert (on[changed] == 3).all() and (m_on > 0.05).mean() > 0.85
+    assert min(counts["were_split"], counts["were_kept"], counts["world_only"], counts["screen_only"]) >= 5, counts
+    assert lim >= 10 and (r.max_radii[r.denom == 0] == 0).all()
+
+
 # ---- the product ------------------------------------------------------------------------------------------------------------------------
 def _src(c):
     return f"synthetic:N={c['n']},W={c['W']},H={c['H']},cams={c['cams']},sh={c['sh']},seed={c['seed']}"
@@ -626,4 +666,41 @@ def test_plugin_adc_without_absgrad_uses_the_scaled_norm(tmp_path):
                   differ_on_firm=int((act != want)[firm].sum()))
     _dump("adc_mean2d", report)
     assert firm.mean() > 0.9 and min(np.bincount(want, minlength=4)[[0, 2]]) > 0.2 * n, report
+    assert np.array_equal(act[firm], want[firm]), (np.flatnonzero(act[firm] != want[firm])[:10], report)
+
+
+@pytest.mark.gpu
+def test_plugin_adc_after_an_opacity_reset_prunes_by_both_limits(tmp_path):
+    """--resetAlphaEvery 4, 96x48: ten steps with opacity resets at 4 and 8 ending in ONE refinement at 10 > resetAlphaEvery, the first
+    kind of refinement that also prunes by world size (--pruneScale3d x extent) and screen radius (--pruneScale2d x the longer image
+    side), both set from the restated state so that they bite (test_adc_after_reset_case_discriminates: some 240 splats change action).
+    The actions decoded from the saved model equal adc_actions(max_world_scale, max_screen_radius) wherever the decision has a 5 %
+    margin, and the logged count is the file's."""
+    c, spec, cams = _case("adc_limits")
+    K, n = c["K"], c["n"]
+    init = _start_model(spec, c["seed"])
+    tg = _hip_targets(spec, cams, c["sh"])
+    r64 = _r64(cams, tg, init, c["sh"], K, K, reset_alpha_every=c["every"])
+    grow, ps3, ps2, mws, lim = _adc_limits(r64, c["W"])
+    flags = _flags(warmupLength=5, refineEvery=10, refineStopIter=1000, resetAlphaEvery=c["every"], growGrad2d="%.9g" % grow,
+                   pruneScale3d="%.9g" % ps3, pruneScale2d="%.9g" % ps2)
+    out = str(tmp_path / "m" / "it")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    _write_ply(out + "_0.ply", init)
+    p = _run(["--inputPath", _src(c), "--maxIteration", str(K), "--outputPath", out, "--load_itr", "0"] + flags, timeout=600)
+    assert "(resumed)" in p.stderr
+    m = re.findall(r"densify @(\d+): (\d+) -> (\d+) splats", p.stderr)
+    got = _read_ply(out + f"_{K}.ply")
+    assert m == [("10", str(n), str(got["pos"].shape[0]))], (m, got["pos"].shape, p.stderr[-1500:])
+    want, margin = r64.adc_actions(grow, max_world_scale=mws, max_screen_radius=lim)
+    off, m_off = r64.adc_actions(grow)
+    firm = margin > 0.05
+    act = _decode_actions({k: r64.P[k].astype(np.float32) for k in KEYS}, got)
+    changed = (want != off) & firm & (m_off > 0.05)
+    report = dict(grow=grow, pruneScale3d=ps3, pruneScale2d=ps2, max_world_scale=mws, max_screen_radius=lim, firm=float(firm.mean()),
+                  want=np.bincount(want, minlength=4).tolist(), got=np.bincount(act, minlength=4).tolist(),
+                  limits_off=np.bincount(off, minlength=4).tolist(), changed_by_the_limits=int(changed.sum()),
+                  differ_on_firm=int((act != want)[firm].sum()))
+    _dump("adc_after_reset", report)
+    assert firm.mean() > 0.85 and changed.sum() >= 5 and min(np.bincount(want, minlength=4)[[0, 2, 3]]) > 0.05 * n, report
     assert np.array_equal(act[firm], want[firm]), (np.flatnonzero(act[firm] != want[firm])[:10], report)

@@ -247,10 +247,14 @@ class TrainStepRef:
         self.grad_accum, self.denom, self.max_radii = (np.zeros(int(keep.sum()), a.dtype) for a in (self.grad_accum, self.denom, self.max_radii))
         self.grad_accum_mean2d = np.zeros(int(keep.sum()), self.dt)
 
-    # ---- ADC refinement decision of gstrain.cpp densify() / densify.hip d_action (before any opacity reset) --------------------------
-    def adc_actions(self, grow_grad2d, min_opacity=0.005, stat="absgrad"):
+    # ---- ADC refinement decision of gstrain.cpp densify() / densify.hip d_action --------------------------------------------------------
+    def adc_actions(self, grow_grad2d, min_opacity=0.005, stat="absgrad", max_world_scale=0.0, max_screen_radius=0):
         """0 keep, 1 clone, 2 split, 3 prune — and the margin of each decision (relative distance to its nearest threshold).
-        stat: "absgrad" (--absgrad 1) or "mean2d" (--absgrad 0: hypot(gx W/2, gy H/2) of the signed dL/dmean2D)."""
+        stat: "absgrad" (--absgrad 1) or "mean2d" (--absgrad 0: hypot(gx W/2, gy H/2) of the signed dL/dmean2D).
+        max_world_scale / max_screen_radius: the two limits a refinement after the first opacity reset also prunes by (densify():
+        pruneScale3d x extent, and max(1, int(pruneScale2d x max(W, H))) pixels below refineScale2dStopIter), both strict, both decided
+        before any growth; 0 = off, the rule before any reset. The radius is an integer, but the plugin's and the restatement's may differ
+        by a pixel: its margin is the distance to limit + 1/2, so that the radii limit and limit + 1 are never firm at a limit >= 10."""
         accum = {"absgrad": self.grad_accum, "mean2d": self.grad_accum_mean2d}[stat]
         op = 1.0 / (1.0 + np.exp(-self.P["opacity"].astype(np.float64)))
         smax = np.exp(self.P["scale"].max(1).astype(np.float64))
@@ -259,4 +263,10 @@ class TrainStepRef:
         act = np.where(op < min_opacity, 3, np.where(avg >= grow_grad2d, np.where(smax > thr_s, 2, 1), 0))
         margin = np.minimum(np.abs(op - min_opacity) / min_opacity, np.abs(avg - grow_grad2d) / grow_grad2d)
         margin = np.where(avg >= grow_grad2d, np.minimum(margin, np.abs(smax - thr_s) / thr_s), margin)
+        if max_world_scale > 0:
+            act = np.where(smax > max_world_scale, 3, act)
+            margin = np.minimum(margin, np.abs(smax - max_world_scale) / max_world_scale)
+        if max_screen_radius > 0:
+            act = np.where(self.max_radii > max_screen_radius, 3, act)
+            margin = np.minimum(margin, np.abs(self.max_radii - (max_screen_radius + 0.5)) / (max_screen_radius + 0.5))
         return act, margin
