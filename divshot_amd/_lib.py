@@ -139,6 +139,7 @@ _PROTOS = {
     "dvs_synth_camera": (C.c_int, [C.POINTER(SceneSpec), C.c_int, C.POINTER(Camera)]),
     "dvs_synth_target": (C.c_int, [C.POINTER(SceneSpec), C.c_int, C.c_void_p]),
     "dvs_make_camera": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int, C.POINTER(Camera)]),
+    "dvs_make_camera_intrinsics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(Camera)]),
     "dvs_camera_downscale": (C.c_int, [C.POINTER(Camera), C.c_int, C.POINTER(Camera)]),
     "dvs_l1_loss_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "dvs_l1_loss_grad_w": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_void_p, C.c_void_p]),
@@ -178,7 +179,14 @@ _EXPORT_PROTOS = {
                                       C.c_void_p, C.c_void_p]),
     "dvs_pack_splat32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
-for _name, (_res, _args) in list(_PROTOS.items()) + list(_EXPORT_PROTOS.items()):
+# include/dvs_init.h: splat initialisation from a sparse point cloud
+_INIT_PROTOS = {
+    "dvs_knn_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "dvs_knn_mean_dist2": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_knn_mean_dist2_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_init_from_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+for _name, (_res, _args) in list(_PROTOS.items()) + list(_EXPORT_PROTOS.items()) + list(_INIT_PROTOS.items()):
     _f = getattr(lib, _name)          # AttributeError here = the .so does not export a declared symbol
     _f.restype = _res
     _f.argtypes = _args

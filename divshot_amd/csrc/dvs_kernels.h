@@ -149,3 +149,9 @@ hipError_t dvs_launch_render_bwd_tr(hipStream_t st, int W, int H, int tiles_x, i
 hipError_t dvs_launch_render_bwd_blocks(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, const uint32_t* ranges,
                                         const uint32_t* sorted_splat, const float* splat2d, const float* bgs /*[n_views][3]*/, const float* final_T,
                                         const uint32_t* n_contrib, const float* dL_dout, float* grad_rows, int absgrad, int grad_mode);
+
+// pack.hip — stages (a) - (c) of the export packer for other users inside the library (knn.hip): the model's box, 30-bit Morton keys
+// over it, the stable segmented sort. *sorted = [n] model indices in Morton order (equal keys in index order), *bounds (nullable) =
+// {min xyz, max xyz}; both live inside `scratch` (dvs_morton_scratch_bytes(n) bytes, 256-byte aligned parts, no initialisation).
+size_t dvs_morton_scratch_bytes(int n);
+hipError_t dvs_launch_morton_order(hipStream_t st, int n, const float* pos, void* scratch, const uint32_t** sorted, const float** bounds);

@@ -222,12 +222,8 @@ bool off16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
 
 extern "C" size_t dvs_pack_scratch_bytes(int n) { return n > 0 ? pack_layout(n).total : 0; }
 
-extern "C" int dvs_pack_compressed(void* stream, int n, const float* pos, const float* sh0, const float* opacity, const float* scale,
-                                   const float* rot, void* scratch, float* chunks, uint32_t* verts, uint32_t* order) {
-    if (n <= 0 || !pos || !sh0 || !opacity || !scale || !rot || !scratch || !chunks || !verts) return DVS_ERR_INVALID;
-    if (off16(pos) || off16(sh0) || off16(opacity) || off16(scale) || off16(rot) || off16(scratch) || off16(chunks) || off16(verts) || off16(order))
-        return DVS_ERR_INVALID;
-    hipStream_t st = (hipStream_t)stream;
+// (a) - (c) for any caller inside the library (dvs_kernels.h): the model indices in Morton order, the model's box
+hipError_t dvs_launch_morton_order(hipStream_t st, int n, const float* pos, void* scratch, const uint32_t** sorted, const float** bounds_out) {
     const PackScratch L = pack_layout(n);
     char* const base = (char*)scratch;
     float* const slots = (float*)(base + L.slots);
@@ -240,16 +236,31 @@ extern "C" int dvs_pack_compressed(void* stream, int n, const float* pos, const 
     hipLaunchKernelGGL(k_pack_bounds, dim3(bblocks), dim3(PK_BLOCK), 0, st, n, pos, slots);
     hipLaunchKernelGGL(k_pack_bounds_final, dim3(1), dim3(PK_BLOCK), 0, st, (int)bblocks, (const float*)slots, bounds);
     hipLaunchKernelGGL(k_pack_morton, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, pos, (const float*)bounds, key[0], val[0]);
-    if (hipGetLastError() != hipSuccess) return DVS_ERR_HIP;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
     // one segment [0, n); ballot ranking (rank_atomic = 0): correct by construction, no probe of the device needed
     const uint32_t part = dvs_fe_part_for((uint64_t)n);
     int cur = 0;
-    if (dvs_launch_seg_init(st, n, 1, 0, seg) != hipSuccess) return DVS_ERR_HIP;
-    if (dvs_launch_seg_sort(st, 1, key[0], val[0], key[1], val[1], seg, 0, 30, (uint64_t)n, part, (uint32_t)((uint32_t)n / part) + 3u,
-                            (uint32_t*)(base + L.hist), (uint32_t*)(base + L.totals), 0u, &cur, nullptr, 1, 0, 0) != hipSuccess)
-        return DVS_ERR_HIP;
+    if ((e = dvs_launch_seg_init(st, n, 1, 0, seg)) != hipSuccess) return e;
+    if ((e = dvs_launch_seg_sort(st, 1, key[0], val[0], key[1], val[1], seg, 0, 30, (uint64_t)n, part, (uint32_t)((uint32_t)n / part) + 3u,
+                                 (uint32_t*)(base + L.hist), (uint32_t*)(base + L.totals), 0u, &cur, nullptr, 1, 0, 0)) != hipSuccess)
+        return e;
+    *sorted = val[cur];
+    if (bounds_out) *bounds_out = bounds;
+    return hipSuccess;
+}
+size_t dvs_morton_scratch_bytes(int n) { return n > 0 ? pack_layout(n).total : 0; }
+
+extern "C" int dvs_pack_compressed(void* stream, int n, const float* pos, const float* sh0, const float* opacity, const float* scale,
+                                   const float* rot, void* scratch, float* chunks, uint32_t* verts, uint32_t* order) {
+    if (n <= 0 || !pos || !sh0 || !opacity || !scale || !rot || !scratch || !chunks || !verts) return DVS_ERR_INVALID;
+    if (off16(pos) || off16(sh0) || off16(opacity) || off16(scale) || off16(rot) || off16(scratch) || off16(chunks) || off16(verts) || off16(order))
+        return DVS_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t* sorted = nullptr;
+    if (dvs_launch_morton_order(st, n, pos, scratch, &sorted, nullptr) != hipSuccess) return DVS_ERR_HIP;
     const unsigned nchunks = (unsigned)(((int64_t)n + PK_CHUNK - 1) / PK_CHUNK);
-    hipLaunchKernelGGL(k_pack_chunks, dim3(nchunks), dim3(PK_BLOCK), 0, st, n, (const uint32_t*)val[cur], pos, sh0, opacity, scale, rot, chunks,
+    hipLaunchKernelGGL(k_pack_chunks, dim3(nchunks), dim3(PK_BLOCK), 0, st, n, sorted, pos, sh0, opacity, scale, rot, chunks,
                        (uint4*)verts, order);
     return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
 }

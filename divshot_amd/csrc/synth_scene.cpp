@@ -31,13 +31,8 @@ struct Pcg32 {
 
 extern "C" {
 
-int dvs_make_camera(const float* R, const float* t, float fov_x_deg, int width, int height, dvs_camera* c) {
-    if (!R || !t || !c || width <= 0 || height <= 0) return DVS_ERR_INVALID;
-    memset(c, 0, sizeof *c);
-    const double tanx = std::tan(0.5 * (double)fov_x_deg * 3.14159265358979323846 / 180.0);
-    const double tany = tanx * (double)height / (double)width;
-    c->tan_fovx = (float)tanx; c->tan_fovy = (float)tany;
-    c->focal_x = (float)(width / (2.0 * tanx)); c->focal_y = (float)(height / (2.0 * tany));
+// the camera of a pose and a pinhole given as tan(fov / 2) per axis and the principal point's offset from the image centre in NDC
+static void fill_camera(const float* R, const float* t, double tanx, double tany, double offx, double offy, int width, int height, dvs_camera* c) {
     c->width = width; c->height = height;
     // view[c*4+r]: out.r = sum_c view[c*4+r] * in.c   (world -> camera)
     for (int r = 0; r < 3; ++r) {
@@ -45,10 +40,11 @@ int dvs_make_camera(const float* R, const float* t, float fov_x_deg, int width, 
         c->view[3 * 4 + r] = t[r];
     }
     c->view[15] = 1.f;
-    // pinhole clip matrix P (camera -> clip): x' = x / tanx, y' = y / tany, w' = z  (only x, y, w are used)
+    // pinhole clip matrix P (camera -> clip): x' = x / tanx + offx z, y' = y / tany + offy z, w' = z  (only x, y, w are used)
     const double zn = 0.01, zf = 100.0;
     double P[16] = {0};  // P[c*4+r]
     P[0 * 4 + 0] = 1.0 / tanx; P[1 * 4 + 1] = 1.0 / tany;
+    P[2 * 4 + 0] = offx; P[2 * 4 + 1] = offy;
     P[2 * 4 + 2] = zf / (zf - zn); P[3 * 4 + 2] = -(zf * zn) / (zf - zn); P[2 * 4 + 3] = 1.0;
     // proj = P * view
     for (int cc = 0; cc < 4; ++cc)
@@ -59,6 +55,30 @@ int dvs_make_camera(const float* R, const float* t, float fov_x_deg, int width, 
         }
     // camera centre = -R^T t
     for (int k = 0; k < 3; ++k) c->campos[k] = -(R[0 * 3 + k] * t[0] + R[1 * 3 + k] * t[1] + R[2 * 3 + k] * t[2]);
+}
+
+int dvs_make_camera(const float* R, const float* t, float fov_x_deg, int width, int height, dvs_camera* c) {
+    if (!R || !t || !c || width <= 0 || height <= 0) return DVS_ERR_INVALID;
+    memset(c, 0, sizeof *c);
+    const double tanx = std::tan(0.5 * (double)fov_x_deg * 3.14159265358979323846 / 180.0);
+    const double tany = tanx * (double)height / (double)width;
+    c->tan_fovx = (float)tanx; c->tan_fovy = (float)tany;
+    c->focal_x = (float)(width / (2.0 * tanx)); c->focal_y = (float)(height / (2.0 * tany));
+    fill_camera(R, t, tanx, tany, 0.0, 0.0, width, height, c);
+    return DVS_OK;
+}
+
+int dvs_make_camera_intrinsics(const float* R, const float* t, double fx, double fy, double cx, double cy, int width, int height, dvs_camera* c) {
+    if (!R || !t || !c || width <= 0 || height <= 0 || !(fx > 0.0) || !(fy > 0.0) || !std::isfinite(fx) || !std::isfinite(fy) ||
+        !std::isfinite(cx) || !std::isfinite(cy))
+        return DVS_ERR_INVALID;
+    memset(c, 0, sizeof *c);
+    const double tanx = (double)width / (2.0 * fx), tany = (double)height / (2.0 * fy);
+    c->tan_fovx = (float)tanx; c->tan_fovy = (float)tany;
+    c->focal_x = (float)fx; c->focal_y = (float)fy;
+    // a pixel's centre is at i + 0.5 in COLMAP and at i here: (X, Y, Z) must land at fx X / Z + cx - 0.5 = ((ndc + 1) W - 1) / 2,
+    // i.e. ndc = (2 fx / W) X / Z + (2 cx / W - 1)
+    fill_camera(R, t, tanx, tany, 2.0 * cx / (double)width - 1.0, 2.0 * cy / (double)height - 1.0, width, height, c);
     return DVS_OK;
 }
 

@@ -1,0 +1,53 @@
+// dataset_io.hpp — reader of the capture format the lineage trains from: a COLMAP sparse model (cameras / images / points3D, binary or
+// text) plus undistorted images. Host only, no GPU dependency; every malformed input is a `false` with a message, never a crash and
+// never an allocation sized by an unchecked count field.
+//   <path>/sparse/0/ (tried first) or <path>/sparse/: cameras, images, points3D as .bin (preferred) or .txt
+//   <path>/images/<name>: binary PPM (P6, maxval 255); a name whose file is absent is retried with its extension replaced by .ppm
+//   <path>/masks/<stem>.pgm (P5, maxval 255): > 127 is trainable; a missing file means all ones
+// Camera models: SIMPLE_PINHOLE and PINHOLE only — anything else has to be undistorted first (the lineage's own requirement).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+namespace gsdata {
+
+struct Camera {
+    uint32_t id = 0;
+    int model = 0;                       // COLMAP model id: 0 SIMPLE_PINHOLE, 1 PINHOLE
+    uint64_t width = 0, height = 0;
+    double fx = 0, fy = 0, cx = 0, cy = 0;
+};
+struct Image {
+    uint32_t id = 0, camera_id = 0;
+    double q[4] = {1, 0, 0, 0};          // qvec (w, x, y, z), world -> camera
+    double t[3] = {0, 0, 0};             // tvec, world -> camera
+    std::string name;
+    size_t camera = 0;                   // index into Dataset::cameras
+};
+struct Dataset {
+    std::string root, sparse_dir;
+    bool binary = false;
+    std::vector<Camera> cameras;
+    std::vector<Image> images;           // ordered by name (a hold-out by index splits as the lineage does)
+    std::vector<float> xyz;              // [points][3]
+    std::vector<uint8_t> rgb;            // [points][3]
+    size_t dropped = 0;                  // points with a non-finite coordinate, not in xyz / rgb
+};
+
+const char* model_name(int model);      // "SIMPLE_PINHOLE", "PINHOLE", ... ("?" outside COLMAP's list)
+
+// the sparse model under `path`; images and masks are read one by one with the calls below
+bool read_dataset(const std::string& path, Dataset* out, std::string* err);
+// image `index` as interleaved 8-bit RGB [H][W][3]; its size must equal its camera's
+bool read_image(const Dataset& d, size_t index, std::vector<uint8_t>* rgb, std::string* err);
+// its mask as [H][W] bytes in {0, 1}; all ones when <root>/masks/<stem>.pgm does not exist
+bool read_mask(const Dataset& d, size_t index, std::vector<uint8_t>* mask, std::string* err);
+// world -> camera rotation of an image, row-major [9], from the normalised qvec
+void rotation_of(const Image& im, float R[9]);
+
+// binary PNM (P6: channels = 3, P5: channels = 1; maxval 255)
+bool read_pnm(const std::string& file, int channels, int* width, int* height, std::vector<uint8_t>* pixels, std::string* err);
+
+}  // namespace gsdata

@@ -12,9 +12,10 @@
 // with ONE RCCL all-reduce over xGMI (include/dvs_comm.h), the densification statistics likewise before each refinement, and the
 // optimizer / densifier run replicated and deterministic so that the replicas stay bit-identical.
 // With resolutionSchedule > 0 the first steps train coarse to fine: on box-filtered views of 1/2^k the size, through level cameras.
-// Out of scope: COLMAP / image ingestion, mesh export, the 2DGS model type. load_train_data accepts a
-// synthetic-scene spec instead of a dataset path. Every GaussianTrainConfig field the hosts set is either honoured
-// or named in the one-time "ignored" line of report_config().
+// load_train_data accepts a capture directory (a COLMAP sparse model plus undistorted PPM images: dataset_io.hpp; the splats start from
+// the sparse points, include/dvs_init.h) or a synthetic-scene spec. Out of scope: JPEG / PNG
+// decoding, distorted camera models, mesh export, the 2DGS model type. Every GaussianTrainConfig field the hosts set is either
+// honoured or named in the one-time "ignored" line of report_config().
 #include <hip/hip_runtime.h>
 #include <chrono>
 #include <cstdarg>
@@ -23,6 +24,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <filesystem>
+#include <functional>
 #include <map>
 #include <stdexcept>
 #include "../../include/gaussian_trainer_scene.hpp"
@@ -31,7 +33,9 @@
 #include "../../include/dvs_train.h"
 #include "../../include/dvs_comm.h"
 #include "../../include/dvs_export.h"
+#include "../../include/dvs_init.h"
 #include "ply_io.hpp"
+#include "dataset_io.hpp"
 
 namespace {
 const int kWidth[6] = {3, 3, 45, 1, 3, 4};          // pos sh0 shN opacity scale rot
@@ -342,7 +346,14 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         }
         host_valid = true;
     }
+    // what the two loaders share: the context and every per-step buffer (W, H, sh_max set by the caller) ...
+    void create_context(int count, int capacity, const std::vector<float> init[6]);
+    // ... and, once cams / the targets / the masks are in place: split, levels, extent, resume or the loader's fresh initialisation,
+    // upload, report_config, the loader's own verbose line (told whether the run resumed), exchange set-up
+    void finish_load(const std::function<void(std::vector<float> (&)[6])>& fresh_init, const char* fresh_name,
+                     const std::function<void(bool)>& describe);
     bool load_synthetic(const std::string& spec_str);
+    bool load_dataset(const std::string& path);
 };
 
 // the fp32 target image of camera ci on the device (expands the 8-bit copy when packLevel has PackF32ToU8)
@@ -570,24 +581,9 @@ bool GaussianTrainerScene::Impl::load_synthetic(const std::string& spec_str) {
     for (int g = 0; g < 6; ++g) gt[g].resize((size_t)spec.n * kWidth[g]);
     DVS_OR_THROW(dvs_synth_splats(&spec, gt[0].data(), gt[1].data(), gt[2].data(), gt[3].data(), gt[4].data(), gt[5].data()));
     const int capacity = std::max(spec.n, cfg.capMax);          // --capMax is the array capacity (gs_train.cpp:89); 1.9 KB of HBM per splat
-    vpi = cfg.viewsPerIter;
-    if (const char* e = getenv("DVS_VIEWS_PER_ITER")) vpi = atoi(e);
-    vpi = std::max(1, std::min(vpi, 16));
-    if (const char* e = getenv("DVS_VIEWS_MODE")) sequential_views = std::string(e) == "sequential";
-    if (vpi > 1 && rank == 0)
-        logf_("config: %d views per trainStep and GPU, %s", vpi, sequential_views ? "one pass per view, gradients accumulated (DVS_VIEWS_MODE=sequential)"
-                                                                                : "ONE multi-view pass (dvs_raster_forward_views / _backward_views), gradients summed");
-    ctx = dvs_create_views(device, (size_t)capacity, W, H, sequential_views ? 1 : vpi);
-    if (!ctx) throw std::runtime_error(std::string("dvs_create_views: ") + dvs_last_error());
     // ground-truth views: render the generating scene once per camera
-    alloc_params(spec.n, capacity, gt);
+    create_context(spec.n, capacity, gt);
     const size_t img = 3 * (size_t)W * H;
-    HIP_OR_THROW(hipMalloc((void**)&d_out, (size_t)vpi * img * sizeof(float)));
-    HIP_OR_THROW(hipMalloc((void**)&d_dL, (size_t)vpi * img * sizeof(float)));
-    HIP_OR_THROW(hipMalloc((void**)&d_loss, 2 * DVS_SSIM_SLOTS * sizeof(float)));
-    HIP_OR_THROW(hipMemset(d_loss, 0, 2 * DVS_SSIM_SLOTS * sizeof(float)));
-    if (cfg.ssimWeight > 0.f)
-        for (int k = 0; k < 3; ++k) HIP_OR_THROW(hipMalloc((void**)&d_ssim_maps[k], img * sizeof(float)));
     dvs_opts opts{sh_max, cfg.mipAntiliased ? 1 : 0, 0, 0, DVS_SHN_TILED};
     const dvs_splats sp = splats();
     for (int c = 0; c < spec.n_cams; ++c) {
@@ -619,6 +615,47 @@ bool GaussianTrainerScene::Impl::load_synthetic(const std::string& spec_str) {
             d_masks.push_back(dm);
         }
     }
+    // trainable initialisation = perturbed ground truth (or the checkpoint when --load_itr is given)
+    finish_load([&](std::vector<float> (&init)[6]) {
+        Lcg r(spec.seed + 17);
+        for (int g = 0; g < 6; ++g) init[g] = gt[g];
+        for (int i = 0; i < spec.n; ++i) {
+            const float z = gt[0][3 * i + 2];
+            for (int k = 0; k < 3; ++k) init[P_POS][3 * i + k] += 0.002f * z * r.sym();
+            for (int k = 0; k < 3; ++k) init[P_SH0][3 * i + k] += 0.5f * r.sym();
+            for (int k = 0; k < 45; ++k) init[P_SHN][45 * (size_t)i + k] = 0.f;
+            init[P_OPA][i] -= 1.0f;
+            for (int k = 0; k < 3; ++k) init[P_SCALE][3 * i + k] += 0.15f * r.sym();
+        }
+    }, "synthetic", [&](bool resumed) {
+        if (cfg.verbose) logf_("synthetic scene: %d splats, %d cameras @ %dx%d, SH degree %d%s", spec.n, spec.n_cams, W, H, sh_max, resumed ? " (resumed)" : "");
+    });
+    return true;
+}
+
+void GaussianTrainerScene::Impl::create_context(int count, int capacity, const std::vector<float> init[6]) {
+    vpi = cfg.viewsPerIter;
+    if (const char* e = getenv("DVS_VIEWS_PER_ITER")) vpi = atoi(e);
+    vpi = std::max(1, std::min(vpi, 16));
+    if (const char* e = getenv("DVS_VIEWS_MODE")) sequential_views = std::string(e) == "sequential";
+    if (vpi > 1 && rank == 0)
+        logf_("config: %d views per trainStep and GPU, %s", vpi, sequential_views ? "one pass per view, gradients accumulated (DVS_VIEWS_MODE=sequential)"
+                                                                                : "ONE multi-view pass (dvs_raster_forward_views / _backward_views), gradients summed");
+    ctx = dvs_create_views(device, (size_t)capacity, W, H, sequential_views ? 1 : vpi);
+    if (!ctx) throw std::runtime_error(std::string("dvs_create_views: ") + dvs_last_error());
+    alloc_params(count, capacity, init);
+    const size_t img = 3 * (size_t)W * H;
+    HIP_OR_THROW(hipMalloc((void**)&d_out, (size_t)vpi * img * sizeof(float)));
+    HIP_OR_THROW(hipMalloc((void**)&d_dL, (size_t)vpi * img * sizeof(float)));
+    HIP_OR_THROW(hipMalloc((void**)&d_loss, 2 * DVS_SSIM_SLOTS * sizeof(float)));
+    HIP_OR_THROW(hipMemset(d_loss, 0, 2 * DVS_SSIM_SLOTS * sizeof(float)));
+    if (cfg.ssimWeight > 0.f)
+        for (int k = 0; k < 3; ++k) HIP_OR_THROW(hipMalloc((void**)&d_ssim_maps[k], img * sizeof(float)));
+}
+
+void GaussianTrainerScene::Impl::finish_load(const std::function<void(std::vector<float> (&)[6])>& fresh_init, const char* fresh_name,
+                                             const std::function<void(bool)>& describe) {
+    const size_t img = 3 * (size_t)W * H;
     if (cfg.packLevel & PackF32ToU8) HIP_OR_THROW(hipMalloc((void**)&d_target_f32, img * sizeof(float)));
     HIP_OR_THROW(hipStreamSynchronize(stream));
     setup_split();
@@ -631,33 +668,155 @@ bool GaussianTrainerScene::Impl::load_synthetic(const std::string& spec_str) {
         for (auto& c : cams) { double d = 0; for (int k = 0; k < 3; ++k) d += (c.campos[k] - mean[k]) * (c.campos[k] - mean[k]); far = std::max(far, std::sqrt(d)); }
         extent = far > 1e-3 ? (float)(1.1 * far) : 5.0f;
     }
-    // trainable initialisation = perturbed ground truth (or the checkpoint when --load_itr is given)
     std::vector<float> init[6];
     bool resumed = false;
     if (loadItr >= 0) {
         std::string err;
         resumed = gsply::read_ply(model_file(loadItr), init[0], init[1], init[2], init[3], init[4], init[5], &err) &&
-                  !init[3].empty() && (int)init[3].size() <= cap;        // the count may differ from the spec after densification
+                  !init[3].empty() && (int)init[3].size() <= cap;        // the count may differ from the loader's after densification
         if (resumed) n = (int)init[3].size();
-        if (!resumed) logf_("could not resume from %s (%s): starting from the synthetic initialisation", model_file(loadItr).c_str(), err.c_str());
+        if (!resumed) logf_("could not resume from %s (%s): starting from the %s initialisation", model_file(loadItr).c_str(), err.c_str(), fresh_name);
         else step = loadItr;
     }
-    if (!resumed) {
-        Lcg r(spec.seed + 17);
-        for (int g = 0; g < 6; ++g) init[g] = gt[g];
-        for (int i = 0; i < spec.n; ++i) {
-            const float z = gt[0][3 * i + 2];
-            for (int k = 0; k < 3; ++k) init[P_POS][3 * i + k] += 0.002f * z * r.sym();
-            for (int k = 0; k < 3; ++k) init[P_SH0][3 * i + k] += 0.5f * r.sym();
-            for (int k = 0; k < 45; ++k) init[P_SHN][45 * (size_t)i + k] = 0.f;
-            init[P_OPA][i] -= 1.0f;
-            for (int k = 0; k < 3; ++k) init[P_SCALE][3 * i + k] += 0.15f * r.sym();
-        }
-    }
+    if (!resumed) fresh_init(init);
     for (int g = 0; g < 6; ++g) { upload(g, init[g]); init_host[g] = init[g]; }
     report_config();
-    if (cfg.verbose) logf_("synthetic scene: %d splats, %d cameras @ %dx%d, SH degree %d%s", spec.n, spec.n_cams, W, H, sh_max, resumed ? " (resumed)" : "");
+    describe(resumed);
     if (exchange_factorised()) setup_exchange();
+}
+
+// A capture directory: a COLMAP sparse model and undistorted PPM images (dataset_io.hpp). The views go up as bytes and are box-filtered
+// on the device when maxImageWidth / maxImageHeight ask for it; the splats start from the sparse points (include/dvs_init.h).
+bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
+    gsdata::Dataset ds;
+    std::string err;
+    if (!gsdata::read_dataset(path, &ds, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
+    const int n_pts = (int)std::min<size_t>(ds.xyz.size() / 3, (size_t)0x7FFFFFFF);
+    if (n_pts <= 0) {
+        logf_("load_train_data('%s'): the sparse model has no usable points (%zu dropped); initialisation without a point cloud is out of scope", path.c_str(), ds.dropped);
+        return false;
+    }
+    // the smallest factor of {1, 2, 4, 8} that fits each image into maxImageWidth x maxImageHeight; one size per run
+    const int max_w = cfg.maxImageWidth > 0 ? cfg.maxImageWidth : 0x7FFFFFFF, max_h = cfg.maxImageHeight > 0 ? cfg.maxImageHeight : 0x7FFFFFFF;
+    std::vector<int> factor(ds.images.size(), 1);
+    int W0 = 0, H0 = 0, model = -1;
+    bool one_model = true;
+    for (size_t i = 0; i < ds.images.size(); ++i) {
+        const gsdata::Camera& c = ds.cameras[ds.images[i].camera];
+        const int w = (int)c.width, h = (int)c.height;
+        int d = 1;
+        while (d <= 8 && (w / d > max_w || h / d > max_h)) d *= 2;
+        if (d > 8 || w / d <= 0 || h / d <= 0) {
+            logf_("load_train_data('%s'): image %s is %dx%d; even 1/8 of it does not fit maxImageWidth / maxImageHeight %dx%d", path.c_str(),
+                  ds.images[i].name.c_str(), w, h, cfg.maxImageWidth, cfg.maxImageHeight);
+            return false;
+        }
+        factor[i] = d;
+        if (i == 0) { W0 = w; H0 = h; W = w / d; H = h / d; model = c.model; }
+        else if (w / d != W || h / d != H) {
+            logf_("load_train_data('%s'): image %s ends up %dx%d but %s ends up %dx%d; this trainer takes one image size per run", path.c_str(),
+                  ds.images[i].name.c_str(), w / d, h / d, ds.images[0].name.c_str(), W, H);
+            return false;
+        }
+        one_model = one_model && c.model == model;
+    }
+    sh_max = 3;
+    const int capacity = std::max(n_pts, cfg.capMax);
+    std::vector<float> zero[6];
+    for (int g = 0; g < 6; ++g) zero[g].assign((size_t)n_pts * kWidth[g], 0.f);
+    create_context(n_pts, capacity, zero);
+    const bool u8 = (cfg.packLevel & PackF32ToU8) != 0;
+    const size_t P = (size_t)W * H, img = 3 * P;
+    std::vector<uint8_t> px, planar, mk;
+    std::vector<float> mkf;
+    for (size_t i = 0; i < ds.images.size(); ++i) {
+        const gsdata::Image& im = ds.images[i];
+        const gsdata::Camera& c = ds.cameras[im.camera];
+        const int w = (int)c.width, h = (int)c.height, d = factor[i];
+        const size_t p0 = (size_t)w * h;
+        if (!gsdata::read_image(ds, i, &px, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
+        planar.resize(3 * p0);                                  // the file is [H][W][3], the trainer's views are planar [3][H][W]
+        for (size_t q = 0; q < p0; ++q) for (int k = 0; k < 3; ++k) planar[(size_t)k * p0 + q] = px[3 * q + k];
+        // 1. the view as bytes; 2. box-filtered by the image's factor (rounded back to 8 bits when the views are kept as bytes)
+        uint8_t* full8 = nullptr;
+        HIP_OR_THROW(hipMalloc((void**)&full8, 3 * p0));
+        HIP_OR_THROW(hipMemcpy(full8, planar.data(), 3 * p0, hipMemcpyHostToDevice));
+        if (u8 && d == 1) {
+            d_targets_u8.push_back(full8); d_targets.push_back(nullptr);
+        } else {
+            float* t = nullptr;
+            HIP_OR_THROW(hipMalloc((void**)&t, img * sizeof(float)));
+            const dvs_downsample_view dv{full8, t};
+            DVS_OR_THROW(dvs_downsample_views(stream, &dv, 1, 3, w, h, d, 1));
+            if (u8) {
+                uint8_t* t8 = nullptr;
+                HIP_OR_THROW(hipMalloc((void**)&t8, img));
+                hipLaunchKernelGGL(k_pack_u8, dim3((unsigned)((img + 255) / 256)), dim3(256), 0, stream, t, t8, img);
+                d_targets_u8.push_back(t8); d_targets.push_back(nullptr);
+            } else {
+                d_targets.push_back(t);
+            }
+            HIP_OR_THROW(hipStreamSynchronize(stream));
+            (void)hipFree(full8);
+            if (u8) (void)hipFree(t);
+        }
+        if (cfg.useMask) {                                      // > 127 trains; a level mask keeps the box filter's fractional weights
+            if (!gsdata::read_mask(ds, i, &mk, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
+            mkf.assign(mk.begin(), mk.end());
+            float* m0 = nullptr;
+            HIP_OR_THROW(hipMalloc((void**)&m0, p0 * sizeof(float)));
+            HIP_OR_THROW(hipMemcpy(m0, mkf.data(), p0 * sizeof(float), hipMemcpyHostToDevice));
+            if (d > 1) {
+                float* md = nullptr;
+                HIP_OR_THROW(hipMalloc((void**)&md, P * sizeof(float)));
+                const dvs_downsample_view dv{m0, md};
+                DVS_OR_THROW(dvs_downsample_views(stream, &dv, 1, 1, w, h, d, 0));
+                HIP_OR_THROW(hipStreamSynchronize(stream));
+                (void)hipFree(m0);
+                m0 = md;
+            }
+            d_masks.push_back(m0);
+        }
+        float R[9];
+        gsdata::rotation_of(im, R);
+        const float t3[3] = {(float)im.t[0], (float)im.t[1], (float)im.t[2]};
+        dvs_camera cam, camd;
+        DVS_OR_THROW(dvs_make_camera_intrinsics(R, t3, c.fx, c.fy, c.cx, c.cy, w, h, &cam));
+        DVS_OR_THROW(dvs_camera_downscale(&cam, d, &camd));
+        cams.push_back(camd);
+    }
+    if (rank == 0) {
+        char lvl[64] = "";
+        if (factor[0] > 1) snprintf(lvl, sizeof lvl, " -> %dx%d (1/%d)", W, H, factor[0]);
+        logf_("dataset: %zu cameras (%s), %dx%d%s, %d points (%zu dropped)", ds.images.size(), one_model ? gsdata::model_name(model) : "mixed pinhole models",
+              W0, H0, lvl, n_pts, ds.dropped);
+    }
+    // 4. the points, 5. their 3-NN scales and the initial parameters, straight into the parameter arrays
+    {
+        uint8_t* d_rgb = nullptr; float* d_dist2 = nullptr; void* d_knn = nullptr;
+        HIP_OR_THROW(hipMalloc((void**)&d_rgb, (size_t)n_pts * 3 + 16));
+        HIP_OR_THROW(hipMalloc((void**)&d_dist2, (size_t)n_pts * sizeof(float) + 16));
+        HIP_OR_THROW(hipMalloc(&d_knn, dvs_knn_scratch_bytes(n_pts)));
+        HIP_OR_THROW(hipMemcpy(d_param[P_POS], ds.xyz.data(), (size_t)n_pts * 3 * sizeof(float), hipMemcpyHostToDevice));
+        HIP_OR_THROW(hipMemcpy(d_rgb, ds.rgb.data(), (size_t)n_pts * 3, hipMemcpyHostToDevice));
+        const auto t_init = std::chrono::steady_clock::now();
+        DVS_OR_THROW(dvs_knn_mean_dist2(stream, n_pts, d_param[P_POS], d_knn, d_dist2));
+        DVS_OR_THROW(dvs_init_from_points(stream, n_pts, d_param[P_POS], d_rgb, d_dist2, d_param[P_SH0], d_param[P_OPA], d_param[P_SCALE], d_param[P_ROT]));
+        HIP_OR_THROW(hipStreamSynchronize(stream));
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_init).count();
+        if (rank == 0) logf_("init: 3-NN scales for %d points: %.3f ms", n_pts, ms);
+        (void)hipFree(d_rgb); (void)hipFree(d_dist2); (void)hipFree(d_knn);
+    }
+    finish_load([&](std::vector<float> (&init)[6]) {          // the device's initialisation, kept on the host too (resetGaussian, getPoints3D)
+        for (int g = 0; g < 6; ++g) {
+            init[g].assign((size_t)n_pts * kWidth[g], 0.f);
+            if (g != P_SHN) HIP_OR_THROW(hipMemcpy(init[g].data(), d_param[g], init[g].size() * sizeof(float), hipMemcpyDeviceToHost));
+        }
+    }, "point-cloud", [&](bool resumed) {
+        if (cfg.verbose && rank == 0)
+            logf_("dataset scene: %d splats, %zu cameras @ %dx%d, SH degree %d%s", n, cams.size(), W, H, sh_max, resumed ? " (resumed; cameras and images from the dataset)" : "");
+    });
+    evaluate(false);                                            // where the point-cloud start stands on the held-out views (evaluation on, rank 0)
     return true;
 }
 
@@ -814,7 +973,15 @@ bool GaussianTrainerScene::loadTrainData(const std::string& path) {
             trainSetup();
             return true;
         }
-        logf_("load_train_data('%s'): dataset ingestion (COLMAP / images) is outside this build's scope; use a 'synthetic:N=..,W=..,H=..,cams=..,sh=..,seed=..' spec", path.c_str());
+        std::error_code ec;
+        if (std::filesystem::is_directory(path, ec)) {
+            if (!m.load_dataset(path)) { m.status = TrainingStatus::Loading_Failed; return false; }
+            m.status = TrainingStatus::Preprocess_Done;
+            trainSetup();
+            return true;
+        }
+        logf_("load_train_data('%s'): not a directory; give a capture directory (sparse/0/ or sparse/ with cameras, images, points3D as .bin or .txt, and images/ "
+              "as binary PPM) or a 'synthetic:N=..,W=..,H=..,cams=..,sh=..,seed=..' spec", path.c_str());
     } catch (const std::exception& e) {
         logf_("load_train_data failed: %s", e.what());
     }

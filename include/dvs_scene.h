@@ -1,11 +1,12 @@
 /*
  * dvs_scene.h — deterministic synthetic scenes for the rasterizer hot path (host-side C-ABI).
  *
- * The reference's data pipeline (COLMAP / image loading inside the closed `gstrain` plugin,
- * load_train_data at application/diverseshot-cli/source/gs_train.cpp:108-122) is out of scope
- * (SURVEY.md §8(b), §8(f)); BASELINE.json's configs are all "random splats / synthetic cams".
- * This generator is the one source of those scenes for bench.py, the tests and libgstrain's
- * `synthetic:` loader, following SURVEY.md §8(d) "Synthetic inputs".
+ * BASELINE.json's configs are all "random splats / synthetic cams". This generator is the one source
+ * of those scenes for bench.py, the tests and libgstrain's `synthetic:` loader, following SURVEY.md
+ * §8(d) "Synthetic inputs". Real captures (a COLMAP sparse model plus undistorted images, the
+ * reference's load_train_data at application/diverseshot-cli/source/gs_train.cpp:108-122) are read by
+ * libgstrain's dataset loader (divshot_amd/gstrain/dataset_io.hpp), whose cameras come from
+ * dvs_make_camera_intrinsics below.
  */
 #ifndef DVS_SCENE_H
 #define DVS_SCENE_H
@@ -33,6 +34,15 @@ int dvs_synth_camera(const dvs_scene_spec* spec, int index, dvs_camera* out);
 int dvs_synth_target(const dvs_scene_spec* spec, int index, float* target);
 /* Build a camera from pose (world->camera rotation R row-major [9], translation t[3]) and pinhole fov. */
 int dvs_make_camera(const float* R, const float* t, float fov_x_deg, int width, int height, dvs_camera* out);
+/* The same camera from pinhole intrinsics in pixels (COLMAP's PINHOLE: fx, fy, cx, cy; SIMPLE_PINHOLE: fx = fy): same view, near / far and
+ * conventions as dvs_make_camera. focal_{x,y} = f{x,y}; tan_fovx = W / (2 fx), tan_fovy = H / (2 fy); the x row of proj carries 2 fx / W
+ * and the offset 2 cx / W - 1 (on the camera's z), the y row likewise from fy, cy, H. COLMAP puts a pixel's centre at i + 0.5, this
+ * rasterizer at i: a camera-space point (X, Y, Z) lands at pixel (fx X / Z + cx - 0.5, fy Y / Z + cy - 0.5). With cx = W / 2,
+ * cy = H / 2 and fx = W / (2 tan), fy = H / (2 tan_y) of a field of view the result equals dvs_make_camera's bit for bit. An off-centre
+ * principal point leaves the 1.3 tan_fov guard of the covariance clamp where it is, centred on the image (the decision of
+ * dvs_camera_downscale below). DVS_ERR_INVALID for a NULL argument, a size <= 0, fx or fy not positive, a non-finite value. */
+int dvs_make_camera_intrinsics(const float* R, const float* t, double fx, double fy, double cx, double cy, int width, int height,
+                               dvs_camera* out);
 /* The camera of `in` for its image box-downsampled by `factor` (1, 2, 4 or 8; dvs_downsample_views, include/dvs_train.h): the level
  * camera of coarse-to-fine training. view, campos, bg unchanged; width = W / d, height = H / d (floor); focal_{x,y} /= d (exact).
  * With s_x = W / (d W_d), s_y = H / (d H_d) in double (1 when d divides the size, > 1 when columns / rows are cropped):
