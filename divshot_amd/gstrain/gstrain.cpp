@@ -16,949 +16,32 @@
 // the sparse points, include/dvs_init.h) or a synthetic-scene spec. Out of scope: JPEG / PNG
 // decoding, distorted camera models, mesh export, the 2DGS model type. Every GaussianTrainConfig field the hosts set is either
 // honoured or named in the one-time "ignored" line of report_config().
-#include <hip/hip_runtime.h>
-#include <chrono>
-#include <cstdarg>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <filesystem>
-#include <functional>
-#include <map>
-#include <stdexcept>
-#include "../../include/gaussian_trainer_scene.hpp"
-#include "../../include/dvs_raster.h"
-#include "../../include/dvs_scene.h"
-#include "../../include/dvs_train.h"
-#include "../../include/dvs_comm.h"
-#include "../../include/dvs_export.h"
-#include "../../include/dvs_init.h"
-#include "ply_io.hpp"
-#include "dataset_io.hpp"
-
-namespace {
-const int kWidth[6] = {3, 3, 45, 1, 3, 4};          // pos sh0 shN opacity scale rot
-enum { P_POS = 0, P_SH0, P_SHN, P_OPA, P_SCALE, P_ROT };
-const int kAllGroups[6] = {P_POS, P_SH0, P_SHN, P_OPA, P_SCALE, P_ROT};
-const int kGeomGroups[4] = {P_POS, P_OPA, P_SCALE, P_ROT};                // what the factorised exchange all-reduces
-constexpr float kAdamBeta1 = 0.9f, kAdamBeta2 = 0.999f, kAdamEps = 1e-15f;
-
-void logf_(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-void logf_(const char* fmt, ...) {
-    va_list ap; va_start(ap, fmt);
-    fputs("[gstrain] ", stderr); vfprintf(stderr, fmt, ap); fputc('\n', stderr);
-    va_end(ap);
-}
-#define HIP_OR_THROW(expr)                                                                          \
-    do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw std::runtime_error(std::string(#expr ": ") + hipGetErrorString(e_)); } while (0)
-#define DVS_OR_THROW(expr)                                                                          \
-    do { int r_ = (expr); if (r_ != DVS_OK) throw std::runtime_error(std::string(#expr ": ") + dvs_last_error()); } while (0)
-
-// training images kept as 8 bits per channel when packLevel has PackF32ToU8 (gs_train.cpp:91-96: the reference's VRAM saver):
-// a quarter of the HBM footprint per view, expanded into one fp32 staging image right before the loss
-__global__ void k_pack_u8(const float* __restrict__ src, uint8_t* __restrict__ dst, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = (uint8_t)fminf(255.f, fmaxf(0.f, rintf(src[i] * 255.f)));
-}
-__global__ void k_unpack_u8(const uint8_t* __restrict__ src, float* __restrict__ dst, size_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = (float)src[i] * (1.0f / 255.0f);
-}
-// useMask (main.cpp:69-70): pixels outside the mask carry no loss gradient; mask [H*W] in {0,1}, dL planar [3,H,W]
-__global__ void k_mask_mul(float* __restrict__ dL, const float* __restrict__ mask, size_t P) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < 3 * P) dL[i] *= mask[i % P];
-}
-__global__ void k_norm2(const float* __restrict__ v2, float* __restrict__ out2, int n) {      // (x, y) -> (|v|, 0)
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) { const float x = v2[2 * i], y = v2[2 * i + 1]; out2[2 * i] = sqrtf(x * x + y * y); out2[2 * i + 1] = 0.f; }
-}
-
-struct Lcg {       // tiny deterministic noise source for the synthetic initialisation
-    uint64_t s;
-    explicit Lcg(uint64_t seed) : s(seed * 6364136223846793005ULL + 1442695040888963407ULL) {}
-    float uni() { s = s * 6364136223846793005ULL + 1442695040888963407ULL; return (float)((s >> 40) * (1.0 / 16777216.0)); }
-    float sym() { return 2.f * uni() - 1.f; }
-};
-}  // namespace
-
-struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     // the class is exported (GSTRAIN_API), its implementation is not
-    GaussianTrainConfig cfg;
-    int loadItr = -1;
-    TrainingStatus status = TrainingStatus::Loading_Prepare;
-    bool training = true;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    dvs_ctx* ctx = nullptr;
-    int n = 0, W = 0, H = 0, sh_max = 3;
-    float* d_param[6] = {}; float* d_grad[6] = {}; float* d_m[6] = {}; float* d_v[6] = {};
-    float* d_param2[6] = {}; float* d_m2[6] = {}; float* d_v2[6] = {};       // densification writes old -> new, then the sets swap
-    float* d_absgrad = nullptr;
-    float* d_grad_flat = nullptr; size_t grad_floats = 0;                    // the six gradient groups live in ONE buffer: one all-reduce
-    float* d_mean2d = nullptr;                                               // dL/dmean2D (ADC statistic when useAbsGrad is off)
-    dvs_comm* comm = nullptr; int rank = 0, world = 1;                       // data-parallel replicas (include/dvs_comm.h)
-    // Gradient exchange of the replicas. factorised (default): the geometry groups (pos, opacity, scale, rot: 44 B/splat) lead the
-    // flat buffer and are all-reduced; of the SH rows only each view's 3-float colour gradient is all-gathered (12 B/splat/view) and
-    // every replica rebuilds the summed rows with dvs_sh_grad_combine — at 8 GPUs 161 MB instead of 413 MB through each GPU's links
-    // per million splats. DVS_EXCHANGE=allreduce: one all-reduce of all 59-float rows.
-    bool factorised = true; size_t geom_floats = 0;
-    float* d_dcolor_local = nullptr; float* d_dcolor_all = nullptr;          // [cap,3] / [world,n,3]
-    float* d_dcolor_scratch = nullptr;                                       // A9's own copy of the colour gradient (the all-gather reads the early one)
-    hipStream_t comm_stream = nullptr; hipEvent_t ev_dcolor = nullptr, ev_bwd = nullptr, ev_comm = nullptr;   // collectives run beside A9
-    hipEvent_t ev_gather = nullptr; std::vector<hipEvent_t> ev_chunk;        // all-gather done / A9 chunk k queued (chunked geometry all-reduce)
-    bool pipeline = false;                                                   // DVS_EXCHANGE_PIPELINE=1 (with DVS_A9_CHUNKS > 1): see trainStep
-    std::vector<hipEvent_t> ev_ar;                                           // chunk k's geometry all-reduce has landed (communication stream)
-    std::vector<int> next_ci;                                                // the NEXT iteration's cameras, drawn early for the pipelined step
-    int a9_chunks = 1;                                                       // DVS_A9_CHUNKS: splat chunks of A9 whose geometry gradients leave one by one (default 1 until
-                                                                             // the chunked exchange has run on real multi-GPU hardware: ADVICE r03; equality with the unchunked
-                                                                             // exchange is asserted by tests/test_gpu_multirank.py::test_plugin_two_ranks_exchanges_agree)
-    std::vector<uint8_t*> d_targets_u8; float* d_target_f32 = nullptr;       // packLevel & PackF32ToU8
-    std::vector<float*> d_masks;                                             // useMask
-    std::vector<float> init_host[6];                                         // initial splats (resetGaussian, getPoints3D)
-    bool terminate = false, pruning = false;
-    int cap = 0;                                                             // array capacity in splats (cfg.capMax)
-    float* d_grad_accum = nullptr; float* d_denom = nullptr; int* d_max_radii = nullptr;
-    uint8_t* d_action = nullptr; uint32_t* d_offsets = nullptr; uint32_t* d_dscratch = nullptr; uint64_t* d_newcount = nullptr;
-    void* d_mcmc = nullptr;                                                  // dvs_mcmc_* scratch (densifyStrategy 1)
-    float extent = 1.f;                                                      // scene extent (camera spread), sets the split/clone scale
-    dvs_fwd_state fwd{};
-    int vpi = 1;                                                             // views per trainStep and GPU, one multi-view pass (cfg.viewsPerIter / DVS_VIEWS_PER_ITER)
-    bool sequential_views = false;                                           // DVS_VIEWS_MODE=sequential: the same views one pass at a time, accumulating (the reference shape)
-    int* d_vis_radius = nullptr;                                             // visibleAdam with vpi > 1: max radius over the step's views
-    std::vector<dvs_camera> cams;
-    std::vector<float*> d_targets;
-    float* d_out = nullptr; float* d_dL = nullptr; float* d_loss = nullptr;     // d_loss[0..63] = (1-w) L1 partial sums, d_loss[64..127] = SSIM partial sums
-    float* d_ssim_maps[3] = {nullptr, nullptr, nullptr};
-    float last_loss = 0.f;
-    int step = 0;
-    uint64_t cam_rng = 88172645463325252ULL;
-    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
-    std::vector<float> host[6];
-    bool host_valid = false;
-    // held-out evaluation (cfg.evalHoldout / evalEvery): camera i is a test camera iff i % eval_holdout == 0. Both lists are empty when
-    // evaluation is off — the draw is then the reference's, over all cameras. The test views are rendered by a context of their own:
-    // the training context's saved forward state, pending backward rows and prepared projection are never touched by an evaluation.
-    int eval_holdout = 0, eval_every = 0;
-    std::vector<int> train_idx, test_idx;
-    dvs_ctx* eval_ctx = nullptr; int eval_views = 0;                         // created at the first evaluation: min(n_test, 8) views per pass
-    float* d_eval_out = nullptr; void* d_eval_scratch = nullptr; double* d_eval_res = nullptr;
-    std::vector<double> eval_res;                                            // [n_test][4] = {mse, l1, ssim, psnr} of the last evaluation
-    double eval_mean[4] = {NAN, NAN, NAN, NAN};
-    int eval_it = -1;
-    // coarse-to-fine training (cfg.resolutionSchedule = S, cfg.numDownscales = K; both 0 here when the schedule is off): the step with
-    // `step` completed steps before it trains at level k = max(K - step / S, 0), on images of W / 2^k x H / 2^k — the stored views
-    // box-filtered by ONE dvs_downsample_views call per step into d_level_targets, the cameras those of dvs_camera_downscale. The
-    // level is a function of the step number alone (every rank derives the same one; a resume lands on the right one). Everything
-    // per pixel of the step (d_out, d_dL, the loss, the densification statistics) has the level's size; the arenas keep the full one.
-    int res_every = 0, res_levels = 0;
-    std::vector<std::vector<dvs_camera>> level_cams;                        // [k - 1][camera], k = 1..K (level 0: cams)
-    float* d_level_targets = nullptr; float* d_level_masks = nullptr;       // [vpi,3,H/2,W/2] / [vpi,H/2,W/2]: room for the largest level below full size
-    int cur_level = -1;                                                      // level of the last step (-1: none yet)
-    int lw = 0, lh = 0;                                                      // image size of the last step (W x H when the schedule is off)
-    int level_first_step = 0; std::chrono::steady_clock::time_point level_t0;
-    // compact exports beside the full PLY (cfg.exportFormats / DVS_EXPORT_FORMATS / the suffix of modelPath): the packers' scratch, the
-    // packed payload on the device and its host copy. Nothing is allocated until a save exports; the buffers only grow.
-    void* d_export_scratch = nullptr; uint8_t* d_export_out = nullptr; size_t export_scratch_cap = 0, export_out_cap = 0;
-    std::vector<uint8_t> export_host;
-
-    ~Impl() { release(); }
-    void release() {
-        if (device >= 0) (void)hipSetDevice(device);
-        for (int g = 0; g < 6; ++g) {
-            for (float** p : {&d_param[g], &d_m[g], &d_v[g], &d_param2[g], &d_m2[g], &d_v2[g]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-            d_grad[g] = nullptr;                                             // slices of d_grad_flat
-        }
-        for (uint8_t* t : d_targets_u8) (void)hipFree(t);
-        d_targets_u8.clear();
-        for (float* t : d_masks) (void)hipFree(t);
-        d_masks.clear();
-        for (float** p : {&d_grad_flat, &d_mean2d, &d_target_f32, &d_level_targets, &d_level_masks, &d_dcolor_local, &d_dcolor_all, &d_dcolor_scratch}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        if (d_vis_radius) { (void)hipFree(d_vis_radius); d_vis_radius = nullptr; }
-        for (hipEvent_t* e : {&ev_dcolor, &ev_bwd, &ev_comm, &ev_gather}) { if (*e) (void)hipEventDestroy(*e); *e = nullptr; }
-        for (hipEvent_t e : ev_chunk) (void)hipEventDestroy(e);
-        ev_chunk.clear();
-        for (hipEvent_t e : ev_ar) (void)hipEventDestroy(e);
-        ev_ar.clear();
-        if (comm_stream) { (void)hipStreamDestroy(comm_stream); comm_stream = nullptr; }
-        if (comm) { dvs_comm_destroy(comm); comm = nullptr; }
-        for (void** p : {(void**)&d_grad_accum, (void**)&d_denom, (void**)&d_max_radii, (void**)&d_action, (void**)&d_offsets,
-                         (void**)&d_dscratch, (void**)&d_newcount, &d_mcmc}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        for (float* t : d_targets) (void)hipFree(t);
-        d_targets.clear();
-        for (float** p : {&d_absgrad, &d_out, &d_dL, &d_loss, &d_ssim_maps[0], &d_ssim_maps[1], &d_ssim_maps[2]}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        for (void** p : {(void**)&d_eval_out, &d_eval_scratch, (void**)&d_eval_res}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        for (void** p : {&d_export_scratch, (void**)&d_export_out}) { if (*p) (void)hipFree(*p); *p = nullptr; }
-        export_scratch_cap = export_out_cap = 0;
-        if (eval_ctx) { dvs_destroy(eval_ctx); eval_ctx = nullptr; }
-        if (ctx) { dvs_destroy(ctx); ctx = nullptr; }
-        if (stream) { (void)hipStreamDestroy(stream); stream = nullptr; }
-    }
-    // floats of group g on the device: the 45 higher-order SH floats live in the DVS_SHN_TILED layout (48 per splat,
-    // whole 64-splat tiles); parameters, gradients and Adam moments share it — the optimizer is element-wise.
-    size_t dev_floats_for(int g, int count) const { return g == P_SHN ? (size_t)((count + 63) / 64) * 64 * 48 : (size_t)count * kWidth[g]; }
-    size_t dev_floats(int g) const { return dev_floats_for(g, n); }
-    void upload(int g, const std::vector<float>& host_rows) {
-        if (g != P_SHN) { HIP_OR_THROW(hipMemcpy(d_param[g], host_rows.data(), host_rows.size() * sizeof(float), hipMemcpyHostToDevice)); return; }
-        float* tmp = nullptr;
-        HIP_OR_THROW(hipMalloc((void**)&tmp, host_rows.size() * sizeof(float) + 4));
-        HIP_OR_THROW(hipMemcpy(tmp, host_rows.data(), host_rows.size() * sizeof(float), hipMemcpyHostToDevice));
-        DVS_OR_THROW(dvs_shn_relayout(ctx, stream, n, tmp, d_param[g], 1));
-        HIP_OR_THROW(hipStreamSynchronize(stream));
-        (void)hipFree(tmp);
-    }
-    void alloc_params(int count, int capacity, const std::vector<float> init[6]) {
-        n = count; cap = std::max(capacity, count);
-        grad_floats = 0;
-        size_t goff[6];
-        static const int order[6] = {P_POS, P_OPA, P_SCALE, P_ROT, P_SH0, P_SHN};       // geometry first: one contiguous all-reduce
-        for (int k = 0; k < 6; ++k) {
-            const int g = order[k];
-            if (g == P_SH0) geom_floats = grad_floats;
-            goff[g] = grad_floats; grad_floats += (dev_floats_for(g, cap) + 3) & ~(size_t)3;                            // 16-B aligned groups
-        }
-        HIP_OR_THROW(hipMalloc((void**)&d_grad_flat, grad_floats * sizeof(float) + 16));
-        HIP_OR_THROW(hipMemset(d_grad_flat, 0, grad_floats * sizeof(float)));
-        for (int g = 0; g < 6; ++g) d_grad[g] = d_grad_flat + goff[g];
-        HIP_OR_THROW(hipMalloc((void**)&d_mean2d, (size_t)cap * 2 * sizeof(float) + 4));
-        for (int g = 0; g < 6; ++g) {
-            const size_t bytes = dev_floats_for(g, cap) * sizeof(float);
-            for (float** p : {&d_param[g], &d_m[g], &d_v[g], &d_param2[g], &d_m2[g], &d_v2[g]}) {
-                HIP_OR_THROW(hipMalloc((void**)p, bytes ? bytes : 4));
-                HIP_OR_THROW(hipMemset(*p, 0, bytes));         // pad lanes of the last tile are never written: keep them zero
-            }
-            upload(g, init[g]);
-        }
-        HIP_OR_THROW(hipMalloc((void**)&d_absgrad, (size_t)cap * 2 * sizeof(float) + 4));
-        HIP_OR_THROW(hipMalloc((void**)&d_grad_accum, (size_t)cap * 4 + 4)); HIP_OR_THROW(hipMalloc((void**)&d_denom, (size_t)cap * 4 + 4));
-        HIP_OR_THROW(hipMalloc((void**)&d_max_radii, (size_t)cap * 4 + 4)); HIP_OR_THROW(hipMalloc((void**)&d_action, (size_t)cap + 4));
-        HIP_OR_THROW(hipMalloc((void**)&d_offsets, (size_t)cap * 4 + 4)); HIP_OR_THROW(hipMalloc((void**)&d_dscratch, ((size_t)cap / 256 + 8) * 4));
-        HIP_OR_THROW(hipMalloc((void**)&d_newcount, 8));
-        HIP_OR_THROW(hipMalloc(&d_mcmc, dvs_mcmc_scratch_bytes(cap)));
-        DVS_OR_THROW(dvs_mcmc_init_scratch(stream, d_mcmc, cap));
-        reset_stats();
-    }
-    void reset_stats() {
-        HIP_OR_THROW(hipMemsetAsync(d_grad_accum, 0, (size_t)cap * 4, stream));
-        HIP_OR_THROW(hipMemsetAsync(d_denom, 0, (size_t)cap * 4, stream));
-        HIP_OR_THROW(hipMemsetAsync(d_max_radii, 0, (size_t)cap * 4, stream));
-    }
-    void apply_plan(const dvs_densify_params& prm, int new_n, bool zero_moments);
-    void densify(int it);
-    void densify_mcmc(int it);
-    void prune_light(int it);
-    void report_config() const;
-    void sync_stats();
-    const float* target_for(int ci);
-    bool mcmc() const { return cfg.densifyStrategy == 1; }
-    bool exchange_factorised() const { return comm && factorised; }
-    bool visible_adam() const { return cfg.visibleAdam && world == 1; }     // per-rank visibility would let the replicas drift apart
-    int sh_degree_at(int s) const { return cfg.progressiveTrain ? std::min(sh_max, s / 1000) : sh_max; }   // SH bands unlocked every 1000 steps
-    void setup_exchange();
-    // cameras: one xorshift stream shared by all ranks; an iteration draws world x vpi views and rank r renders views r vpi .. r vpi + vpi - 1
-    // (vpi = 1: one view per GPU and iteration, as the reference's trainStep renders one camera; vpi = 8 on one GPU: BASELINE config C4)
-    void draw_cameras(std::vector<int>& ci) {
-        ci.assign((size_t)world * vpi, 0);                  // every rank knows every rank's cameras: the SH rows are rebuilt from them
-        for (int& c : ci) {
-            cam_rng ^= cam_rng << 13; cam_rng ^= cam_rng >> 7; cam_rng ^= cam_rng << 17;
-            if (train_idx.empty()) c = cfg.singleCamera ? 0 : (int)(cam_rng % cams.size());
-            else c = train_idx[cfg.singleCamera ? 0 : (size_t)(cam_rng % train_idx.size())];     // held-out cameras are never trained on
-        }
-    }
-    void setup_split();
-    bool evaluate(bool write_json, bool force = false);
-    void run_evaluation();
-    void write_eval_json() const;
-    std::vector<dvs_camera> rank_cameras(const std::vector<int>& ci_all, int level) const {     // this rank's views of an iteration's draw, at a level
-        std::vector<dvs_camera> v((size_t)vpi);
-        for (int k = 0; k < vpi; ++k) {
-            const size_t ci = (size_t)ci_all[(size_t)rank * vpi + k];
-            v[(size_t)k] = level > 0 ? level_cams[(size_t)level - 1][ci] : cams[ci];
-        }
-        return v;
-    }
-    int level_of(int s) const { return res_every > 0 ? std::max(res_levels - s / res_every, 0) : 0; }   // s: completed steps before the step
-    void setup_levels();
-    const int* any_view_radii() {                            // max radius over the step's views (view-major fwd.radii of the multi-view pass)
-        if (!d_vis_radius) HIP_OR_THROW(hipMalloc((void**)&d_vis_radius, (size_t)cap * sizeof(int) + 16));
-        DVS_OR_THROW(dvs_any_view_radius(stream, n, vpi, fwd.radii, d_vis_radius));
-        return d_vis_radius;
-    }
-    // ---- the phases of one trainStep ----
-    struct Step {                                                            // one iteration, carried through its phases
-        int it = 0, deg = 0;                                                 // the iteration being computed, its SH degree
-        int level = 0, div = 1, Wd = 0, Hd = 0;                              // resolution level of the step, 2^level, the level's image size
-        std::vector<int> ci_all;                                             // the iteration's cameras, [rank][local view]
-        std::vector<dvs_camera> vcams;                                       // this rank's views
-        dvs_opts opts{};
-        bool mcmc = false, absgrad = false, want_stats = false;
-        bool refine_now = false, reset_now = false, prune_now = false;
-        float lr_pos = 0.f;
-        dvs_adam_group adam[6] = {};                                         // Adam groups over the whole arrays
-        const int* adam_gate = nullptr;                                      // (render_backward) visible-only Adam: radius > 0 in the step's views
-        int chunk_per = 0, n_chunks = 0;                                     // (render_backward) > 0: the geometry gradients left behind A9 in chunks
-    };
-    Step plan_step();                                                        // decides the step; launches nothing
-    void enter_level(const Step& s);
-    void close_level();
-    void level_targets(const Step& s);
-    void loss_of_view(const Step& s, int v);
-    void render_backward(Step& s);
-    void exchange(const Step& s, bool pipelined);
-    void finish_range(const Step& s, int first, int count, const int* groups, int n_groups, const int* gate);
-    void finish_pipelined(const Step& s);
-    dvs_splats splats() const {
-        dvs_splats s{};
-        s.pos = d_param[P_POS]; s.sh0 = d_param[P_SH0]; s.shN = d_param[P_SHN]; s.opacity = d_param[P_OPA];
-        s.scale = d_param[P_SCALE]; s.rot = d_param[P_ROT]; s.n = n;
-        return s;
-    }
-    std::string model_file(int it) const { return cfg.modelPath + "_" + std::to_string(it) + ".ply"; }
-    bool model_path_ends(const char* suffix) const {
-        const size_t k = strlen(suffix);
-        return cfg.modelPath.size() >= k && cfg.modelPath.compare(cfg.modelPath.size() - k, k, suffix) == 0;
-    }
-    // EXPORT_* bits of the compact formats a save writes; decided at every use, since the editor sets modelPath after construction
-    enum { EXPORT_COMPRESSED = 1, EXPORT_SPLAT = 2 };
-    int suffix_formats() const { return model_path_ends(".compressed.ply") ? EXPORT_COMPRESSED : model_path_ends(".splat") ? EXPORT_SPLAT : 0; }
-    int export_formats() const {
-        int f = cfg.exportFormats;
-        if (const char* e = getenv("DVS_EXPORT_FORMATS")) f = atoi(e);
-        if (f == 0) f = suffix_formats();
-        return f & (EXPORT_COMPRESSED | EXPORT_SPLAT);
-    }
-    void export_model(int format);
-    void fetch_host() {
-        if (host_valid) return;
-        HIP_OR_THROW(hipStreamSynchronize(stream));
-        for (int g = 0; g < 6; ++g) {
-            host[g].resize((size_t)n * kWidth[g]);             // host copies are always in the reference layout (update_from_cpu)
-            const float* src = d_param[g];
-            float* tmp = nullptr;
-            if (g == P_SHN) {
-                HIP_OR_THROW(hipMalloc((void**)&tmp, host[g].size() * sizeof(float) + 4));
-                DVS_OR_THROW(dvs_shn_relayout(ctx, stream, n, d_param[g], tmp, 0));
-                HIP_OR_THROW(hipStreamSynchronize(stream));
-                src = tmp;
-            }
-            HIP_OR_THROW(hipMemcpy(host[g].data(), src, host[g].size() * sizeof(float), hipMemcpyDeviceToHost));
-            if (tmp) (void)hipFree(tmp);
-        }
-        host_valid = true;
-    }
-    // what the two loaders share: the context and every per-step buffer (W, H, sh_max set by the caller) ...
-    void create_context(int count, int capacity, const std::vector<float> init[6]);
-    // ... and, once cams / the targets / the masks are in place: split, levels, extent, resume or the loader's fresh initialisation,
-    // upload, report_config, the loader's own verbose line (told whether the run resumed), exchange set-up
-    void finish_load(const std::function<void(std::vector<float> (&)[6])>& fresh_init, const char* fresh_name,
-                     const std::function<void(bool)>& describe);
-    bool load_synthetic(const std::string& spec_str);
-    bool load_dataset(const std::string& path);
-};
-
-// the fp32 target image of camera ci on the device (expands the 8-bit copy when packLevel has PackF32ToU8)
-const float* GaussianTrainerScene::Impl::target_for(int ci) {
-    if (!(cfg.packLevel & PackF32ToU8)) return d_targets[ci];
-    const size_t img = 3 * (size_t)W * H;
-    hipLaunchKernelGGL(k_unpack_u8, dim3((unsigned)((img + 255) / 256)), dim3(256), 0, stream, d_targets_u8[ci], d_target_f32, img);
-    return d_target_f32;
-}
-
-// One line per decision: which GaussianTrainConfig fields this build honours and which it ignores (gs_train.cpp:50-103 sets them all).
-void GaussianTrainerScene::Impl::report_config() const {
-    if (rank != 0) return;
-    static const char* strat[3] = {"ADC (clone / split / prune)", "MCMC (relocation + growth)", "ADC+ (ADC on abs-grad statistics with revised opacity)"};
-    logf_("config: densifyStrategy %d = %s; pruneStrategy %d (%s) every %d steps after refineStopIter %d; capMax %d; packLevel %d (%s%s); "
-          "useMask %d; useAbsGrad %d; mipAntiliased %d; visibleAdam %d; singleCamera %d; progressiveTrain %d; world %d",
-          cfg.densifyStrategy, strat[std::min(2, std::max(0, cfg.densifyStrategy))], cfg.pruneStrategy,
-          cfg.pruneStrategy > 0 ? "light prune: opacity < pruneOpacity or scale > pruneScale3d" : "off", cfg.pruneInterval, cfg.refineStopIter,
-          cfg.capMax, cfg.packLevel, (cfg.packLevel & PackF32ToU8) ? "PackF32ToU8: 8-bit training views" : "fp32 training views",
-          (cfg.packLevel & PackTileID) ? ", PackTileID: always on here (the tile sort's keys are tile ids inside a view, written as 16-bit words while a view has <= 65536 tiles)" : "",
-          (int)cfg.useMask, (int)cfg.useAbsGrad, (int)cfg.mipAntiliased, (int)cfg.visibleAdam, (int)cfg.singleCamera, (int)cfg.progressiveTrain, world);
-    if (!test_idx.empty()) {
-        std::string idx;
-        for (int c : test_idx) idx += " " + std::to_string(c);
-        logf_("config: evaluation: %zu of %zu cameras held out of training (evalHoldout %d: cameras%s), scored at every save%s", test_idx.size(),
-              cams.size(), eval_holdout, idx.c_str(), eval_every > 0 ? (" and every " + std::to_string(eval_every) + " steps").c_str() : "");
-    }
-    if (res_every > 0)
-        logf_("config: resolutionSchedule %d, numDownscales %d: coarse-to-fine training, the step after s completed ones renders 1/2^max(%d - s/%d, 0) of "
-              "%dx%d (targets box-filtered per step, cameras of dvs_camera_downscale); full resolution from iteration %d; evaluation always at full size",
-              res_every, res_levels, res_levels, res_every, W, H, res_levels * res_every + 1);
-    if (const int fmts = export_formats())
-        logf_("config: exportFormats %d: every save also writes%s%s beside the full PLY, packed on the device%s", fmts,
-              (fmts & EXPORT_COMPRESSED) ? " <modelPath>_<it>.compressed.ply" : "", (fmts & EXPORT_SPLAT) ? " <modelPath>_<it>.splat" : "",
-              (cfg.exportFormats == 0 && !getenv("DVS_EXPORT_FORMATS")) ? " (turned on by the suffix of modelPath)" : "");
-    std::string ign;
-    if (model_path_ends(".spz")) ign += " modelPath suffix .spz(spz export: the full PLY is written)";
-    if (cfg.modelType != 0) ign += " modelType(only 3DGS)";
-    if (cfg.cullSH) ign += " cullSH";
-    if (cfg.pixelGradScale) ign += " pixelGradScale";
-    if (cfg.bestQuality) ign += " bestQuality";
-    if (cfg.normalConsistencyLoss) ign += " normalConsistencyLoss(2DGS)";
-    if (cfg.enableBg) ign += " enableBg";
-    if (cfg.enableFocusRegion) ign += " enableFocusRegion";
-    if (cfg.exportMesh) ign += " exportMesh";
-    if (cfg.outputSparsePoints) ign += " outputSparsePoints";
-    if (cfg.maxImageCount) ign += " maxImageCount";
-    if (!cfg.cameraPosePath.empty() || !cfg.pointCloudPath.empty()) ign += " cameraPosePath/pointCloudPath(dataset ingestion)";
-    if (cfg.visibleAdam && world > 1) ign += " visibleAdam(off with WORLD_SIZE > 1: the visible set differs per rank)";
-    if (!ign.empty()) logf_("config: IGNORED by this build:%s", ign.c_str());
-}
-
-// the train / test split of cfg.evalHoldout (DVS_EVAL_HOLDOUT): a function of the camera index alone, so every rank derives the same one
-void GaussianTrainerScene::Impl::setup_split() {
-    eval_holdout = cfg.evalHoldout; eval_every = cfg.evalEvery;
-    if (const char* e = getenv("DVS_EVAL_HOLDOUT")) eval_holdout = atoi(e);
-    if (const char* e = getenv("DVS_EVAL_EVERY")) eval_every = atoi(e);
-    train_idx.clear(); test_idx.clear();
-    if (eval_holdout <= 0) { eval_holdout = 0; return; }
-    for (int c = 0; c < (int)cams.size(); ++c) (c % eval_holdout == 0 ? test_idx : train_idx).push_back(c);
-    if (train_idx.empty() || test_idx.empty()) {
-        if (rank == 0)
-            logf_("evaluation is OFF: evalHoldout %d over %zu cameras leaves %zu to train on and %zu to test on; training on every camera",
-                  eval_holdout, cams.size(), train_idx.size(), test_idx.size());
-        train_idx.clear(); test_idx.clear(); eval_holdout = 0;
-    }
-}
-
-// Held-out evaluation, on the training stream: the test cameras rendered from the current parameters at the full SH degree (what a
-// viewer shows from the saved PLY), min(n_test, 8) views per multi-view pass of a SEPARATE context, each pass scored by one
-// dvs_image_metrics_views call against the stored targets (8-bit ones as they are, the camera's mask when useMask), then ONE copy of
-// the [n_test][4] doubles to the host. Only rank 0 evaluates (the replicas are identical). -> false when evaluation is off.
-// A save right after the step that was just scored (evalEvery divides the iteration) writes that result: the parameters are the same.
-bool GaussianTrainerScene::Impl::evaluate(bool write_json, bool force) {
-    if (test_idx.empty() || rank != 0 || !ctx) return false;
-    HIP_OR_THROW(hipSetDevice(device));
-    if (force || eval_it != step) run_evaluation();
-    if (write_json) write_eval_json();
-    return true;
-}
-void GaussianTrainerScene::Impl::run_evaluation() {
-    const int nt = (int)test_idx.size();
-    const size_t img = 3 * (size_t)W * H;
-    if (!eval_ctx) {
-        eval_views = std::min(nt, 8);
-        eval_ctx = dvs_create_views(device, (size_t)cap, W, H, eval_views);
-        if (!eval_ctx) throw std::runtime_error(std::string("dvs_create_views (evaluation): ") + dvs_last_error());
-        HIP_OR_THROW(hipMalloc((void**)&d_eval_out, (size_t)eval_views * img * sizeof(float)));
-        HIP_OR_THROW(hipMalloc(&d_eval_scratch, dvs_image_metrics_scratch_bytes(W, H, eval_views)));
-        HIP_OR_THROW(hipMalloc((void**)&d_eval_res, (size_t)nt * 4 * sizeof(double)));
-    }
-    dvs_opts opts{};
-    opts.sh_degree = sh_max; opts.antialias = cfg.mipAntiliased ? 1 : 0; opts.shn_layout = DVS_SHN_TILED; opts.tile_bounds = DVS_TILES_CANONICAL;
-    const dvs_splats sp = splats();
-    const bool u8 = (cfg.packLevel & PackF32ToU8) != 0;
-    for (int first = 0; first < nt; first += eval_views) {
-        const int nb = std::min(eval_views, nt - first);
-        std::vector<dvs_camera> bc((size_t)nb);
-        dvs_metrics_view mv[DVS_METRICS_MAX_VIEWS] = {};
-        for (int k = 0; k < nb; ++k) {
-            const size_t ci = (size_t)test_idx[(size_t)(first + k)];
-            bc[(size_t)k] = cams[ci];
-            mv[k].img = d_eval_out + (size_t)k * img;
-            mv[k].target = u8 ? (const void*)d_targets_u8[ci] : (const void*)d_targets[ci];
-            mv[k].mask = cfg.useMask && !d_masks.empty() ? d_masks[ci] : nullptr;
-        }
-        DVS_OR_THROW(dvs_raster_forward_views(eval_ctx, stream, &sp, bc.data(), nb, &opts, d_eval_out));
-        DVS_OR_THROW(dvs_image_metrics_views(stream, mv, nb, W, H, u8 ? 1 : 0, d_eval_scratch, d_eval_res + (size_t)first * 4));
-    }
-    eval_res.assign((size_t)nt * 4, 0.0);
-    HIP_OR_THROW(hipMemcpyAsync(eval_res.data(), d_eval_res, eval_res.size() * sizeof(double), hipMemcpyDeviceToHost, stream));
-    HIP_OR_THROW(hipStreamSynchronize(stream));
-    for (int k = 0; k < 4; ++k) {
-        double a = 0.0;
-        for (int v = 0; v < nt; ++v) a += eval_res[(size_t)v * 4 + k];
-        eval_mean[k] = a / nt;
-    }
-    eval_it = step;
-    logf_("eval @%d: %d views, PSNR %.17g dB, SSIM %.17g, L1 %.17g", step, nt, eval_mean[3], eval_mean[2], eval_mean[1]);
-}
-// <modelPath>_<it>_eval.json: the last evaluation, every double with 17 significant digits (they read back bit for bit)
-void GaussianTrainerScene::Impl::write_eval_json() const {
-    const int nt = (int)test_idx.size();
-    const std::string file = cfg.modelPath + "_" + std::to_string(step) + "_eval.json";
-    FILE* f = fopen(file.c_str(), "w");
-    if (!f) { logf_("evaluation: cannot write %s", file.c_str()); return; }
-    fprintf(f, "{\n  \"iteration\": %d,\n  \"n_splats\": %d,\n  \"sh_degree\": %d,\n  \"holdout\": %d,\n  \"views\": [\n", step, n, sh_max, eval_holdout);
-    for (int v = 0; v < nt; ++v) {
-        const double* r = &eval_res[(size_t)v * 4];
-        fprintf(f, "    {\"camera\": %d, \"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}%s\n", test_idx[(size_t)v], r[3], r[2], r[1], r[0],
-                v + 1 < nt ? "," : "");
-    }
-    fprintf(f, "  ],\n  \"mean\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}\n}\n", eval_mean[3], eval_mean[2], eval_mean[1], eval_mean[0]);
-    fclose(f);
-}
-
-// cfg.resolutionSchedule / numDownscales (DVS_RESOLUTION_SCHEDULE / DVS_NUM_DOWNSCALES): K clamped once to the largest value that leaves
-// min(W, H) >> K >= 16 (and to the factor 8 of dvs_downsample_views); level cameras of every (camera, level) and the staging buffers
-void GaussianTrainerScene::Impl::setup_levels() {
-    res_every = cfg.resolutionSchedule; res_levels = cfg.numDownscales;
-    if (const char* e = getenv("DVS_RESOLUTION_SCHEDULE")) res_every = atoi(e);
-    if (const char* e = getenv("DVS_NUM_DOWNSCALES")) res_levels = atoi(e);
-    lw = W; lh = H; cur_level = -1;
-    if (res_every <= 0) { res_every = 0; res_levels = 0; return; }
-    int k = std::max(0, std::min(res_levels, 3));
-    while (k > 0 && (std::min(W, H) >> k) < 16) --k;
-    if (k != res_levels && rank == 0)
-        logf_("resolutionSchedule: numDownscales %d clamped to %d (levels 1/2 .. 1/8, the smaller side of %dx%d stays >= 16 pixels)", res_levels, k, W, H);
-    res_levels = k;
-    level_cams.assign((size_t)res_levels, std::vector<dvs_camera>(cams.size()));
-    for (int l = 1; l <= res_levels; ++l)
-        for (size_t c = 0; c < cams.size(); ++c) DVS_OR_THROW(dvs_camera_downscale(&cams[c], 1 << l, &level_cams[(size_t)l - 1][c]));
-    if (res_levels == 0) return;
-    const size_t P = (size_t)(W / 2) * (size_t)(H / 2);
-    HIP_OR_THROW(hipMalloc((void**)&d_level_targets, (size_t)vpi * 3 * P * sizeof(float) + 16));
-    if (cfg.useMask) HIP_OR_THROW(hipMalloc((void**)&d_level_masks, (size_t)vpi * P * sizeof(float) + 16));
-}
-
-// A step at another level than the one before it (the first step included): ONE stream synchronisation closes the finished level's
-// wall time and opens the new one's. max_radii is in pixels of its level and starts again; grad_accum / denom are in NDC units and carry over.
-void GaussianTrainerScene::Impl::enter_level(const Step& s) {
-    if (s.level == cur_level) return;
-    if (cur_level >= 0) {
-        close_level();
-        HIP_OR_THROW(hipMemsetAsync(d_max_radii, 0, (size_t)cap * 4, stream));
-    } else {
-        HIP_OR_THROW(hipStreamSynchronize(stream));
-    }
-    cur_level = s.level; level_first_step = step; level_t0 = std::chrono::steady_clock::now();
-    if (rank == 0) logf_("resolution @%d: %dx%d (1/%d)", s.it, s.Wd, s.Hd, s.div);
-}
-void GaussianTrainerScene::Impl::close_level() {                            // (also when training ends)
-    if (cur_level < 0) return;
-    HIP_OR_THROW(hipStreamSynchronize(stream));
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - level_t0).count();
-    const int steps = step - level_first_step;
-    if (rank == 0 && steps > 0) logf_("resolution: %d steps at %dx%d: %.4f ms/step", steps, W >> cur_level, H >> cur_level, ms / steps);
-    cur_level = -1;
-}
-
-// the step's views at its level (level > 0): ONE launch for the images, one more for the masks
-void GaussianTrainerScene::Impl::level_targets(const Step& s) {
-    const bool u8 = (cfg.packLevel & PackF32ToU8) != 0, masked = cfg.useMask && !d_masks.empty();
-    const size_t P = (size_t)s.Wd * s.Hd;
-    dvs_downsample_view tv[DVS_DOWNSAMPLE_MAX_VIEWS] = {}, mv[DVS_DOWNSAMPLE_MAX_VIEWS] = {};
-    for (int v = 0; v < vpi; ++v) {
-        const size_t ci = (size_t)s.ci_all[(size_t)rank * vpi + v];
-        tv[v].src = u8 ? (const void*)d_targets_u8[ci] : (const void*)d_targets[ci];
-        tv[v].dst = d_level_targets + (size_t)v * 3 * P;
-        if (masked) { mv[v].src = d_masks[ci]; mv[v].dst = d_level_masks + (size_t)v * P; }
-    }
-    DVS_OR_THROW(dvs_downsample_views(stream, tv, vpi, 3, W, H, s.div, u8 ? 1 : 0));
-    if (masked) DVS_OR_THROW(dvs_downsample_views(stream, mv, vpi, 1, W, H, s.div, 0));   // fractional weights at the ellipse's edge: they scale the gradient
-}
-
-// data parallel: the densification statistics are per-view sums / maxima — make them global before a refinement decision
-void GaussianTrainerScene::Impl::sync_stats() {
-    if (!comm) return;
-    DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, stream, d_grad_accum, (size_t)n));
-    DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, stream, d_denom, (size_t)n));
-    DVS_OR_THROW(dvs_comm_all_reduce_max_i32(comm, stream, d_max_radii, (size_t)n));
-}
-
-bool GaussianTrainerScene::Impl::load_synthetic(const std::string& spec_str) {
-    // "synthetic:N=100000,W=800,H=800,cams=8,sh=3,seed=1"
-    std::map<std::string, double> kv = {{"N", 100000}, {"W", 800}, {"H", 800}, {"cams", 8}, {"sh", 3}, {"seed", 1}};
-    size_t p = spec_str.find(':');
-    std::string rest = p == std::string::npos ? "" : spec_str.substr(p + 1);
-    while (!rest.empty()) {
-        size_t c = rest.find(',');
-        std::string item = rest.substr(0, c);
-        rest = c == std::string::npos ? "" : rest.substr(c + 1);
-        size_t e = item.find('=');
-        if (e == std::string::npos) continue;
-        kv[item.substr(0, e)] = atof(item.substr(e + 1).c_str());
-    }
-    dvs_scene_spec spec{};
-    spec.n = (int)kv["N"]; spec.width = (int)kv["W"]; spec.height = (int)kv["H"]; spec.sh_degree = (int)kv["sh"];
-    spec.n_cams = (int)kv["cams"]; spec.seed = (uint64_t)kv["seed"]; spec.fov_x_deg = 60.f; spec.scale_log_offset = 0.f;
-    if (spec.n <= 0 || spec.width <= 0 || spec.height <= 0 || spec.n_cams <= 0 || spec.sh_degree < 0 || spec.sh_degree > 3) return false;
-    if (spec.width > cfg.maxImageWidth || spec.height > cfg.maxImageHeight)
-        logf_("note: synthetic image %dx%d exceeds maxImageWidth/Height %dx%d (kept as is)", spec.width, spec.height, cfg.maxImageWidth, cfg.maxImageHeight);
-    W = spec.width; H = spec.height; sh_max = spec.sh_degree;
-    std::vector<float> gt[6];
-    for (int g = 0; g < 6; ++g) gt[g].resize((size_t)spec.n * kWidth[g]);
-    DVS_OR_THROW(dvs_synth_splats(&spec, gt[0].data(), gt[1].data(), gt[2].data(), gt[3].data(), gt[4].data(), gt[5].data()));
-    const int capacity = std::max(spec.n, cfg.capMax);          // --capMax is the array capacity (gs_train.cpp:89); 1.9 KB of HBM per splat
-    // ground-truth views: render the generating scene once per camera
-    create_context(spec.n, capacity, gt);
-    const size_t img = 3 * (size_t)W * H;
-    dvs_opts opts{sh_max, cfg.mipAntiliased ? 1 : 0, 0, 0, DVS_SHN_TILED};
-    const dvs_splats sp = splats();
-    for (int c = 0; c < spec.n_cams; ++c) {
-        dvs_camera cam;
-        DVS_OR_THROW(dvs_synth_camera(&spec, c, &cam));
-        float* t = nullptr;
-        HIP_OR_THROW(hipMalloc((void**)&t, img * sizeof(float)));
-        DVS_OR_THROW(dvs_raster_forward(ctx, stream, &sp, &cam, &opts, t, nullptr, nullptr));
-        cams.push_back(cam);
-        if (cfg.packLevel & PackF32ToU8) {                     // keep the view as 8 bits per channel, expand per step (target_for)
-            uint8_t* t8 = nullptr;
-            HIP_OR_THROW(hipMalloc((void**)&t8, img));
-            hipLaunchKernelGGL(k_pack_u8, dim3((unsigned)((img + 255) / 256)), dim3(256), 0, stream, t, t8, img);
-            HIP_OR_THROW(hipStreamSynchronize(stream));
-            (void)hipFree(t);
-            d_targets_u8.push_back(t8); d_targets.push_back(nullptr);
-        } else {
-            d_targets.push_back(t);
-        }
-        if (cfg.useMask) {                                     // synthetic mask: an ellipse inscribed in the image (no dataset masks here)
-            std::vector<float> mk((size_t)W * H);
-            for (int y = 0; y < H; ++y) for (int x = 0; x < W; ++x) {
-                const float u = (x + 0.5f) / W * 2.f - 1.f, v = (y + 0.5f) / H * 2.f - 1.f;
-                mk[(size_t)y * W + x] = (u * u + v * v <= 1.f) ? 1.f : 0.f;
-            }
-            float* dm = nullptr;
-            HIP_OR_THROW(hipMalloc((void**)&dm, mk.size() * sizeof(float)));
-            HIP_OR_THROW(hipMemcpy(dm, mk.data(), mk.size() * sizeof(float), hipMemcpyHostToDevice));
-            d_masks.push_back(dm);
-        }
-    }
-    // trainable initialisation = perturbed ground truth (or the checkpoint when --load_itr is given)
-    finish_load([&](std::vector<float> (&init)[6]) {
-        Lcg r(spec.seed + 17);
-        for (int g = 0; g < 6; ++g) init[g] = gt[g];
-        for (int i = 0; i < spec.n; ++i) {
-            const float z = gt[0][3 * i + 2];
-            for (int k = 0; k < 3; ++k) init[P_POS][3 * i + k] += 0.002f * z * r.sym();
-            for (int k = 0; k < 3; ++k) init[P_SH0][3 * i + k] += 0.5f * r.sym();
-            for (int k = 0; k < 45; ++k) init[P_SHN][45 * (size_t)i + k] = 0.f;
-            init[P_OPA][i] -= 1.0f;
-            for (int k = 0; k < 3; ++k) init[P_SCALE][3 * i + k] += 0.15f * r.sym();
-        }
-    }, "synthetic", [&](bool resumed) {
-        if (cfg.verbose) logf_("synthetic scene: %d splats, %d cameras @ %dx%d, SH degree %d%s", spec.n, spec.n_cams, W, H, sh_max, resumed ? " (resumed)" : "");
-    });
-    return true;
-}
-
-void GaussianTrainerScene::Impl::create_context(int count, int capacity, const std::vector<float> init[6]) {
-    vpi = cfg.viewsPerIter;
-    if (const char* e = getenv("DVS_VIEWS_PER_ITER")) vpi = atoi(e);
-    vpi = std::max(1, std::min(vpi, 16));
-    if (const char* e = getenv("DVS_VIEWS_MODE")) sequential_views = std::string(e) == "sequential";
-    if (vpi > 1 && rank == 0)
-        logf_("config: %d views per trainStep and GPU, %s", vpi, sequential_views ? "one pass per view, gradients accumulated (DVS_VIEWS_MODE=sequential)"
-                                                                                : "ONE multi-view pass (dvs_raster_forward_views / _backward_views), gradients summed");
-    ctx = dvs_create_views(device, (size_t)capacity, W, H, sequential_views ? 1 : vpi);
-    if (!ctx) throw std::runtime_error(std::string("dvs_create_views: ") + dvs_last_error());
-    alloc_params(count, capacity, init);
-    const size_t img = 3 * (size_t)W * H;
-    HIP_OR_THROW(hipMalloc((void**)&d_out, (size_t)vpi * img * sizeof(float)));
-    HIP_OR_THROW(hipMalloc((void**)&d_dL, (size_t)vpi * img * sizeof(float)));
-    HIP_OR_THROW(hipMalloc((void**)&d_loss, 2 * DVS_SSIM_SLOTS * sizeof(float)));
-    HIP_OR_THROW(hipMemset(d_loss, 0, 2 * DVS_SSIM_SLOTS * sizeof(float)));
-    if (cfg.ssimWeight > 0.f)
-        for (int k = 0; k < 3; ++k) HIP_OR_THROW(hipMalloc((void**)&d_ssim_maps[k], img * sizeof(float)));
-}
-
-void GaussianTrainerScene::Impl::finish_load(const std::function<void(std::vector<float> (&)[6])>& fresh_init, const char* fresh_name,
-                                             const std::function<void(bool)>& describe) {
-    const size_t img = 3 * (size_t)W * H;
-    if (cfg.packLevel & PackF32ToU8) HIP_OR_THROW(hipMalloc((void**)&d_target_f32, img * sizeof(float)));
-    HIP_OR_THROW(hipStreamSynchronize(stream));
-    setup_split();
-    setup_levels();
-    {   // scene extent = 1.1 x the largest distance of a camera centre from their mean (the usual "cameras_extent"); a single
-        // camera or a tiny rig falls back to half the depth range of the synthetic slab
-        double mean[3] = {0, 0, 0};
-        for (auto& c : cams) for (int k = 0; k < 3; ++k) mean[k] += c.campos[k] / cams.size();
-        double far = 0;
-        for (auto& c : cams) { double d = 0; for (int k = 0; k < 3; ++k) d += (c.campos[k] - mean[k]) * (c.campos[k] - mean[k]); far = std::max(far, std::sqrt(d)); }
-        extent = far > 1e-3 ? (float)(1.1 * far) : 5.0f;
-    }
-    std::vector<float> init[6];
-    bool resumed = false;
-    if (loadItr >= 0) {
-        std::string err;
-        resumed = gsply::read_ply(model_file(loadItr), init[0], init[1], init[2], init[3], init[4], init[5], &err) &&
-                  !init[3].empty() && (int)init[3].size() <= cap;        // the count may differ from the loader's after densification
-        if (resumed) n = (int)init[3].size();
-        if (!resumed) logf_("could not resume from %s (%s): starting from the %s initialisation", model_file(loadItr).c_str(), err.c_str(), fresh_name);
-        else step = loadItr;
-    }
-    if (!resumed) fresh_init(init);
-    for (int g = 0; g < 6; ++g) { upload(g, init[g]); init_host[g] = init[g]; }
-    report_config();
-    describe(resumed);
-    if (exchange_factorised()) setup_exchange();
-}
-
-// A capture directory: a COLMAP sparse model and undistorted PPM images (dataset_io.hpp). The views go up as bytes and are box-filtered
-// on the device when maxImageWidth / maxImageHeight ask for it; the splats start from the sparse points (include/dvs_init.h).
-bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
-    gsdata::Dataset ds;
-    std::string err;
-    if (!gsdata::read_dataset(path, &ds, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-    const int n_pts = (int)std::min<size_t>(ds.xyz.size() / 3, (size_t)0x7FFFFFFF);
-    if (n_pts <= 0) {
-        logf_("load_train_data('%s'): the sparse model has no usable points (%zu dropped); initialisation without a point cloud is out of scope", path.c_str(), ds.dropped);
-        return false;
-    }
-    // the smallest factor of {1, 2, 4, 8} that fits each image into maxImageWidth x maxImageHeight; one size per run
-    const int max_w = cfg.maxImageWidth > 0 ? cfg.maxImageWidth : 0x7FFFFFFF, max_h = cfg.maxImageHeight > 0 ? cfg.maxImageHeight : 0x7FFFFFFF;
-    std::vector<int> factor(ds.images.size(), 1);
-    int W0 = 0, H0 = 0, model = -1;
-    bool one_model = true;
-    for (size_t i = 0; i < ds.images.size(); ++i) {
-        const gsdata::Camera& c = ds.cameras[ds.images[i].camera];
-        const int w = (int)c.width, h = (int)c.height;
-        int d = 1;
-        while (d <= 8 && (w / d > max_w || h / d > max_h)) d *= 2;
-        if (d > 8 || w / d <= 0 || h / d <= 0) {
-            logf_("load_train_data('%s'): image %s is %dx%d; even 1/8 of it does not fit maxImageWidth / maxImageHeight %dx%d", path.c_str(),
-                  ds.images[i].name.c_str(), w, h, cfg.maxImageWidth, cfg.maxImageHeight);
-            return false;
-        }
-        factor[i] = d;
-        if (i == 0) { W0 = w; H0 = h; W = w / d; H = h / d; model = c.model; }
-        else if (w / d != W || h / d != H) {
-            logf_("load_train_data('%s'): image %s ends up %dx%d but %s ends up %dx%d; this trainer takes one image size per run", path.c_str(),
-                  ds.images[i].name.c_str(), w / d, h / d, ds.images[0].name.c_str(), W, H);
-            return false;
-        }
-        one_model = one_model && c.model == model;
-    }
-    sh_max = 3;
-    const int capacity = std::max(n_pts, cfg.capMax);
-    std::vector<float> zero[6];
-    for (int g = 0; g < 6; ++g) zero[g].assign((size_t)n_pts * kWidth[g], 0.f);
-    create_context(n_pts, capacity, zero);
-    const bool u8 = (cfg.packLevel & PackF32ToU8) != 0;
-    const size_t P = (size_t)W * H, img = 3 * P;
-    std::vector<uint8_t> px, planar, mk;
-    std::vector<float> mkf;
-    for (size_t i = 0; i < ds.images.size(); ++i) {
-        const gsdata::Image& im = ds.images[i];
-        const gsdata::Camera& c = ds.cameras[im.camera];
-        const int w = (int)c.width, h = (int)c.height, d = factor[i];
-        const size_t p0 = (size_t)w * h;
-        if (!gsdata::read_image(ds, i, &px, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-        planar.resize(3 * p0);                                  // the file is [H][W][3], the trainer's views are planar [3][H][W]
-        for (size_t q = 0; q < p0; ++q) for (int k = 0; k < 3; ++k) planar[(size_t)k * p0 + q] = px[3 * q + k];
-        // 1. the view as bytes; 2. box-filtered by the image's factor (rounded back to 8 bits when the views are kept as bytes)
-        uint8_t* full8 = nullptr;
-        HIP_OR_THROW(hipMalloc((void**)&full8, 3 * p0));
-        HIP_OR_THROW(hipMemcpy(full8, planar.data(), 3 * p0, hipMemcpyHostToDevice));
-        if (u8 && d == 1) {
-            d_targets_u8.push_back(full8); d_targets.push_back(nullptr);
-        } else {
-            float* t = nullptr;
-            HIP_OR_THROW(hipMalloc((void**)&t, img * sizeof(float)));
-            const dvs_downsample_view dv{full8, t};
-            DVS_OR_THROW(dvs_downsample_views(stream, &dv, 1, 3, w, h, d, 1));
-            if (u8) {
-                uint8_t* t8 = nullptr;
-                HIP_OR_THROW(hipMalloc((void**)&t8, img));
-                hipLaunchKernelGGL(k_pack_u8, dim3((unsigned)((img + 255) / 256)), dim3(256), 0, stream, t, t8, img);
-                d_targets_u8.push_back(t8); d_targets.push_back(nullptr);
-            } else {
-                d_targets.push_back(t);
-            }
-            HIP_OR_THROW(hipStreamSynchronize(stream));
-            (void)hipFree(full8);
-            if (u8) (void)hipFree(t);
-        }
-        if (cfg.useMask) {                                      // > 127 trains; a level mask keeps the box filter's fractional weights
-            if (!gsdata::read_mask(ds, i, &mk, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-            mkf.assign(mk.begin(), mk.end());
-            float* m0 = nullptr;
-            HIP_OR_THROW(hipMalloc((void**)&m0, p0 * sizeof(float)));
-            HIP_OR_THROW(hipMemcpy(m0, mkf.data(), p0 * sizeof(float), hipMemcpyHostToDevice));
-            if (d > 1) {
-                float* md = nullptr;
-                HIP_OR_THROW(hipMalloc((void**)&md, P * sizeof(float)));
-                const dvs_downsample_view dv{m0, md};
-                DVS_OR_THROW(dvs_downsample_views(stream, &dv, 1, 1, w, h, d, 0));
-                HIP_OR_THROW(hipStreamSynchronize(stream));
-                (void)hipFree(m0);
-                m0 = md;
-            }
-            d_masks.push_back(m0);
-        }
-        float R[9];
-        gsdata::rotation_of(im, R);
-        const float t3[3] = {(float)im.t[0], (float)im.t[1], (float)im.t[2]};
-        dvs_camera cam, camd;
-        DVS_OR_THROW(dvs_make_camera_intrinsics(R, t3, c.fx, c.fy, c.cx, c.cy, w, h, &cam));
-        DVS_OR_THROW(dvs_camera_downscale(&cam, d, &camd));
-        cams.push_back(camd);
-    }
-    if (rank == 0) {
-        char lvl[64] = "";
-        if (factor[0] > 1) snprintf(lvl, sizeof lvl, " -> %dx%d (1/%d)", W, H, factor[0]);
-        logf_("dataset: %zu cameras (%s), %dx%d%s, %d points (%zu dropped)", ds.images.size(), one_model ? gsdata::model_name(model) : "mixed pinhole models",
-              W0, H0, lvl, n_pts, ds.dropped);
-    }
-    // 4. the points, 5. their 3-NN scales and the initial parameters, straight into the parameter arrays
-    {
-        uint8_t* d_rgb = nullptr; float* d_dist2 = nullptr; void* d_knn = nullptr;
-        HIP_OR_THROW(hipMalloc((void**)&d_rgb, (size_t)n_pts * 3 + 16));
-        HIP_OR_THROW(hipMalloc((void**)&d_dist2, (size_t)n_pts * sizeof(float) + 16));
-        HIP_OR_THROW(hipMalloc(&d_knn, dvs_knn_scratch_bytes(n_pts)));
-        HIP_OR_THROW(hipMemcpy(d_param[P_POS], ds.xyz.data(), (size_t)n_pts * 3 * sizeof(float), hipMemcpyHostToDevice));
-        HIP_OR_THROW(hipMemcpy(d_rgb, ds.rgb.data(), (size_t)n_pts * 3, hipMemcpyHostToDevice));
-        const auto t_init = std::chrono::steady_clock::now();
-        DVS_OR_THROW(dvs_knn_mean_dist2(stream, n_pts, d_param[P_POS], d_knn, d_dist2));
-        DVS_OR_THROW(dvs_init_from_points(stream, n_pts, d_param[P_POS], d_rgb, d_dist2, d_param[P_SH0], d_param[P_OPA], d_param[P_SCALE], d_param[P_ROT]));
-        HIP_OR_THROW(hipStreamSynchronize(stream));
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_init).count();
-        if (rank == 0) logf_("init: 3-NN scales for %d points: %.3f ms", n_pts, ms);
-        (void)hipFree(d_rgb); (void)hipFree(d_dist2); (void)hipFree(d_knn);
-    }
-    finish_load([&](std::vector<float> (&init)[6]) {          // the device's initialisation, kept on the host too (resetGaussian, getPoints3D)
-        for (int g = 0; g < 6; ++g) {
-            init[g].assign((size_t)n_pts * kWidth[g], 0.f);
-            if (g != P_SHN) HIP_OR_THROW(hipMemcpy(init[g].data(), d_param[g], init[g].size() * sizeof(float), hipMemcpyDeviceToHost));
-        }
-    }, "point-cloud", [&](bool resumed) {
-        if (cfg.verbose && rank == 0)
-            logf_("dataset scene: %d splats, %zu cameras @ %dx%d, SH degree %d%s", n, cams.size(), W, H, sh_max, resumed ? " (resumed; cameras and images from the dataset)" : "");
-    });
-    evaluate(false);                                            // where the point-cloud start stands on the held-out views (evaluation on, rank 0)
-    return true;
-}
-
-// factorised exchange: the SH rows are not written by the backward, only each view's colour gradient, which leaves right after
-// the composite backward (dvs_raster_backward_dcolor) so that its all-gather runs on the communication stream while A9 computes
-void GaussianTrainerScene::Impl::setup_exchange() {
-    HIP_OR_THROW(hipMalloc((void**)&d_dcolor_local, (size_t)vpi * cap * 3 * sizeof(float) + 16));
-    HIP_OR_THROW(hipMalloc((void**)&d_dcolor_scratch, (size_t)vpi * cap * 3 * sizeof(float) + 16));
-    HIP_OR_THROW(hipMalloc((void**)&d_dcolor_all, (size_t)world * vpi * cap * 3 * sizeof(float) + 16));
-    HIP_OR_THROW(hipStreamCreateWithFlags(&comm_stream, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&ev_dcolor, &ev_bwd, &ev_comm, &ev_gather}) HIP_OR_THROW(hipEventCreateWithFlags(e, hipEventDisableTiming));
-    if (const char* e = getenv("DVS_A9_CHUNKS")) a9_chunks = std::max(1, std::min(64, atoi(e)));
-    if (const char* e = getenv("DVS_EXCHANGE_PIPELINE")) pipeline = e[0] == '1' && a9_chunks > 1;
-    ev_chunk.resize((size_t)a9_chunks); ev_ar.resize((size_t)a9_chunks);
-    for (hipEvent_t& e : ev_chunk) HIP_OR_THROW(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    for (hipEvent_t& e : ev_ar) HIP_OR_THROW(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (rank == 0 && a9_chunks > 1)
-        logf_("gradient exchange: A9 in %d splat chunks, each chunk's geometry all-reduce behind it%s", a9_chunks,
-              pipeline ? "; PIPELINED across the iteration boundary: Adam and the next iteration's projection run chunk by chunk as the all-reduces land "
-                         "(DVS_EXCHANGE_PIPELINE=1)" : "");
-}
-
-// applies the plan to the parameter, m and v sets (old -> new) and swaps the sets. The SH tile pads of every new set are zeroed
-// first; with zero_moments (densify) the whole new m and v groups are
-void GaussianTrainerScene::Impl::apply_plan(const dvs_densify_params& prm, int new_n, bool zero_moments) {
-    for (int set = 0; set < 3; ++set) {
-        float** src = set == 0 ? d_param : (set == 1 ? d_m : d_v);
-        float** dst = set == 0 ? d_param2 : (set == 1 ? d_m2 : d_v2);
-        const float* s6[6] = {src[0], src[1], src[2], src[3], src[4], src[5]};
-        for (int g = 0; g < 6; ++g)
-            if (g == P_SHN || (set > 0 && zero_moments)) HIP_OR_THROW(hipMemsetAsync(dst[g], 0, dev_floats_for(g, new_n) * sizeof(float), stream));
-        DVS_OR_THROW(dvs_densify_apply(stream, n, d_action, d_offsets, &prm, set == 0 ? 0 : 1, s6, dst, new_n));
-        for (int g = 0; g < 6; ++g) std::swap(src[g], dst[g]);
-    }
-}
-
-// densifyStrategy 1 (MCMC): dead splats are relocated onto live ones drawn ~ opacity, then the model grows by 5 % up to the cap.
-// In place: no second buffer set, no host round trip.
-void GaussianTrainerScene::Impl::densify_mcmc(int it) {
-    dvs_mcmc_sets sets{};
-    for (int g = 0; g < 6; ++g) { sets.param[g] = d_param[g]; sets.m[g] = d_m[g]; sets.v[g] = d_v[g]; }
-    DVS_OR_THROW(dvs_mcmc_relocate(stream, n, &sets, cfg.min_opacity, 2u * (uint32_t)it, DVS_SHN_TILED, d_mcmc, cap, nullptr));
-    const int target = std::min(cap, (int)(1.05 * (double)n));
-    const int n_new = target - n;
-    if (n_new > 0) {
-        DVS_OR_THROW(dvs_mcmc_grow(stream, n, n_new, &sets, cfg.min_opacity, 2u * (uint32_t)it + 1u, DVS_SHN_TILED, d_mcmc, cap));
-        if (cfg.verbose) logf_("mcmc @%d: %d -> %d splats", it, n, n + n_new);
-        n += n_new;
-        HIP_OR_THROW(hipMemsetAsync(d_grad[P_SHN], 0, dev_floats_for(P_SHN, cap) * sizeof(float), stream));   // pad lanes of the new last tile
-    }
-    host_valid = false;
-}
-
-// clone / split / prune between two iterations (densifyStrategy 0 ADC; 2 "ADC+" is served by the same rule)
-void GaussianTrainerScene::Impl::densify(int it) {
-    sync_stats();
-    dvs_densify_params prm{};
-    prm.grad_threshold = cfg.growGrad2d;
-    prm.scale_threshold = 0.01f * extent;                       // percent_dense x extent
-    prm.min_opacity = cfg.min_opacity;
-    const bool after_reset = it > cfg.resetAlphaEvery;
-    prm.max_world_scale = after_reset ? cfg.pruneScale3d * extent : 0.f;                     // `pruneScale3d` (fraction of the scene extent)
-    prm.max_screen_radius = after_reset && it < cfg.refineScale2dStopIter                    // `pruneScale2d` (fraction of the image size)
-                                ? std::max(1, (int)(cfg.pruneScale2d * (float)std::max(lw, lh))) : 0;   // (max_radii is in pixels of the level)
-    prm.cap_max = 0; prm.seed = (uint32_t)it; prm.shn_layout = DVS_SHN_TILED;  // no kernel cap: over capMax, the loop below re-plans prune-only
-    prm.revised_opacity = (cfg.revisedOpacity || cfg.densifyStrategy == 2) ? 1 : 0;      // ADC+ always uses the revised opacity of the copies
-    uint64_t new_n = 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        DVS_OR_THROW(dvs_densify_plan(stream, n, d_param[P_OPA], d_param[P_SCALE], d_grad_accum, d_denom, d_max_radii, &prm, d_action,
-                                      d_offsets, d_dscratch, d_newcount));
-        HIP_OR_THROW(hipMemcpyAsync(&new_n, d_newcount, 8, hipMemcpyDeviceToHost, stream));
-        HIP_OR_THROW(hipStreamSynchronize(stream));
-        if (new_n <= (uint64_t)cap) break;
-        prm.grad_threshold = 3.0e38f;                            // at the cap: prune only, no growth this round
-    }
-    if (new_n == 0 || new_n > (uint64_t)cap) { reset_stats(); return; }
-    apply_plan(prm, (int)new_n, true);
-    if (cfg.verbose) {
-        logf_("densify @%d: %d -> %llu splats", it, n, (unsigned long long)new_n);
-        uint64_t cap_ = 0, grows_ = 0, lastT_ = 0, over_ = 0;        // the rasterizer's instance arena at this point (HBM pressure of big scenes)
-        if (dvs_get_arena_info(ctx, &cap_, &grows_, &lastT_, &over_) == DVS_OK)
-            logf_("raster @%d: T = %llu tile instances in the last pass, instance arena %llu (enlarged %llu times), overflowed forwards %llu",
-                  it, (unsigned long long)lastT_, (unsigned long long)cap_, (unsigned long long)grows_, (unsigned long long)over_);
-    }
-    n = (int)new_n;
-    HIP_OR_THROW(hipMemsetAsync(d_grad[P_SHN], 0, dev_floats_for(P_SHN, cap) * sizeof(float), stream));   // pad lanes of the new last tile
-    reset_stats();
-    host_valid = false;
-}
-
-// pruneStrategy > 0 ("Light Gaussian Prune" in the reference's log, screenshots/cli_example.png): after refinement has stopped, every
-// pruneInterval steps splats that became transparent (opacity < pruneOpacity) or oversized (scale > pruneScale3d x extent) are removed
-// and the arrays compacted; no growth. Runs replicated (deterministic) on every rank.
-void GaussianTrainerScene::Impl::prune_light(int it) {
-    pruning = true;
-    dvs_densify_params prm{};
-    prm.grad_threshold = 3.0e38f;                               // never clone / split
-    prm.scale_threshold = 0.01f * extent;
-    prm.min_opacity = std::max(cfg.pruneOpacity, cfg.min_opacity);       // --minOpacity is the only opacity threshold the CLI exposes
-    prm.max_world_scale = cfg.pruneScale3d * extent;
-    prm.max_screen_radius = 0;
-    prm.cap_max = 0; prm.seed = (uint32_t)it; prm.shn_layout = DVS_SHN_TILED; prm.revised_opacity = 0;   // (no growth: nothing to cap)
-    reset_stats();
-    uint64_t new_n = 0;
-    DVS_OR_THROW(dvs_densify_plan(stream, n, d_param[P_OPA], d_param[P_SCALE], d_grad_accum, d_denom, d_max_radii, &prm, d_action,
-                                  d_offsets, d_dscratch, d_newcount));
-    HIP_OR_THROW(hipMemcpyAsync(&new_n, d_newcount, 8, hipMemcpyDeviceToHost, stream));
-    HIP_OR_THROW(hipStreamSynchronize(stream));
-    if (new_n > 0 && new_n < (uint64_t)n) {
-        apply_plan(prm, (int)new_n, false);
-        if (cfg.verbose && rank == 0) logf_("light prune @%d: %d -> %llu splats", it, n, (unsigned long long)new_n);
-        n = (int)new_n;
-        HIP_OR_THROW(hipMemsetAsync(d_grad_flat, 0, grad_floats * sizeof(float), stream));
-        host_valid = false;
-    }
-    pruning = false;
-}
+#include "trainer.hpp"
 
 GaussianTrainerScene::GaussianTrainerScene(const GaussianTrainConfig& cfg, int loadItr) : impl_(new Impl()) {
-    impl_->cfg = cfg;
-    impl_->loadItr = loadItr;
-    const char* lr = getenv("LOCAL_RANK");
-    impl_->device = lr ? atoi(lr) : 0;
+    Impl& m = *impl_;
+    m.cfg = cfg;
+    m.loadItr = loadItr;
+    m.device = env_int("LOCAL_RANK", 0);
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
         throw std::runtime_error("gstrain: no HIP device visible (this plugin has no CPU fallback)");
-    impl_->device %= count;
-    HIP_OR_THROW(hipSetDevice(impl_->device));
-    HIP_OR_THROW(hipStreamCreate(&impl_->stream));
+    m.device %= count;
+    HIP_OR_THROW(hipSetDevice(m.device));
+    hipStream_t stream = nullptr;
+    HIP_OR_THROW(hipStreamCreate(&stream));
+    m.stream.reset(stream);
     // data parallel when launched as one process per GPU (RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT); DVS_FORCE_COMM=1 runs the
     // collectives on a 1-rank communicator too (single-GPU proof of the RCCL path)
-    const char* ws = getenv("WORLD_SIZE"); const char* rk = getenv("RANK"); const char* force = getenv("DVS_FORCE_COMM");
-    const int world = ws ? atoi(ws) : 1;
-    if (world > 1 || (force && force[0] == '1')) {
-        impl_->comm = dvs_comm_create(impl_->device, rk ? atoi(rk) : 0, std::max(1, world), nullptr, 0);
-        if (!impl_->comm) throw std::runtime_error(std::string("gstrain: dvs_comm_create failed: ") + dvs_last_error());
-        impl_->rank = dvs_comm_rank(impl_->comm); impl_->world = dvs_comm_world(impl_->comm);
-        if (const char* ex = getenv("DVS_EXCHANGE")) impl_->factorised = std::string(ex) != "allreduce";
-        const char* be = getenv("DVS_COMM_BACKEND");
-        logf_("rank %d of %d on device %d: %s communicator up, gradient exchange: %s", impl_->rank, impl_->world, impl_->device,
-              be && std::string(be) == "tcp" ? "host-staged TCP (TEST backend)" : "RCCL",
-              impl_->factorised ? "factorised (all-gather of colour gradients + all-reduce of 44 B/splat)" : "all-reduce of all rows");
+    const int world = env_int("WORLD_SIZE", 1);
+    if (world > 1 || env_is("DVS_FORCE_COMM", "1")) {
+        m.comm.reset(dvs_comm_create(m.device, env_int("RANK", 0), std::max(1, world), nullptr, 0));
+        if (!m.comm) throw std::runtime_error(std::string("gstrain: dvs_comm_create failed: ") + dvs_last_error());
+        m.rank = dvs_comm_rank(m.comm.get()); m.world = dvs_comm_world(m.comm.get());
+        m.factorised = !env_is("DVS_EXCHANGE", "allreduce");
+        logf_("rank %d of %d on device %d: %s communicator up, gradient exchange: %s", m.rank, m.world, m.device,
+              env_is("DVS_COMM_BACKEND", "tcp") ? "host-staged TCP (TEST backend)" : "RCCL",
+              m.factorised ? "factorised (all-gather of colour gradients + all-reduce of 44 B/splat)" : "all-reduce of all rows");
     }
 }
 GaussianTrainerScene::~GaussianTrainerScene() = default;
@@ -967,15 +50,10 @@ bool GaussianTrainerScene::loadTrainData(const std::string& path) {
     Impl& m = *impl_;
     try {
         HIP_OR_THROW(hipSetDevice(m.device));
-        if (path.rfind("synthetic", 0) == 0) {
-            if (!m.load_synthetic(path)) { m.status = TrainingStatus::Loading_Failed; return false; }
-            m.status = TrainingStatus::Preprocess_Done;
-            trainSetup();
-            return true;
-        }
+        const bool synthetic = path.rfind("synthetic", 0) == 0;
         std::error_code ec;
-        if (std::filesystem::is_directory(path, ec)) {
-            if (!m.load_dataset(path)) { m.status = TrainingStatus::Loading_Failed; return false; }
+        if (synthetic || std::filesystem::is_directory(path, ec)) {
+            if (!(synthetic ? m.load_synthetic(path) : m.load_dataset(path))) { m.status = TrainingStatus::Loading_Failed; return false; }
             m.status = TrainingStatus::Preprocess_Done;
             trainSetup();
             return true;
@@ -995,207 +73,6 @@ void GaussianTrainerScene::trainSetup() {
     curIteration = impl_->step;
 }
 
-GaussianTrainerScene::Impl::Step GaussianTrainerScene::Impl::plan_step() {
-    Step s;
-    if (next_ci.size() == (size_t)world * vpi) { s.ci_all = next_ci; next_ci.clear(); }   // (drawn by the previous, pipelined step: the same stream)
-    else draw_cameras(s.ci_all);
-    s.level = level_of(step); s.div = 1 << s.level; s.Wd = W / s.div; s.Hd = H / s.div;
-    s.vcams = rank_cameras(s.ci_all, s.level);
-    s.it = step + 1;
-    s.deg = sh_degree_at(step);
-    s.mcmc = mcmc();
-    s.absgrad = cfg.useAbsGrad || cfg.densifyStrategy == 2;                  // ADC+ always splits on the abs-grad statistic
-    const bool refining = s.it < cfg.refineStopIter;
-    // densification statistics of the step's views, summed over the ranks in densify(): per view and visible
-    // splat  grad_accum += |abs-grad|, denom += 1, max_radii = max
-    s.want_stats = refining && !s.mcmc;
-    s.refine_now = refining && s.it > cfg.warmupLength && cfg.refineEvery > 0 && s.it % cfg.refineEvery == 0;
-    s.reset_now = refining && !s.mcmc && cfg.resetAlphaEvery > 0 && s.it % cfg.resetAlphaEvery == 0;
-    s.prune_now = !refining && cfg.pruneStrategy > 0 && cfg.pruneInterval > 0 && s.it % cfg.pruneInterval == 0;
-    s.opts.sh_degree = s.deg; s.opts.antialias = cfg.mipAntiliased ? 1 : 0; s.opts.absgrad = s.absgrad ? 1 : 0; s.opts.accumulate = 0;
-    s.opts.shn_layout = DVS_SHN_TILED;
-    s.opts.grad_mode = DVS_GRAD_LINEAGE;        // the backward of the lineage the reference credits (README.md:95)
-    static const bool tight_tiles = [] { const char* e = getenv("DVS_TIGHT_TILES"); return e && e[0] == '1'; }();
-    s.opts.tile_bounds = tight_tiles ? DVS_TILES_TIGHT : DVS_TILES_CANONICAL;   // opt-in: same images and gradients, shorter tile lists (dvs_raster.h)
-    // Adam, per-group learning rates (names gs_train.cpp:52-57; position lr decays exponentially init -> final, scaled by the scene extent)
-    const float t = std::min(1.0f, (float)step / (float)std::max(1, cfg.numIters));
-    s.lr_pos = extent * std::exp((1.f - t) * std::log(cfg.poslrInit) + t * std::log(cfg.poslrFinal));
-    const float lr[6] = {s.lr_pos, cfg.featurelr, cfg.featurelr / 20.f, cfg.opacitylr, cfg.scalinglr, cfg.rotationlr};
-    // one launch per set of groups; shN chunks above the active SH degree have g = m = v = 0 (Adam is the identity there)
-    for (int k = 0; k < 6; ++k)
-        s.adam[k] = dvs_adam_group{d_param[k], d_grad[k], d_m[k], d_v[k], (uint64_t)dev_floats(k), lr[k], kWidth[k],
-                                   k == P_SHN ? DVS_SHN_TILED : DVS_SHN_ROWS, 0};
-    s.adam[P_SHN].active_chunks = s.deg >= 3 ? 0 : (3 * ((s.deg + 1) * (s.deg + 1) - 1) + 3) / 4;
-    if (s.deg == 0) s.adam[P_SHN].count = 0;
-    return s;
-}
-
-// photometric loss (1-w) L1 + w (1 - SSIM), w = --ssim (main.cpp:24-25), of view v: its gradient goes straight into d_dL[v]; the loss
-// sums of the step's views add up in d_loss (getCurrentLoss reports their mean)
-void GaussianTrainerScene::Impl::loss_of_view(const Step& s, int v) {
-    const int ci = s.ci_all[(size_t)rank * vpi + v];
-    const int W = s.Wd, H = s.Hd;                                            // the step's level: everything below is per pixel of it
-    const size_t img = 3 * (size_t)W * H;
-    const float* target = s.level > 0 ? d_level_targets + (size_t)v * img : target_for(ci);
-    const float* out = d_out + (size_t)v * img;
-    float* dL = d_dL + (size_t)v * img;
-    const float w_ssim = d_ssim_maps[0] ? cfg.ssimWeight : 0.f;
-    if (w_ssim > 0.f) {     // SSIM maps, then the L1 and SSIM gradients in one pass over the image
-        DVS_OR_THROW(dvs_ssim_forward(stream, out, target, W, H, d_ssim_maps[0], d_ssim_maps[1], d_ssim_maps[2], d_loss + DVS_SSIM_SLOTS));
-        DVS_OR_THROW(dvs_loss_l1_ssim_backward(stream, out, target, W, H, d_ssim_maps[0], d_ssim_maps[1], d_ssim_maps[2], w_ssim, dL, d_loss));
-    } else {
-        DVS_OR_THROW(dvs_l1_loss_grad_w(stream, out, target, img, 1.f, dL, d_loss));
-    }
-    if (cfg.useMask && !d_masks.empty()) {
-        const size_t P = (size_t)W * H;
-        hipLaunchKernelGGL(k_mask_mul, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, stream, dL,
-                           s.level > 0 ? d_level_masks + (size_t)v * P : d_masks[(size_t)ci], P);
-    }
-}
-
-// forward, loss, composite backward, statistics and A9 of the step's views: ONE multi-view pass (parameters read once, one depth sort /
-// scan / (view, tile) sort / composite launch for all V views, the gradient rows written once: their sum over the views), or with
-// DVS_VIEWS_MODE=sequential one pass per view, gradients accumulating (the reference shape, kept as the check of the multi-view pass)
-void GaussianTrainerScene::Impl::render_backward(Step& s) {
-    const bool fact = exchange_factorised(), seq = sequential_views;
-    const int passes = seq ? vpi : 1, views = seq ? 1 : vpi;                 // views per pass
-    const dvs_splats sp = splats();
-    const int W = s.Wd, H = s.Hd;                                            // the step's level
-    const size_t img = 3 * (size_t)W * H;
-    if (s.level > 0) level_targets(s);
-    dvs_opts opts = s.opts;
-    dvs_splat_grads g{};
-    g.pos = d_grad[P_POS]; g.sh0 = d_grad[P_SH0]; g.shN = d_grad[P_SHN]; g.opacity = d_grad[P_OPA];
-    g.scale = d_grad[P_SCALE]; g.rot = d_grad[P_ROT]; g.absgrad2d = s.absgrad ? d_absgrad : nullptr;
-    g.mean2d = (s.want_stats && !s.absgrad) ? d_mean2d : nullptr;          // ADC without abs-grad: dL/dmean2D feeds the statistic
-    if (fact) { g.sh0 = nullptr; g.shN = nullptr; }                          // (the SH rows are rebuilt after the exchange)
-    for (int v = 0; v < passes; ++v) {                                      // v: the first view of the pass
-        const dvs_camera* cam = &s.vcams[(size_t)v];
-        opts.accumulate = v > 0 ? 1 : 0;
-        if (seq) {
-            DVS_OR_THROW(dvs_raster_forward(ctx, stream, &sp, cam, &opts, d_out + (size_t)v * img, &fwd, nullptr));
-        } else {
-            DVS_OR_THROW(dvs_raster_forward_views(ctx, stream, &sp, cam, views, &opts, d_out));
-            DVS_OR_THROW(dvs_get_view_state(ctx, 0, &fwd));                   // (view-major arrays: fwd.radii = [V][n])
-        }
-        for (int u = v; u < v + views; ++u) loss_of_view(s, u);
-        DVS_OR_THROW(dvs_raster_backward_composite(ctx, stream, cam, &opts, d_dL + (size_t)v * img));
-        if (fact) {
-            g.dcolor = d_dcolor_scratch + (size_t)v * n * 3;                 // A9's own copy of the colour gradient
-            DVS_OR_THROW(dvs_raster_backward_dcolor(ctx, stream, d_dcolor_local + (size_t)v * n * 3));
-        }
-        if (fact && v == passes - 1) {      // all local views' colour gradients leave in ONE all-gather, under the last pass's A9
-            HIP_OR_THROW(hipEventRecord(ev_dcolor, stream));
-            HIP_OR_THROW(hipStreamWaitEvent(comm_stream, ev_dcolor, 0));
-            DVS_OR_THROW(dvs_comm_all_gather_f32(comm, comm_stream, d_dcolor_local, d_dcolor_all, (size_t)vpi * n * 3));
-        }
-        if (s.want_stats && s.absgrad) {    // per view, from the composite backward's rows (before A9 consumes them): the exact single-view rule
-            const float* rows = nullptr; int rf = 0;
-            DVS_OR_THROW(dvs_get_bwd_intermediates(ctx, &rows, &rf));
-            DVS_OR_THROW(dvs_densify_accumulate_rows(stream, n, views, fwd.radii, rows, W, H, d_grad_accum, d_denom, d_max_radii));
-        }
-        if (fact && !seq && a9_chunks > 1 && n >= 256 * a9_chunks) {
-            // A9 in splat chunks: as soon as chunk k is queued its 44 B/splat of geometry gradients (four ranges of the flat buffer, one
-            // grouped collective) start their all-reduce on the communication stream, under the A9 of the chunks behind it
-            HIP_OR_THROW(hipEventRecord(ev_gather, comm_stream));            // (behind the colour all-gather queued above)
-            s.chunk_per = ((n + a9_chunks - 1) / a9_chunks + 255) / 256 * 256;
-            for (int first = 0; first < n; first += s.chunk_per, ++s.n_chunks) {
-                const int count = std::min(s.chunk_per, n - first);
-                const size_t k = (size_t)s.n_chunks;
-                DVS_OR_THROW(dvs_raster_backward_project_chunk(ctx, stream, &sp, cam, &opts, &g, first, count));
-                HIP_OR_THROW(hipEventRecord(ev_chunk[k], stream));
-                HIP_OR_THROW(hipStreamWaitEvent(comm_stream, ev_chunk[k], 0));
-                DVS_OR_THROW(dvs_comm_group_start(comm));
-                DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, comm_stream, d_grad[P_POS] + 3 * (size_t)first, 3 * (size_t)count));
-                DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, comm_stream, d_grad[P_SCALE] + 3 * (size_t)first, 3 * (size_t)count));
-                DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, comm_stream, d_grad[P_ROT] + 4 * (size_t)first, 4 * (size_t)count));
-                DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, comm_stream, d_grad[P_OPA] + (size_t)first, (size_t)count));
-                DVS_OR_THROW(dvs_comm_group_end(comm));
-                HIP_OR_THROW(hipEventRecord(ev_ar[k], comm_stream));
-            }
-        } else {
-            DVS_OR_THROW(dvs_raster_backward_project(ctx, stream, &sp, cam, &opts, &g));
-        }
-        if (s.want_stats && !s.absgrad) {
-            // the standard rule, threshold growGrad2d (0.0002): hypot(gx W/2, gy H/2) of the view's dL/dmean2D (pixel units) per visible
-            // splat. One view per step: the signed components go to dvs_densify_accumulate as they are — it scales each by (W/2, H/2)
-            // and takes the norm. The multi-view pass hands out the SUM over the views of dL/dmean2D: its norm is taken FIRST (k_norm2:
-            // (|g|, 0)), so that what is accumulated, once per step for splats visible in at least one view, is |sum g| W/2 — both
-            // components scaled by W/2 (documented difference for V > 1)
-            if (v > 0) throw std::runtime_error("gstrain: DVS_VIEWS_MODE=sequential with useAbsGrad off needs per-view mean2d rows (use the multi-view pass)");
-            const int* radii = seq || vpi == 1 ? fwd.radii : any_view_radii();
-            if (vpi > 1) hipLaunchKernelGGL(k_norm2, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_mean2d, d_mean2d, n);
-            DVS_OR_THROW(dvs_densify_accumulate(stream, n, radii, d_mean2d, W, H, d_grad_accum, d_denom, d_max_radii));
-        }
-    }
-    if (visible_adam()) s.adam_gate = seq || vpi == 1 ? fwd.radii : any_view_radii();   // (sequential: the last view's — a single-view notion there)
-}
-
-// data parallel, over RCCL / xGMI: all-gather of the views' colour gradients + all-reduce of the geometry groups, then every
-// replica rebuilds the summed SH rows from all views (factorised) — or ONE sum-all-reduce of all six groups (they share a buffer)
-void GaussianTrainerScene::Impl::exchange(const Step& s, bool pipelined) {
-    if (!comm) return;
-    if (!factorised) { DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, stream, d_grad_flat, grad_floats)); return; }
-    if (s.n_chunks == 0) {          // (all collectives on the communication stream, in the same order on every rank)
-        HIP_OR_THROW(hipEventRecord(ev_gather, comm_stream));                // (behind the colour all-gather)
-        HIP_OR_THROW(hipEventRecord(ev_bwd, stream));
-        HIP_OR_THROW(hipStreamWaitEvent(comm_stream, ev_bwd, 0));
-        DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm, comm_stream, d_grad_flat, geom_floats));
-    }
-    HIP_OR_THROW(hipEventRecord(ev_comm, comm_stream));
-    // The SH rows need only the colour all-gather: they are rebuilt and their Adam step (sh0 + shN: 192 of the 236 B per splat) runs
-    // WHILE the geometry all-reduce is still on the links; the geometry groups follow when it has landed.
-    HIP_OR_THROW(hipStreamWaitEvent(stream, ev_gather, 0));
-    std::vector<float> campos(s.ci_all.size() * 3);             // slot order of the all-gather: [rank][local view]
-    for (size_t q = 0; q < s.ci_all.size(); ++q) for (int k = 0; k < 3; ++k) campos[q * 3 + k] = cams[(size_t)s.ci_all[q]].campos[k];
-    DVS_OR_THROW(dvs_sh_grad_combine(ctx, stream, n, d_param[P_POS], s.deg, (int)s.ci_all.size(), campos.data(), d_dcolor_all,
-                                     d_grad[P_SH0], d_grad[P_SHN], 0, DVS_SHN_TILED));
-    const dvs_adam_group sh_groups[2] = {s.adam[P_SH0], s.adam[P_SHN]};
-    DVS_OR_THROW(dvs_adam_step_groups(stream, sh_groups, 2, kAdamBeta1, kAdamBeta2, kAdamEps, s.it, s.adam_gate, n));
-    if (!pipelined) HIP_OR_THROW(hipStreamWaitEvent(stream, ev_comm, 0));
-}
-
-// the optimizer tail on the splats [first, first + count): MCMC regularisers, Adam on the given groups, exploration noise. All are
-// element-wise, so a range is bit-identical to the whole-array calls.
-void GaussianTrainerScene::Impl::finish_range(const Step& s, int first, int count, const int* groups, int n_groups, const int* gate) {
-    if (s.mcmc)        // opacity and scale regularisers of the MCMC strategy (0.01 each in the published rule): a function of the replicated
-                       // parameters, added once (after the exchange) on every rank
-        DVS_OR_THROW(dvs_mcmc_regularize_range(stream, n, first, count, d_param[P_OPA], d_param[P_SCALE], d_grad[P_OPA], d_grad[P_SCALE], 0.01f, 0.01f));
-    dvs_adam_group ag[6];
-    for (int k = 0; k < n_groups; ++k) {
-        ag[k] = s.adam[groups[k]];
-        if (ag[k].layout != DVS_SHN_ROWS) continue;                      // (the tiled shN group is only ever stepped whole: first 0, count n)
-        const size_t off = (size_t)ag[k].width * (size_t)first;
-        ag[k].param += off; ag[k].grad += off; ag[k].m += off; ag[k].v += off; ag[k].count = (uint64_t)ag[k].width * (uint64_t)count;
-    }
-    DVS_OR_THROW(dvs_adam_step_groups(stream, ag, n_groups, kAdamBeta1, kAdamBeta2, kAdamEps, s.it, gate ? gate + first : nullptr, count));
-    if (s.mcmc && cfg.noiselr > 0.f)      // exploration noise, scaled by the position learning rate (`noiselr`, gs_train.cpp:97)
-        DVS_OR_THROW(dvs_mcmc_add_noise_range(stream, n, first, count, d_param[P_POS], d_param[P_SCALE], d_param[P_ROT], d_param[P_OPA],
-                                              cfg.noiselr * s.lr_pos, (uint32_t)s.it));
-}
-
-// PIPELINED exchange (round 6; SURVEY 8(e) "Overlap"; DVS_EXCHANGE_PIPELINE=1, off by default until it has run on real links): the
-// geometry gradients left in chunks behind A9. Here every chunk is finished as soon as ITS all-reduce has landed — regulariser,
-// Adam on the four geometry groups, exploration noise, each on the chunk's splat range (all element-wise: bit-identical to the
-// whole-array calls) — and then the NEXT iteration's projection (A2) of that chunk is queued: A2 is per splat, and the chunk's
-// parameters are final (the SH groups were stepped in exchange(), under the all-reduces). Only the last chunk's all-reduce is exposed;
-// the all-reduces of the chunks before it run under the Adam / A2 of their predecessors. Iterations that refine, reset or prune
-// change the parameters after Adam: no early projection there (the next forward projects everything itself).
-void GaussianTrainerScene::Impl::finish_pipelined(const Step& s) {
-    const bool early = !s.refine_now && !s.reset_now && !s.prune_now && s.it < cfg.numIters;
-    if (early) draw_cameras(next_ci);
-    const std::vector<dvs_camera> ncams = early ? rank_cameras(next_ci, level_of(s.it)) : std::vector<dvs_camera>();   // (the NEXT step's level)
-    dvs_opts nopts = s.opts;
-    nopts.sh_degree = sh_degree_at(s.it);                               // (what the next trainStep will compute from step = it)
-    const dvs_splats sp = splats();
-    for (int k = 0; k < s.n_chunks; ++k) {
-        const int first = k * s.chunk_per, count = std::min(s.chunk_per, n - first);
-        HIP_OR_THROW(hipStreamWaitEvent(stream, ev_ar[(size_t)k], 0));
-        finish_range(s, first, count, kGeomGroups, 4, nullptr);        // ungated Adam, unlike the unpipelined tail (s.adam_gate)
-        if (early) DVS_OR_THROW(dvs_raster_forward_views_prepare(ctx, stream, &sp, ncams.data(), vpi, &nopts, first, count));
-    }
-}
-
 void GaussianTrainerScene::trainStep() {
     Impl& m = *impl_;
     if (!m.ctx || m.cams.empty()) throw std::runtime_error("trainStep before loadTrainData");
@@ -1203,7 +80,7 @@ void GaussianTrainerScene::trainStep() {
     Impl::Step s = m.plan_step();
     if (m.res_every > 0) m.enter_level(s);
     m.lw = s.Wd; m.lh = s.Hd;
-    HIP_OR_THROW(hipMemsetAsync(m.d_loss, 0, 2 * DVS_SSIM_SLOTS * sizeof(float), m.stream));
+    HIP_OR_THROW(hipMemsetAsync(m.d_loss.get(), 0, 2 * DVS_SSIM_SLOTS * sizeof(float), m.stream.get()));
     m.render_backward(s);
     const bool pipelined = m.pipeline && s.n_chunks > 0;
     m.exchange(s, pipelined);
@@ -1212,7 +89,7 @@ void GaussianTrainerScene::trainStep() {
     else m.finish_range(s, 0, m.n, kAllGroups, 6, s.adam_gate);
     if (s.refine_now) { if (s.mcmc) m.densify_mcmc(s.it); else m.densify(s.it); }
     if (s.reset_now)
-        DVS_OR_THROW(dvs_reset_opacity(m.stream, m.n, m.d_param[P_OPA], 0.01f, m.d_m[P_OPA], m.d_v[P_OPA]));
+        DVS_OR_THROW(dvs_reset_opacity(m.stream.get(), m.n, m.d_param[P_OPA].get(), 0.01f, m.d_m[P_OPA].get(), m.d_v[P_OPA].get()));
     if (s.prune_now) {
         m.prune_light(s.it);
         pruenIteraions.push_back(s.it);
@@ -1230,7 +107,7 @@ void GaussianTrainerScene::saveGaussianModel() {
     Impl& m = *impl_;
     // the replicas are identical: one file — unless DVS_SAVE_ALL_RANKS=1 asks every rank for its own (<model>_<it>.ply.rank<r>), which
     // is how the two-rank test checks that they ARE identical, bit for bit
-    static const bool all_ranks = [] { const char* e = getenv("DVS_SAVE_ALL_RANKS"); return e && e[0] == '1'; }();
+    static const bool all_ranks = env_is("DVS_SAVE_ALL_RANKS", "1");
     if (m.rank != 0 && !all_ranks) return;
     const auto t_save = std::chrono::steady_clock::now();
     m.fetch_host();
@@ -1255,47 +132,6 @@ void GaussianTrainerScene::saveGaussianModel() {
     m.evaluate(true);                                                       // <modelPath>_<it>_eval.json beside the PLY (rank 0, evaluation on)
 }
 
-// One compact export of the current model: packed on the training stream from the device arrays (shN is not read, so its tiled layout
-// does not matter), the packed payload alone copied to the host and written to <modelPath>_<step>.compressed.ply / .splat.
-void GaussianTrainerScene::Impl::export_model(int format) {
-    const auto t_start = std::chrono::steady_clock::now();
-    const bool compressed = format == EXPORT_COMPRESSED;
-    const size_t n_chunks = ((size_t)n + 255) / 256;
-    const size_t chunk_bytes = n_chunks * 12 * sizeof(float);              // (a multiple of 16: the vertex records follow on a 16-byte boundary)
-    const size_t bytes = compressed ? chunk_bytes + (size_t)n * 16 : (size_t)n * 32;
-    if (bytes > export_out_cap) {
-        if (d_export_out) { (void)hipFree(d_export_out); d_export_out = nullptr; export_out_cap = 0; }
-        HIP_OR_THROW(hipMalloc((void**)&d_export_out, bytes));
-        export_out_cap = bytes;
-    }
-    if (export_host.size() < bytes) export_host.resize(bytes);
-    int status;
-    if (compressed) {
-        const size_t need = dvs_pack_scratch_bytes(n);
-        if (need > export_scratch_cap) {
-            if (d_export_scratch) { (void)hipFree(d_export_scratch); d_export_scratch = nullptr; export_scratch_cap = 0; }
-            HIP_OR_THROW(hipMalloc(&d_export_scratch, need));
-            export_scratch_cap = need;
-        }
-        status = dvs_pack_compressed(stream, n, d_param[P_POS], d_param[P_SH0], d_param[P_OPA], d_param[P_SCALE], d_param[P_ROT], d_export_scratch,
-                                     (float*)d_export_out, (uint32_t*)(d_export_out + chunk_bytes), nullptr);
-    } else {
-        status = dvs_pack_splat32(stream, n, d_param[P_POS], d_param[P_SH0], d_param[P_OPA], d_param[P_SCALE], d_param[P_ROT], d_export_out);
-    }
-    if (status != DVS_OK) throw std::runtime_error(std::string(compressed ? "dvs_pack_compressed" : "dvs_pack_splat32") + ": status " + std::to_string(status));
-    HIP_OR_THROW(hipMemcpyAsync(export_host.data(), d_export_out, bytes, hipMemcpyDeviceToHost, stream));
-    HIP_OR_THROW(hipStreamSynchronize(stream));
-    const std::string file = cfg.modelPath + "_" + std::to_string(step) + (compressed ? ".compressed.ply" : ".splat");
-    std::string err;
-    const bool ok = compressed ? gsply::write_compressed_ply(file, (size_t)n, (const float*)export_host.data(),
-                                                             (const uint32_t*)(export_host.data() + chunk_bytes), cfg.mipAntiliased, &err)
-                               : gsply::write_splat(file, (size_t)n, export_host.data(), &err);
-    if (!ok) { logf_("export @%d: %s", step, err.c_str()); return; }
-    std::error_code ec;
-    const auto file_bytes = std::filesystem::file_size(file, ec);
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    logf_("export @%d: %s %d splats, %llu bytes, %.2f ms", step, compressed ? "compressed.ply" : "splat", n, (unsigned long long)(ec ? bytes : file_bytes), ms);
-}
 void GaussianTrainerScene::exportMesh(const std::string&) { logf_("export_mesh: mesh extraction is outside this build's scope"); }
 void GaussianTrainerScene::exportSparsePointCloud(const std::string& path) {
     Impl& m = *impl_;
@@ -1325,20 +161,20 @@ void GaussianTrainerScene::resetGaussian() {
     Impl& m = *impl_;
     if (!m.ctx || m.init_host[P_OPA].empty()) return;
     HIP_OR_THROW(hipSetDevice(m.device));
-    HIP_OR_THROW(hipStreamSynchronize(m.stream));
+    HIP_OR_THROW(hipStreamSynchronize(m.stream.get()));
     m.n = (int)m.init_host[P_OPA].size();
     for (int g = 0; g < 6; ++g) {
         const size_t bytes = m.dev_floats_for(g, m.cap) * sizeof(float);
-        for (float** p : {&m.d_param[g], &m.d_m[g], &m.d_v[g]}) HIP_OR_THROW(hipMemset(*p, 0, bytes));
+        for (DevBuf<float>* p : {&m.d_param[g], &m.d_m[g], &m.d_v[g]}) HIP_OR_THROW(hipMemset(p->get(), 0, bytes));
         m.upload(g, m.init_host[g]);
     }
-    HIP_OR_THROW(hipMemset(m.d_grad_flat, 0, m.grad_floats * sizeof(float)));
+    HIP_OR_THROW(hipMemset(m.d_grad_flat.get(), 0, m.grad_floats * sizeof(float)));
     m.reset_stats();
     m.step = 0; curIteration = 0; pruenIteraions.clear();
     m.eval_it = -1;
     m.cur_level = -1; m.lw = m.W; m.lh = m.H;
     m.host_valid = false;
-    (void)dvs_raster_forward_cancel_prepared(m.ctx);          // (a pipelined step may have projected the next iteration's splats already)
+    (void)dvs_raster_forward_cancel_prepared(m.ctx.get());          // (a pipelined step may have projected the next iteration's splats already)
     m.status = TrainingStatus::Training;
     m.t0 = std::chrono::steady_clock::now();
 }
@@ -1418,8 +254,8 @@ float GaussianTrainerScene::getCurrentLoss() {
     Impl& m = *impl_;
     if (m.d_loss && m.stream) {
         float h[2 * DVS_SSIM_SLOTS] = {0.f};
-        (void)hipStreamSynchronize(m.stream);
-        (void)hipMemcpy(h, m.d_loss, sizeof h, hipMemcpyDeviceToHost);
+        (void)hipStreamSynchronize(m.stream.get());
+        (void)hipMemcpy(h, m.d_loss.get(), sizeof h, hipMemcpyDeviceToHost);
         const float w = m.d_ssim_maps[0] ? m.cfg.ssimWeight : 0.f;
         double l1 = 0, ssim_sum = 0;
         for (int k = 0; k < DVS_SSIM_SLOTS; ++k) { l1 += h[k]; ssim_sum += h[DVS_SSIM_SLOTS + k]; }

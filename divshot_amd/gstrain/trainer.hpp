@@ -1,0 +1,239 @@
+// trainer.hpp — GaussianTrainerScene::Impl, the state behind `libgstrain.so`, and what its source files share. The members are defined
+// in trainer_load.cpp (loaders, allocation), trainer_step.cpp (one trainStep), trainer_refine.cpp (densification, pruning) and
+// trainer_output.cpp (configuration report, evaluation, export); gstrain.cpp holds the GaussianTrainerScene members and the C symbols.
+#pragma once
+#include <chrono>
+#include <cstdarg>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <filesystem>
+#include <functional>
+#include <map>
+#include <string_view>
+#include "../../include/gaussian_trainer_scene.hpp"
+#include "../../include/dvs_scene.h"
+#include "../../include/dvs_train.h"
+#include "../../include/dvs_export.h"
+#include "../../include/dvs_init.h"
+#include "device_mem.hpp"
+#include "ply_io.hpp"
+#include "dataset_io.hpp"
+
+namespace {
+const int kWidth[6] = {3, 3, 45, 1, 3, 4};          // pos sh0 shN opacity scale rot
+enum { P_POS = 0, P_SH0, P_SHN, P_OPA, P_SCALE, P_ROT };
+const int kAllGroups[6] = {P_POS, P_SH0, P_SHN, P_OPA, P_SCALE, P_ROT};
+const int kGeomGroups[4] = {P_POS, P_OPA, P_SCALE, P_ROT};                // what the factorised exchange all-reduces
+
+__attribute__((format(printf, 1, 2))) inline void logf_(const char* fmt, ...) {
+    va_list ap; va_start(ap, fmt);
+    fputs("[gstrain] ", stderr); vfprintf(stderr, fmt, ap); fputc('\n', stderr);
+    va_end(ap);
+}
+#define HIP_OR_THROW(expr)                                                                          \
+    do { hipError_t e_ = (expr); if (e_ != hipSuccess) throw std::runtime_error(std::string(#expr ": ") + hipGetErrorString(e_)); } while (0)
+#define DVS_OR_THROW(expr)                                                                          \
+    do { int r_ = (expr); if (r_ != DVS_OK) throw std::runtime_error(std::string(#expr ": ") + dvs_last_error()); } while (0)
+
+// the DVS_* environment overrides: the integer value of `name` (atoi) or `fallback` when it is not set; whether it is set to `value`
+inline int env_int(const char* name, int fallback) { const char* e = getenv(name); return e ? atoi(e) : fallback; }
+inline bool env_is(const char* name, const char* value) { const char* e = getenv(name); return e && std::string_view(e) == value; }
+}  // namespace
+
+struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     // the class is exported (GSTRAIN_API), its implementation is not
+    GaussianTrainConfig cfg;
+    int loadItr = -1;
+    TrainingStatus status = TrainingStatus::Loading_Prepare;
+    bool training = true;
+    int device = 0;
+    // Members are destroyed in reverse order of declaration: the training stream last, both contexts after every buffer declared below
+    // them, the communicator after its stream. Keep these five first, in this order.
+    Stream stream;
+    Ctx ctx, eval_ctx;                                                       // eval_ctx: created at the first evaluation
+    Comm comm; int rank = 0, world = 1;                                      // data-parallel replicas (include/dvs_comm.h)
+    Stream comm_stream;                                                      // collectives run beside A9
+    int n = 0, W = 0, H = 0, sh_max = 3;
+    DevBuf<float> d_param[6], d_m[6], d_v[6];
+    DevBuf<float> d_param2[6], d_m2[6], d_v2[6];                             // densification writes old -> new, then the sets swap
+    DevBuf<float> d_absgrad;
+    DevBuf<float> d_grad_flat; size_t grad_floats = 0;                       // the six gradient groups live in ONE buffer: one all-reduce
+    float* d_grad[6] = {};                                                   // (slices of d_grad_flat)
+    DevBuf<float> d_mean2d;                                                  // dL/dmean2D (ADC statistic when useAbsGrad is off)
+    // Gradient exchange of the replicas. factorised (default): the geometry groups (pos, opacity, scale, rot: 44 B/splat) lead the
+    // flat buffer and are all-reduced; of the SH rows only each view's 3-float colour gradient is all-gathered (12 B/splat/view) and
+    // every replica rebuilds the summed rows with dvs_sh_grad_combine — at 8 GPUs 161 MB instead of 413 MB through each GPU's links
+    // per million splats. DVS_EXCHANGE=allreduce: one all-reduce of all 59-float rows.
+    bool factorised = true; size_t geom_floats = 0;
+    DevBuf<float> d_dcolor_local, d_dcolor_all;                              // [cap,3] / [world,n,3]
+    DevBuf<float> d_dcolor_scratch;                                          // A9's own copy of the colour gradient (the all-gather reads the early one)
+    Event ev_dcolor, ev_bwd, ev_comm;
+    Event ev_gather; std::vector<Event> ev_chunk;                            // all-gather done / A9 chunk k queued (chunked geometry all-reduce)
+    bool pipeline = false;                                                   // DVS_EXCHANGE_PIPELINE=1 (with DVS_A9_CHUNKS > 1): see trainStep
+    std::vector<Event> ev_ar;                                                // chunk k's geometry all-reduce has landed (communication stream)
+    std::vector<int> next_ci;                                                // the NEXT iteration's cameras, drawn early for the pipelined step
+    int a9_chunks = 1;                                                       // DVS_A9_CHUNKS: splat chunks of A9 whose geometry gradients leave one by one (default 1 until
+                                                                             // the chunked exchange has run on real multi-GPU hardware: ADVICE r03; equality with the unchunked
+                                                                             // exchange is asserted by tests/test_gpu_multirank.py::test_plugin_two_ranks_exchanges_agree)
+    // The training views, one entry per camera of `cams`: the image as fp32 or, when packLevel has PackF32ToU8, as 8 bits per channel
+    // (gs_train.cpp:91-96, the reference's VRAM saver: a quarter of the HBM footprint, expanded into d_target_f32 right before the
+    // loss), and the camera's mask when useMask was on at load time
+    struct View { DevBuf<float> f32; DevBuf<uint8_t> u8; DevBuf<float> mask; };
+    std::vector<View> views;
+    std::vector<dvs_camera> cams;
+    DevBuf<float> d_target_f32;
+    bool views_u8() const { return (cfg.packLevel & PackF32ToU8) != 0; }
+    const void* view_pixels(size_t ci) const { return views_u8() ? (const void*)views[ci].u8.get() : (const void*)views[ci].f32.get(); }
+    const float* view_mask(size_t ci) const { return cfg.useMask ? views[ci].mask.get() : nullptr; }   // (nullptr too when loaded without masks)
+    void store_view(DevBuf<float> image, DevBuf<float> mask);
+    std::vector<float> init_host[6];                                         // initial splats (resetGaussian, getPoints3D)
+    bool terminate = false, pruning = false;
+    int cap = 0;                                                             // array capacity in splats (cfg.capMax)
+    DevBuf<float> d_grad_accum, d_denom; DevBuf<int> d_max_radii;
+    DevBuf<uint8_t> d_action; DevBuf<uint32_t> d_offsets, d_dscratch; DevBuf<uint64_t> d_newcount;
+    DevBuf<void> d_mcmc;                                                     // dvs_mcmc_* scratch (densifyStrategy 1)
+    float extent = 1.f;                                                      // scene extent (camera spread), sets the split/clone scale
+    dvs_fwd_state fwd{};                                                     // (views into the context's arrays)
+    int vpi = 1;                                                             // views per trainStep and GPU, one multi-view pass (cfg.viewsPerIter / DVS_VIEWS_PER_ITER)
+    bool sequential_views = false;                                           // DVS_VIEWS_MODE=sequential: the same views one pass at a time, accumulating (the reference shape)
+    DevBuf<int> d_vis_radius;                                                // visibleAdam with vpi > 1: max radius over the step's views
+    DevBuf<float> d_out, d_dL, d_loss;                                       // d_loss[0..63] = (1-w) L1 partial sums, d_loss[64..127] = SSIM partial sums
+    DevBuf<float> d_ssim_maps[3];
+    float last_loss = 0.f;
+    int step = 0;
+    uint64_t cam_rng = 88172645463325252ULL;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    std::vector<float> host[6];
+    bool host_valid = false;
+    // held-out evaluation (cfg.evalHoldout / evalEvery): camera i is a test camera iff i % eval_holdout == 0. Both lists are empty when
+    // evaluation is off — the draw is then the reference's, over all cameras. The test views are rendered by a context of their own:
+    // the training context's saved forward state, pending backward rows and prepared projection are never touched by an evaluation.
+    int eval_holdout = 0, eval_every = 0;
+    std::vector<int> train_idx, test_idx;
+    int eval_views = 0;                                                      // min(n_test, 8) views per pass of eval_ctx
+    DevBuf<float> d_eval_out; DevBuf<void> d_eval_scratch; DevBuf<double> d_eval_res;
+    std::vector<double> eval_res;                                            // [n_test][4] = {mse, l1, ssim, psnr} of the last evaluation
+    double eval_mean[4] = {NAN, NAN, NAN, NAN};
+    int eval_it = -1;
+    // coarse-to-fine training (cfg.resolutionSchedule = S, cfg.numDownscales = K; both 0 here when the schedule is off): the step with
+    // `step` completed steps before it trains at level k = max(K - step / S, 0), on images of W / 2^k x H / 2^k — the stored views
+    // box-filtered by ONE dvs_downsample_views call per step into d_level_targets, the cameras those of dvs_camera_downscale. The
+    // level is a function of the step number alone (every rank derives the same one; a resume lands on the right one). Everything
+    // per pixel of the step (d_out, d_dL, the loss, the densification statistics) has the level's size; the arenas keep the full one.
+    int res_every = 0, res_levels = 0;
+    std::vector<std::vector<dvs_camera>> level_cams;                        // [k - 1][camera], k = 1..K (level 0: cams)
+    DevBuf<float> d_level_targets, d_level_masks;                           // [vpi,3,H/2,W/2] / [vpi,H/2,W/2]: room for the largest level below full size
+    int cur_level = -1;                                                      // level of the last step (-1: none yet)
+    int lw = 0, lh = 0;                                                      // image size of the last step (W x H when the schedule is off)
+    int level_first_step = 0; std::chrono::steady_clock::time_point level_t0;
+    // compact exports beside the full PLY (cfg.exportFormats / DVS_EXPORT_FORMATS / the suffix of modelPath): the packers' scratch, the
+    // packed payload on the device and its host copy. Nothing is allocated until a save exports; the buffers only grow.
+    DevBuf<void> d_export_scratch; DevBuf<uint8_t> d_export_out; size_t export_scratch_cap = 0, export_out_cap = 0;
+    std::vector<uint8_t> export_host;
+
+    ~Impl() { if (device >= 0) (void)hipSetDevice(device); }                // (the members release themselves, after this body)
+    // floats of group g on the device: the 45 higher-order SH floats live in the DVS_SHN_TILED layout (48 per splat,
+    // whole 64-splat tiles); parameters, gradients and Adam moments share it — the optimizer is element-wise.
+    size_t dev_floats_for(int g, int count) const { return g == P_SHN ? (size_t)((count + 63) / 64) * 64 * 48 : (size_t)count * kWidth[g]; }
+    size_t dev_floats(int g) const { return dev_floats_for(g, n); }
+    void upload(int g, const std::vector<float>& host_rows);
+    void alloc_params(int count, int capacity, const std::vector<float> init[6]);
+    void reset_stats() {
+        HIP_OR_THROW(hipMemsetAsync(d_grad_accum.get(), 0, (size_t)cap * 4, stream.get()));
+        HIP_OR_THROW(hipMemsetAsync(d_denom.get(), 0, (size_t)cap * 4, stream.get()));
+        HIP_OR_THROW(hipMemsetAsync(d_max_radii.get(), 0, (size_t)cap * 4, stream.get()));
+    }
+    dvs_densify_params plan_params(int it) const;
+    uint64_t plan(const dvs_densify_params& prm);
+    void apply_plan(const dvs_densify_params& prm, int new_n, bool zero_moments);
+    void densify(int it);
+    void densify_mcmc(int it);
+    void prune_light(int it);
+    void report_config() const;
+    void sync_stats();
+    const float* target_for(int ci);
+    bool mcmc() const { return cfg.densifyStrategy == 1; }
+    bool exchange_factorised() const { return comm && factorised; }
+    bool visible_adam() const { return cfg.visibleAdam && world == 1; }     // per-rank visibility would let the replicas drift apart
+    int sh_degree_at(int s) const { return cfg.progressiveTrain ? std::min(sh_max, s / 1000) : sh_max; }   // SH bands unlocked every 1000 steps
+    void setup_exchange();
+    // cameras: one xorshift stream shared by all ranks; an iteration draws world x vpi views and rank r renders views r vpi .. r vpi + vpi - 1
+    // (vpi = 1: one view per GPU and iteration, as the reference's trainStep renders one camera; vpi = 8 on one GPU: BASELINE config C4)
+    void draw_cameras(std::vector<int>& ci) {
+        ci.assign((size_t)world * vpi, 0);                  // every rank knows every rank's cameras: the SH rows are rebuilt from them
+        for (int& c : ci) {
+            cam_rng ^= cam_rng << 13; cam_rng ^= cam_rng >> 7; cam_rng ^= cam_rng << 17;
+            if (train_idx.empty()) c = cfg.singleCamera ? 0 : (int)(cam_rng % cams.size());
+            else c = train_idx[cfg.singleCamera ? 0 : (size_t)(cam_rng % train_idx.size())];     // held-out cameras are never trained on
+        }
+    }
+    void setup_split();
+    bool evaluate(bool write_json, bool force = false);
+    void run_evaluation();
+    void write_eval_json() const;
+    std::vector<dvs_camera> rank_cameras(const std::vector<int>& ci_all, int level) const {     // this rank's views of an iteration's draw, at a level
+        std::vector<dvs_camera> v((size_t)vpi);
+        for (int k = 0; k < vpi; ++k) {
+            const size_t ci = (size_t)ci_all[(size_t)rank * vpi + k];
+            v[(size_t)k] = level > 0 ? level_cams[(size_t)level - 1][ci] : cams[ci];
+        }
+        return v;
+    }
+    int level_of(int s) const { return res_every > 0 ? std::max(res_levels - s / res_every, 0) : 0; }   // s: completed steps before the step
+    void setup_levels();
+    const int* any_view_radii() {                            // max radius over the step's views (view-major fwd.radii of the multi-view pass)
+        if (!d_vis_radius) d_vis_radius.alloc((size_t)cap * sizeof(int) + 16);
+        DVS_OR_THROW(dvs_any_view_radius(stream.get(), n, vpi, fwd.radii, d_vis_radius.get()));
+        return d_vis_radius.get();
+    }
+    // ---- the phases of one trainStep ----
+    struct Step {                                                            // one iteration, carried through its phases
+        int it = 0, deg = 0;                                                 // the iteration being computed, its SH degree
+        int level = 0, div = 1, Wd = 0, Hd = 0;                              // resolution level of the step, 2^level, the level's image size
+        std::vector<int> ci_all;                                             // the iteration's cameras, [rank][local view]
+        std::vector<dvs_camera> vcams;                                       // this rank's views
+        dvs_opts opts{};
+        bool mcmc = false, absgrad = false, want_stats = false;
+        bool refine_now = false, reset_now = false, prune_now = false;
+        float lr_pos = 0.f;
+        dvs_adam_group adam[6] = {};                                         // Adam groups over the whole arrays
+        const int* adam_gate = nullptr;                                      // (render_backward) visible-only Adam: radius > 0 in the step's views
+        int chunk_per = 0, n_chunks = 0;                                     // (render_backward) > 0: the geometry gradients left behind A9 in chunks
+    };
+    Step plan_step();                                                        // decides the step; launches nothing
+    void enter_level(const Step& s);
+    void close_level();
+    void level_targets(const Step& s);
+    void loss_of_view(const Step& s, int v);
+    void render_backward(Step& s);
+    void exchange(const Step& s, bool pipelined);
+    void finish_range(const Step& s, int first, int count, const int* groups, int n_groups, const int* gate);
+    void finish_pipelined(const Step& s);
+    dvs_splats splats() const {
+        dvs_splats s{};
+        s.pos = d_param[P_POS].get(); s.sh0 = d_param[P_SH0].get(); s.shN = d_param[P_SHN].get(); s.opacity = d_param[P_OPA].get();
+        s.scale = d_param[P_SCALE].get(); s.rot = d_param[P_ROT].get(); s.n = n;
+        return s;
+    }
+    std::string model_file(int it) const { return cfg.modelPath + "_" + std::to_string(it) + ".ply"; }
+    bool model_path_ends(const char* suffix) const {
+        const size_t k = strlen(suffix);
+        return cfg.modelPath.size() >= k && cfg.modelPath.compare(cfg.modelPath.size() - k, k, suffix) == 0;
+    }
+    // EXPORT_* bits of the compact formats a save writes; decided at every use, since the editor sets modelPath after construction
+    enum { EXPORT_COMPRESSED = 1, EXPORT_SPLAT = 2 };
+    int suffix_formats() const { return model_path_ends(".compressed.ply") ? EXPORT_COMPRESSED : model_path_ends(".splat") ? EXPORT_SPLAT : 0; }
+    int asked_formats() const { return env_int("DVS_EXPORT_FORMATS", cfg.exportFormats); }   // 0: the suffix of modelPath decides
+    int export_formats() const { return (asked_formats() ? asked_formats() : suffix_formats()) & (EXPORT_COMPRESSED | EXPORT_SPLAT); }
+    void export_model(int format);
+    void fetch_host();
+    // what the two loaders share: the context and every per-step buffer (W, H, sh_max set by the caller) ...
+    void create_context(int count, int capacity, const std::vector<float> init[6]);
+    // ... and, once cams and the views are in place: split, levels, extent, resume or the loader's fresh initialisation,
+    // upload, report_config, the loader's own verbose line (told whether the run resumed), exchange set-up
+    void finish_load(const std::function<void(std::vector<float> (&)[6])>& fresh_init, const char* fresh_name,
+                     const std::function<void(bool)>& describe);
+    bool load_synthetic(const std::string& spec_str);
+    bool load_dataset(const std::string& path);
+};

@@ -1,0 +1,164 @@
+// trainer_output.cpp — what the trainer reports and writes: the configuration lines, held-out evaluation, host copies, compact exports.
+#include "trainer.hpp"
+
+// One line per decision: which GaussianTrainConfig fields this build honours and which it ignores (gs_train.cpp:50-103 sets them all).
+void GaussianTrainerScene::Impl::report_config() const {
+    if (rank != 0) return;
+    static const char* strat[3] = {"ADC (clone / split / prune)", "MCMC (relocation + growth)", "ADC+ (ADC on abs-grad statistics with revised opacity)"};
+    logf_("config: densifyStrategy %d = %s; pruneStrategy %d (%s) every %d steps after refineStopIter %d; capMax %d; packLevel %d (%s%s); "
+          "useMask %d; useAbsGrad %d; mipAntiliased %d; visibleAdam %d; singleCamera %d; progressiveTrain %d; world %d",
+          cfg.densifyStrategy, strat[std::min(2, std::max(0, cfg.densifyStrategy))], cfg.pruneStrategy,
+          cfg.pruneStrategy > 0 ? "light prune: opacity < pruneOpacity or scale > pruneScale3d" : "off", cfg.pruneInterval, cfg.refineStopIter,
+          cfg.capMax, cfg.packLevel, views_u8() ? "PackF32ToU8: 8-bit training views" : "fp32 training views",
+          (cfg.packLevel & PackTileID) ? ", PackTileID: always on here (the tile sort's keys are tile ids inside a view, written as 16-bit words while a view has <= 65536 tiles)" : "",
+          (int)cfg.useMask, (int)cfg.useAbsGrad, (int)cfg.mipAntiliased, (int)cfg.visibleAdam, (int)cfg.singleCamera, (int)cfg.progressiveTrain, world);
+    if (!test_idx.empty()) {
+        std::string idx;
+        for (int c : test_idx) idx += " " + std::to_string(c);
+        logf_("config: evaluation: %zu of %zu cameras held out of training (evalHoldout %d: cameras%s), scored at every save%s", test_idx.size(),
+              cams.size(), eval_holdout, idx.c_str(), eval_every > 0 ? (" and every " + std::to_string(eval_every) + " steps").c_str() : "");
+    }
+    if (res_every > 0)
+        logf_("config: resolutionSchedule %d, numDownscales %d: coarse-to-fine training, the step after s completed ones renders 1/2^max(%d - s/%d, 0) of "
+              "%dx%d (targets box-filtered per step, cameras of dvs_camera_downscale); full resolution from iteration %d; evaluation always at full size",
+              res_every, res_levels, res_levels, res_every, W, H, res_levels * res_every + 1);
+    if (const int fmts = export_formats())
+        logf_("config: exportFormats %d: every save also writes%s%s beside the full PLY, packed on the device%s", fmts,
+              (fmts & EXPORT_COMPRESSED) ? " <modelPath>_<it>.compressed.ply" : "", (fmts & EXPORT_SPLAT) ? " <modelPath>_<it>.splat" : "",
+              asked_formats() == 0 ? " (turned on by the suffix of modelPath)" : "");
+    std::string ign;
+    if (model_path_ends(".spz")) ign += " modelPath suffix .spz(spz export: the full PLY is written)";
+    if (cfg.modelType != 0) ign += " modelType(only 3DGS)";
+    if (cfg.cullSH) ign += " cullSH";
+    if (cfg.pixelGradScale) ign += " pixelGradScale";
+    if (cfg.bestQuality) ign += " bestQuality";
+    if (cfg.normalConsistencyLoss) ign += " normalConsistencyLoss(2DGS)";
+    if (cfg.enableBg) ign += " enableBg";
+    if (cfg.enableFocusRegion) ign += " enableFocusRegion";
+    if (cfg.exportMesh) ign += " exportMesh";
+    if (cfg.outputSparsePoints) ign += " outputSparsePoints";
+    if (cfg.maxImageCount) ign += " maxImageCount";
+    if (!cfg.cameraPosePath.empty() || !cfg.pointCloudPath.empty()) ign += " cameraPosePath/pointCloudPath(dataset ingestion)";
+    if (cfg.visibleAdam && world > 1) ign += " visibleAdam(off with WORLD_SIZE > 1: the visible set differs per rank)";
+    if (!ign.empty()) logf_("config: IGNORED by this build:%s", ign.c_str());
+}
+
+// Held-out evaluation, on the training stream: the test cameras rendered from the current parameters at the full SH degree (what a
+// viewer shows from the saved PLY), min(n_test, 8) views per multi-view pass of a SEPARATE context, each pass scored by one
+// dvs_image_metrics_views call against the stored targets (8-bit ones as they are, the camera's mask when useMask), then ONE copy of
+// the [n_test][4] doubles to the host. Only rank 0 evaluates (the replicas are identical). -> false when evaluation is off.
+// A save right after the step that was just scored (evalEvery divides the iteration) writes that result: the parameters are the same.
+bool GaussianTrainerScene::Impl::evaluate(bool write_json, bool force) {
+    if (test_idx.empty() || rank != 0 || !ctx) return false;
+    HIP_OR_THROW(hipSetDevice(device));
+    if (force || eval_it != step) run_evaluation();
+    if (write_json) write_eval_json();
+    return true;
+}
+void GaussianTrainerScene::Impl::run_evaluation() {
+    const int nt = (int)test_idx.size();
+    const size_t img = 3 * (size_t)W * H;
+    if (!eval_ctx) {
+        eval_views = std::min(nt, 8);
+        eval_ctx.reset(dvs_create_views(device, (size_t)cap, W, H, eval_views));
+        if (!eval_ctx) throw std::runtime_error(std::string("dvs_create_views (evaluation): ") + dvs_last_error());
+        d_eval_out.alloc((size_t)eval_views * img * sizeof(float));
+        d_eval_scratch.alloc(dvs_image_metrics_scratch_bytes(W, H, eval_views));
+        d_eval_res.alloc((size_t)nt * 4 * sizeof(double));
+    }
+    dvs_opts opts{};
+    opts.sh_degree = sh_max; opts.antialias = cfg.mipAntiliased ? 1 : 0; opts.shn_layout = DVS_SHN_TILED; opts.tile_bounds = DVS_TILES_CANONICAL;
+    const dvs_splats sp = splats();
+    for (int first = 0; first < nt; first += eval_views) {
+        const int nb = std::min(eval_views, nt - first);
+        std::vector<dvs_camera> bc((size_t)nb);
+        dvs_metrics_view mv[DVS_METRICS_MAX_VIEWS] = {};
+        for (int k = 0; k < nb; ++k) {
+            const size_t ci = (size_t)test_idx[(size_t)(first + k)];
+            bc[(size_t)k] = cams[ci];
+            mv[k].img = d_eval_out.get() + (size_t)k * img;
+            mv[k].target = view_pixels(ci);
+            mv[k].mask = view_mask(ci);
+        }
+        DVS_OR_THROW(dvs_raster_forward_views(eval_ctx.get(), stream.get(), &sp, bc.data(), nb, &opts, d_eval_out.get()));
+        DVS_OR_THROW(dvs_image_metrics_views(stream.get(), mv, nb, W, H, views_u8() ? 1 : 0, d_eval_scratch.get(), d_eval_res.get() + (size_t)first * 4));
+    }
+    eval_res.assign((size_t)nt * 4, 0.0);
+    HIP_OR_THROW(hipMemcpyAsync(eval_res.data(), d_eval_res.get(), eval_res.size() * sizeof(double), hipMemcpyDeviceToHost, stream.get()));
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    for (int k = 0; k < 4; ++k) {
+        double a = 0.0;
+        for (int v = 0; v < nt; ++v) a += eval_res[(size_t)v * 4 + k];
+        eval_mean[k] = a / nt;
+    }
+    eval_it = step;
+    logf_("eval @%d: %d views, PSNR %.17g dB, SSIM %.17g, L1 %.17g", step, nt, eval_mean[3], eval_mean[2], eval_mean[1]);
+}
+// <modelPath>_<it>_eval.json: the last evaluation, every double with 17 significant digits (they read back bit for bit)
+void GaussianTrainerScene::Impl::write_eval_json() const {
+    const int nt = (int)test_idx.size();
+    const std::string file = cfg.modelPath + "_" + std::to_string(step) + "_eval.json";
+    FILE* f = fopen(file.c_str(), "w");
+    if (!f) { logf_("evaluation: cannot write %s", file.c_str()); return; }
+    fprintf(f, "{\n  \"iteration\": %d,\n  \"n_splats\": %d,\n  \"sh_degree\": %d,\n  \"holdout\": %d,\n  \"views\": [\n", step, n, sh_max, eval_holdout);
+    for (int v = 0; v < nt; ++v) {
+        const double* r = &eval_res[(size_t)v * 4];
+        fprintf(f, "    {\"camera\": %d, \"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}%s\n", test_idx[(size_t)v], r[3], r[2], r[1], r[0],
+                v + 1 < nt ? "," : "");
+    }
+    fprintf(f, "  ],\n  \"mean\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}\n}\n", eval_mean[3], eval_mean[2], eval_mean[1], eval_mean[0]);
+    fclose(f);
+}
+
+void GaussianTrainerScene::Impl::fetch_host() {
+    if (host_valid) return;
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    for (int g = 0; g < 6; ++g) {
+        host[g].resize((size_t)n * kWidth[g]);             // host copies are always in the reference layout (update_from_cpu)
+        DevBuf<float> rows;                                 // (shN: back in the reference layout first)
+        if (g == P_SHN) {
+            rows.alloc(host[g].size() * sizeof(float) + 4);
+            DVS_OR_THROW(dvs_shn_relayout(ctx.get(), stream.get(), n, d_param[g].get(), rows.get(), 0));
+            HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+        }
+        HIP_OR_THROW(hipMemcpy(host[g].data(), rows ? rows.get() : d_param[g].get(), host[g].size() * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    host_valid = true;
+}
+
+// One compact export of the current model: packed on the training stream from the device arrays (shN is not read, so its tiled layout
+// does not matter), the packed payload alone copied to the host and written to <modelPath>_<step>.compressed.ply / .splat.
+void GaussianTrainerScene::Impl::export_model(int format) {
+    const auto t_start = std::chrono::steady_clock::now();
+    const bool compressed = format == EXPORT_COMPRESSED;
+    const size_t n_chunks = ((size_t)n + 255) / 256;
+    const size_t chunk_bytes = n_chunks * 12 * sizeof(float);              // (a multiple of 16: the vertex records follow on a 16-byte boundary)
+    const size_t bytes = compressed ? chunk_bytes + (size_t)n * 16 : (size_t)n * 32;
+    const auto grow = [](auto& buf, size_t& buf_cap, size_t need) {         // (the capacity is 0 while the buffer is being replaced)
+        if (need > buf_cap) { buf_cap = 0; buf.alloc(need); buf_cap = need; }
+    };
+    grow(d_export_out, export_out_cap, bytes);
+    if (export_host.size() < bytes) export_host.resize(bytes);
+    const float *pos = d_param[P_POS].get(), *sh0 = d_param[P_SH0].get(), *opa = d_param[P_OPA].get(), *scale = d_param[P_SCALE].get(), *rot = d_param[P_ROT].get();
+    uint8_t* const out = d_export_out.get();
+    int status;
+    if (compressed) {
+        grow(d_export_scratch, export_scratch_cap, dvs_pack_scratch_bytes(n));
+        status = dvs_pack_compressed(stream.get(), n, pos, sh0, opa, scale, rot, d_export_scratch.get(), (float*)out, (uint32_t*)(out + chunk_bytes), nullptr);
+    } else {
+        status = dvs_pack_splat32(stream.get(), n, pos, sh0, opa, scale, rot, out);
+    }
+    if (status != DVS_OK) throw std::runtime_error(std::string(compressed ? "dvs_pack_compressed" : "dvs_pack_splat32") + ": status " + std::to_string(status));
+    HIP_OR_THROW(hipMemcpyAsync(export_host.data(), out, bytes, hipMemcpyDeviceToHost, stream.get()));
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    const std::string file = cfg.modelPath + "_" + std::to_string(step) + (compressed ? ".compressed.ply" : ".splat");
+    std::string err;
+    const bool ok = compressed ? gsply::write_compressed_ply(file, (size_t)n, (const float*)export_host.data(),
+                                                             (const uint32_t*)(export_host.data() + chunk_bytes), cfg.mipAntiliased, &err)
+                               : gsply::write_splat(file, (size_t)n, export_host.data(), &err);
+    if (!ok) { logf_("export @%d: %s", step, err.c_str()); return; }
+    std::error_code ec;
+    const auto file_bytes = std::filesystem::file_size(file, ec);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    logf_("export @%d: %s %d splats, %llu bytes, %.2f ms", step, compressed ? "compressed.ply" : "splat", n, (unsigned long long)(ec ? bytes : file_bytes), ms);
+}

@@ -1,0 +1,113 @@
+// trainer_refine.cpp — what changes the number of splats between two iterations: ADC / ADC+ densification, MCMC relocation, light prune.
+#include "trainer.hpp"
+
+// data parallel: the densification statistics are per-view sums / maxima — make them global before a refinement decision
+void GaussianTrainerScene::Impl::sync_stats() {
+    if (!comm) return;
+    DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm.get(), stream.get(), d_grad_accum.get(), (size_t)n));
+    DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm.get(), stream.get(), d_denom.get(), (size_t)n));
+    DVS_OR_THROW(dvs_comm_all_reduce_max_i32(comm.get(), stream.get(), d_max_radii.get(), (size_t)n));
+}
+
+// the plan parameters densify() and prune_light() share; everything else starts out zero (no size limit, plain opacity of the copies)
+dvs_densify_params GaussianTrainerScene::Impl::plan_params(int it) const {
+    dvs_densify_params prm{};
+    prm.scale_threshold = 0.01f * extent;                       // percent_dense x extent
+    prm.cap_max = 0; prm.seed = (uint32_t)it; prm.shn_layout = DVS_SHN_TILED;   // no kernel cap: densify() re-plans prune-only over capMax
+    return prm;
+}
+
+// plans (d_action, d_offsets) on the statistics and waits for the count of splats the plan leaves
+uint64_t GaussianTrainerScene::Impl::plan(const dvs_densify_params& prm) {
+    uint64_t new_n = 0;
+    DVS_OR_THROW(dvs_densify_plan(stream.get(), n, d_param[P_OPA].get(), d_param[P_SCALE].get(), d_grad_accum.get(), d_denom.get(), d_max_radii.get(),
+                                  &prm, d_action.get(), d_offsets.get(), d_dscratch.get(), d_newcount.get()));
+    HIP_OR_THROW(hipMemcpyAsync(&new_n, d_newcount.get(), 8, hipMemcpyDeviceToHost, stream.get()));
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    return new_n;
+}
+
+// applies the plan to the parameter, m and v sets (old -> new) and swaps the sets. The SH tile pads of every new set are zeroed
+// first; with zero_moments (densify) the whole new m and v groups are
+void GaussianTrainerScene::Impl::apply_plan(const dvs_densify_params& prm, int new_n, bool zero_moments) {
+    for (int set = 0; set < 3; ++set) {
+        DevBuf<float>* src = set == 0 ? d_param : (set == 1 ? d_m : d_v);
+        DevBuf<float>* dst = set == 0 ? d_param2 : (set == 1 ? d_m2 : d_v2);
+        const float* s6[6]; float* d6[6];
+        for (int g = 0; g < 6; ++g) { s6[g] = src[g].get(); d6[g] = dst[g].get(); }
+        for (int g = 0; g < 6; ++g)
+            if (g == P_SHN || (set > 0 && zero_moments)) HIP_OR_THROW(hipMemsetAsync(d6[g], 0, dev_floats_for(g, new_n) * sizeof(float), stream.get()));
+        DVS_OR_THROW(dvs_densify_apply(stream.get(), n, d_action.get(), d_offsets.get(), &prm, set == 0 ? 0 : 1, s6, d6, new_n));
+        for (int g = 0; g < 6; ++g) std::swap(src[g], dst[g]);               // (the owners: what was written is now the live set)
+    }
+}
+
+// densifyStrategy 1 (MCMC): dead splats are relocated onto live ones drawn ~ opacity, then the model grows by 5 % up to the cap.
+// In place: no second buffer set, no host round trip.
+void GaussianTrainerScene::Impl::densify_mcmc(int it) {
+    dvs_mcmc_sets sets{};
+    for (int g = 0; g < 6; ++g) { sets.param[g] = d_param[g].get(); sets.m[g] = d_m[g].get(); sets.v[g] = d_v[g].get(); }
+    DVS_OR_THROW(dvs_mcmc_relocate(stream.get(), n, &sets, cfg.min_opacity, 2u * (uint32_t)it, DVS_SHN_TILED, d_mcmc.get(), cap, nullptr));
+    const int target = std::min(cap, (int)(1.05 * (double)n));
+    const int n_new = target - n;
+    if (n_new > 0) {
+        DVS_OR_THROW(dvs_mcmc_grow(stream.get(), n, n_new, &sets, cfg.min_opacity, 2u * (uint32_t)it + 1u, DVS_SHN_TILED, d_mcmc.get(), cap));
+        if (cfg.verbose) logf_("mcmc @%d: %d -> %d splats", it, n, n + n_new);
+        n += n_new;
+        HIP_OR_THROW(hipMemsetAsync(d_grad[P_SHN], 0, dev_floats_for(P_SHN, cap) * sizeof(float), stream.get()));   // pad lanes of the new last tile
+    }
+    host_valid = false;
+}
+
+// clone / split / prune between two iterations (densifyStrategy 0 ADC; 2 "ADC+" is served by the same rule)
+void GaussianTrainerScene::Impl::densify(int it) {
+    sync_stats();
+    dvs_densify_params prm = plan_params(it);
+    prm.grad_threshold = cfg.growGrad2d;
+    prm.min_opacity = cfg.min_opacity;
+    const bool after_reset = it > cfg.resetAlphaEvery;
+    prm.max_world_scale = after_reset ? cfg.pruneScale3d * extent : 0.f;                     // `pruneScale3d` (fraction of the scene extent)
+    prm.max_screen_radius = after_reset && it < cfg.refineScale2dStopIter                    // `pruneScale2d` (fraction of the image size)
+                                ? std::max(1, (int)(cfg.pruneScale2d * (float)std::max(lw, lh))) : 0;   // (max_radii is in pixels of the level)
+    prm.revised_opacity = (cfg.revisedOpacity || cfg.densifyStrategy == 2) ? 1 : 0;      // ADC+ always uses the revised opacity of the copies
+    uint64_t new_n = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        new_n = plan(prm);
+        if (new_n <= (uint64_t)cap) break;
+        prm.grad_threshold = 3.0e38f;                            // at the cap: prune only, no growth this round
+    }
+    if (new_n == 0 || new_n > (uint64_t)cap) { reset_stats(); return; }
+    apply_plan(prm, (int)new_n, true);
+    if (cfg.verbose) {
+        logf_("densify @%d: %d -> %llu splats", it, n, (unsigned long long)new_n);
+        uint64_t cap_ = 0, grows_ = 0, lastT_ = 0, over_ = 0;        // the rasterizer's instance arena at this point (HBM pressure of big scenes)
+        if (dvs_get_arena_info(ctx.get(), &cap_, &grows_, &lastT_, &over_) == DVS_OK)
+            logf_("raster @%d: T = %llu tile instances in the last pass, instance arena %llu (enlarged %llu times), overflowed forwards %llu",
+                  it, (unsigned long long)lastT_, (unsigned long long)cap_, (unsigned long long)grows_, (unsigned long long)over_);
+    }
+    n = (int)new_n;
+    HIP_OR_THROW(hipMemsetAsync(d_grad[P_SHN], 0, dev_floats_for(P_SHN, cap) * sizeof(float), stream.get()));   // pad lanes of the new last tile
+    reset_stats();
+    host_valid = false;
+}
+
+// pruneStrategy > 0 ("Light Gaussian Prune" in the reference's log, screenshots/cli_example.png): after refinement has stopped, every
+// pruneInterval steps splats that became transparent (opacity < pruneOpacity) or oversized (scale > pruneScale3d x extent) are removed
+// and the arrays compacted; no growth. Runs replicated (deterministic) on every rank.
+void GaussianTrainerScene::Impl::prune_light(int it) {
+    pruning = true;
+    dvs_densify_params prm = plan_params(it);
+    prm.grad_threshold = 3.0e38f;                               // never clone / split
+    prm.min_opacity = std::max(cfg.pruneOpacity, cfg.min_opacity);       // --minOpacity is the only opacity threshold the CLI exposes
+    prm.max_world_scale = cfg.pruneScale3d * extent;
+    reset_stats();
+    const uint64_t new_n = plan(prm);
+    if (new_n > 0 && new_n < (uint64_t)n) {
+        apply_plan(prm, (int)new_n, false);
+        if (cfg.verbose && rank == 0) logf_("light prune @%d: %d -> %llu splats", it, n, (unsigned long long)new_n);
+        n = (int)new_n;
+        HIP_OR_THROW(hipMemsetAsync(d_grad_flat.get(), 0, grad_floats * sizeof(float), stream.get()));
+        host_valid = false;
+    }
+    pruning = false;
+}

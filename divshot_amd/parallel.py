@@ -318,7 +318,7 @@ class ShardedAdam:
 # ---- the product's exchange: include/dvs_comm.h (librccl behind plain C), driven with the plugin's stream / event choreography ---------
 class DvsComm:
     """ctypes handle of a dvs_comm communicator (include/dvs_comm.h): the SAME C entry points libgstrain.so's train_step() calls
-    (divshot_amd/gstrain/gstrain.cpp) — RCCL over xGMI, or, with DVS_COMM_BACKEND=tcp, the host-staged test backend. rank / world /
+    (divshot_amd/gstrain/trainer_step.cpp) — RCCL over xGMI, or, with DVS_COMM_BACKEND=tcp, the host-staged test backend. rank / world /
     rendezvous come from the launcher's environment (RANK, WORLD_SIZE, MASTER_ADDR, MASTER_PORT) unless given."""
 
     def __init__(self, device_index, rank=-1, world=0, master_addr=None, master_port=0):
@@ -386,7 +386,7 @@ class DvsComm:
 
 class DvsCommExchange:
     """The factorised exchange of FactorisedExchange, executed by the PRODUCT's communication layer with the product's choreography
-    (gstrain.cpp train_step): every collective goes through include/dvs_comm.h on a dedicated communication stream,
+    (gstrain/trainer_step.cpp render_backward / exchange): every collective goes through include/dvs_comm.h on a dedicated communication stream,
     in the same order on every rank —
       * the colour gradients of all local views leave in ONE all-gather as soon as dvs_raster_backward_dcolor has produced them
         (under A9),

@@ -1,6 +1,6 @@
 """`train_step` at step level with the options the reference CLI turns on by default, and the other host flags of the step: progressive
 SH (--progressTrain 1), 8-bit training views (--packLevel 1), --useMask, --mipAntiliased, the opacity reset inside the step, the light
-prune, ADC on the statistic of --absgrad 0, and the ADC refinement after an opacity reset (both size limits on). The kernel-level suites pin the ops; these pin how gstrain.cpp wires them: on which step
+prune, ADC on the statistic of --absgrad 0, and the ADC refinement after an opacity reset (both size limits on). The kernel-level suites pin the ops; these pin how the trainer (gstrain/trainer_step.cpp, trainer_refine.cpp) wires them: on which step
 they run, with which arguments, and what state they leave for the next Adam step.
 
 CPU part (not marked gpu): the restatement's own pieces (pack formula, mask, degree schedule), and for every GPU case below
@@ -388,7 +388,7 @@ def _adc_limits(r, W):
     """the flags of the post-reset refinement case, from the restated state after its ten steps: growGrad2d at the median of the
     abs-grad statistic, pruneScale3d at the 0.9 quantile of max exp(scale) / extent, pruneScale2d so that the radius limit is the 0.97
     quantile of max_radii (in the middle between two pixels) -> (grow, pruneScale3d, pruneScale2d, max_world_scale, max_screen_radius),
-    the last two as gstrain.cpp densify() computes them in float32 from the flags"""
+    the last two as trainer_refine.cpp densify() computes them in float32 from the flags"""
     f = np.float32
     avg = r.grad_accum / np.maximum(r.denom, 1)
     grow = float(f(np.median(avg[r.denom > 0])))

@@ -11,7 +11,7 @@ this build's plugin defines (divshot_amd/gstrain/gstrain.cpp trainStep) from ind
   (sqrt((|gx| W/2)^2 + (|gy| H/2)^2) per visible splat, denominator + 1), and the statistic of `--absgrad 0`, the same expression on the
   signed dL/dmean2D.
 
-Options of the step, each off by default (the host flags of gstrain.cpp plan_step / loss_of_view / trainStep): start_step (a resume
+Options of the step, each off by default (the host flags of gstrain/trainer_step.cpp plan_step / loss_of_view and gstrain.cpp trainStep): start_step (a resume
 through --load_itr), progressive (SH degree min(sh, step // 1000)), antialias, pack_u8 (8-bit training views), mask (the synthetic
 inscribed-ellipse mask on the photometric gradient), reset_alpha_every (the opacity reset inside the step) and the light prune
 (prune_decisions / apply_prune).
@@ -91,7 +91,7 @@ def pack_unpack_u8(t):
 
 
 def ellipse_mask(W, H):
-    """--useMask on a synthetic scene (gstrain.cpp load_synthetic): 1 inside the ellipse inscribed in the image, 0 outside; pixel
+    """--useMask on a synthetic scene (gstrain/trainer_load.cpp load_synthetic): 1 inside the ellipse inscribed in the image, 0 outside; pixel
     centres u = (x + 0.5) / W * 2 - 1, v likewise, u^2 + v^2 <= 1, evaluated in float32 as the plugin does. -> [H, W] float32"""
     f = np.float32
     u = (np.arange(W, dtype=np.float32) + f(0.5)) / f(W) * f(2.0) - f(1.0)
@@ -100,7 +100,7 @@ def ellipse_mask(W, H):
 
 
 def sh_degree_at(step, sh_degree, progressive=True):
-    """the SH degree a step trains at: one more band every 1000 steps with --progressTrain 1 (gstrain.cpp sh_degree_at)"""
+    """the SH degree a step trains at: one more band every 1000 steps with --progressTrain 1 (gstrain/trainer.hpp sh_degree_at)"""
     return min(sh_degree, step // 1000) if progressive else sh_degree
 
 
@@ -111,7 +111,7 @@ def shn_active_chunks(deg):
 
 
 def scene_extent(cams):
-    """1.1 x the largest distance of a camera centre from their mean; tiny rigs fall back to 5 (gstrain.cpp load_synthetic)."""
+    """1.1 x the largest distance of a camera centre from their mean; tiny rigs fall back to 5 (gstrain/trainer_load.cpp finish_load)."""
     c = np.array([[cam.campos[0], cam.campos[1], cam.campos[2]] for cam in cams], np.float64)
     far = np.sqrt(((c - c.mean(0)) ** 2).sum(1)).max()
     return float(np.float32(1.1 * far)) if far > 1e-3 else 5.0
@@ -122,7 +122,7 @@ class TrainStepRef:
                  ssim_weight=0.0, mcmc_reg=None, start_step=0, progressive=False, antialias=False, pack_u8=False, mask=False,
                  reset_alpha_every=0):
         """ssim_weight: w of L = (1 - w) mean|x - y| + w (1 - mean SSIM) (--ssim, main.cpp:24: 0.2; 0 = L1 only).
-        mcmc_reg: (opacity_reg, scale_reg) of densifyStrategy 1 (gstrain.cpp: 0.01, 0.01), added to the summed gradients once per step.
+        mcmc_reg: (opacity_reg, scale_reg) of densifyStrategy 1 (gstrain/trainer_step.cpp finish_range: 0.01, 0.01), added to the summed gradients once per step.
         start_step: a resume through --load_itr — the step number (Adam bias correction, position-rate schedule, SH degree) starts there,
         the moments at zero and the camera stream at its seed. progressive: --progressTrain 1. antialias: --mipAntiliased 1.
         pack_u8: --packLevel 1, the targets go through 8 bits. mask: --useMask 1, the photometric gradient (not the reported loss) is
@@ -229,7 +229,7 @@ class TrainStepRef:
             self.V["opacity"][:] = 0
         return G
 
-    # ---- light prune of gstrain.cpp prune_light() (pruneStrategy > 0, after refinement has stopped) ----------------------------------
+    # ---- light prune of gstrain/trainer_refine.cpp prune_light() (pruneStrategy > 0, after refinement has stopped) ----------------------------------
     def prune_decisions(self, prune_opacity=0.005, min_opacity=0.005, prune_scale3d=0.1):
         """-> (prune [n] bool, margin [n]): a splat goes when sigmoid(opacity) < max(pruneOpacity, min_opacity) or max exp(scale) >
         pruneScale3d x extent; margin = relative distance to the nearer threshold."""
@@ -247,7 +247,7 @@ class TrainStepRef:
         self.grad_accum, self.denom, self.max_radii = (np.zeros(int(keep.sum()), a.dtype) for a in (self.grad_accum, self.denom, self.max_radii))
         self.grad_accum_mean2d = np.zeros(int(keep.sum()), self.dt)
 
-    # ---- ADC refinement decision of gstrain.cpp densify() / densify.hip d_action --------------------------------------------------------
+    # ---- ADC refinement decision of gstrain/trainer_refine.cpp densify() / densify.hip d_action --------------------------------------------------------
     def adc_actions(self, grow_grad2d, min_opacity=0.005, stat="absgrad", max_world_scale=0.0, max_screen_radius=0):
         """0 keep, 1 clone, 2 split, 3 prune — and the margin of each decision (relative distance to its nearest threshold).
         stat: "absgrad" (--absgrad 1) or "mean2d" (--absgrad 0: hypot(gx W/2, gy H/2) of the signed dL/dmean2D).
