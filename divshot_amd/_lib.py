@@ -173,11 +173,20 @@ _PROTOS = {
                                        C.c_int32]),
 }
 # include/dvs_export.h: the model export packers (a table of their own: _PROTOS is the list of the four headers above)
+class SpzLayout(C.Structure):          # dvs_spz_layout: positions, alphas, colors, scales, rotations, sh
+    _fields_ = [("off", C.c_uint64 * 6), ("bytes", C.c_uint64 * 6), ("total", C.c_uint64)]
+
+
 _EXPORT_PROTOS = {
     "dvs_pack_scratch_bytes": (C.c_size_t, [C.c_int]),
     "dvs_pack_compressed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
     "dvs_pack_splat32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_spz_layout_for": (C.c_int, [C.c_int, C.c_int, C.POINTER(SpzLayout)]),
+    "dvs_pack_spz": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
+    "dvs_unpack_spz": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                 C.c_void_p]),
 }
 # include/dvs_init.h: splat initialisation from a sparse point cloud
 _INIT_PROTOS = {

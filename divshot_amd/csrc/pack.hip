@@ -1,6 +1,7 @@
 // pack.hip — model export packers (include/dvs_export.h): the device-resident splats into the payload of DIVSHOT's chunked, quantised
 // .compressed.ply (external/tinygsplat/tiny_gsplat.cpp:293-396, tiny_gsplat.hpp:342-468) and into 32-byte .splat records
-// (tiny_gsplat.cpp:243-291). A per-splat streaming job over 56 B of input per splat; shN is never read.
+// (tiny_gsplat.cpp:243-291): a per-splat streaming job over 56 B of input per splat, shN is never read; and into / out of the six byte
+// sections of .spz version 3 (external/spz/src/load-spz.cc), which also carries the 45 higher-order SH floats.
 //   (a) k_pack_bounds / k_pack_bounds_final: min / max of pos per axis. Every workgroup writes its partial result to its own slot, one
 //       small workgroup combines the slots: no float atomics, the result does not depend on the schedule.
 //   (b) k_pack_morton: one 30-bit Morton key (10 bits per axis over the model's box) and the splat index per splat.
@@ -11,7 +12,8 @@
 //       calcMinMax seeds them with p[start] instead of p[indices[start]], tiny_gsplat.hpp:332, which can only widen the box: not
 //       reproduced); a lane leaves ONE 16-byte record, so a wavefront stores 1 KiB contiguously; lanes 0-11 write the chunk row.
 //   (e) k_pack_splat32: one 32-byte record per splat in the model's order, two 16-byte stores per lane.
-// Results are defined bit for bit (tests/compressed_ply_ref.py restates them in numpy): compiled without contraction (EXACT), IEEE
+//   (f) k_pack_spz / k_unpack_spz: one wavefront per 64-splat tile, the sections' slices staged in LDS (see there).
+// Results are defined bit for bit (tests/compressed_ply_ref.py and tests/spz_ref.py restate them in numpy): compiled without contraction (EXACT), IEEE
 // division and square root, min / max are order-independent. No atomics, no inline assembly, plain vector stores.
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -202,6 +204,192 @@ k_pack_splat32(int n, const float* __restrict__ pos, const float* __restrict__ s
     out[2 * i + 1] = b;
 }
 
+// ---- (f) .spz, version 3 (external/spz/src/load-spz.cc packGaussians / unpackGaussians) ---------------------------------------------
+// One wavefront owns 64 consecutive splats = one tile of DVS_SHN_TILED; a workgroup of four waves has one LDS image per wave holding the
+// tile's slice of the sh, positions, colors and scales sections (64 * (3 DIM + 9 + 3 + 3) bytes: 3840 B at degree 3, 15 KiB per
+// workgroup). A lane quantises its own splat into the image byte by byte; the wave then moves each slice as 16-byte words (64 * 9,
+// 64 * 3 and 64 * 3 DIM are multiples of 16 and every section starts on a 16-byte boundary, so a whole tile's slice is aligned in every
+// section). The last, partial tile goes byte by byte. alphas (one byte per lane, 64 contiguous bytes per wave) and rotations (one dword
+// per lane, 256 contiguous bytes) are whole records per lane and are stored directly. DVS_SHN_ROWS input is read as dwords, lane after
+// lane through the tile's rows, into the same image. The decoder is the mirror image.
+struct SpzOff { uint64_t a[6]; };                          // byte offsets of positions, alphas, colors, scales, rotations, sh
+constexpr int SPZ_POS = 64 * 9, SPZ_VEC3 = 64 * 3;         // bytes of one tile in positions / in colors and scales
+template <int DIM> constexpr int spz_image_bytes() { return 64 * 3 * DIM + SPZ_POS + 2 * SPZ_VEC3; }
+
+__device__ __forceinline__ void spz_store_slice(const uint8_t* img, uint8_t* dst, int tile_bytes, int valid_bytes, int lane) {
+    if (valid_bytes == tile_bytes) {
+        for (int k = lane; k < tile_bytes / 16; k += 64) reinterpret_cast<uint4*>(dst)[k] = reinterpret_cast<const uint4*>(img)[k];
+    } else {
+        for (int b = lane; b < valid_bytes; b += 64) dst[b] = img[b];
+    }
+}
+__device__ __forceinline__ void spz_load_slice(uint8_t* img, const uint8_t* src, int tile_bytes, int valid_bytes, int lane) {
+    if (valid_bytes == tile_bytes) {
+        for (int k = lane; k < tile_bytes / 16; k += 64) reinterpret_cast<uint4*>(img)[k] = reinterpret_cast<const uint4*>(src)[k];
+    } else {
+        for (int b = lane; b < valid_bytes; b += 64) img[b] = src[b];
+    }
+}
+
+// toUint8 (load-spz.cc:74): round half away from zero, clamp; a NaN gives 0
+__device__ __forceinline__ uint32_t spz_u8(float v) { return (uint32_t)fminf(fmaxf(roundf(v), 0.0f), 255.0f); }
+// 24-bit fixed point with 12 fractional bits, saturated; a position that is not finite gives 0
+__device__ __forceinline__ uint32_t spz_fixed24(float p) {
+    if (!(fabsf(p) < __builtin_inff())) return 0u;
+    const float f = fminf(fmaxf(roundf(p * 4096.0f), -8388608.0f), 8388607.0f);
+    return (uint32_t)(int32_t)f & 0xFFFFFFu;
+}
+// quantizeSH (load-spz.cc:77-81) with bucket size B; a NaN gives the byte of 0
+template <int B> __device__ __forceinline__ uint8_t spz_sh(float x) {
+    float r = roundf(x * 128.0f);
+    r = r == r ? fminf(fmaxf(r, -512.0f), 512.0f) : 0.0f;
+    int q = (int)r + 128;
+    q = (q + B / 2) / B * B;
+    return (uint8_t)min(max(q, 0), 255);
+}
+// packQuaternionSmallestThree (load-spz.cc:216-255) of the repository's (w, x, y, z)
+__device__ __forceinline__ uint32_t spz_rot(const float4 r) {
+    float q[4] = {r.y, r.z, r.w, r.x};                                     // the format's (x, y, z, w)
+    const float ss = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
+    if (!(ss > 0.0f) || !(ss < __builtin_inff())) { q[0] = q[1] = q[2] = 0.0f; q[3] = 1.0f; }
+    else {
+        const float len = dvs_sqrt_rn(ss);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = q[k] / len;
+    }
+    int largest = 0;
+    float ql = q[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) if (fabsf(q[k]) > fabsf(ql)) { largest = k; ql = q[k]; }      // the first of equal magnitudes stays
+    const uint32_t negate = ql < 0.0f ? 1u : 0u;
+    uint32_t comp = (uint32_t)largest;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (k != largest) {
+            const uint32_t mag = (uint32_t)(511.0f * (fabsf(q[k]) / 0.70710678f) + 0.5f);
+            comp = (comp << 10) | (((q[k] < 0.0f ? 1u : 0u) ^ negate) << 9) | min(mag, 511u);
+        }
+    return comp;
+}
+
+template <int DIM>
+__global__ void __launch_bounds__(PK_BLOCK)
+k_pack_spz(int n, SpzOff off, const float* __restrict__ pos, const float* __restrict__ sh0, const float* __restrict__ shN, int tiled,
+           const float* __restrict__ opacity, const float* __restrict__ scale, const float* __restrict__ rot, uint8_t* __restrict__ out) {
+    constexpr int SHB = 3 * DIM, IMG16 = spz_image_bytes<DIM>() / 16;
+    __shared__ uint4 lds[PK_WAVES * IMG16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tile = (int64_t)blockIdx.x * PK_WAVES + wave, i0 = tile * 64, i = i0 + lane;
+    const int count = (int)(n - i0 >= 64 ? 64 : n - i0 > 0 ? n - i0 : 0);  // splats of this wave's tile (0: a wave past the model)
+    uint8_t* const img_sh = reinterpret_cast<uint8_t*>(lds + wave * IMG16);
+    uint8_t* const img_pos = img_sh + 64 * SHB;
+    uint8_t* const img_col = img_pos + SPZ_POS;
+    uint8_t* const img_scl = img_col + SPZ_VEC3;
+    if (lane < count) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const uint32_t f = spz_fixed24(pos[3 * i + k]);
+            img_pos[lane * 9 + 3 * k] = (uint8_t)f; img_pos[lane * 9 + 3 * k + 1] = (uint8_t)(f >> 8); img_pos[lane * 9 + 3 * k + 2] = (uint8_t)(f >> 16);
+            img_col[lane * 3 + k] = (uint8_t)spz_u8(sh0[3 * i + k] * (0.15f * 255.0f) + (0.5f * 255.0f));
+            img_scl[lane * 3 + k] = (uint8_t)spz_u8((scale[3 * i + k] + 10.0f) * 16.0f);
+        }
+        const float o = opacity[i];
+        out[off.a[1] + i] = (uint8_t)(o == o ? spz_u8(dvs_sigmoid_det(o) * 255.0f) : 0u);         // a NaN logit: alpha 0
+        reinterpret_cast<uint32_t*>(out + off.a[4])[i] = spz_rot(reinterpret_cast<const float4*>(rot)[i]);
+    }
+    if (DIM > 0 && count > 0) {
+        if (tiled) {                                                       // (whole tiles are allocated: every lane's chunk is in bounds)
+#pragma unroll
+            for (int c = 0; c < (SHB + 3) / 4; ++c) {
+                const float4 v = reinterpret_cast<const float4*>(shN)[(tile * 12 + c) * 64 + lane];
+                const float e4[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (4 * c + k < SHB) img_sh[lane * SHB + 4 * c + k] = 4 * c + k < 9 ? spz_sh<8>(e4[k]) : spz_sh<16>(e4[k]);
+            }
+        } else {
+            for (int idx = lane; idx < count * SHB; idx += 64) {
+                const int s = idx / SHB, e = idx - s * SHB;
+                const float x = shN[(i0 + s) * 45 + e];
+                img_sh[idx] = e < 9 ? spz_sh<8>(x) : spz_sh<16>(x);
+            }
+        }
+    }
+    __syncthreads();
+    if (count == 0) return;
+    if (DIM > 0) spz_store_slice(img_sh, out + off.a[5] + (size_t)tile * (64 * SHB), 64 * SHB, count * SHB, lane);
+    spz_store_slice(img_pos, out + off.a[0] + (size_t)tile * SPZ_POS, SPZ_POS, count * 9, lane);
+    spz_store_slice(img_col, out + off.a[2] + (size_t)tile * SPZ_VEC3, SPZ_VEC3, count * 3, lane);
+    spz_store_slice(img_scl, out + off.a[3] + (size_t)tile * SPZ_VEC3, SPZ_VEC3, count * 3, lane);
+}
+
+// unpackGaussians (load-spz.cc:467-531): shN == nullptr skips the higher bands (degree 0 only)
+template <int DIM>
+__global__ void __launch_bounds__(PK_BLOCK)
+k_unpack_spz(int n, SpzOff off, const uint8_t* __restrict__ in, float* __restrict__ pos, float* __restrict__ sh0, float* __restrict__ shN, int tiled,
+             float* __restrict__ opacity, float* __restrict__ scale, float* __restrict__ rot) {
+    constexpr int SHB = 3 * DIM, IMG16 = spz_image_bytes<DIM>() / 16;
+    __shared__ uint4 lds[PK_WAVES * IMG16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t tile = (int64_t)blockIdx.x * PK_WAVES + wave, i0 = tile * 64, i = i0 + lane;
+    const int count = (int)(n - i0 >= 64 ? 64 : n - i0 > 0 ? n - i0 : 0);
+    uint8_t* const img_sh = reinterpret_cast<uint8_t*>(lds + wave * IMG16);
+    uint8_t* const img_pos = img_sh + 64 * SHB;
+    uint8_t* const img_col = img_pos + SPZ_POS;
+    uint8_t* const img_scl = img_col + SPZ_VEC3;
+    if (count > 0) {
+        if (DIM > 0) spz_load_slice(img_sh, in + off.a[5] + (size_t)tile * (64 * SHB), 64 * SHB, count * SHB, lane);
+        spz_load_slice(img_pos, in + off.a[0] + (size_t)tile * SPZ_POS, SPZ_POS, count * 9, lane);
+        spz_load_slice(img_col, in + off.a[2] + (size_t)tile * SPZ_VEC3, SPZ_VEC3, count * 3, lane);
+        spz_load_slice(img_scl, in + off.a[3] + (size_t)tile * SPZ_VEC3, SPZ_VEC3, count * 3, lane);
+    }
+    __syncthreads();
+    if (count == 0) return;
+    const bool valid = lane < count;
+    if (valid) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const uint8_t* b = img_pos + lane * 9 + 3 * k;
+            const int32_t fixed = (int32_t)(((uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16) << 8) >> 8;      // sign extension of bit 23
+            pos[3 * i + k] = (float)fixed * (1.0f / 4096.0f);
+            sh0[3 * i + k] = (((float)img_col[lane * 3 + k] / 255.0f) - 0.5f) / 0.15f;
+            scale[3 * i + k] = (float)img_scl[lane * 3 + k] / 16.0f - 10.0f;
+        }
+        const float a = (float)in[off.a[1] + i] / 255.0f;
+        opacity[i] = logf(a / (1.0f - a));                                 // bytes 0 / 255: -inf / +inf
+        uint32_t comp = reinterpret_cast<const uint32_t*>(in + off.a[4])[i];
+        const int largest = (int)(comp >> 30);
+        float q[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sum = 0.0f;                 // (x, y, z, w)
+#pragma unroll
+        for (int k = 3; k >= 0; --k)
+            if (k != largest) {
+                const float m = (0.70710678f * (float)(comp & 511u)) / 511.0f;
+                q[k] = (comp >> 9) & 1u ? -m : m;
+                comp >>= 10;
+                sum += q[k] * q[k];
+            }
+        const float big = dvs_sqrt_rn(1.0f - sum);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) if (k == largest) q[k] = big;
+        reinterpret_cast<float4*>(rot)[i] = make_float4(q[3], q[0], q[1], q[2]);
+    }
+    if (!shN) return;
+    if (tiled) {                                                           // the whole tile: the pads and the lanes past the model are 0
+#pragma unroll
+        for (int c = 0; c < 12; ++c) {
+            float e4[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) e4[k] = (4 * c + k < SHB && valid) ? ((float)img_sh[lane * SHB + 4 * c + k] - 128.0f) / 128.0f : 0.0f;
+            reinterpret_cast<float4*>(shN)[(tile * 12 + c) * 64 + lane] = make_float4(e4[0], e4[1], e4[2], e4[3]);
+        }
+    } else {
+        for (int idx = lane; idx < count * 45; idx += 64) {
+            const int s = idx / 45, e = idx - s * 45;
+            shN[(i0 + s) * 45 + e] = e < SHB ? ((float)img_sh[s * SHB + e] - 128.0f) / 128.0f : 0.0f;
+        }
+    }
+}
+
 // the scratch of dvs_pack_compressed: byte offsets of its parts, each on a 256-byte boundary
 struct PackScratch { size_t slots, bounds, seg, totals, hist, key[2], val[2], total; };
 PackScratch pack_layout(int n) {
@@ -271,5 +459,64 @@ extern "C" int dvs_pack_splat32(void* stream, int n, const float* pos, const flo
     if (off16(pos) || off16(sh0) || off16(opacity) || off16(scale) || off16(rot) || off16(out)) return DVS_ERR_INVALID;
     const unsigned nblocks = (unsigned)(((int64_t)n + PK_BLOCK - 1) / PK_BLOCK);
     hipLaunchKernelGGL(k_pack_splat32, dim3(nblocks), dim3(PK_BLOCK), 0, (hipStream_t)stream, n, pos, sh0, opacity, scale, rot, (uint4*)out);
+    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+}
+
+extern "C" int dvs_spz_layout_for(int n, int sh_degree, dvs_spz_layout* out) {
+    if (n <= 0 || sh_degree < 0 || sh_degree > 3 || !out) return DVS_ERR_INVALID;
+    static const int dim[4] = {0, 3, 8, 15};
+    const uint64_t per[6] = {9, 1, 3, 3, 4, (uint64_t)(3 * dim[sh_degree])};
+    uint64_t o = 0;
+    for (int k = 0; k < 6; ++k) { out->off[k] = o; out->bytes[k] = per[k] * (uint64_t)n; o = (o + out->bytes[k] + 15) & ~(uint64_t)15; }
+    out->total = o;
+    return DVS_OK;
+}
+
+namespace {
+bool spz_args_ok(int n, int sh_degree, int shn_layout, const void* const* ptrs, int n_ptrs, const void* shN) {
+    if (n <= 0 || sh_degree < 0 || sh_degree > 3 || (shn_layout != DVS_SHN_ROWS && shn_layout != DVS_SHN_TILED)) return false;
+    for (int k = 0; k < n_ptrs; ++k) if (!ptrs[k] || off16(ptrs[k])) return false;
+    return !off16(shN) && (shN || sh_degree == 0);
+}
+SpzOff spz_offsets(int n, int sh_degree) {
+    dvs_spz_layout L;
+    (void)dvs_spz_layout_for(n, sh_degree, &L);
+    SpzOff o;
+    for (int k = 0; k < 6; ++k) o.a[k] = L.off[k];
+    return o;
+}
+}  // namespace
+
+extern "C" int dvs_pack_spz(void* stream, int n, int sh_degree, const float* pos, const float* sh0, const float* shN, int shn_layout,
+                            const float* opacity, const float* scale, const float* rot, uint8_t* out) {
+    const void* const ptrs[6] = {pos, sh0, opacity, scale, rot, out};
+    if (!spz_args_ok(n, sh_degree, shn_layout, ptrs, 6, shN)) return DVS_ERR_INVALID;
+    const SpzOff off = spz_offsets(n, sh_degree);
+    const unsigned nblocks = (unsigned)(((int64_t)n + PK_BLOCK - 1) / PK_BLOCK);
+    hipStream_t st = (hipStream_t)stream;
+    const int tiled = shn_layout == DVS_SHN_TILED;
+    switch (sh_degree) {
+        case 0: hipLaunchKernelGGL(k_pack_spz<0>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
+        case 1: hipLaunchKernelGGL(k_pack_spz<3>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
+        case 2: hipLaunchKernelGGL(k_pack_spz<8>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
+        default: hipLaunchKernelGGL(k_pack_spz<15>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
+    }
+    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+}
+
+extern "C" int dvs_unpack_spz(void* stream, int n, int sh_degree, const uint8_t* packed, float* pos, float* sh0, float* shN, int shn_layout,
+                              float* opacity, float* scale, float* rot) {
+    const void* const ptrs[6] = {packed, pos, sh0, opacity, scale, rot};
+    if (!spz_args_ok(n, sh_degree, shn_layout, ptrs, 6, shN)) return DVS_ERR_INVALID;
+    const SpzOff off = spz_offsets(n, sh_degree);
+    const unsigned nblocks = (unsigned)(((int64_t)n + PK_BLOCK - 1) / PK_BLOCK);
+    hipStream_t st = (hipStream_t)stream;
+    const int tiled = shn_layout == DVS_SHN_TILED;
+    switch (sh_degree) {
+        case 0: hipLaunchKernelGGL(k_unpack_spz<0>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
+        case 1: hipLaunchKernelGGL(k_unpack_spz<3>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
+        case 2: hipLaunchKernelGGL(k_unpack_spz<8>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
+        default: hipLaunchKernelGGL(k_unpack_spz<15>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
+    }
     return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
 }

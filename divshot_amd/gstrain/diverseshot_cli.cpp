@@ -37,6 +37,9 @@ static std::map<std::string, std::string> g_opts = {
     // extension of this build: compact formats every save writes beside the full PLY: compressed | splat | compressed,splat
     // (<outputPath>_<it>.compressed.ply / .splat); empty = none, unless --outputPath itself ends in .compressed.ply / .splat
     {"exportFormat", ""},
+    // extension of this build: a switch, every save also writes <outputPath>_<it>.spz (the compact format that keeps the SH bands above 0;
+    // with --eval its decoded model is scored on the held-out views too); also on when --outputPath itself ends in .spz
+    {"exportSpz", "0"},
     // the config fields pruneScale3d / pruneScale2d (the reference's CLI has no flag for them): after the first opacity reset a refinement
     // also prunes splats larger than this fraction of the scene extent / whose screen radius exceeds this fraction of the image size
     {"pruneScale3d", "0.1"}, {"pruneScale2d", "0.15"}};
@@ -65,7 +68,7 @@ int main(int argc, const char* argv[]) {
         std::string val;
         size_t eq = a.find('=');
         if (eq != std::string::npos) { val = a.substr(eq + 1); a = a.substr(0, eq); }
-        else if (a == "eval") val = "1";
+        else if (a == "eval" || a == "exportSpz") val = "1";
         else if (i + 1 < argc) val = argv[++i];
         if (!g_opts.count(a)) { std::cout << "Command Line Error: unknown flag --" << a << "\n"; return 1; }   // config_extras_mode::error
         g_opts[a] = val;
@@ -125,6 +128,7 @@ int main(int argc, const char* argv[]) {
         else { std::cout << "Command Line Error: --exportFormat takes compressed, splat or compressed,splat, not '" << tok << "'\n"; return 1; }
         at = comma + 1;
     }
+    if (as_bool(g_opts["exportSpz"])) train_config.exportFormats |= 4;
     train_config.normalConsistencyLoss = false;
     if (train_config.exportMesh) { train_config.normalConsistencyLoss = true; train_config.useMask = true; }
     train_config.verbose = true;

@@ -127,7 +127,7 @@ void GaussianTrainerScene::saveGaussianModel() {
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_save).count());
     }
     if (m.rank == 0)
-        for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT})
+        for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT, (int)Impl::EXPORT_SPZ})
             if (m.export_formats() & format) m.export_model(format);
     m.evaluate(true);                                                       // <modelPath>_<it>_eval.json beside the PLY (rank 0, evaluation on)
 }

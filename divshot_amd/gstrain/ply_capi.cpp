@@ -1,7 +1,9 @@
 // ply_capi.cpp — libgsplyio.so: plain-C entry points of the compact-format file writers (ply_io.hpp), in a host-only library of their
 // own so that the wire formats can be tested from Python without a GPU or the HIP runtime. libgstrain.so links the same ply_io.cpp
 // and keeps its pinned set of exported symbols.
+#include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include "ply_io.hpp"
 
@@ -14,5 +16,13 @@ __attribute__((visibility("default"))) int gstrain_write_compressed_ply(const ch
 __attribute__((visibility("default"))) int gstrain_write_splat(const char* path, uint64_t n, const uint8_t* bytes) {
     std::string err;
     return gsply::write_splat(path, (size_t)n, bytes, &err) ? 0 : 1;
+}
+// `packed`: the six sections at layout->off[k]; on failure the message goes to err_out (when given, NUL-terminated, at most err_cap bytes)
+__attribute__((visibility("default"))) int gstrain_write_spz(const char* path, uint64_t n, int sh_degree, int antialiased, const uint8_t* packed,
+                                                              const dvs_spz_layout* layout, char* err_out, uint64_t err_cap) {
+    std::string err;
+    if (gsply::write_spz(path, (size_t)n, sh_degree, antialiased != 0, packed, *layout, &err)) return 0;
+    if (err_out && err_cap > 0) { const size_t k = std::min<size_t>(err.size(), (size_t)err_cap - 1); memcpy(err_out, err.data(), k); err_out[k] = 0; }
+    return 1;
 }
 }

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "../../include/dvs_export.h"
 
 namespace gsply {
 bool write_ply(const std::string& path, size_t n, const float* pos, const float* sh0, const float* shN, const float* opacity,
@@ -19,4 +20,10 @@ bool read_ply(const std::string& path, std::vector<float>& pos, std::vector<floa
 // (tiny_gsplat.cpp:766-815); and the headerless .splat file of 32-byte records (tiny_gsplat.cpp:243-291).
 bool write_compressed_ply(const std::string& path, size_t n, const float* chunks, const uint32_t* verts, bool antialiased, std::string* err);
 bool write_splat(const std::string& path, size_t n, const uint8_t* bytes, std::string* err);
+// .spz version 3 (external/spz/src/load-spz.cc serializePackedGaussians / saveSpz): through gzip, the 16-byte header — magic 0x5053474e,
+// version 3, numPoints, shDegree, fractionalBits 12, flags (bit 0: antialiased), reserved 0 — then the six sections of the buffer
+// dvs_pack_spz filled, bytes[k] bytes from off[k] each. zlib is resolved at run time (dlopen of libz.so.1: gzopen / gzwrite /
+// gzclose); without it the call fails with a message naming the library or the symbol.
+bool write_spz(const std::string& path, size_t n, int sh_degree, bool antialiased, const uint8_t* packed, const dvs_spz_layout& layout,
+               std::string* err);
 }

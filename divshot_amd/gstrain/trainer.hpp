@@ -131,6 +131,11 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     // packed payload on the device and its host copy. Nothing is allocated until a save exports; the buffers only grow.
     DevBuf<void> d_export_scratch; DevBuf<uint8_t> d_export_out; size_t export_scratch_cap = 0, export_out_cap = 0;
     std::vector<uint8_t> export_host;
+    // the .spz export's fidelity score (evaluation on, rank 0): the packed payload decoded on the device into a second parameter set
+    // in the tiled layout, rendered and scored on the test cameras like the full model. Allocated at the first such export, only grows.
+    DevBuf<float> d_decoded[6]; int decoded_cap = 0;
+    double spz_mean[4] = {NAN, NAN, NAN, NAN};                               // {mse, l1, ssim, psnr} means of the decoded model ...
+    int spz_it = -1;                                                         // ... at this iteration (-1: none)
 
     ~Impl() { if (device >= 0) (void)hipSetDevice(device); }                // (the members release themselves, after this body)
     // floats of group g on the device: the 45 higher-order SH floats live in the DVS_SHN_TILED layout (48 per splat,
@@ -171,6 +176,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     void setup_split();
     bool evaluate(bool write_json, bool force = false);
     void run_evaluation();
+    void score_views(const dvs_splats& sp, std::vector<double>& res, double mean[4]);     // [n_test][4] and their means, synchronous
     void write_eval_json() const;
     std::vector<dvs_camera> rank_cameras(const std::vector<int>& ci_all, int level) const {     // this rank's views of an iteration's draw, at a level
         std::vector<dvs_camera> v((size_t)vpi);
@@ -222,11 +228,14 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         return cfg.modelPath.size() >= k && cfg.modelPath.compare(cfg.modelPath.size() - k, k, suffix) == 0;
     }
     // EXPORT_* bits of the compact formats a save writes; decided at every use, since the editor sets modelPath after construction
-    enum { EXPORT_COMPRESSED = 1, EXPORT_SPLAT = 2 };
-    int suffix_formats() const { return model_path_ends(".compressed.ply") ? EXPORT_COMPRESSED : model_path_ends(".splat") ? EXPORT_SPLAT : 0; }
+    enum { EXPORT_COMPRESSED = 1, EXPORT_SPLAT = 2, EXPORT_SPZ = 4 };
+    int suffix_formats() const {
+        return model_path_ends(".compressed.ply") ? EXPORT_COMPRESSED : model_path_ends(".splat") ? EXPORT_SPLAT : model_path_ends(".spz") ? EXPORT_SPZ : 0;
+    }
     int asked_formats() const { return env_int("DVS_EXPORT_FORMATS", cfg.exportFormats); }   // 0: the suffix of modelPath decides
-    int export_formats() const { return (asked_formats() ? asked_formats() : suffix_formats()) & (EXPORT_COMPRESSED | EXPORT_SPLAT); }
+    int export_formats() const { return (asked_formats() ? asked_formats() : suffix_formats()) & (EXPORT_COMPRESSED | EXPORT_SPLAT | EXPORT_SPZ); }
     void export_model(int format);
+    void export_spz();
     void fetch_host();
     // what the two loaders share: the context and every per-step buffer (W, H, sh_max set by the caller) ...
     void create_context(int count, int capacity, const std::vector<float> init[6]);

@@ -23,11 +23,11 @@ void GaussianTrainerScene::Impl::report_config() const {
               "%dx%d (targets box-filtered per step, cameras of dvs_camera_downscale); full resolution from iteration %d; evaluation always at full size",
               res_every, res_levels, res_levels, res_every, W, H, res_levels * res_every + 1);
     if (const int fmts = export_formats())
-        logf_("config: exportFormats %d: every save also writes%s%s beside the full PLY, packed on the device%s", fmts,
+        logf_("config: exportFormats %d: every save also writes%s%s%s beside the full PLY, packed on the device%s%s", fmts,
               (fmts & EXPORT_COMPRESSED) ? " <modelPath>_<it>.compressed.ply" : "", (fmts & EXPORT_SPLAT) ? " <modelPath>_<it>.splat" : "",
-              asked_formats() == 0 ? " (turned on by the suffix of modelPath)" : "");
+              (fmts & EXPORT_SPZ) ? " <modelPath>_<it>.spz" : "", asked_formats() == 0 ? " (turned on by the suffix of modelPath)" : "",
+              (fmts & EXPORT_SPZ) && !test_idx.empty() ? "; the .spz payload is decoded on the device and scored on the held-out views" : "");
     std::string ign;
-    if (model_path_ends(".spz")) ign += " modelPath suffix .spz(spz export: the full PLY is written)";
     if (cfg.modelType != 0) ign += " modelType(only 3DGS)";
     if (cfg.cullSH) ign += " cullSH";
     if (cfg.pixelGradScale) ign += " pixelGradScale";
@@ -56,6 +56,12 @@ bool GaussianTrainerScene::Impl::evaluate(bool write_json, bool force) {
     return true;
 }
 void GaussianTrainerScene::Impl::run_evaluation() {
+    score_views(splats(), eval_res, eval_mean);
+    eval_it = step;
+    logf_("eval @%d: %d views, PSNR %.17g dB, SSIM %.17g, L1 %.17g", step, (int)test_idx.size(), eval_mean[3], eval_mean[2], eval_mean[1]);
+}
+// the test cameras rendered from `sp` (DVS_SHN_TILED, at most `cap` splats) and scored: res = [n_test][4] {mse, l1, ssim, psnr}, mean = their means
+void GaussianTrainerScene::Impl::score_views(const dvs_splats& sp, std::vector<double>& res, double mean[4]) {
     const int nt = (int)test_idx.size();
     const size_t img = 3 * (size_t)W * H;
     if (!eval_ctx) {
@@ -68,7 +74,6 @@ void GaussianTrainerScene::Impl::run_evaluation() {
     }
     dvs_opts opts{};
     opts.sh_degree = sh_max; opts.antialias = cfg.mipAntiliased ? 1 : 0; opts.shn_layout = DVS_SHN_TILED; opts.tile_bounds = DVS_TILES_CANONICAL;
-    const dvs_splats sp = splats();
     for (int first = 0; first < nt; first += eval_views) {
         const int nb = std::min(eval_views, nt - first);
         std::vector<dvs_camera> bc((size_t)nb);
@@ -83,16 +88,14 @@ void GaussianTrainerScene::Impl::run_evaluation() {
         DVS_OR_THROW(dvs_raster_forward_views(eval_ctx.get(), stream.get(), &sp, bc.data(), nb, &opts, d_eval_out.get()));
         DVS_OR_THROW(dvs_image_metrics_views(stream.get(), mv, nb, W, H, views_u8() ? 1 : 0, d_eval_scratch.get(), d_eval_res.get() + (size_t)first * 4));
     }
-    eval_res.assign((size_t)nt * 4, 0.0);
-    HIP_OR_THROW(hipMemcpyAsync(eval_res.data(), d_eval_res.get(), eval_res.size() * sizeof(double), hipMemcpyDeviceToHost, stream.get()));
+    res.assign((size_t)nt * 4, 0.0);
+    HIP_OR_THROW(hipMemcpyAsync(res.data(), d_eval_res.get(), res.size() * sizeof(double), hipMemcpyDeviceToHost, stream.get()));
     HIP_OR_THROW(hipStreamSynchronize(stream.get()));
     for (int k = 0; k < 4; ++k) {
         double a = 0.0;
-        for (int v = 0; v < nt; ++v) a += eval_res[(size_t)v * 4 + k];
-        eval_mean[k] = a / nt;
+        for (int v = 0; v < nt; ++v) a += res[(size_t)v * 4 + k];
+        mean[k] = a / nt;
     }
-    eval_it = step;
-    logf_("eval @%d: %d views, PSNR %.17g dB, SSIM %.17g, L1 %.17g", step, nt, eval_mean[3], eval_mean[2], eval_mean[1]);
 }
 // <modelPath>_<it>_eval.json: the last evaluation, every double with 17 significant digits (they read back bit for bit)
 void GaussianTrainerScene::Impl::write_eval_json() const {
@@ -106,7 +109,10 @@ void GaussianTrainerScene::Impl::write_eval_json() const {
         fprintf(f, "    {\"camera\": %d, \"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}%s\n", test_idx[(size_t)v], r[3], r[2], r[1], r[0],
                 v + 1 < nt ? "," : "");
     }
-    fprintf(f, "  ],\n  \"mean\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}\n}\n", eval_mean[3], eval_mean[2], eval_mean[1], eval_mean[0]);
+    fprintf(f, "  ],\n  \"mean\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}", eval_mean[3], eval_mean[2], eval_mean[1], eval_mean[0]);
+    if (spz_it == step)                                                      // the decoded .spz model's means, scored by this save's export
+        fprintf(f, ",\n  \"exports\": {\"spz\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}}", spz_mean[3], spz_mean[2], spz_mean[1], spz_mean[0]);
+    fprintf(f, "\n}\n");
     fclose(f);
 }
 
@@ -129,6 +135,7 @@ void GaussianTrainerScene::Impl::fetch_host() {
 // One compact export of the current model: packed on the training stream from the device arrays (shN is not read, so its tiled layout
 // does not matter), the packed payload alone copied to the host and written to <modelPath>_<step>.compressed.ply / .splat.
 void GaussianTrainerScene::Impl::export_model(int format) {
+    if (format == EXPORT_SPZ) { export_spz(); return; }
     const auto t_start = std::chrono::steady_clock::now();
     const bool compressed = format == EXPORT_COMPRESSED;
     const size_t n_chunks = ((size_t)n + 255) / 256;
@@ -161,4 +168,46 @@ void GaussianTrainerScene::Impl::export_model(int format) {
     const auto file_bytes = std::filesystem::file_size(file, ec);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
     logf_("export @%d: %s %d splats, %llu bytes, %.2f ms", step, compressed ? "compressed.ply" : "splat", n, (unsigned long long)(ec ? bytes : file_bytes), ms);
+}
+
+// The .spz export: the six sections packed from the tiled arrays at the model's sh_max (the one compact format that keeps the
+// higher SH bands), layout.total bytes copied to the host, gzipped into <modelPath>_<step>.spz. With evaluation on, the device payload
+// is then decoded into a second parameter set and scored on the test cameras: what the compact file costs in dB. That score is
+// reported beside the full model's (log line, "exports" in the eval JSON) and never replaces it.
+void GaussianTrainerScene::Impl::export_spz() {
+    const auto t_start = std::chrono::steady_clock::now();
+    dvs_spz_layout layout;
+    if (dvs_spz_layout_for(n, sh_max, &layout) != DVS_OK) throw std::runtime_error("dvs_spz_layout_for: invalid arguments");
+    const size_t bytes = (size_t)layout.total;
+    if (bytes > export_out_cap) { export_out_cap = 0; d_export_out.alloc(bytes); export_out_cap = bytes; }
+    if (export_host.size() < bytes) export_host.resize(bytes);
+    const int status = dvs_pack_spz(stream.get(), n, sh_max, d_param[P_POS].get(), d_param[P_SH0].get(), d_param[P_SHN].get(), DVS_SHN_TILED,
+                                    d_param[P_OPA].get(), d_param[P_SCALE].get(), d_param[P_ROT].get(), d_export_out.get());
+    if (status != DVS_OK) throw std::runtime_error("dvs_pack_spz: status " + std::to_string(status));
+    HIP_OR_THROW(hipMemcpyAsync(export_host.data(), d_export_out.get(), bytes, hipMemcpyDeviceToHost, stream.get()));
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    const std::string file = cfg.modelPath + "_" + std::to_string(step) + ".spz";
+    std::string err;
+    if (!gsply::write_spz(file, (size_t)n, sh_max, cfg.mipAntiliased, export_host.data(), layout, &err)) { logf_("export @%d: %s", step, err.c_str()); return; }
+    std::error_code ec;
+    const auto file_bytes = std::filesystem::file_size(file, ec);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    logf_("export @%d: spz %d splats, %llu bytes, %.2f ms", step, n, (unsigned long long)(ec ? 0 : file_bytes), ms);
+    if (test_idx.empty() || rank != 0) return;
+    if (n > decoded_cap) {
+        decoded_cap = 0;
+        for (int g = 0; g < 6; ++g) d_decoded[g].alloc(dev_floats_for(g, n) * sizeof(float) + 16);
+        decoded_cap = n;
+    }
+    const int rc = dvs_unpack_spz(stream.get(), n, sh_max, d_export_out.get(), d_decoded[P_POS].get(), d_decoded[P_SH0].get(), d_decoded[P_SHN].get(),
+                                  DVS_SHN_TILED, d_decoded[P_OPA].get(), d_decoded[P_SCALE].get(), d_decoded[P_ROT].get());
+    if (rc != DVS_OK) throw std::runtime_error("dvs_unpack_spz: status " + std::to_string(rc));
+    if (eval_it != step) run_evaluation();                                  // the full model of the same parameters: the comparison
+    dvs_splats sp{};
+    sp.pos = d_decoded[P_POS].get(); sp.sh0 = d_decoded[P_SH0].get(); sp.shN = d_decoded[P_SHN].get(); sp.opacity = d_decoded[P_OPA].get();
+    sp.scale = d_decoded[P_SCALE].get(); sp.rot = d_decoded[P_ROT].get(); sp.n = n;
+    std::vector<double> res;
+    score_views(sp, res, spz_mean);
+    spz_it = step;
+    logf_("export @%d: spz decoded model: PSNR %.17g dB (full model %.17g dB), SSIM %.17g, L1 %.17g", step, spz_mean[3], eval_mean[3], spz_mean[2], spz_mean[1]);
 }

@@ -84,9 +84,10 @@ struct GaussianTrainConfig {
     // extension of this build, appended the same way (0 = the reference's behaviour: saveGaussianModel() writes the full PLY only). Bit
     // flags of the viewer's compact formats that every saveGaussianModel() writes BESIDE <modelPath>_<it>.ply (which stays the resume
     // format): 1 = <modelPath>_<it>.compressed.ply (chunked, quantised: 16 B per splat + 48 B per 256), 2 = <modelPath>_<it>.splat
-    // (32 B per splat). Packed on the device from the trained arrays (include/dvs_export.h); only the packed payload crosses to the host.
+    // (32 B per splat), 4 = <modelPath>_<it>.spz (version 3, gzipped, 20 + 3 dim B per splat: keeps the SH bands above 0). Packed on the
+    // device from the trained arrays (include/dvs_export.h); only the packed payload crosses to the host.
     // The editor passes its "Splat Format" choice only as the suffix of modelPath (editor.cpp:1886-1904, 2024): while this field is 0 a
-    // modelPath ending in ".compressed.ply" / ".splat" turns on the matching bit. DVS_EXPORT_FORMATS overrides the field.
+    // modelPath ending in ".compressed.ply" / ".splat" / ".spz" turns on the matching bit. DVS_EXPORT_FORMATS overrides the field.
     int exportFormats = 0;
 };
 
