@@ -195,7 +195,17 @@ _INIT_PROTOS = {
     "dvs_knn_mean_dist2_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dvs_init_from_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
-for _name, (_res, _args) in list(_PROTOS.items()) + list(_EXPORT_PROTOS.items()) + list(_INIT_PROTOS.items()):
+# include/dvs_image.h: JPEG reconstruction from quantised DCT coefficients
+class JpegDesc(C.Structure):           # dvs_jpeg_desc
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32),
+                ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3), ("_pad", C.c_int32), ("offset", C.c_uint64 * 3),
+                ("quant", (C.c_uint16 * 64) * 3)]
+
+
+_IMAGE_PROTOS = {
+    "dvs_jpeg_reconstruct": (C.c_int, [C.c_void_p, C.POINTER(JpegDesc), C.c_void_p, C.c_void_p]),
+}
+for _name, (_res, _args) in list(_PROTOS.items()) + list(_EXPORT_PROTOS.items()) + list(_INIT_PROTOS.items()) + list(_IMAGE_PROTOS.items()):
     _f = getattr(lib, _name)          # AttributeError here = the .so does not export a declared symbol
     _f.restype = _res
     _f.argtypes = _args
@@ -204,3 +214,51 @@ for _name, (_res, _args) in list(_PROTOS.items()) + list(_EXPORT_PROTOS.items())
 def check(status, what="dvs call"):
     if status != 0:
         raise DvsError(f"{what} failed with status {status}: {lib.dvs_last_error().decode()}")
+
+
+# libgsplyio.so, the host-only library of the plugin's file readers and writers (no HIP runtime behind it): the JPEG coefficient decoder
+_JPEG_HOST_PROTOS = {
+    "gstrain_jpeg_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int]),
+    "gstrain_jpeg_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gstrain_jpeg_coefficients": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gstrain_jpeg_close": (None, [C.c_void_p]),
+}
+_host_lib = None
+
+
+def host_lib():
+    """libgsplyio.so with the gstrain_jpeg_* prototypes bound; loaded on first use (divshot_amd/gstrain builds it)"""
+    global _host_lib
+    if _host_lib is None:
+        path = os.path.join(_HERE, "lib", "libgsplyio.so")
+        if not os.path.exists(path):
+            raise ImportError(f"{path} is missing: build it with `make -C divshot_amd/gstrain`")
+        h = C.CDLL(path)
+        for name, (res, args) in _JPEG_HOST_PROTOS.items():
+            f = getattr(h, name)
+            f.restype = res
+            f.argtypes = args
+        _host_lib = h
+    return _host_lib
+
+
+def jpeg_decode_coefficients(path):
+    """-> (JpegDesc, int16 numpy array): gsjpeg::decode_coefficients of a file, as dvs_jpeg_reconstruct takes them; DvsError with the
+    decoder's message for a file it rejects"""
+    import numpy as np
+    h = host_lib()
+    err = C.create_string_buffer(1024)
+    f = h.gstrain_jpeg_open(os.fsencode(path), err, 1024)
+    if not f:
+        raise DvsError(err.value.decode(errors="replace"))
+    try:
+        ints, offs, desc = (C.c_int32 * 15)(), (C.c_uint64 * 4)(), JpegDesc()
+        check(h.gstrain_jpeg_info(f, ints, C.addressof(desc.quant), offs), "gstrain_jpeg_info")
+        desc.width, desc.height, desc.components, desc.hs, desc.vs = ints[0], ints[1], ints[2], ints[3], ints[6]
+        for k in range(3):
+            desc.blocks_w[k], desc.blocks_h[k], desc.offset[k] = ints[9 + k], ints[12 + k], offs[k]
+        coef = np.zeros(offs[3], np.int16)
+        check(h.gstrain_jpeg_coefficients(f, coef.ctypes.data), "gstrain_jpeg_coefficients")
+        return desc, coef
+    finally:
+        h.gstrain_jpeg_close(f)

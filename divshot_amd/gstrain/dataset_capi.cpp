@@ -59,6 +59,18 @@ GSDATA_API int gstrain_dataset_points(const void* h, float* xyz, uint8_t* rgb) {
     if (!d->xyz.empty()) { memcpy(xyz, d->xyz.data(), d->xyz.size() * sizeof(float)); memcpy(rgb, d->rgb.data(), d->rgb.size()); }
     return 0;
 }
+// the file image `index` is read from (NUL-terminated into `file`) and whether it is decoded as a JPEG
+GSDATA_API int gstrain_dataset_resolve_image(const void* h, uint64_t index, char* file, int file_cap, int* is_jpeg, char* err, int cap) {
+    const gsdata::Dataset* d = (const gsdata::Dataset*)h;
+    if (!d || !file || file_cap <= 0 || !is_jpeg) return report(false, "NULL argument", err, cap);
+    std::string path, msg;
+    bool jpeg = false;
+    if (!gsdata::resolve_image(*d, (size_t)index, &path, &jpeg, &msg)) return report(false, msg, err, cap);
+    if (path.size() + 1 > (size_t)file_cap) return report(false, "path longer than the buffer", err, cap);
+    memcpy(file, path.c_str(), path.size() + 1);
+    *is_jpeg = jpeg ? 1 : 0;
+    return 0;
+}
 // rgb [H][W][3] of the image's camera size; mask (nullable) [H][W] in {0, 1}
 GSDATA_API int gstrain_dataset_read_image(const void* h, uint64_t index, uint8_t* rgb, uint8_t* mask, char* err, int cap) {
     const gsdata::Dataset* d = (const gsdata::Dataset*)h;

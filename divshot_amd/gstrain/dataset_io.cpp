@@ -2,6 +2,7 @@
 // through a bounds-checked cursor: every count is compared with the bytes that are left before anything is sized by it.
 #include "dataset_io.hpp"
 #include <algorithm>
+#include <cctype>
 #include <cerrno>
 #include <cmath>
 #include <cstdio>
@@ -335,6 +336,29 @@ void rotation_of(const Image& im, float R[9]) {
                          2 * x * y + 2 * w * z,     1 - 2 * x * x - 2 * z * z, 2 * y * z - 2 * w * x,
                          2 * z * x - 2 * w * y,     2 * y * z + 2 * w * x,     1 - 2 * x * x - 2 * y * y};
     for (int k = 0; k < 9; ++k) R[k] = (float)r[k];
+}
+
+bool resolve_image(const Dataset& d, size_t index, std::string* file, bool* is_jpeg, std::string* err) {
+    if (index >= d.images.size()) return fail(err, "image index out of range");
+    const fs::path named = fs::path(d.root) / "images" / d.images[index].name;
+    *is_jpeg = false;
+    if (path_exists(named)) {
+        std::string ext = named.extension().string();
+        for (char& c : ext) c = (char)tolower((unsigned char)c);
+        *is_jpeg = ext == ".jpg" || ext == ".jpeg";
+        *file = named.string();
+        return true;
+    }
+    for (const char* ext : {".ppm", ".jpg", ".jpeg", ".JPG", ".JPEG"}) {
+        fs::path alt = named;
+        alt.replace_extension(ext);
+        if (path_exists(alt)) { *is_jpeg = ext[1] != 'p'; *file = alt.string(); return true; }
+    }
+    fs::path ppm = named;
+    ppm.replace_extension(".ppm");
+    const std::string stem = named.stem().string();
+    return fail(err, "image " + named.string() + " does not exist (nor " + ppm.filename().string() + "); JPEG and PNG are not decoded here, convert the images to PPM" +
+                         " — nor is there a JPEG for the loader to decode under " + stem + ".jpg, " + stem + ".jpeg, " + stem + ".JPG or " + stem + ".JPEG");
 }
 
 bool read_image(const Dataset& d, size_t index, std::vector<uint8_t>* rgb, std::string* err) {

@@ -2,7 +2,9 @@
 // text) plus undistorted images. Host only, no GPU dependency; every malformed input is a `false` with a message, never a crash and
 // never an allocation sized by an unchecked count field.
 //   <path>/sparse/0/ (tried first) or <path>/sparse/: cameras, images, points3D as .bin (preferred) or .txt
-//   <path>/images/<name>: binary PPM (P6, maxval 255); a name whose file is absent is retried with its extension replaced by .ppm
+//   <path>/images/<name>: binary PPM (P6, maxval 255), or baseline JPEG when the file's extension is .jpg / .jpeg in any case (decoded by
+//                         jpeg_io.hpp + dvs_jpeg_reconstruct, not here); a name whose file is absent is retried with its extension replaced
+//                         by .ppm, then .jpg, .jpeg, .JPG, .JPEG
 //   <path>/masks/<stem>.pgm (P5, maxval 255): > 127 is trainable; a missing file means all ones
 // Camera models: SIMPLE_PINHOLE and PINHOLE only — anything else has to be undistorted first (the lineage's own requirement).
 #pragma once
@@ -40,7 +42,10 @@ const char* model_name(int model);      // "SIMPLE_PINHOLE", "PINHOLE", ... ("?"
 
 // the sparse model under `path`; images and masks are read one by one with the calls below
 bool read_dataset(const std::string& path, Dataset* out, std::string* err);
-// image `index` as interleaved 8-bit RGB [H][W][3]; its size must equal its camera's
+// the file of image `index` and whether it is a JPEG: an existing <name> is a JPEG by its extension (.jpg / .jpeg, any case) and a PPM
+// otherwise; an absent one is retried as <stem>.ppm, then <stem>.jpg, .jpeg, .JPG, .JPEG
+bool resolve_image(const Dataset& d, size_t index, std::string* file, bool* is_jpeg, std::string* err);
+// image `index` as interleaved 8-bit RGB [H][W][3]; its size must equal its camera's (PPM only: <name>, else <stem>.ppm)
 bool read_image(const Dataset& d, size_t index, std::vector<uint8_t>* rgb, std::string* err);
 // its mask as [H][W] bytes in {0, 1}; all ones when <root>/masks/<stem>.pgm does not exist
 bool read_mask(const Dataset& d, size_t index, std::vector<uint8_t>* mask, std::string* err);

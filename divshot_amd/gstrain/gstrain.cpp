@@ -94,7 +94,8 @@ void GaussianTrainerScene::trainStep() {
         m.prune_light(s.it);
         pruenIteraions.push_back(s.it);
     }
-    if (m.cfg.verbose && m.rank == 0 && (m.step % 100 == 0))          // same line the editor logs (application/editor/source/editor.cpp:1554)
+    // same line the editor logs (application/editor/source/editor.cpp:1554), every 100 steps as there unless DVS_LOSS_EVERY said otherwise at load
+    if (m.cfg.verbose && m.rank == 0 && (m.step % m.loss_every == 0))
         logf_("Iteraions %d, loss : %f", m.step, (double)getCurrentLoss());
     m.step = s.it;
     curIteration = s.it;

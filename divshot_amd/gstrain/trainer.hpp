@@ -110,6 +110,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     // evaluation is off — the draw is then the reference's, over all cameras. The test views are rendered by a context of their own:
     // the training context's saved forward state, pending backward rows and prepared projection are never touched by an evaluation.
     int eval_holdout = 0, eval_every = 0;
+    int loss_every = 100;                                                    // steps between two loss log lines (DVS_LOSS_EVERY, read at load)
     std::vector<int> train_idx, test_idx;
     int eval_views = 0;                                                      // min(n_test, 8) views per pass of eval_ctx
     DevBuf<float> d_eval_out; DevBuf<void> d_eval_scratch; DevBuf<double> d_eval_res;

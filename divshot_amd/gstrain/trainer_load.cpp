@@ -1,11 +1,79 @@
 // trainer_load.cpp — load_train_data: the synthetic-scene and capture-directory loaders and the allocations they share.
 #include "trainer.hpp"
+#include <condition_variable>
+#include <mutex>
+#include <thread>
+#include "jpeg_io.hpp"
+#include "../../include/dvs_image.h"
 
 namespace {
 __global__ void k_pack_u8(const float* __restrict__ src, uint8_t* __restrict__ dst, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = (uint8_t)fminf(255.f, fmaxf(0.f, rintf(src[i] * 255.f)));
 }
+
+// Host threads that entropy-decode the JPEG images of a capture ahead of the loader: entropy decoding is the serial cost of a JPEG, so up
+// to `threads` files are decoded at once, never more than `window` images beyond the one the loader has taken (the memory held is
+// bounded by the window, not by the capture). take() hands the images out strictly in order, so nothing depends on the thread count.
+class JpegAhead {
+public:
+    struct Result { gsjpeg::Frame frame; std::string err; bool ok = false, done = false; };
+    JpegAhead(std::vector<std::string> files, int threads) : files_(std::move(files)), slots_(files_.size()), window_(2 * (size_t)threads) {
+        for (int t = 0; t < threads && (size_t)t < files_.size(); ++t) workers_.emplace_back([this] { work(); });
+    }
+    ~JpegAhead() {
+        { std::lock_guard<std::mutex> lock(m_); stop_ = true; }
+        cv_.notify_all();
+        for (std::thread& t : workers_) t.join();
+    }
+    Result take(size_t i) {                                  // i = 0, 1, 2, ... in this order
+        std::unique_lock<std::mutex> lock(m_);
+        cv_.wait(lock, [&] { return slots_[i].done; });
+        Result r = std::move(slots_[i]);
+        slots_[i] = Result();
+        taken_ = i + 1;
+        lock.unlock();
+        cv_.notify_all();
+        return r;
+    }
+    double wall_ms() {                                       // wall time during which at least one thread was decoding: waits on a full window are not in it
+        std::lock_guard<std::mutex> lock(m_);
+        return busy_ms_;
+    }
+
+private:
+    void work() {
+        for (;;) {
+            size_t i;
+            {
+                std::unique_lock<std::mutex> lock(m_);
+                cv_.wait(lock, [&] { return stop_ || next_ >= files_.size() || next_ < taken_ + window_; });
+                if (stop_ || next_ >= files_.size()) return;
+                i = next_++;
+                if (busy_++ == 0) busy_since_ = std::chrono::steady_clock::now();
+            }
+            Result r;
+            r.ok = gsjpeg::decode_coefficients(files_[i], &r.frame, &r.err);
+            r.done = true;
+            {
+                std::lock_guard<std::mutex> lock(m_);
+                slots_[i] = std::move(r);
+                if (--busy_ == 0) busy_ms_ += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - busy_since_).count();
+            }
+            cv_.notify_all();
+        }
+    }
+    std::vector<std::string> files_;
+    std::vector<Result> slots_;
+    size_t window_, next_ = 0, taken_ = 0;
+    bool stop_ = false;
+    int busy_ = 0;                                           // threads inside a decode
+    double busy_ms_ = 0;
+    std::chrono::steady_clock::time_point busy_since_;
+    std::mutex m_;
+    std::condition_variable cv_;
+    std::vector<std::thread> workers_;
+};
 
 struct Lcg {       // tiny deterministic noise source for the synthetic initialisation
     uint64_t s;
@@ -92,6 +160,7 @@ void GaussianTrainerScene::Impl::store_view(DevBuf<float> image, DevBuf<float> m
 // the train / test split of cfg.evalHoldout (DVS_EVAL_HOLDOUT): a function of the camera index alone, so every rank derives the same one
 void GaussianTrainerScene::Impl::setup_split() {
     eval_holdout = env_int("DVS_EVAL_HOLDOUT", cfg.evalHoldout); eval_every = env_int("DVS_EVAL_EVERY", cfg.evalEvery);
+    loss_every = std::max(1, env_int("DVS_LOSS_EVERY", 100));
     train_idx.clear(); test_idx.clear();
     if (eval_holdout <= 0) { eval_holdout = 0; return; }
     for (int c = 0; c < (int)cams.size(); ++c) (c % eval_holdout == 0 ? test_idx : train_idx).push_back(c);
@@ -240,7 +309,9 @@ bool GaussianTrainerScene::Impl::load_synthetic(const std::string& spec_str) {
     return true;
 }
 
-// A capture directory: a COLMAP sparse model and undistorted PPM images (dataset_io.hpp). The views go up as bytes and are box-filtered
+// A capture directory: a COLMAP sparse model and undistorted images, binary PPM or baseline JPEG (dataset_io.hpp). A JPEG is entropy-decoded
+// on the host (jpeg_io.hpp, ahead of the loop by JpegAhead) and reconstructed on the device (dvs_jpeg_reconstruct) into the same planar
+// bytes a PPM is uploaded as; everything after that is one path. The views go up as bytes and are box-filtered
 // on the device when maxImageWidth / maxImageHeight ask for it; the splats start from the sparse points (include/dvs_init.h).
 bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
     gsdata::Dataset ds;
@@ -284,19 +355,63 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
     const size_t P = (size_t)W * H, img = 3 * P;
     std::vector<uint8_t> px, planar, mk;
     std::vector<float> mkf;
+    // which file each image is read from; the JPEGs among them are decoded ahead by DVS_LOAD_THREADS host threads (default 8, 1..16:
+    // never sized from the machine's CPU count)
+    std::vector<std::string> jpeg_files, jpeg_names;
+    std::vector<char> is_jpeg(ds.images.size(), 0);
+    for (size_t i = 0; i < ds.images.size(); ++i) {
+        std::string file;
+        bool jpeg = false;
+        if (!gsdata::resolve_image(ds, i, &file, &jpeg, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
+        is_jpeg[i] = jpeg ? 1 : 0;
+        if (jpeg) jpeg_files.push_back(file);
+    }
+    jpeg_names = jpeg_files;
+    const size_t n_jpeg = jpeg_files.size();
+    const int load_threads = std::max(1, std::min(env_int("DVS_LOAD_THREADS", 8), 16));
+    JpegAhead ahead(std::move(jpeg_files), load_threads);
+    Event ev_j0, ev_j1;
+    if (n_jpeg) {
+        for (Event* e : {&ev_j0, &ev_j1}) { hipEvent_t ev = nullptr; HIP_OR_THROW(hipEventCreate(&ev)); e->reset(ev); }
+    }
+    double recon_ms = 0;
+    size_t jpeg_at = 0;
     for (size_t i = 0; i < ds.images.size(); ++i) {
         const gsdata::Image& im = ds.images[i];
         const gsdata::Camera& c = ds.cameras[im.camera];
         const int w = (int)c.width, h = (int)c.height, d = factor[i];
         const size_t p0 = (size_t)w * h;
-        if (!gsdata::read_image(ds, i, &px, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-        planar.resize(3 * p0);                                  // the file is [H][W][3], the trainer's views are planar [3][H][W]
-        for (size_t q = 0; q < p0; ++q) for (int k = 0; k < 3; ++k) planar[(size_t)k * p0 + q] = px[3 * q + k];
         // 1. the view as bytes; 2. box-filtered by the image's factor (rounded back to 8 bits when the views are kept as bytes) unless the
         // bytes are the view as they are; 3. its mask. The owners free whatever an early return or a throw leaves behind.
         DevBuf<uint8_t> full8(3 * p0);
         DevBuf<float> t, mask;
-        HIP_OR_THROW(hipMemcpy(full8.get(), planar.data(), 3 * p0, hipMemcpyHostToDevice));
+        if (is_jpeg[i]) {
+            JpegAhead::Result r = ahead.take(jpeg_at++);
+            if (!r.ok) { logf_("load_train_data('%s'): %s", path.c_str(), r.err.c_str()); return false; }
+            const gsjpeg::Frame& f = r.frame;
+            if (f.width != w || f.height != h) {
+                logf_("load_train_data('%s'): %s is %dx%d but its camera %u is %dx%d", path.c_str(), jpeg_names[jpeg_at - 1].c_str(), f.width, f.height, c.id, w, h);
+                return false;
+            }
+            dvs_jpeg_desc desc{};
+            desc.width = f.width; desc.height = f.height; desc.components = f.components; desc.hs = f.hs[0]; desc.vs = f.vs[0];
+            for (int k = 0; k < 3; ++k) { desc.blocks_w[k] = f.blocks_w[k]; desc.blocks_h[k] = f.blocks_h[k]; desc.offset[k] = f.offset[k]; }
+            memcpy(desc.quant, f.quant, sizeof desc.quant);
+            DevBuf<int16_t> d_coef(f.coef.size() * sizeof(int16_t));
+            HIP_OR_THROW(hipMemcpy(d_coef.get(), f.coef.data(), f.coef.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+            HIP_OR_THROW(hipEventRecord(ev_j0.get(), stream.get()));
+            DVS_OR_THROW(dvs_jpeg_reconstruct(stream.get(), &desc, d_coef.get(), full8.get()));
+            HIP_OR_THROW(hipEventRecord(ev_j1.get(), stream.get()));
+            HIP_OR_THROW(hipEventSynchronize(ev_j1.get()));          // the coefficients are freed at the end of this scope
+            float ms = 0;
+            HIP_OR_THROW(hipEventElapsedTime(&ms, ev_j0.get(), ev_j1.get()));
+            recon_ms += ms;
+        } else {
+            if (!gsdata::read_image(ds, i, &px, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
+            planar.resize(3 * p0);                              // the file is [H][W][3], the trainer's views are planar [3][H][W]
+            for (size_t q = 0; q < p0; ++q) for (int k = 0; k < 3; ++k) planar[(size_t)k * p0 + q] = px[3 * q + k];
+            HIP_OR_THROW(hipMemcpy(full8.get(), planar.data(), 3 * p0, hipMemcpyHostToDevice));
+        }
         if (!(u8 && d == 1)) {
             t.alloc(img * sizeof(float));
             const dvs_downsample_view dv{full8.get(), t.get()};
@@ -334,6 +449,9 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
         if (factor[0] > 1) snprintf(lvl, sizeof lvl, " -> %dx%d (1/%d)", W, H, factor[0]);
         logf_("dataset: %zu cameras (%s), %dx%d%s, %d points (%zu dropped)", ds.images.size(), one_model ? gsdata::model_name(model) : "mixed pinhole models",
               W0, H0, lvl, n_pts, ds.dropped);
+        if (n_jpeg)
+            logf_("dataset: jpeg: %zu of %zu images, entropy decode %.3f ms (host, %d threads, wall), reconstruction %.3f ms (device, events)", n_jpeg,
+                  ds.images.size(), ahead.wall_ms(), load_threads, recon_ms);
     }
     // 4. the points, 5. their 3-NN scales and the initial parameters, straight into the parameter arrays
     {
