@@ -195,16 +195,33 @@ _INIT_PROTOS = {
     "dvs_knn_mean_dist2_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dvs_init_from_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
-# include/dvs_image.h: JPEG reconstruction from quantised DCT coefficients
+# include/dvs_image.h: JPEG reconstruction from quantised DCT coefficients; undistortion of a distorted COLMAP camera's view
 class JpegDesc(C.Structure):           # dvs_jpeg_desc
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("components", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32),
                 ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3), ("_pad", C.c_int32), ("offset", C.c_uint64 * 3),
                 ("quant", (C.c_uint16 * 64) * 3)]
 
 
+class UndistortDesc(C.Structure):      # dvs_undistort_desc
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32)] + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "ifx", "ify", "k1", "k2", "p1", "p2")]
+
+
 _IMAGE_PROTOS = {
     "dvs_jpeg_reconstruct": (C.c_int, [C.c_void_p, C.POINTER(JpegDesc), C.c_void_p, C.c_void_p]),
+    "dvs_undistort_desc_from_colmap": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(UndistortDesc)]),
+    "dvs_undistort_view": (C.c_int, [C.c_void_p, C.POINTER(UndistortDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+
+
+def undistort_desc(model, params, width, height):
+    """-> UndistortDesc of COLMAP model id 2, 3 or 4 and its parameter list (dvs_undistort_desc_from_colmap); DvsError when refused"""
+    prm = (C.c_double * len(params))(*[float(v) for v in params])
+    if len(params) != {2: 4, 3: 5, 4: 8}.get(int(model), -1):
+        raise DvsError(f"camera model {model} with {len(params)} parameters has no undistortion descriptor")
+    d = UndistortDesc()
+    if lib.dvs_undistort_desc_from_colmap(int(model), prm, int(width), int(height), C.byref(d)) != 0:
+        raise DvsError(f"dvs_undistort_desc_from_colmap refused model {model}, {width}x{height}, {list(params)}")
+    return d
 for _name, (_res, _args) in list(_PROTOS.items()) + list(_EXPORT_PROTOS.items()) + list(_INIT_PROTOS.items()) + list(_IMAGE_PROTOS.items()):
     _f = getattr(lib, _name)          # AttributeError here = the .so does not export a declared symbol
     _f.restype = _res

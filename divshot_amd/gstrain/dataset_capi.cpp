@@ -22,6 +22,15 @@ GSDATA_API void* gstrain_dataset_open(const char* path, char* err, int cap) {
     if (!path || !gsdata::read_dataset(path, d, &msg)) { report(false, path ? msg : "NULL path", err, cap); delete d; return nullptr; }
     return d;
 }
+// flags: bit 0 = accept the distorted models SIMPLE_RADIAL, RADIAL and OPENCV (gsdata::ReadOptions::accept_distorted)
+GSDATA_API void* gstrain_dataset_open_ex(const char* path, uint32_t flags, char* err, int cap) {
+    gsdata::Dataset* d = new gsdata::Dataset();
+    gsdata::ReadOptions opt;
+    opt.accept_distorted = (flags & 1u) != 0;
+    std::string msg;
+    if (!path || !gsdata::read_dataset(path, opt, d, &msg)) { report(false, path ? msg : "NULL path", err, cap); delete d; return nullptr; }
+    return d;
+}
 GSDATA_API void gstrain_dataset_close(void* h) { delete (gsdata::Dataset*)h; }
 // counts[5] = {cameras, images, points, dropped points, 1 if the model was read from .bin files}
 GSDATA_API int gstrain_dataset_counts(const void* h, uint64_t* counts) {
@@ -37,6 +46,13 @@ GSDATA_API int gstrain_dataset_camera(const void* h, uint64_t index, uint64_t* i
     const gsdata::Camera& c = d->cameras[index];
     ints[0] = c.id; ints[1] = (uint64_t)c.model; ints[2] = c.width; ints[3] = c.height;
     params[0] = c.fx; params[1] = c.fy; params[2] = c.cx; params[3] = c.cy;
+    return 0;
+}
+// k[4] = {k1, k2, p1, p2} of camera `index` (zeros for a pinhole model)
+GSDATA_API int gstrain_dataset_camera_distortion(const void* h, uint64_t index, double* k) {
+    const gsdata::Dataset* d = (const gsdata::Dataset*)h;
+    if (!d || !k || index >= d->cameras.size()) return 1;
+    for (int i = 0; i < 4; ++i) k[i] = d->cameras[index].dist[i];
     return 0;
 }
 // image `index` in name order: ints[3] = {image id, camera id, index of its camera}, pose[7] = {qw, qx, qy, qz, tx, ty, tz},

@@ -23,7 +23,11 @@ const int kModelParams[] = {3, 4, 4, 5, 8, 8, 12, 5, 4, 5, 12};
 constexpr int kNumModels = 11;
 constexpr uint64_t kMaxSide = 1u << 16;                    // an image side beyond this is a corrupt field, not a photograph
 
-std::string undistort_hint(const std::string& model) {
+// the reader that takes pinhole models only (the default) and the one that also takes the three models the loader undistorts
+std::string undistort_hint(const std::string& model, bool accept_distorted = false) {
+    if (accept_distorted)
+        return "camera model " + model + " is not supported: SIMPLE_PINHOLE and PINHOLE are read as they are, SIMPLE_RADIAL, RADIAL and OPENCV "
+               "are undistorted by the loader; undistort a capture of any other model first (colmap image_undistorter)";
     return "camera model " + model + " is not supported: only SIMPLE_PINHOLE and PINHOLE are; undistort the capture first "
            "(colmap image_undistorter), as the lineage requires";
 }
@@ -57,15 +61,21 @@ struct Cursor {                          // little-endian fields out of a byte b
     template <class T> T get() { T v; take(&v, sizeof v); return v; }
 };
 
-bool finish_camera(Camera& c, const double* prm, const std::string& where, std::string* err) {
+bool model_accepted(int model, bool accept_distorted) { return model <= 1 || (accept_distorted && model <= 4); }
+
+bool finish_camera(Camera& c, const double* prm, const std::string& where, bool accept_distorted, std::string* err) {
     if (c.model < 0 || c.model >= kNumModels) return fail(err, where + ": unknown camera model id " + std::to_string(c.model));
-    if (c.model > 1) return fail(err, where + ": " + undistort_hint(kModels[c.model]));
+    if (!model_accepted(c.model, accept_distorted)) return fail(err, where + ": " + undistort_hint(kModels[c.model], accept_distorted));
     if (c.width == 0 || c.height == 0 || c.width > kMaxSide || c.height > kMaxSide)
         return fail(err, where + ": camera " + std::to_string(c.id) + " has size " + std::to_string(c.width) + "x" + std::to_string(c.height));
-    if (c.model == 0) { c.fx = c.fy = prm[0]; c.cx = prm[1]; c.cy = prm[2]; }
-    else { c.fx = prm[0]; c.fy = prm[1]; c.cx = prm[2]; c.cy = prm[3]; }
+    if (c.model == 0 || c.model == 2 || c.model == 3) { c.fx = c.fy = prm[0]; c.cx = prm[1]; c.cy = prm[2]; }      // f cx cy [k1 [k2]]
+    else { c.fx = prm[0]; c.fy = prm[1]; c.cx = prm[2]; c.cy = prm[3]; }                                           // fx fy cx cy [k1 k2 p1 p2]
+    if (c.model == 2 || c.model == 3) { c.dist[0] = prm[3]; if (c.model == 3) c.dist[1] = prm[4]; }
+    if (c.model == 4) for (int k = 0; k < 4; ++k) c.dist[k] = prm[4 + k];
     if (!(c.fx > 0) || !(c.fy > 0) || !std::isfinite(c.fx) || !std::isfinite(c.fy) || !std::isfinite(c.cx) || !std::isfinite(c.cy))
         return fail(err, where + ": camera " + std::to_string(c.id) + " has a focal length or principal point that is not a positive / finite number");
+    for (double k : c.dist)
+        if (!std::isfinite(k)) return fail(err, where + ": camera " + std::to_string(c.id) + " has a distortion coefficient that is not a finite number");
     return true;
 }
 
@@ -77,7 +87,7 @@ void add_point(Dataset* d, const double xyz[3], const uint8_t rgb[3]) {
 }
 
 // ---- binary ----
-bool cameras_bin(const std::string& file, Dataset* d, std::string* err) {
+bool cameras_bin(const std::string& file, bool accept_distorted, Dataset* d, std::string* err) {
     std::vector<uint8_t> buf;
     if (!read_file(file, &buf, err)) return false;
     Cursor c(buf);
@@ -92,7 +102,7 @@ bool cameras_bin(const std::string& file, Dataset* d, std::string* err) {
         double prm[12] = {0};
         c.take(prm, sizeof(double) * (size_t)kModelParams[cam.model]);
         if (!c.ok) return fail(err, file + ": truncated in the parameters of camera record " + std::to_string(i));
-        if (!finish_camera(cam, prm, file, err)) return false;
+        if (!finish_camera(cam, prm, file, accept_distorted, err)) return false;
         d->cameras.push_back(cam);
     }
     if (c.left) return fail(err, file + ": " + std::to_string(c.left) + " bytes after the last camera record");
@@ -184,7 +194,7 @@ bool to_u64(const std::string& s, uint64_t* v) {
     return e == s.c_str() + s.size() && errno == 0;
 }
 
-bool cameras_txt(const std::string& file, Dataset* d, std::string* err) {
+bool cameras_txt(const std::string& file, bool accept_distorted, Dataset* d, std::string* err) {
     Lines L;
     if (!L.load(file, err)) return false;
     for (size_t ln = 0; ln < L.v.size(); ++ln) {
@@ -199,11 +209,11 @@ bool cameras_txt(const std::string& file, Dataset* d, std::string* err) {
         cam.model = -1;
         for (int m = 0; m < kNumModels; ++m) if (t[1] == kModels[m]) cam.model = m;
         if (cam.model < 0) return fail(err, where + ": unknown camera model " + t[1]);
-        if (cam.model > 1) return fail(err, where + ": " + undistort_hint(t[1]));
+        if (!model_accepted(cam.model, accept_distorted)) return fail(err, where + ": " + undistort_hint(t[1], accept_distorted));
         if (t.size() != 4 + (size_t)kModelParams[cam.model]) return fail(err, where + ": " + t[1] + " takes " + std::to_string(kModelParams[cam.model]) + " parameters");
         double prm[12] = {0};
         for (int k = 0; k < kModelParams[cam.model]; ++k) if (!to_double(t[4 + (size_t)k], &prm[k])) return fail(err, where + ": bad camera parameter");
-        if (!finish_camera(cam, prm, where, err)) return false;
+        if (!finish_camera(cam, prm, where, accept_distorted, err)) return false;
         d->cameras.push_back(cam);
     }
     return true;
@@ -290,7 +300,9 @@ bool read_pnm(const std::string& file, int channels, int* width, int* height, st
     return true;
 }
 
-bool read_dataset(const std::string& path, Dataset* d, std::string* err) {
+bool read_dataset(const std::string& path, Dataset* d, std::string* err) { return read_dataset(path, ReadOptions(), d, err); }
+
+bool read_dataset(const std::string& path, const ReadOptions& opt, Dataset* d, std::string* err) {
     *d = Dataset();
     d->root = path;
     std::error_code ec;
@@ -309,7 +321,7 @@ bool read_dataset(const std::string& path, Dataset* d, std::string* err) {
         return fail(err, "no COLMAP sparse model under " + path + ": cameras, images and points3D (.bin or .txt) are looked for in sparse/0/, then sparse/");
     if (!fs::is_directory(fs::path(path) / "images", ec)) return fail(err, "no images/ directory under " + path);
     const std::string base = d->sparse_dir + "/", ext = d->binary ? ".bin" : ".txt";
-    if (!(d->binary ? cameras_bin(base + "cameras" + ext, d, err) : cameras_txt(base + "cameras" + ext, d, err))) return false;
+    if (!(d->binary ? cameras_bin(base + "cameras" + ext, opt.accept_distorted, d, err) : cameras_txt(base + "cameras" + ext, opt.accept_distorted, d, err))) return false;
     if (!(d->binary ? images_bin(base + "images" + ext, d, err) : images_txt(base + "images" + ext, d, err))) return false;
     if (!(d->binary ? points_bin(base + "points3D" + ext, d, err) : points_txt(base + "points3D" + ext, d, err))) return false;
     if (d->cameras.empty()) return fail(err, d->sparse_dir + ": no cameras");

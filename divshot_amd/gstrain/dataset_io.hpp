@@ -1,12 +1,15 @@
 // dataset_io.hpp — reader of the capture format the lineage trains from: a COLMAP sparse model (cameras / images / points3D, binary or
-// text) plus undistorted images. Host only, no GPU dependency; every malformed input is a `false` with a message, never a crash and
+// text) plus its images. Host only, no GPU dependency; every malformed input is a `false` with a message, never a crash and
 // never an allocation sized by an unchecked count field.
 //   <path>/sparse/0/ (tried first) or <path>/sparse/: cameras, images, points3D as .bin (preferred) or .txt
 //   <path>/images/<name>: binary PPM (P6, maxval 255), or baseline JPEG when the file's extension is .jpg / .jpeg in any case (decoded by
 //                         jpeg_io.hpp + dvs_jpeg_reconstruct, not here); a name whose file is absent is retried with its extension replaced
 //                         by .ppm, then .jpg, .jpeg, .JPG, .JPEG
 //   <path>/masks/<stem>.pgm (P5, maxval 255): > 127 is trainable; a missing file means all ones
-// Camera models: SIMPLE_PINHOLE and PINHOLE only — anything else has to be undistorted first (the lineage's own requirement).
+// Camera models: SIMPLE_PINHOLE and PINHOLE by default — anything else is refused with the hint to undistort the capture first (the
+// lineage's own requirement). With ReadOptions::accept_distorted also SIMPLE_RADIAL, RADIAL and OPENCV, whose coefficients come back
+// in Camera::dist: the trainer's loader undistorts their views on the device (include/dvs_image.h: dvs_undistort_view). The fisheye
+// models, FULL_OPENCV and FOV stay refused either way: they need atan or a division, and a pinhole target suits no wide fisheye.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -17,9 +20,10 @@ namespace gsdata {
 
 struct Camera {
     uint32_t id = 0;
-    int model = 0;                       // COLMAP model id: 0 SIMPLE_PINHOLE, 1 PINHOLE
+    int model = 0;                       // COLMAP model id: 0 SIMPLE_PINHOLE, 1 PINHOLE; with accept_distorted also 2 SIMPLE_RADIAL, 3 RADIAL, 4 OPENCV
     uint64_t width = 0, height = 0;
     double fx = 0, fy = 0, cx = 0, cy = 0;
+    double dist[4] = {0, 0, 0, 0};       // k1, k2, p1, p2 (the coefficients a model lacks are 0)
 };
 struct Image {
     uint32_t id = 0, camera_id = 0;
@@ -42,6 +46,10 @@ const char* model_name(int model);      // "SIMPLE_PINHOLE", "PINHOLE", ... ("?"
 
 // the sparse model under `path`; images and masks are read one by one with the calls below
 bool read_dataset(const std::string& path, Dataset* out, std::string* err);
+struct ReadOptions {
+    bool accept_distorted = false;      // also read SIMPLE_RADIAL, RADIAL and OPENCV cameras (fx, fy, cx, cy and dist)
+};
+bool read_dataset(const std::string& path, const ReadOptions& opt, Dataset* out, std::string* err);
 // the file of image `index` and whether it is a JPEG: an existing <name> is a JPEG by its extension (.jpg / .jpeg, any case) and a PPM
 // otherwise; an absent one is retried as <stem>.ppm, then <stem>.jpg, .jpeg, .JPG, .JPEG
 bool resolve_image(const Dataset& d, size_t index, std::string* file, bool* is_jpeg, std::string* err);

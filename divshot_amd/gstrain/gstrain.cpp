@@ -12,9 +12,10 @@
 // with ONE RCCL all-reduce over xGMI (include/dvs_comm.h), the densification statistics likewise before each refinement, and the
 // optimizer / densifier run replicated and deterministic so that the replicas stay bit-identical.
 // With resolutionSchedule > 0 the first steps train coarse to fine: on box-filtered views of 1/2^k the size, through level cameras.
-// load_train_data accepts a capture directory (a COLMAP sparse model plus undistorted PPM images: dataset_io.hpp; the splats start from
-// the sparse points, include/dvs_init.h) or a synthetic-scene spec. Out of scope: JPEG / PNG
-// decoding, distorted camera models, mesh export, the 2DGS model type. Every GaussianTrainConfig field the hosts set is either
+// load_train_data accepts a capture directory (a COLMAP sparse model plus PPM or baseline JPEG images: dataset_io.hpp; views of
+// SIMPLE_RADIAL / RADIAL / OPENCV cameras are undistorted on the device, include/dvs_image.h; the splats start from the sparse points,
+// include/dvs_init.h) or a synthetic-scene spec. Out of scope: PNG and progressive-JPEG
+// decoding, fisheye / FULL_OPENCV / FOV camera models, mesh export, the 2DGS model type. Every GaussianTrainConfig field the hosts set is either
 // honoured or named in the one-time "ignored" line of report_config().
 #include "trainer.hpp"
 

@@ -78,14 +78,17 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
                                                                              // exchange is asserted by tests/test_gpu_multirank.py::test_plugin_two_ranks_exchanges_agree)
     // The training views, one entry per camera of `cams`: the image as fp32 or, when packLevel has PackF32ToU8, as 8 bits per channel
     // (gs_train.cpp:91-96, the reference's VRAM saver: a quarter of the HBM footprint, expanded into d_target_f32 right before the
-    // loss), and the camera's mask when useMask was on at load time
+    // loss), and the camera's mask when useMask was on at load time or the capture had a distorted camera (`undistorted`: the views of
+    // SIMPLE_RADIAL / RADIAL / OPENCV cameras were remapped to pinhole views at load time and their pixels without a source are masked
+    // out; every view of such a capture carries a mask, a pinhole view's being its file mask or all ones)
     struct View { DevBuf<float> f32; DevBuf<uint8_t> u8; DevBuf<float> mask; };
     std::vector<View> views;
     std::vector<dvs_camera> cams;
     DevBuf<float> d_target_f32;
     bool views_u8() const { return (cfg.packLevel & PackF32ToU8) != 0; }
     const void* view_pixels(size_t ci) const { return views_u8() ? (const void*)views[ci].u8.get() : (const void*)views[ci].f32.get(); }
-    const float* view_mask(size_t ci) const { return cfg.useMask ? views[ci].mask.get() : nullptr; }   // (nullptr too when loaded without masks)
+    bool undistorted = false;
+    const float* view_mask(size_t ci) const { return cfg.useMask || undistorted ? views[ci].mask.get() : nullptr; }   // (nullptr too when loaded without masks)
     void store_view(DevBuf<float> image, DevBuf<float> mask);
     std::vector<float> init_host[6];                                         // initial splats (resetGaussian, getPoints3D)
     bool terminate = false, pruning = false;

@@ -189,7 +189,7 @@ void GaussianTrainerScene::Impl::setup_levels() {
     if (res_levels == 0) return;
     const size_t P = (size_t)(W / 2) * (size_t)(H / 2);
     d_level_targets.alloc((size_t)vpi * 3 * P * sizeof(float) + 16);
-    if (cfg.useMask) d_level_masks.alloc((size_t)vpi * P * sizeof(float) + 16);
+    if (cfg.useMask || undistorted) d_level_masks.alloc((size_t)vpi * P * sizeof(float) + 16);
 }
 
 // factorised exchange: the SH rows are not written by the backward, only each view's colour gradient, which leaves right after
@@ -309,14 +309,18 @@ bool GaussianTrainerScene::Impl::load_synthetic(const std::string& spec_str) {
     return true;
 }
 
-// A capture directory: a COLMAP sparse model and undistorted images, binary PPM or baseline JPEG (dataset_io.hpp). A JPEG is entropy-decoded
+// A capture directory: a COLMAP sparse model and its images, binary PPM or baseline JPEG (dataset_io.hpp). A JPEG is entropy-decoded
 // on the host (jpeg_io.hpp, ahead of the loop by JpegAhead) and reconstructed on the device (dvs_jpeg_reconstruct) into the same planar
-// bytes a PPM is uploaded as; everything after that is one path. The views go up as bytes and are box-filtered
+// bytes a PPM is uploaded as. The view of a SIMPLE_RADIAL / RADIAL / OPENCV camera is then remapped on the device into the view of the
+// pinhole camera with the same fx, fy, cx, cy and size (dvs_undistort_view); the pixels without a source are blank and masked out, not
+// cropped, so a capture with one such camera carries a mask on every view. Everything after that is one path. The views go up as bytes and are box-filtered
 // on the device when maxImageWidth / maxImageHeight ask for it; the splats start from the sparse points (include/dvs_init.h).
 bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
     gsdata::Dataset ds;
     std::string err;
-    if (!gsdata::read_dataset(path, &ds, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
+    gsdata::ReadOptions read_opt;
+    read_opt.accept_distorted = true;
+    if (!gsdata::read_dataset(path, read_opt, &ds, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
     const int n_pts = (int)std::min<size_t>(ds.xyz.size() / 3, (size_t)0x7FFFFFFF);
     if (n_pts <= 0) {
         logf_("load_train_data('%s'): the sparse model has no usable points (%zu dropped); initialisation without a point cloud is out of scope", path.c_str(), ds.dropped);
@@ -327,8 +331,13 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
     std::vector<int> factor(ds.images.size(), 1);
     int W0 = 0, H0 = 0, model = -1;
     bool one_model = true;
+    const auto is_distorted = [](const gsdata::Camera& c) { return c.model >= 2 && c.model <= 4; };
+    size_t n_distorted = 0;
+    bool distorted_models[5] = {false, false, false, false, false};
+    undistorted = false;
     for (size_t i = 0; i < ds.images.size(); ++i) {
         const gsdata::Camera& c = ds.cameras[ds.images[i].camera];
+        if (is_distorted(c)) { ++n_distorted; distorted_models[c.model] = true; undistorted = true; }
         const int w = (int)c.width, h = (int)c.height;
         int d = 1;
         while (d <= 8 && (w / d > max_w || h / d > max_h)) d *= 2;
@@ -376,6 +385,17 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
     }
     double recon_ms = 0;
     size_t jpeg_at = 0;
+    // the undistortion's events and the count of pixels without a source, summed over the distorted views on the device
+    Event ev_u0, ev_u1;
+    DevBuf<uint32_t> d_invalid;
+    double undistort_ms = 0;
+    uint64_t undistort_pixels = 0;
+    if (undistorted) {
+        for (Event* e : {&ev_u0, &ev_u1}) { hipEvent_t ev = nullptr; HIP_OR_THROW(hipEventCreate(&ev)); e->reset(ev); }
+        d_invalid.alloc(sizeof(uint32_t));
+        HIP_OR_THROW(hipMemset(d_invalid.get(), 0, sizeof(uint32_t)));
+    }
+    const bool masked = cfg.useMask || undistorted;           // (a capture of pinhole cameras only: cfg.useMask, as ever)
     for (size_t i = 0; i < ds.images.size(); ++i) {
         const gsdata::Image& im = ds.images[i];
         const gsdata::Camera& c = ds.cameras[im.camera];
@@ -412,16 +432,46 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
             for (size_t q = 0; q < p0; ++q) for (int k = 0; k < 3; ++k) planar[(size_t)k * p0 + q] = px[3 * q + k];
             HIP_OR_THROW(hipMemcpy(full8.get(), planar.data(), 3 * p0, hipMemcpyHostToDevice));
         }
+        if (is_distorted(c)) {                                  // full8 := the pinhole camera's view; mask := valid and, with useMask, trainable
+            const double prm[8] = {c.fx, c.fy, c.cx, c.cy, c.dist[0], c.dist[1], c.dist[2], c.dist[3]};      // the camera in OPENCV's order (absent coefficients are 0)
+            dvs_undistort_desc desc;
+            if (dvs_undistort_desc_from_colmap(4, prm, w, h, &desc) != DVS_OK) {
+                logf_("load_train_data('%s'): the parameters of camera %u (%s) do not round to finite fp32 values", path.c_str(), c.id, gsdata::model_name(c.model));
+                return false;
+            }
+            DevBuf<uint8_t> pinhole(3 * p0), d_mk;
+            if (cfg.useMask) {
+                if (!gsdata::read_mask(ds, i, &mk, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
+                d_mk.alloc(p0);
+                HIP_OR_THROW(hipMemcpy(d_mk.get(), mk.data(), p0, hipMemcpyHostToDevice));
+            }
+            mask.alloc(p0 * sizeof(float));
+            HIP_OR_THROW(hipEventRecord(ev_u0.get(), stream.get()));
+            DVS_OR_THROW(dvs_undistort_view(stream.get(), &desc, 3, full8.get(), d_mk.get(), pinhole.get(), mask.get(), d_invalid.get()));
+            HIP_OR_THROW(hipEventRecord(ev_u1.get(), stream.get()));
+            HIP_OR_THROW(hipEventSynchronize(ev_u1.get()));          // the source bytes and the source mask are freed below
+            float ms = 0;
+            HIP_OR_THROW(hipEventElapsedTime(&ms, ev_u0.get(), ev_u1.get()));
+            undistort_ms += ms;
+            undistort_pixels += p0;
+            full8 = std::move(pinhole);
+        }
         if (!(u8 && d == 1)) {
             t.alloc(img * sizeof(float));
             const dvs_downsample_view dv{full8.get(), t.get()};
             DVS_OR_THROW(dvs_downsample_views(stream.get(), &dv, 1, 3, w, h, d, 1));
         }
-        if (cfg.useMask) {                                      // > 127 trains; a level mask keeps the box filter's fractional weights
-            if (!gsdata::read_mask(ds, i, &mk, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-            mkf.assign(mk.begin(), mk.end());
-            mask.alloc(p0 * sizeof(float));
-            HIP_OR_THROW(hipMemcpy(mask.get(), mkf.data(), p0 * sizeof(float), hipMemcpyHostToDevice));
+        if (masked) {                                           // > 127 trains; a level mask keeps the box filter's fractional weights
+            if (!is_distorted(c)) {                             // (a distorted view's mask came out of the undistortion)
+                if (cfg.useMask) {
+                    if (!gsdata::read_mask(ds, i, &mk, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
+                    mkf.assign(mk.begin(), mk.end());
+                } else {
+                    mkf.assign(p0, 1.f);                        // a pinhole view beside distorted ones, no mask files asked for
+                }
+                mask.alloc(p0 * sizeof(float));
+                HIP_OR_THROW(hipMemcpy(mask.get(), mkf.data(), p0 * sizeof(float), hipMemcpyHostToDevice));
+            }
             if (d > 1) {
                 DevBuf<float> md(P * sizeof(float));
                 const dvs_downsample_view dv{mask.get(), md.get()};
@@ -447,11 +497,19 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
     if (rank == 0) {
         char lvl[64] = "";
         if (factor[0] > 1) snprintf(lvl, sizeof lvl, " -> %dx%d (1/%d)", W, H, factor[0]);
-        logf_("dataset: %zu cameras (%s), %dx%d%s, %d points (%zu dropped)", ds.images.size(), one_model ? gsdata::model_name(model) : "mixed pinhole models",
+        logf_("dataset: %zu cameras (%s), %dx%d%s, %d points (%zu dropped)", ds.images.size(), one_model ? gsdata::model_name(model) : undistorted ? "mixed models" : "mixed pinhole models",
               W0, H0, lvl, n_pts, ds.dropped);
         if (n_jpeg)
             logf_("dataset: jpeg: %zu of %zu images, entropy decode %.3f ms (host, %d threads, wall), reconstruction %.3f ms (device, events)", n_jpeg,
                   ds.images.size(), ahead.wall_ms(), load_threads, recon_ms);
+        if (undistorted) {
+            uint32_t invalid = 0;
+            HIP_OR_THROW(hipMemcpy(&invalid, d_invalid.get(), sizeof invalid, hipMemcpyDeviceToHost));
+            std::string names;
+            for (int m = 2; m <= 4; ++m) if (distorted_models[m]) names += std::string(names.empty() ? "" : ", ") + gsdata::model_name(m);
+            logf_("dataset: undistort: %zu of %zu images (%s), %.3f ms (device, events), %u of %llu pixels have no source and are masked out", n_distorted,
+                  ds.images.size(), names.c_str(), undistort_ms, invalid, (unsigned long long)undistort_pixels);
+        }
     }
     // 4. the points, 5. their 3-NN scales and the initial parameters, straight into the parameter arrays
     {

@@ -45,7 +45,7 @@ void GaussianTrainerScene::Impl::report_config() const {
 
 // Held-out evaluation, on the training stream: the test cameras rendered from the current parameters at the full SH degree (what a
 // viewer shows from the saved PLY), min(n_test, 8) views per multi-view pass of a SEPARATE context, each pass scored by one
-// dvs_image_metrics_views call against the stored targets (8-bit ones as they are, the camera's mask when useMask), then ONE copy of
+// dvs_image_metrics_views call against the stored targets (8-bit ones as they are, the camera's mask when useMask or when the capture was undistorted), then ONE copy of
 // the [n_test][4] doubles to the host. Only rank 0 evaluates (the replicas are identical). -> false when evaluation is off.
 // A save right after the step that was just scored (evalEvery divides the iteration) writes that result: the parameters are the same.
 bool GaussianTrainerScene::Impl::evaluate(bool write_json, bool force) {

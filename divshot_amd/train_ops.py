@@ -1,4 +1,4 @@
-"""ctypes wrappers of include/dvs_train.h (loss gradient, SSIM, fused Adam) on torch CUDA tensors."""
+"""ctypes wrappers of include/dvs_train.h (loss gradient, SSIM, fused Adam) and of the view calls of include/dvs_image.h on torch CUDA tensors."""
 import ctypes as C
 import torch
 from ._lib import lib, check, AdamGroup, MetricsView, DownsampleView
@@ -92,6 +92,22 @@ def downsample_views(srcs, factor):
         a.src, a.dst = x.data_ptr(), o.data_ptr()
     check(lib.dvs_downsample_views(_st(), arr, V, planes, W, H, int(factor), int(u8)), "dvs_downsample_views")
     return outs
+
+
+def undistort_view(src, desc, mask=None):
+    """A distorted camera's view as its pinhole camera sees it (dvs_undistort_view) -> (dst uint8 [planes,H,W], mask float32 [H,W],
+    invalid: int32 1-element tensor, the number of pixels without a source) (asynchronous). src: contiguous uint8 [planes,H,W], planes
+    1..4; desc: _lib.UndistortDesc (undistort_desc()); mask: None or a contiguous uint8 [H,W] tensor of 0 / 1 in the source's geometry."""
+    if src.dtype != torch.uint8 or src.dim() != 3 or not src.is_contiguous() or tuple(src.shape[1:]) != (desc.height, desc.width):
+        raise ValueError("undistort_view: src must be a contiguous uint8 [planes,H,W] tensor of the descriptor's size")
+    if mask is not None and (mask.dtype != torch.uint8 or tuple(mask.shape) != tuple(src.shape[1:]) or not mask.is_contiguous()):
+        raise ValueError("undistort_view: mask must be a contiguous uint8 [H,W] tensor")
+    dst = torch.empty_like(src)
+    out_mask = torch.empty(tuple(src.shape[1:]), dtype=torch.float32, device=src.device)
+    invalid = torch.zeros(1, dtype=torch.int32, device=src.device)
+    check(lib.dvs_undistort_view(_st(), C.byref(desc), int(src.shape[0]), src.data_ptr(), mask.data_ptr() if mask is not None else None,
+                                 dst.data_ptr(), out_mask.data_ptr(), invalid.data_ptr()), "dvs_undistort_view")
+    return dst, out_mask, invalid
 
 
 def adam_step(param, grad, m, v, lr, step, beta1=0.9, beta2=0.999, eps=1e-15):

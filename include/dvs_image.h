@@ -1,5 +1,8 @@
 /*
- * dvs_image.h — C-ABI of the parallel half of baseline JPEG decoding: quantised DCT coefficients (gstrain/jpeg_io.hpp decodes them on
+ * dvs_image.h — C-ABI of the image work of the capture loader on the device: the parallel half of baseline JPEG decoding (below) and
+ * the undistortion of a view taken through a distorted COLMAP camera (dvs_undistort_view, at the end).
+ *
+ * JPEG: quantised DCT coefficients (gstrain/jpeg_io.hpp decodes them on
  * the host) -> planar 8-bit RGB on the device, in one kernel: dequantisation, 8x8 inverse DCT, chroma upsampling, YCbCr -> RGB.
  *
  * Conventions of dvs_export.h: `stream` is a hipStream_t, the call is asynchronous and returns a DVS_* status (dvs_raster.h). No
@@ -45,6 +48,43 @@ typedef struct dvs_jpeg_desc {
  * DVS_ERR_INVALID for a NULL pointer, coef off a 16-byte boundary, or a desc that contradicts itself (sizes, sampling, block counts,
  * offsets that are no multiple of 8). */
 int dvs_jpeg_reconstruct(void* stream, const dvs_jpeg_desc* desc, const int16_t* coef, uint8_t* rgb);
+
+/* ---- undistortion: a view of a SIMPLE_RADIAL, RADIAL or OPENCV camera -> the view of the pinhole camera that keeps its fx, fy, cx, cy
+ * and its W x H. Coefficients a model lacks are 0; a pixel centre is at (x + 0.5, y + 0.5), COLMAP's convention. The ten floats of
+ * the descriptor are each rounded ONCE from the doubles (the reciprocals ifx = 1 / fx, ify = 1 / fy are taken in double). Per target
+ * pixel (x, y), in fp32, every `*` and `+` a separate round-to-nearest operation in the written order and bracketing (the file is
+ * compiled without contraction), no division, no transcendental function; tests/undistort_ref.py restates it:
+ *   u  = (((float)x + 0.5f) - cx) * ifx          v  = (((float)y + 0.5f) - cy) * ify
+ *   u2 = u*u   v2 = v*v   uv = u*v   r2 = u2 + v2
+ *   rad = (k1 + k2*r2) * r2
+ *   du = (u*rad + (2.0f*p1)*uv) + p2*(r2 + 2.0f*u2)
+ *   dv = (v*rad + (2.0f*p2)*uv) + p1*(r2 + 2.0f*v2)
+ *   xs = (fx*(u + du) + cx) - 0.5f               ys = (fy*(v + dv) + cy) - 0.5f        (source index coordinates)
+ *   in range  iff  xs > -1 && xs < W && ys > -1 && ys < H      (a NaN fails; only then is anything converted to int)
+ *   qx = (int)floorf(xs*32.0f + 0.5f)            qy likewise                            (1/32-pixel fixed point)
+ *   valid  iff  in range && 0 <= qx <= 32*(W-1) && 0 <= qy <= 32*(H-1)
+ *   x0 = qx >> 5, ax = qx & 31, x1 = min(x0+1, W-1);   y0, ay, y1 likewise
+ *   out = ((32-ax)*(32-ay)*s[y0][x0] + ax*(32-ay)*s[y0][x1] + (32-ax)*ay*s[y1][x0] + ax*ay*s[y1][x1] + 512) >> 10     per plane, integers
+ * An invalid pixel writes 0 to every plane and 0 to the mask. A source mask (bytes in {0, 1}, the source image's geometry) goes through
+ * the same integer formula as 255 m; the pixel is trainable iff the result is > 127. The output mask is 1.0f iff the pixel is valid and
+ * trainable (without a source mask: iff valid), else 0.0f. Zero coefficients reproduce the source byte for byte with every pixel
+ * valid: validity is decided on qx, not on xs. */
+typedef struct dvs_undistort_desc { int32_t width, height; float fx, fy, cx, cy, ifx, ify, k1, k2, p1, p2; } dvs_undistort_desc;
+
+/* host only: COLMAP model id 2 (SIMPLE_RADIAL: f cx cy k), 3 (RADIAL: f cx cy k1 k2) or 4 (OPENCV: fx fy cx cy k1 k2 p1 p2) and its
+ * parameter doubles -> desc; DVS_ERR_INVALID for another model, a NULL pointer, a parameter that is not finite (as a double or once
+ * rounded to fp32, the reciprocals included), f <= 0, a side outside 1..65536 */
+int dvs_undistort_desc_from_colmap(int model, const double* params, int width, int height, dvs_undistort_desc* out);
+
+/* src, dst: DEVICE planar [planes][H][W] bytes, planes 1..4, no alignment requirement, dst must not overlap src: the four bytes a lane
+ * owns leave as one dword store when dst is on a 4-byte boundary and W is a multiple of 4, as single bytes otherwise, the same bytes
+ * either way. mask_src: nullable DEVICE [H][W] bytes in {0,1}; mask_dst: nullable DEVICE [H][W] floats (16-byte stores when it is on a
+ * 16-byte boundary and W is a multiple of 4); invalid_count: nullable DEVICE uint32, INCREMENTED by the number of invalid pixels (the
+ * caller zeroes it; one atomic per wavefront that has any — an integer sum, so the count does not depend on their order).
+ * `desc` is a HOST pointer, read before the call returns. No scratch; two calls on the same inputs return identical results.
+ * DVS_ERR_INVALID for a NULL desc / src / dst, planes outside 1..4, a side outside 1..65536, dst overlapping src. */
+int dvs_undistort_view(void* stream, const dvs_undistort_desc* desc, int planes, const uint8_t* src, const uint8_t* mask_src,
+                       uint8_t* dst, float* mask_dst, uint32_t* invalid_count);
 
 #ifdef __cplusplus
 }
