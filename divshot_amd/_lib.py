@@ -208,6 +208,9 @@ class UndistortDesc(C.Structure):      # dvs_undistort_desc
 
 _IMAGE_PROTOS = {
     "dvs_jpeg_reconstruct": (C.c_int, [C.c_void_p, C.POINTER(JpegDesc), C.c_void_p, C.c_void_p]),
+    "dvs_jpeg_encode_desc": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JpegDesc)]),
+    "dvs_jpeg_encode_coef_count": (C.c_size_t, [C.POINTER(JpegDesc)]),
+    "dvs_jpeg_encode_views": (C.c_int, [C.c_void_p, C.POINTER(JpegDesc), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int]),
     "dvs_undistort_desc_from_colmap": (C.c_int, [C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int, C.POINTER(UndistortDesc)]),
     "dvs_undistort_view": (C.c_int, [C.c_void_p, C.POINTER(UndistortDesc), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
@@ -239,6 +242,11 @@ _JPEG_HOST_PROTOS = {
     "gstrain_jpeg_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gstrain_jpeg_coefficients": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gstrain_jpeg_close": (None, [C.c_void_p]),
+    "gstrain_jpeg_open_memory": (C.c_void_p, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_int]),
+    "gstrain_jpeg_encode": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_int]),
+    "gstrain_jpeg_encoded_size": (C.c_uint64, [C.c_void_p]),
+    "gstrain_jpeg_encoded_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gstrain_jpeg_encoded_free": (None, [C.c_void_p]),
 }
 _host_lib = None
 
@@ -259,13 +267,48 @@ def host_lib():
     return _host_lib
 
 
+def jpeg_encode_desc(width, height, sampling, quality):
+    """-> JpegDesc of dvs_jpeg_encode_desc (host only); sampling 0 = 4:2:0, 1 = 4:4:4; DvsError when refused"""
+    d = JpegDesc()
+    if lib.dvs_jpeg_encode_desc(int(width), int(height), int(sampling), int(quality), C.byref(d)) != 0:
+        raise DvsError(f"dvs_jpeg_encode_desc refused {width}x{height}, sampling {sampling}, quality {quality}")
+    return d
+
+
+def jpeg_encode_coefficients(desc, coef):
+    """-> bytes: gsjpeg::encode_coefficients of a frame given as (JpegDesc, int16 numpy array), the pair jpeg_decode_coefficients
+    returns; DvsError with the encoder's message for a frame it refuses"""
+    import numpy as np
+    h = host_lib()
+    coef = np.ascontiguousarray(coef, np.int16)
+    ints, offs = (C.c_int32 * 15)(), (C.c_uint64 * 4)()
+    ints[0], ints[1], ints[2] = desc.width, desc.height, desc.components
+    for k in range(3):
+        ints[3 + k], ints[6 + k] = (desc.hs, desc.vs) if k == 0 else (1, 1)
+        ints[9 + k], ints[12 + k], offs[k] = desc.blocks_w[k], desc.blocks_h[k], desc.offset[k]
+    offs[3] = coef.size
+    err = C.create_string_buffer(1024)
+    e = h.gstrain_jpeg_encode(ints, C.addressof(desc.quant), offs, coef.ctypes.data, err, 1024)
+    if not e:
+        raise DvsError(err.value.decode(errors="replace"))
+    try:
+        out = np.zeros(h.gstrain_jpeg_encoded_size(e), np.uint8)
+        check(h.gstrain_jpeg_encoded_bytes(e, out.ctypes.data), "gstrain_jpeg_encoded_bytes")
+        return out.tobytes()
+    finally:
+        h.gstrain_jpeg_encoded_free(e)
+
+
 def jpeg_decode_coefficients(path):
-    """-> (JpegDesc, int16 numpy array): gsjpeg::decode_coefficients of a file, as dvs_jpeg_reconstruct takes them; DvsError with the
-    decoder's message for a file it rejects"""
+    """-> (JpegDesc, int16 numpy array): gsjpeg::decode_coefficients of a file (or of `bytes` in memory), as dvs_jpeg_reconstruct takes
+    them; DvsError with the decoder's message for a file it rejects"""
     import numpy as np
     h = host_lib()
     err = C.create_string_buffer(1024)
-    f = h.gstrain_jpeg_open(os.fsencode(path), err, 1024)
+    if isinstance(path, (bytes, bytearray)):
+        f = h.gstrain_jpeg_open_memory(bytes(path), len(path), err, 1024)
+    else:
+        f = h.gstrain_jpeg_open(os.fsencode(path), err, 1024)
     if not f:
         raise DvsError(err.value.decode(errors="replace"))
     try:

@@ -42,7 +42,10 @@ static std::map<std::string, std::string> g_opts = {
     {"exportSpz", "0"},
     // the config fields pruneScale3d / pruneScale2d (the reference's CLI has no flag for them): after the first opacity reset a refinement
     // also prunes splats larger than this fraction of the scene extent / whose screen radius exceeds this fraction of the image size
-    {"pruneScale3d", "0.1"}, {"pruneScale2d", "0.15"}};
+    {"pruneScale3d", "0.1"}, {"pruneScale2d", "0.15"},
+    // extension of this build: every save also writes rendered views as JPEG files to <outputPath>_<it>_renders/: --renderViews test (the
+    // held-out cameras of --eval) | train | all; --renderQuality 1..100; --renderSampling 420 | 444
+    {"renderViews", ""}, {"renderQuality", "90"}, {"renderSampling", "420"}};
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
 
@@ -129,6 +132,18 @@ int main(int argc, const char* argv[]) {
         at = comma + 1;
     }
     if (as_bool(g_opts["exportSpz"])) train_config.exportFormats |= 4;
+    {
+        const std::string &rv = g_opts["renderViews"], &rs = g_opts["renderSampling"];
+        const int q = atoi(g_opts["renderQuality"].c_str());
+        if (rv == "test") train_config.renderViews = 1;
+        else if (rv == "train") train_config.renderViews = 2;
+        else if (rv == "all") train_config.renderViews = 3;
+        else if (!rv.empty()) { std::cout << "Command Line Error: --renderViews takes test, train or all, not '" << rv << "'\n"; return 1; }
+        if (rs != "420" && rs != "444") { std::cout << "Command Line Error: --renderSampling takes 420 or 444, not '" << rs << "'\n"; return 1; }
+        if (q < 1 || q > 100) { std::cout << "Command Line Error: --renderQuality takes 1..100, not '" << g_opts["renderQuality"] << "'\n"; return 1; }
+        train_config.renderSampling = rs == "444" ? 1 : 0;
+        train_config.renderQuality = (uint8_t)q;
+    }
     train_config.normalConsistencyLoss = false;
     if (train_config.exportMesh) { train_config.normalConsistencyLoss = true; train_config.useMask = true; }
     train_config.verbose = true;

@@ -132,6 +132,7 @@ void GaussianTrainerScene::saveGaussianModel() {
         for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT, (int)Impl::EXPORT_SPZ})
             if (m.export_formats() & format) m.export_model(format);
     m.evaluate(true);                                                       // <modelPath>_<it>_eval.json beside the PLY (rank 0, evaluation on)
+    m.render_at_save();                                                     // <modelPath>_<it>_renders/*.jpg (rank 0, renderViews on)
 }
 
 void GaussianTrainerScene::exportMesh(const std::string&) { logf_("export_mesh: mesh extraction is outside this build's scope"); }
@@ -281,6 +282,19 @@ bool GaussianTrainerScene::evaluateTestSet() { return impl_->evaluate(false, tru
 double GaussianTrainerScene::getTestPSNR() const { return impl_->eval_mean[3]; }
 double GaussianTrainerScene::getTestSSIM() const { return impl_->eval_mean[2]; }
 double GaussianTrainerScene::getTestL1() const { return impl_->eval_mean[1]; }
+bool GaussianTrainerScene::renderCameraToJpeg(int camera, const std::string& path) {
+    Impl& m = *impl_;
+    try {
+        if (!m.ctx || camera < 0 || camera >= (int)m.cams.size() || path.empty()) return false;
+        HIP_OR_THROW(hipSetDevice(m.device));
+        return m.render_to_jpeg({camera}, {path}, nullptr);
+    } catch (const std::exception& e) {
+        logf_("renderCameraToJpeg(%d, '%s') failed: %s", camera, path.c_str(), e.what());
+    } catch (...) {
+        logf_("renderCameraToJpeg(%d, '%s') failed: unknown exception", camera, path.c_str());
+    }
+    return false;
+}
 const std::vector<float>& GaussianTrainerScene::getGaussianPositionCpu() { impl_->fetch_host(); return impl_->host[P_POS]; }
 const std::vector<float>& GaussianTrainerScene::getGaussianSH0Cpu() { impl_->fetch_host(); return impl_->host[P_SH0]; }
 const std::vector<float>& GaussianTrainerScene::getGaussianSHNCpu() { impl_->fetch_host(); return impl_->host[P_SHN]; }

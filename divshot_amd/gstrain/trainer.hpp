@@ -1,6 +1,7 @@
 // trainer.hpp — GaussianTrainerScene::Impl, the state behind `libgstrain.so`, and what its source files share. The members are defined
-// in trainer_load.cpp (loaders, allocation), trainer_step.cpp (one trainStep), trainer_refine.cpp (densification, pruning) and
-// trainer_output.cpp (configuration report, evaluation, export); gstrain.cpp holds the GaussianTrainerScene members and the C symbols.
+// in trainer_load.cpp (loaders, allocation), trainer_step.cpp (one trainStep), trainer_refine.cpp (densification, pruning),
+// trainer_output.cpp (configuration report, evaluation, export) and trainer_render.cpp (rendered views as JPEG files); gstrain.cpp holds
+// the GaussianTrainerScene members and the C symbols.
 #pragma once
 #include <chrono>
 #include <cstdarg>
@@ -140,6 +141,25 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     DevBuf<float> d_decoded[6]; int decoded_cap = 0;
     double spz_mean[4] = {NAN, NAN, NAN, NAN};                               // {mse, l1, ssim, psnr} means of the decoded model ...
     int spz_it = -1;                                                         // ... at this iteration (-1: none)
+
+    // rendered views as JPEG files (cfg.renderViews / renderQuality / renderSampling and their DVS_RENDER_* overrides, read at load): at
+    // every save rank 0 renders the selected cameras through eval_ctx with the evaluation's options (what `eval @it` scored), turns
+    // each pass into quantised DCT coefficients with ONE dvs_jpeg_encode_views launch, copies them to the host and Huffman-codes them
+    // on up to DVS_LOAD_THREADS threads into <modelPath>_<it>_renders/<name>.jpg. Nothing is allocated until the first render; the
+    // buffers only grow. The training context, its pending rows and its prepared projection are never touched.
+    enum { RENDER_TEST = 1, RENDER_TRAIN = 2 };
+    int render_views = 0, render_quality = 90, render_sampling = 0;
+    std::vector<std::string> cam_names;                                      // per camera, in step with cams: the image's stem, empty for a synthetic camera
+    bool cam_names_ok = false;                                               // every camera has a stem and they are unique (else the files are cam_%04d)
+    DevBuf<int16_t> d_render_coef; size_t render_coef_cap = 0;               // [eval_views][coefficients of a view]
+    std::vector<int16_t> render_coef_host;
+    Event ev_render0, ev_render1;
+    struct RenderStats { size_t views = 0, bytes = 0; double transform_ms = 0, entropy_ms = 0; int threads = 0; };
+    void setup_render();
+    std::string camera_name(int c) const;
+    void ensure_eval_ctx();
+    bool render_to_jpeg(const std::vector<int>& which, const std::vector<std::string>& files, RenderStats* stats);
+    void render_at_save();
 
     ~Impl() { if (device >= 0) (void)hipSetDevice(device); }                // (the members release themselves, after this body)
     // floats of group g on the device: the 45 higher-order SH floats live in the DVS_SHN_TILED layout (48 per splat,

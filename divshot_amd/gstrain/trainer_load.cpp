@@ -219,6 +219,7 @@ void GaussianTrainerScene::Impl::finish_load(const std::function<void(std::vecto
     if (views_u8()) d_target_f32.alloc(3 * (size_t)W * H * sizeof(float));
     HIP_OR_THROW(hipStreamSynchronize(stream.get()));
     setup_split();
+    setup_render();
     setup_levels();
     {   // scene extent = 1.1 x the largest distance of a camera centre from their mean (the usual "cameras_extent"); a single
         // camera or a tiny rig falls back to half the depth range of the synthetic slab
@@ -280,6 +281,7 @@ bool GaussianTrainerScene::Impl::load_synthetic(const std::string& spec_str) {
         DevBuf<float> t(img * sizeof(float)), mask;
         DVS_OR_THROW(dvs_raster_forward(ctx.get(), stream.get(), &sp, &cam, &opts, t.get(), nullptr, nullptr));
         cams.push_back(cam);
+        cam_names.emplace_back();                           // (a synthetic camera has no file: cam_%04d)
         if (cfg.useMask) {                                     // synthetic mask: an ellipse inscribed in the image (no dataset masks here)
             std::vector<float> mk((size_t)W * H);
             for (int y = 0; y < H; ++y) for (int x = 0; x < W; ++x) {
@@ -493,6 +495,7 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
         DVS_OR_THROW(dvs_make_camera_intrinsics(R, t3, c.fx, c.fy, c.cx, c.cy, w, h, &cam));
         DVS_OR_THROW(dvs_camera_downscale(&cam, d, &camd));
         cams.push_back(camd);
+        cam_names.push_back(std::filesystem::path(im.name).stem().string());
     }
     if (rank == 0) {
         char lvl[64] = "";

@@ -27,6 +27,11 @@ void GaussianTrainerScene::Impl::report_config() const {
               (fmts & EXPORT_COMPRESSED) ? " <modelPath>_<it>.compressed.ply" : "", (fmts & EXPORT_SPLAT) ? " <modelPath>_<it>.splat" : "",
               (fmts & EXPORT_SPZ) ? " <modelPath>_<it>.spz" : "", asked_formats() == 0 ? " (turned on by the suffix of modelPath)" : "",
               (fmts & EXPORT_SPZ) && !test_idx.empty() ? "; the .spz payload is decoded on the device and scored on the held-out views" : "");
+    if (render_views)
+        logf_("config: renderViews %d: every save also writes the %s cameras as JPEG files (quality %d, %s) to <modelPath>_<it>_renders/, rendered with the "
+              "evaluation's options; transform on the device, entropy coding on the host%s", render_views,
+              render_views == RENDER_TEST ? "test" : render_views == RENDER_TRAIN ? "training" : "test and training", render_quality,
+              render_sampling == 1 ? "4:4:4" : "4:2:0", (render_views & RENDER_TEST) && test_idx.empty() ? " (no camera is held out: every camera is a training camera)" : "");
     std::string ign;
     if (cfg.modelType != 0) ign += " modelType(only 3DGS)";
     if (cfg.cullSH) ign += " cullSH";
@@ -60,15 +65,21 @@ void GaussianTrainerScene::Impl::run_evaluation() {
     eval_it = step;
     logf_("eval @%d: %d views, PSNR %.17g dB, SSIM %.17g, L1 %.17g", step, (int)test_idx.size(), eval_mean[3], eval_mean[2], eval_mean[1]);
 }
+// the context the held-out views are rendered by (and the views written as JPEG files): min(n_test, 8) views per pass — of all
+// cameras when nothing is held out and only pictures are asked for — created at the first use together with its output images
+void GaussianTrainerScene::Impl::ensure_eval_ctx() {
+    if (eval_ctx) return;
+    eval_views = std::min(test_idx.empty() ? (int)cams.size() : (int)test_idx.size(), 8);
+    eval_ctx.reset(dvs_create_views(device, (size_t)cap, W, H, eval_views));
+    if (!eval_ctx) throw std::runtime_error(std::string("dvs_create_views (evaluation): ") + dvs_last_error());
+    d_eval_out.alloc((size_t)eval_views * 3 * (size_t)W * H * sizeof(float));
+}
 // the test cameras rendered from `sp` (DVS_SHN_TILED, at most `cap` splats) and scored: res = [n_test][4] {mse, l1, ssim, psnr}, mean = their means
 void GaussianTrainerScene::Impl::score_views(const dvs_splats& sp, std::vector<double>& res, double mean[4]) {
     const int nt = (int)test_idx.size();
     const size_t img = 3 * (size_t)W * H;
-    if (!eval_ctx) {
-        eval_views = std::min(nt, 8);
-        eval_ctx.reset(dvs_create_views(device, (size_t)cap, W, H, eval_views));
-        if (!eval_ctx) throw std::runtime_error(std::string("dvs_create_views (evaluation): ") + dvs_last_error());
-        d_eval_out.alloc((size_t)eval_views * img * sizeof(float));
+    ensure_eval_ctx();
+    if (!d_eval_scratch) {
         d_eval_scratch.alloc(dvs_image_metrics_scratch_bytes(W, H, eval_views));
         d_eval_res.alloc((size_t)nt * 4 * sizeof(double));
     }

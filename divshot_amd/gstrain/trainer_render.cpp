@@ -1,0 +1,130 @@
+// trainer_render.cpp — rendered views as JPEG files: the selected cameras through the evaluation context, the forward DCT and
+// quantisation on the device (dvs_jpeg_encode_views), the entropy coder on host threads (jpeg_write.hpp).
+#include "trainer.hpp"
+#include <atomic>
+#include <thread>
+#include "jpeg_write.hpp"
+#include "../../include/dvs_image.h"
+
+void GaussianTrainerScene::Impl::setup_render() {
+    render_views = env_int("DVS_RENDER_VIEWS", cfg.renderViews) & (RENDER_TEST | RENDER_TRAIN);
+    render_quality = std::max(1, std::min(env_int("DVS_RENDER_QUALITY", cfg.renderQuality), 100));
+    render_sampling = env_int("DVS_RENDER_SAMPLING", cfg.renderSampling) == 1 ? DVS_JPEG_SAMPLING_444 : DVS_JPEG_SAMPLING_420;
+    // file names: the image stems when every camera has one and they are unique, cam_%04d otherwise (a synthetic scene). cam_names is
+    // filled in step with cams by both loaders.
+    std::map<std::string, int> seen;
+    cam_names_ok = cam_names.size() == cams.size();
+    for (const std::string& s : cam_names) cam_names_ok = cam_names_ok && !s.empty() && seen[s]++ == 0;
+}
+
+std::string GaussianTrainerScene::Impl::camera_name(int c) const {
+    if (cam_names_ok) return cam_names[(size_t)c];
+    char name[32];
+    snprintf(name, sizeof name, "cam_%04d", c);
+    return name;
+}
+
+// cameras `which` rendered from the current parameters and written to `files`: at most eval_views per pass; per pass one multi-view
+// forward, ONE encode launch (timed by events), one copy of the coefficients, then up to DVS_LOAD_THREADS host threads that code one
+// view each at a time and write its file. Synchronous. -> false when a file could not be coded or written (the others are still written).
+bool GaussianTrainerScene::Impl::render_to_jpeg(const std::vector<int>& which, const std::vector<std::string>& files, RenderStats* stats) {
+    ensure_eval_ctx();
+    dvs_jpeg_desc desc;
+    if (dvs_jpeg_encode_desc(W, H, render_sampling, render_quality, &desc) != DVS_OK) throw std::runtime_error("dvs_jpeg_encode_desc: invalid arguments");
+    const size_t count = dvs_jpeg_encode_coef_count(&desc), img = 3 * (size_t)W * H;
+    if (render_coef_cap < (size_t)eval_views * count) {
+        render_coef_cap = 0;
+        d_render_coef.alloc((size_t)eval_views * count * sizeof(int16_t));
+        render_coef_cap = (size_t)eval_views * count;
+    }
+    if (render_coef_host.size() < (size_t)eval_views * count) render_coef_host.resize((size_t)eval_views * count);
+    if (!ev_render0)
+        for (Event* e : {&ev_render0, &ev_render1}) { hipEvent_t ev = nullptr; HIP_OR_THROW(hipEventCreate(&ev)); e->reset(ev); }
+    dvs_opts opts{};                                                         // the evaluation's (score_views)
+    opts.sh_degree = sh_max; opts.antialias = cfg.mipAntiliased ? 1 : 0; opts.shn_layout = DVS_SHN_TILED; opts.tile_bounds = DVS_TILES_CANONICAL;
+    const dvs_splats sp = splats();
+    const int load_threads = std::max(1, std::min(env_int("DVS_LOAD_THREADS", 8), 16));     // never the machine's CPU count
+    gsjpeg::Frame shape;                                                     // what every view's frame shares
+    shape.width = W; shape.height = H; shape.components = 3;
+    shape.hs[0] = desc.hs; shape.vs[0] = desc.vs;
+    for (int c = 0; c < 3; ++c) { shape.blocks_w[c] = desc.blocks_w[c]; shape.blocks_h[c] = desc.blocks_h[c]; shape.offset[c] = desc.offset[c]; }
+    memcpy(shape.quant, desc.quant, sizeof shape.quant);
+    bool all_ok = true;
+    const int total = (int)which.size();
+    for (int first = 0; first < total; first += eval_views) {
+        const int nb = std::min(eval_views, total - first);
+        std::vector<dvs_camera> bc((size_t)nb);
+        const float* images[DVS_JPEG_ENCODE_MAX_VIEWS];
+        int16_t* coefs[DVS_JPEG_ENCODE_MAX_VIEWS];
+        for (int k = 0; k < nb; ++k) {
+            bc[(size_t)k] = cams[(size_t)which[(size_t)(first + k)]];
+            images[k] = d_eval_out.get() + (size_t)k * img;
+            coefs[k] = d_render_coef.get() + (size_t)k * count;
+        }
+        DVS_OR_THROW(dvs_raster_forward_views(eval_ctx.get(), stream.get(), &sp, bc.data(), nb, &opts, d_eval_out.get()));
+        HIP_OR_THROW(hipEventRecord(ev_render0.get(), stream.get()));
+        DVS_OR_THROW(dvs_jpeg_encode_views(stream.get(), &desc, images, coefs, nb));
+        HIP_OR_THROW(hipEventRecord(ev_render1.get(), stream.get()));
+        HIP_OR_THROW(hipMemcpyAsync(render_coef_host.data(), d_render_coef.get(), (size_t)nb * count * sizeof(int16_t), hipMemcpyDeviceToHost, stream.get()));
+        HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+        float ms = 0;
+        HIP_OR_THROW(hipEventElapsedTime(&ms, ev_render0.get(), ev_render1.get()));
+        const auto t_host = std::chrono::steady_clock::now();
+        std::vector<size_t> bytes((size_t)nb, 0);
+        std::vector<std::string> errs((size_t)nb);
+        std::atomic<int> next{0};
+        const auto work = [&]() noexcept {                                   // views are handed out one at a time: any number of threads finishes them all
+            for (int k = next++; k < nb; k = next++) {
+                try {
+                    std::string out;
+                    const std::string& file = files[(size_t)(first + k)];
+                    if (!gsjpeg::encode_coefficients(W, H, 3, shape.hs, shape.vs, shape.quant, shape.blocks_w, shape.blocks_h, shape.offset,
+                                                     render_coef_host.data() + (size_t)k * count, count, &out, &errs[(size_t)k])) continue;
+                    FILE* f = fopen(file.c_str(), "wb");
+                    if (!f || fwrite(out.data(), 1, out.size(), f) != out.size()) errs[(size_t)k] = "cannot write " + file;
+                    else bytes[(size_t)k] = out.size();
+                    if (f && fclose(f) != 0) { errs[(size_t)k] = "cannot write " + file; bytes[(size_t)k] = 0; }
+                } catch (...) {
+                    try { errs[(size_t)k] = "out of memory while coding the view"; } catch (...) {}
+                }
+            }
+        };
+        std::vector<std::thread> workers;
+        try {                                                                // a thread that cannot be started is not needed: this one works too
+            workers.reserve((size_t)load_threads);
+            for (int t = 1; t < std::min(load_threads, nb); ++t) workers.emplace_back(work);
+        } catch (...) {}
+        const int nthreads = (int)workers.size() + 1;
+        work();
+        for (std::thread& t : workers) t.join();
+        const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host).count();
+        for (int k = 0; k < nb; ++k) {
+            if (!errs[(size_t)k].empty()) { logf_("render @%d: camera %d: %s", step, which[(size_t)(first + k)], errs[(size_t)k].c_str()); all_ok = false; }
+            else if (stats) { stats->views += 1; stats->bytes += bytes[(size_t)k]; }
+        }
+        if (stats) { stats->transform_ms += ms; stats->entropy_ms += host_ms; stats->threads = std::max(stats->threads, nthreads); }
+    }
+    return all_ok;
+}
+
+// at a save, rank 0: the cameras cfg.renderViews selects, into <modelPath>_<step>_renders/
+void GaussianTrainerScene::Impl::render_at_save() {
+    if (!render_views || rank != 0 || !ctx) return;
+    HIP_OR_THROW(hipSetDevice(device));
+    std::vector<int> which;
+    for (int c = 0; c < (int)cams.size(); ++c) {
+        const bool test = eval_holdout > 0 && c % eval_holdout == 0;
+        if (render_views & (test ? RENDER_TEST : RENDER_TRAIN)) which.push_back(c);
+    }
+    if (which.empty()) { logf_("render @%d: 0 views (renderViews %d selects no camera: nothing is held out)", step, render_views); return; }
+    const std::string dir = cfg.modelPath + "_" + std::to_string(step) + "_renders";
+    std::error_code ec;
+    std::filesystem::create_directories(dir, ec);
+    if (ec) { logf_("render @%d: cannot create %s: %s", step, dir.c_str(), ec.message().c_str()); return; }
+    std::vector<std::string> files;
+    for (int c : which) files.push_back(dir + "/" + camera_name(c) + ".jpg");
+    RenderStats st;
+    render_to_jpeg(which, files, &st);
+    logf_("render @%d: %zu views, %zu bytes, transform %.3f ms (device, events), entropy coding %.3f ms (host, %d threads, wall)", step, st.views,
+          st.bytes, st.transform_ms, st.entropy_ms, st.threads);
+}

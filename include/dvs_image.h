@@ -1,6 +1,7 @@
 /*
- * dvs_image.h — C-ABI of the image work of the capture loader on the device: the parallel half of baseline JPEG decoding (below) and
- * the undistortion of a view taken through a distorted COLMAP camera (dvs_undistort_view, at the end).
+ * dvs_image.h — C-ABI of the image work on the device: the parallel half of baseline JPEG decoding (below), the parallel half of
+ * baseline JPEG encoding (dvs_jpeg_encode_views, after it) and the undistortion of a view taken through a distorted COLMAP camera
+ * (dvs_undistort_view, at the end).
  *
  * JPEG: quantised DCT coefficients (gstrain/jpeg_io.hpp decodes them on
  * the host) -> planar 8-bit RGB on the device, in one kernel: dequantisation, 8x8 inverse DCT, chroma upsampling, YCbCr -> RGB.
@@ -48,6 +49,51 @@ typedef struct dvs_jpeg_desc {
  * DVS_ERR_INVALID for a NULL pointer, coef off a 16-byte boundary, or a desc that contradicts itself (sizes, sampling, block counts,
  * offsets that are no multiple of 8). */
 int dvs_jpeg_reconstruct(void* stream, const dvs_jpeg_desc* desc, const int16_t* coef, uint8_t* rgb);
+
+/* ---- encoding: planar fp32 RGB (what dvs_raster_forward_views writes) -> quantised DCT coefficients, the mirror image of the above;
+ * gstrain/jpeg_write.hpp Huffman-codes them on the host. One launch takes up to DVS_JPEG_ENCODE_MAX_VIEWS views of one size. No
+ * scratch, no atomics: two calls return identical bytes, and a view's output does not depend on the other views of the call. The
+ * result is defined bit for bit; after the first step it is integer arithmetic in which every intermediate fits int32;
+ * tests/jpeg_enc_ref.py restates it:
+ *   float to byte  b = (int)min(255, max(0, rint(x * 255))): the fp32 product rounded to the nearest integer, ties to even; NaN -> 0.
+ *                  This is the rule by which the trainer keeps 8-bit training views (GSPackLevel::PackF32ToU8), not the
+ *                  truncation of x * 255 + 0.5: a render and its target are quantised alike. The two differ only on ties.
+ *   padding        columns >= W and rows >= H up to the MCU grid repeat column W - 1 / row H - 1
+ *   colour         Y  = ( 19595 R + 38470 G +  7471 B + 32768) >> 16
+ *                  Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16
+ *                  Cr = ( 32768 R - 27439 G -  5329 B + 8388608 + 32767) >> 16      (16-bit BT.601, the forward counterpart of the
+ *                                                                                      decoder's constants; each lands in 0..255)
+ *   subsampling    2x2: chroma sample (i, j) = (c[2j][2i] + c[2j][2i+1] + c[2j+1][2i] + c[2j+1][2i+1] + 2) >> 2 — inside the MCU
+ *   forward DCT    s = sample - 128, the decoder's table T[u][x], rows first, SEVEN fractional bits kept between the passes and SIX
+ *                  kept in F, which is the coefficient in 1/64 units (rounding F to an integer first and dividing by a small q
+ *                  afterwards would round twice: at q = 2 every true |F| in [0.5, 1) would become 1):
+ *                                row[y][u] = (sum_x T[u][x] * s[y][x] + 2^5) >> 6          (|row| <= 46336 < 2^17)
+ *                                F[v][u]   = (sum_y T[v][y] * row[y][u] + 2^13) >> 14      (|sum| <= 23168 * 46336 < 2^31; |F| < 2^16 + 2^6)
+ *   quantisation   c = sign(F) * (((|F| + 32 q) >> 6) / q)  (integer division; equal to (|F| + 64 q / 2) / (64 q): half away from zero
+ *                  of the coefficient with its fraction), then clamp to [-1023, 1023], what a baseline Huffman stream can carry
+ *                  (only a DC of -1024 at q = 1 ever meets the clamp) */
+#define DVS_JPEG_ENCODE_MAX_VIEWS 16
+#define DVS_JPEG_SAMPLING_420 0     /* hs = vs = 2 */
+#define DVS_JPEG_SAMPLING_444 1     /* hs = vs = 1 */
+
+/* host only: the descriptor of a width x height encode: three components, the sampling's block counts, the components one after the
+ * other from offset 0, and the two Annex K quantiser tables (K.1 for Y, K.2 for Cb and Cr) scaled by the IJG quality rule
+ * (scale = 5000 / quality below 50, 200 - 2 quality from 50 on; q = (base * scale + 50) / 100 clamped to 1..255).
+ * DVS_ERR_INVALID for a NULL desc, a side outside 1..65500, another sampling, a quality outside 1..100. */
+int dvs_jpeg_encode_desc(int width, int height, int sampling, int quality, dvs_jpeg_desc* desc);
+
+/* host only: int16 values one view's coefficients take (the end of the last component); 0 for a desc dvs_jpeg_encode_views refuses */
+size_t dvs_jpeg_encode_coef_count(const dvs_jpeg_desc* desc);
+
+/* coef[v] = the coefficients of images[v], v < n_views, in the layout dvs_jpeg_reconstruct reads (padding blocks included). `desc`,
+ * `images` and `coef` are HOST pointers, read before the call returns; images[v] is a DEVICE pointer to planar [3][height][width] fp32
+ * with no alignment requirement beyond a float's: rows are read with 16-byte loads when every images[v] is on a 16-byte boundary and
+ * width is a multiple of 4, element by element otherwise, the same bytes either way; coef[v] is a DEVICE pointer on a 16-byte
+ * boundary to dvs_jpeg_encode_coef_count(desc) values; a block row of 8 coefficients leaves as one 16-byte store.
+ * DVS_ERR_INVALID for a NULL pointer, n_views outside 1..16, a coef[v] off a 16-byte boundary, or a desc that contradicts itself
+ * (sizes, components other than 3, a sampling other than 1x1 / 2x2, block counts, offsets that are no multiple of 8 or make two
+ * components overlap, a quantiser outside 1..255). */
+int dvs_jpeg_encode_views(void* stream, const dvs_jpeg_desc* desc, const float* const* images, int16_t* const* coef, int n_views);
 
 /* ---- undistortion: a view of a SIMPLE_RADIAL, RADIAL or OPENCV camera -> the view of the pinhole camera that keeps its fx, fy, cx, cy
  * and its W x H. Coefficients a model lacks are 0; a pixel centre is at (x + 0.5, y + 0.5), COLMAP's convention. The ten floats of

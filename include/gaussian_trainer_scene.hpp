@@ -89,6 +89,16 @@ struct GaussianTrainConfig {
     // The editor passes its "Splat Format" choice only as the suffix of modelPath (editor.cpp:1886-1904, 2024): while this field is 0 a
     // modelPath ending in ".compressed.ply" / ".splat" / ".spz" turns on the matching bit. DVS_EXPORT_FORMATS overrides the field.
     int exportFormats = 0;
+    // extension of this build, appended the same way (0 = the reference's behaviour: a save writes no picture). renderViews: bit 1 = the
+    // test cameras (evalHoldout), bit 2 = the training cameras; at every saveGaussianModel() they are rendered with the evaluation's
+    // options (full SH degree, mipAntiliased) and written as baseline JPEG files <modelPath>_<it>_renders/<image stem>.jpg (cam_%04d.jpg for
+    // a synthetic scene): the forward DCT and quantisation run on the device (include/dvs_image.h dvs_jpeg_encode_views), only the
+    // coefficients cross to the host, which Huffman-codes them. renderQuality: the IJG quality 1..100; renderSampling: 0 = 4:2:0,
+    // 1 = 4:4:4. DVS_RENDER_VIEWS / DVS_RENDER_QUALITY / DVS_RENDER_SAMPLING override them. The three are bytes: they sit in what was
+    // the struct's tail padding behind exportFormats, so sizeof(GaussianTrainConfig) is what it was.
+    uint8_t renderViews = 0;
+    uint8_t renderQuality = 90;
+    uint8_t renderSampling = 0;
 };
 
 class GSTRAIN_API GaussianTrainerScene {
@@ -140,6 +150,10 @@ public:
     double getTestPSNR() const;                       // means over the test cameras of the last evaluation, NaN before the first
     double getTestSSIM() const;
     double getTestL1() const;
+    // rendered views (extension of this build): camera i (any camera, held out or not) rendered now from the current parameters with the
+    // evaluation's options and written to `path` as a baseline JPEG at the config's renderQuality / renderSampling; synchronises.
+    // false for a bad index, before loadTrainData, or when the file cannot be written; nothing is thrown.
+    bool renderCameraToJpeg(int camera, const std::string& path);
     // trainer -> viewer hand-off (editor.cpp:1459-1473 -> GaussianModel::update_from_cpu, gaussian_model.cpp:43-68)
     const std::vector<float>& getGaussianPositionCpu();
     const std::vector<float>& getGaussianSH0Cpu();
