@@ -79,6 +79,7 @@ _PROTOS = {
     "dvs_create_views": (C.c_void_p, [C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int]),
     "dvs_destroy": (None, [C.c_void_p]),
     "dvs_raster_forward_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Splats), C.POINTER(Camera), C.c_int, C.POINTER(Opts), C.c_void_p]),
+    "dvs_raster_depth_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p]),
     "dvs_raster_forward_cancel_prepared": (C.c_int, [C.c_void_p]),
     "dvs_raster_forward_views_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Splats), C.POINTER(Camera), C.c_int, C.POINTER(Opts), C.c_int64, C.c_int64]),
     "dvs_raster_backward_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Splats), C.POINTER(Camera), C.c_int, C.POINTER(Opts),
@@ -216,6 +217,25 @@ _IMAGE_PROTOS = {
 }
 
 
+# include/dvs_mesh.h: TSDF fusion of depth maps and marching tetrahedra
+class TsdfGridDesc(C.Structure):       # dvs_tsdf_grid
+    _fields_ = [("origin", C.c_float * 3), ("voxel", C.c_float), ("dims", C.c_int32 * 3), ("_pad", C.c_int32), ("tsdf", C.c_void_p),
+                ("weight", C.c_void_p), ("rgb", C.c_void_p)]
+
+
+_MESH_PROTOS = {
+    "dvs_tsdf_bytes": (C.c_size_t, [C.POINTER(C.c_int32)]),
+    "dvs_tsdf_create": (C.c_int, [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int32), C.POINTER(TsdfGridDesc)]),
+    "dvs_tsdf_destroy": (None, [C.POINTER(TsdfGridDesc)]),
+    "dvs_tsdf_clear": (C.c_int, [C.c_void_p, C.POINTER(TsdfGridDesc)]),
+    "dvs_tsdf_integrate": (C.c_int, [C.c_void_p, C.POINTER(TsdfGridDesc), C.POINTER(Camera), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_float]),
+    "dvs_mesh_scratch_bytes": (C.c_size_t, [C.POINTER(C.c_int32)]),
+    "dvs_mesh_extract_count": (C.c_int, [C.c_void_p, C.POINTER(TsdfGridDesc), C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "dvs_mesh_extract_write": (C.c_int, [C.c_void_p, C.POINTER(TsdfGridDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+}
+
+
 def undistort_desc(model, params, width, height):
     """-> UndistortDesc of COLMAP model id 2, 3 or 4 and its parameter list (dvs_undistort_desc_from_colmap); DvsError when refused"""
     prm = (C.c_double * len(params))(*[float(v) for v in params])
@@ -225,7 +245,7 @@ def undistort_desc(model, params, width, height):
     if lib.dvs_undistort_desc_from_colmap(int(model), prm, int(width), int(height), C.byref(d)) != 0:
         raise DvsError(f"dvs_undistort_desc_from_colmap refused model {model}, {width}x{height}, {list(params)}")
     return d
-for _name, (_res, _args) in list(_PROTOS.items()) + list(_EXPORT_PROTOS.items()) + list(_INIT_PROTOS.items()) + list(_IMAGE_PROTOS.items()):
+for _name, (_res, _args) in list(_PROTOS.items()) + list(_EXPORT_PROTOS.items()) + list(_INIT_PROTOS.items()) + list(_IMAGE_PROTOS.items()) + list(_MESH_PROTOS.items()):
     _f = getattr(lib, _name)          # AttributeError here = the .so does not export a declared symbol
     _f.restype = _res
     _f.argtypes = _args
@@ -248,6 +268,10 @@ _JPEG_HOST_PROTOS = {
     "gstrain_jpeg_encoded_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gstrain_jpeg_encoded_free": (None, [C.c_void_p]),
 }
+# ... and the mesh file writer (ply_io.hpp write_mesh_ply)
+_MESH_HOST_PROTOS = {
+    "gstrain_write_mesh_ply": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64]),
+}
 _host_lib = None
 
 
@@ -259,12 +283,27 @@ def host_lib():
         if not os.path.exists(path):
             raise ImportError(f"{path} is missing: build it with `make -C divshot_amd/gstrain`")
         h = C.CDLL(path)
-        for name, (res, args) in _JPEG_HOST_PROTOS.items():
+        for name, (res, args) in list(_JPEG_HOST_PROTOS.items()) + list(_MESH_HOST_PROTOS.items()):
             f = getattr(h, name)
             f.restype = res
             f.argtypes = args
         _host_lib = h
     return _host_lib
+
+
+def write_mesh_ply(path, xyz, rgb, tri):
+    """gsply::write_mesh_ply through libgsplyio.so: xyz float32 [nv,3], rgb uint8 [nv,3], tri uint32 [nt,3]; DvsError with the writer's
+    message when it refuses (an index >= nv, a file it cannot write)"""
+    import numpy as np
+    h = host_lib()
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    rgb = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    tri = np.ascontiguousarray(tri, np.uint32).reshape(-1, 3)
+    if rgb.shape[0] != xyz.shape[0]:
+        raise DvsError("write_mesh_ply: xyz and rgb differ in length")
+    err = C.create_string_buffer(1024)
+    if h.gstrain_write_mesh_ply(os.fsencode(path), xyz.shape[0], xyz.ctypes.data, rgb.ctypes.data, tri.shape[0], tri.ctypes.data, err, 1024) != 0:
+        raise DvsError(err.value.decode(errors="replace"))
 
 
 def jpeg_encode_desc(width, height, sampling, quality):

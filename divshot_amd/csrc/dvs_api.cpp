@@ -613,6 +613,18 @@ int dvs_get_view_state(dvs_ctx* c, int view, dvs_fwd_state* out) {
     return DVS_OK;
 }
 
+// Depth and alpha maps of the last forward: a forward-only pass over the saved lists (depth.hip); reads the state, changes none of it
+int dvs_raster_depth_views(dvs_ctx* c, void* stream, const dvs_opts* opts, float* out_depth, float* out_alpha) {
+    const char* const who = "dvs_raster_depth_views";
+    if (!c || !opts || !out_depth || !out_alpha) return fail(DVS_ERR_INVALID, who, "null argument");
+    if (!c->fwd.have) return fail(DVS_ERR_STATE, who, "no forward on this context (valid after dvs_raster_forward / _views until the next forward)");
+    HIPCHECK(hipSetDevice(c->device));
+    const dvs_fwd_state& s = c->fwd.st;
+    HIPCHECK(dvs_launch_depth_views((hipStream_t)stream, s.width, s.height, s.tiles_x, s.tiles_y, c->fwd.n_views, s.ranges, s.sorted_splat, s.splat2d,
+                                    s.n_contrib, out_depth, out_alpha));
+    return DVS_OK;
+}
+
 // A8: zero the 48-B rows if needed, then the alpha-composite backward into them (all views of the last forward in one launch)
 static int bwd_composite(dvs_ctx* c, hipStream_t st, const dvs_camera* cams, const dvs_opts* opts, const float* dL_drgb, StageScope& tm) {
     const dvs_fwd_state& s = c->fwd.st;

@@ -131,6 +131,9 @@ hipError_t dvs_launch_render_fwd(hipStream_t st, int W, int H, int tiles_x, int 
                                  position -> number of such entries before it in its tile*/,
                                  uint64_t* take_masks /*test hook (or null): [take_cap][4] zeroed by the caller — per list position and 8x8 quadrant, the pixels that took the entry*/,
                                  uint64_t take_cap, uint32_t* ranges_out = nullptr /*where k_render_fwd leaves (start, end) when `ranges` is encoded*/);
+// depth.hip — expected depth and alpha of the saved forward state, all n_views views in one launch (out arrays are [n_views][H][W])
+hipError_t dvs_launch_depth_views(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, const uint32_t* ranges /*canonical (start, end)*/,
+                                  const uint32_t* sorted_splat, const float* splat2d, const uint32_t* n_contrib, float* out_depth, float* out_alpha);
 // A8 kernel variants (dvs_set_backward_variant): same inputs, same 48-B row contract, results equal to fp32 roundoff
 enum { DVS_BWD_BLOCKS = 0 /*per-4x4-block lists, four cursors per wave, 12-value group reduction per step (round 2): kept in the release library as
        the independent-summation-order cross-check of the parity tests*/, DVS_BWD_REDUCE = 1 /*per-quadrant masks, wave-wide reduction tree per visit

@@ -45,7 +45,10 @@ static std::map<std::string, std::string> g_opts = {
     {"pruneScale3d", "0.1"}, {"pruneScale2d", "0.15"},
     // extension of this build: every save also writes rendered views as JPEG files to <outputPath>_<it>_renders/: --renderViews test (the
     // held-out cameras of --eval) | train | all; --renderQuality 1..100; --renderSampling 420 | 444
-    {"renderViews", ""}, {"renderQuality", "90"}, {"renderSampling", "420"}};
+    {"renderViews", ""}, {"renderQuality", "90"}, {"renderSampling", "420"},
+    // the reference's config field meshResolution (its CLI has no flag for it): > 0 = the final save also writes <outputPath>_<it>_mesh.ply,
+    // the surface extracted on a grid of that many voxels along its longest side (16..1024). --exportMesh keeps the reference's meaning.
+    {"meshResolution", "0"}};
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
 
@@ -144,6 +147,8 @@ int main(int argc, const char* argv[]) {
         train_config.renderSampling = rs == "444" ? 1 : 0;
         train_config.renderQuality = (uint8_t)q;
     }
+    train_config.meshResolution = atoi(g_opts["meshResolution"].c_str());
+    if (train_config.meshResolution < 0) { std::cout << "Command Line Error: --meshResolution takes 0 (off) or a grid resolution, not '" << g_opts["meshResolution"] << "'\n"; return 1; }
     train_config.normalConsistencyLoss = false;
     if (train_config.exportMesh) { train_config.normalConsistencyLoss = true; train_config.useMask = true; }
     train_config.verbose = true;

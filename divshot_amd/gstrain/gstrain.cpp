@@ -15,7 +15,8 @@
 // load_train_data accepts a capture directory (a COLMAP sparse model plus PPM or baseline JPEG images: dataset_io.hpp; views of
 // SIMPLE_RADIAL / RADIAL / OPENCV cameras are undistorted on the device, include/dvs_image.h; the splats start from the sparse points,
 // include/dvs_init.h) or a synthetic-scene spec. Out of scope: PNG and progressive-JPEG
-// decoding, fisheye / FULL_OPENCV / FOV camera models, mesh export, the 2DGS model type. Every GaussianTrainConfig field the hosts set is either
+// decoding, fisheye / FULL_OPENCV / FOV camera models, training for mesh export with the normal-consistency loss, the 2DGS model type
+// (mesh export itself — depth maps, TSDF fusion, marching tetrahedra — is trainer_mesh.cpp). Every GaussianTrainConfig field the hosts set is either
 // honoured or named in the one-time "ignored" line of report_config().
 #include "trainer.hpp"
 
@@ -133,9 +134,18 @@ void GaussianTrainerScene::saveGaussianModel() {
             if (m.export_formats() & format) m.export_model(format);
     m.evaluate(true);                                                       // <modelPath>_<it>_eval.json beside the PLY (rank 0, evaluation on)
     m.render_at_save();                                                     // <modelPath>_<it>_renders/*.jpg (rank 0, renderViews on)
+    if (m.rank == 0 && m.mesh_resolution() > 0 && m.status == TrainingStatus::Training_Done)
+        m.extract_mesh(m.mesh_file(m.step), m.mesh_resolution());           // <modelPath>_<it>_mesh.ply (the finished model only)
 }
 
-void GaussianTrainerScene::exportMesh(const std::string&) { logf_("export_mesh: mesh extraction is outside this build's scope"); }
+// export_mesh() / exportMesh(""): <modelPath>_<it>_mesh.ply when meshResolution (DVS_MESH_RESOLUTION) > 0, else today's log line and no
+// file; exportMesh(path): that file, at resolution 256 when the field is 0.
+void GaussianTrainerScene::exportMesh(const std::string& path) {
+    Impl& m = *impl_;
+    const int res = m.mesh_resolution();
+    if (path.empty() && res <= 0) { logf_("export_mesh: mesh extraction is outside this build's scope"); return; }
+    m.extract_mesh(path.empty() ? m.mesh_file(m.step) : path, res > 0 ? res : 256);
+}
 void GaussianTrainerScene::exportSparsePointCloud(const std::string& path) {
     Impl& m = *impl_;
     m.fetch_host();

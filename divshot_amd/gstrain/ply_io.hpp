@@ -26,4 +26,9 @@ bool write_splat(const std::string& path, size_t n, const uint8_t* bytes, std::s
 // gzclose); without it the call fails with a message naming the library or the symbol.
 bool write_spz(const std::string& path, size_t n, int sh_degree, bool antialiased, const uint8_t* packed, const dvs_spz_layout& layout,
                std::string* err);
+// The extracted surface (include/dvs_mesh.h): binary_little_endian PLY, `element vertex` x y z float + red green blue uchar (15 bytes),
+// `element face` with `property list uchar uint vertex_indices` (13 bytes per triangle). An empty mesh is a valid file with zero
+// elements. Refused, with a message, when an index is >= n_vertices (nothing is written then).
+bool write_mesh_ply(const std::string& path, size_t n_vertices, const float* xyz, const uint8_t* rgb, size_t n_triangles, const uint32_t* tri,
+                    std::string* err);
 }

@@ -1,6 +1,7 @@
 // trainer.hpp — GaussianTrainerScene::Impl, the state behind `libgstrain.so`, and what its source files share. The members are defined
 // in trainer_load.cpp (loaders, allocation), trainer_step.cpp (one trainStep), trainer_refine.cpp (densification, pruning),
-// trainer_output.cpp (configuration report, evaluation, export) and trainer_render.cpp (rendered views as JPEG files); gstrain.cpp holds
+// trainer_output.cpp (configuration report, evaluation, export), trainer_render.cpp (rendered views as JPEG files) and trainer_mesh.cpp
+// (mesh export); gstrain.cpp holds
 // the GaussianTrainerScene members and the C symbols.
 #pragma once
 #include <chrono>
@@ -160,6 +161,14 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     void ensure_eval_ctx();
     bool render_to_jpeg(const std::vector<int>& which, const std::vector<std::string>& files, RenderStats* stats);
     void render_at_save();
+
+    // mesh export (cfg.meshResolution / DVS_MESH_RESOLUTION; trainer_mesh.cpp): the depth and alpha maps of a pass of eval_ctx. Nothing is
+    // allocated until the first mesh; the buffers only grow. The grid and the extraction scratch live for one extraction.
+    DevBuf<float> d_mesh_depth, d_mesh_alpha; size_t mesh_maps_cap = 0;
+    int mesh_resolution() const;
+    std::string mesh_file(int it) const { return cfg.modelPath + "_" + std::to_string(it) + "_mesh.ply"; }
+    bool mesh_bounds(float lo[3], float hi[3]);
+    bool extract_mesh(const std::string& path, int resolution);
 
     ~Impl() { if (device >= 0) (void)hipSetDevice(device); }                // (the members release themselves, after this body)
     // floats of group g on the device: the 45 higher-order SH floats live in the DVS_SHN_TILED layout (48 per splat,

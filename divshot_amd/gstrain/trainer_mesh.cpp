@@ -1,0 +1,153 @@
+// trainer_mesh.cpp — mesh export: the training cameras rendered through the evaluation context, their depth and alpha maps
+// (dvs_raster_depth_views) fused into a TSDF grid and the grid's surface extracted by marching tetrahedra (include/dvs_mesh.h), written
+// as a binary PLY (ply_io.hpp write_mesh_ply). Everything on the training stream; the training context is never touched.
+#include "trainer.hpp"
+#include "../../include/dvs_mesh.h"
+
+namespace {
+double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+struct GridGuard {                                                           // frees the grid on every way out
+    dvs_tsdf_grid g{};
+    ~GridGuard() { dvs_tsdf_destroy(&g); }
+};
+}  // namespace
+
+int GaussianTrainerScene::Impl::mesh_resolution() const { return env_int("DVS_MESH_RESOLUTION", cfg.meshResolution); }
+
+// The box the grid covers: DVS_MESH_BOUNDS=x0,y0,z0,x1,y1,z1, or the box of the centres of the splats with sigmoid(opacity) >= 0.5
+// cut to the cube of half-side 3 x extent about the camera centroid (extent: the scene extent the prune rules use).
+bool GaussianTrainerScene::Impl::mesh_bounds(float lo[3], float hi[3]) {
+    if (const char* e = getenv("DVS_MESH_BOUNDS")) {
+        float v[6];
+        if (sscanf(e, "%f,%f,%f,%f,%f,%f", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5]) == 6 && v[3] > v[0] && v[4] > v[1] && v[5] > v[2]) {
+            for (int k = 0; k < 3; ++k) { lo[k] = v[k]; hi[k] = v[3 + k]; }
+            return true;
+        }
+        logf_("mesh: DVS_MESH_BOUNDS='%s' is not x0,y0,z0,x1,y1,z1 with x1 > x0, y1 > y0, z1 > z0: ignored", e);
+    }
+    fetch_host();
+    double centre[3] = {0, 0, 0};
+    for (const dvs_camera& c : cams) for (int k = 0; k < 3; ++k) centre[k] += c.campos[k] / (double)cams.size();
+    for (int k = 0; k < 3; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; }
+    for (int i = 0; i < n; ++i) {
+        if (!(host[P_OPA][(size_t)i] >= 0.f)) continue;                      // sigmoid(o) >= 0.5 <=> o >= 0 (a NaN fails)
+        for (int k = 0; k < 3; ++k) {
+            const float p = host[P_POS][3 * (size_t)i + k];
+            if (!std::isfinite(p)) continue;
+            lo[k] = std::min(lo[k], p); hi[k] = std::max(hi[k], p);
+        }
+    }
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = std::max(lo[k], (float)(centre[k] - 3.0 * extent));
+        hi[k] = std::min(hi[k], (float)(centre[k] + 3.0 * extent));
+        if (!(hi[k] > lo[k])) return false;
+    }
+    return true;
+}
+
+// -> false when the grid does not fit the device or the file could not be written; throws on a failed device call. An empty box (no
+// opaque splat inside the cube) gives the empty mesh. Rank 0 only.
+bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resolution) {
+    if (rank != 0 || !ctx || cams.empty()) return false;
+    HIP_OR_THROW(hipSetDevice(device));
+    const TrainingStatus before = status;
+    status = TrainingStatus::GS2Mesh;
+    struct Restore { TrainingStatus& s; TrainingStatus v; ~Restore() { s = v; } } restore{status, before};
+    const int res = std::min(1024, std::max(16, resolution));
+    if (res != resolution) logf_("mesh @%d: meshResolution %d clamped to %d (16..1024)", step, resolution, res);
+    float lo[3], hi[3];
+    if (!mesh_bounds(lo, hi)) {
+        // nothing opaque inside the cube: the empty mesh, a valid file with zero elements, and the same log line
+        std::error_code ec0;
+        const auto dir = std::filesystem::path(path).parent_path();
+        if (!dir.empty()) std::filesystem::create_directories(dir, ec0);
+        std::string err0;
+        if (!gsply::write_mesh_ply(path, 0, nullptr, nullptr, 0, nullptr, &err0)) { logf_("mesh @%d: %s", step, err0.c_str()); return false; }
+        logf_("mesh @%d: 0 vertices, 0 triangles, grid 0x0x0, voxel 0, bounds %.9g,%.9g,%.9g,%.9g,%.9g,%.9g (no splat with opacity >= 0.5 within 3 x extent "
+              "= %.9g of the cameras' centroid; DVS_MESH_BOUNDS sets the box), trunc 0, 0 views; render+depth 0.00 ms, fusion 0.00 ms, extraction 0.00 ms -> %s",
+              step, (double)lo[0], (double)lo[1], (double)lo[2], (double)hi[0], (double)hi[1], (double)hi[2], 3.0 * (double)extent, path.c_str());
+        return true;
+    }
+    const float longest = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
+    const float voxel = longest / (float)res;
+    int32_t dims[3];
+    for (int k = 0; k < 3; ++k) dims[k] = std::min(DVS_TSDF_MAX_DIM, std::max(2, (int)std::ceil((hi[k] - lo[k]) / voxel) + 1));
+    const char* tv = getenv("DVS_MESH_TRUNC_VOXELS");
+    const float trunc_voxels = tv && atof(tv) > 0.0 ? (float)atof(tv) : 4.0f;
+    const float trunc = trunc_voxels * voxel;
+
+    GridGuard grid;
+    const int rc = dvs_tsdf_create(lo, voxel, dims, &grid.g);
+    if (rc == DVS_ERR_CAPACITY) { logf_("mesh @%d: a %dx%dx%d grid (%zu bytes) does not fit the free device memory: no mesh", step, dims[0], dims[1], dims[2], dvs_tsdf_bytes(dims)); return false; }
+    if (rc != DVS_OK) throw std::runtime_error("dvs_tsdf_create: status " + std::to_string(rc));
+
+    // render + depth + fusion: the training cameras in index order, eval_views per pass, the evaluation's options
+    ensure_eval_ctx();
+    const size_t P = (size_t)W * H;
+    if (mesh_maps_cap < (size_t)eval_views * P) {
+        mesh_maps_cap = 0;
+        d_mesh_depth.alloc((size_t)eval_views * P * sizeof(float));
+        d_mesh_alpha.alloc((size_t)eval_views * P * sizeof(float));
+        mesh_maps_cap = (size_t)eval_views * P;
+    }
+    std::vector<int> which = train_idx;
+    if (which.empty()) for (int c = 0; c < (int)cams.size(); ++c) which.push_back(c);
+    dvs_opts opts{};                                                         // the evaluation's (score_views)
+    opts.sh_degree = sh_max; opts.antialias = cfg.mipAntiliased ? 1 : 0; opts.shn_layout = DVS_SHN_TILED; opts.tile_bounds = DVS_TILES_CANONICAL;
+    const dvs_splats sp = splats();
+    double render_ms = 0, fuse_ms = 0;
+    for (int first = 0; first < (int)which.size(); first += eval_views) {
+        const int nb = std::min(eval_views, (int)which.size() - first);
+        std::vector<dvs_camera> bc((size_t)nb);
+        const float* masks[DVS_TSDF_MAX_VIEWS] = {};
+        for (int k = 0; k < nb; ++k) {
+            const size_t ci = (size_t)which[(size_t)(first + k)];
+            bc[(size_t)k] = cams[ci];
+            masks[k] = view_mask(ci);
+        }
+        auto t0_ = std::chrono::steady_clock::now();
+        DVS_OR_THROW(dvs_raster_forward_views(eval_ctx.get(), stream.get(), &sp, bc.data(), nb, &opts, d_eval_out.get()));
+        DVS_OR_THROW(dvs_raster_depth_views(eval_ctx.get(), stream.get(), &opts, d_mesh_depth.get(), d_mesh_alpha.get()));
+        HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+        render_ms += ms_since(t0_);
+        t0_ = std::chrono::steady_clock::now();
+        const int ri = dvs_tsdf_integrate(stream.get(), &grid.g, bc.data(), nb, d_mesh_depth.get(), d_mesh_alpha.get(), d_eval_out.get(), masks, W, H, trunc);
+        if (ri != DVS_OK) throw std::runtime_error("dvs_tsdf_integrate: status " + std::to_string(ri));
+        HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+        fuse_ms += ms_since(t0_);
+    }
+
+    // extraction, then the three arrays to the host
+    const auto t_ex = std::chrono::steady_clock::now();
+    DevBuf<void> scratch;
+    scratch.alloc(dvs_mesh_scratch_bytes(dims) + 256);
+    void* const sc = (void*)(((uintptr_t)scratch.get() + 255) & ~(uintptr_t)255);
+    uint32_t nv = 0, nt = 0;
+    const int rcount = dvs_mesh_extract_count(stream.get(), &grid.g, sc, &nv, &nt);
+    if (rcount != DVS_OK) throw std::runtime_error("dvs_mesh_extract_count: status " + std::to_string(rcount));
+    std::vector<float> xyz((size_t)nv * 3);
+    std::vector<uint8_t> rgb((size_t)nv * 3);
+    std::vector<uint32_t> tri((size_t)nt * 3);
+    if (nv > 0 && nt > 0) {
+        DevBuf<float> d_xyz; DevBuf<uint8_t> d_rgb; DevBuf<uint32_t> d_tri;
+        d_xyz.alloc(xyz.size() * sizeof(float)); d_rgb.alloc(rgb.size()); d_tri.alloc(tri.size() * sizeof(uint32_t));
+        const int rw = dvs_mesh_extract_write(stream.get(), &grid.g, sc, d_xyz.get(), d_rgb.get(), d_tri.get());
+        if (rw != DVS_OK) throw std::runtime_error("dvs_mesh_extract_write: status " + std::to_string(rw));
+        HIP_OR_THROW(hipMemcpyAsync(xyz.data(), d_xyz.get(), xyz.size() * sizeof(float), hipMemcpyDeviceToHost, stream.get()));
+        HIP_OR_THROW(hipMemcpyAsync(rgb.data(), d_rgb.get(), rgb.size(), hipMemcpyDeviceToHost, stream.get()));
+        HIP_OR_THROW(hipMemcpyAsync(tri.data(), d_tri.get(), tri.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.get()));
+        HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    } else { nv = 0; nt = 0; xyz.clear(); rgb.clear(); tri.clear(); }
+    const double extract_ms = ms_since(t_ex);
+
+    std::error_code ec;
+    const auto parent = std::filesystem::path(path).parent_path();
+    if (!parent.empty()) std::filesystem::create_directories(parent, ec);
+    std::string err;
+    if (!gsply::write_mesh_ply(path, nv, xyz.data(), rgb.data(), nt, tri.data(), &err)) { logf_("mesh @%d: %s", step, err.c_str()); return false; }
+    logf_("mesh @%d: %u vertices, %u triangles, grid %dx%dx%d, voxel %.9g, bounds %.9g,%.9g,%.9g,%.9g,%.9g,%.9g, trunc %.9g, %d views; render+depth %.2f ms, "
+          "fusion %.2f ms, extraction %.2f ms -> %s", step, nv, nt, dims[0], dims[1], dims[2], (double)voxel, (double)lo[0], (double)lo[1], (double)lo[2],
+          (double)(lo[0] + (dims[0] - 1) * voxel), (double)(lo[1] + (dims[1] - 1) * voxel), (double)(lo[2] + (dims[2] - 1) * voxel), (double)trunc,
+          (int)which.size(), render_ms, fuse_ms, extract_ms, path.c_str());
+    return true;
+}

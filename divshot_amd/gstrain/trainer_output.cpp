@@ -32,6 +32,10 @@ void GaussianTrainerScene::Impl::report_config() const {
               "evaluation's options; transform on the device, entropy coding on the host%s", render_views,
               render_views == RENDER_TEST ? "test" : render_views == RENDER_TRAIN ? "training" : "test and training", render_quality,
               render_sampling == 1 ? "4:4:4" : "4:2:0", (render_views & RENDER_TEST) && test_idx.empty() ? " (no camera is held out: every camera is a training camera)" : "");
+    if (const int res = mesh_resolution(); res > 0)
+        logf_("config: meshResolution %d: a save of the finished model and export_mesh() also write <modelPath>_<it>_mesh.ply — the training cameras' "
+              "depth maps fused into a TSDF grid of %d voxels along the longest side, marching tetrahedra, all on the device", res,
+              std::min(1024, std::max(16, res)));
     std::string ign;
     if (cfg.modelType != 0) ign += " modelType(only 3DGS)";
     if (cfg.cullSH) ign += " cullSH";

@@ -261,6 +261,15 @@ int dvs_raster_forward_views_prepare(dvs_ctx* ctx, void* stream, const dvs_splat
 int dvs_raster_forward_cancel_prepared(dvs_ctx* ctx);
 int dvs_get_view_state(dvs_ctx* ctx, int view, dvs_fwd_state* state);
 
+/* Depth and alpha maps of the last forward on the context: valid after dvs_raster_forward or dvs_raster_forward_views until the next
+ * forward (DVS_ERR_STATE otherwise), in synchronous and asynchronous mode and with either tile_bounds setting. A separate forward-only
+ * pass over the saved state (per-tile lists, n_contrib, the splat2d records); the composite kernels and their outputs are untouched.
+ * Per pixel it walks the tile's list entries [start, start + n_contrib) in order with the forward's rules (skip when power > 0, skip
+ * when alpha < 1/255, alpha = min(0.99, opacity exp(power))) and accumulates w = alpha T, D += w z (z = DVS_S2D_DEPTH), T *= 1 - alpha:
+ *   out_alpha = 1 - T (equal to 1 - final_T),   out_depth = D / out_alpha where out_alpha >= 1/255, else 0.
+ * out_depth, out_alpha: DEVICE [n_views,H,W] of the last forward. `opts` are those of that forward. Asynchronous, on `stream`. */
+int dvs_raster_depth_views(dvs_ctx* ctx, void* stream, const dvs_opts* opts, float* out_depth, float* out_alpha);
+
 /* Asynchronous forward. By default dvs_raster_forward synchronises `stream` once (it reads the instance count T to size the sort).
  * With dvs_set_async(ctx, 1) it never synchronises: the instance arena is over-allocated, T stays on the device and every kernel over
  * instances reads it there; *num_rendered and saved->num_rendered are DVS_T_UNKNOWN (dvs_get_num_rendered synchronises on demand).

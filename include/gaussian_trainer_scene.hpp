@@ -114,7 +114,7 @@ public:
     void trainSetup();
     void trainStep();                                 // one iteration: sample camera -> raster fwd -> loss -> raster bwd -> Adam
     void saveGaussianModel();                         // PLY at modelPath (external/tinygsplat/tiny_gsplat.cpp:168-241 layout)
-    void exportMesh(const std::string& path);         // out of scope: logs and returns
+    void exportMesh(const std::string& path);         // <path> ("": <modelPath>_<it>_mesh.ply, only when meshResolution > 0): INTEGRATION.md "Mesh export"
     void exportSparsePointCloud(const std::string& path);   // editor.cpp:3535 — writes the splat centres as an ASCII PLY point cloud
     void saveCameraDatas(const std::string& path);          // editor.cpp:3512 — one line per camera: centre, view matrix, intrinsics
     bool isTrain() const;
