@@ -237,6 +237,109 @@ k_reset_opacity(int n, float* __restrict__ opacity, float logit_max, float* __re
     if (v) v[i] = 0.f;
 }
 
+// ---- importance-scored pruning: exact selection of the splats a prune keeps (dvs_importance_plan) -------------------------------------
+// The pruned splats are the p = n - min(keep, n) smallest in the total order (score, then larger index first). A most-significant-
+// digit-first radix select over the 64-bit score finds the p-th smallest score S: eight rounds of (256-bin histogram of the next byte
+// over the splats that match the bytes chosen so far | one workgroup picks the byte in which the rank falls). Every splat below S
+// goes, every one above stays, and of the E splats equal to S the first E - r in index order stay (r = p - #{score < S}): the mark
+// pass resolves that with one scan of the equal flags. No host round trip: rank, prefix and cut live in the scratch.
+struct ImpState {
+    unsigned long long prefix;     // the bytes of S chosen so far (the others zero); after the last round: S
+    unsigned long long rank;       // 1-based rank of the p-th smallest among the splats that match the prefix; after the last round: r
+    unsigned long long cut;        // splats equal to S that stay (E - r); n when nothing is pruned
+};
+#define IMP_HIST_WORDS (8 * 256)
+__device__ __forceinline__ ImpState* imp_state(void* scratch) { return (ImpState*)scratch; }
+__device__ __forceinline__ uint32_t* imp_hist(void* scratch) { return (uint32_t*)((char*)scratch + 32); }
+__device__ __forceinline__ uint32_t* imp_blocks(void* scratch) { return imp_hist(scratch) + IMP_HIST_WORDS; }
+
+__global__ void __launch_bounds__(DB) k_importance_init(void* scratch, unsigned long long n, unsigned long long prune) {
+    uint32_t* h = imp_hist(scratch);
+    for (int k = threadIdx.x; k < IMP_HIST_WORDS; k += DB) h[k] = 0u;
+    if (threadIdx.x == 0) { ImpState* s = imp_state(scratch); s->prefix = 0ull; s->rank = prune; s->cut = n; }
+}
+// round `round` (0 = the most significant byte): counts byte (score >> shift) & 255 of the splats whose higher bytes equal the prefix's
+__global__ void __launch_bounds__(DB)
+k_importance_hist(int n, const unsigned long long* __restrict__ score, void* scratch, int round) {
+    __shared__ uint32_t h[256];
+    h[threadIdx.x] = 0u;
+    __syncthreads();
+    const int shift = 56 - 8 * round;
+    const unsigned long long prefix = imp_state(scratch)->prefix;
+    for (int64_t i = (int64_t)blockIdx.x * DB + threadIdx.x; i < n; i += (int64_t)gridDim.x * DB) {
+        const unsigned long long k = score[i];
+        if (round == 0 || (k >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&h[(uint32_t)(k >> shift) & 255u], 1u);
+    }
+    __syncthreads();
+    const uint32_t c = h[threadIdx.x];
+    if (c) atomicAdd(&imp_hist(scratch)[round * 256 + threadIdx.x], c);
+}
+// one workgroup, thread = byte value: the byte g with #{byte < g} < rank <= #{byte <= g}
+__global__ void __launch_bounds__(DB) k_importance_pick(void* scratch, int round) {
+    __shared__ uint32_t tmp[DB / 64 + 1];
+    ImpState* s = imp_state(scratch);
+    const unsigned long long rank = s->rank;
+    const uint32_t c = imp_hist(scratch)[round * 256 + threadIdx.x];
+    uint32_t tot;
+    const uint32_t below = d_block_excl_scan(c, tmp, &tot);               // (its barriers order the read of rank before the write below)
+    if ((unsigned long long)below < rank && rank <= (unsigned long long)below + c) {             // exactly one thread: 1 <= rank <= tot
+        s->prefix |= (unsigned long long)threadIdx.x << (56 - 8 * round);
+        s->rank = rank - below;
+        if (round == 7) s->cut = (unsigned long long)c - (rank - below);
+    }
+}
+// per block: (splats below S) | (splats equal to S) << 16, both <= DB
+__global__ void __launch_bounds__(DB)
+k_importance_blocksum(int n, const unsigned long long* __restrict__ score, void* scratch) {
+    __shared__ uint32_t tmp[DB / 64 + 1];
+    const int i = blockIdx.x * DB + threadIdx.x;
+    const unsigned long long S = imp_state(scratch)->prefix;
+    const unsigned long long k = i < n ? score[i] : ~0ull;
+    uint32_t tot;
+    (void)d_block_excl_scan((i < n && k < S ? 1u : 0u) | (i < n && k == S ? 1u << 16 : 0u), tmp, &tot);
+    if (threadIdx.x == 0) imp_blocks(scratch)[2 * blockIdx.x] = tot;
+}
+// single workgroup over the nb packed block sums, DB blocks per chunk with a running carry: per block the splats kept before it
+// (its first index - those below S before it - those equal to S before it beyond the first `cut`) and the equal ones before it
+__global__ void __launch_bounds__(DB) k_importance_scan_blocks(void* scratch, uint32_t nb, unsigned long long new_n, uint64_t* __restrict__ new_count) {
+    __shared__ uint32_t tmp[DB / 64 + 1];
+    uint32_t* blocks = imp_blocks(scratch);
+    const unsigned long long cut = imp_state(scratch)->cut;
+    unsigned long long cl = 0, ce = 0;
+    for (uint32_t base = 0; base < nb; base += DB) {
+        const uint32_t idx = base + threadIdx.x;
+        const uint32_t v = idx < nb ? blocks[2 * idx] : 0u;
+        uint32_t tl, te;
+        const unsigned long long el = cl + d_block_excl_scan(v & 0xffffu, tmp, &tl);
+        const unsigned long long ee = ce + d_block_excl_scan(v >> 16, tmp, &te);
+        if (idx < nb) {
+            blocks[2 * idx] = (uint32_t)((unsigned long long)idx * DB - el - (ee > cut ? ee - cut : 0ull));
+            blocks[2 * idx + 1] = (uint32_t)ee;
+        }
+        cl += tl; ce += te;
+    }
+    if (threadIdx.x == 0) *new_count = new_n;
+}
+__global__ void __launch_bounds__(DB)
+k_importance_mark(int n, const unsigned long long* __restrict__ score, const void* scratch, uint8_t* __restrict__ action,
+                  uint32_t* __restrict__ offsets) {
+    __shared__ uint32_t tmp[DB / 64 + 1];
+    const int i = blockIdx.x * DB + threadIdx.x;
+    const ImpState* s = (const ImpState*)scratch;
+    const unsigned long long S = s->prefix, cut = s->cut;
+    const uint32_t* blocks = (const uint32_t*)((const char*)scratch + 32) + IMP_HIST_WORDS;
+    const unsigned long long k = i < n ? score[i] : 0ull;
+    const bool equal = i < n && k == S;
+    uint32_t tot;
+    const uint32_t eq_before = blocks[2 * blockIdx.x + 1] + d_block_excl_scan(equal ? 1u : 0u, tmp, &tot);
+    const bool kept = i < n && (k > S || (equal && (unsigned long long)eq_before < cut));
+    const uint32_t ex = d_block_excl_scan(kept ? 1u : 0u, tmp, &tot);
+    if (i < n) {
+        action[i] = (uint8_t)(kept ? DVS_DENSIFY_KEEP : DVS_DENSIFY_PRUNE);
+        offsets[i] = blocks[2 * blockIdx.x] + ex;
+    }
+}
+
 extern "C" {
 int dvs_densify_accumulate(void* stream, int n, const int32_t* radii, const float* absgrad2d, int width, int height, float* grad_accum,
                            float* denom, int32_t* max_radii) {
@@ -278,6 +381,31 @@ int dvs_densify_apply(void* stream, int n, const uint8_t* action, const uint32_t
     if (n == 0) return DVS_OK;
     hipLaunchKernelGGL(k_densify_apply, dim3((n + DB - 1) / DB), dim3(DB), 0, (hipStream_t)stream, n, action, offsets, *prm, mode, src[0], src[1],
                        src[2], src[3], src[4], src[5], dst[0], dst[1], dst[2], dst[3], dst[4], dst[5], new_n);
+    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+}
+size_t dvs_importance_scratch_bytes(int n) {
+    if (n <= 0) return 0;
+    const size_t nb = ((size_t)n + DB - 1) / DB;
+    return (32 + (IMP_HIST_WORDS + 2 * nb) * sizeof(uint32_t) + 255) & ~(size_t)255;
+}
+int dvs_importance_plan(void* stream, int n, const uint64_t* score, uint32_t keep, uint8_t* action, uint32_t* offsets, void* scratch,
+                        uint64_t* new_count) {
+    if (n <= 0 || keep == 0 || !score || !action || !offsets || !scratch || !new_count || ((uintptr_t)score & 7u) || ((uintptr_t)scratch & 15u) ||
+        ((uintptr_t)new_count & 7u))
+        return DVS_ERR_INVALID;
+    hipStream_t st = (hipStream_t)stream;
+    const uint32_t nb = (uint32_t)((n + DB - 1) / DB);
+    const uint64_t kept = keep < (uint32_t)n ? keep : (uint32_t)n, prune = (uint64_t)n - kept;
+    const unsigned long long* sc = (const unsigned long long*)score;
+    hipLaunchKernelGGL(k_importance_init, dim3(1), dim3(DB), 0, st, scratch, (unsigned long long)n, (unsigned long long)prune);
+    if (prune > 0)                                                        // (nothing pruned: S = 0 and cut = n keep every splat)
+        for (int round = 0; round < 8; ++round) {
+            hipLaunchKernelGGL(k_importance_hist, dim3(nb < 1024u ? nb : 1024u), dim3(DB), 0, st, n, sc, scratch, round);
+            hipLaunchKernelGGL(k_importance_pick, dim3(1), dim3(DB), 0, st, scratch, round);
+        }
+    hipLaunchKernelGGL(k_importance_blocksum, dim3(nb), dim3(DB), 0, st, n, sc, scratch);
+    hipLaunchKernelGGL(k_importance_scan_blocks, dim3(1), dim3(DB), 0, st, scratch, nb, (unsigned long long)kept, new_count);
+    hipLaunchKernelGGL(k_importance_mark, dim3(nb), dim3(DB), 0, st, n, sc, (const void*)scratch, action, offsets);
     return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
 }
 int dvs_reset_opacity(void* stream, int n, float* opacity, float max_opacity, float* adam_m, float* adam_v) {

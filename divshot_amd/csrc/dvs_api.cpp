@@ -625,6 +625,20 @@ int dvs_raster_depth_views(dvs_ctx* c, void* stream, const dvs_opts* opts, float
     return DVS_OK;
 }
 
+// Per-splat blend weights of the last forward: a forward-only pass over the saved lists (importance.hip); reads the state, changes none of it
+int dvs_raster_importance_views(dvs_ctx* c, void* stream, const dvs_opts* opts, const float* const* masks, uint64_t* score_sum, uint32_t* score_max,
+                                uint32_t* hits) {
+    const char* const who = "dvs_raster_importance_views";
+    if (!c || !opts || !score_sum) return fail(DVS_ERR_INVALID, who, "null argument");
+    if (((uintptr_t)score_sum | (uintptr_t)score_max | (uintptr_t)hits) & 15u) return fail(DVS_ERR_INVALID, who, "score arrays must be 16-byte aligned");
+    if (!c->fwd.have) return fail(DVS_ERR_STATE, who, "no forward on this context (valid after dvs_raster_forward / _views until the next forward)");
+    HIPCHECK(hipSetDevice(c->device));
+    const dvs_fwd_state& s = c->fwd.st;
+    HIPCHECK(dvs_launch_importance_views((hipStream_t)stream, s.width, s.height, s.tiles_x, s.tiles_y, c->fwd.n_views, s.n, s.ranges, s.sorted_splat,
+                                         s.splat2d, s.n_contrib, masks, score_sum, score_max, hits));
+    return DVS_OK;
+}
+
 // A8: zero the 48-B rows if needed, then the alpha-composite backward into them (all views of the last forward in one launch)
 static int bwd_composite(dvs_ctx* c, hipStream_t st, const dvs_camera* cams, const dvs_opts* opts, const float* dL_drgb, StageScope& tm) {
     const dvs_fwd_state& s = c->fwd.st;

@@ -134,6 +134,11 @@ hipError_t dvs_launch_render_fwd(hipStream_t st, int W, int H, int tiles_x, int 
 // depth.hip — expected depth and alpha of the saved forward state, all n_views views in one launch (out arrays are [n_views][H][W])
 hipError_t dvs_launch_depth_views(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, const uint32_t* ranges /*canonical (start, end)*/,
                                   const uint32_t* sorted_splat, const float* splat2d, const uint32_t* n_contrib, float* out_depth, float* out_alpha);
+// importance.hip — per-splat blend weight of the saved forward state, all n_views views in one launch: accumulates into score_sum [n] (uint64),
+// score_max [n] and hits [n] (either may be null); masks = HOST array [n_views] of DEVICE [H,W] pointers, or null, entries may be null
+hipError_t dvs_launch_importance_views(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, int n, const uint32_t* ranges /*canonical (start, end)*/,
+                                       const uint32_t* sorted_splat, const float* splat2d, const uint32_t* n_contrib, const float* const* masks,
+                                       uint64_t* score_sum, uint32_t* score_max, uint32_t* hits);
 // A8 kernel variants (dvs_set_backward_variant): same inputs, same 48-B row contract, results equal to fp32 roundoff
 enum { DVS_BWD_BLOCKS = 0 /*per-4x4-block lists, four cursors per wave, 12-value group reduction per step (round 2): kept in the release library as
        the independent-summation-order cross-check of the parity tests*/, DVS_BWD_REDUCE = 1 /*per-quadrant masks, wave-wide reduction tree per visit

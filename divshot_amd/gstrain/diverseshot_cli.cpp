@@ -48,7 +48,10 @@ static std::map<std::string, std::string> g_opts = {
     {"renderViews", ""}, {"renderQuality", "90"}, {"renderSampling", "420"},
     // the reference's config field meshResolution (its CLI has no flag for it): > 0 = the final save also writes <outputPath>_<it>_mesh.ply,
     // the surface extracted on a grid of that many voxels along its longest side (16..1024). --exportMesh keeps the reference's meaning.
-    {"meshResolution", "0"}};
+    {"meshResolution", "0"},
+    // extension of this build: --importancePrune P (0..90) removes, at every prune occasion (--pruneStrategy > 0, every --pruneEvery steps after
+    // --refineStopIter) and after the light prune, the P % of the splats that contribute least to the training views; 0 = off
+    {"importancePrune", "0"}};
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
 
@@ -149,6 +152,12 @@ int main(int argc, const char* argv[]) {
     }
     train_config.meshResolution = atoi(g_opts["meshResolution"].c_str());
     if (train_config.meshResolution < 0) { std::cout << "Command Line Error: --meshResolution takes 0 (off) or a grid resolution, not '" << g_opts["meshResolution"] << "'\n"; return 1; }
+    {
+        const std::string& ip = g_opts["importancePrune"];
+        const bool digits = !ip.empty() && ip.size() <= 2 && ip.find_first_not_of("0123456789") == std::string::npos;
+        if (!digits || atoi(ip.c_str()) > 90) { std::cout << "Command Line Error: --importancePrune takes an integer 0..90, not '" << ip << "'\n"; return 1; }
+        train_config.importancePrune = (uint8_t)atoi(ip.c_str());
+    }
     train_config.normalConsistencyLoss = false;
     if (train_config.exportMesh) { train_config.normalConsistencyLoss = true; train_config.useMask = true; }
     train_config.verbose = true;

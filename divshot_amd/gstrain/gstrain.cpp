@@ -94,6 +94,7 @@ void GaussianTrainerScene::trainStep() {
         DVS_OR_THROW(dvs_reset_opacity(m.stream.get(), m.n, m.d_param[P_OPA].get(), 0.01f, m.d_m[P_OPA].get(), m.d_v[P_OPA].get()));
     if (s.prune_now) {
         m.prune_light(s.it);
+        m.prune_importance(s.it);                                            // (nothing when importancePrune is 0)
         pruenIteraions.push_back(s.it);
     }
     // same line the editor logs (application/editor/source/editor.cpp:1554), every 100 steps as there unless DVS_LOSS_EVERY said otherwise at load

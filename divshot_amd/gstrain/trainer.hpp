@@ -4,6 +4,7 @@
 // (mesh export); gstrain.cpp holds
 // the GaussianTrainerScene members and the C symbols.
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <cstdarg>
 #include <cmath>
@@ -169,6 +170,12 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     std::string mesh_file(int it) const { return cfg.modelPath + "_" + std::to_string(it) + "_mesh.ply"; }
     bool mesh_bounds(float lo[3], float hi[3]);
     bool extract_mesh(const std::string& path, int resolution);
+
+    // importance prune (cfg.importancePrune / DVS_IMPORTANCE_PRUNE; trainer_refine.cpp): the per-splat score summed over the training views
+    // and the selection's scratch. Nothing is allocated until the first such prune.
+    DevBuf<uint64_t> d_imp_score; DevBuf<void> d_imp_scratch;
+    int importance_prune() const { return std::min(90, std::max(0, env_int("DVS_IMPORTANCE_PRUNE", cfg.importancePrune))); }   // percent, 0 = off
+    void prune_importance(int it);
 
     ~Impl() { if (device >= 0) (void)hipSetDevice(device); }                // (the members release themselves, after this body)
     // floats of group g on the device: the 45 higher-order SH floats live in the DVS_SHN_TILED layout (48 per splat,

@@ -36,6 +36,13 @@ void GaussianTrainerScene::Impl::report_config() const {
         logf_("config: meshResolution %d: a save of the finished model and export_mesh() also write <modelPath>_<it>_mesh.ply — the training cameras' "
               "depth maps fused into a TSDF grid of %d voxels along the longest side, marching tetrahedra, all on the device", res,
               std::min(1024, std::max(16, res)));
+    if (const int P = importance_prune(); P > 0) {
+        const int asked = env_int("DVS_IMPORTANCE_PRUNE", cfg.importancePrune);
+        if (asked > 90) logf_("config: importancePrune %d clamped to 90", asked);
+        logf_("config: importancePrune %d: at every prune occasion%s, after the light prune, the %d %% of the splats with the smallest blend weight "
+              "summed over the %zu training cameras are removed (scored and selected on the device, every rank for itself)", P,
+              cfg.pruneStrategy > 0 ? "" : " (none: pruneStrategy is 0)", P, train_idx.empty() ? cams.size() : train_idx.size());
+    }
     std::string ign;
     if (cfg.modelType != 0) ign += " modelType(only 3DGS)";
     if (cfg.cullSH) ign += " cullSH";

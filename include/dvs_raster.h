@@ -270,6 +270,26 @@ int dvs_get_view_state(dvs_ctx* ctx, int view, dvs_fwd_state* state);
  * out_depth, out_alpha: DEVICE [n_views,H,W] of the last forward. `opts` are those of that forward. Asynchronous, on `stream`. */
 int dvs_raster_depth_views(dvs_ctx* ctx, void* stream, const dvs_opts* opts, float* out_depth, float* out_alpha);
 
+/* Per-splat blend weight of the last forward on the context — what every splat contributed to the rendered views, the score of the
+ * importance prune (dvs_importance_plan, dvs_train.h). Valid when dvs_raster_depth_views is (DVS_ERR_STATE otherwise), in synchronous
+ * and asynchronous mode and with either tile_bounds setting; a separate forward-only pass over the saved state like that one. Per pixel
+ * of every view it walks the tile's list entries [start, start + n_contrib) in order with the forward's rules and operations; every
+ * entry a pixel takes gets w = alpha T (the weight its colour is blended with), and per splat i the pass ACCUMULATES INTO three DEVICE
+ * arrays of n elements, 16-byte aligned, which the caller zeroes (so that a caller sums over as many passes as it likes):
+ *   score_sum[i] += sum of q = (uint32_t)rintf(w * 2^24) over the (view, pixel) pairs that took the splat. An integer on purpose:
+ *                   integer adds commute, so the array is bit-reproducible from run to run and identical on every rank. In units of
+ *                   2^-24; q >= 6 for every taken pair (alpha >= 1/255, T >= 1e-4), so 0 means that no pixel took the splat.
+ *   score_max[i]  = max(score_max[i], bits of w): for w >= 0 the unsigned order of the bits is the order of the floats; read the array
+ *                   as float. May be NULL.
+ *   hits[i]      += the number of (view, pixel) pairs that took the splat. May be NULL.
+ * masks: HOST array [n_views] of DEVICE [H,W] float pointers as dvs_tsdf_integrate takes them (read before the call returns), or NULL,
+ * and so may each entry: a pixel whose mask value is 0 contributes nothing to any of the three. The sum over the splats of a view's
+ * score_sum / 2^24 is the sum over its unmasked pixels of the alpha of dvs_raster_depth_views (sum of w = 1 - final_T), to the
+ * rounding of q. DVS_ERR_INVALID for a NULL ctx, opts or score_sum and for misaligned arrays. `opts` are those of that forward.
+ * Asynchronous, on `stream`. */
+int dvs_raster_importance_views(dvs_ctx* ctx, void* stream, const dvs_opts* opts, const float* const* masks, uint64_t* score_sum,
+                                uint32_t* score_max, uint32_t* hits);
+
 /* Asynchronous forward. By default dvs_raster_forward synchronises `stream` once (it reads the instance count T to size the sort).
  * With dvs_set_async(ctx, 1) it never synchronises: the instance arena is over-allocated, T stays on the device and every kernel over
  * instances reads it there; *num_rendered and saved->num_rendered are DVS_T_UNKNOWN (dvs_get_num_rendered synchronises on demand).

@@ -169,6 +169,17 @@ int dvs_densify_plan(void* stream, int n, const float* opacity, const float* sca
 /* src/dst: six DEVICE arrays in A0 order (pos, sh0, shN, opacity, scale, rot); dst sized for the new count. */
 int dvs_densify_apply(void* stream, int n, const uint8_t* action, const uint32_t* offsets, const dvs_densify_params* prm, int mode,
                       const float* const src[6], float* const dst[6], int new_n);
+/* Importance prune: keeps the `keep` splats with the largest score (dvs_raster_importance_views' score_sum summed over the training views,
+ * dvs_raster.h) and leaves the plan in the form dvs_densify_plan does, so that dvs_densify_apply (modes 0 and 1) compacts from it.
+ * Exactly n - min(keep, n) splats are marked DVS_DENSIFY_PRUNE, the rest DVS_DENSIFY_KEEP: the pruned ones are the smallest in the total
+ * order (score, then larger index first) — the result is unique, ties included. offsets[n] = the exclusive scan of the kept splats,
+ * *new_count (DEVICE uint64) = min(keep, n). Exact and on the device: a most-significant-byte-first radix select over the 64-bit score
+ * (eight histogram + pick rounds), then one marking pass that resolves the ties by index; no host round trip. Asynchronous on `stream`.
+ * scratch: dvs_importance_scratch_bytes(n) bytes, 16-byte aligned, contents irrelevant. DVS_ERR_INVALID for n <= 0, keep == 0, NULL or
+ * misaligned pointers. */
+size_t dvs_importance_scratch_bytes(int n);
+int dvs_importance_plan(void* stream, int n, const uint64_t* score, uint32_t keep, uint8_t* action, uint32_t* offsets, void* scratch,
+                        uint64_t* new_count);
 /* opacity reset (--resetAlphaEvery): opacity = min(opacity, logit(max_opacity)); zeroes the matching Adam moments if given. */
 int dvs_reset_opacity(void* stream, int n, float* opacity, float max_opacity, float* adam_m, float* adam_v);
 

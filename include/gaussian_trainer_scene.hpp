@@ -99,6 +99,13 @@ struct GaussianTrainConfig {
     uint8_t renderViews = 0;
     uint8_t renderQuality = 90;
     uint8_t renderSampling = 0;
+    // extension of this build, the last free byte of that tail padding (0 = the reference's behaviour: the light prune alone).
+    // importancePrune = P in 1..90: at every prune occasion (pruneStrategy > 0, every pruneInterval steps after refineStopIter; there is
+    // no second schedule), after the light prune, the P % of the splats that contribute least to the training views are removed. The
+    // score of a splat is its blend weight alpha T summed over every pixel of every training camera (dvs_raster_importance_views,
+    // dvs_raster.h), so a splat hidden behind others in every view goes first whatever its opacity. Values above 90 are clamped.
+    // DVS_IMPORTANCE_PRUNE overrides the field.
+    uint8_t importancePrune = 0;
 };
 
 class GSTRAIN_API GaussianTrainerScene {
