@@ -226,6 +226,10 @@ class TsdfGridDesc(C.Structure):       # dvs_tsdf_grid
                 ("weight", C.c_void_p), ("rgb", C.c_void_p)]
 
 
+class MeshCleanInfo(C.Structure):      # dvs_mesh_clean_info
+    _fields_ = [(n, C.c_uint32) for n in ("n_components", "largest", "kept_components", "kept_vertices", "kept_triangles", "n_bad")]
+
+
 _MESH_PROTOS = {
     "dvs_tsdf_bytes": (C.c_size_t, [C.POINTER(C.c_int32)]),
     "dvs_tsdf_create": (C.c_int, [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int32), C.POINTER(TsdfGridDesc)]),
@@ -236,6 +240,12 @@ _MESH_PROTOS = {
     "dvs_mesh_scratch_bytes": (C.c_size_t, [C.POINTER(C.c_int32)]),
     "dvs_mesh_extract_count": (C.c_int, [C.c_void_p, C.POINTER(TsdfGridDesc), C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "dvs_mesh_extract_write": (C.c_int, [C.c_void_p, C.POINTER(TsdfGridDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_mesh_extract_normals": (C.c_int, [C.c_void_p, C.POINTER(TsdfGridDesc), C.c_void_p, C.c_void_p]),
+    "dvs_mesh_components": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "dvs_mesh_clean_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "dvs_mesh_clean_count": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(MeshCleanInfo)]),
+    "dvs_mesh_clean_write": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -274,6 +284,7 @@ _JPEG_HOST_PROTOS = {
 # ... and the mesh file writer (ply_io.hpp write_mesh_ply)
 _MESH_HOST_PROTOS = {
     "gstrain_write_mesh_ply": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64]),
+    "gstrain_write_mesh_ply_normals": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64]),
 }
 _host_lib = None
 
@@ -294,9 +305,10 @@ def host_lib():
     return _host_lib
 
 
-def write_mesh_ply(path, xyz, rgb, tri):
-    """gsply::write_mesh_ply through libgsplyio.so: xyz float32 [nv,3], rgb uint8 [nv,3], tri uint32 [nt,3]; DvsError with the writer's
-    message when it refuses (an index >= nv, a file it cannot write)"""
+def write_mesh_ply(path, xyz, rgb, tri, normals=None):
+    """gsply::write_mesh_ply through libgsplyio.so: xyz float32 [nv,3], rgb uint8 [nv,3], tri uint32 [nt,3], normals None or float32 [nv,3]
+    (then the vertex carries nx ny nz between z and red); DvsError with the writer's message when it refuses (an index >= nv, a file it
+    cannot write)"""
     import numpy as np
     h = host_lib()
     xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
@@ -305,7 +317,15 @@ def write_mesh_ply(path, xyz, rgb, tri):
     if rgb.shape[0] != xyz.shape[0]:
         raise DvsError("write_mesh_ply: xyz and rgb differ in length")
     err = C.create_string_buffer(1024)
-    if h.gstrain_write_mesh_ply(os.fsencode(path), xyz.shape[0], xyz.ctypes.data, rgb.ctypes.data, tri.shape[0], tri.ctypes.data, err, 1024) != 0:
+    if normals is None:
+        rc = h.gstrain_write_mesh_ply(os.fsencode(path), xyz.shape[0], xyz.ctypes.data, rgb.ctypes.data, tri.shape[0], tri.ctypes.data, err, 1024)
+    else:
+        normals = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if normals.shape[0] != xyz.shape[0]:
+            raise DvsError("write_mesh_ply: xyz and normals differ in length")
+        rc = h.gstrain_write_mesh_ply_normals(os.fsencode(path), xyz.shape[0], xyz.ctypes.data, normals.ctypes.data, rgb.ctypes.data, tri.shape[0],
+                                              tri.ctypes.data, err, 1024)
+    if rc != 0:
         raise DvsError(err.value.decode(errors="replace"))
 
 

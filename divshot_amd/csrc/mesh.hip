@@ -16,10 +16,12 @@
 #include <string.h>
 #include "../../include/dvs_mesh.h"
 #include "dvs_device.h"
+#include "dvs_kernels.h"
 
 #define MB 256
 #define SCAN_ITEMS 8
 #define SCAN_TILE (MB * SCAN_ITEMS)
+static_assert(SCAN_TILE == DVS_SCAN_TILE, "dvs_kernels.h tells the scan's other users how many block sums it needs");
 
 namespace {
 struct GridDims { int dx, dy, dz; };
@@ -328,6 +330,17 @@ hipError_t scan_in_place(hipStream_t st, uint32_t* v, size_t n, uint32_t* bsum, 
     return hipGetLastError();
 }
 }  // namespace
+
+// for mesh_clean.hip (dvs_kernels.h): the same scan, and where the extraction's scratch keeps what the normals read
+hipError_t dvs_launch_scan_u32(hipStream_t st, uint32_t* v, size_t n, uint32_t* bsum, unsigned long long* total) {
+    return scan_in_place(st, v, n, bsum, (uint32_t)((n + SCAN_TILE - 1) / SCAN_TILE), total);
+}
+bool dvs_mesh_scratch_parts(const int32_t dims[3], size_t* vert_off, size_t* flags) {
+    if (!dims_ok(dims)) return false;
+    const MeshScratch L = mesh_layout((size_t)dims[0] * dims[1] * dims[2]);
+    *vert_off = L.vert_off; *flags = L.flags;
+    return true;
+}
 
 extern "C" size_t dvs_tsdf_bytes(const int32_t dims[3]) { return dims_ok(dims) ? (size_t)dims[0] * dims[1] * dims[2] * 20 : 0; }
 

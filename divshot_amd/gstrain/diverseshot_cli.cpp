@@ -51,7 +51,12 @@ static std::map<std::string, std::string> g_opts = {
     {"meshResolution", "0"},
     // extension of this build: --importancePrune P (0..90) removes, at every prune occasion (--pruneStrategy > 0, every --pruneEvery steps after
     // --refineStopIter) and after the light prune, the P % of the splats that contribute least to the training views; 0 = off
-    {"importancePrune", "0"}};
+    {"importancePrune", "0"},
+    // extensions of this build, for the mesh --meshResolution writes: --meshMinComponent P (percent, 0..100, at most two decimals) drops the
+    // connected components with fewer than P % of the largest one's triangles; --meshNormals 1 adds nx ny nz, the TSDF gradient's unit
+    // normals. The config struct has no room left: when given they are handed to the plugin as DVS_MESH_MIN_COMPONENT / DVS_MESH_NORMALS.
+    {"meshMinComponent", "0"}, {"meshNormals", "0"}};
+static std::map<std::string, bool> g_given;
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
 
@@ -81,6 +86,22 @@ int main(int argc, const char* argv[]) {
         else if (i + 1 < argc) val = argv[++i];
         if (!g_opts.count(a)) { std::cout << "Command Line Error: unknown flag --" << a << "\n"; return 1; }   // config_extras_mode::error
         g_opts[a] = val;
+        g_given[a] = true;
+    }
+    if (g_given.count("meshMinComponent")) {
+        const std::string& v = g_opts["meshMinComponent"];
+        const size_t dot = v.find('.');
+        const std::string whole = v.substr(0, dot), frac = dot == std::string::npos ? "" : v.substr(dot + 1);
+        const bool ok = !whole.empty() && whole.size() <= 3 && whole.find_first_not_of("0123456789") == std::string::npos && frac.size() <= 2 &&
+                        frac.find_first_not_of("0123456789") == std::string::npos &&
+                        atoi(whole.c_str()) * 100 + atoi((frac + "00").substr(0, 2).c_str()) <= 10000;
+        if (!ok) { std::cout << "Command Line Error: --meshMinComponent takes a percentage 0..100 with at most two decimals, not '" << v << "'\n"; return 1; }
+        setenv("DVS_MESH_MIN_COMPONENT", v.c_str(), 1);                     // before the plugin is loaded
+    }
+    if (g_given.count("meshNormals")) {
+        const std::string& v = g_opts["meshNormals"];
+        if (v != "0" && v != "1") { std::cout << "Command Line Error: --meshNormals takes 0 or 1, not '" << v << "'\n"; return 1; }
+        setenv("DVS_MESH_NORMALS", v.c_str(), 1);
     }
     // plugin: "libgstrain.so" next to the executable (plugin.cpp:74 builds parent_path / "lib<name>.so")
     std::error_code ec;

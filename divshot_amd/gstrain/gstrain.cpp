@@ -147,6 +147,13 @@ void GaussianTrainerScene::exportMesh(const std::string& path) {
     if (path.empty() && res <= 0) { logf_("export_mesh: mesh extraction is outside this build's scope"); return; }
     m.extract_mesh(path.empty() ? m.mesh_file(m.step) : path, res > 0 ? res : 256);
 }
+// The editor's switch for what DVS_MESH_MIN_COMPONENT / DVS_MESH_NORMALS set for the CLI: once called it wins over the environment.
+void GaussianTrainerScene::setMeshCleanup(float minComponentPercent, bool normals) {
+    Impl& m = *impl_;
+    const float p = std::isfinite(minComponentPercent) ? std::min(100.0f, std::max(0.0f, minComponentPercent)) : 0.0f;
+    m.mesh_min_bp_set = (int)std::lround((double)p * 100.0);
+    m.mesh_normals_set = normals ? 1 : 0;
+}
 void GaussianTrainerScene::exportSparsePointCloud(const std::string& path) {
     Impl& m = *impl_;
     m.fetch_host();

@@ -32,4 +32,13 @@ __attribute__((visibility("default"))) int gstrain_write_mesh_ply(const char* pa
     if (err_out && err_cap > 0) { const size_t k = std::min<size_t>(err.size(), (size_t)err_cap - 1); memcpy(err_out, err.data(), k); err_out[k] = 0; }
     return 1;
 }
+// ... with vertex normals ([n_vertices][3]; NULL = the call above)
+__attribute__((visibility("default"))) int gstrain_write_mesh_ply_normals(const char* path, uint64_t n_vertices, const float* xyz, const float* normals,
+                                                                           const uint8_t* rgb, uint64_t n_triangles, const uint32_t* tri, char* err_out,
+                                                                           uint64_t err_cap) {
+    std::string err;
+    if (gsply::write_mesh_ply(path, (size_t)n_vertices, xyz, rgb, (size_t)n_triangles, tri, &err, normals)) return 0;
+    if (err_out && err_cap > 0) { const size_t k = std::min<size_t>(err.size(), (size_t)err_cap - 1); memcpy(err_out, err.data(), k); err_out[k] = 0; }
+    return 1;
+}
 }

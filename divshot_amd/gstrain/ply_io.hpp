@@ -28,7 +28,8 @@ bool write_spz(const std::string& path, size_t n, int sh_degree, bool antialiase
                std::string* err);
 // The extracted surface (include/dvs_mesh.h): binary_little_endian PLY, `element vertex` x y z float + red green blue uchar (15 bytes),
 // `element face` with `property list uchar uint vertex_indices` (13 bytes per triangle). An empty mesh is a valid file with zero
-// elements. Refused, with a message, when an index is >= n_vertices (nothing is written then).
+// elements. Refused, with a message, when an index is >= n_vertices (nothing is written then). With `normals` ([n_vertices][3]) the
+// vertex carries nx ny nz float between z and red (27 bytes); without them the file is what it always was.
 bool write_mesh_ply(const std::string& path, size_t n_vertices, const float* xyz, const uint8_t* rgb, size_t n_triangles, const uint32_t* tri,
-                    std::string* err);
+                    std::string* err, const float* normals = nullptr);
 }

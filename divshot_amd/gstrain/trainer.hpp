@@ -170,6 +170,11 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     std::string mesh_file(int it) const { return cfg.modelPath + "_" + std::to_string(it) + "_mesh.ply"; }
     bool mesh_bounds(float lo[3], float hi[3]);
     bool extract_mesh(const std::string& path, int resolution);
+    // what happens to the mesh before it is written: DVS_MESH_MIN_COMPONENT (percent of the largest component's triangles, at most two
+    // decimals; kept here in 1/100 percent) and DVS_MESH_NORMALS (0 | 1), or what setMeshCleanup said (-1: it was not called)
+    int mesh_min_bp_set = -1, mesh_normals_set = -1;
+    int mesh_min_bp() const;
+    bool mesh_normals() const;
 
     // importance prune (cfg.importancePrune / DVS_IMPORTANCE_PRUNE; trainer_refine.cpp): the per-splat score summed over the training views
     // and the selection's scratch. Nothing is allocated until the first such prune.

@@ -1,6 +1,7 @@
 // trainer_mesh.cpp — mesh export: the training cameras rendered through the evaluation context, their depth and alpha maps
 // (dvs_raster_depth_views) fused into a TSDF grid and the grid's surface extracted by marching tetrahedra (include/dvs_mesh.h), written
-// as a binary PLY (ply_io.hpp write_mesh_ply). Everything on the training stream; the training context is never touched.
+// optionally given normals and freed of its small components on the device (DVS_MESH_NORMALS, DVS_MESH_MIN_COMPONENT / setMeshCleanup),
+// and written as a binary PLY (ply_io.hpp write_mesh_ply). Everything on the training stream; the training context is never touched.
 #include "trainer.hpp"
 #include "../../include/dvs_mesh.h"
 
@@ -13,6 +14,26 @@ struct GridGuard {                                                           // 
 }  // namespace
 
 int GaussianTrainerScene::Impl::mesh_resolution() const { return env_int("DVS_MESH_RESOLUTION", cfg.meshResolution); }
+
+// DVS_MESH_MIN_COMPONENT: digits with at most two decimals, 0..100 -> 1/100 percent; anything else is reported once and ignored
+int GaussianTrainerScene::Impl::mesh_min_bp() const {
+    if (mesh_min_bp_set >= 0) return mesh_min_bp_set;
+    const char* e = getenv("DVS_MESH_MIN_COMPONENT");
+    if (!e) return 0;
+    int whole = 0, frac = 0, nw = 0, nf = 0;
+    const char* c = e;
+    for (; *c >= '0' && *c <= '9' && nw < 4; ++c, ++nw) whole = whole * 10 + (*c - '0');
+    if (*c == '.') for (++c; *c >= '0' && *c <= '9' && nf < 3; ++c, ++nf) frac = frac * 10 + (*c - '0');
+    const int bp = whole * 100 + (nf == 1 ? frac * 10 : frac);
+    if (*c || nw == 0 || nw > 3 || nf > 2 || bp > 10000) {
+        static bool said = false;
+        if (!said) logf_("mesh: DVS_MESH_MIN_COMPONENT='%s' is not a percentage 0..100 with at most two decimals: ignored", e);
+        said = true;
+        return 0;
+    }
+    return bp;
+}
+bool GaussianTrainerScene::Impl::mesh_normals() const { return mesh_normals_set >= 0 ? mesh_normals_set != 0 : env_is("DVS_MESH_NORMALS", "1"); }
 
 // The box the grid covers: DVS_MESH_BOUNDS=x0,y0,z0,x1,y1,z1, or the box of the centres of the splats with sigmoid(opacity) >= 0.5
 // cut to the cube of half-side 3 x extent about the camera centroid (extent: the scene extent the prune rules use).
@@ -62,7 +83,8 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
         const auto dir = std::filesystem::path(path).parent_path();
         if (!dir.empty()) std::filesystem::create_directories(dir, ec0);
         std::string err0;
-        if (!gsply::write_mesh_ply(path, 0, nullptr, nullptr, 0, nullptr, &err0)) { logf_("mesh @%d: %s", step, err0.c_str()); return false; }
+        static const float no_normals[3] = {0, 0, 0};                     // (zero vertices: only the header's nx ny nz)
+        if (!gsply::write_mesh_ply(path, 0, nullptr, nullptr, 0, nullptr, &err0, mesh_normals() ? no_normals : nullptr)) { logf_("mesh @%d: %s", step, err0.c_str()); return false; }
         logf_("mesh @%d: 0 vertices, 0 triangles, grid 0x0x0, voxel 0, bounds %.9g,%.9g,%.9g,%.9g,%.9g,%.9g (no splat with opacity >= 0.5 within 3 x extent "
               "= %.9g of the cameras' centroid; DVS_MESH_BOUNDS sets the box), trunc 0, 0 views; render+depth 0.00 ms, fusion 0.00 ms, extraction 0.00 ms -> %s",
               step, (double)lo[0], (double)lo[1], (double)lo[2], (double)hi[0], (double)hi[1], (double)hi[2], 3.0 * (double)extent, path.c_str());
@@ -117,7 +139,7 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
         fuse_ms += ms_since(t0_);
     }
 
-    // extraction, then the three arrays to the host
+    // extraction, normals and clean-up when asked for, then the final arrays alone to the host
     const auto t_ex = std::chrono::steady_clock::now();
     DevBuf<void> scratch;
     scratch.alloc(dvs_mesh_scratch_bytes(dims) + 256);
@@ -125,29 +147,75 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
     uint32_t nv = 0, nt = 0;
     const int rcount = dvs_mesh_extract_count(stream.get(), &grid.g, sc, &nv, &nt);
     if (rcount != DVS_OK) throw std::runtime_error("dvs_mesh_extract_count: status " + std::to_string(rcount));
-    std::vector<float> xyz((size_t)nv * 3);
-    std::vector<uint8_t> rgb((size_t)nv * 3);
-    std::vector<uint32_t> tri((size_t)nt * 3);
+    std::vector<float> xyz, nrm;
+    std::vector<uint8_t> rgb;
+    std::vector<uint32_t> tri;
+    const bool want_normals = mesh_normals();
+    const uint32_t min_bp = (uint32_t)mesh_min_bp();
+    bool cleaned = false;
+    dvs_mesh_clean_info info{};
+    double normals_ms = 0, clean_ms = 0;
     if (nv > 0 && nt > 0) {
-        DevBuf<float> d_xyz; DevBuf<uint8_t> d_rgb; DevBuf<uint32_t> d_tri;
-        d_xyz.alloc(xyz.size() * sizeof(float)); d_rgb.alloc(rgb.size()); d_tri.alloc(tri.size() * sizeof(uint32_t));
+        DevBuf<float> d_xyz, d_nrm, c_xyz, c_nrm; DevBuf<uint8_t> d_rgb, c_rgb; DevBuf<uint32_t> d_tri, c_tri;
+        d_xyz.alloc((size_t)nv * 3 * sizeof(float)); d_rgb.alloc((size_t)nv * 3); d_tri.alloc((size_t)nt * 3 * sizeof(uint32_t));
         const int rw = dvs_mesh_extract_write(stream.get(), &grid.g, sc, d_xyz.get(), d_rgb.get(), d_tri.get());
         if (rw != DVS_OK) throw std::runtime_error("dvs_mesh_extract_write: status " + std::to_string(rw));
-        HIP_OR_THROW(hipMemcpyAsync(xyz.data(), d_xyz.get(), xyz.size() * sizeof(float), hipMemcpyDeviceToHost, stream.get()));
-        HIP_OR_THROW(hipMemcpyAsync(rgb.data(), d_rgb.get(), rgb.size(), hipMemcpyDeviceToHost, stream.get()));
-        HIP_OR_THROW(hipMemcpyAsync(tri.data(), d_tri.get(), tri.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.get()));
+        const float *f_xyz = d_xyz.get(), *f_nrm = nullptr; const uint8_t* f_rgb = d_rgb.get(); const uint32_t* f_tri = d_tri.get();   // the final arrays
+        if (want_normals) {
+            d_nrm.alloc((size_t)nv * 3 * sizeof(float));
+            HIP_OR_THROW(hipStreamSynchronize(stream.get()));                // (the timers' boundary; only when normals are asked for)
+            const auto t_n = std::chrono::steady_clock::now();
+            const int rn = dvs_mesh_extract_normals(stream.get(), &grid.g, sc, d_nrm.get());
+            if (rn != DVS_OK) throw std::runtime_error("dvs_mesh_extract_normals: status " + std::to_string(rn));
+            HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+            normals_ms = ms_since(t_n);
+            f_nrm = d_nrm.get();
+        }
+        if (min_bp > 0) {
+            HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+            const auto t_c = std::chrono::steady_clock::now();
+            DevBuf<void> cscratch;
+            cscratch.alloc(dvs_mesh_clean_scratch_bytes(nv, nt) + 256);
+            void* const cs = (void*)(((uintptr_t)cscratch.get() + 255) & ~(uintptr_t)255);
+            const int rc_ = dvs_mesh_clean_count(stream.get(), nv, d_tri.get(), nt, min_bp, cs, &info);
+            if (rc_ != DVS_OK) throw std::runtime_error("dvs_mesh_clean_count: status " + std::to_string(rc_));
+            c_xyz.alloc(std::max<size_t>(1, info.kept_vertices) * 3 * sizeof(float)); c_rgb.alloc(std::max<size_t>(1, info.kept_vertices) * 3);
+            c_tri.alloc(std::max<size_t>(1, info.kept_triangles) * 3 * sizeof(uint32_t));
+            if (want_normals) c_nrm.alloc(std::max<size_t>(1, info.kept_vertices) * 3 * sizeof(float));
+            const int rcw = dvs_mesh_clean_write(stream.get(), nv, d_xyz.get(), d_rgb.get(), f_nrm, d_tri.get(), nt, cs, c_xyz.get(), c_rgb.get(),
+                                                 want_normals ? c_nrm.get() : nullptr, c_tri.get());
+            if (rcw != DVS_OK) throw std::runtime_error("dvs_mesh_clean_write: status " + std::to_string(rcw));
+            HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+            clean_ms = ms_since(t_c);
+            cleaned = true;
+            nv = info.kept_vertices; nt = info.kept_triangles;
+            f_xyz = c_xyz.get(); f_rgb = c_rgb.get(); f_tri = c_tri.get(); f_nrm = want_normals ? c_nrm.get() : nullptr;
+        }
+        xyz.resize((size_t)nv * 3); rgb.resize((size_t)nv * 3); tri.resize((size_t)nt * 3);
+        if (want_normals) nrm.resize((size_t)nv * 3);
+        if (nv > 0) {
+            HIP_OR_THROW(hipMemcpyAsync(xyz.data(), f_xyz, xyz.size() * sizeof(float), hipMemcpyDeviceToHost, stream.get()));
+            HIP_OR_THROW(hipMemcpyAsync(rgb.data(), f_rgb, rgb.size(), hipMemcpyDeviceToHost, stream.get()));
+            if (want_normals) HIP_OR_THROW(hipMemcpyAsync(nrm.data(), f_nrm, nrm.size() * sizeof(float), hipMemcpyDeviceToHost, stream.get()));
+        }
+        if (nt > 0) HIP_OR_THROW(hipMemcpyAsync(tri.data(), f_tri, tri.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.get()));
         HIP_OR_THROW(hipStreamSynchronize(stream.get()));
-    } else { nv = 0; nt = 0; xyz.clear(); rgb.clear(); tri.clear(); }
-    const double extract_ms = ms_since(t_ex);
+    } else { nv = 0; nt = 0; }
+    const double extract_ms = ms_since(t_ex) - normals_ms - clean_ms;        // (count, write and the copies to the host, as before)
+    char extras[256] = "";
+    if (cleaned)
+        snprintf(extras, sizeof extras, ", cleanup: %u of %u components kept (largest %u triangles, min %g %%), %.2f ms", info.kept_components,
+                 info.n_components, info.largest, min_bp / 100.0, clean_ms);
+    if (want_normals) snprintf(extras + strlen(extras), sizeof extras - strlen(extras), ", normals %.2f ms", normals_ms);
 
     std::error_code ec;
     const auto parent = std::filesystem::path(path).parent_path();
     if (!parent.empty()) std::filesystem::create_directories(parent, ec);
     std::string err;
-    if (!gsply::write_mesh_ply(path, nv, xyz.data(), rgb.data(), nt, tri.data(), &err)) { logf_("mesh @%d: %s", step, err.c_str()); return false; }
+    if (!gsply::write_mesh_ply(path, nv, xyz.data(), rgb.data(), nt, tri.data(), &err, want_normals ? nrm.data() : nullptr)) { logf_("mesh @%d: %s", step, err.c_str()); return false; }
     logf_("mesh @%d: %u vertices, %u triangles, grid %dx%dx%d, voxel %.9g, bounds %.9g,%.9g,%.9g,%.9g,%.9g,%.9g, trunc %.9g, %d views; render+depth %.2f ms, "
-          "fusion %.2f ms, extraction %.2f ms -> %s", step, nv, nt, dims[0], dims[1], dims[2], (double)voxel, (double)lo[0], (double)lo[1], (double)lo[2],
+          "fusion %.2f ms, extraction %.2f ms%s -> %s", step, nv, nt, dims[0], dims[1], dims[2], (double)voxel, (double)lo[0], (double)lo[1], (double)lo[2],
           (double)(lo[0] + (dims[0] - 1) * voxel), (double)(lo[1] + (dims[1] - 1) * voxel), (double)(lo[2] + (dims[2] - 1) * voxel), (double)trunc,
-          (int)which.size(), render_ms, fuse_ms, extract_ms, path.c_str());
+          (int)which.size(), render_ms, fuse_ms, extract_ms, extras, path.c_str());
     return true;
 }

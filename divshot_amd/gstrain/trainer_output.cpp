@@ -36,6 +36,10 @@ void GaussianTrainerScene::Impl::report_config() const {
         logf_("config: meshResolution %d: a save of the finished model and export_mesh() also write <modelPath>_<it>_mesh.ply — the training cameras' "
               "depth maps fused into a TSDF grid of %d voxels along the longest side, marching tetrahedra, all on the device", res,
               std::min(1024, std::max(16, res)));
+    if (mesh_min_bp() > 0 || mesh_normals())
+        logf_("config: mesh clean-up: components with fewer than %g %% of the largest one's triangles are dropped%s, on the device, before the mesh "
+              "is written%s", mesh_min_bp() / 100.0, mesh_min_bp() > 0 ? "" : " (off)",
+              mesh_normals() ? "; vertex normals nx ny nz from the TSDF gradient" : "");
     if (const int P = importance_prune(); P > 0) {
         const int asked = env_int("DVS_IMPORTANCE_PRUNE", cfg.importancePrune);
         if (asked > 90) logf_("config: importancePrune %d clamped to 90", asked);

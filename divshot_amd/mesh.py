@@ -4,11 +4,13 @@ torch supplies device buffers and the HIP stream; all compute runs in libdvsrast
     depth, alpha = depth_maps(rasterizer)              # of the rasterizer's last forward / forward_views
     grid = TsdfGrid((x0, y0, z0), voxel, (nx, ny, nz)); grid.integrate(cams, depth, alpha, rgb, trunc=4 * voxel)
     xyz, rgb, tri = grid.extract()                      # numpy: float32 [nv,3], uint8 [nv,3], uint32 [nt,3]
+    xyz, rgb, tri, nrm = grid.extract(normals=True)     # ... and the TSDF gradient's unit normals, float32 [nv,3]
+    xyz, rgb, tri, nrm, info = clean_mesh(xyz, rgb, tri, min_bp=100, normals=nrm)   # components below 1 % of the largest dropped
 """
 import ctypes as C
 import numpy as np
 import torch
-from ._lib import lib, Camera, Opts, TsdfGridDesc, check, DvsError, write_mesh_ply  # noqa: F401
+from ._lib import lib, Camera, Opts, TsdfGridDesc, MeshCleanInfo, check, DvsError, write_mesh_ply  # noqa: F401
 from .raster import _stream_ptr
 
 
@@ -77,8 +79,9 @@ class TsdfGrid:
             check(lib.dvs_tsdf_integrate(_stream_ptr(), C.byref(self.desc), cam_arr, V, depth.data_ptr(), alpha.data_ptr(), rgb.data_ptr(),
                                          mask_arr, W, H, float(trunc)), "dvs_tsdf_integrate")
 
-    def extract(self):
-        """marching tetrahedra over the grid -> (xyz float32 [nv,3], rgb uint8 [nv,3], tri uint32 [nt,3]) as numpy"""
+    def extract(self, normals=False):
+        """marching tetrahedra over the grid -> (xyz float32 [nv,3], rgb uint8 [nv,3], tri uint32 [nt,3]) as numpy; with normals=True a
+        fourth array, the unit normals float32 [nv,3] of dvs_mesh_extract_normals"""
         dims = (C.c_int32 * 3)(*self.dims)
         scratch = torch.empty(lib.dvs_mesh_scratch_bytes(dims) + 256, dtype=torch.uint8, device=self.tdev)
         sp = (scratch.data_ptr() + 255) & ~255
@@ -89,5 +92,67 @@ class TsdfGrid:
             rgb = torch.empty((max(nv.value, 1), 3), dtype=torch.uint8, device=self.tdev)
             tri = torch.empty((max(nt.value, 1), 3), dtype=torch.int32, device=self.tdev)
             check(lib.dvs_mesh_extract_write(_stream_ptr(), C.byref(self.desc), sp, xyz.data_ptr(), rgb.data_ptr(), tri.data_ptr()), "dvs_mesh_extract_write")
+            if normals:
+                nrm = torch.empty((max(nv.value, 1), 3), dtype=torch.float32, device=self.tdev)
+                check(lib.dvs_mesh_extract_normals(_stream_ptr(), C.byref(self.desc), sp, nrm.data_ptr()), "dvs_mesh_extract_normals")
             torch.cuda.synchronize()
-        return xyz[:nv.value].cpu().numpy(), rgb[:nv.value].cpu().numpy(), tri[:nt.value].cpu().numpy().view(np.uint32)
+        out = (xyz[:nv.value].cpu().numpy(), rgb[:nv.value].cpu().numpy(), tri[:nt.value].cpu().numpy().view(np.uint32))
+        return out + (nrm[:nv.value].cpu().numpy(),) if normals else out
+
+
+def _tri_to_device(tri, device):
+    tri = np.ascontiguousarray(tri, np.uint32).reshape(-1, 3)
+    d = torch.empty((max(len(tri), 1), 3), dtype=torch.int32, device=device)
+    if len(tri):
+        d[:len(tri)].copy_(torch.from_numpy(tri.view(np.int32)))
+    return tri, d
+
+
+def mesh_components(tri, n_vertices, device=0):
+    """dvs_mesh_components of a numpy index buffer uint32 [nt,3] -> (label uint32 [n_vertices]: the smallest vertex index of each
+    vertex's component, n_bad: the triangles ignored for an index >= n_vertices)"""
+    tdev = torch.device("cuda", device)
+    n_vertices = int(n_vertices)
+    tri, d_tri = _tri_to_device(tri, tdev)
+    label = torch.empty(max(n_vertices, 1), dtype=torch.int32, device=tdev)
+    bad = torch.zeros(1, dtype=torch.int32, device=tdev)
+    with torch.cuda.device(tdev):
+        check(lib.dvs_mesh_components(_stream_ptr(), n_vertices, d_tri.data_ptr(), len(tri), label.data_ptr(), bad.data_ptr()), "dvs_mesh_components")
+        torch.cuda.synchronize()
+    return label[:n_vertices].cpu().numpy().view(np.uint32), int(bad.cpu().numpy().view(np.uint32)[0])
+
+
+def clean_mesh(xyz, rgb, tri, min_bp, normals=None, device=0):
+    """dvs_mesh_clean_count / _write on numpy arrays: the components with fewer than min_bp / 10000 of the largest one's triangles are
+    dropped (min_bp in 1/100 percent, 0..10000) -> (xyz, rgb, tri, normals or None, info) with info a dict of dvs_mesh_clean_info"""
+    tdev = torch.device("cuda", device)
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    rgb = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    nv = len(xyz)
+    if len(rgb) != nv or (normals is not None and len(normals) != nv):
+        raise DvsError("clean_mesh: xyz, rgb and normals differ in length")
+    tri, d_tri = _tri_to_device(tri, tdev)
+
+    def up(a, dtype):
+        d = torch.empty((max(nv, 1), 3), dtype=dtype, device=tdev)
+        if nv:
+            d[:nv].copy_(torch.from_numpy(a))
+        return d
+    d_xyz, d_rgb = up(xyz, torch.float32), up(rgb, torch.uint8)
+    d_nrm = None if normals is None else up(np.ascontiguousarray(normals, np.float32).reshape(-1, 3), torch.float32)
+    scratch = torch.empty(lib.dvs_mesh_clean_scratch_bytes(nv, len(tri)) + 256, dtype=torch.uint8, device=tdev)
+    sp = (scratch.data_ptr() + 255) & ~255
+    info = MeshCleanInfo()
+    with torch.cuda.device(tdev):
+        check(lib.dvs_mesh_clean_count(_stream_ptr(), nv, d_tri.data_ptr(), len(tri), int(min_bp), sp, C.byref(info)), "dvs_mesh_clean_count")
+        kv, kt = info.kept_vertices, info.kept_triangles
+        o_xyz = torch.empty((max(kv, 1), 3), dtype=torch.float32, device=tdev)
+        o_rgb = torch.empty((max(kv, 1), 3), dtype=torch.uint8, device=tdev)
+        o_nrm = None if d_nrm is None else torch.empty((max(kv, 1), 3), dtype=torch.float32, device=tdev)
+        o_tri = torch.empty((max(kt, 1), 3), dtype=torch.int32, device=tdev)
+        check(lib.dvs_mesh_clean_write(_stream_ptr(), nv, d_xyz.data_ptr(), d_rgb.data_ptr(), None if d_nrm is None else d_nrm.data_ptr(), d_tri.data_ptr(),
+                                       len(tri), sp, o_xyz.data_ptr(), o_rgb.data_ptr(), None if o_nrm is None else o_nrm.data_ptr(), o_tri.data_ptr()),
+              "dvs_mesh_clean_write")
+        torch.cuda.synchronize()
+    return (o_xyz[:kv].cpu().numpy(), o_rgb[:kv].cpu().numpy(), o_tri[:kt].cpu().numpy().view(np.uint32),
+            None if o_nrm is None else o_nrm[:kv].cpu().numpy(), {name: getattr(info, name) for name, _ in MeshCleanInfo._fields_})

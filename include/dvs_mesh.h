@@ -1,10 +1,12 @@
 /*
  * dvs_mesh.h — C-ABI of surface extraction from a trained model: truncated-signed-distance (TSDF) fusion of rendered depth maps
- * (dvs_raster_depth_views, dvs_raster.h) into a voxel grid, and marching tetrahedra over that grid into a welded, indexed mesh.
+ * (dvs_raster_depth_views, dvs_raster.h) into a voxel grid, marching tetrahedra over that grid into a welded, indexed mesh, and what
+ * is done to that mesh before it is written: vertex normals from the grid, removal of small connected components.
  *
  * Conventions of dvs_train.h: `stream` is a hipStream_t, arrays are DEVICE pointers unless marked HOST, calls are asynchronous unless
- * they say otherwise and return a DVS_* status (dvs_raster.h); the current HIP device is the caller's. No atomics anywhere and no
- * dependence on the launch shape: two runs on the same inputs return identical bytes. fp32 arithmetic without contraction.
+ * they say otherwise and return a DVS_* status (dvs_raster.h); the current HIP device is the caller's. The only atomics are integer
+ * atomics whose result does not depend on order (minimum, maximum, sum — in the component passes below) and there is no dependence
+ * on the launch shape: two runs on the same inputs still return identical bytes. fp32 arithmetic without contraction.
  */
 #ifndef DVS_MESH_H
 #define DVS_MESH_H
@@ -75,6 +77,57 @@ int dvs_tsdf_integrate(void* stream, const dvs_tsdf_grid* grid, const dvs_camera
 size_t dvs_mesh_scratch_bytes(const int32_t dims[3]);
 int dvs_mesh_extract_count(void* stream, const dvs_tsdf_grid* grid, void* scratch, uint32_t* n_vertices, uint32_t* n_triangles);
 int dvs_mesh_extract_write(void* stream, const dvs_tsdf_grid* grid, const void* scratch, float* xyz, uint8_t* rgb, uint32_t* tri);
+
+/* Vertex normals from the grid, for the vertices of dvs_mesh_extract_write in the same order: normals [n_vertices][3], from the scratch
+ * dvs_mesh_extract_count filled and the unchanged grid. The gradient g(q) of a voxel q has, per axis with unit step e, the component
+ *   (tsdf(q + e) - tsdf(q - e)) / 2   when both neighbours count,
+ *   tsdf(q + e) - tsdf(q)  or  tsdf(q) - tsdf(q - e)   when only q + e / only q - e counts,
+ *   0   when neither does,
+ * where a neighbour counts iff it is inside the grid and has weight > 0. The vertex on the edge from p to p + d, at the extraction's
+ * own t = a / (a - b), gets n = (1 - t) * g(p) + t * g(p + d) (two products, one sum per component), divided by its length
+ * sqrt((n.x * n.x + n.y * n.y) + n.z * n.z) — or (0, 0, 0) when that sum of squares is < 1e-30. tsdf is positive outside, so n points
+ * outwards, to the side the triangles' winding faces. One thread per voxel over its vertices, as the extraction writes them: every
+ * normal has one writer, no atomics. */
+int dvs_mesh_extract_normals(void* stream, const dvs_tsdf_grid* grid, const void* scratch /*of dvs_mesh_extract_count*/, float* normals);
+
+/* Connected components of an indexed triangle list: two vertices are connected when a triangle uses both. label [n_vertices] receives
+ * for every vertex the SMALLEST vertex index of its component (a vertex no triangle uses is its own component) — a function of the mesh
+ * alone, identical from run to run. A triangle with an index >= n_vertices is ignored (never dereferenced) and counted in *n_bad
+ * (DEVICE, one word, zeroed by the call; may be NULL); an index repeated inside a triangle is legal; n_triangles == 0 (label[v] = v)
+ * and n_vertices == 0 (every triangle is bad) are legal.
+ * Hook-and-compress union-find with label as the parent array: parent[v] = v; one thread per triangle unions (v0, v1) and (v0, v2) by
+ * linking the larger root under the smaller with an atomic minimum, retrying with the displaced link when it loses a race; a last
+ * launch follows every vertex to its root. parent[x] <= x throughout, so every walk goes strictly downwards and has at most n_vertices
+ * steps, and a retry's larger root is smaller than the one before: every device loop is capped by n_vertices. A loop that reaches its
+ * cap (possible only on corrupted memory) sets a device error word; the next dvs_mesh_clean_count on that device returns
+ * DVS_ERR_STATE for it, and clears it. No kernel waits for another workgroup. */
+int dvs_mesh_components(void* stream, uint32_t n_vertices, const uint32_t* tri, uint32_t n_triangles, uint32_t* label /*[n_vertices]*/,
+                        uint32_t* n_bad /*device, 1 word, may be NULL*/);
+
+/* Clean-up of an extracted mesh: the components that are small next to the largest are dropped, with their vertices.
+ * A component with c triangles is kept iff c > 0 and (uint64) c * 10000 >= (uint64) largest * min_bp — min_bp in 1/100 of a percent,
+ * 0..10000 (DVS_ERR_INVALID above): 0 keeps everything that has a triangle, 10000 only the components that tie for largest. Triangle
+ * counts and `largest` are integer sums / maxima at the component's root. Kept triangles keep their order; kept vertices are the
+ * vertices a kept triangle uses, in their old order, so vertices without a triangle disappear; indices are remapped through an
+ * exclusive scan; xyz, rgb and normals move unchanged, bit for bit.
+ * dvs_mesh_clean_count runs the component, counting, marking and scan passes into `scratch` (dvs_mesh_clean_scratch_bytes bytes,
+ * 256-byte aligned, no initialisation) and synchronises the stream ONCE to fill *info; DVS_ERR_STATE when a capped device loop ran
+ * out (see dvs_mesh_components). dvs_mesh_clean_write then writes out_xyz / out_rgb / out_normals [kept_vertices][3] and out_tri
+ * [kept_triangles][3] from the same scratch and the unchanged inputs; normals and out_normals are both given or both NULL. */
+typedef struct dvs_mesh_clean_info {
+    uint32_t n_components;      /* components with at least one triangle */
+    uint32_t largest;           /* triangles of the biggest */
+    uint32_t kept_components;
+    uint32_t kept_vertices;
+    uint32_t kept_triangles;
+    uint32_t n_bad;             /* triangles ignored for an index >= n_vertices */
+} dvs_mesh_clean_info;
+size_t dvs_mesh_clean_scratch_bytes(uint32_t n_vertices, uint32_t n_triangles);
+int dvs_mesh_clean_count(void* stream, uint32_t n_vertices, const uint32_t* tri, uint32_t n_triangles, uint32_t min_bp, void* scratch,
+                         dvs_mesh_clean_info* info /*HOST*/);
+int dvs_mesh_clean_write(void* stream, uint32_t n_vertices, const float* xyz, const uint8_t* rgb, const float* normals /*or NULL*/,
+                         const uint32_t* tri, uint32_t n_triangles, const void* scratch, float* out_xyz, uint8_t* out_rgb,
+                         float* out_normals /*or NULL*/, uint32_t* out_tri);
 
 #ifdef __cplusplus
 }

@@ -122,6 +122,10 @@ public:
     void trainStep();                                 // one iteration: sample camera -> raster fwd -> loss -> raster bwd -> Adam
     void saveGaussianModel();                         // PLY at modelPath (external/tinygsplat/tiny_gsplat.cpp:168-241 layout)
     void exportMesh(const std::string& path);         // <path> ("": <modelPath>_<it>_mesh.ply, only when meshResolution > 0): INTEGRATION.md "Mesh export"
+    // mesh clean-up (extension of this build; INTEGRATION.md "Mesh export"): components with fewer than minComponentPercent % (0..100, two
+    // decimals count; 0 = off) of the largest component's triangles are dropped before the mesh is written, and `normals` adds the
+    // TSDF gradient's unit normals nx ny nz to the file. Wins over DVS_MESH_MIN_COMPONENT / DVS_MESH_NORMALS once called.
+    void setMeshCleanup(float minComponentPercent, bool normals);
     void exportSparsePointCloud(const std::string& path);   // editor.cpp:3535 — writes the splat centres as an ASCII PLY point cloud
     void saveCameraDatas(const std::string& path);          // editor.cpp:3512 — one line per camera: centre, view matrix, intrinsics
     bool isTrain() const;
