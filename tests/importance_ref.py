@@ -39,3 +39,15 @@ def importance(splat2d, ranges, sorted_splat, n_contrib, W, H, n, view, mask=Non
                 excl[i] = True
             T = np.where(take, T * (1.0 - a), T)
     return wsum, wmax, hits, excl
+
+
+def oracle_records(mean2d, conic_opacity):
+    """the record layout importance() reads, from the CPU oracle's own forward state (oracle.get("mean2d"), get("conic_opacity")): one
+    [n,16] row per splat with the pixel centre at S2D_X / S2D_Y, the conic's (a, b, c) at S2D_CONIC .. + 2 and the opacity the composite
+    multiplies exp(power) by at S2D_OPACITY -> float64 [n,16]; the list values of a single oracle view index these rows (view = 0)"""
+    n = mean2d.shape[0]
+    rec = np.zeros((n, 16))
+    rec[:, S2D_X], rec[:, S2D_Y] = mean2d[:, 0], mean2d[:, 1]
+    rec[:, S2D_CONIC:S2D_CONIC + 3] = conic_opacity[:, :3]
+    rec[:, S2D_OPACITY] = conic_opacity[:, 3]
+    return rec

@@ -13,8 +13,9 @@ this build's plugin defines (divshot_amd/gstrain/gstrain.cpp trainStep) from ind
 
 Options of the step, each off by default (the host flags of gstrain/trainer_step.cpp plan_step / loss_of_view and gstrain.cpp trainStep): start_step (a resume
 through --load_itr), progressive (SH degree min(sh, step // 1000)), antialias, pack_u8 (8-bit training views), mask (the synthetic
-inscribed-ellipse mask on the photometric gradient), reset_alpha_every (the opacity reset inside the step) and the light prune
-(prune_decisions / apply_prune).
+inscribed-ellipse mask on the photometric gradient), reset_alpha_every (the opacity reset inside the step), train_cams (the training
+cameras of a hold-out), the light prune (prune_decisions / apply_prune) and the importance prune (importance_scores /
+importance_decisions).
 
 dtype float32 mirrors the arithmetic the plugin performs; float64 is the ground truth of the same recurrences. The parity test compares
 the plugin with the float64 trajectory on every element where the float32 restatement itself stays within tolerance of it: Adam with
@@ -120,13 +121,16 @@ def scene_extent(cams):
 class TrainStepRef:
     def __init__(self, oracle_cls, cams, targets, init, sh_degree, num_iters, dtype=np.float32, views_per_step=1, world=1, lr=None,
                  ssim_weight=0.0, mcmc_reg=None, start_step=0, progressive=False, antialias=False, pack_u8=False, mask=False,
-                 reset_alpha_every=0):
+                 reset_alpha_every=0, train_cams=None):
         """ssim_weight: w of L = (1 - w) mean|x - y| + w (1 - mean SSIM) (--ssim, main.cpp:24: 0.2; 0 = L1 only).
         mcmc_reg: (opacity_reg, scale_reg) of densifyStrategy 1 (gstrain/trainer_step.cpp finish_range: 0.01, 0.01), added to the summed gradients once per step.
         start_step: a resume through --load_itr — the step number (Adam bias correction, position-rate schedule, SH degree) starts there,
         the moments at zero and the camera stream at its seed. progressive: --progressTrain 1. antialias: --mipAntiliased 1.
         pack_u8: --packLevel 1, the targets go through 8 bits. mask: --useMask 1, the photometric gradient (not the reported loss) is
-        multiplied by ellipse_mask. reset_alpha_every: --resetAlphaEvery, applied after the Adam step of iterations it % r == 0."""
+        multiplied by ellipse_mask. reset_alpha_every: --resetAlphaEvery, applied after the Adam step of iterations it % r == 0.
+        train_cams: --evalHoldout h, the indices i with i % h != 0 in order — a draw is train_cams[xorshift % len(train_cams)] (gstrain/
+        trainer.hpp draw_cameras: held-out cameras are never trained on); None = every camera, cams[xorshift % len(cams)]. The extent
+        stays that of ALL cameras (trainer_load.cpp finish_load)."""
         self.w_ssim, self.mcmc_reg = float(ssim_weight), mcmc_reg
         self.dt = np.dtype(dtype)
         self.orc = oracle_cls(self.dt)
@@ -143,7 +147,8 @@ class TrainStepRef:
         self.lr = dict(LR, **(lr or {}))
         self.step = self.start = int(start_step)
         n = self.P["pos"].shape[0]
-        self.order = camera_stream(len(cams), 4096 * views_per_step * world)
+        self.train_cams = list(range(len(cams))) if train_cams is None else [int(c) for c in train_cams]
+        self.order = [self.train_cams[d] for d in camera_stream(len(self.train_cams), 4096 * views_per_step * world)]
         self.grad_accum, self.denom, self.max_radii = np.zeros(n, self.dt), np.zeros(n, self.dt), np.zeros(n, np.int32)
         self.grad_accum_mean2d = np.zeros(n, self.dt)         # the statistic of --absgrad 0
         self.losses = []
@@ -247,6 +252,27 @@ class TrainStepRef:
         self.grad_accum, self.denom, self.max_radii = (np.zeros(int(keep.sum()), a.dtype) for a in (self.grad_accum, self.denom, self.max_radii))
         self.grad_accum_mean2d = np.zeros(int(keep.sum()), self.dt)
 
+    # ---- importance prune of gstrain/trainer_refine.cpp prune_importance() (--importancePrune P, after the light prune) ---------------------------------
+    def importance_scores(self, cam_indices, mask=False):
+        """-> (score [n] float64, excluded [n] bool): the blend weight alpha T of every splat summed over the pixels of the listed cameras
+        (include/dvs_raster.h dvs_raster_importance_views), from the current parameters: per camera the oracle forward at the model's
+        FULL SH degree and the run's anti-alias setting (the evaluation's options, whatever degree the step trains at), its own state
+        (mean2d, conic_opacity, vals, ranges, n_contrib) through tests/importance_ref.py; mask: ellipse_mask(W, H), a pixel outside it
+        contributes nothing. excluded: the OR over the cameras of importance_ref's threshold bands. The product sums rintf(w 2^24) in a
+        uint64; this stays in float64."""
+        import importance_ref as IR
+        n = self.P["pos"].shape[0]
+        score, excluded = np.zeros(n), np.zeros(n, bool)
+        for ci in cam_indices:
+            cam = self.cams[ci]
+            self.orc.forward(self.P, cam, sh_degree=self.deg, antialias=self.antialias)
+            rec = IR.oracle_records(self.orc.get("mean2d"), self.orc.get("conic_opacity"))
+            m = ellipse_mask(cam.width, cam.height) if mask else None
+            wsum, _, _, excl = IR.importance(rec, self.orc.get("ranges"), self.orc.get("vals"), self.orc.get("n_contrib"), cam.width, cam.height, n, 0, mask=m)
+            score += wsum
+            excluded |= excl
+        return score, excluded
+
     # ---- ADC refinement decision of gstrain/trainer_refine.cpp densify() / densify.hip d_action --------------------------------------------------------
     def adc_actions(self, grow_grad2d, min_opacity=0.005, stat="absgrad", max_world_scale=0.0, max_screen_radius=0):
         """0 keep, 1 clone, 2 split, 3 prune — and the margin of each decision (relative distance to its nearest threshold).
@@ -270,3 +296,23 @@ class TrainStepRef:
             act = np.where(self.max_radii > max_screen_radius, 3, act)
             margin = np.minimum(margin, np.abs(self.max_radii - (max_screen_radius + 0.5)) / (max_screen_radius + 0.5))
         return act, margin
+
+
+def importance_decisions(scores, excluded, keep):
+    """-> (prune [n] bool, margin [n]): the n - keep smallest go, in the total order (score, then larger index first) that include/
+    dvs_train.h documents for dvs_importance_plan; margin = |score - cut| / max(cut, tiny), cut = the score of the last kept splat (the
+    smallest score that survives) — 0 for an excluded splat, and for a zero-score splat when the cut is itself 0 (ties decided by the
+    index alone: whether a splat scores exactly 0 is not something a restatement in another precision can promise)."""
+    s = np.asarray(scores, np.float64)
+    n = s.shape[0]
+    keep = min(int(keep), n)
+    order = np.lexsort((-np.arange(n), s))                  # ascending score; among equals the larger index first
+    prune = np.zeros(n, bool)
+    prune[order[:n - keep]] = True
+    cut = s[order[n - keep]] if keep > 0 else np.inf
+    with np.errstate(over="ignore"):                        # (a cut of 0: every positive score is infinitely far from it)
+        margin = np.abs(s - cut) / max(cut, np.finfo(np.float64).tiny)
+    margin[np.asarray(excluded, bool)] = 0.0
+    if cut == 0:
+        margin[s == 0] = 0.0
+    return prune, margin
