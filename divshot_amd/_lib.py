@@ -46,6 +46,10 @@ class SplatGrads(C.Structure):
                 ("scale", C.c_void_p), ("rot", C.c_void_p), ("absgrad2d", C.c_void_p), ("mean2d", C.c_void_p), ("dcolor", C.c_void_p)]
 
 
+class Sky(C.Structure):
+    _fields_ = [("tex", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32)]
+
+
 class DensifyParams(C.Structure):
     _fields_ = [("grad_threshold", C.c_float), ("scale_threshold", C.c_float), ("min_opacity", C.c_float), ("max_world_scale", C.c_float),
                 ("max_screen_radius", C.c_int32), ("cap_max", C.c_int32), ("seed", C.c_uint32), ("shn_layout", C.c_int32), ("revised_opacity", C.c_int32)]
@@ -81,6 +85,9 @@ _PROTOS = {
     "dvs_raster_forward_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Splats), C.POINTER(Camera), C.c_int, C.POINTER(Opts), C.c_void_p]),
     "dvs_raster_depth_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p]),
     "dvs_raster_importance_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Opts), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_sky_forward_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.c_int, C.POINTER(Sky), C.c_void_p, C.c_void_p]),
+    "dvs_sky_backward_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.c_int, C.POINTER(Opts), C.POINTER(Sky), C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "dvs_raster_forward_cancel_prepared": (C.c_int, [C.c_void_p]),
     "dvs_raster_forward_views_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Splats), C.POINTER(Camera), C.c_int, C.POINTER(Opts), C.c_int64, C.c_int64]),
     "dvs_raster_backward_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Splats), C.POINTER(Camera), C.c_int, C.POINTER(Opts),

@@ -172,6 +172,7 @@ struct Forward {
 struct Backward {
     Buf g_rows;
     Buf dcolor;                          // [views, n, 3] per-view colour gradients of a batched A9 when the caller gives no buffer
+    Buf sky_rgb;                         // [views, 3, H, W] the sky lookup of dvs_sky_backward_views when the caller gives none
     int variant = DVS_BWD_TR;            // which A8 kernel (dvs_set_backward_variant; env DVS_BWD_VARIANT at create): the measured winner
     bool keep_rows = false;              // parity tests: leave the A8 rows in place after the backward
     bool rows_clean = false;             // gradient rows are all-zero (k_preprocess_bwd re-zeroes what it reads)
@@ -637,6 +638,82 @@ int dvs_raster_importance_views(dvs_ctx* c, void* stream, const dvs_opts* opts, 
     HIPCHECK(dvs_launch_importance_views((hipStream_t)stream, s.width, s.height, s.tiles_x, s.tiles_y, c->fwd.n_views, s.n, s.ranges, s.sorted_splat,
                                          s.splat2d, s.n_contrib, masks, score_sum, score_max, hits));
     return DVS_OK;
+}
+
+// The sky texture behind the splats (sky.hip): separate passes over the saved state, before and after the composite backward; the composite
+// kernels run with bg = 0 and know nothing of it.
+static int check_dL(const float* dL_drgb, const char* who);
+// What both entry points check first; minv [n_views][9] receives, per view, the inverse of rows 0, 1, 3 of proj's 3x3 part (fp64, then rounded).
+static int check_sky(dvs_ctx* c, const dvs_camera* cams, int n_views, const dvs_sky* sky, const char* who, float* minv) {
+    if (!c || !cams || !sky || !sky->tex) return fail(DVS_ERR_INVALID, who, "null argument");
+    if ((uintptr_t)sky->tex & 15u) return fail(DVS_ERR_INVALID, who, "the texture must be 16-byte aligned");
+    if (sky->height < 2 || sky->width != 2 * sky->height) return fail(DVS_ERR_INVALID, who, "the texture must have height >= 2 and width == 2 * height");
+    if (n_views < 1 || n_views > DVS_MAX_VIEWS) return fail(DVS_ERR_INVALID, who, "bad n_views");
+    for (int v = 0; v < n_views; ++v) {
+        if (cams[v].bg[0] != 0.f || cams[v].bg[1] != 0.f || cams[v].bg[2] != 0.f)
+            return fail(DVS_ERR_INVALID, who, "cams[v].bg must be zero: the sky texture is the background (never both)");
+        const int rows[3] = {0, 1, 3};
+        double m[3][3], inv[3][3];
+        for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) m[i][k] = (double)cams[v].proj[k * 4 + rows[i]];
+        const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                           m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+        if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return fail(DVS_ERR_INVALID, who, "cams[v].proj is singular: no ray per pixel");
+        for (int i = 0; i < 3; ++i)
+            for (int k = 0; k < 3; ++k) {               // inv[i][k] = cofactor(k, i) / det
+                const int r0 = (k + 1) % 3, r1 = (k + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
+                inv[i][k] = (m[r0][c0] * m[r1][c1] - m[r0][c1] * m[r1][c0]) / det;
+            }
+        for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) minv[9 * v + 3 * i + k] = (float)inv[i][k];
+    }
+    if (!c->fwd.have || n_views != c->fwd.n_views)
+        return fail(DVS_ERR_STATE, who, "no matching forward on this context (valid after dvs_raster_forward / _views until the next forward)");
+    for (int v = 0; v < n_views; ++v)
+        if (c->fwd.st.width != cams[v].width || c->fwd.st.height != cams[v].height)
+            return fail(DVS_ERR_STATE, who, "a camera's image size is not that of the last forward on this context");
+    return DVS_OK;
+}
+int dvs_sky_forward_views(dvs_ctx* c, void* stream, const dvs_camera* cams, int n_views, const dvs_sky* sky, float* out_rgb, float* sky_rgb) {
+    const char* const who = "dvs_sky_forward_views";
+    float minv[DVS_MAX_VIEWS * 9];
+    if (!out_rgb) return fail(DVS_ERR_INVALID, who, "null argument");
+    if (((uintptr_t)out_rgb | (uintptr_t)sky_rgb) & 15u) return fail(DVS_ERR_INVALID, who, "images must be 16-byte aligned");
+    TRY(check_sky(c, cams, n_views, sky, who, minv));
+    HIPCHECK(hipSetDevice(c->device));
+    const dvs_fwd_state& s = c->fwd.st;
+    StageScope tm(c, (hipStream_t)stream, /*append=*/true);
+    tm.begin();
+    HIPCHECK(dvs_launch_sky_forward(tm.st, s.width, s.height, n_views, minv, sky->tex, sky->width, sky->height, s.final_T, out_rgb, sky_rgb));
+    tm.stage("sky_fwd");
+    return tm.finish();
+}
+int dvs_sky_backward_views(dvs_ctx* c, void* stream, const dvs_camera* cams, int n_views, const dvs_opts* opts, const dvs_sky* sky,
+                           const float* dL_drgb, const float* sky_rgb, float* g_tex) {
+    const char* const who = "dvs_sky_backward_views";
+    float minv[DVS_MAX_VIEWS * 9];
+    if (!opts || !g_tex) return fail(DVS_ERR_INVALID, who, "null argument");
+    TRY(check_dL(dL_drgb, who));
+    if (((uintptr_t)sky_rgb | (uintptr_t)g_tex) & 15u) return fail(DVS_ERR_INVALID, who, "sky_rgb and g_tex must be 16-byte aligned");
+    if (opts->grad_mode != DVS_GRAD_TRUE && opts->grad_mode != DVS_GRAD_LINEAGE) return fail(DVS_ERR_INVALID, who, "bad grad_mode");
+    TRY(check_sky(c, cams, n_views, sky, who, minv));
+    if (!c->bwd.rows_pending || c->bwd.proj_next != 0)
+        return fail(DVS_ERR_STATE, who, "no composite backward pending on this context (call between dvs_raster_backward_composite and the projection)");
+    HIPCHECK(hipSetDevice(c->device));
+    const dvs_fwd_state& s = c->fwd.st;
+    StageScope tm(c, (hipStream_t)stream, /*append=*/true);
+    tm.begin();
+    if (!sky_rgb) {                                     // the caller kept no lookup: redo it into the context's own buffer
+        TRY(c->bwd.sky_rgb.ensure((size_t)n_views * 3 * s.width * s.height * sizeof(float)));
+        HIPCHECK(dvs_launch_sky_forward(tm.st, s.width, s.height, n_views, minv, sky->tex, sky->width, sky->height, s.final_T, nullptr,
+                                        c->bwd.sky_rgb.as<float>()));
+        sky_rgb = c->bwd.sky_rgb.as<float>();
+        tm.stage("sky_lookup");
+    }
+    HIPCHECK(dvs_launch_sky_backward_tex(tm.st, s.width, s.height, n_views, minv, sky->width, sky->height, s.final_T, dL_drgb, g_tex));
+    tm.stage("sky_bwd_tex");
+    HIPCHECK(dvs_launch_sky_backward_rows(tm.st, s.width, s.height, s.tiles_x, s.tiles_y, n_views, s.n, s.ranges, s.sorted_splat, s.splat2d, s.final_T,
+                                          s.n_contrib, dL_drgb, sky_rgb, c->bwd.g_rows.as<float>(), opts->grad_mode));
+    tm.stage("sky_bwd_rows");
+    return tm.finish();
 }
 
 // A8: zero the 48-B rows if needed, then the alpha-composite backward into them (all views of the last forward in one launch)

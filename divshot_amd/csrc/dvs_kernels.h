@@ -139,6 +139,18 @@ hipError_t dvs_launch_depth_views(hipStream_t st, int W, int H, int tiles_x, int
 hipError_t dvs_launch_importance_views(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, int n, const uint32_t* ranges /*canonical (start, end)*/,
                                        const uint32_t* sorted_splat, const float* splat2d, const uint32_t* n_contrib, const float* const* masks,
                                        uint64_t* score_sum, uint32_t* score_max, uint32_t* hits);
+// sky.hip — the sky texture behind the splats, all n_views views in one launch each. minv = HOST [n_views][9]: per view the inverse of rows
+// 0, 1, 3 of proj's 3x3 part, row-major (world ray of a pixel = minv (ndc_x, ndc_y, 1)); tex = DEVICE [Hs][Ws][3].
+// forward: out_rgb += final_T s in place (null: skipped), s -> sky_rgb (null: skipped); both are [n_views][3][H][W]
+hipError_t dvs_launch_sky_forward(hipStream_t st, int W, int H, int n_views, const float* minv, const float* tex, int Ws, int Hs, const float* final_T,
+                                  float* out_rgb, float* sky_rgb);
+// g_tex [Hs][Ws][3] += final_T dL_dout times the bilinear weights
+hipError_t dvs_launch_sky_backward_tex(hipStream_t st, int W, int H, int n_views, const float* minv, int Ws, int Hs, const float* final_T,
+                                       const float* dL_dout, float* g_tex);
+// grad_rows [n_views][n][12] columns 0..5 += the gradient of sum_p final_T (sky_rgb . dL_dout) through final_T
+hipError_t dvs_launch_sky_backward_rows(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, int n, const uint32_t* ranges /*canonical (start, end)*/,
+                                        const uint32_t* sorted_splat, const float* splat2d, const float* final_T, const uint32_t* n_contrib,
+                                        const float* dL_dout, const float* sky_rgb, float* grad_rows, int grad_mode);
 // A8 kernel variants (dvs_set_backward_variant): same inputs, same 48-B row contract, results equal to fp32 roundoff
 enum { DVS_BWD_BLOCKS = 0 /*per-4x4-block lists, four cursors per wave, 12-value group reduction per step (round 2): kept in the release library as
        the independent-summation-order cross-check of the parity tests*/, DVS_BWD_REDUCE = 1 /*per-quadrant masks, wave-wide reduction tree per visit

@@ -1,0 +1,293 @@
+// sky.hip — the sky model: a learned equirectangular texture behind the splats (dvs_sky_forward_views / dvs_sky_backward_views), for gfx950.
+//
+// The composite kernels are untouched: with cam.bg = 0 they leave C(p) and final_T(p), and the passes below add what a background that
+// varies per pixel needs, out(p) = C(p) + final_T(p) s(p), from the state the forward saved (like depth.hip and importance.hip).
+//
+// The ray of pixel (x, y) (centre = the integer index: ndc_x = (2 x + 1) / W - 1) is derived from `proj`, not from tan_fov: the loaders
+// produce cameras with an off-centre principal point (dvs_make_camera_intrinsics: COLMAP's cx, cy; dvs_camera_downscale: a cropped
+// level), and for those (ndc_x tan_fovx, ndc_y tan_fovy, 1) is not the pixel's ray. For a world direction d the clip coordinates are
+// (x, y, w) = M d with M the rows 0, 1, 3 of proj's 3x3 part (the camera centre maps to x = y = w = 0), so d = M^-1 (ndc_x, ndc_y, 1);
+// the host inverts M in fp64 once per view (dvs_api.cpp) and the nine floats arrive as the FIRST kernel parameter, read through the
+// kernarg segment (as ViewBg, render_common.h). For a centred pinhole this is R^T (ndc_x tan_fovx, ndc_y tan_fovy, 1).
+// The lookup: u = (atan2(d.x, d.z) / 2 pi + 0.5) Ws - 0.5, v = (asin(d.y / |d|) / pi + 0.5) Hs - 0.5, texel centres at integer (u, v),
+// bilinear, u wrapping modulo Ws, v clamped to [0, Hs - 1]. tests/sky_ref.py restates it in fp64.
+//
+//   k_sky_forward        one thread per pixel, all views in one launch: out_rgb += final_T s in place, and s to sky_rgb when given.
+//   k_sky_backward_tex   dL/dtex: final_T g times the four bilinear weights, scattered with non-returning fp32 atomics. It repeats the
+//                        lookup's trigonometry (it needs the texel indices and weights, which sky_rgb does not hold). Consecutive lanes
+//                        are consecutive pixels of an image row and a texel is many pixels wide (45 at 1080p, 60 degrees, Ws = 256), so
+//                        the twelve products are first summed over runs of lanes that share a texel quad: a segmented inclusive scan
+//                        inside each 16-lane row with DPP row shifts (no LDS, no barrier), and only the last lane of a run issues the
+//                        atomics, none for a zero. Chosen over a per-workgroup LDS footprint because the footprint of 256 pixels of an
+//                        image row is not bounded (a row through the zenith sweeps every column of the texture), while runs need no
+//                        bound: where they are short the pass falls back to what the naive scatter costs.
+//   k_sky_backward_rows  the gradient through final_T = prod (1 - alpha_k): with h(p) = s(p) . g(p), every entry i pixel p took gets
+//                        dL/dalpha_i -= h final_T / (1 - alpha_i), chained exactly as k_render_bwd_tr chains its own dL/dalpha:
+//                        v5 = G dL/dalpha, gated by the 0.99 cap unless DVS_GRAD_LINEAGE, the moments of v5 about the splat's mean with
+//                        d = mean - pixel times the opacity into row columns 0..4, the plain sum into column 5 (dvs_get_bwd_intermediates).
+//                        This is the term the constant-bg path forms inside the composite backward from bg_dot. Shaped like
+//                        importance.hip: one 256-thread workgroup per (view, tile), entries staged through LDS in batches of 256, alpha
+//                        formed by the operations of k_render_fwd in its order; no back-to-front T: final_T is saved and alpha_i is
+//                        recomputed. Per (wave, entry): ballot first, then the six sums over the wave (four DPP steps per 16-lane row,
+//                        four v_readlane), lane 0 stores them in the wave's LDS slot; after the batch thread j folds the four waves'
+//                        slots of entry j and issues at most one non-returning atomic per value. Columns 9, 10 (abs-grad) are NOT
+//                        touched: the densification statistic stays that of the colour path. Pixels with n_contrib == 0 or h == 0 walk nothing.
+#include "dvs_device.h"
+#include "dvs_kernels.h"
+#include "render_common.h"
+
+struct SkyRays { float m[DVS_MAX_VIEWS][12]; };                 // per view: M^-1 row-major in [0..8] (d_r = m[3 r] nx + m[3 r + 1] ny + m[3 r + 2])
+struct SkyRay { float m[9]; };
+__device__ __forceinline__ SkyRay sky_load_ray(int v) {
+    typedef const __attribute__((address_space(4))) float* KF;
+    const KF f = (KF)__builtin_amdgcn_kernarg_segment_ptr() + (size_t)v * 12;
+    SkyRay r;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) r.m[k] = f[k];
+    return r;
+}
+
+struct SkyTap { int i00, i01, i10, i11; float w00, w01, w10, w11; };      // texel indices (y Ws + x) and bilinear weights
+__device__ __forceinline__ SkyTap sky_tap(const SkyRay& r, int x, int y, int W, int H, int Ws, int Hs) {
+    const float nx = (float)(2 * x + 1) / (float)W - 1.0f, ny = (float)(2 * y + 1) / (float)H - 1.0f;
+    const float dx = (r.m[0] * nx + r.m[1] * ny) + r.m[2], dy = (r.m[3] * nx + r.m[4] * ny) + r.m[5], dz = (r.m[6] * nx + r.m[7] * ny) + r.m[8];
+    const float len = sqrtf((dx * dx + dy * dy) + dz * dz);
+    const float sy = fminf(1.0f, fmaxf(-1.0f, dy / len));
+    const float u = (atan2f(dx, dz) * 0.15915494309189535f + 0.5f) * (float)Ws - 0.5f;
+    const float v = fminf((float)(Hs - 1), fmaxf(0.0f, (asinf(sy) * 0.31830988618379069f + 0.5f) * (float)Hs - 0.5f));
+    const float uf = floorf(u), vf = floorf(v);
+    const float fu = u - uf, fv = v - vf;
+    int x0 = (int)uf % Ws;                                      // u in [-0.5, Ws - 0.5] up to rounding: one wrap either way
+    if (x0 < 0) x0 += Ws;
+    const int x1 = x0 + 1 == Ws ? 0 : x0 + 1;
+    const int y0 = min(max((int)vf, 0), Hs - 1), y1 = min(y0 + 1, Hs - 1);
+    SkyTap t;
+    t.i00 = y0 * Ws + x0; t.i01 = y0 * Ws + x1; t.i10 = y1 * Ws + x0; t.i11 = y1 * Ws + x1;
+    t.w00 = (1.0f - fu) * (1.0f - fv); t.w01 = fu * (1.0f - fv); t.w10 = (1.0f - fu) * fv; t.w11 = fu * fv;
+    return t;
+}
+
+__global__ void __launch_bounds__(RB)
+k_sky_forward(SkyRays rays_arg /* MUST stay the first parameter: read through sky_load_ray() */, int W, int H, int n_views, const float* __restrict__ tex,
+              int Ws, int Hs, const float* __restrict__ final_T, float* __restrict__ out_rgb /*[views,3,H,W] or null*/,
+              float* __restrict__ sky_rgb /*[views,3,H,W] or null*/) {
+    (void)rays_arg;
+    const size_t P = (size_t)W * H;
+    const size_t gid = (size_t)blockIdx.x * RB + threadIdx.x;
+    if (gid >= P * (size_t)n_views) return;
+    const int view = (int)(gid / P);
+    const size_t p = gid - (size_t)view * P;
+    const int y = (int)(p / (size_t)W), x = (int)(p - (size_t)y * W);
+    const SkyTap t = sky_tap(sky_load_ray(view), x, y, W, H, Ws, Hs);
+    const float T = final_T[gid];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float s = ((t.w00 * tex[3 * (size_t)t.i00 + c] + t.w01 * tex[3 * (size_t)t.i01 + c]) + t.w10 * tex[3 * (size_t)t.i10 + c]) + t.w11 * tex[3 * (size_t)t.i11 + c];
+        const size_t o = ((size_t)view * 3 + c) * P + p;
+        if (sky_rgb) sky_rgb[o] = s;
+        if (out_rgb) out_rgb[o] = out_rgb[o] + T * s;
+    }
+}
+
+template <int CTRL> __device__ __forceinline__ float sky_dpp(float v) {
+    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));       // (a source outside the 16-lane row reads 0)
+}
+template <int CTRL> __device__ __forceinline__ int sky_dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
+
+// one step of the segmented inclusive scan inside a 16-lane row: lane l adds lane l - D unless a run starts between them
+template <int D> __device__ __forceinline__ void sky_scan_step(float (&val)[12], int& stop) {
+    const int ostop = sky_dpp_i<0x110 + D>(stop);               // row_shr:D
+#pragma unroll
+    for (int k = 0; k < 12; ++k) {
+        const float o = sky_dpp<0x110 + D>(val[k]);
+        val[k] = stop ? val[k] : val[k] + o;
+    }
+    stop |= ostop;                                              // (lanes l < D of the row already hold the stop of the row's first lane)
+}
+
+__global__ void __launch_bounds__(RB)
+k_sky_backward_tex(SkyRays rays_arg /* MUST stay the first parameter */, int W, int H, int n_views, int Ws, int Hs, const float* __restrict__ final_T,
+                   const float* __restrict__ dL_dout /*[views,3,H,W]*/, float* __restrict__ g_tex /*[Hs,Ws,3], accumulated into*/) {
+    (void)rays_arg;
+    const size_t P = (size_t)W * H;
+    const size_t gid = (size_t)blockIdx.x * RB + threadIdx.x;
+    const bool valid = gid < P * (size_t)n_views;               // (no early return: the row shifts below run with all 64 lanes)
+    float val[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) val[k] = 0.f;
+    SkyTap t{};
+    int key = -1;
+    if (valid) {
+        const int view = (int)(gid / P);
+        const size_t p = gid - (size_t)view * P;
+        const int y = (int)(p / (size_t)W), x = (int)(p - (size_t)y * W);
+        t = sky_tap(sky_load_ray(view), x, y, W, H, Ws, Hs);
+        key = t.i00;                                            // (i01, i10, i11 follow from i00)
+        const float T = final_T[gid];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float tg = T * dL_dout[((size_t)view * 3 + c) * P + p];
+            val[c] = t.w00 * tg; val[3 + c] = t.w01 * tg; val[6 + c] = t.w10 * tg; val[9 + c] = t.w11 * tg;
+        }
+    }
+    const int lane16 = threadIdx.x & 15;
+    const int prev = sky_dpp_i<0x111>(key), next = sky_dpp_i<0x101>(key);          // row_shr:1, row_shl:1
+    int stop = (lane16 == 0 || prev != key) ? 1 : 0;            // a run starts here
+    const bool last = lane16 == 15 || next != key;              // ... and ends here
+    sky_scan_step<1>(val, stop);
+    sky_scan_step<2>(val, stop);
+    sky_scan_step<4>(val, stop);
+    sky_scan_step<8>(val, stop);
+    if (valid && last) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            if (val[c] != 0.f) atomicAdd(&g_tex[3 * (size_t)t.i00 + c], val[c]);
+            if (val[3 + c] != 0.f) atomicAdd(&g_tex[3 * (size_t)t.i01 + c], val[3 + c]);
+            if (val[6 + c] != 0.f) atomicAdd(&g_tex[3 * (size_t)t.i10 + c], val[6 + c]);
+            if (val[9 + c] != 0.f) atomicAdd(&g_tex[3 * (size_t)t.i11 + c], val[9 + c]);
+        }
+    }
+}
+
+struct __attribute__((aligned(16))) SkyRowsLds {
+    float4 a[RB];       // mean x, mean y, cs.x, cs.y        (as importance.hip)
+    float4 b[RB];       // cs.z, opacity, -, -
+    float acc[RB / 64][6][RB];                                  // [wave][value][entry of the batch]
+    uint32_t wmax[RB / 64];
+};
+
+__device__ __forceinline__ float sky_wave_sum(float v) {        // all 64 lanes active; the result is wave-uniform
+    v += sky_dpp<0xB1>(v);            // quad_perm [1,0,3,2]
+    v += sky_dpp<0x4E>(v);            // quad_perm [2,3,0,1]
+    v += sky_dpp<0x141>(v);           // row_half_mirror
+    v += sky_dpp<0x140>(v);           // row_mirror
+    const int b = __float_as_int(v);
+    return (__int_as_float(__builtin_amdgcn_readlane(b, 0)) + __int_as_float(__builtin_amdgcn_readlane(b, 16))) +
+           (__int_as_float(__builtin_amdgcn_readlane(b, 32)) + __int_as_float(__builtin_amdgcn_readlane(b, 48)));
+}
+
+template <bool LINEAGE>
+__global__ void __launch_bounds__(RB)
+k_sky_backward_rows(int W, int H, int tiles_x, int tiles_per_view, int num_tiles, int n, const uint2* __restrict__ ranges,
+                    const uint32_t* __restrict__ sorted_splat, const float4* __restrict__ splat2d, const float* __restrict__ final_T,
+                    const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dout /*[views,3,H,W]*/,
+                    const float* __restrict__ sky_rgb /*[views,3,H,W]*/, float* __restrict__ grow /*[views,n,12]*/) {
+    __shared__ SkyRowsLds L;
+    const int tile_g = tile_of_block(blockIdx.x, num_tiles);
+    if (tile_g >= num_tiles) return;                                       // (whole workgroup: no barrier is skipped by a part of it)
+    const int view = tile_g / tiles_per_view, tile = tile_g - view * tiles_per_view;
+    const int tx = tile % tiles_x, ty = tile / tiles_x;
+    const int t = threadIdx.x, wave = t >> 6;
+    const int px = tx * DVS_TILE + (t & 15), py = ty * DVS_TILE + (t >> 4);
+    const bool inside = px < W && py < H;
+    const size_t P = (size_t)W * H;
+    const size_t pix = (size_t)py * W + px;
+    float c5 = 0.f;                                                        // -h final_T: dL/dalpha_i = c5 / (1 - alpha_i)
+    if (inside) {
+        const float* const g = dL_dout + (size_t)view * 3 * P + pix;
+        const float* const s = sky_rgb + (size_t)view * 3 * P + pix;
+        const float h = (s[0] * g[0] + s[P] * g[P]) + s[2 * P] * g[2 * P];
+        c5 = -(final_T[(size_t)view * P + pix] * h);
+    }
+    const uint2 range = ranges[tile_g];
+    const uint32_t total = range.y - range.x;
+    const uint32_t mine = (inside && c5 != 0.f) ? min(n_contrib[(size_t)view * P + pix], total) : 0u;   // entries this pixel walks; never more than the tile's list holds
+    uint32_t wm = mine;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, d, 64));
+    if ((t & 63) == 0) L.wmax[wave] = wm;
+    __syncthreads();
+    const uint32_t need = max(max(L.wmax[0], L.wmax[1]), max(L.wmax[2], L.wmax[3]));   // entries the workgroup stages
+
+    const float pxf = (float)px, pyf = (float)py;
+    for (uint32_t base = 0; base < need; base += RB) {
+        const uint32_t cnt = min((uint32_t)RB, need - base);
+        uint32_t id = 0;
+        float op = 0.f;
+        if ((uint32_t)t < cnt) {
+            id = sorted_splat[range.x + base + t];                         // batch-wide value: view * n + splat, the record's and the row's index
+            const float4 r0 = splat2d[4 * (size_t)id], r1 = splat2d[4 * (size_t)id + 1];
+            op = r1.y;
+            L.a[t] = make_float4(r0.x, r0.y, -0.72134752044448170f * r0.z, -1.4426950408889634f * r0.w);
+            L.b[t] = make_float4(-0.72134752044448170f * r1.x, r1.y, 0.f, 0.f);
+#pragma unroll
+            for (int w = 0; w < RB / 64; ++w)
+#pragma unroll
+                for (int k = 0; k < 6; ++k) L.acc[w][k][t] = 0.f;
+        }
+        __syncthreads();
+        const uint32_t stop = mine > base ? min(cnt, mine - base) : 0u;
+        const uint32_t wave_stop = wm > base ? min(cnt, wm - base) : 0u;   // wave-uniform: the cross-lane steps below run with all 64 lanes
+        for (uint32_t j = 0; j < wave_stop; ++j) {
+            const float4 A = L.a[j], B = L.b[j];
+            const float dx = A.x - pxf, dy = A.y - pyf;                    // d = mean - pixel
+            const float p2 = __builtin_fmaf(B.x * dy, dy, __builtin_fmaf(A.w, dy, A.z * dx) * dx);
+            const float G = __builtin_amdgcn_exp2f(p2);
+            const float oa = B.y * G;
+            const float alpha = fminf(DVS_ALPHA_MAX, oa);
+            const bool take = j < stop && !(p2 > 0.f || alpha < DVS_ALPHA_MIN);
+            // DVS_GRAD_TRUE: the 0.99 clamp blocks the gradient; DVS_GRAD_LINEAGE: it passes as if alpha = opacity * G (k_render_bwd_tr)
+            const bool gate = LINEAGE ? take : (take && !(oa > DVS_ALPHA_MAX));
+            if (__ballot(gate) == 0ull) continue;
+            const float v5 = gate ? G * (c5 * __builtin_amdgcn_rcpf(1.f - alpha)) : 0.f;
+            const float vx = v5 * dx, vy = v5 * dy;
+            const float s0 = sky_wave_sum(vx), s1 = sky_wave_sum(vy), s2 = sky_wave_sum(vx * dx), s3 = sky_wave_sum(vx * dy),
+                        s4 = sky_wave_sum(vy * dy), s5 = sky_wave_sum(v5);
+            if ((t & 63) == 0) {
+                L.acc[wave][0][j] = s0; L.acc[wave][1][j] = s1; L.acc[wave][2][j] = s2; L.acc[wave][3][j] = s3; L.acc[wave][4][j] = s4;
+                L.acc[wave][5][j] = s5;
+            }
+        }
+        __syncthreads();
+        if ((uint32_t)t < cnt && id - (uint32_t)view * (uint32_t)n < (uint32_t)n) {
+            float* const row = grow + (size_t)id * 12;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                const float v = (L.acc[0][k][t] + L.acc[1][k][t]) + (L.acc[2][k][t] + L.acc[3][k][t]);
+                // the moment sums were taken over v5 = G dL/dalpha; the row contract wants them over opacity * v5 (column 5 is dL/dopacity itself)
+                if (v != 0.f) atomicAdd(&row[k], k == 5 ? v : v * op);
+            }
+        }
+        // (the next batch's staging writes only what this thread has just read, and the barrier after it orders the rest)
+    }
+}
+
+static SkyRays make_sky_rays(int n_views, const float* minv /*[n_views][9]*/) {
+    SkyRays r{};
+    for (int v = 0; v < n_views && v < DVS_MAX_VIEWS; ++v) for (int k = 0; k < 9; ++k) r.m[v][k] = minv[9 * v + k];
+    return r;
+}
+
+hipError_t dvs_launch_sky_forward(hipStream_t st, int W, int H, int n_views, const float* minv, const float* tex, int Ws, int Hs, const float* final_T,
+                                  float* out_rgb, float* sky_rgb) {
+    const size_t total = (size_t)W * H * n_views;
+    if (total == 0) return hipSuccess;
+    if (n_views > DVS_MAX_VIEWS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sky_forward, dim3((unsigned)((total + RB - 1) / RB)), dim3(RB), 0, st, make_sky_rays(n_views, minv), W, H, n_views, tex, Ws, Hs,
+                       final_T, out_rgb, sky_rgb);
+    return hipGetLastError();
+}
+
+hipError_t dvs_launch_sky_backward_tex(hipStream_t st, int W, int H, int n_views, const float* minv, int Ws, int Hs, const float* final_T,
+                                       const float* dL_dout, float* g_tex) {
+    const size_t total = (size_t)W * H * n_views;
+    if (total == 0) return hipSuccess;
+    if (n_views > DVS_MAX_VIEWS) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_sky_backward_tex, dim3((unsigned)((total + RB - 1) / RB)), dim3(RB), 0, st, make_sky_rays(n_views, minv), W, H, n_views, Ws, Hs,
+                       final_T, dL_dout, g_tex);
+    return hipGetLastError();
+}
+
+hipError_t dvs_launch_sky_backward_rows(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, int n, const uint32_t* ranges,
+                                        const uint32_t* sorted_splat, const float* splat2d, const float* final_T, const uint32_t* n_contrib,
+                                        const float* dL_dout, const float* sky_rgb, float* grad_rows, int grad_mode) {
+    const int tiles_pv = tiles_x * tiles_y, num_tiles = tiles_pv * n_views;
+    if (num_tiles <= 0 || n <= 0) return hipSuccess;
+    const int grid = ((num_tiles + 7) >> 3) << 3;
+#define DVS_SKY_ROWS(LN)                                                                                                                       \
+    hipLaunchKernelGGL((k_sky_backward_rows<LN>), dim3(grid), dim3(RB), 0, st, W, H, tiles_x, tiles_pv, num_tiles, n, (const uint2*)ranges,   \
+                       sorted_splat, (const float4*)splat2d, final_T, n_contrib, dL_dout, sky_rgb, grad_rows)
+    if (grad_mode == 1) DVS_SKY_ROWS(true); else DVS_SKY_ROWS(false);
+#undef DVS_SKY_ROWS
+    return hipGetLastError();
+}

@@ -55,7 +55,11 @@ static std::map<std::string, std::string> g_opts = {
     // extensions of this build, for the mesh --meshResolution writes: --meshMinComponent P (percent, 0..100, at most two decimals) drops the
     // connected components with fewer than P % of the largest one's triangles; --meshNormals 1 adds nx ny nz, the TSDF gradient's unit
     // normals. The config struct has no room left: when given they are handed to the plugin as DVS_MESH_MIN_COMPONENT / DVS_MESH_NORMALS.
-    {"meshMinComponent", "0"}, {"meshNormals", "0"}};
+    {"meshMinComponent", "0"}, {"meshNormals", "0"},
+    // the reference's config field enableBg ("Create Sky Model"; its CLI has no flag for it): --enableBg 1 trains an equirectangular sky
+    // texture behind the splats and writes <outputPath>_<it>.sky at every save. --skyResolution Hs (default 128, clamped to 16..1024) is the
+    // texture's height, its width 2 Hs; the config struct has no room left: it is handed to the plugin as DVS_SKY_RESOLUTION.
+    {"enableBg", "0"}, {"skyResolution", "128"}};
 static std::map<std::string, bool> g_given;
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
@@ -102,6 +106,12 @@ int main(int argc, const char* argv[]) {
         const std::string& v = g_opts["meshNormals"];
         if (v != "0" && v != "1") { std::cout << "Command Line Error: --meshNormals takes 0 or 1, not '" << v << "'\n"; return 1; }
         setenv("DVS_MESH_NORMALS", v.c_str(), 1);
+    }
+    if (g_opts["enableBg"] != "0" && g_opts["enableBg"] != "1") { std::cout << "Command Line Error: --enableBg takes 0 or 1, not '" << g_opts["enableBg"] << "'\n"; return 1; }
+    if (g_given.count("skyResolution")) {
+        const std::string& v = g_opts["skyResolution"];
+        if (v.empty() || v.size() > 5 || v.find_first_not_of("0123456789") != std::string::npos) { std::cout << "Command Line Error: --skyResolution takes a texture height (16..1024), not '" << v << "'\n"; return 1; }
+        setenv("DVS_SKY_RESOLUTION", v.c_str(), 1);                         // before the plugin is loaded
     }
     // plugin: "libgstrain.so" next to the executable (plugin.cpp:74 builds parent_path / "lib<name>.so")
     std::error_code ec;
@@ -179,6 +189,7 @@ int main(int argc, const char* argv[]) {
         if (!digits || atoi(ip.c_str()) > 90) { std::cout << "Command Line Error: --importancePrune takes an integer 0..90, not '" << ip << "'\n"; return 1; }
         train_config.importancePrune = (uint8_t)atoi(ip.c_str());
     }
+    train_config.enableBg = g_opts["enableBg"] == "1";
     train_config.normalConsistencyLoss = false;
     if (train_config.exportMesh) { train_config.normalConsistencyLoss = true; train_config.useMask = true; }
     train_config.verbose = true;

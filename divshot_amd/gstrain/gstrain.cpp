@@ -89,6 +89,7 @@ void GaussianTrainerScene::trainStep() {
     if (pipelined) m.finish_pipelined(s);
     else if (m.exchange_factorised()) m.finish_range(s, 0, m.n, kGeomGroups, 4, s.adam_gate);     // (the SH groups were stepped in exchange())
     else m.finish_range(s, 0, m.n, kAllGroups, 6, s.adam_gate);
+    m.step_sky(s);                                                          // (nothing when enableBg is off)
     if (s.refine_now) { if (s.mcmc) m.densify_mcmc(s.it); else m.densify(s.it); }
     if (s.reset_now)
         DVS_OR_THROW(dvs_reset_opacity(m.stream.get(), m.n, m.d_param[P_OPA].get(), 0.01f, m.d_m[P_OPA].get(), m.d_v[P_OPA].get()));
@@ -124,6 +125,7 @@ void GaussianTrainerScene::saveGaussianModel() {
                           m.host[5].data(), m.cfg.mipAntiliased, &err))
         logf_("save_splat_model: %s", err.c_str());
     else if (m.cfg.verbose) logf_("saved %d splats to %s", m.n, file.c_str());
+    m.save_sky();                                                           // <modelPath>_<it>.sky[.rank<r>] (enableBg on)
     if (m.rank == 0 && m.export_formats()) {                                // the comparison for the compact exports' lines below
         std::error_code fec;
         const auto ply_bytes = std::filesystem::file_size(file, fec);
@@ -190,6 +192,7 @@ void GaussianTrainerScene::resetGaussian() {
         m.upload(g, m.init_host[g]);
     }
     HIP_OR_THROW(hipMemset(m.d_grad_flat.get(), 0, m.grad_floats * sizeof(float)));
+    if (m.sky_on) for (DevBuf<float>* b : {&m.d_sky, &m.d_sky_m, &m.d_sky_v}) HIP_OR_THROW(hipMemset(b->get(), 0, m.sky_floats() * sizeof(float)));
     m.reset_stats();
     m.step = 0; curIteration = 0; pruenIteraions.clear();
     m.eval_it = -1;

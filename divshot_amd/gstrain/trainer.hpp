@@ -182,6 +182,27 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     int importance_prune() const { return std::min(90, std::max(0, env_int("DVS_IMPORTANCE_PRUNE", cfg.importancePrune))); }   // percent, 0 = off
     void prune_importance(int it);
 
+    // sky model (cfg.enableBg, the reference's "Create Sky Model"; trainer_output.cpp): an equirectangular fp32 texture [sky_h][2 sky_h][3]
+    // behind the splats (dvs_sky_forward_views / dvs_sky_backward_views, dvs_raster.h), initialised to zero, its own Adam state, the
+    // step's gradient, and the lookup the forward leaves for the backward. Every camera of the trainer has bg = 0 (the loaders set
+    // none). Nothing is allocated, launched or written while enableBg is off. DVS_SKY_RESOLUTION (--skyResolution; 128, clamped to
+    // 16..1024) and DVS_SKY_LR (0.01) are read at load.
+    struct Step;
+    bool sky_on = false; int sky_h = 0; float sky_lr = 0.01f;
+    DevBuf<float> d_sky, d_sky_m, d_sky_v, d_sky_grad, d_sky_rgb;
+    size_t sky_floats() const { return (size_t)sky_h * 2 * sky_h * 3; }
+    dvs_sky sky() const { dvs_sky s{}; s.tex = d_sky.get(); s.width = 2 * sky_h; s.height = sky_h; return s; }
+    std::string sky_file(int it) const { return cfg.modelPath + "_" + std::to_string(it) + ".sky"; }
+    void setup_sky(bool resumed);
+    void step_sky(const Step& s);
+    void save_sky();
+    // out (+)= final_T s for the nb views `c` just rendered into `out` (evaluation, written renders); nothing when the sky is off
+    void composite_sky(dvs_ctx* c, const dvs_camera* bc, int nb, float* out) {
+        if (!sky_on) return;
+        const dvs_sky s = sky();
+        DVS_OR_THROW(dvs_sky_forward_views(c, stream.get(), bc, nb, &s, out, nullptr));
+    }
+
     ~Impl() { if (device >= 0) (void)hipSetDevice(device); }                // (the members release themselves, after this body)
     // floats of group g on the device: the 45 higher-order SH floats live in the DVS_SHN_TILED layout (48 per splat,
     // whole 64-splat tiles); parameters, gradients and Adam moments share it — the optimizer is element-wise.

@@ -241,6 +241,7 @@ void GaussianTrainerScene::Impl::finish_load(const std::function<void(std::vecto
     }
     if (!resumed) fresh_init(init);
     for (int g = 0; g < 6; ++g) { upload(g, init[g]); init_host[g] = init[g]; }
+    setup_sky(resumed);
     report_config();
     describe(resumed);
     if (exchange_factorised()) setup_exchange();

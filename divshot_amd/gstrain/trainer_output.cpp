@@ -1,5 +1,6 @@
 // trainer_output.cpp — what the trainer reports and writes: the configuration lines, held-out evaluation, host copies, compact exports.
 #include "trainer.hpp"
+#include "sky_io.hpp"
 
 // One line per decision: which GaussianTrainConfig fields this build honours and which it ignores (gs_train.cpp:50-103 sets them all).
 void GaussianTrainerScene::Impl::report_config() const {
@@ -47,13 +48,16 @@ void GaussianTrainerScene::Impl::report_config() const {
               "summed over the %zu training cameras are removed (scored and selected on the device, every rank for itself)", P,
               cfg.pruneStrategy > 0 ? "" : " (none: pruneStrategy is 0)", P, train_idx.empty() ? cams.size() : train_idx.size());
     }
+    if (sky_on)
+        logf_("config: skyModel %dx%d: enableBg — an equirectangular fp32 texture behind the splats, looked up along each pixel's ray and trained with "
+              "them (Adam, lr %g); every save also writes <modelPath>_<it>.sky; evaluation and written renders composite it; mesh export, the "
+              "importance score and the depth pass do not see it", 2 * sky_h, sky_h, (double)sky_lr);
     std::string ign;
     if (cfg.modelType != 0) ign += " modelType(only 3DGS)";
     if (cfg.cullSH) ign += " cullSH";
     if (cfg.pixelGradScale) ign += " pixelGradScale";
     if (cfg.bestQuality) ign += " bestQuality";
     if (cfg.normalConsistencyLoss) ign += " normalConsistencyLoss(2DGS)";
-    if (cfg.enableBg) ign += " enableBg";
     if (cfg.enableFocusRegion) ign += " enableFocusRegion";
     if (cfg.exportMesh) ign += " exportMesh";
     if (cfg.outputSparsePoints) ign += " outputSparsePoints";
@@ -112,6 +116,7 @@ void GaussianTrainerScene::Impl::score_views(const dvs_splats& sp, std::vector<d
             mv[k].mask = view_mask(ci);
         }
         DVS_OR_THROW(dvs_raster_forward_views(eval_ctx.get(), stream.get(), &sp, bc.data(), nb, &opts, d_eval_out.get()));
+        composite_sky(eval_ctx.get(), bc.data(), nb, d_eval_out.get());     // what was trained: the sky behind the splats
         DVS_OR_THROW(dvs_image_metrics_views(stream.get(), mv, nb, W, H, views_u8() ? 1 : 0, d_eval_scratch.get(), d_eval_res.get() + (size_t)first * 4));
     }
     res.assign((size_t)nt * 4, 0.0);
@@ -140,6 +145,35 @@ void GaussianTrainerScene::Impl::write_eval_json() const {
         fprintf(f, ",\n  \"exports\": {\"spz\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}}", spz_mean[3], spz_mean[2], spz_mean[1], spz_mean[0]);
     fprintf(f, "\n}\n");
     fclose(f);
+}
+
+// The sky texture: allocated (zero: the first forward is the image over black) when enableBg is on; a resume reads <modelPath>_<it>.sky
+// when it is there and fits the configured size, else starts from zero and says so.
+void GaussianTrainerScene::Impl::setup_sky(bool resumed) {
+    sky_on = cfg.enableBg;
+    if (!sky_on) return;
+    sky_h = std::min(1024, std::max(16, env_int("DVS_SKY_RESOLUTION", 128)));
+    if (const char* e = getenv("DVS_SKY_LR")) { const float v = (float)atof(e); if (v > 0.f && std::isfinite(v)) sky_lr = v; }
+    const size_t bytes = sky_floats() * sizeof(float);
+    for (DevBuf<float>* b : {&d_sky, &d_sky_m, &d_sky_v, &d_sky_grad}) { b->alloc(bytes); HIP_OR_THROW(hipMemset(b->get(), 0, bytes)); }
+    d_sky_rgb.alloc((size_t)vpi * 3 * (size_t)W * H * sizeof(float));
+    if (!resumed) return;
+    uint32_t w = 0, h = 0; std::vector<float> tex; std::string err;
+    const std::string file = sky_file(loadItr);
+    if (!gssky::read_sky(file, &w, &h, &tex, &err)) { logf_("sky: could not read %s (%s): the texture starts from zero", file.c_str(), err.c_str()); return; }
+    if ((int)h != sky_h) { logf_("sky: %s is %ux%u, this run asks for %dx%d: the texture starts from zero", file.c_str(), w, h, 2 * sky_h, sky_h); return; }
+    HIP_OR_THROW(hipMemcpy(d_sky.get(), tex.data(), bytes, hipMemcpyHostToDevice));
+    logf_("sky: read the %ux%u texture from %s", w, h, file.c_str());
+}
+void GaussianTrainerScene::Impl::save_sky() {
+    if (!sky_on) return;
+    std::vector<float> tex(sky_floats());
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    HIP_OR_THROW(hipMemcpy(tex.data(), d_sky.get(), tex.size() * sizeof(float), hipMemcpyDeviceToHost));
+    const std::string file = sky_file(step) + (rank != 0 ? ".rank" + std::to_string(rank) : std::string());      // (the PLY's convention)
+    std::string err;
+    if (!gssky::write_sky(file, (uint32_t)(2 * sky_h), (uint32_t)sky_h, tex.data(), &err)) logf_("save_splat_model: %s", err.c_str());
+    else if (cfg.verbose) logf_("saved the %dx%d sky texture to %s", 2 * sky_h, sky_h, file.c_str());
 }
 
 void GaussianTrainerScene::Impl::fetch_host() {

@@ -62,6 +62,7 @@ bool GaussianTrainerScene::Impl::render_to_jpeg(const std::vector<int>& which, c
             coefs[k] = d_render_coef.get() + (size_t)k * count;
         }
         DVS_OR_THROW(dvs_raster_forward_views(eval_ctx.get(), stream.get(), &sp, bc.data(), nb, &opts, d_eval_out.get()));
+        composite_sky(eval_ctx.get(), bc.data(), nb, d_eval_out.get());
         HIP_OR_THROW(hipEventRecord(ev_render0.get(), stream.get()));
         DVS_OR_THROW(dvs_jpeg_encode_views(stream.get(), &desc, images, coefs, nb));
         HIP_OR_THROW(hipEventRecord(ev_render1.get(), stream.get()));

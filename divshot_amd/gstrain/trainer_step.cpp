@@ -140,6 +140,8 @@ void GaussianTrainerScene::Impl::render_backward(Step& s) {
     g.scale = d_grad[P_SCALE]; g.rot = d_grad[P_ROT]; g.absgrad2d = s.absgrad ? d_absgrad.get() : nullptr;
     g.mean2d = (s.want_stats && !s.absgrad) ? d_mean2d.get() : nullptr;    // ADC without abs-grad: dL/dmean2D feeds the statistic
     if (fact) { g.sh0 = nullptr; g.shN = nullptr; }                          // (the SH rows are rebuilt after the exchange)
+    const dvs_sky sky_tex = sky();
+    if (sky_on) HIP_OR_THROW(hipMemsetAsync(d_sky_grad.get(), 0, sky_floats() * sizeof(float), st));
     for (int v = 0; v < passes; ++v) {                                      // v: the first view of the pass
         const dvs_camera* cam = &s.vcams[(size_t)v];
         opts.accumulate = v > 0 ? 1 : 0;
@@ -149,8 +151,13 @@ void GaussianTrainerScene::Impl::render_backward(Step& s) {
             DVS_OR_THROW(dvs_raster_forward_views(ctx.get(), st, &sp, cam, pass_views, &opts, d_out.get()));
             DVS_OR_THROW(dvs_get_view_state(ctx.get(), 0, &fwd));             // (view-major arrays: fwd.radii = [V][n])
         }
+        if (sky_on)                                                         // out = C + final_T s; s stays for the backward
+            DVS_OR_THROW(dvs_sky_forward_views(ctx.get(), st, cam, pass_views, &sky_tex, d_out.get() + (size_t)v * img, d_sky_rgb.get() + (size_t)v * img));
         for (int u = v; u < v + pass_views; ++u) loss_of_view(s, u);
         DVS_OR_THROW(dvs_raster_backward_composite(ctx.get(), st, cam, &opts, d_dL.get() + (size_t)v * img));
+        if (sky_on)                                                         // the texel gradient, and the gradient through final_T into the pending rows
+            DVS_OR_THROW(dvs_sky_backward_views(ctx.get(), st, cam, pass_views, &opts, &sky_tex, d_dL.get() + (size_t)v * img,
+                                                d_sky_rgb.get() + (size_t)v * img, d_sky_grad.get()));
         if (fact) {
             g.dcolor = d_dcolor_scratch.get() + (size_t)v * n * 3;           // A9's own copy of the colour gradient
             DVS_OR_THROW(dvs_raster_backward_dcolor(ctx.get(), st, d_dcolor_local.get() + (size_t)v * n * 3));
@@ -200,6 +207,15 @@ void GaussianTrainerScene::Impl::render_backward(Step& s) {
         }
     }
     if (visible_adam()) s.adam_gate = seq || vpi == 1 ? fwd.radii : any_view_radii();   // (sequential: the last view's — a single-view notion there)
+}
+
+// the sky texture's optimizer step: its gradient summed over the ranks (one all-reduce, on the training stream: the texture is small),
+// so that the replicas keep identical textures, then plain Adam with the betas and eps of the other groups
+void GaussianTrainerScene::Impl::step_sky(const Step& s) {
+    if (!sky_on) return;
+    if (comm) DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm.get(), stream.get(), d_sky_grad.get(), sky_floats()));
+    DVS_OR_THROW(dvs_adam_step(stream.get(), d_sky.get(), d_sky_grad.get(), d_sky_m.get(), d_sky_v.get(), sky_floats(), sky_lr, kAdamBeta1, kAdamBeta2,
+                               kAdamEps, s.it));
 }
 
 // data parallel, over RCCL / xGMI: all-gather of the views' colour gradients + all-reduce of the geometry groups, then every

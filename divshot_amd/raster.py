@@ -7,7 +7,7 @@ image + saved state, backward -> per-splat gradient rows).
 import ctypes as C
 import numpy as np
 import torch
-from ._lib import lib, Splats, Camera, Opts, FwdState, SplatGrads, check, DvsError
+from ._lib import lib, Splats, Camera, Opts, FwdState, SplatGrads, Sky, check, DvsError
 
 PARAM_KEYS = ("pos", "sh0", "shN", "opacity", "scale", "rot")
 PARAM_WIDTH = {"pos": 3, "sh0": 3, "shN": 45, "opacity": 1, "scale": 3, "rot": 4}
@@ -305,6 +305,35 @@ class Rasterizer:
                 if after_chunk is not None:
                     after_chunk(k, first, count)
         return grads
+
+    # -- sky model (dvs_sky_forward_views / dvs_sky_backward_views) -------------------------------------------------
+    def _sky_args(self, tex):
+        assert tex.is_cuda and tex.dtype == torch.float32 and tex.is_contiguous() and tex.dim() == 3 and tex.shape[2] == 3
+        cams = self._cams if getattr(self, "_cams", None) is not None else (Camera * 1)(self._cam)
+        return cams, len(cams), Sky(tex.data_ptr(), tex.shape[1], tex.shape[0])
+
+    def sky_forward(self, tex, out_rgb, want_sky_rgb=False):
+        """After forward / forward_views with cam.bg = 0: out_rgb += final_T * s in place, s = the lookup of the equirectangular texture
+        tex [Hs,Ws,3] (CUDA) along every pixel's ray. want_sky_rgb: also return s, shaped like out_rgb, for sky_backward."""
+        cams, V, sky = self._sky_args(tex)
+        assert out_rgb.is_cuda and out_rgb.dtype == torch.float32 and out_rgb.is_contiguous()
+        s = torch.empty_like(out_rgb) if want_sky_rgb else None
+        with torch.cuda.device(self.tdev):
+            check(lib.dvs_sky_forward_views(self.ctx, _stream_ptr(), cams, V, C.byref(sky), out_rgb.data_ptr(), s.data_ptr() if want_sky_rgb else None),
+                  "dvs_sky_forward_views")
+        return s
+
+    def sky_backward(self, tex, dL_drgb, g_tex=None, sky_rgb=None):
+        """Between backward_composite and backward_project: g_tex (+)= dL/dtex (a new zeroed tensor when None) and the pending rows gain
+        the gradient through final_T. sky_rgb: what sky_forward returned, or None (the lookup is repeated). Returns g_tex."""
+        cams, V, sky = self._sky_args(tex)
+        assert dL_drgb.is_cuda and dL_drgb.dtype == torch.float32 and dL_drgb.is_contiguous()
+        if g_tex is None:
+            g_tex = torch.zeros_like(tex)
+        with torch.cuda.device(self.tdev):
+            check(lib.dvs_sky_backward_views(self.ctx, _stream_ptr(), cams, V, C.byref(self._opts), C.byref(sky), dL_drgb.data_ptr(),
+                                             sky_rgb.data_ptr() if sky_rgb is not None else None, g_tex.data_ptr()), "dvs_sky_backward_views")
+        return g_tex
 
     def sh_grad_combine(self, pos, campos, dcolor_all, g_sh0, g_shN, sh_degree, accumulate=False, shn_tiled=False):
         """g_sh0/g_shN (+)= sum over views of the SH rows implied by dcolor_all [V,n,3]; campos: [V,3] host floats."""

@@ -290,6 +290,44 @@ int dvs_raster_depth_views(dvs_ctx* ctx, void* stream, const dvs_opts* opts, flo
 int dvs_raster_importance_views(dvs_ctx* ctx, void* stream, const dvs_opts* opts, const float* const* masks, uint64_t* score_sum,
                                 uint32_t* score_max, uint32_t* hits);
 
+/* Sky model: a learned equirectangular RGB texture behind the splats, instead of the constant dvs_camera.bg. fp32 values used as they
+ * are (no activation). Two separate passes over the state the forward saved; the composite kernels run with bg = 0 and are untouched.
+ *   tex     DEVICE [height][width][3], 16-byte aligned, width == 2 * height, height >= 2; texel centres at integer (u, v).
+ * The ray of pixel (x, y) (centre = the integer index, ndc_x = (2 x + 1) / W - 1) is derived from `proj`, because cameras with an
+ * off-centre principal point exist (dvs_make_camera_intrinsics, dvs_camera_downscale): a world direction d has clip coordinates
+ * (x, y, w) = M d with M the rows 0, 1, 3 of proj's 3x3 part, so d = normalize(M^-1 (ndc_x, ndc_y, 1)) — for a centred pinhole this is
+ * normalize(R^T (ndc_x tan_fovx, ndc_y tan_fovy, 1)) with R the rotation of `view`. The lookup s(p):
+ *   u = (atan2(d.x, d.z) / 2 pi + 0.5) width - 0.5,   v = (asin(clamp(d.y, -1, 1)) / pi + 0.5) height - 0.5,
+ * bilinear, u wrapping modulo width, v clamped to [0, height - 1].
+ * Both calls return DVS_ERR_INVALID for NULL or misaligned pointers, width != 2 height, height < 2, a singular proj, or any cams[v].bg
+ * component that is not zero (never both backgrounds). */
+typedef struct dvs_sky {
+    float* tex;
+    int32_t width, height;
+} dvs_sky;
+
+/* out_rgb(p) += final_T(p) s(p), in place on the image [n_views,3,H,W] the last forward on the context wrote with these cameras (bg = 0):
+ * afterwards out = C + final_T s. sky_rgb: DEVICE [n_views,3,H,W] or NULL; when given it receives s, which dvs_sky_backward_views reads
+ * instead of repeating the lookup. Valid after dvs_raster_forward / _views until the next forward (DVS_ERR_STATE otherwise, also for
+ * another n_views or image size), in synchronous and asynchronous mode and with either tile_bounds setting. Asynchronous, on `stream`. */
+int dvs_sky_forward_views(dvs_ctx* ctx, void* stream, const dvs_camera* cams, int n_views, const dvs_sky* sky, float* out_rgb, float* sky_rgb);
+
+/* The sky's share of the backward, to be called BETWEEN dvs_raster_backward_composite and dvs_raster_backward_project (or the first
+ * dvs_raster_backward_project_chunk): DVS_ERR_STATE when no composite backward is pending. With g = dL_drgb [n_views,3,H,W] (16-byte
+ * aligned, the array the composite backward got) and h(p) = s(p) . g(p):
+ *   g_tex [height][width][3] += final_T(p) g(p) times the four bilinear weights of p   (ACCUMULATED INTO: the caller zeroes it)
+ *   the context's pending intermediate rows (dvs_get_bwd_intermediates) gain the gradient through final_T = prod (1 - alpha_k): for every
+ *   entry i pixel p took, dL/dalpha_i -= h(p) final_T(p) / (1 - alpha_i), chained to the opacity and the Gaussian exactly as the composite
+ *   backward chains its own dL/dalpha, in both grad_modes (columns 0..5 of the row: S_x, S_y, S_xx, S_xy, S_yy, dL/dopacity).
+ *   The abs-grad columns (9, 10) are NOT touched: the densification statistic stays that of the colour path.
+ * For a texture whose texels all hold one colour b this reproduces, together with the composite backward at bg = 0, the gradients of
+ * the constant cam.bg = b path. sky_rgb: what dvs_sky_forward_views wrote, or NULL (the lookup is then repeated into a context-owned
+ * buffer, which is allocated or enlarged at that call: a hipMalloc in the middle of the stream, so pass sky_rgb under graph capture).
+ * The cameras must be those of the forward: their count and image sizes are checked (DVS_ERR_STATE), their poses are the caller's
+ * responsibility. `opts` are those of the forward. Asynchronous, on `stream`. */
+int dvs_sky_backward_views(dvs_ctx* ctx, void* stream, const dvs_camera* cams, int n_views, const dvs_opts* opts, const dvs_sky* sky,
+                           const float* dL_drgb, const float* sky_rgb, float* g_tex);
+
 /* Asynchronous forward. By default dvs_raster_forward synchronises `stream` once (it reads the instance count T to size the sort).
  * With dvs_set_async(ctx, 1) it never synchronises: the instance arena is over-allocated, T stays on the device and every kernel over
  * instances reads it there; *num_rendered and saved->num_rendered are DVS_T_UNKNOWN (dvs_get_num_rendered synchronises on demand).
