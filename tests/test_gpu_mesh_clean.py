@@ -131,6 +131,53 @@ def test_tie_for_largest_keeps_both_and_bad_triangles_are_dropped(gpu_device):
     assert got[4]["kept_components"] == 4 and got[4]["kept_triangles"] == 90 and got[4]["kept_vertices"] == 42 + 11 + 42 + 3
 
 
+# ---- 2b. compaction past 256 block sums ---------------------------------------------------------------------------------------------
+BIG_STRIP, BIG_ISOLATED = 400000, 200000
+
+
+def big_mesh():
+    """one strip of 400 000 triangles over 400 002 vertices, then 200 000 isolated triangles on their own 600 000 vertices; triangles
+    shuffled, corners shuffled inside each triangle, vertex ids permuted -> (xyz, rgb, tri, normals, in_strip [nt], perm)"""
+    r = np.random.default_rng(17)
+    nv = BIG_STRIP + 2 + 3 * BIG_ISOLATED
+    tri = np.concatenate([strip(0, BIG_STRIP), BIG_STRIP + 2 + np.arange(3 * BIG_ISOLATED).reshape(-1, 3)])
+    perm = r.permutation(nv)
+    order = r.permutation(len(tri))
+    tri = r.permuted(perm[tri][order], axis=1)
+    xyz = r.normal(0, 1, (nv, 3)).astype(np.float32)
+    rgb = r.integers(0, 256, (nv, 3)).astype(np.uint8)
+    nrm = r.normal(0, 1, (nv, 3)).astype(np.float32)
+    return xyz, rgb, tri.astype(np.uint32), nrm, order < BIG_STRIP, perm
+
+
+def test_compaction_past_256_block_sums(gpu_device):
+    """1 000 002 vertices are 489 block sums of the shared scan and 600 000 triangles 293: k_scan_block_sums runs two rounds for each,
+    and the second needs the first's carry. With min_bp = 1 an isolated triangle goes (1 x 10 000 < 400 000 x 1)."""
+    xyz, rgb, tri, nrm, in_strip, perm = big_mesh()
+    nv, nt = len(xyz), len(tri)
+    assert nv == 1000002 and nt == 600000 and (nv + 2047) // 2048 == 489 and (nt + 2047) // 2048 == 293
+    # the expectation by construction: the strip's vertices in ascending (permuted) index, its triangles in input order
+    used = np.zeros(nv, bool)
+    used[perm[:BIG_STRIP + 2]] = True
+    remap = np.cumsum(used) - 1
+    want_tri = remap[tri[in_strip].astype(np.int64)].astype(np.uint32)
+    # what the second round's carry is worth: kept vertices and triangles on both sides of element 524 288
+    assert 10000 < used[:524288].sum() < used.sum() - 10000 and 10000 < in_strip[:524288].sum() < in_strip.sum() - 10000
+    ref = CR.clean(xyz, rgb, tri, 1, normals=nrm)
+    want_info = dict(n_components=200001, largest=400000, kept_components=1, kept_vertices=400002, kept_triangles=400000, n_bad=0)
+    assert ref[4] == want_info
+    assert ref[2].tobytes() == want_tri.tobytes() and ref[0].tobytes() == xyz[used].tobytes()       # the restatement agrees with the construction
+    got = mesh.clean_mesh(xyz, rgb, tri, 1, normals=nrm)
+    assert got[4] == want_info, got[4]
+    for g, r_, name in zip(got[:4], ref[:4], ("xyz", "rgb", "tri", "normals")):
+        assert g.dtype == r_.dtype and g.shape == r_.shape and g.tobytes() == r_.tobytes(), name
+    # min_bp = 0: everything is kept and the compaction is the identity
+    got = mesh.clean_mesh(xyz, rgb, tri, 0, normals=nrm)
+    assert got[4] == dict(n_components=200001, largest=400000, kept_components=200001, kept_vertices=nv, kept_triangles=nt, n_bad=0), got[4]
+    for g, r_, name in zip(got[:4], (xyz, rgb, tri, nrm), ("xyz", "rgb", "tri", "normals")):
+        assert g.dtype == r_.dtype and g.shape == r_.shape and g.tobytes() == r_.tobytes(), name
+
+
 # ---- 3. on an extracted mesh, 4. normals -------------------------------------------------------------------------------------------
 NX, NY, NZ = 24, 16, 16
 ORIGIN, VOXEL = (-1.5, -1.0, -1.0), 0.125
