@@ -256,6 +256,22 @@ _MESH_PROTOS = {
 }
 
 
+# include/dvs_region.h: the focus region (an oriented box): which splats it keeps, which pixels' rays cross it
+class Region(C.Structure):             # dvs_region
+    _fields_ = [("w2b", C.c_float * 12), ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+
+class RegionMaskView(C.Structure):     # dvs_region_mask_view
+    _fields_ = [("cam", Camera), ("in_mask", C.c_void_p), ("out", C.c_void_p)]
+
+
+_REGION_PROTOS = {
+    "dvs_region_from_trs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Region), C.c_void_p]),
+    "dvs_region_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(Region), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_region_mask_views": (C.c_int, [C.c_void_p, C.POINTER(RegionMaskView), C.c_int, C.c_int, C.c_int, C.POINTER(Region)]),
+}
+
+
 def undistort_desc(model, params, width, height):
     """-> UndistortDesc of COLMAP model id 2, 3 or 4 and its parameter list (dvs_undistort_desc_from_colmap); DvsError when refused"""
     prm = (C.c_double * len(params))(*[float(v) for v in params])
@@ -265,7 +281,7 @@ def undistort_desc(model, params, width, height):
     if lib.dvs_undistort_desc_from_colmap(int(model), prm, int(width), int(height), C.byref(d)) != 0:
         raise DvsError(f"dvs_undistort_desc_from_colmap refused model {model}, {width}x{height}, {list(params)}")
     return d
-for _name, (_res, _args) in list(_PROTOS.items()) + list(_EXPORT_PROTOS.items()) + list(_INIT_PROTOS.items()) + list(_IMAGE_PROTOS.items()) + list(_MESH_PROTOS.items()):
+for _name, (_res, _args) in list(_PROTOS.items()) + list(_EXPORT_PROTOS.items()) + list(_INIT_PROTOS.items()) + list(_IMAGE_PROTOS.items()) + list(_MESH_PROTOS.items()) + list(_REGION_PROTOS.items()):
     _f = getattr(lib, _name)          # AttributeError here = the .so does not export a declared symbol
     _f.restype = _res
     _f.argtypes = _args

@@ -4,24 +4,8 @@
 #include "../../include/dvs_train.h"
 #include "../../include/dvs_raster.h"
 #include "dvs_device.h"
+#include "block_scan.h"
 
-#define DB 256
-
-__device__ __forceinline__ uint32_t d_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ uint32_t d_block_excl_scan(uint32_t v, uint32_t* tmp, uint32_t* total) {
-    const uint32_t lane = d_lane(), wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
-    if (lane == 63) tmp[wave] = inc;
-    __syncthreads();
-    uint32_t wbase = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < DB / 64; ++w) { const uint32_t t = tmp[w]; if ((uint32_t)w < wave) wbase += t; tot += t; }
-    __syncthreads();
-    *total = tot;
-    return wbase + inc - v;
-}
 __device__ __forceinline__ int64_t d_shn_index(int layout, int i, int e) {
     return layout == DVS_SHN_TILED ? ((((int64_t)(i >> 6) * 12 + (e >> 2)) * 64 + (i & 63)) * 4 + (e & 3)) : ((int64_t)i * 45 + e);
 }

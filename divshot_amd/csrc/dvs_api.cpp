@@ -643,7 +643,23 @@ int dvs_raster_importance_views(dvs_ctx* c, void* stream, const dvs_opts* opts, 
 // The sky texture behind the splats (sky.hip): separate passes over the saved state, before and after the composite backward; the composite
 // kernels run with bg = 0 and know nothing of it.
 static int check_dL(const float* dL_drgb, const char* who);
-// What both entry points check first; minv [n_views][9] receives, per view, the inverse of rows 0, 1, 3 of proj's 3x3 part (fp64, then rounded).
+// minv [9] <- the inverse of rows 0, 1, 3 of proj's 3x3 part (fp64, then rounded): the pixel ray of pixel_ray.h; false for a singular proj
+extern "C++" bool dvs_pixel_ray_matrix(const dvs_camera* cam, float* minv) {      // (declared in dvs_kernels.h; region.hip calls it too)
+    const int rows[3] = {0, 1, 3};
+    double m[3][3], inv[3][3];
+    for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) m[i][k] = (double)cam->proj[k * 4 + rows[i]];
+    const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                       m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+    if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return false;
+    for (int i = 0; i < 3; ++i)
+        for (int k = 0; k < 3; ++k) {               // inv[i][k] = cofactor(k, i) / det
+            const int r0 = (k + 1) % 3, r1 = (k + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
+            inv[i][k] = (m[r0][c0] * m[r1][c1] - m[r0][c1] * m[r1][c0]) / det;
+        }
+    for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) minv[3 * i + k] = (float)inv[i][k];
+    return true;
+}
+// What both entry points check first; minv [n_views][9] receives, per view, the pixel ray matrix.
 static int check_sky(dvs_ctx* c, const dvs_camera* cams, int n_views, const dvs_sky* sky, const char* who, float* minv) {
     if (!c || !cams || !sky || !sky->tex) return fail(DVS_ERR_INVALID, who, "null argument");
     if ((uintptr_t)sky->tex & 15u) return fail(DVS_ERR_INVALID, who, "the texture must be 16-byte aligned");
@@ -652,18 +668,7 @@ static int check_sky(dvs_ctx* c, const dvs_camera* cams, int n_views, const dvs_
     for (int v = 0; v < n_views; ++v) {
         if (cams[v].bg[0] != 0.f || cams[v].bg[1] != 0.f || cams[v].bg[2] != 0.f)
             return fail(DVS_ERR_INVALID, who, "cams[v].bg must be zero: the sky texture is the background (never both)");
-        const int rows[3] = {0, 1, 3};
-        double m[3][3], inv[3][3];
-        for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) m[i][k] = (double)cams[v].proj[k * 4 + rows[i]];
-        const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
-                           m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
-        if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return fail(DVS_ERR_INVALID, who, "cams[v].proj is singular: no ray per pixel");
-        for (int i = 0; i < 3; ++i)
-            for (int k = 0; k < 3; ++k) {               // inv[i][k] = cofactor(k, i) / det
-                const int r0 = (k + 1) % 3, r1 = (k + 2) % 3, c0 = (i + 1) % 3, c1 = (i + 2) % 3;
-                inv[i][k] = (m[r0][c0] * m[r1][c1] - m[r0][c1] * m[r1][c0]) / det;
-            }
-        for (int i = 0; i < 3; ++i) for (int k = 0; k < 3; ++k) minv[9 * v + 3 * i + k] = (float)inv[i][k];
+        if (!dvs_pixel_ray_matrix(&cams[v], minv + 9 * v)) return fail(DVS_ERR_INVALID, who, "cams[v].proj is singular: no ray per pixel");
     }
     if (!c->fwd.have || n_views != c->fwd.n_views)
         return fail(DVS_ERR_STATE, who, "no matching forward on this context (valid after dvs_raster_forward / _views until the next forward)");

@@ -151,6 +151,10 @@ hipError_t dvs_launch_sky_backward_tex(hipStream_t st, int W, int H, int n_views
 hipError_t dvs_launch_sky_backward_rows(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, int n, const uint32_t* ranges /*canonical (start, end)*/,
                                         const uint32_t* sorted_splat, const float* splat2d, const float* final_T, const uint32_t* n_contrib,
                                         const float* dL_dout, const float* sky_rgb, float* grad_rows, int grad_mode);
+// dvs_api.cpp — minv [9] <- the matrix of pixel_ray.h for `cam` (the inverse of rows 0, 1, 3 of proj's 3x3 part, fp64 then rounded);
+// false for a singular proj. For sky.hip's entry points and region.hip's mask.
+struct dvs_camera;
+bool dvs_pixel_ray_matrix(const dvs_camera* cam, float* minv);
 // A8 kernel variants (dvs_set_backward_variant): same inputs, same 48-B row contract, results equal to fp32 roundoff
 enum { DVS_BWD_BLOCKS = 0 /*per-4x4-block lists, four cursors per wave, 12-value group reduction per step (round 2): kept in the release library as
        the independent-summation-order cross-check of the parity tests*/, DVS_BWD_REDUCE = 1 /*per-quadrant masks, wave-wide reduction tree per visit

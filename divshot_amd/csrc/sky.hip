@@ -3,12 +3,7 @@
 // The composite kernels are untouched: with cam.bg = 0 they leave C(p) and final_T(p), and the passes below add what a background that
 // varies per pixel needs, out(p) = C(p) + final_T(p) s(p), from the state the forward saved (like depth.hip and importance.hip).
 //
-// The ray of pixel (x, y) (centre = the integer index: ndc_x = (2 x + 1) / W - 1) is derived from `proj`, not from tan_fov: the loaders
-// produce cameras with an off-centre principal point (dvs_make_camera_intrinsics: COLMAP's cx, cy; dvs_camera_downscale: a cropped
-// level), and for those (ndc_x tan_fovx, ndc_y tan_fovy, 1) is not the pixel's ray. For a world direction d the clip coordinates are
-// (x, y, w) = M d with M the rows 0, 1, 3 of proj's 3x3 part (the camera centre maps to x = y = w = 0), so d = M^-1 (ndc_x, ndc_y, 1);
-// the host inverts M in fp64 once per view (dvs_api.cpp) and the nine floats arrive as the FIRST kernel parameter, read through the
-// kernarg segment (as ViewBg, render_common.h). For a centred pinhole this is R^T (ndc_x tan_fovx, ndc_y tan_fovy, 1).
+// The ray of pixel (x, y) is pixel_ray.h's (shared with the focus region's mask): d = M^-1 (ndc_x, ndc_y, 1), M^-1 the FIRST kernel parameter.
 // The lookup: u = (atan2(d.x, d.z) / 2 pi + 0.5) Ws - 0.5, v = (asin(d.y / |d|) / pi + 0.5) Hs - 0.5, texel centres at integer (u, v),
 // bilinear, u wrapping modulo Ws, v clamped to [0, Hs - 1]. tests/sky_ref.py restates it in fp64.
 //
@@ -35,22 +30,16 @@
 #include "dvs_device.h"
 #include "dvs_kernels.h"
 #include "render_common.h"
+#include "pixel_ray.h"
 
-struct SkyRays { float m[DVS_MAX_VIEWS][12]; };                 // per view: M^-1 row-major in [0..8] (d_r = m[3 r] nx + m[3 r + 1] ny + m[3 r + 2])
-struct SkyRay { float m[9]; };
-__device__ __forceinline__ SkyRay sky_load_ray(int v) {
-    typedef const __attribute__((address_space(4))) float* KF;
-    const KF f = (KF)__builtin_amdgcn_kernarg_segment_ptr() + (size_t)v * 12;
-    SkyRay r;
-#pragma unroll
-    for (int k = 0; k < 9; ++k) r.m[k] = f[k];
-    return r;
-}
+typedef PixelRays SkyRays;
+typedef PixelRay SkyRay;
+__device__ __forceinline__ SkyRay sky_load_ray(int v) { return pixel_ray_load(v); }
 
 struct SkyTap { int i00, i01, i10, i11; float w00, w01, w10, w11; };      // texel indices (y Ws + x) and bilinear weights
 __device__ __forceinline__ SkyTap sky_tap(const SkyRay& r, int x, int y, int W, int H, int Ws, int Hs) {
-    const float nx = (float)(2 * x + 1) / (float)W - 1.0f, ny = (float)(2 * y + 1) / (float)H - 1.0f;
-    const float dx = (r.m[0] * nx + r.m[1] * ny) + r.m[2], dy = (r.m[3] * nx + r.m[4] * ny) + r.m[5], dz = (r.m[6] * nx + r.m[7] * ny) + r.m[8];
+    float dx, dy, dz;
+    pixel_ray_dir(r, x, y, W, H, dx, dy, dz);
     const float len = sqrtf((dx * dx + dy * dy) + dz * dz);
     const float sy = fminf(1.0f, fmaxf(-1.0f, dy / len));
     const float u = (atan2f(dx, dz) * 0.15915494309189535f + 0.5f) * (float)Ws - 0.5f;
@@ -252,11 +241,7 @@ k_sky_backward_rows(int W, int H, int tiles_x, int tiles_per_view, int num_tiles
     }
 }
 
-static SkyRays make_sky_rays(int n_views, const float* minv /*[n_views][9]*/) {
-    SkyRays r{};
-    for (int v = 0; v < n_views && v < DVS_MAX_VIEWS; ++v) for (int k = 0; k < 9; ++k) r.m[v][k] = minv[9 * v + k];
-    return r;
-}
+static SkyRays make_sky_rays(int n_views, const float* minv /*[n_views][9]*/) { return make_pixel_rays(n_views, minv); }
 
 hipError_t dvs_launch_sky_forward(hipStream_t st, int W, int H, int n_views, const float* minv, const float* tex, int Ws, int Hs, const float* final_T,
                                   float* out_rgb, float* sky_rgb) {

@@ -59,7 +59,12 @@ static std::map<std::string, std::string> g_opts = {
     // the reference's config field enableBg ("Create Sky Model"; its CLI has no flag for it): --enableBg 1 trains an equirectangular sky
     // texture behind the splats and writes <outputPath>_<it>.sky at every save. --skyResolution Hs (default 128, clamped to 16..1024) is the
     // texture's height, its width 2 Hs; the config struct has no room left: it is handed to the plugin as DVS_SKY_RESOLUTION.
-    {"enableBg", "0"}, {"skyResolution", "128"}};
+    {"enableBg", "0"}, {"skyResolution", "128"},
+    // the reference's config field enableFocusRegion (its CLI has no flag for it; the editor's "Focus Region"): --enableFocusRegion 1 keeps and
+    // trains only the splats inside an oriented box. --focusRegion x0,y0,z0,x1,y1,z1 is the box (default: the bounds of the initial splat
+    // centres), --focusRotation rx,ry,rz turns it about the origin (Euler angles in radians, as the editor's). The config struct has no room
+    // left: the two are handed to the plugin as DVS_FOCUS_REGION / DVS_FOCUS_ROTATION.
+    {"enableFocusRegion", "0"}, {"focusRegion", ""}, {"focusRotation", ""}};
 static std::map<std::string, bool> g_given;
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
@@ -112,6 +117,21 @@ int main(int argc, const char* argv[]) {
         const std::string& v = g_opts["skyResolution"];
         if (v.empty() || v.size() > 5 || v.find_first_not_of("0123456789") != std::string::npos) { std::cout << "Command Line Error: --skyResolution takes a texture height (16..1024), not '" << v << "'\n"; return 1; }
         setenv("DVS_SKY_RESOLUTION", v.c_str(), 1);                         // before the plugin is loaded
+    }
+    if (g_opts["enableFocusRegion"] != "0" && g_opts["enableFocusRegion"] != "1") { std::cout << "Command Line Error: --enableFocusRegion takes 0 or 1, not '" << g_opts["enableFocusRegion"] << "'\n"; return 1; }
+    if (g_given.count("focusRegion")) {
+        const std::string& v = g_opts["focusRegion"];
+        float b[6]; char tail = 0;
+        if (sscanf(v.c_str(), "%f,%f,%f,%f,%f,%f%c", &b[0], &b[1], &b[2], &b[3], &b[4], &b[5], &tail) != 6 || !(b[3] > b[0] && b[4] > b[1] && b[5] > b[2])) {
+            std::cout << "Command Line Error: --focusRegion takes x0,y0,z0,x1,y1,z1 with x1 > x0, y1 > y0, z1 > z0, not '" << v << "'\n"; return 1;
+        }
+        setenv("DVS_FOCUS_REGION", v.c_str(), 1);                           // before the plugin is loaded
+    }
+    if (g_given.count("focusRotation")) {
+        const std::string& v = g_opts["focusRotation"];
+        float r[3]; char tail = 0;
+        if (sscanf(v.c_str(), "%f,%f,%f%c", &r[0], &r[1], &r[2], &tail) != 3) { std::cout << "Command Line Error: --focusRotation takes rx,ry,rz (radians), not '" << v << "'\n"; return 1; }
+        setenv("DVS_FOCUS_ROTATION", v.c_str(), 1);
     }
     // plugin: "libgstrain.so" next to the executable (plugin.cpp:74 builds parent_path / "lib<name>.so")
     std::error_code ec;
@@ -190,6 +210,7 @@ int main(int argc, const char* argv[]) {
         train_config.importancePrune = (uint8_t)atoi(ip.c_str());
     }
     train_config.enableBg = g_opts["enableBg"] == "1";
+    train_config.enableFocusRegion = g_opts["enableFocusRegion"] == "1";
     train_config.normalConsistencyLoss = false;
     if (train_config.exportMesh) { train_config.normalConsistencyLoss = true; train_config.useMask = true; }
     train_config.verbose = true;

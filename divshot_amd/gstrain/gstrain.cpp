@@ -57,6 +57,7 @@ bool GaussianTrainerScene::loadTrainData(const std::string& path) {
         if (synthetic || std::filesystem::is_directory(path, ec)) {
             if (!(synthetic ? m.load_synthetic(path) : m.load_dataset(path))) { m.status = TrainingStatus::Loading_Failed; return false; }
             m.status = TrainingStatus::Preprocess_Done;
+            focus_region_rotation.x = m.focus_trs[3]; focus_region_rotation.y = m.focus_trs[4]; focus_region_rotation.z = m.focus_trs[5];   // (DVS_FOCUS_ROTATION)
             trainSetup();
             return true;
         }
@@ -79,6 +80,10 @@ void GaussianTrainerScene::trainStep() {
     Impl& m = *impl_;
     if (!m.ctx || m.cams.empty()) throw std::runtime_error("trainStep before loadTrainData");
     HIP_OR_THROW(hipSetDevice(m.device));
+    // focus region: the editor flips the flag in the config itself, so a change shows only here. While the flag is off both tests are
+    // false and nothing happens; the prune runs before plan_step(), which takes the arrays' addresses and the splat count.
+    if (m.cfg.enableFocusRegion != m.region_flag_seen) { m.region_flag_seen = m.cfg.enableFocusRegion; m.region_dirty = true; }
+    if (m.cfg.enableFocusRegion && m.region_dirty) m.prune_region(m.step + 1);
     Impl::Step s = m.plan_step();
     if (m.res_every > 0) m.enter_level(s);
     m.lw = s.Wd; m.lh = s.Hd;
@@ -90,10 +95,14 @@ void GaussianTrainerScene::trainStep() {
     else if (m.exchange_factorised()) m.finish_range(s, 0, m.n, kGeomGroups, 4, s.adam_gate);     // (the SH groups were stepped in exchange())
     else m.finish_range(s, 0, m.n, kAllGroups, 6, s.adam_gate);
     m.step_sky(s);                                                          // (nothing when enableBg is off)
-    if (s.refine_now) { if (s.mcmc) m.densify_mcmc(s.it); else m.densify(s.it); }
+    if (s.refine_now) {
+        if (m.cfg.enableFocusRegion) m.prune_region(s.it);                   // (MCMC: relocation draws from inside splats only)
+        if (s.mcmc) m.densify_mcmc(s.it); else m.densify(s.it);
+    }
     if (s.reset_now)
         DVS_OR_THROW(dvs_reset_opacity(m.stream.get(), m.n, m.d_param[P_OPA].get(), 0.01f, m.d_m[P_OPA].get(), m.d_v[P_OPA].get()));
     if (s.prune_now) {
+        if (m.cfg.enableFocusRegion) m.prune_region(s.it);
         m.prune_light(s.it);
         m.prune_importance(s.it);                                            // (nothing when importancePrune is 0)
         pruenIteraions.push_back(s.it);
@@ -110,6 +119,7 @@ void GaussianTrainerScene::trainStep() {
 
 void GaussianTrainerScene::saveGaussianModel() {
     Impl& m = *impl_;
+    if (m.cfg.enableFocusRegion && m.ctx) m.prune_region(m.step);           // what is written holds inside splats only (every rank: the replicas stay identical)
     // the replicas are identical: one file — unless DVS_SAVE_ALL_RANKS=1 asks every rank for its own (<model>_<it>.ply.rank<r>), which
     // is how the two-rank test checks that they ARE identical, bit for bit
     static const bool all_ranks = env_is("DVS_SAVE_ALL_RANKS", "1");
@@ -196,6 +206,7 @@ void GaussianTrainerScene::resetGaussian() {
     m.reset_stats();
     m.step = 0; curIteration = 0; pruenIteraions.clear();
     m.eval_it = -1;
+    m.region_dirty = true;                                                  // (the initial splats are all back: the next step prunes them again)
     m.cur_level = -1; m.lw = m.W; m.lh = m.H;
     m.host_valid = false;
     (void)dvs_raster_forward_cancel_prepared(m.ctx.get());          // (a pipelined step may have projected the next iteration's splats already)
@@ -209,7 +220,25 @@ void GaussianTrainerScene::setModelPath(const std::string& path) {
     if (impl_->export_formats() != before) impl_->report_config();         // the editor's "Splat Format" arrives as the suffix of the path
 }
 void GaussianTrainerScene::updateFocusRegion(const dvs_types::Vec3& position, const dvs_types::Vec3& rotation, const dvs_types::Vec3& scale) {
-    focus_region_position = position; focus_region_rotation = rotation; focus_region_scale = scale;     // stored; enableFocusRegion is not used by the trainer
+    // F = T(position) R(rotation) S(scale), the editor's own maths::Transform (include/dvs_region.h); a zero scale component is refused with
+    // a log line and the previous region stays, in the public fields too. The next trainStep() prunes to the new region.
+    const float pos[3] = {position.x, position.y, position.z}, rot[3] = {rotation.x, rotation.y, rotation.z}, sc[3] = {scale.x, scale.y, scale.z};
+    if (!impl_->set_region(pos, rot, sc)) return;
+    focus_region_position = position; focus_region_rotation = rotation; focus_region_scale = scale;
+}
+// (lo, hi) of the region in ITS OWN coordinates and F, box-local -> world: the editor draws F applied to the box's twelve edges
+// (scene_view_panel.cpp:1393-1415)
+std::pair<dvs_types::Vec3, dvs_types::Vec3> GaussianTrainerScene::getFocusRegion() const {
+    dvs_types::Vec3 a{}, b{};
+    a.x = impl_->focus_lo[0]; a.y = impl_->focus_lo[1]; a.z = impl_->focus_lo[2];
+    b.x = impl_->focus_hi[0]; b.y = impl_->focus_hi[1]; b.z = impl_->focus_hi[2];
+    return {a, b};
+}
+dvs_types::Mat4 GaussianTrainerScene::getFocusRegionTransform() const {
+    dvs_types::Mat4 F{};
+    float* o = reinterpret_cast<float*>(&F);
+    for (int c = 0; c < 4; ++c) for (int r = 0; r < 4; ++r) o[c * 4 + r] = impl_->region_b2w[r * 4 + c];      // column-major
+    return F;
 }
 std::string GaussianTrainerScene::getCurrentTrainingPhaseName() const {
     switch (impl_->status) {

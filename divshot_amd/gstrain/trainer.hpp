@@ -1,7 +1,7 @@
 // trainer.hpp — GaussianTrainerScene::Impl, the state behind `libgstrain.so`, and what its source files share. The members are defined
 // in trainer_load.cpp (loaders, allocation), trainer_step.cpp (one trainStep), trainer_refine.cpp (densification, pruning),
 // trainer_output.cpp (configuration report, evaluation, export), trainer_render.cpp (rendered views as JPEG files) and trainer_mesh.cpp
-// (mesh export); gstrain.cpp holds
+// (mesh export); the focus region's members sit beside the code they feed (trainer_step.cpp, trainer_refine.cpp); gstrain.cpp holds
 // the GaussianTrainerScene members and the C symbols.
 #pragma once
 #include <algorithm>
@@ -20,6 +20,7 @@
 #include "../../include/dvs_train.h"
 #include "../../include/dvs_export.h"
 #include "../../include/dvs_init.h"
+#include "../../include/dvs_region.h"
 #include "device_mem.hpp"
 #include "ply_io.hpp"
 #include "dataset_io.hpp"
@@ -203,6 +204,22 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         DVS_OR_THROW(dvs_sky_forward_views(c, stream.get(), bc, nb, &s, out, nullptr));
     }
 
+    // focus region (cfg.enableFocusRegion, which the editor flips live; INTEGRATION.md "Focus region"): the box (focus_lo, focus_hi) is fixed
+    // at load — the bounds of the initial centres, or DVS_FOCUS_REGION — and updateFocusRegion() moves it through F = T R S (include/dvs_region.h).
+    // While the flag is on, splats whose centre is outside are removed (prune_region) and the loss and the evaluation see only the pixels
+    // whose ray crosses the box (region_masks). While it is off nothing below is allocated, launched or written by a step.
+    float focus_lo[3] = {0.f, 0.f, 0.f}, focus_hi[3] = {0.f, 0.f, 0.f};
+    float focus_trs[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f};       // position, rotation (radians), scale of the region in force
+    dvs_region region{};
+    float region_b2w[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // F, row-major
+    bool region_dirty = false;                                               // the region or the flag changed since the last region prune
+    bool region_flag_seen = false;                                           // cfg.enableFocusRegion as the last trainStep saw it
+    DevBuf<float> d_region_mask;                                             // [max(vpi, 8), H, W]: a step's or an evaluation pass's masks; allocated at the first use
+    void setup_region();
+    bool set_region(const float* pos, const float* rot, const float* scale);
+    void prune_region(int it);
+    const float* region_masks(const dvs_camera* bc, const float* const* in, int nb, int w, int h);
+
     ~Impl() { if (device >= 0) (void)hipSetDevice(device); }                // (the members release themselves, after this body)
     // floats of group g on the device: the 45 higher-order SH floats live in the DVS_SHN_TILED layout (48 per splat,
     // whole 64-splat tiles); parameters, gradients and Adam moments share it — the optimizer is element-wise.
@@ -270,6 +287,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         bool refine_now = false, reset_now = false, prune_now = false;
         float lr_pos = 0.f;
         dvs_adam_group adam[6] = {};                                         // Adam groups over the whole arrays
+        const float* region_mask = nullptr;                                  // (render_backward) enableFocusRegion: the step's masks [vpi, Hd, Wd]
         const int* adam_gate = nullptr;                                      // (render_backward) visible-only Adam: radius > 0 in the step's views
         int chunk_per = 0, n_chunks = 0;                                     // (render_backward) > 0: the geometry gradients left behind A9 in chunks
     };

@@ -242,8 +242,11 @@ void GaussianTrainerScene::Impl::finish_load(const std::function<void(std::vecto
     if (!resumed) fresh_init(init);
     for (int g = 0; g < 6; ++g) { upload(g, init[g]); init_host[g] = init[g]; }
     setup_sky(resumed);
+    setup_region();
     report_config();
     describe(resumed);
+    if (cfg.enableFocusRegion) prune_region(step);
+    region_dirty = false;
     if (exchange_factorised()) setup_exchange();
 }
 

@@ -35,7 +35,7 @@ int GaussianTrainerScene::Impl::mesh_min_bp() const {
 }
 bool GaussianTrainerScene::Impl::mesh_normals() const { return mesh_normals_set >= 0 ? mesh_normals_set != 0 : env_is("DVS_MESH_NORMALS", "1"); }
 
-// The box the grid covers: DVS_MESH_BOUNDS=x0,y0,z0,x1,y1,z1, or the box of the centres of the splats with sigmoid(opacity) >= 0.5
+// The box the grid covers: DVS_MESH_BOUNDS=x0,y0,z0,x1,y1,z1, or with enableFocusRegion the focus region's world bounds, or the box of the centres of the splats with sigmoid(opacity) >= 0.5
 // cut to the cube of half-side 3 x extent about the camera centroid (extent: the scene extent the prune rules use).
 bool GaussianTrainerScene::Impl::mesh_bounds(float lo[3], float hi[3]) {
     if (const char* e = getenv("DVS_MESH_BOUNDS")) {
@@ -45,6 +45,17 @@ bool GaussianTrainerScene::Impl::mesh_bounds(float lo[3], float hi[3]) {
             return true;
         }
         logf_("mesh: DVS_MESH_BOUNDS='%s' is not x0,y0,z0,x1,y1,z1 with x1 > x0, y1 > y0, z1 > z0: ignored", e);
+    }
+    if (cfg.enableFocusRegion) {            // the world axis-aligned bounds of the region's eight corners
+        for (int k = 0; k < 3; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; }
+        for (int c = 0; c < 8; ++c) {
+            const float b[3] = {(c & 1) ? focus_hi[0] : focus_lo[0], (c & 2) ? focus_hi[1] : focus_lo[1], (c & 4) ? focus_hi[2] : focus_lo[2]};
+            for (int k = 0; k < 3; ++k) {
+                const float w = region_b2w[4 * k] * b[0] + region_b2w[4 * k + 1] * b[1] + region_b2w[4 * k + 2] * b[2] + region_b2w[4 * k + 3];
+                lo[k] = std::min(lo[k], w); hi[k] = std::max(hi[k], w);
+            }
+        }
+        return hi[0] > lo[0] && hi[1] > lo[1] && hi[2] > lo[2];
     }
     fetch_host();
     double centre[3] = {0, 0, 0};

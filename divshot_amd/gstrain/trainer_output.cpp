@@ -52,13 +52,19 @@ void GaussianTrainerScene::Impl::report_config() const {
         logf_("config: skyModel %dx%d: enableBg — an equirectangular fp32 texture behind the splats, looked up along each pixel's ray and trained with "
               "them (Adam, lr %g); every save also writes <modelPath>_<it>.sky; evaluation and written renders composite it; mesh export, the "
               "importance score and the depth pass do not see it", 2 * sky_h, sky_h, (double)sky_lr);
+    if (cfg.enableFocusRegion)
+        logf_("config: focusRegion box %.9g,%.9g,%.9g .. %.9g,%.9g,%.9g under F = T(%g,%g,%g) R(%g,%g,%g rad, Rz Ry Rx) S(%g,%g,%g): a splat stays while "
+              "its centre p has lo <= F^-1 p <= hi (faces included, extents not considered; pruned after load, when the region changes, before every "
+              "refinement, prune and save); the loss and the evaluation see only the pixels whose ray crosses the box; mesh export takes its world bounds",
+              (double)focus_lo[0], (double)focus_lo[1], (double)focus_lo[2], (double)focus_hi[0], (double)focus_hi[1], (double)focus_hi[2],
+              (double)focus_trs[0], (double)focus_trs[1], (double)focus_trs[2], (double)focus_trs[3], (double)focus_trs[4], (double)focus_trs[5],
+              (double)focus_trs[6], (double)focus_trs[7], (double)focus_trs[8]);
     std::string ign;
     if (cfg.modelType != 0) ign += " modelType(only 3DGS)";
     if (cfg.cullSH) ign += " cullSH";
     if (cfg.pixelGradScale) ign += " pixelGradScale";
     if (cfg.bestQuality) ign += " bestQuality";
     if (cfg.normalConsistencyLoss) ign += " normalConsistencyLoss(2DGS)";
-    if (cfg.enableFocusRegion) ign += " enableFocusRegion";
     if (cfg.exportMesh) ign += " exportMesh";
     if (cfg.outputSparsePoints) ign += " outputSparsePoints";
     if (cfg.maxImageCount) ign += " maxImageCount";
@@ -114,6 +120,12 @@ void GaussianTrainerScene::Impl::score_views(const dvs_splats& sp, std::vector<d
             mv[k].img = d_eval_out.get() + (size_t)k * img;
             mv[k].target = view_pixels(ci);
             mv[k].mask = view_mask(ci);
+        }
+        if (cfg.enableFocusRegion) {        // what the loss saw: the camera's mask x the region's hit
+            const float* in[DVS_METRICS_MAX_VIEWS];
+            for (int k = 0; k < nb; ++k) in[k] = mv[k].mask;
+            const float* rm = region_masks(bc.data(), in, nb, W, H);
+            for (int k = 0; k < nb; ++k) mv[k].mask = rm + (size_t)k * W * H;
         }
         DVS_OR_THROW(dvs_raster_forward_views(eval_ctx.get(), stream.get(), &sp, bc.data(), nb, &opts, d_eval_out.get()));
         composite_sky(eval_ctx.get(), bc.data(), nb, d_eval_out.get());     // what was trained: the sky behind the splats

@@ -1,5 +1,5 @@
 // trainer_refine.cpp — what changes the number of splats between two iterations: ADC / ADC+ densification, MCMC relocation, light prune,
-// importance prune.
+// importance prune, focus-region prune.
 #include "trainer.hpp"
 
 namespace {
@@ -114,6 +114,32 @@ void GaussianTrainerScene::Impl::prune_light(int it) {
         HIP_OR_THROW(hipMemsetAsync(d_grad_flat.get(), 0, grad_floats * sizeof(float), stream.get()));
         host_valid = false;
     }
+    pruning = false;
+}
+
+// enableFocusRegion: the splats whose centre lies outside the region go (dvs_region_plan: extents are not looked at, a NaN centre is
+// outside), the arrays and both Adam moments are compacted through the plan -> apply path, the gradients and the densification
+// statistics start again as after an importance prune. Called right after load, at the start of the first trainStep() after the
+// region or the flag changed, before every refinement (ADC and MCMC: relocation then draws from inside splats only), at every prune
+// occasion before the light prune, and before every save. A plan that would leave no splat is logged and not applied. A pure function
+// of the replicated positions and the region: every rank removes the same splats, no communication.
+void GaussianTrainerScene::Impl::prune_region(int it) {
+    region_dirty = false;
+    if (n <= 0) return;
+    uint64_t new_n = 0;
+    DVS_OR_THROW(dvs_region_plan(stream.get(), n, d_param[P_POS].get(), &region, d_action.get(), d_offsets.get(), d_dscratch.get(), d_newcount.get()));
+    HIP_OR_THROW(hipMemcpyAsync(&new_n, d_newcount.get(), 8, hipMemcpyDeviceToHost, stream.get()));
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    if (new_n == 0) { if (rank == 0) logf_("region prune @%d: none of the %d splats lies inside the focus region: nothing removed", it, n); return; }
+    if (new_n >= (uint64_t)n) return;
+    pruning = true;
+    apply_plan(plan_params(it), (int)new_n, false);
+    HIP_OR_THROW(hipMemsetAsync(d_grad_flat.get(), 0, grad_floats * sizeof(float), stream.get()));
+    reset_stats();
+    (void)dvs_raster_forward_cancel_prepared(ctx.get());                   // (a pipelined step may have projected the next iteration's splats already)
+    if (cfg.verbose && rank == 0) logf_("region prune @%d: %d -> %llu splats", it, n, (unsigned long long)new_n);
+    n = (int)new_n;
+    host_valid = false;
     pruning = false;
 }
 

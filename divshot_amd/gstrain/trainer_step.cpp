@@ -116,11 +116,66 @@ void GaussianTrainerScene::Impl::loss_of_view(const Step& s, int v) {
     } else {
         DVS_OR_THROW(dvs_l1_loss_grad_w(stream.get(), out, target, img, 1.f, dL, d_loss.get()));
     }
-    if (const float* mask = view_mask((size_t)ci)) {
-        const size_t P = (size_t)W * H;
-        hipLaunchKernelGGL(k_mask_mul, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, stream.get(), dL,
-                           s.level > 0 ? d_level_masks.get() + (size_t)v * P : mask, P);
+    const size_t P = (size_t)W * H;
+    const float* mask = view_mask((size_t)ci);
+    if (mask && s.level > 0) mask = d_level_masks.get() + (size_t)v * P;
+    if (s.region_mask) mask = s.region_mask + (size_t)v * P;                // (the camera's mask x the region's hit)
+    if (mask) hipLaunchKernelGGL(k_mask_mul, dim3((unsigned)((3 * P + 255) / 256)), dim3(256), 0, stream.get(), dL, mask, P);
+}
+
+// ---- focus region ----
+// The box of the region: DVS_FOCUS_REGION=x0,y0,z0,x1,y1,z1 (--focusRegion), or the axis-aligned bounds of the initial centres; the
+// initial rotation DVS_FOCUS_ROTATION=rx,ry,rz (--focusRotation; radians, as updateFocusRegion's). Malformed values are reported once
+// (this runs once, at load) and ignored.
+void GaussianTrainerScene::Impl::setup_region() {
+    for (int k = 0; k < 3; ++k) { focus_lo[k] = INFINITY; focus_hi[k] = -INFINITY; }
+    const std::vector<float>& p = init_host[P_POS];
+    for (size_t i = 0; i + 2 < p.size(); i += 3) {
+        if (!(std::isfinite(p[i]) && std::isfinite(p[i + 1]) && std::isfinite(p[i + 2]))) continue;
+        for (int k = 0; k < 3; ++k) { focus_lo[k] = std::min(focus_lo[k], p[i + k]); focus_hi[k] = std::max(focus_hi[k], p[i + k]); }
     }
+    for (int k = 0; k < 3; ++k) if (!(focus_hi[k] >= focus_lo[k])) focus_lo[k] = focus_hi[k] = 0.f;      // (no finite centre)
+    if (const char* e = getenv("DVS_FOCUS_REGION")) {
+        float v[6]; char tail = 0;
+        if (sscanf(e, "%f,%f,%f,%f,%f,%f%c", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &tail) == 6 && v[3] > v[0] && v[4] > v[1] && v[5] > v[2] &&
+            std::all_of(v, v + 6, [](float f) { return std::isfinite(f); }))
+            for (int k = 0; k < 3; ++k) { focus_lo[k] = v[k]; focus_hi[k] = v[3 + k]; }
+        else logf_("focus region: DVS_FOCUS_REGION='%s' is not x0,y0,z0,x1,y1,z1 with x1 > x0, y1 > y0, z1 > z0: ignored", e);
+    }
+    float rot[3] = {0.f, 0.f, 0.f};
+    if (const char* e = getenv("DVS_FOCUS_ROTATION")) {
+        float v[3]; char tail = 0;
+        if (sscanf(e, "%f,%f,%f%c", &v[0], &v[1], &v[2], &tail) == 3 && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]))
+            for (int k = 0; k < 3; ++k) rot[k] = v[k];
+        else logf_("focus region: DVS_FOCUS_ROTATION='%s' is not rx,ry,rz (radians): ignored", e);
+    }
+    const float zero[3] = {0.f, 0.f, 0.f}, one[3] = {1.f, 1.f, 1.f};
+    set_region(zero, rot, one);
+    region_flag_seen = cfg.enableFocusRegion;
+}
+// -> false (with a log line, the previous region stays) when dvs_region_from_trs refuses the vectors: a zero or non-finite scale
+bool GaussianTrainerScene::Impl::set_region(const float* pos, const float* rot, const float* scale) {
+    dvs_region r; float b2w[16];
+    if (dvs_region_from_trs(pos, rot, scale, focus_lo, focus_hi, &r, b2w) != DVS_OK) {
+        logf_("focus region: position %g,%g,%g rotation %g,%g,%g scale %g,%g,%g refused (every scale component must be finite and not zero): the "
+              "previous region stays", (double)pos[0], (double)pos[1], (double)pos[2], (double)rot[0], (double)rot[1], (double)rot[2], (double)scale[0],
+              (double)scale[1], (double)scale[2]);
+        return false;
+    }
+    region = r;
+    memcpy(region_b2w, b2w, sizeof b2w);
+    for (int k = 0; k < 3; ++k) { focus_trs[k] = pos[k]; focus_trs[3 + k] = rot[k]; focus_trs[6 + k] = scale[k]; }
+    region_dirty = true;
+    return true;
+}
+// the masks of nb views of w x h: out[k] = in[k] x (the ray of the pixel crosses the region), in[k] = nullptr: all ones. ONE launch
+// (dvs_region_mask_views) into d_region_mask; what it returns is valid until the next call.
+const float* GaussianTrainerScene::Impl::region_masks(const dvs_camera* bc, const float* const* in, int nb, int w, int h) {
+    if (!d_region_mask) d_region_mask.alloc((size_t)std::max(vpi, 8) * (size_t)W * H * sizeof(float) + 16);
+    dvs_region_mask_view mv[DVS_REGION_MAX_VIEWS] = {};
+    for (int k = 0; k < nb; ++k) { mv[k].cam = bc[k]; mv[k].in_mask = in[k]; mv[k].out = d_region_mask.get() + (size_t)k * w * h; }
+    if (dvs_region_mask_views(stream.get(), mv, nb, w, h, &region) != DVS_OK) throw std::runtime_error("dvs_region_mask_views refused the step's views");
+    return d_region_mask.get();
 }
 
 // forward, loss, composite backward, statistics and A9 of the step's views: ONE multi-view pass (parameters read once, one depth sort /
@@ -134,6 +189,12 @@ void GaussianTrainerScene::Impl::render_backward(Step& s) {
     const size_t img = 3 * (size_t)W * H;
     hipStream_t const st = stream.get(), cst = comm_stream.get();
     if (s.level > 0) level_targets(s);
+    if (cfg.enableFocusRegion) {            // the step's masks: the camera's (at the step's level) x the region's hit, from the level's own camera
+        const float* in[DVS_REGION_MAX_VIEWS] = {};
+        for (int v = 0; v < vpi; ++v)
+            if (const float* mask = view_mask((size_t)s.ci_all[(size_t)rank * vpi + v])) in[v] = s.level > 0 ? d_level_masks.get() + (size_t)v * W * H : mask;
+        s.region_mask = region_masks(s.vcams.data(), in, vpi, W, H);
+    }
     dvs_opts opts = s.opts;
     dvs_splat_grads g{};
     g.pos = d_grad[P_POS]; g.sh0 = d_grad[P_SH0]; g.shN = d_grad[P_SHN]; g.opacity = d_grad[P_OPA];

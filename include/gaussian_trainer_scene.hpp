@@ -18,6 +18,7 @@
 #include <cstdint>
 #include <memory>
 #include <string>
+#include <utility>
 #include <vector>
 
 enum GSPackLevel : int { PackF32ToU8 = 1, PackTileID = 2 };   // bit flags (gs_train.cpp:91-96)
@@ -138,6 +139,13 @@ public:
     void setDensifyStrategy(int strategy);            // inspector_panel.cpp:789 (0 ADC / 1 MCMC / 2 ADC+)
     void setModelPath(const std::string& path);       // editor.cpp:2024
     void updateFocusRegion(const dvs_types::Vec3& position, const dvs_types::Vec3& rotation, const dvs_types::Vec3& scale);   // inspector_panel.cpp:933
+    // The focus region (config enableFocusRegion; INTEGRATION.md "Focus region"): (lo, hi) of the box in its own coordinates — fixed at load
+    // to the bounds of the initial splat centres, or what DVS_FOCUS_REGION says — and F = T(position) R(rotation) S(scale), box -> world, of
+    // the last updateFocusRegion() that was accepted (rotation: Euler angles in radians, R = Rz Ry Rx, as the editor's maths::Transform:
+    // diverse/source/maths/transform.cpp:129). The editor draws F applied to the box (scene_view_panel.cpp:1393-1415). While the flag is
+    // on the trainer keeps the splats whose centre p has lo <= F^-1 p <= hi and trains on the pixels whose ray crosses the box.
+    std::pair<dvs_types::Vec3, dvs_types::Vec3> getFocusRegion() const;     // scene_view_panel.cpp:1393
+    dvs_types::Mat4 getFocusRegionTransform() const;                        // scene_view_panel.cpp:1394
     std::string getCurrentTrainingPhaseName() const;  // inspector_panel.cpp:997
     float getProgressOnCurrentPhase() const;          // inspector_panel.cpp:999, scene_view_panel.cpp:1022 (0..1)
     double getEstimateTrainingTime() const;           // inspector_panel.cpp:998: remaining seconds at the current rate
