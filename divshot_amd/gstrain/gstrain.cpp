@@ -139,8 +139,7 @@ void GaussianTrainerScene::saveGaussianModel() {
     if (m.rank == 0 && m.export_formats()) {                                // the comparison for the compact exports' lines below
         std::error_code fec;
         const auto ply_bytes = std::filesystem::file_size(file, fec);
-        logf_("export @%d: ply %d splats, %llu bytes, %.2f ms", m.step, m.n, (unsigned long long)(fec ? 0 : ply_bytes),
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_save).count());
+        logf_("export @%d: ply %d splats, %llu bytes, %.2f ms", m.step, m.n, (unsigned long long)(fec ? 0 : ply_bytes), ms_since(t_save));
     }
     if (m.rank == 0)
         for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT, (int)Impl::EXPORT_SPZ})

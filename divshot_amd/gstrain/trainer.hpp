@@ -1,8 +1,8 @@
 // trainer.hpp — GaussianTrainerScene::Impl, the state behind `libgstrain.so`, and what its source files share. The members are defined
 // in trainer_load.cpp (loaders, allocation), trainer_step.cpp (one trainStep), trainer_refine.cpp (densification, pruning),
-// trainer_output.cpp (configuration report, evaluation, export), trainer_render.cpp (rendered views as JPEG files) and trainer_mesh.cpp
-// (mesh export); the focus region's members sit beside the code they feed (trainer_step.cpp, trainer_refine.cpp); gstrain.cpp holds
-// the GaussianTrainerScene members and the C symbols.
+// trainer_output.cpp (configuration report, the evaluation context and its pass loop, evaluation, export), trainer_render.cpp (rendered
+// views as JPEG files) and trainer_mesh.cpp (mesh export); the focus region's members sit beside the code they feed (trainer_step.cpp,
+// trainer_refine.cpp); gstrain.cpp holds the GaussianTrainerScene members and the C symbols.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -44,6 +44,7 @@ __attribute__((format(printf, 1, 2))) inline void logf_(const char* fmt, ...) {
 // the DVS_* environment overrides: the integer value of `name` (atoi) or `fallback` when it is not set; whether it is set to `value`
 inline int env_int(const char* name, int fallback) { const char* e = getenv(name); return e ? atoi(e) : fallback; }
 inline bool env_is(const char* name, const char* value) { const char* e = getenv(name); return e && std::string_view(e) == value; }
+inline double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
 }  // namespace
 
 struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     // the class is exported (GSTRAIN_API), its implementation is not
@@ -121,6 +122,28 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     std::vector<int> train_idx, test_idx;
     int eval_views = 0;                                                      // min(n_test, 8) views per pass of eval_ctx
     DevBuf<float> d_eval_out; DevBuf<void> d_eval_scratch; DevBuf<double> d_eval_res;
+    // Everything that renders through eval_ctx does it here (trainer_output.cpp): the cameras `which` of `sp` (DVS_SHN_TILED, at most
+    // `cap` splats) in list order, eval_views per pass, with eval_opts() — one dvs_raster_forward_views into d_eval_out per pass, then
+    // composite_sky when with_sky, then per_pass; nothing else is launched and nothing waits. per_pass runs before the next forward, so
+    // it is where the context's saved forward state is consumed (dvs_raster_depth_views, dvs_raster_importance_views).
+    //   caller            cameras             sky   masks
+    //   score_views       test_idx            yes   view_mask x region_masks (enableFocusRegion), made in per_pass: only the metric reads them
+    //   render_to_jpeg    what is asked for   yes   none
+    //   extract_mesh      training_cameras()  no    view_mask
+    //   prune_importance  training_cameras()  no    view_mask
+    struct EvalPass { int first, nb; const int* cam; const dvs_camera* cams; const float* images; };   // views which[first .. first + nb): their indices
+                                                                             // (&which[first]), their cameras [nb], d_eval_out [nb][3][H][W]
+    void for_each_eval_pass(const dvs_splats& sp, const std::vector<int>& which, bool with_sky, const std::function<void(const EvalPass&)>& per_pass);
+    dvs_opts eval_opts() const {                                             // full SH degree, what a viewer shows from the saved PLY
+        dvs_opts o{};
+        o.sh_degree = sh_max; o.antialias = cfg.mipAntiliased ? 1 : 0; o.shn_layout = DVS_SHN_TILED; o.tile_bounds = DVS_TILES_CANONICAL;
+        return o;
+    }
+    std::vector<int> training_cameras() const {                              // train_idx, or every camera when nothing is held out
+        std::vector<int> v = train_idx;
+        if (v.empty()) for (int c = 0; c < (int)cams.size(); ++c) v.push_back(c);
+        return v;
+    }
     std::vector<double> eval_res;                                            // [n_test][4] = {mse, l1, ssim, psnr} of the last evaluation
     double eval_mean[4] = {NAN, NAN, NAN, NAN};
     int eval_it = -1;
@@ -136,25 +159,25 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     int lw = 0, lh = 0;                                                      // image size of the last step (W x H when the schedule is off)
     int level_first_step = 0; std::chrono::steady_clock::time_point level_t0;
     // compact exports beside the full PLY (cfg.exportFormats / DVS_EXPORT_FORMATS / the suffix of modelPath): the packers' scratch, the
-    // packed payload on the device and its host copy. Nothing is allocated until a save exports; the buffers only grow.
-    DevBuf<void> d_export_scratch; DevBuf<uint8_t> d_export_out; size_t export_scratch_cap = 0, export_out_cap = 0;
+    // packed payload on the device and its host copy. Nothing is allocated until a save exports.
+    GrowBuf<void> d_export_scratch; GrowBuf<uint8_t> d_export_out;
     std::vector<uint8_t> export_host;
     // the .spz export's fidelity score (evaluation on, rank 0): the packed payload decoded on the device into a second parameter set
-    // in the tiled layout, rendered and scored on the test cameras like the full model. Allocated at the first such export, only grows.
-    DevBuf<float> d_decoded[6]; int decoded_cap = 0;
+    // in the tiled layout, rendered and scored on the test cameras like the full model. Allocated at the first such export.
+    GrowBuf<float> d_decoded[6];
     double spz_mean[4] = {NAN, NAN, NAN, NAN};                               // {mse, l1, ssim, psnr} means of the decoded model ...
     int spz_it = -1;                                                         // ... at this iteration (-1: none)
 
     // rendered views as JPEG files (cfg.renderViews / renderQuality / renderSampling and their DVS_RENDER_* overrides, read at load): at
-    // every save rank 0 renders the selected cameras through eval_ctx with the evaluation's options (what `eval @it` scored), turns
-    // each pass into quantised DCT coefficients with ONE dvs_jpeg_encode_views launch, copies them to the host and Huffman-codes them
-    // on up to DVS_LOAD_THREADS threads into <modelPath>_<it>_renders/<name>.jpg. Nothing is allocated until the first render; the
-    // buffers only grow. The training context, its pending rows and its prepared projection are never touched.
+    // every save rank 0 renders the selected cameras through eval_ctx (for_each_eval_pass: what `eval @it` scored), turns each pass
+    // into quantised DCT coefficients with ONE dvs_jpeg_encode_views launch, copies them to the host and Huffman-codes them on up to
+    // DVS_LOAD_THREADS threads into <modelPath>_<it>_renders/<name>.jpg. Nothing is allocated until the first render. The training
+    // context, its pending rows and its prepared projection are never touched.
     enum { RENDER_TEST = 1, RENDER_TRAIN = 2 };
     int render_views = 0, render_quality = 90, render_sampling = 0;
     std::vector<std::string> cam_names;                                      // per camera, in step with cams: the image's stem, empty for a synthetic camera
     bool cam_names_ok = false;                                               // every camera has a stem and they are unique (else the files are cam_%04d)
-    DevBuf<int16_t> d_render_coef; size_t render_coef_cap = 0;               // [eval_views][coefficients of a view]
+    GrowBuf<int16_t> d_render_coef;                                          // [eval_views][coefficients of a view]
     std::vector<int16_t> render_coef_host;
     Event ev_render0, ev_render1;
     struct RenderStats { size_t views = 0, bytes = 0; double transform_ms = 0, entropy_ms = 0; int threads = 0; };
@@ -165,8 +188,8 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     void render_at_save();
 
     // mesh export (cfg.meshResolution / DVS_MESH_RESOLUTION; trainer_mesh.cpp): the depth and alpha maps of a pass of eval_ctx. Nothing is
-    // allocated until the first mesh; the buffers only grow. The grid and the extraction scratch live for one extraction.
-    DevBuf<float> d_mesh_depth, d_mesh_alpha; size_t mesh_maps_cap = 0;
+    // allocated until the first mesh. The grid and the extraction scratch live for one extraction.
+    GrowBuf<float> d_mesh_depth, d_mesh_alpha;
     int mesh_resolution() const;
     std::string mesh_file(int it) const { return cfg.modelPath + "_" + std::to_string(it) + "_mesh.ply"; }
     bool mesh_bounds(float lo[3], float hi[3]);
@@ -197,7 +220,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     void setup_sky(bool resumed);
     void step_sky(const Step& s);
     void save_sky();
-    // out (+)= final_T s for the nb views `c` just rendered into `out` (evaluation, written renders); nothing when the sky is off
+    // out (+)= final_T s for the nb views `c` just rendered into `out` (for_each_eval_pass); nothing when the sky is off
     void composite_sky(dvs_ctx* c, const dvs_camera* bc, int nb, float* out) {
         if (!sky_on) return;
         const dvs_sky s = sky();
@@ -300,12 +323,14 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     void exchange(const Step& s, bool pipelined);
     void finish_range(const Step& s, int first, int count, const int* groups, int n_groups, const int* gate);
     void finish_pipelined(const Step& s);
-    dvs_splats splats() const {
+    template <class Buf>
+    static dvs_splats splats_of(const Buf (&p)[6], int n) {                  // a parameter set in the device layout (d_param, d_decoded)
         dvs_splats s{};
-        s.pos = d_param[P_POS].get(); s.sh0 = d_param[P_SH0].get(); s.shN = d_param[P_SHN].get(); s.opacity = d_param[P_OPA].get();
-        s.scale = d_param[P_SCALE].get(); s.rot = d_param[P_ROT].get(); s.n = n;
+        s.pos = p[P_POS].get(); s.sh0 = p[P_SH0].get(); s.shN = p[P_SHN].get(); s.opacity = p[P_OPA].get();
+        s.scale = p[P_SCALE].get(); s.rot = p[P_ROT].get(); s.n = n;
         return s;
     }
+    dvs_splats splats() const { return splats_of(d_param, n); }
     std::string model_file(int it) const { return cfg.modelPath + "_" + std::to_string(it) + ".ply"; }
     bool model_path_ends(const char* suffix) const {
         const size_t k = strlen(suffix);
@@ -320,6 +345,10 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     int export_formats() const { return (asked_formats() ? asked_formats() : suffix_formats()) & (EXPORT_COMPRESSED | EXPORT_SPLAT | EXPORT_SPZ); }
     void export_model(int format);
     void export_spz();
+    // the tail of both: `bytes` of d_export_out to the host, the file through `write`, the `export @` line (unknown_size: the byte
+    // count it prints when the file's size cannot be read). -> false when the file could not be written (logged)
+    bool write_export(std::chrono::steady_clock::time_point t_start, size_t bytes, const std::string& file, const char* word, size_t unknown_size,
+                      const std::function<bool(std::string*)>& write);
     void fetch_host();
     // what the two loaders share: the context and every per-step buffer (W, H, sh_max set by the caller) ...
     void create_context(int count, int capacity, const std::vector<float> init[6]);

@@ -1,4 +1,4 @@
-// trainer_mesh.cpp — mesh export: the training cameras rendered through the evaluation context, their depth and alpha maps
+// trainer_mesh.cpp — mesh export: the training cameras rendered through the evaluation context (for_each_eval_pass), their depth and alpha maps
 // (dvs_raster_depth_views) fused into a TSDF grid and the grid's surface extracted by marching tetrahedra (include/dvs_mesh.h), written
 // optionally given normals and freed of its small components on the device (DVS_MESH_NORMALS, DVS_MESH_MIN_COMPONENT / setMeshCleanup),
 // and written as a binary PLY (ply_io.hpp write_mesh_ply). Everything on the training stream; the training context is never touched.
@@ -6,7 +6,6 @@
 #include "../../include/dvs_mesh.h"
 
 namespace {
-double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
 struct GridGuard {                                                           // frees the grid on every way out
     dvs_tsdf_grid g{};
     ~GridGuard() { dvs_tsdf_destroy(&g); }
@@ -87,15 +86,20 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
     struct Restore { TrainingStatus& s; TrainingStatus v; ~Restore() { s = v; } } restore{status, before};
     const int res = std::min(1024, std::max(16, resolution));
     if (res != resolution) logf_("mesh @%d: meshResolution %d clamped to %d (16..1024)", step, resolution, res);
+    const auto write_ply = [&](uint32_t nv, const float* xyz, const uint8_t* rgb, uint32_t nt, const uint32_t* tri, const float* nrm) {
+        std::error_code ec;
+        const auto parent = std::filesystem::path(path).parent_path();
+        if (!parent.empty()) std::filesystem::create_directories(parent, ec);
+        std::string err;
+        const bool ok = gsply::write_mesh_ply(path, nv, xyz, rgb, nt, tri, &err, nrm);
+        if (!ok) logf_("mesh @%d: %s", step, err.c_str());
+        return ok;
+    };
     float lo[3], hi[3];
     if (!mesh_bounds(lo, hi)) {
         // nothing opaque inside the cube: the empty mesh, a valid file with zero elements, and the same log line
-        std::error_code ec0;
-        const auto dir = std::filesystem::path(path).parent_path();
-        if (!dir.empty()) std::filesystem::create_directories(dir, ec0);
-        std::string err0;
         static const float no_normals[3] = {0, 0, 0};                     // (zero vertices: only the header's nx ny nz)
-        if (!gsply::write_mesh_ply(path, 0, nullptr, nullptr, 0, nullptr, &err0, mesh_normals() ? no_normals : nullptr)) { logf_("mesh @%d: %s", step, err0.c_str()); return false; }
+        if (!write_ply(0, nullptr, nullptr, 0, nullptr, mesh_normals() ? no_normals : nullptr)) return false;
         logf_("mesh @%d: 0 vertices, 0 triangles, grid 0x0x0, voxel 0, bounds %.9g,%.9g,%.9g,%.9g,%.9g,%.9g (no splat with opacity >= 0.5 within 3 x extent "
               "= %.9g of the cameras' centroid; DVS_MESH_BOUNDS sets the box), trunc 0, 0 views; render+depth 0.00 ms, fusion 0.00 ms, extraction 0.00 ms -> %s",
               step, (double)lo[0], (double)lo[1], (double)lo[2], (double)hi[0], (double)hi[1], (double)hi[2], 3.0 * (double)extent, path.c_str());
@@ -114,41 +118,28 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
     if (rc == DVS_ERR_CAPACITY) { logf_("mesh @%d: a %dx%dx%d grid (%zu bytes) does not fit the free device memory: no mesh", step, dims[0], dims[1], dims[2], dvs_tsdf_bytes(dims)); return false; }
     if (rc != DVS_OK) throw std::runtime_error("dvs_tsdf_create: status " + std::to_string(rc));
 
-    // render + depth + fusion: the training cameras in index order, eval_views per pass, the evaluation's options
+    // render + depth + fusion: a pass's depth and alpha maps from the forward for_each_eval_pass just ran, fused under the cameras' masks
     ensure_eval_ctx();
-    const size_t P = (size_t)W * H;
-    if (mesh_maps_cap < (size_t)eval_views * P) {
-        mesh_maps_cap = 0;
-        d_mesh_depth.alloc((size_t)eval_views * P * sizeof(float));
-        d_mesh_alpha.alloc((size_t)eval_views * P * sizeof(float));
-        mesh_maps_cap = (size_t)eval_views * P;
-    }
-    std::vector<int> which = train_idx;
-    if (which.empty()) for (int c = 0; c < (int)cams.size(); ++c) which.push_back(c);
-    dvs_opts opts{};                                                         // the evaluation's (score_views)
-    opts.sh_degree = sh_max; opts.antialias = cfg.mipAntiliased ? 1 : 0; opts.shn_layout = DVS_SHN_TILED; opts.tile_bounds = DVS_TILES_CANONICAL;
-    const dvs_splats sp = splats();
+    const size_t map_bytes = (size_t)eval_views * W * H * sizeof(float);
+    d_mesh_depth.reserve(map_bytes);
+    d_mesh_alpha.reserve(map_bytes);
+    const std::vector<int> which = training_cameras();
+    const dvs_opts opts = eval_opts();
     double render_ms = 0, fuse_ms = 0;
-    for (int first = 0; first < (int)which.size(); first += eval_views) {
-        const int nb = std::min(eval_views, (int)which.size() - first);
-        std::vector<dvs_camera> bc((size_t)nb);
+    auto t0_ = std::chrono::steady_clock::now();                             // (a pass's forward is launched before its per_pass)
+    for_each_eval_pass(splats(), which, false, [&](const EvalPass& p) {
         const float* masks[DVS_TSDF_MAX_VIEWS] = {};
-        for (int k = 0; k < nb; ++k) {
-            const size_t ci = (size_t)which[(size_t)(first + k)];
-            bc[(size_t)k] = cams[ci];
-            masks[k] = view_mask(ci);
-        }
-        auto t0_ = std::chrono::steady_clock::now();
-        DVS_OR_THROW(dvs_raster_forward_views(eval_ctx.get(), stream.get(), &sp, bc.data(), nb, &opts, d_eval_out.get()));
+        for (int k = 0; k < p.nb; ++k) masks[k] = view_mask((size_t)p.cam[k]);
         DVS_OR_THROW(dvs_raster_depth_views(eval_ctx.get(), stream.get(), &opts, d_mesh_depth.get(), d_mesh_alpha.get()));
         HIP_OR_THROW(hipStreamSynchronize(stream.get()));
         render_ms += ms_since(t0_);
         t0_ = std::chrono::steady_clock::now();
-        const int ri = dvs_tsdf_integrate(stream.get(), &grid.g, bc.data(), nb, d_mesh_depth.get(), d_mesh_alpha.get(), d_eval_out.get(), masks, W, H, trunc);
+        const int ri = dvs_tsdf_integrate(stream.get(), &grid.g, p.cams, p.nb, d_mesh_depth.get(), d_mesh_alpha.get(), p.images, masks, W, H, trunc);
         if (ri != DVS_OK) throw std::runtime_error("dvs_tsdf_integrate: status " + std::to_string(ri));
         HIP_OR_THROW(hipStreamSynchronize(stream.get()));
         fuse_ms += ms_since(t0_);
-    }
+        t0_ = std::chrono::steady_clock::now();
+    });
 
     // extraction, normals and clean-up when asked for, then the final arrays alone to the host
     const auto t_ex = std::chrono::steady_clock::now();
@@ -219,11 +210,7 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
                  info.n_components, info.largest, min_bp / 100.0, clean_ms);
     if (want_normals) snprintf(extras + strlen(extras), sizeof extras - strlen(extras), ", normals %.2f ms", normals_ms);
 
-    std::error_code ec;
-    const auto parent = std::filesystem::path(path).parent_path();
-    if (!parent.empty()) std::filesystem::create_directories(parent, ec);
-    std::string err;
-    if (!gsply::write_mesh_ply(path, nv, xyz.data(), rgb.data(), nt, tri.data(), &err, want_normals ? nrm.data() : nullptr)) { logf_("mesh @%d: %s", step, err.c_str()); return false; }
+    if (!write_ply(nv, xyz.data(), rgb.data(), nt, tri.data(), want_normals ? nrm.data() : nullptr)) return false;
     logf_("mesh @%d: %u vertices, %u triangles, grid %dx%dx%d, voxel %.9g, bounds %.9g,%.9g,%.9g,%.9g,%.9g,%.9g, trunc %.9g, %d views; render+depth %.2f ms, "
           "fusion %.2f ms, extraction %.2f ms%s -> %s", step, nv, nt, dims[0], dims[1], dims[2], (double)voxel, (double)lo[0], (double)lo[1], (double)lo[2],
           (double)(lo[0] + (dims[0] - 1) * voxel), (double)(lo[1] + (dims[1] - 1) * voxel), (double)(lo[2] + (dims[2] - 1) * voxel), (double)trunc,

@@ -99,7 +99,21 @@ void GaussianTrainerScene::Impl::ensure_eval_ctx() {
     if (!eval_ctx) throw std::runtime_error(std::string("dvs_create_views (evaluation): ") + dvs_last_error());
     d_eval_out.alloc((size_t)eval_views * 3 * (size_t)W * H * sizeof(float));
 }
-// the test cameras rendered from `sp` (DVS_SHN_TILED, at most `cap` splats) and scored: res = [n_test][4] {mse, l1, ssim, psnr}, mean = their means
+void GaussianTrainerScene::Impl::for_each_eval_pass(const dvs_splats& sp, const std::vector<int>& which, bool with_sky,
+                                                    const std::function<void(const EvalPass&)>& per_pass) {
+    ensure_eval_ctx();
+    const dvs_opts opts = eval_opts();
+    std::vector<dvs_camera> bc((size_t)eval_views);
+    const int total = (int)which.size();
+    for (int first = 0; first < total; first += eval_views) {
+        const int nb = std::min(eval_views, total - first);
+        for (int k = 0; k < nb; ++k) bc[(size_t)k] = cams[(size_t)which[(size_t)(first + k)]];
+        DVS_OR_THROW(dvs_raster_forward_views(eval_ctx.get(), stream.get(), &sp, bc.data(), nb, &opts, d_eval_out.get()));
+        if (with_sky) composite_sky(eval_ctx.get(), bc.data(), nb, d_eval_out.get());     // what was trained: the sky behind the splats
+        per_pass(EvalPass{first, nb, &which[(size_t)first], bc.data(), d_eval_out.get()});
+    }
+}
+// the test cameras rendered from `sp` and scored: res = [n_test][4] {mse, l1, ssim, psnr}, mean = their means
 void GaussianTrainerScene::Impl::score_views(const dvs_splats& sp, std::vector<double>& res, double mean[4]) {
     const int nt = (int)test_idx.size();
     const size_t img = 3 * (size_t)W * H;
@@ -108,29 +122,22 @@ void GaussianTrainerScene::Impl::score_views(const dvs_splats& sp, std::vector<d
         d_eval_scratch.alloc(dvs_image_metrics_scratch_bytes(W, H, eval_views));
         d_eval_res.alloc((size_t)nt * 4 * sizeof(double));
     }
-    dvs_opts opts{};
-    opts.sh_degree = sh_max; opts.antialias = cfg.mipAntiliased ? 1 : 0; opts.shn_layout = DVS_SHN_TILED; opts.tile_bounds = DVS_TILES_CANONICAL;
-    for (int first = 0; first < nt; first += eval_views) {
-        const int nb = std::min(eval_views, nt - first);
-        std::vector<dvs_camera> bc((size_t)nb);
+    for_each_eval_pass(sp, test_idx, true, [&](const EvalPass& p) {
         dvs_metrics_view mv[DVS_METRICS_MAX_VIEWS] = {};
-        for (int k = 0; k < nb; ++k) {
-            const size_t ci = (size_t)test_idx[(size_t)(first + k)];
-            bc[(size_t)k] = cams[ci];
-            mv[k].img = d_eval_out.get() + (size_t)k * img;
+        for (int k = 0; k < p.nb; ++k) {
+            const size_t ci = (size_t)p.cam[k];
+            mv[k].img = p.images + (size_t)k * img;
             mv[k].target = view_pixels(ci);
             mv[k].mask = view_mask(ci);
         }
         if (cfg.enableFocusRegion) {        // what the loss saw: the camera's mask x the region's hit
             const float* in[DVS_METRICS_MAX_VIEWS];
-            for (int k = 0; k < nb; ++k) in[k] = mv[k].mask;
-            const float* rm = region_masks(bc.data(), in, nb, W, H);
-            for (int k = 0; k < nb; ++k) mv[k].mask = rm + (size_t)k * W * H;
+            for (int k = 0; k < p.nb; ++k) in[k] = mv[k].mask;
+            const float* rm = region_masks(p.cams, in, p.nb, W, H);
+            for (int k = 0; k < p.nb; ++k) mv[k].mask = rm + (size_t)k * W * H;
         }
-        DVS_OR_THROW(dvs_raster_forward_views(eval_ctx.get(), stream.get(), &sp, bc.data(), nb, &opts, d_eval_out.get()));
-        composite_sky(eval_ctx.get(), bc.data(), nb, d_eval_out.get());     // what was trained: the sky behind the splats
-        DVS_OR_THROW(dvs_image_metrics_views(stream.get(), mv, nb, W, H, views_u8() ? 1 : 0, d_eval_scratch.get(), d_eval_res.get() + (size_t)first * 4));
-    }
+        DVS_OR_THROW(dvs_image_metrics_views(stream.get(), mv, p.nb, W, H, views_u8() ? 1 : 0, d_eval_scratch.get(), d_eval_res.get() + (size_t)p.first * 4));
+    });
     res.assign((size_t)nt * 4, 0.0);
     HIP_OR_THROW(hipMemcpyAsync(res.data(), d_eval_res.get(), res.size() * sizeof(double), hipMemcpyDeviceToHost, stream.get()));
     HIP_OR_THROW(hipStreamSynchronize(stream.get()));
@@ -204,6 +211,20 @@ void GaussianTrainerScene::Impl::fetch_host() {
     host_valid = true;
 }
 
+// The tail of a compact export, after its packer: the payload to the host, the file, the log line.
+bool GaussianTrainerScene::Impl::write_export(std::chrono::steady_clock::time_point t_start, size_t bytes, const std::string& file, const char* word,
+                                              size_t unknown_size, const std::function<bool(std::string*)>& write) {
+    if (export_host.size() < bytes) export_host.resize(bytes);
+    HIP_OR_THROW(hipMemcpyAsync(export_host.data(), d_export_out.get(), bytes, hipMemcpyDeviceToHost, stream.get()));
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    std::string err;
+    if (!write(&err)) { logf_("export @%d: %s", step, err.c_str()); return false; }
+    std::error_code ec;
+    const auto file_bytes = std::filesystem::file_size(file, ec);
+    logf_("export @%d: %s %d splats, %llu bytes, %.2f ms", step, word, n, (unsigned long long)(ec ? unknown_size : file_bytes), ms_since(t_start));
+    return true;
+}
+
 // One compact export of the current model: packed on the training stream from the device arrays (shN is not read, so its tiled layout
 // does not matter), the packed payload alone copied to the host and written to <modelPath>_<step>.compressed.ply / .splat.
 void GaussianTrainerScene::Impl::export_model(int format) {
@@ -213,33 +234,23 @@ void GaussianTrainerScene::Impl::export_model(int format) {
     const size_t n_chunks = ((size_t)n + 255) / 256;
     const size_t chunk_bytes = n_chunks * 12 * sizeof(float);              // (a multiple of 16: the vertex records follow on a 16-byte boundary)
     const size_t bytes = compressed ? chunk_bytes + (size_t)n * 16 : (size_t)n * 32;
-    const auto grow = [](auto& buf, size_t& buf_cap, size_t need) {         // (the capacity is 0 while the buffer is being replaced)
-        if (need > buf_cap) { buf_cap = 0; buf.alloc(need); buf_cap = need; }
-    };
-    grow(d_export_out, export_out_cap, bytes);
-    if (export_host.size() < bytes) export_host.resize(bytes);
+    d_export_out.reserve(bytes);
     const float *pos = d_param[P_POS].get(), *sh0 = d_param[P_SH0].get(), *opa = d_param[P_OPA].get(), *scale = d_param[P_SCALE].get(), *rot = d_param[P_ROT].get();
     uint8_t* const out = d_export_out.get();
     int status;
     if (compressed) {
-        grow(d_export_scratch, export_scratch_cap, dvs_pack_scratch_bytes(n));
+        d_export_scratch.reserve(dvs_pack_scratch_bytes(n));
         status = dvs_pack_compressed(stream.get(), n, pos, sh0, opa, scale, rot, d_export_scratch.get(), (float*)out, (uint32_t*)(out + chunk_bytes), nullptr);
     } else {
         status = dvs_pack_splat32(stream.get(), n, pos, sh0, opa, scale, rot, out);
     }
     if (status != DVS_OK) throw std::runtime_error(std::string(compressed ? "dvs_pack_compressed" : "dvs_pack_splat32") + ": status " + std::to_string(status));
-    HIP_OR_THROW(hipMemcpyAsync(export_host.data(), out, bytes, hipMemcpyDeviceToHost, stream.get()));
-    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
     const std::string file = cfg.modelPath + "_" + std::to_string(step) + (compressed ? ".compressed.ply" : ".splat");
-    std::string err;
-    const bool ok = compressed ? gsply::write_compressed_ply(file, (size_t)n, (const float*)export_host.data(),
-                                                             (const uint32_t*)(export_host.data() + chunk_bytes), cfg.mipAntiliased, &err)
-                               : gsply::write_splat(file, (size_t)n, export_host.data(), &err);
-    if (!ok) { logf_("export @%d: %s", step, err.c_str()); return; }
-    std::error_code ec;
-    const auto file_bytes = std::filesystem::file_size(file, ec);
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    logf_("export @%d: %s %d splats, %llu bytes, %.2f ms", step, compressed ? "compressed.ply" : "splat", n, (unsigned long long)(ec ? bytes : file_bytes), ms);
+    write_export(t_start, bytes, file, compressed ? "compressed.ply" : "splat", bytes, [&](std::string* err) {
+        return compressed ? gsply::write_compressed_ply(file, (size_t)n, (const float*)export_host.data(),
+                                                        (const uint32_t*)(export_host.data() + chunk_bytes), cfg.mipAntiliased, err)
+                          : gsply::write_splat(file, (size_t)n, export_host.data(), err);
+    });
 }
 
 // The .spz export: the six sections packed from the tiled arrays at the model's sh_max (the one compact format that keeps the
@@ -251,35 +262,22 @@ void GaussianTrainerScene::Impl::export_spz() {
     dvs_spz_layout layout;
     if (dvs_spz_layout_for(n, sh_max, &layout) != DVS_OK) throw std::runtime_error("dvs_spz_layout_for: invalid arguments");
     const size_t bytes = (size_t)layout.total;
-    if (bytes > export_out_cap) { export_out_cap = 0; d_export_out.alloc(bytes); export_out_cap = bytes; }
-    if (export_host.size() < bytes) export_host.resize(bytes);
+    d_export_out.reserve(bytes);
     const int status = dvs_pack_spz(stream.get(), n, sh_max, d_param[P_POS].get(), d_param[P_SH0].get(), d_param[P_SHN].get(), DVS_SHN_TILED,
                                     d_param[P_OPA].get(), d_param[P_SCALE].get(), d_param[P_ROT].get(), d_export_out.get());
     if (status != DVS_OK) throw std::runtime_error("dvs_pack_spz: status " + std::to_string(status));
-    HIP_OR_THROW(hipMemcpyAsync(export_host.data(), d_export_out.get(), bytes, hipMemcpyDeviceToHost, stream.get()));
-    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
     const std::string file = cfg.modelPath + "_" + std::to_string(step) + ".spz";
-    std::string err;
-    if (!gsply::write_spz(file, (size_t)n, sh_max, cfg.mipAntiliased, export_host.data(), layout, &err)) { logf_("export @%d: %s", step, err.c_str()); return; }
-    std::error_code ec;
-    const auto file_bytes = std::filesystem::file_size(file, ec);
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-    logf_("export @%d: spz %d splats, %llu bytes, %.2f ms", step, n, (unsigned long long)(ec ? 0 : file_bytes), ms);
+    if (!write_export(t_start, bytes, file, "spz", 0, [&](std::string* err) {
+            return gsply::write_spz(file, (size_t)n, sh_max, cfg.mipAntiliased, export_host.data(), layout, err);
+        })) return;
     if (test_idx.empty() || rank != 0) return;
-    if (n > decoded_cap) {
-        decoded_cap = 0;
-        for (int g = 0; g < 6; ++g) d_decoded[g].alloc(dev_floats_for(g, n) * sizeof(float) + 16);
-        decoded_cap = n;
-    }
+    for (int g = 0; g < 6; ++g) d_decoded[g].reserve(dev_floats_for(g, n) * sizeof(float) + 16);
     const int rc = dvs_unpack_spz(stream.get(), n, sh_max, d_export_out.get(), d_decoded[P_POS].get(), d_decoded[P_SH0].get(), d_decoded[P_SHN].get(),
                                   DVS_SHN_TILED, d_decoded[P_OPA].get(), d_decoded[P_SCALE].get(), d_decoded[P_ROT].get());
     if (rc != DVS_OK) throw std::runtime_error("dvs_unpack_spz: status " + std::to_string(rc));
     if (eval_it != step) run_evaluation();                                  // the full model of the same parameters: the comparison
-    dvs_splats sp{};
-    sp.pos = d_decoded[P_POS].get(); sp.sh0 = d_decoded[P_SH0].get(); sp.shN = d_decoded[P_SHN].get(); sp.opacity = d_decoded[P_OPA].get();
-    sp.scale = d_decoded[P_SCALE].get(); sp.rot = d_decoded[P_ROT].get(); sp.n = n;
     std::vector<double> res;
-    score_views(sp, res, spz_mean);
+    score_views(splats_of(d_decoded, n), res, spz_mean);
     spz_it = step;
     logf_("export @%d: spz decoded model: PSNR %.17g dB (full model %.17g dB), SSIM %.17g, L1 %.17g", step, spz_mean[3], eval_mean[3], spz_mean[2], spz_mean[1]);
 }

@@ -2,10 +2,6 @@
 // importance prune, focus-region prune.
 #include "trainer.hpp"
 
-namespace {
-double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
-}  // namespace
-
 // data parallel: the densification statistics are per-view sums / maxima — make them global before a refinement decision
 void GaussianTrainerScene::Impl::sync_stats() {
     if (!comm) return;
@@ -145,10 +141,9 @@ void GaussianTrainerScene::Impl::prune_region(int it) {
 
 // importancePrune = P > 0: at every prune occasion, after the light prune, the P % of the splats that contribute least to the training
 // views go. The score of a splat is its blend weight alpha T summed over the pixels of all training cameras (dvs_raster_importance_views),
-// rendered through the evaluation context as extract_mesh renders them: in index order, eval_views per pass, the evaluation's options,
-// the camera's mask. dvs_importance_plan keeps the n - n P / 100 best exactly, ties by index; the existing apply path compacts the
-// parameters and the moments. Every rank scores all training cameras itself: integer scores, an exact selection, no communication —
-// the replicas stay bit-identical.
+// rendered through the evaluation context (for_each_eval_pass, without the sky) under the camera's mask. dvs_importance_plan keeps
+// the n - n P / 100 best exactly, ties by index; the existing apply path compacts the parameters and the moments. Every rank scores
+// all training cameras itself: integer scores, an exact selection, no communication — the replicas stay bit-identical.
 void GaussianTrainerScene::Impl::prune_importance(int it) {
     const int P = importance_prune();
     const int new_n = n - (int)((int64_t)n * P / 100);
@@ -159,26 +154,16 @@ void GaussianTrainerScene::Impl::prune_importance(int it) {
         d_imp_score.alloc((size_t)cap * sizeof(uint64_t) + 16);
         d_imp_scratch.alloc(dvs_importance_scratch_bytes(cap));
     }
-    std::vector<int> which = train_idx;
-    if (which.empty()) for (int c = 0; c < (int)cams.size(); ++c) which.push_back(c);
-    dvs_opts opts{};                                                         // the evaluation's (score_views)
-    opts.sh_degree = sh_max; opts.antialias = cfg.mipAntiliased ? 1 : 0; opts.shn_layout = DVS_SHN_TILED; opts.tile_bounds = DVS_TILES_CANONICAL;
-    const dvs_splats sp = splats();
+    const std::vector<int> which = training_cameras();
+    const dvs_opts opts = eval_opts();
     HIP_OR_THROW(hipStreamSynchronize(stream.get()));
     auto t0_ = std::chrono::steady_clock::now();
     HIP_OR_THROW(hipMemsetAsync(d_imp_score.get(), 0, (size_t)n * sizeof(uint64_t), stream.get()));
-    for (int first = 0; first < (int)which.size(); first += eval_views) {
-        const int nb = std::min(eval_views, (int)which.size() - first);
-        std::vector<dvs_camera> bc((size_t)nb);
-        std::vector<const float*> masks((size_t)nb);
-        for (int k = 0; k < nb; ++k) {
-            const size_t ci = (size_t)which[(size_t)(first + k)];
-            bc[(size_t)k] = cams[ci];
-            masks[(size_t)k] = view_mask(ci);
-        }
-        DVS_OR_THROW(dvs_raster_forward_views(eval_ctx.get(), stream.get(), &sp, bc.data(), nb, &opts, d_eval_out.get()));
+    for_each_eval_pass(splats(), which, false, [&](const EvalPass& p) {
+        std::vector<const float*> masks((size_t)p.nb);
+        for (int k = 0; k < p.nb; ++k) masks[(size_t)k] = view_mask((size_t)p.cam[k]);
         DVS_OR_THROW(dvs_raster_importance_views(eval_ctx.get(), stream.get(), &opts, masks.data(), d_imp_score.get(), nullptr, nullptr));
-    }
+    });
     HIP_OR_THROW(hipStreamSynchronize(stream.get()));
     const double score_ms = ms_since(t0_);
     size_t never = 0;                                                        // (for the log line only: nothing below depends on the host copy)

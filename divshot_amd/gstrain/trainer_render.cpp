@@ -24,25 +24,18 @@ std::string GaussianTrainerScene::Impl::camera_name(int c) const {
     return name;
 }
 
-// cameras `which` rendered from the current parameters and written to `files`: at most eval_views per pass; per pass one multi-view
-// forward, ONE encode launch (timed by events), one copy of the coefficients, then up to DVS_LOAD_THREADS host threads that code one
+// cameras `which` rendered from the current parameters and written to `files`: per pass of for_each_eval_pass (the sky composited),
+// ONE encode launch (timed by events), one copy of the coefficients, then up to DVS_LOAD_THREADS host threads that code one
 // view each at a time and write its file. Synchronous. -> false when a file could not be coded or written (the others are still written).
 bool GaussianTrainerScene::Impl::render_to_jpeg(const std::vector<int>& which, const std::vector<std::string>& files, RenderStats* stats) {
     ensure_eval_ctx();
     dvs_jpeg_desc desc;
     if (dvs_jpeg_encode_desc(W, H, render_sampling, render_quality, &desc) != DVS_OK) throw std::runtime_error("dvs_jpeg_encode_desc: invalid arguments");
     const size_t count = dvs_jpeg_encode_coef_count(&desc), img = 3 * (size_t)W * H;
-    if (render_coef_cap < (size_t)eval_views * count) {
-        render_coef_cap = 0;
-        d_render_coef.alloc((size_t)eval_views * count * sizeof(int16_t));
-        render_coef_cap = (size_t)eval_views * count;
-    }
+    d_render_coef.reserve((size_t)eval_views * count * sizeof(int16_t));
     if (render_coef_host.size() < (size_t)eval_views * count) render_coef_host.resize((size_t)eval_views * count);
     if (!ev_render0)
         for (Event* e : {&ev_render0, &ev_render1}) { hipEvent_t ev = nullptr; HIP_OR_THROW(hipEventCreate(&ev)); e->reset(ev); }
-    dvs_opts opts{};                                                         // the evaluation's (score_views)
-    opts.sh_degree = sh_max; opts.antialias = cfg.mipAntiliased ? 1 : 0; opts.shn_layout = DVS_SHN_TILED; opts.tile_bounds = DVS_TILES_CANONICAL;
-    const dvs_splats sp = splats();
     const int load_threads = std::max(1, std::min(env_int("DVS_LOAD_THREADS", 8), 16));     // never the machine's CPU count
     gsjpeg::Frame shape;                                                     // what every view's frame shares
     shape.width = W; shape.height = H; shape.components = 3;
@@ -50,19 +43,14 @@ bool GaussianTrainerScene::Impl::render_to_jpeg(const std::vector<int>& which, c
     for (int c = 0; c < 3; ++c) { shape.blocks_w[c] = desc.blocks_w[c]; shape.blocks_h[c] = desc.blocks_h[c]; shape.offset[c] = desc.offset[c]; }
     memcpy(shape.quant, desc.quant, sizeof shape.quant);
     bool all_ok = true;
-    const int total = (int)which.size();
-    for (int first = 0; first < total; first += eval_views) {
-        const int nb = std::min(eval_views, total - first);
-        std::vector<dvs_camera> bc((size_t)nb);
+    for_each_eval_pass(splats(), which, true, [&](const EvalPass& p) {
+        const int first = p.first, nb = p.nb;
         const float* images[DVS_JPEG_ENCODE_MAX_VIEWS];
         int16_t* coefs[DVS_JPEG_ENCODE_MAX_VIEWS];
         for (int k = 0; k < nb; ++k) {
-            bc[(size_t)k] = cams[(size_t)which[(size_t)(first + k)]];
-            images[k] = d_eval_out.get() + (size_t)k * img;
+            images[k] = p.images + (size_t)k * img;
             coefs[k] = d_render_coef.get() + (size_t)k * count;
         }
-        DVS_OR_THROW(dvs_raster_forward_views(eval_ctx.get(), stream.get(), &sp, bc.data(), nb, &opts, d_eval_out.get()));
-        composite_sky(eval_ctx.get(), bc.data(), nb, d_eval_out.get());
         HIP_OR_THROW(hipEventRecord(ev_render0.get(), stream.get()));
         DVS_OR_THROW(dvs_jpeg_encode_views(stream.get(), &desc, images, coefs, nb));
         HIP_OR_THROW(hipEventRecord(ev_render1.get(), stream.get()));
@@ -98,13 +86,13 @@ bool GaussianTrainerScene::Impl::render_to_jpeg(const std::vector<int>& which, c
         const int nthreads = (int)workers.size() + 1;
         work();
         for (std::thread& t : workers) t.join();
-        const double host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host).count();
+        const double host_ms = ms_since(t_host);
         for (int k = 0; k < nb; ++k) {
             if (!errs[(size_t)k].empty()) { logf_("render @%d: camera %d: %s", step, which[(size_t)(first + k)], errs[(size_t)k].c_str()); all_ok = false; }
             else if (stats) { stats->views += 1; stats->bytes += bytes[(size_t)k]; }
         }
         if (stats) { stats->transform_ms += ms; stats->entropy_ms += host_ms; stats->threads = std::max(stats->threads, nthreads); }
-    }
+    });
     return all_ok;
 }
 

@@ -13,7 +13,10 @@ Flag variants: --renderViews all writes one file per camera, the default samplin
 error. Off: the same run without the flag leaves no _renders directory and no `render @` / `config: render` line, and its `eval @20`
 line equals the flagged run's — compared at 16x12 (--maxImageWidth 16: one tile), where the trainer repeats from run to run
 (tests/test_gpu_dataset_jpeg.py explains why a view of at most two tiles does). renderCameraToJpeg through a host that links the class
-(tests/hosts/render_one.cpp): a valid file for camera 1, false for camera -1."""
+(tests/hosts/render_one.cpp): a valid file for camera 1, false for camera -1.
+
+The pass boundary: with --evalHoldout 3 the evaluation context renders 3 views per pass; renders of all 8 cameras, the mesh export and the
+importance prune over the 5 training cameras and the scored .spz export then all end in a partial pass, and two runs write the same bytes."""
 import json
 import os
 import re
@@ -128,6 +131,34 @@ def test_training_cameras_alone_and_the_environment_override(gpu_device, capture
     assert "eval @" not in p.stderr and "(quality 75, 4:4:4)" in p.stderr
     assert sorted(os.listdir(out + "_2_renders")) == [f"view_{k:03d}.jpg" for k in range(CAMS)]
     assert decode_file(os.path.join(out + "_2_renders", "view_003.jpg"))[0].shape == (3, 12, 16)
+
+
+def test_every_user_of_the_evaluation_context_crosses_a_pass_boundary(gpu_device, capture, tmp_path):
+    """--evalHoldout 3 holds out cameras 0, 3, 6: the evaluation context renders 3 views per pass, so the 8 written renders go through
+    it as 3 + 3 + 2 and the 5 training cameras of the mesh export and of the importance prune (one occasion, iteration 12) as 3 + 2;
+    the .spz export scores its decoded model through it as well. At 16x12 two runs of the command write the same bytes."""
+    env = {k: v for k, v in os.environ.items() if not k.startswith("DVS_RENDER_")}
+    env.update(DVS_MESH_RESOLUTION="16", DVS_MESH_BOUNDS="-1.5,-1,2.5,1.5,1,4", DVS_IMPORTANCE_PRUNE="20", DVS_EXPORT_FORMATS="4")   # (the box of the points)
+    runs = []
+    for tag in ("a", "b"):
+        out = str(tmp_path / tag / "iteration")
+        p = subprocess.run([DRIVER, "--inputPath", capture[0], "--maxIteration", str(STEPS), "--maxImageWidth", "16", "--evalHoldout", "3", "--renderViews", "all",
+                            "--refineStopIter", "5", "--pruneEvery", "12", "--outputPath", out], capture_output=True, text=True, timeout=300, env=env)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+        files = {}
+        for d, _, names in os.walk(os.path.dirname(out)):
+            files.update({os.path.relpath(os.path.join(d, n), os.path.dirname(out)): open(os.path.join(d, n), "rb").read() for n in names})
+        runs.append((p.stderr, files))
+    log, files = runs[0]
+    assert sorted(n for n in files if n.endswith(".jpg")) == [f"iteration_{STEPS}_renders/view_{k:03d}.jpg" for k in range(CAMS)], sorted(files)
+    ev = json.loads(files[f"iteration_{STEPS}_eval.json"])
+    assert [v["camera"] for v in ev["views"]] == [0, 3, 6] and set(ev["exports"]["spz"]) == {"psnr", "ssim", "l1", "mse"}
+    assert re.search(rf"render @{STEPS}: {CAMS} views, ", log), log[-3000:]
+    assert re.findall(rf"mesh @{STEPS}: .* trunc \S+, (\d+) views; ", log) == ["5"], log[-3000:]
+    assert re.findall(r"importance prune @(\d+): \d+ -> \d+ splats, (\d+) views, ", log) == [("12", "5")], log[-3000:]
+    assert {f"iteration_{STEPS}.ply", f"iteration_{STEPS}.spz", f"iteration_{STEPS}_mesh.ply"} <= set(files)
+    assert sorted(files) == sorted(runs[1][1])
+    assert [n for n in sorted(files) if files[n] != runs[1][1][n]] == []
 
 
 def test_bad_flag_values_are_command_line_errors(tmp_path):
