@@ -6,18 +6,8 @@
 #include "dvs_device.h"
 #include "block_scan.h"
 
-__device__ __forceinline__ int64_t d_shn_index(int layout, int i, int e) {
-    return layout == DVS_SHN_TILED ? ((((int64_t)(i >> 6) * 12 + (e >> 2)) * 64 + (i & 63)) * 4 + (e & 3)) : ((int64_t)i * 45 + e);
-}
-// counter-based RNG: one 32-bit hash per (seed, splat, draw)
-__device__ __forceinline__ uint32_t d_hash(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ (c + 0x165667B1u) * 0xC2B2AE3Du;
-    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
-    return h;
-}
-__device__ __forceinline__ float d_uniform(uint32_t h) { return ((h >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 __device__ __forceinline__ float d_normal(uint32_t seed, uint32_t id, uint32_t k) {
-    const float u1 = d_uniform(d_hash(seed, id, 2 * k)), u2 = d_uniform(d_hash(seed, id, 2 * k + 1));
+    const float u1 = dvs_uniform24(dvs_hash3(seed, id, 2 * k)), u2 = dvs_uniform24(dvs_hash3(seed, id, 2 * k + 1));
     return sqrtf(-2.0f * __logf(u1)) * __cosf(6.2831853f * u2);
 }
 
@@ -91,12 +81,12 @@ __global__ void __launch_bounds__(DB)
 k_densify_blocksum(int n, const float* __restrict__ opacity, const float* __restrict__ scale, const float* __restrict__ grad_accum,
                    const float* __restrict__ denom, const int* __restrict__ max_radii, dvs_densify_params p, uint8_t* __restrict__ action,
                    uint32_t* __restrict__ block_sums) {
-    __shared__ uint32_t tmp[DB / 64 + 1];
+    __shared__ uint32_t tmp[DB / 64];
     const int i = blockIdx.x * DB + threadIdx.x;
     int a = DVS_DENSIFY_PRUNE;
     if (i < n) { a = d_action(i, opacity, scale, grad_accum, denom, max_radii, p); action[i] = (uint8_t)a; }
     uint32_t tot;
-    (void)d_block_excl_scan((a != DVS_DENSIFY_PRUNE ? 1u : 0u) | (d_grows(a) ? 1u << 16 : 0u), tmp, &tot);
+    (void)dvs_block_excl_scan((a != DVS_DENSIFY_PRUNE ? 1u : 0u) | (d_grows(a) ? 1u << 16 : 0u), tmp, &tot);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
 }
 // single workgroup over the nb packed block sums, DB blocks per chunk with a running carry. Pass 1: totals S (survivors) and G (growth
@@ -106,15 +96,15 @@ k_densify_blocksum(int n, const float* __restrict__ opacity, const float* __rest
 // word after the block offsets: block_sums[nb] = cut << 8 | left (cut = nb: every candidate is accepted).
 __global__ void __launch_bounds__(DB)
 k_densify_scan_blocks(uint32_t* __restrict__ block_sums, uint32_t nb, int cap_max, uint64_t* __restrict__ total) {
-    __shared__ uint32_t tmp[DB / 64 + 1];
+    __shared__ uint32_t tmp[DB / 64];
     __shared__ uint32_t cut_word;
     uint64_t S = 0, G = 0;
     for (uint32_t base = 0; base < nb; base += DB) {
         const uint32_t idx = base + threadIdx.x;
         const uint32_t v = idx < nb ? block_sums[idx] : 0u;
         uint32_t ts, tg;
-        (void)d_block_excl_scan(v & 0xffffu, tmp, &ts);
-        (void)d_block_excl_scan(v >> 16, tmp, &tg);
+        (void)dvs_block_excl_scan(v & 0xffffu, tmp, &ts);
+        (void)dvs_block_excl_scan(v >> 16, tmp, &tg);
         S += ts; G += tg;
     }
     const uint64_t budget = cap_max > 0 ? ((uint64_t)cap_max > S ? min(G, (uint64_t)cap_max - S) : 0ull) : G;
@@ -125,8 +115,8 @@ k_densify_scan_blocks(uint32_t* __restrict__ block_sums, uint32_t nb, int cap_ma
         const uint32_t idx = base + threadIdx.x;
         const uint32_t v = idx < nb ? block_sums[idx] : 0u;
         uint32_t ts, tg;
-        const uint64_t es = cs + d_block_excl_scan(v & 0xffffu, tmp, &ts);
-        const uint64_t eg = cg + d_block_excl_scan(v >> 16, tmp, &tg);
+        const uint64_t es = cs + dvs_block_excl_scan(v & 0xffffu, tmp, &ts);
+        const uint64_t eg = cg + dvs_block_excl_scan(v >> 16, tmp, &tg);
         if (idx < nb) {
             block_sums[idx] = (uint32_t)(es + min(eg, budget));
             if (eg <= budget && budget < eg + (v >> 16)) cut_word = idx << 8 | (uint32_t)(budget - eg);     // (one block at most)
@@ -142,13 +132,13 @@ k_densify_scan_blocks(uint32_t* __restrict__ block_sums, uint32_t nb, int cap_ma
 // growth candidates past the budget are demoted to KEEP (action rewritten); offsets = exclusive scan of the final output counts
 __global__ void __launch_bounds__(DB)
 k_densify_offsets(int n, uint8_t* __restrict__ action, const uint32_t* __restrict__ block_offsets, uint32_t* __restrict__ offsets) {
-    __shared__ uint32_t tmp[DB / 64 + 1];
+    __shared__ uint32_t tmp[DB / 64];
     const int i = blockIdx.x * DB + threadIdx.x;
     int a = i < n ? action[i] : DVS_DENSIFY_PRUNE;
     const uint32_t cut = block_offsets[gridDim.x];
     const uint32_t quota = blockIdx.x < (cut >> 8) ? (uint32_t)DB : (blockIdx.x == (cut >> 8) ? (cut & 0xffu) : 0u);
     uint32_t tot;
-    const uint32_t ex = d_block_excl_scan((a != DVS_DENSIFY_PRUNE ? 1u : 0u) | (d_grows(a) ? 1u << 16 : 0u), tmp, &tot);
+    const uint32_t ex = dvs_block_excl_scan((a != DVS_DENSIFY_PRUNE ? 1u : 0u) | (d_grows(a) ? 1u << 16 : 0u), tmp, &tot);
     const uint32_t rank = ex >> 16;                                  // growth candidates before i in this block
     if (d_grows(a) && rank >= quota) { a = DVS_DENSIFY_KEEP; action[i] = (uint8_t)a; }
     if (i < n) offsets[i] = block_offsets[blockIdx.x] + (ex & 0xffffu) + min(rank, quota);
@@ -208,7 +198,7 @@ k_densify_apply(int n, const uint8_t* __restrict__ action, const uint32_t* __res
             op = __logf(no / (1.0f - no));
         }
         d_op[j] = fresh ? 0.f : op;
-        for (int e = 0; e < 45; ++e) d_shn[d_shn_index(p.shn_layout, j, e)] = fresh ? 0.f : s_shn[d_shn_index(p.shn_layout, i, e)];
+        for (int e = 0; e < 45; ++e) d_shn[dvs_shn_index(p.shn_layout, j, e)] = fresh ? 0.f : s_shn[dvs_shn_index(p.shn_layout, i, e)];
     }
 }
 
@@ -233,9 +223,13 @@ struct ImpState {
     unsigned long long cut;        // splats equal to S that stay (E - r); n when nothing is pruned
 };
 #define IMP_HIST_WORDS (8 * 256)
-__device__ __forceinline__ ImpState* imp_state(void* scratch) { return (ImpState*)scratch; }
-__device__ __forceinline__ uint32_t* imp_hist(void* scratch) { return (uint32_t*)((char*)scratch + 32); }
-__device__ __forceinline__ uint32_t* imp_blocks(void* scratch) { return imp_hist(scratch) + IMP_HIST_WORDS; }
+// the scratch's three parts; a const scratch gives const parts (k_importance_mark only reads)
+__device__ __forceinline__ const ImpState* imp_state(const void* scratch) { return (const ImpState*)scratch; }
+__device__ __forceinline__ const uint32_t* imp_hist(const void* scratch) { return (const uint32_t*)((const char*)scratch + 32); }
+__device__ __forceinline__ const uint32_t* imp_blocks(const void* scratch) { return imp_hist(scratch) + IMP_HIST_WORDS; }
+__device__ __forceinline__ ImpState* imp_state(void* scratch) { return const_cast<ImpState*>(imp_state((const void*)scratch)); }
+__device__ __forceinline__ uint32_t* imp_hist(void* scratch) { return const_cast<uint32_t*>(imp_hist((const void*)scratch)); }
+__device__ __forceinline__ uint32_t* imp_blocks(void* scratch) { return const_cast<uint32_t*>(imp_blocks((const void*)scratch)); }
 
 __global__ void __launch_bounds__(DB) k_importance_init(void* scratch, unsigned long long n, unsigned long long prune) {
     uint32_t* h = imp_hist(scratch);
@@ -260,12 +254,12 @@ k_importance_hist(int n, const unsigned long long* __restrict__ score, void* scr
 }
 // one workgroup, thread = byte value: the byte g with #{byte < g} < rank <= #{byte <= g}
 __global__ void __launch_bounds__(DB) k_importance_pick(void* scratch, int round) {
-    __shared__ uint32_t tmp[DB / 64 + 1];
+    __shared__ uint32_t tmp[DB / 64];
     ImpState* s = imp_state(scratch);
     const unsigned long long rank = s->rank;
     const uint32_t c = imp_hist(scratch)[round * 256 + threadIdx.x];
     uint32_t tot;
-    const uint32_t below = d_block_excl_scan(c, tmp, &tot);               // (its barriers order the read of rank before the write below)
+    const uint32_t below = dvs_block_excl_scan(c, tmp, &tot);               // (its barriers order the read of rank before the write below)
     if ((unsigned long long)below < rank && rank <= (unsigned long long)below + c) {             // exactly one thread: 1 <= rank <= tot
         s->prefix |= (unsigned long long)threadIdx.x << (56 - 8 * round);
         s->rank = rank - below;
@@ -275,18 +269,18 @@ __global__ void __launch_bounds__(DB) k_importance_pick(void* scratch, int round
 // per block: (splats below S) | (splats equal to S) << 16, both <= DB
 __global__ void __launch_bounds__(DB)
 k_importance_blocksum(int n, const unsigned long long* __restrict__ score, void* scratch) {
-    __shared__ uint32_t tmp[DB / 64 + 1];
+    __shared__ uint32_t tmp[DB / 64];
     const int i = blockIdx.x * DB + threadIdx.x;
     const unsigned long long S = imp_state(scratch)->prefix;
     const unsigned long long k = i < n ? score[i] : ~0ull;
     uint32_t tot;
-    (void)d_block_excl_scan((i < n && k < S ? 1u : 0u) | (i < n && k == S ? 1u << 16 : 0u), tmp, &tot);
+    (void)dvs_block_excl_scan((i < n && k < S ? 1u : 0u) | (i < n && k == S ? 1u << 16 : 0u), tmp, &tot);
     if (threadIdx.x == 0) imp_blocks(scratch)[2 * blockIdx.x] = tot;
 }
 // single workgroup over the nb packed block sums, DB blocks per chunk with a running carry: per block the splats kept before it
 // (its first index - those below S before it - those equal to S before it beyond the first `cut`) and the equal ones before it
 __global__ void __launch_bounds__(DB) k_importance_scan_blocks(void* scratch, uint32_t nb, unsigned long long new_n, uint64_t* __restrict__ new_count) {
-    __shared__ uint32_t tmp[DB / 64 + 1];
+    __shared__ uint32_t tmp[DB / 64];
     uint32_t* blocks = imp_blocks(scratch);
     const unsigned long long cut = imp_state(scratch)->cut;
     unsigned long long cl = 0, ce = 0;
@@ -294,8 +288,8 @@ __global__ void __launch_bounds__(DB) k_importance_scan_blocks(void* scratch, ui
         const uint32_t idx = base + threadIdx.x;
         const uint32_t v = idx < nb ? blocks[2 * idx] : 0u;
         uint32_t tl, te;
-        const unsigned long long el = cl + d_block_excl_scan(v & 0xffffu, tmp, &tl);
-        const unsigned long long ee = ce + d_block_excl_scan(v >> 16, tmp, &te);
+        const unsigned long long el = cl + dvs_block_excl_scan(v & 0xffffu, tmp, &tl);
+        const unsigned long long ee = ce + dvs_block_excl_scan(v >> 16, tmp, &te);
         if (idx < nb) {
             blocks[2 * idx] = (uint32_t)((unsigned long long)idx * DB - el - (ee > cut ? ee - cut : 0ull));
             blocks[2 * idx + 1] = (uint32_t)ee;
@@ -307,17 +301,16 @@ __global__ void __launch_bounds__(DB) k_importance_scan_blocks(void* scratch, ui
 __global__ void __launch_bounds__(DB)
 k_importance_mark(int n, const unsigned long long* __restrict__ score, const void* scratch, uint8_t* __restrict__ action,
                   uint32_t* __restrict__ offsets) {
-    __shared__ uint32_t tmp[DB / 64 + 1];
+    __shared__ uint32_t tmp[DB / 64];
     const int i = blockIdx.x * DB + threadIdx.x;
-    const ImpState* s = (const ImpState*)scratch;
-    const unsigned long long S = s->prefix, cut = s->cut;
-    const uint32_t* blocks = (const uint32_t*)((const char*)scratch + 32) + IMP_HIST_WORDS;
+    const unsigned long long S = imp_state(scratch)->prefix, cut = imp_state(scratch)->cut;
+    const uint32_t* blocks = imp_blocks(scratch);
     const unsigned long long k = i < n ? score[i] : 0ull;
     const bool equal = i < n && k == S;
     uint32_t tot;
-    const uint32_t eq_before = blocks[2 * blockIdx.x + 1] + d_block_excl_scan(equal ? 1u : 0u, tmp, &tot);
+    const uint32_t eq_before = blocks[2 * blockIdx.x + 1] + dvs_block_excl_scan(equal ? 1u : 0u, tmp, &tot);
     const bool kept = i < n && (k > S || (equal && (unsigned long long)eq_before < cut));
-    const uint32_t ex = d_block_excl_scan(kept ? 1u : 0u, tmp, &tot);
+    const uint32_t ex = dvs_block_excl_scan(kept ? 1u : 0u, tmp, &tot);
     if (i < n) {
         action[i] = (uint8_t)(kept ? DVS_DENSIFY_KEEP : DVS_DENSIFY_PRUNE);
         offsets[i] = blocks[2 * blockIdx.x] + ex;
@@ -331,7 +324,7 @@ int dvs_densify_accumulate(void* stream, int n, const int32_t* radii, const floa
     if (n == 0) return DVS_OK;
     hipLaunchKernelGGL(k_densify_accumulate, dim3((n + DB - 1) / DB), dim3(DB), 0, (hipStream_t)stream, n, radii, (const float2*)absgrad2d,
                        0.5f * (float)width, 0.5f * (float)height, grad_accum, denom, max_radii);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 int dvs_densify_accumulate_rows(void* stream, int n, int n_views, const int32_t* radii, const float* rows, int width, int height,
                                 float* grad_accum, float* denom, int32_t* max_radii) {
@@ -339,13 +332,13 @@ int dvs_densify_accumulate_rows(void* stream, int n, int n_views, const int32_t*
     if (n == 0) return DVS_OK;
     hipLaunchKernelGGL(k_densify_accumulate_rows, dim3((n + DB - 1) / DB), dim3(DB), 0, (hipStream_t)stream, n, n_views, radii, rows,
                        0.5f * (float)width, 0.5f * (float)height, grad_accum, denom, max_radii);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 int dvs_any_view_radius(void* stream, int n, int n_views, const int32_t* radii, int32_t* out) {
     if (n < 0 || n_views < 1 || (n > 0 && (!radii || !out))) return DVS_ERR_INVALID;
     if (n == 0) return DVS_OK;
     hipLaunchKernelGGL(k_any_view_radius, dim3((n + DB - 1) / DB), dim3(DB), 0, (hipStream_t)stream, n, n_views, radii, out);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 int dvs_densify_plan(void* stream, int n, const float* opacity, const float* scale, const float* grad_accum, const float* denom,
                      const int32_t* max_radii, const dvs_densify_params* prm, uint8_t* action, uint32_t* offsets, uint32_t* scratch,
@@ -357,7 +350,7 @@ int dvs_densify_plan(void* stream, int n, const float* opacity, const float* sca
     if (nb) hipLaunchKernelGGL(k_densify_blocksum, dim3(nb), dim3(DB), 0, st, n, opacity, scale, grad_accum, denom, max_radii, *prm, action, scratch);
     hipLaunchKernelGGL(k_densify_scan_blocks, dim3(1), dim3(DB), 0, st, scratch, nb, prm->cap_max, new_count);
     if (nb) hipLaunchKernelGGL(k_densify_offsets, dim3(nb), dim3(DB), 0, st, n, action, scratch, offsets);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 int dvs_densify_apply(void* stream, int n, const uint8_t* action, const uint32_t* offsets, const dvs_densify_params* prm, int mode,
                       const float* const src[6], float* const dst[6], int new_n) {
@@ -365,12 +358,12 @@ int dvs_densify_apply(void* stream, int n, const uint8_t* action, const uint32_t
     if (n == 0) return DVS_OK;
     hipLaunchKernelGGL(k_densify_apply, dim3((n + DB - 1) / DB), dim3(DB), 0, (hipStream_t)stream, n, action, offsets, *prm, mode, src[0], src[1],
                        src[2], src[3], src[4], src[5], dst[0], dst[1], dst[2], dst[3], dst[4], dst[5], new_n);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 size_t dvs_importance_scratch_bytes(int n) {
     if (n <= 0) return 0;
     const size_t nb = ((size_t)n + DB - 1) / DB;
-    return (32 + (IMP_HIST_WORDS + 2 * nb) * sizeof(uint32_t) + 255) & ~(size_t)255;
+    return dvs_align256(32 + (IMP_HIST_WORDS + 2 * nb) * sizeof(uint32_t));
 }
 int dvs_importance_plan(void* stream, int n, const uint64_t* score, uint32_t keep, uint8_t* action, uint32_t* offsets, void* scratch,
                         uint64_t* new_count) {
@@ -390,13 +383,13 @@ int dvs_importance_plan(void* stream, int n, const uint64_t* score, uint32_t kee
     hipLaunchKernelGGL(k_importance_blocksum, dim3(nb), dim3(DB), 0, st, n, sc, scratch);
     hipLaunchKernelGGL(k_importance_scan_blocks, dim3(1), dim3(DB), 0, st, scratch, nb, (unsigned long long)kept, new_count);
     hipLaunchKernelGGL(k_importance_mark, dim3(nb), dim3(DB), 0, st, n, sc, (const void*)scratch, action, offsets);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 int dvs_reset_opacity(void* stream, int n, float* opacity, float max_opacity, float* adam_m, float* adam_v) {
     if (n < 0 || (n > 0 && !opacity) || !(max_opacity > 0.f && max_opacity < 1.f)) return DVS_ERR_INVALID;
     if (n == 0) return DVS_OK;
     hipLaunchKernelGGL(k_reset_opacity, dim3((n + DB - 1) / DB), dim3(DB), 0, (hipStream_t)stream, n, opacity,
                        logf(max_opacity / (1.f - max_opacity)), adam_m, adam_v);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 }

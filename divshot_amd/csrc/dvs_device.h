@@ -6,6 +6,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/dvs_raster.h"
+
+// what a C-ABI entry point returns after its launches
+static inline int dvs_launch_status() { return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP; }
+// scratch carving: parts start on 256-byte boundaries
+static inline size_t dvs_align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 #define DVS_TILE 16
 #define DVS_ALPHA_MIN (1.0f / 255.0f)
@@ -62,6 +68,24 @@ __device__ __forceinline__ DvsCam dvs_load_cam(int v) {
     for (int k = 0; k < (int)(sizeof(DvsCam) / 4); ++k) d[k] = w[k];
     return cam;
 }
+// One word of type T at a byte offset of the kernarg segment: the typed reader for whatever else a kernel indexes by a runtime view number
+// (pixel_ray.h's matrices, region.hip's origins and pointers).
+template <class T> __device__ __forceinline__ T dvs_karg(size_t byte_offset) {
+    typedef const __attribute__((address_space(4))) T* KP;
+    return *(KP)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + byte_offset);
+}
+
+// Address of element e (0..44) of splat i's shN: the ONE definition densify.hip's split / clone and mcmc.hip's relocation share.
+__device__ __forceinline__ int64_t dvs_shn_index(int layout, int i, int e) {
+    return layout == DVS_SHN_TILED ? ((((int64_t)(i >> 6) * 12 + (e >> 2)) * 64 + (i & 63)) * 4 + (e & 3)) : ((int64_t)i * 45 + e);
+}
+// counter-based RNG: one 32-bit hash per (seed, index, draw), and the uniform in (0, 1) of its high 24 bits
+__device__ __forceinline__ uint32_t dvs_hash3(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ (c + 0x165667B1u) * 0xC2B2AE3Du;
+    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
+    return h;
+}
+__device__ __forceinline__ float dvs_uniform24(uint32_t h) { return ((h >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
 // Deterministic exp: exp feeds integer decisions (scale -> cov -> radius -> tile rect), so it is a
 // fixed sequence of IEEE-exact operations (v_rndne, v_fma, v_mul, v_add, exponent insert), not

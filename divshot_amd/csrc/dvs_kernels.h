@@ -180,9 +180,12 @@ hipError_t dvs_launch_render_bwd_blocks(hipStream_t st, int W, int H, int tiles_
 size_t dvs_morton_scratch_bytes(int n);
 hipError_t dvs_launch_morton_order(hipStream_t st, int n, const float* pos, void* scratch, const uint32_t** sorted, const float** bounds);
 
-// mesh.hip — for mesh_clean.hip: the extraction's exclusive scan, in place, of n > 0 words (reduce, one workgroup over the block sums,
-// rescan): bsum = ceil(n / DVS_SCAN_TILE) words of scratch, *total (device) = the sum in 64 bits. And the byte offsets, inside the
-// scratch of dvs_mesh_extract_count, of vert_off [voxels] (uint32) and flags [voxels] (uint8); false for dims the extraction refuses.
+// scan.hip — the exclusive scan, in place, of n > 0 words (reduce, one workgroup over the block sums, rescan): bsum =
+// ceil(n / DVS_SCAN_TILE) words of scratch, *total (device) = the sum in 64 bits. And its middle step alone, for a caller that made the
+// block sums itself: bsum [nb] -> exclusive offsets in place (32-bit words), *total = the sum in 64 bits; nb = 0 leaves *total = 0.
 #define DVS_SCAN_TILE 2048
 hipError_t dvs_launch_scan_u32(hipStream_t st, uint32_t* v, size_t n, uint32_t* bsum, unsigned long long* total);
+__attribute__((visibility("hidden"))) hipError_t dvs_launch_block_sums_excl(hipStream_t st, uint32_t* bsum, uint32_t nb, unsigned long long* total);
+// mesh.hip — for mesh_clean.hip: the byte offsets, inside the scratch of dvs_mesh_extract_count, of vert_off [voxels] (uint32) and
+// flags [voxels] (uint8); false for dims the extraction refuses.
 bool dvs_mesh_scratch_parts(const int32_t dims[3], size_t* vert_off, size_t* flags);

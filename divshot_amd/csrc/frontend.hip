@@ -25,14 +25,14 @@
 #include <cstdlib>
 #include "dvs_device.h"
 #include "dvs_kernels.h"
+#include "block_scan.h"
 
 #define FE_BLOCK 256
+static_assert(FE_BLOCK == DB, "block_scan.h scans a workgroup of DB threads");
 #define FE_WAVES (FE_BLOCK / 64)
 #define FE_MAXBINS DVS_FE_MAXBINS // (dvs_kernels.h: the host sizes the totals table with it)
 #define FE_REORDER_BITS 9         // digits up to this width are re-ordered in LDS before the global stores
 #define FE_CULLED 0xFFFFFFFFu
-
-__device__ __forceinline__ uint32_t fe_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 
 // peers = lanes of this wave holding the same b-bit digit (invalid lanes never match valid ones). Per bit: the lane's bit as a 0 / ~0 word
 // (v_bfe_i32), its ballot, and ONE v_bitop3_b32 per mask half — peers & ~(ballot ^ word) keeps the lanes whose bit equals this lane's —
@@ -50,33 +50,6 @@ __device__ __forceinline__ uint64_t fe_match(uint32_t d, bool valid, uint32_t b)
     return valid ? peers : 0ull;
 }
 
-// Wave64 inclusive prefix sum in six DPP additions (gfx9 row operations: shift right by 1, 2, 4, 8 inside the 16-lane rows, then lane 15
-// of rows 0 / 2 into rows 1 / 3, then lane 31 into rows 2 / 3). No LDS crossbar round trip per step (a __shfl_up step is a ds_bpermute:
-// ~60 cycles of latency on a dependent chain).
-__device__ __forceinline__ uint32_t fe_wave_incl_scan(uint32_t v) {
-#define FE_DPP_ADD(ctrl, rmask) v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ctrl, rmask, 0xF, false)
-    FE_DPP_ADD(0x111, 0xF); FE_DPP_ADD(0x112, 0xF); FE_DPP_ADD(0x114, 0xF); FE_DPP_ADD(0x118, 0xF);   // row_shr:1, 2, 4, 8
-    FE_DPP_ADD(0x142, 0xA);                                                                              // row_bcast:15 -> rows 1, 3
-    FE_DPP_ADD(0x143, 0xC);                                                                              // row_bcast:31 -> rows 2, 3
-#undef FE_DPP_ADD
-    return v;
-}
-__device__ __forceinline__ uint32_t fe_wave_sum(uint32_t v) { return (uint32_t)__builtin_amdgcn_readlane((int)fe_wave_incl_scan(v), 63); }
-
-// block-wide exclusive scan of one uint32 per thread (256 threads); tmp = LDS[FE_WAVES]
-__device__ __forceinline__ uint32_t fe_block_excl_scan(uint32_t v, uint32_t* tmp, uint32_t* total) {
-    const uint32_t lane = fe_lane(), wave = threadIdx.x >> 6;
-    const uint32_t inc = fe_wave_incl_scan(v);
-    if (lane == 63) tmp[wave] = inc;
-    __syncthreads();
-    uint32_t wbase = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < FE_WAVES; ++w) { const uint32_t t = tmp[w]; if ((uint32_t)w < wave) wbase += t; tot += t; }
-    __syncthreads();
-    *total = tot;
-    return wbase + inc - v;
-}
-
 // ---- segmented LSD pass = per-partition digit histogram, row scan, scatter --------------------------------------------------------
 // A pass is described by (adaptive, pass, shift, bits): adaptive = the depth sort (digit width and key offset per view from the
 // segment descriptor, shift = pass * width), otherwise the given shift / width (tile sort, dvs_sort_pairs_u32).
@@ -90,7 +63,7 @@ k_seg_hist(const uint32_t* __restrict__ keys, DvsSeg* __restrict__ seg, int V, i
            uint32_t* __restrict__ hist, uint32_t nbtot, const uint32_t* __restrict__ kred, int key16 /*the keys are 16-bit (A4's tile ids)*/) {
     __shared__ uint32_t h[FE_MAXBINS];
     constexpr uint32_t PART = FE_BLOCK * ITEMS;
-    const uint32_t lane = fe_lane(), wave = threadIdx.x >> 6, tid = threadIdx.x;
+    const uint32_t lane = dvs_lane(), wave = threadIdx.x >> 6, tid = threadIdx.x;
     const uint32_t view = blockIdx.x % (uint32_t)V, w = blockIdx.x / (uint32_t)V, gv = gridDim.x / (uint32_t)V;
     const uint32_t s_base = seg[view].base, s_count = seg[view].count, s_pstart = seg[view].pstart;
     uint32_t b = (uint32_t)bits_s, shift = (uint32_t)shift_s, sub = 0u;
@@ -144,7 +117,7 @@ k_seg_hist(const uint32_t* __restrict__ keys, DvsSeg* __restrict__ seg, int V, i
 __global__ void __launch_bounds__(FE_BLOCK)
 k_seg_rowscan(uint32_t* __restrict__ hist, uint32_t nbtot, const DvsSeg* __restrict__ seg, int V, int adaptive, int bits_s, uint32_t part,
               uint32_t* __restrict__ totals) {
-    const uint32_t lane = fe_lane(), wave = threadIdx.x >> 6;
+    const uint32_t lane = dvs_lane(), wave = threadIdx.x >> 6;
     const uint32_t view = blockIdx.x % (uint32_t)V, d = (blockIdx.x / (uint32_t)V) * FE_WAVES + wave;
     const uint32_t b = adaptive ? seg[view].bits : (uint32_t)bits_s;
     if (d >= (1u << b)) return;
@@ -159,7 +132,7 @@ k_seg_rowscan(uint32_t* __restrict__ hist, uint32_t nbtot, const DvsSeg* __restr
         for (int k = 0; k < 16; ++k) {
             if (c0 + (uint32_t)k * 64 < nparts) {                  // (uniform)
                 const uint32_t i = c0 + (uint32_t)k * 64 + lane;
-                const uint32_t inc = fe_wave_incl_scan(v[k]);
+                const uint32_t inc = dvs_wave_incl_scan(v[k]);
                 if (i < nparts) row[i] = carry + inc - v[k];
                 carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
             }
@@ -204,7 +177,7 @@ k_seg_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__
               from all partitions leave (~start, end); k_render_fwd turns that into (start, end)*/) {
     constexpr uint32_t PART = FE_BLOCK * ITEMS;
     __shared__ __attribute__((aligned(16))) uint32_t lds[FeScatterLds<ITEMS>::WORDS];
-    const uint32_t lane = fe_lane(), wave = threadIdx.x >> 6, tid = threadIdx.x;
+    const uint32_t lane = dvs_lane(), wave = threadIdx.x >> 6, tid = threadIdx.x;
     const uint32_t view = blockIdx.x % (uint32_t)V, w = blockIdx.x / (uint32_t)V, gv = gridDim.x / (uint32_t)V;
     const DvsSeg S = seg_in[view];
     const uint32_t b = adaptive ? S.bits : (uint32_t)bits_s;
@@ -268,7 +241,7 @@ k_seg_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__
             for (uint32_t k = 0; k < 8; ++k) { const uint32_t d = tid * 8u + k; s += d < nbins ? vtot[d] : 0u; }
         }
         uint32_t tot;
-        const uint32_t off = fe_block_excl_scan(s, tmp, &tot);
+        const uint32_t off = dvs_block_excl_scan(s, tmp, &tot);
         if (!wide) { dex0 = off; dex1 += off; }
         else {
             uint32_t run = off;
@@ -327,7 +300,7 @@ k_seg_scatter(const uint32_t* __restrict__ keys_in, const uint32_t* __restrict__
                 c0[wv] = two & 0xFFFFu; c1[wv] = two >> 16; bc0 += c0[wv]; bc1 += c1[wv];
             }
             uint32_t nvalid;
-            uint32_t run = fe_block_excl_scan(bc0 + bc1, tmp, &nvalid);               // where the thread's first bin starts in the stage
+            uint32_t run = dvs_block_excl_scan(bc0 + bc1, tmp, &nvalid);               // where the thread's first bin starts in the stage
             gdelta[tid * 2u] = dex0 + hp0 - run;                                       // global position of stage slot s with digit d = gdelta[d] + s
             gdelta[tid * 2u + 1u] = dex1 + hp1 - (run + bc0);
             uint32_t run1 = run + bc0;
@@ -508,7 +481,7 @@ __global__ void __launch_bounds__(FE_BLOCK)
 k_fe_probe_rank_atomic(uint32_t* __restrict__ bad, uint32_t seed) {
     __shared__ uint32_t cnt_a[FE_WAVES * 256];             // packed u16 counters, atomic form: 512 digits per wave
     __shared__ uint16_t cnt_b[FE_WAVES * 512];             // ballot form
-    const uint32_t lane = fe_lane(), wave = threadIdx.x >> 6;
+    const uint32_t lane = dvs_lane(), wave = threadIdx.x >> 6;
     uint32_t errs = 0;
     for (uint32_t pat = 0; pat < 24; ++pat) {
         for (uint32_t e = threadIdx.x; e < FE_WAVES * 256; e += FE_BLOCK) cnt_a[e] = 0u;
@@ -571,7 +544,7 @@ k_seg_blocksum(int n, int V, uint32_t nbv, uint32_t nsb, const DvsSeg* __restric
     const uint32_t nvis = seg_vis[view].count;
     if (blk0 * FE_BLOCK >= nvis) return;                      // (uniform; A4 never reads the sums of blocks behind the visible splats)
     const size_t o = (size_t)view * n;
-    const uint32_t lane = fe_lane(), wave = threadIdx.x >> 6;
+    const uint32_t lane = dvs_lane(), wave = threadIdx.x >> 6;
     uint32_t id[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) { const uint32_t j = (blk0 + (uint32_t)k) * FE_BLOCK + threadIdx.x; id[k] = j < nvis ? sorted_ids[o + j] : 0u; }
@@ -583,7 +556,7 @@ k_seg_blocksum(int n, int V, uint32_t nbv, uint32_t nsb, const DvsSeg* __restric
         const uint32_t j = (blk0 + (uint32_t)k) * FE_BLOCK + threadIdx.x;
         uint32_t v = 0;
         if (j < nvis) { rect_sorted[o + j] = r[k]; v = FeRect<FMT>::count(r[k]); }
-        const uint32_t s = fe_wave_sum(v);
+        const uint32_t s = dvs_wave_sum(v);
         if (lane == 0) wsum[k][wave] = s;
     }
     __syncthreads();
@@ -608,7 +581,7 @@ __global__ void __launch_bounds__(1024)
 k_seg_totals(int V, uint32_t nsb, const unsigned long long* __restrict__ super, uint32_t* __restrict__ superexcl, DvsSeg* __restrict__ seg_tile,
              uint32_t tile_part, unsigned long long* __restrict__ total, unsigned long long capacity) {
     __shared__ unsigned long long vsum[DVS_MAX_VIEWS];
-    const uint32_t lane = fe_lane(), wave = threadIdx.x >> 6;
+    const uint32_t lane = dvs_lane(), wave = threadIdx.x >> 6;
     if (wave < (uint32_t)V) {
         unsigned long long carry = 0ull;
         for (uint32_t c0 = 0; c0 < nsb; c0 += 64) {
@@ -690,7 +663,7 @@ k_seg_duplicate(int n, int V, uint32_t nbv, uint32_t nsb, const DvsSeg* __restri
     const uint32_t nvis = seg_vis[view].count;
     if (blk0 * FE_BLOCK >= nvis) return;
     const size_t o = (size_t)view * n;
-    const uint32_t lane = fe_lane(), w0 = (threadIdx.x >> 6) * 64u;
+    const uint32_t lane = dvs_lane(), w0 = (threadIdx.x >> 6) * 64u;
     uint32_t id[2] = {0u, 0u};
     typename FeRect<FMT>::T r[2] = {FeRect<FMT>::zero(), FeRect<FMT>::zero()};
 #pragma unroll
@@ -704,12 +677,12 @@ k_seg_duplicate(int n, int V, uint32_t nbv, uint32_t nsb, const DvsSeg* __restri
     const unsigned long long vbase = (unsigned long long)seg_tile[view].base + superexcl[(size_t)view * nsb + sb];
     // (seg_tile.base is the clamped start: when it was clamped the forward has overflowed and every store below is dropped)
     uint32_t before, tot;
-    (void)fe_block_excl_scan(part, tmp, &before);
+    (void)dvs_block_excl_scan(part, tmp, &before);
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         if ((blk0 + (uint32_t)h) * FE_BLOCK >= nvis) break;        // (uniform)
         const uint32_t touched = FeRect<FMT>::count(r[h]);          // (0 for the lanes behind the visible splats: zero rectangle)
-        const uint32_t pre = fe_block_excl_scan(touched, tmp, &tot);
+        const uint32_t pre = dvs_block_excl_scan(touched, tmp, &tot);
         s_pre[threadIdx.x] = pre;
         s_id[threadIdx.x] = (uint32_t)o + id[h];
         s_tile[threadIdx.x] = FeRect<FMT>::miny(r[h]) * (uint32_t)tiles_x + FeRect<FMT>::minx(r[h]);

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/dvs_raster.h"
+#include "dvs_device.h"
 #include "../../include/dvs_image.h"
 
 namespace {
@@ -201,5 +202,5 @@ extern "C" int dvs_jpeg_reconstruct(void* stream, const dvs_jpeg_desc* desc, con
     const bool vec = ((uintptr_t)rgb & 15u) == 0 && desc->width % 16 == 0;
     if (vec) hipLaunchKernelGGL(k_jpeg_reconstruct<true>, grid, dim3(JP_BLOCK), 0, (hipStream_t)stream, *desc, coef, rgb);
     else hipLaunchKernelGGL(k_jpeg_reconstruct<false>, grid, dim3(JP_BLOCK), 0, (hipStream_t)stream, *desc, coef, rgb);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }

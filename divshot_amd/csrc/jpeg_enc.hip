@@ -27,6 +27,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "../../include/dvs_raster.h"
+#include "dvs_device.h"
 #include "../../include/dvs_image.h"
 
 namespace {
@@ -267,5 +268,5 @@ extern "C" int dvs_jpeg_encode_views(void* stream, const dvs_jpeg_desc* desc, co
     const dim3 grid((unsigned)((mx + JE_TBX - 1) / JE_TBX), (unsigned)((my + JE_TBY - 1) / JE_TBY), (unsigned)n_views);
     if (vec) hipLaunchKernelGGL(k_jpeg_encode<true>, grid, dim3(JE_BLOCK), 0, (hipStream_t)stream, *desc, V);
     else hipLaunchKernelGGL(k_jpeg_encode<false>, grid, dim3(JE_BLOCK), 0, (hipStream_t)stream, *desc, V);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }

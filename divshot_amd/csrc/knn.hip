@@ -180,7 +180,7 @@ int knn_run(hipStream_t st, int n, const float* pos, void* scratch, float* dist2
     hipLaunchKernelGGL(k_knn_gather, dim3((unsigned)n_boxes), dim3(KN_BLOCK), 0, st, n, sorted, pos, rec, box);
     const unsigned sblocks = (unsigned)(((int64_t)n + KN_BLOCK - 1) / KN_BLOCK);
     hipLaunchKernelGGL(k_knn_search, dim3(sblocks), dim3(KN_BLOCK), 0, st, n, n_boxes, (const float4*)rec, (const float4*)box, dist2, visited);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 }  // namespace
 
@@ -206,5 +206,5 @@ extern "C" int dvs_init_from_points(void* stream, int n, const float* pos, const
     const unsigned nblocks = (unsigned)(((int64_t)n + KN_BLOCK - 1) / KN_BLOCK);
     hipLaunchKernelGGL(k_init_from_points, dim3(nblocks), dim3(KN_BLOCK), 0, (hipStream_t)stream, n, rgb, dist2, opacity0, sh0, opacity, scale,
                        (float4*)rot);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }

@@ -18,15 +18,6 @@
 #define MB 256
 #define MCMC_NMAX 51
 
-__device__ __forceinline__ int64_t m_shn_index(int layout, int i, int e) {
-    return layout == DVS_SHN_TILED ? ((((int64_t)(i >> 6) * 12 + (e >> 2)) * 64 + (i & 63)) * 4 + (e & 3)) : ((int64_t)i * 45 + e);
-}
-__device__ __forceinline__ uint32_t m_hash(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ (c + 0x165667B1u) * 0xC2B2AE3Du;
-    h ^= h >> 15; h *= 0x2C1B3C6Du; h ^= h >> 12; h *= 0x297A2D39u; h ^= h >> 15;
-    return h;
-}
-__device__ __forceinline__ float m_uniform(uint32_t h) { return ((h >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 __device__ __forceinline__ float m_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
 
 // scratch layout (one allocation, see dvs_mcmc_scratch_bytes)
@@ -41,28 +32,29 @@ struct McmcScratch {
     double* total_w;      // [1]
     uint32_t* n_dead;     // [1]
 };
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 static McmcScratch carve(void* base, size_t cap) {
     const size_t nb = (cap + MB - 1) / MB + 1;
     char* p = (char*)base;
     McmcScratch s;
-    s.cdf = (double*)p; p += align256(cap * 8);
-    s.blk_w = (double*)p; p += align256(nb * 8);
-    s.dead_pos = (uint32_t*)p; p += align256(cap * 4);
-    s.blk_d = (uint32_t*)p; p += align256(nb * 4);
-    s.dead_list = (uint32_t*)p; p += align256(cap * 4);
-    s.src = (uint32_t*)p; p += align256(cap * 4);
-    s.count = (uint32_t*)p; p += align256(cap * 4);
+    s.cdf = (double*)p; p += dvs_align256(cap * 8);
+    s.blk_w = (double*)p; p += dvs_align256(nb * 8);
+    s.dead_pos = (uint32_t*)p; p += dvs_align256(cap * 4);
+    s.blk_d = (uint32_t*)p; p += dvs_align256(nb * 4);
+    s.dead_list = (uint32_t*)p; p += dvs_align256(cap * 4);
+    s.src = (uint32_t*)p; p += dvs_align256(cap * 4);
+    s.count = (uint32_t*)p; p += dvs_align256(cap * 4);
     s.total_w = (double*)p; p += 256;
     s.n_dead = (uint32_t*)p; p += 256;
     return s;
 }
 static size_t scratch_bytes(size_t cap) {
     const size_t nb = (cap + MB - 1) / MB + 1;
-    return align256(cap * 8) + align256(nb * 8) + 4 * align256(cap * 4) + align256(nb * 4) + 512;
+    return dvs_align256(cap * 8) + dvs_align256(nb * 8) + 4 * dvs_align256(cap * 4) + dvs_align256(nb * 4) + 512;
 }
 
 // block-level inclusive scans (fp64 weights, u32 dead flags) ------------------------------------------------------------
+// Not block_scan.h's: the two scans are fused, and the order of the fp64 additions (six shuffle steps, then the waves in turn) defines
+// the cdf bit for bit.
 __device__ __forceinline__ void m_block_scan(double w, uint32_t d, double* tw, uint32_t* td, double* inc_w, uint32_t* exc_d,
                                              double* tot_w, uint32_t* tot_d) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -132,7 +124,7 @@ k_mcmc_sample(int n, int k_fixed, const uint32_t* __restrict__ k_dev, const doub
     if (j >= k) return;
     const double tot = *total_w;
     if (!(tot > 0.0)) { src[j] = 0xffffffffu; return; }             // nothing alive: leave the destinations alone
-    const uint32_t h0 = m_hash(seed, (uint32_t)j, 0u), h1 = m_hash(seed, (uint32_t)j, 1u);
+    const uint32_t h0 = dvs_hash3(seed, (uint32_t)j, 0u), h1 = dvs_hash3(seed, (uint32_t)j, 1u);
     const double u = (((double)h0 * 4294967296.0 + (double)h1) + 0.5) * (1.0 / 18446744073709551616.0) * tot;
     int lo = 0, hi = n - 1;
     while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf[mid] > u) hi = mid; else lo = mid + 1; }
@@ -178,11 +170,11 @@ k_mcmc_copy(int n, int k_fixed, const uint32_t* __restrict__ k_dev, const uint32
 #pragma unroll
     for (int c = 0; c < 4; ++c) S.p[5][4 * (int64_t)d + c] = S.p[5][4 * (int64_t)s + c];
     S.p[3][d] = __logf(no / (1.0f - no));
-    for (int e = 0; e < 45; ++e) S.p[2][m_shn_index(layout, d, e)] = S.p[2][m_shn_index(layout, (int)s, e)];
+    for (int e = 0; e < 45; ++e) S.p[2][dvs_shn_index(layout, d, e)] = S.p[2][dvs_shn_index(layout, (int)s, e)];
     for (int g = 0; g < 6; ++g) {
         const int w = g == 2 ? 45 : (g == 3 ? 1 : (g == 5 ? 4 : 3));
         for (int e = 0; e < w; ++e) {
-            const int64_t at = g == 2 ? m_shn_index(layout, d, e) : (int64_t)d * w + e;
+            const int64_t at = g == 2 ? dvs_shn_index(layout, d, e) : (int64_t)d * w + e;
             if (S.m[g]) S.m[g][at] = 0.f;
             if (S.v[g]) S.v[g][at] = 0.f;
         }
@@ -204,7 +196,7 @@ k_mcmc_update_src(int n, uint32_t* __restrict__ count, float min_opacity, int la
     for (int g = 0; g < 6; ++g) {
         const int w = g == 2 ? 45 : (g == 3 ? 1 : (g == 5 ? 4 : 3));
         for (int e = 0; e < w; ++e) {
-            const int64_t at = g == 2 ? m_shn_index(layout, i, e) : (int64_t)i * w + e;
+            const int64_t at = g == 2 ? dvs_shn_index(layout, i, e) : (int64_t)i * w + e;
             if (S.m[g]) S.m[g][at] = 0.f;
             if (S.v[g]) S.v[g][at] = 0.f;
         }
@@ -229,7 +221,7 @@ k_mcmc_noise(int i0, int n /*the splats [i0, n)*/, float* __restrict__ pos, cons
     for (int k = 0; k < 3; ++k) {
         const float e = __expf(scale[3 * (int64_t)i + k]);
         s2[k] = e * e;
-        const float u1 = m_uniform(m_hash(seed, (uint32_t)i, 2u * k)), u2 = m_uniform(m_hash(seed, (uint32_t)i, 2u * k + 1u));
+        const float u1 = dvs_uniform24(dvs_hash3(seed, (uint32_t)i, 2u * k)), u2 = dvs_uniform24(dvs_hash3(seed, (uint32_t)i, 2u * k + 1u));
         z[k] = sqrtf(-2.0f * __logf(u1)) * __cosf(6.2831853f * u2) * gate * lr;
     }
     // Sigma z = R diag(s^2) R^T z
@@ -267,7 +259,7 @@ static int run_draws(hipStream_t st, int n, int k_fixed, bool relocate, int dst_
     hipLaunchKernelGGL(k_mcmc_copy, dim3(kb), dim3(MB), 0, st, n, k_fixed, relocate ? S.n_dead : nullptr, relocate ? S.dead_list : nullptr,
                        dst_base, S.src, S.count, min_opacity, layout, D);
     hipLaunchKernelGGL(k_mcmc_update_src, dim3(nb), dim3(MB), 0, st, n, S.count, min_opacity, layout, D);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 
 extern "C" {
@@ -302,7 +294,7 @@ int dvs_mcmc_add_noise_range(void* stream, int n, int first, int count, float* p
     if (n < 0 || first < 0 || count < 0 || first + count > n || (n > 0 && (!pos || !scale || !rot || !opacity))) return DVS_ERR_INVALID;
     if (count == 0 || lr == 0.f) return DVS_OK;
     hipLaunchKernelGGL(k_mcmc_noise, dim3((count + MB - 1) / MB), dim3(MB), 0, (hipStream_t)stream, first, first + count, pos, scale, rot, opacity, lr, seed);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 int dvs_mcmc_add_noise(void* stream, int n, float* pos, const float* scale, const float* rot, const float* opacity, float lr, uint32_t seed) {
     return dvs_mcmc_add_noise_range(stream, n, 0, n, pos, scale, rot, opacity, lr, seed);
@@ -314,7 +306,7 @@ int dvs_mcmc_regularize_range(void* stream, int n, int first, int count, const f
     if (count == 0) return DVS_OK;
     hipLaunchKernelGGL(k_mcmc_regularize, dim3((count + MB - 1) / MB), dim3(MB), 0, (hipStream_t)stream, first, first + count, opacity, scale, g_opacity, g_scale,
                        opacity_reg / (float)n, scale_reg / (3.0f * (float)n));
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 int dvs_mcmc_regularize(void* stream, int n, const float* opacity, const float* scale, float* g_opacity, float* g_scale, float opacity_reg,
                         float scale_reg) {

@@ -9,8 +9,7 @@
 //   k_mesh_tricount   tri_off[v]   = triangles of cell v (0 if it does not take part)
 //   scan              tri_off      -> exclusive
 //   k_mesh_verts / k_mesh_tris     write the arrays
-// The scan is a plain reduce-then-scan: block sums of 2048 elements, one workgroup scans the block sums with a 64-bit carry, the
-// blocks rescan their elements from their offset.
+// The scan is scan.hip's (dvs_launch_scan_u32), with ceil(voxels / DVS_SCAN_TILE) block sums each.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -19,9 +18,6 @@
 #include "dvs_kernels.h"
 
 #define MB 256
-#define SCAN_ITEMS 8
-#define SCAN_TILE (MB * SCAN_ITEMS)
-static_assert(SCAN_TILE == DVS_SCAN_TILE, "dvs_kernels.h tells the scan's other users how many block sums it needs");
 
 namespace {
 struct GridDims { int dx, dy, dz; };
@@ -29,7 +25,6 @@ __host__ __device__ inline size_t grid_voxels(const GridDims& g) { return (size_
 bool dims_ok(const int32_t d[3]) { return d && d[0] >= 2 && d[1] >= 2 && d[2] >= 2 && d[0] <= DVS_TSDF_MAX_DIM && d[1] <= DVS_TSDF_MAX_DIM && d[2] <= DVS_TSDF_MAX_DIM; }
 bool grid_ok(const dvs_tsdf_grid* g) { return g && dims_ok(g->dims) && g->voxel > 0.f && g->tsdf && g->weight && g->rgb; }
 unsigned blocks_for(size_t n) { return (unsigned)((n + MB - 1) / MB); }
-size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // ---- the 16-case table of the six tetrahedra, derived at compile time -------------------------------------------------------------
 // Tetrahedron t has the cell corners c[0] = 0, c[1] = 1 << p0, c[2] = c[1] | 1 << p1, c[3] = 7 for the t-th permutation (p0, p1, p2) of
@@ -86,60 +81,6 @@ __device__ __forceinline__ uint32_t tet_case(uint32_t cube, int t) {
     const int p0 = t >> 1, p1 = (t & 1) ? (p0 == 2 ? 1 : 2) : (p0 == 0 ? 1 : 0);
     const uint32_t c1 = 1u << p0, c2 = c1 | (1u << p1);
     return (cube & 1u) | (((cube >> c1) & 1u) << 1) | (((cube >> c2) & 1u) << 2) | (((cube >> 7) & 1u) << 3);
-}
-
-__device__ __forceinline__ uint32_t m_lane() { return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-// exclusive scan of one value per thread over the workgroup; *total = the workgroup's sum. tmp: MB / 64 words of LDS.
-__device__ __forceinline__ uint32_t m_block_excl_scan(uint32_t v, uint32_t* tmp, uint32_t* total) {
-    const uint32_t lane = m_lane(), wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= (uint32_t)d) inc += o; }
-    if (lane == 63) tmp[wave] = inc;
-    __syncthreads();
-    uint32_t wbase = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < MB / 64; ++w) { const uint32_t s = tmp[w]; if ((uint32_t)w < wave) wbase += s; tot += s; }
-    __syncthreads();
-    *total = tot;
-    return wbase + inc - v;
-}
-
-// ---- scan ---------------------------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(MB) k_scan_reduce(const uint32_t* __restrict__ v, size_t n, uint32_t* __restrict__ bsum) {
-    __shared__ uint32_t tmp[MB / 64];
-    const size_t first = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
-    uint32_t s = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) if (first + k < n) s += v[first + k];
-    uint32_t tot;
-    (void)m_block_excl_scan(s, tmp, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-// one workgroup: block sums -> exclusive offsets (32-bit words; the true total in 64 bits, for the caller's range check)
-__global__ void __launch_bounds__(MB) k_scan_block_sums(uint32_t* __restrict__ bsum, uint32_t nb, unsigned long long* __restrict__ total) {
-    __shared__ uint32_t tmp[MB / 64];
-    unsigned long long carry = 0;
-    for (uint32_t base = 0; base < nb; base += MB) {
-        const uint32_t i = base + threadIdx.x;
-        const uint32_t s = i < nb ? bsum[i] : 0u;
-        uint32_t tot;
-        const uint32_t ex = m_block_excl_scan(s, tmp, &tot);
-        if (i < nb) bsum[i] = (uint32_t)carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) *total = carry;
-}
-__global__ void __launch_bounds__(MB) k_scan_apply(uint32_t* __restrict__ v, size_t n, const uint32_t* __restrict__ bsum) {
-    __shared__ uint32_t tmp[MB / 64];
-    const size_t first = (size_t)blockIdx.x * SCAN_TILE + (size_t)threadIdx.x * SCAN_ITEMS;
-    uint32_t item[SCAN_ITEMS], s = 0;
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) { item[k] = first + k < n ? v[first + k] : 0u; s += item[k]; }
-    uint32_t tot;
-    uint32_t run = bsum[blockIdx.x] + m_block_excl_scan(s, tmp, &tot);
-#pragma unroll
-    for (int k = 0; k < SCAN_ITEMS; ++k) { if (first + k < n) v[first + k] = run; run += item[k]; }
 }
 
 // ---- TSDF ---------------------------------------------------------------------------------------------------------------------
@@ -311,30 +252,21 @@ k_mesh_tris(GridDims g, const float* __restrict__ tsdf, const uint8_t* __restric
 struct MeshScratch { size_t vert_off, tri_off, flags, cell_ok, bsum_v, bsum_t, totals, total; uint32_t nb; };
 MeshScratch mesh_layout(size_t nv) {
     MeshScratch L{};
-    L.nb = (uint32_t)((nv + SCAN_TILE - 1) / SCAN_TILE);
+    L.nb = (uint32_t)((nv + DVS_SCAN_TILE - 1) / DVS_SCAN_TILE);
     size_t o = 0;
-    L.vert_off = o; o = align256(o + nv * 4);
-    L.tri_off = o; o = align256(o + nv * 4);
-    L.flags = o; o = align256(o + nv);
-    L.cell_ok = o; o = align256(o + nv);
-    L.bsum_v = o; o = align256(o + (size_t)L.nb * 4);
-    L.bsum_t = o; o = align256(o + (size_t)L.nb * 4);
-    L.totals = o; o = align256(o + 16);
+    L.vert_off = o; o = dvs_align256(o + nv * 4);
+    L.tri_off = o; o = dvs_align256(o + nv * 4);
+    L.flags = o; o = dvs_align256(o + nv);
+    L.cell_ok = o; o = dvs_align256(o + nv);
+    L.bsum_v = o; o = dvs_align256(o + (size_t)L.nb * 4);
+    L.bsum_t = o; o = dvs_align256(o + (size_t)L.nb * 4);
+    L.totals = o; o = dvs_align256(o + 16);
     L.total = o;
     return L;
 }
-hipError_t scan_in_place(hipStream_t st, uint32_t* v, size_t n, uint32_t* bsum, uint32_t nb, unsigned long long* total) {
-    hipLaunchKernelGGL(k_scan_reduce, dim3(nb), dim3(MB), 0, st, (const uint32_t*)v, n, bsum);
-    hipLaunchKernelGGL(k_scan_block_sums, dim3(1), dim3(MB), 0, st, bsum, nb, total);
-    hipLaunchKernelGGL(k_scan_apply, dim3(nb), dim3(MB), 0, st, v, n, (const uint32_t*)bsum);
-    return hipGetLastError();
-}
 }  // namespace
 
-// for mesh_clean.hip (dvs_kernels.h): the same scan, and where the extraction's scratch keeps what the normals read
-hipError_t dvs_launch_scan_u32(hipStream_t st, uint32_t* v, size_t n, uint32_t* bsum, unsigned long long* total) {
-    return scan_in_place(st, v, n, bsum, (uint32_t)((n + SCAN_TILE - 1) / SCAN_TILE), total);
-}
+// for mesh_clean.hip (dvs_kernels.h): where the extraction's scratch keeps what the normals read
 bool dvs_mesh_scratch_parts(const int32_t dims[3], size_t* vert_off, size_t* flags) {
     if (!dims_ok(dims)) return false;
     const MeshScratch L = mesh_layout((size_t)dims[0] * dims[1] * dims[2]);
@@ -348,7 +280,7 @@ extern "C" int dvs_tsdf_clear(void* stream, const dvs_tsdf_grid* grid) {
     if (!grid_ok(grid)) return DVS_ERR_INVALID;
     const size_t nv = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];
     hipLaunchKernelGGL(k_tsdf_clear, dim3(blocks_for(nv)), dim3(MB), 0, (hipStream_t)stream, nv, grid->tsdf, grid->weight, grid->rgb);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 
 extern "C" int dvs_tsdf_create(const float origin[3], float voxel, const int32_t dims[3], dvs_tsdf_grid* out) {
@@ -390,7 +322,7 @@ extern "C" int dvs_tsdf_integrate(void* stream, const dvs_tsdf_grid* grid, const
     const GridDims g{grid->dims[0], grid->dims[1], grid->dims[2]};
     hipLaunchKernelGGL(k_tsdf_integrate, dim3(blocks_for(grid_voxels(g))), dim3(MB), 0, (hipStream_t)stream, views, n_views, g, grid->origin[0],
                        grid->origin[1], grid->origin[2], grid->voxel, grid->tsdf, grid->weight, grid->rgb, depth, alpha, rgb, W, H, trunc);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 
 extern "C" size_t dvs_mesh_scratch_bytes(const int32_t dims[3]) { return dims_ok(dims) ? mesh_layout((size_t)dims[0] * dims[1] * dims[2]).total : 0; }
@@ -408,9 +340,9 @@ extern "C" int dvs_mesh_extract_count(void* stream, const dvs_tsdf_grid* grid, v
     const dim3 grid_dim(blocks_for(nv)), block(MB);
     hipLaunchKernelGGL(k_mesh_cells, grid_dim, block, 0, st, g, (const float*)grid->weight, cell_ok);
     hipLaunchKernelGGL(k_mesh_edges, grid_dim, block, 0, st, g, (const float*)grid->tsdf, (const uint8_t*)cell_ok, flags, vert_off);
-    if (scan_in_place(st, vert_off, nv, (uint32_t*)(base + L.bsum_v), L.nb, totals) != hipSuccess) return DVS_ERR_HIP;
+    if (dvs_launch_scan_u32(st, vert_off, nv, (uint32_t*)(base + L.bsum_v), totals) != hipSuccess) return DVS_ERR_HIP;
     hipLaunchKernelGGL(k_mesh_tricount, grid_dim, block, 0, st, g, (const float*)grid->tsdf, (const uint8_t*)cell_ok, tri_off);
-    if (scan_in_place(st, tri_off, nv, (uint32_t*)(base + L.bsum_t), L.nb, totals + 1) != hipSuccess) return DVS_ERR_HIP;
+    if (dvs_launch_scan_u32(st, tri_off, nv, (uint32_t*)(base + L.bsum_t), totals + 1) != hipSuccess) return DVS_ERR_HIP;
     unsigned long long host_totals[2] = {0, 0};
     if (hipMemcpyAsync(host_totals, totals, sizeof host_totals, hipMemcpyDeviceToHost, st) != hipSuccess) return DVS_ERR_HIP;
     if (hipStreamSynchronize(st) != hipSuccess) return DVS_ERR_HIP;
@@ -433,5 +365,5 @@ extern "C" int dvs_mesh_extract_write(void* stream, const dvs_tsdf_grid* grid, c
     hipLaunchKernelGGL(k_mesh_verts, grid_dim, block, 0, st, g, grid->origin[0], grid->origin[1], grid->origin[2], grid->voxel, (const float*)grid->tsdf,
                        (const float*)grid->rgb, flags, vert_off, xyz, rgb);
     hipLaunchKernelGGL(k_mesh_tris, grid_dim, block, 0, st, g, (const float*)grid->tsdf, cell_ok, flags, vert_off, tri_off, tri);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }

@@ -33,7 +33,6 @@ namespace {
 __device__ uint32_t g_mesh_err;        // != 0: a capped loop ran out (one word per device)
 
 unsigned cblocks(size_t n) { return (unsigned)((n + CB - 1) / CB); }
-size_t calign256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 __device__ __forceinline__ uint32_t ld_relaxed(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
@@ -108,13 +107,13 @@ CleanLayout clean_layout(uint32_t nv, uint32_t nt) {
     CleanLayout L{};
     const size_t v = nv ? nv : 1, t = nt ? nt : 1;
     size_t o = 0;
-    L.label = o; o = calign256(o + v * 4);
-    L.cnt = o; o = calign256(o + v * 4);
-    L.voff = o; o = calign256(o + v * 4);
-    L.toff = o; o = calign256(o + t * 4);
-    L.bsum_v = o; o = calign256(o + ((v + DVS_SCAN_TILE - 1) / DVS_SCAN_TILE) * 4);
-    L.bsum_t = o; o = calign256(o + ((t + DVS_SCAN_TILE - 1) / DVS_SCAN_TILE) * 4);
-    L.block = o; o = calign256(o + sizeof(CleanBlock));
+    L.label = o; o = dvs_align256(o + v * 4);
+    L.cnt = o; o = dvs_align256(o + v * 4);
+    L.voff = o; o = dvs_align256(o + v * 4);
+    L.toff = o; o = dvs_align256(o + t * 4);
+    L.bsum_v = o; o = dvs_align256(o + ((v + DVS_SCAN_TILE - 1) / DVS_SCAN_TILE) * 4);
+    L.bsum_t = o; o = dvs_align256(o + ((t + DVS_SCAN_TILE - 1) / DVS_SCAN_TILE) * 4);
+    L.block = o; o = dvs_align256(o + sizeof(CleanBlock));
     L.total = o;
     return L;
 }
@@ -262,7 +261,7 @@ extern "C" int dvs_mesh_components(void* stream, uint32_t n_vertices, const uint
     // (with no vertex every triangle is bad: the union pass still counts them, and dereferences nothing but tri)
     if (n_triangles > 0) hipLaunchKernelGGL(k_cc_union, dim3(cblocks(n_triangles)), dim3(CB), 0, st, n_vertices, tri, n_triangles, label, n_bad);
     if (n_vertices > 0 && n_triangles > 0) hipLaunchKernelGGL(k_cc_flatten, dim3(cblocks(n_vertices)), dim3(CB), 0, st, n_vertices, label);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 
 extern "C" size_t dvs_mesh_clean_scratch_bytes(uint32_t n_vertices, uint32_t n_triangles) { return clean_layout(n_vertices, n_triangles).total; }
@@ -315,7 +314,7 @@ extern "C" int dvs_mesh_clean_write(void* stream, uint32_t n_vertices, const flo
     hipLaunchKernelGGL(k_clean_write_v, dim3(cblocks(n_vertices)), dim3(CB), 0, st, n_vertices, xyz, rgb, normals, label, cnt, voff, blk, out_xyz, out_rgb,
                        out_normals);
     hipLaunchKernelGGL(k_clean_write_t, dim3(cblocks(n_triangles)), dim3(CB), 0, st, n_vertices, tri, n_triangles, label, cnt, voff, toff, blk, out_tri);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 
 extern "C" int dvs_mesh_extract_normals(void* stream, const dvs_tsdf_grid* grid, const void* scratch, float* normals) {
@@ -328,5 +327,5 @@ extern "C" int dvs_mesh_extract_normals(void* stream, const dvs_tsdf_grid* grid,
     const char* const base = (const char*)scratch;
     hipLaunchKernelGGL(k_mesh_normals, dim3(cblocks(nv)), dim3(CB), 0, (hipStream_t)stream, g, (const float*)grid->tsdf, (const float*)grid->weight,
                        (const uint8_t*)(base + flags_off), (const uint32_t*)(base + vert_off_off), normals);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }

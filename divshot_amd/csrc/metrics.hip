@@ -18,6 +18,7 @@
 #include <cstdint>
 #include "../../include/dvs_train.h"
 #include "../../include/dvs_raster.h"
+#include "dvs_device.h"
 #include "ssim_common.h"
 
 namespace {
@@ -156,6 +157,6 @@ int dvs_image_metrics_views(void* stream, const dvs_metrics_view* views, int n_v
     if (hipGetLastError() != hipSuccess) return DVS_ERR_HIP;
     hipLaunchKernelGGL(k_image_metrics_final, dim3(n_views), dim3(256), 0, (hipStream_t)stream, (const float*)scratch, (int)(grid.x * grid.y),
                        3.0 * (double)width * (double)height, out);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 }

@@ -450,7 +450,7 @@ extern "C" int dvs_pack_compressed(void* stream, int n, const float* pos, const 
     const unsigned nchunks = (unsigned)(((int64_t)n + PK_CHUNK - 1) / PK_CHUNK);
     hipLaunchKernelGGL(k_pack_chunks, dim3(nchunks), dim3(PK_BLOCK), 0, st, n, sorted, pos, sh0, opacity, scale, rot, chunks,
                        (uint4*)verts, order);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 
 extern "C" int dvs_pack_splat32(void* stream, int n, const float* pos, const float* sh0, const float* opacity, const float* scale,
@@ -459,7 +459,7 @@ extern "C" int dvs_pack_splat32(void* stream, int n, const float* pos, const flo
     if (off16(pos) || off16(sh0) || off16(opacity) || off16(scale) || off16(rot) || off16(out)) return DVS_ERR_INVALID;
     const unsigned nblocks = (unsigned)(((int64_t)n + PK_BLOCK - 1) / PK_BLOCK);
     hipLaunchKernelGGL(k_pack_splat32, dim3(nblocks), dim3(PK_BLOCK), 0, (hipStream_t)stream, n, pos, sh0, opacity, scale, rot, (uint4*)out);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 
 extern "C" int dvs_spz_layout_for(int n, int sh_degree, dvs_spz_layout* out) {
@@ -501,7 +501,7 @@ extern "C" int dvs_pack_spz(void* stream, int n, int sh_degree, const float* pos
         case 2: hipLaunchKernelGGL(k_pack_spz<8>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
         default: hipLaunchKernelGGL(k_pack_spz<15>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
     }
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 
 extern "C" int dvs_unpack_spz(void* stream, int n, int sh_degree, const uint8_t* packed, float* pos, float* sh0, float* shN, int shn_layout,
@@ -518,5 +518,5 @@ extern "C" int dvs_unpack_spz(void* stream, int n, int sh_degree, const uint8_t*
         case 2: hipLaunchKernelGGL(k_unpack_spz<8>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
         default: hipLaunchKernelGGL(k_unpack_spz<15>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
     }
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }

@@ -16,11 +16,9 @@ struct PixelRays { float m[DVS_MAX_VIEWS][12]; };               // per view: M^-
 struct PixelRay { float m[9]; };
 // view v's matrix of the PixelRays that lead the kernel's first parameter
 __device__ __forceinline__ PixelRay pixel_ray_load(int v) {
-    typedef const __attribute__((address_space(4))) float* KF;
-    const KF f = (KF)__builtin_amdgcn_kernarg_segment_ptr() + (size_t)v * 12;
     PixelRay r;
 #pragma unroll
-    for (int k = 0; k < 9; ++k) r.m[k] = f[k];
+    for (int k = 0; k < 9; ++k) r.m[k] = dvs_karg<float>(((size_t)v * 12 + k) * sizeof(float));
     return r;
 }
 __device__ __forceinline__ void pixel_ray_dir(const PixelRay& r, int x, int y, int W, int H, float& dx, float& dy, float& dz) {

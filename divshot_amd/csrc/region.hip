@@ -8,8 +8,7 @@
 //                     load one each (coalesced 16-byte words) into LDS and every thread reads its three floats back with stride 3
 //                     (odd: no bank conflict). The last, partial block and a misaligned array take the scalar path. Writes
 //                     action[i] and the block's kept count.
-//   k_region_scan     one workgroup over the block counts, 256 per chunk with a running carry (as k_densify_scan_blocks): block
-//                     offsets in place, the total to *new_count.
+//   (scan.hip)        dvs_launch_block_sums_excl: one workgroup over the block counts, block offsets in place, the total to *new_count.
 //   k_region_offsets  offsets[i] = the block's offset + the exclusive scan of the kept flags inside the block, from action[].
 //   k_region_mask     one thread per pixel (scalar path) or per four consecutive pixels (16-byte path), blockIdx.y = the view, so that
 //                     what a view needs (its ray matrix, its origin in the box, its two pointers) is wave-uniform and comes from the
@@ -36,7 +35,7 @@ __device__ __forceinline__ bool region_inside(const dvs_region& r, float x, floa
 
 __global__ void __launch_bounds__(DB)
 k_region_flags(int n, const float* __restrict__ pos, dvs_region region, int aligned, uint8_t* __restrict__ action, uint32_t* __restrict__ block_sums) {
-    __shared__ uint32_t tmp[DB / 64 + 1];
+    __shared__ uint32_t tmp[DB / 64];
     __shared__ float4 stage[3 * DB / 4];
     const int i = blockIdx.x * DB + threadIdx.x;
     float x = 0.f, y = 0.f, z = 0.f;
@@ -51,29 +50,16 @@ k_region_flags(int n, const float* __restrict__ pos, dvs_region region, int alig
     const bool keep = i < n && region_inside(region, x, y, z);
     if (i < n) action[i] = (uint8_t)(keep ? DVS_DENSIFY_KEEP : DVS_DENSIFY_PRUNE);
     uint32_t tot;
-    (void)d_block_excl_scan(keep ? 1u : 0u, tmp, &tot);
+    (void)dvs_block_excl_scan(keep ? 1u : 0u, tmp, &tot);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = tot;
-}
-__global__ void __launch_bounds__(DB) k_region_scan(uint32_t* __restrict__ block_sums, uint32_t nb, uint64_t* __restrict__ total) {
-    __shared__ uint32_t tmp[DB / 64 + 1];
-    uint64_t carry = 0;
-    for (uint32_t base = 0; base < nb; base += DB) {
-        const uint32_t idx = base + threadIdx.x;
-        const uint32_t v = idx < nb ? block_sums[idx] : 0u;
-        uint32_t t;
-        const uint64_t e = carry + d_block_excl_scan(v, tmp, &t);
-        if (idx < nb) block_sums[idx] = (uint32_t)e;
-        carry += t;
-    }
-    if (threadIdx.x == 0) *total = carry;
 }
 __global__ void __launch_bounds__(DB)
 k_region_offsets(int n, const uint8_t* __restrict__ action, const uint32_t* __restrict__ block_offsets, uint32_t* __restrict__ offsets) {
-    __shared__ uint32_t tmp[DB / 64 + 1];
+    __shared__ uint32_t tmp[DB / 64];
     const int i = blockIdx.x * DB + threadIdx.x;
     const bool keep = i < n && action[i] == DVS_DENSIFY_KEEP;
     uint32_t tot;
-    const uint32_t ex = d_block_excl_scan(keep ? 1u : 0u, tmp, &tot);
+    const uint32_t ex = dvs_block_excl_scan(keep ? 1u : 0u, tmp, &tot);
     if (i < n) offsets[i] = block_offsets[blockIdx.x] + ex;
 }
 
@@ -85,10 +71,6 @@ struct RegionMaskArgs {
     float* out[DVS_REGION_MAX_VIEWS];
 };
 static_assert(DVS_REGION_MAX_VIEWS == DVS_MAX_VIEWS, "one table size for the views of a launch");
-template <class T> __device__ __forceinline__ T region_karg(size_t byte_offset) {
-    typedef const __attribute__((address_space(4))) T* KP;
-    return *(KP)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + byte_offset);
-}
 
 __device__ __forceinline__ float region_hit(const PixelRay& ray, const float (&o)[3], const dvs_region& r, int x, int y, int W, int H) {
     float dx, dy, dz;
@@ -116,9 +98,9 @@ k_region_mask(RegionMaskArgs args /* MUST stay the first parameter */, dvs_regio
     const PixelRay ray = pixel_ray_load(view);
     float o[3];
 #pragma unroll
-    for (int k = 0; k < 3; ++k) o[k] = region_karg<float>(offsetof(RegionMaskArgs, rays) + ((size_t)view * 12 + 9 + k) * sizeof(float));
-    const float* const in = region_karg<const float*>(offsetof(RegionMaskArgs, in) + (size_t)view * sizeof(void*));
-    float* const out = region_karg<float*>(offsetof(RegionMaskArgs, out) + (size_t)view * sizeof(void*));
+    for (int k = 0; k < 3; ++k) o[k] = dvs_karg<float>(offsetof(RegionMaskArgs, rays) + ((size_t)view * 12 + 9 + k) * sizeof(float));
+    const float* const in = dvs_karg<const float*>(offsetof(RegionMaskArgs, in) + (size_t)view * sizeof(void*));
+    float* const out = dvs_karg<float*>(offsetof(RegionMaskArgs, out) + (size_t)view * sizeof(void*));
     const size_t P = (size_t)W * H;
     const size_t t = (size_t)blockIdx.x * DB + threadIdx.x;
     if (VEC) {                                                   // P % 4 == 0, in / out 16-byte aligned
@@ -180,9 +162,10 @@ int dvs_region_plan(void* stream, int n, const float* pos, const dvs_region* reg
     hipStream_t st = (hipStream_t)stream;
     const uint32_t nb = (uint32_t)(((int64_t)n + DB - 1) / DB);
     hipLaunchKernelGGL(k_region_flags, dim3(nb), dim3(DB), 0, st, n, pos, *region, ((uintptr_t)pos & 15u) ? 0 : 1, action, scratch);
-    hipLaunchKernelGGL(k_region_scan, dim3(1), dim3(DB), 0, st, scratch, nb, new_count);
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "new_count is the scan's 64-bit total");
+    if (dvs_launch_block_sums_excl(st, scratch, nb, (unsigned long long*)new_count) != hipSuccess) return DVS_ERR_HIP;
     hipLaunchKernelGGL(k_region_offsets, dim3(nb), dim3(DB), 0, st, n, (const uint8_t*)action, (const uint32_t*)scratch, offsets);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 
 int dvs_region_mask_views(void* stream, const dvs_region_mask_view* views, int n_views, int width, int height, const dvs_region* region) {
@@ -204,6 +187,6 @@ int dvs_region_mask_views(void* stream, const dvs_region_mask_view* views, int n
     const dim3 grid((unsigned)((work + DB - 1) / DB), (unsigned)n_views);
     if (vec) hipLaunchKernelGGL(k_region_mask<true>, grid, dim3(DB), 0, (hipStream_t)stream, a, *region, width, height);
     else hipLaunchKernelGGL(k_region_mask<false>, grid, dim3(DB), 0, (hipStream_t)stream, a, *region, width, height);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 }

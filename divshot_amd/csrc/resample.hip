@@ -15,6 +15,7 @@
 #include <cstdint>
 #include "../../include/dvs_train.h"
 #include "../../include/dvs_raster.h"
+#include "dvs_device.h"
 
 namespace {
 struct DownsampleViews { dvs_downsample_view v[DVS_DOWNSAMPLE_MAX_VIEWS]; };       // 256 B of kernel arguments
@@ -136,5 +137,5 @@ extern "C" int dvs_downsample_views(void* stream, const dvs_downsample_view* vie
     const dim3 grid((unsigned)(((Wd + 3) / 4 + DS_TX - 1) / DS_TX), (unsigned)((rows + DS_TY - 1) / DS_TY), (unsigned)n_views);
     if (src_u8) launch<true>(factor, grid, (hipStream_t)stream, a, planes, width, height, Wd, Hd);
     else launch<false>(factor, grid, (hipStream_t)stream, a, planes, width, height, Wd, Hd);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }

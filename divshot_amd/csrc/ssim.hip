@@ -11,6 +11,7 @@
 #include <climits>
 #include "../../include/dvs_train.h"
 #include "../../include/dvs_raster.h"
+#include "dvs_device.h"
 #include "ssim_common.h"
 
 // load the 26x26 patches of NP planes (zero outside the image) into LDS. All 3*NP global loads are issued before the first
@@ -151,7 +152,7 @@ int dvs_ssim_forward(void* stream, const float* img, const float* target, int wi
     const dim3 grid((width + ST - 1) / ST, (height + ST - 1) / ST, 3);
     hipLaunchKernelGGL(k_ssim_fwd, grid, dim3(ST * ST), 0, (hipStream_t)stream, img, target, width, height, dm_dmu1, dm_dsigma1_sq,
                        dm_dsigma12, ssim_sum);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 int dvs_ssim_backward(void* stream, const float* img, const float* target, int width, int height, const float* dm_dmu1,
                       const float* dm_dsigma1_sq, const float* dm_dsigma12, float scale, float* dL_dimg, int accumulate) {
@@ -165,7 +166,7 @@ int dvs_ssim_backward(void* stream, const float* img, const float* target, int w
     else
         hipLaunchKernelGGL((k_ssim_bwd<false, false>), grid, dim3(ST * ST), 0, (hipStream_t)stream, img, target, width, height, dm_dmu1,
                            dm_dsigma1_sq, dm_dsigma12, s, dL_dimg, 0.f, (float*)nullptr);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 int dvs_loss_l1_ssim_backward(void* stream, const float* img, const float* target, int width, int height, const float* dm_dmu1,
                               const float* dm_dsigma1_sq, const float* dm_dsigma12, float ssim_weight, float* dL_dimg, float* l1_sum) {
@@ -177,6 +178,6 @@ int dvs_loss_l1_ssim_backward(void* stream, const float* img, const float* targe
     // L = (1-w) mean|x-y| + w (1 - mean SSIM)  ->  dL/dx = (1-w)/count sign(x-y) - w/count dSSIM/dx
     hipLaunchKernelGGL((k_ssim_bwd<false, true>), grid, dim3(ST * ST), 0, (hipStream_t)stream, img, target, width, height, dm_dmu1,
                        dm_dsigma1_sq, dm_dsigma12, -ssim_weight / count, dL_dimg, (1.0f - ssim_weight) / count, l1_sum);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 }

@@ -4,6 +4,7 @@
 #include <cstdint>
 #include "../../include/dvs_train.h"
 #include "../../include/dvs_raster.h"
+#include "dvs_device.h"
 
 #define TB 256
 
@@ -159,7 +160,7 @@ int dvs_l1_loss_grad_w(void* stream, const float* rgb, const float* target, size
     if (count == 0) return DVS_OK;
     hipLaunchKernelGGL(k_loss_grad<true>, dim3(grid_for(count)), dim3(TB), 0, (hipStream_t)stream, rgb, target, count,
                        weight / (float)count, dL, loss_accum);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 int dvs_l1_loss_grad(void* stream, const float* rgb, const float* target, size_t count, float* dL, float* loss_accum) {
     return dvs_l1_loss_grad_w(stream, rgb, target, count, 1.0f, dL, loss_accum);
@@ -169,7 +170,7 @@ int dvs_l2_loss_grad(void* stream, const float* rgb, const float* target, size_t
     if (count == 0) return DVS_OK;
     hipLaunchKernelGGL(k_loss_grad<false>, dim3(grid_for(count)), dim3(TB), 0, (hipStream_t)stream, rgb, target, count, scale, dL,
                        loss_accum);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 int dvs_adam_step(void* stream, float* param, const float* grad, float* m, float* v, size_t count, float lr, float beta1,
                   float beta2, float eps, int step) {
@@ -178,7 +179,7 @@ int dvs_adam_step(void* stream, float* param, const float* grad, float* m, float
     const float bc1 = 1.0f / (1.0f - powf(beta1, (float)step)), bc2 = 1.0f / (1.0f - powf(beta2, (float)step));
     hipLaunchKernelGGL(k_adam, dim3(grid_for(count)), dim3(TB), 0, (hipStream_t)stream, param, grad, m, v, count, lr, beta1, beta2,
                        eps, bc1, bc2);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 int dvs_adam_step_groups(void* stream, const dvs_adam_group* groups, int n_groups, float beta1, float beta2, float eps, int step,
                          const int32_t* visible, int32_t n_splats) {
@@ -213,6 +214,6 @@ int dvs_adam_step_groups(void* stream, const dvs_adam_group* groups, int n_group
     if (blocks > 0x7fffffffull) return DVS_ERR_INVALID;
     const float bc1 = 1.0f / (1.0f - powf(beta1, (float)step)), bc2 = 1.0f / (1.0f - powf(beta2, (float)step));
     hipLaunchKernelGGL(k_adam_groups, dim3((unsigned)blocks), dim3(TB), 0, (hipStream_t)stream, G, visible, n_splats, beta1, beta2, eps, bc1, bc2);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
 }

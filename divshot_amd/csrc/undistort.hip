@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstdint>
 #include "../../include/dvs_raster.h"
+#include "dvs_device.h"
 #include "../../include/dvs_image.h"
 
 namespace {
@@ -127,5 +128,5 @@ extern "C" int dvs_undistort_view(void* stream, const dvs_undistort_desc* desc, 
     const dim3 grid((unsigned)(((W + 3) / 4 + UD_TX - 1) / UD_TX), (unsigned)((H + UD_TY - 1) / UD_TY));       // (grid.y <= 16384)
     hipLaunchKernelGGL(k_undistort, grid, dim3(UD_TX, UD_TY), 0, (hipStream_t)stream, *desc, planes, src, mask_src, dst, mask_dst, invalid_count,
                        vec_dst, vec_mask);
-    return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+    return dvs_launch_status();
 }
