@@ -237,6 +237,10 @@ class MeshCleanInfo(C.Structure):      # dvs_mesh_clean_info
     _fields_ = [(n, C.c_uint32) for n in ("n_components", "largest", "kept_components", "kept_vertices", "kept_triangles", "n_bad")]
 
 
+class MeshDecimateInfo(C.Structure):   # dvs_mesh_decimate_info
+    _fields_ = [(n, C.c_uint32) for n in ("out_vertices", "out_triangles", "n_clusters", "n_degenerate", "n_duplicate", "n_bad")]
+
+
 _MESH_PROTOS = {
     "dvs_tsdf_bytes": (C.c_size_t, [C.POINTER(C.c_int32)]),
     "dvs_tsdf_create": (C.c_int, [C.POINTER(C.c_float), C.c_float, C.POINTER(C.c_int32), C.POINTER(TsdfGridDesc)]),
@@ -253,6 +257,11 @@ _MESH_PROTOS = {
     "dvs_mesh_clean_count": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(MeshCleanInfo)]),
     "dvs_mesh_clean_write": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_mesh_decimate_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "dvs_mesh_decimate_count": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_float,
+                                          C.POINTER(C.c_int32), C.c_void_p, C.POINTER(MeshDecimateInfo)]),
+    "dvs_mesh_decimate_write": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -1,7 +1,7 @@
 // scan.hip — the device-wide exclusive scan of 32-bit words (dvs_kernels.h), for gfx950: a plain reduce-then-scan. Block sums of
 // DVS_SCAN_TILE elements, one workgroup scans the block sums with a 64-bit carry, the blocks rescan their elements from their offset.
 // Integer only; no atomics: every output word has exactly one writer. Users: mesh.hip (vertex and triangle offsets), mesh_clean.hip
-// (compaction), region.hip (the middle step alone, over its own block counts).
+// (compaction), mesh_decimate.hip (cluster numbers, compaction), region.hip (the middle step alone, over its own block counts).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "dvs_kernels.h"

@@ -56,6 +56,9 @@ static std::map<std::string, std::string> g_opts = {
     // connected components with fewer than P % of the largest one's triangles; --meshNormals 1 adds nx ny nz, the TSDF gradient's unit
     // normals. The config struct has no room left: when given they are handed to the plugin as DVS_MESH_MIN_COMPONENT / DVS_MESH_NORMALS.
     {"meshMinComponent", "0"}, {"meshNormals", "0"},
+    // extension of this build: --meshDecimate F (0 = off, or 2..16) decimates that mesh last, by vertex clustering: all vertices inside a cell
+    // of F voxels of the extraction grid per axis become one. Handed to the plugin as DVS_MESH_DECIMATE, like the two above.
+    {"meshDecimate", "0"},
     // the reference's config field enableBg ("Create Sky Model"; its CLI has no flag for it): --enableBg 1 trains an equirectangular sky
     // texture behind the splats and writes <outputPath>_<it>.sky at every save. --skyResolution Hs (default 128, clamped to 16..1024) is the
     // texture's height, its width 2 Hs; the config struct has no room left: it is handed to the plugin as DVS_SKY_RESOLUTION.
@@ -111,6 +114,13 @@ int main(int argc, const char* argv[]) {
         const std::string& v = g_opts["meshNormals"];
         if (v != "0" && v != "1") { std::cout << "Command Line Error: --meshNormals takes 0 or 1, not '" << v << "'\n"; return 1; }
         setenv("DVS_MESH_NORMALS", v.c_str(), 1);
+    }
+    if (g_given.count("meshDecimate")) {
+        const std::string& v = g_opts["meshDecimate"];
+        const bool digits = !v.empty() && v.size() <= 2 && v.find_first_not_of("0123456789") == std::string::npos;
+        const int f = digits ? atoi(v.c_str()) : -1;
+        if (!(f == 0 || (f >= 2 && f <= 16))) { std::cout << "Command Line Error: --meshDecimate takes 0 (off) or an integer 2..16, not '" << v << "'\n"; return 1; }
+        setenv("DVS_MESH_DECIMATE", v.c_str(), 1);                          // before the plugin is loaded
     }
     if (g_opts["enableBg"] != "0" && g_opts["enableBg"] != "1") { std::cout << "Command Line Error: --enableBg takes 0 or 1, not '" << g_opts["enableBg"] << "'\n"; return 1; }
     if (g_given.count("skyResolution")) {

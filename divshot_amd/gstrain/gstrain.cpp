@@ -165,6 +165,12 @@ void GaussianTrainerScene::setMeshCleanup(float minComponentPercent, bool normal
     m.mesh_min_bp_set = (int)std::lround((double)p * 100.0);
     m.mesh_normals_set = normals ? 1 : 0;
 }
+// The editor's switch for what DVS_MESH_DECIMATE sets for the CLI: once called it wins over the environment.
+void GaussianTrainerScene::setMeshDecimate(int factor) {
+    Impl& m = *impl_;
+    if (factor != 0 && (factor < 2 || factor > 16)) { logf_("setMeshDecimate: %d is not 0 (off) or a factor 2..16: decimation is off", factor); factor = 0; }
+    m.mesh_decimate_set = factor;
+}
 void GaussianTrainerScene::exportSparsePointCloud(const std::string& path) {
     Impl& m = *impl_;
     m.fetch_host();

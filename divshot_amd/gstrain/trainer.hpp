@@ -199,6 +199,10 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     int mesh_min_bp_set = -1, mesh_normals_set = -1;
     int mesh_min_bp() const;
     bool mesh_normals() const;
+    // decimation of the mesh, last before it is written: DVS_MESH_DECIMATE (0 = off, or 2..16 voxels of the extraction grid per cell and
+    // axis), or what setMeshDecimate said (-1: it was not called)
+    int mesh_decimate_set = -1;
+    int mesh_decimate() const;
 
     // importance prune (cfg.importancePrune / DVS_IMPORTANCE_PRUNE; trainer_refine.cpp): the per-splat score summed over the training views
     // and the selection's scratch. Nothing is allocated until the first such prune.

@@ -1,7 +1,7 @@
 // trainer_mesh.cpp — mesh export: the training cameras rendered through the evaluation context (for_each_eval_pass), their depth and alpha maps
 // (dvs_raster_depth_views) fused into a TSDF grid and the grid's surface extracted by marching tetrahedra (include/dvs_mesh.h), written
-// optionally given normals and freed of its small components on the device (DVS_MESH_NORMALS, DVS_MESH_MIN_COMPONENT / setMeshCleanup),
-// and written as a binary PLY (ply_io.hpp write_mesh_ply). Everything on the training stream; the training context is never touched.
+// optionally given normals, freed of its small components (DVS_MESH_NORMALS, DVS_MESH_MIN_COMPONENT / setMeshCleanup) and decimated by
+// vertex clustering (DVS_MESH_DECIMATE / setMeshDecimate) on the device, and written as a binary PLY (ply_io.hpp write_mesh_ply). Everything on the training stream; the training context is never touched.
 #include "trainer.hpp"
 #include "../../include/dvs_mesh.h"
 
@@ -33,6 +33,22 @@ int GaussianTrainerScene::Impl::mesh_min_bp() const {
     return bp;
 }
 bool GaussianTrainerScene::Impl::mesh_normals() const { return mesh_normals_set >= 0 ? mesh_normals_set != 0 : env_is("DVS_MESH_NORMALS", "1"); }
+// DVS_MESH_DECIMATE: one or two digits, 0 (off) or 2..16; anything else is reported once and ignored
+int GaussianTrainerScene::Impl::mesh_decimate() const {
+    if (mesh_decimate_set >= 0) return mesh_decimate_set;
+    const char* e = getenv("DVS_MESH_DECIMATE");
+    if (!e) return 0;
+    int f = 0, nd = 0;
+    const char* c = e;
+    for (; *c >= '0' && *c <= '9' && nd < 3; ++c, ++nd) f = f * 10 + (*c - '0');
+    if (*c || nd == 0 || nd > 2 || !(f == 0 || (f >= 2 && f <= 16))) {
+        static bool said = false;
+        if (!said) logf_("mesh: DVS_MESH_DECIMATE='%s' is not 0 (off) or an integer 2..16: ignored", e);
+        said = true;
+        return 0;
+    }
+    return f;
+}
 
 // The box the grid covers: DVS_MESH_BOUNDS=x0,y0,z0,x1,y1,z1, or with enableFocusRegion the focus region's world bounds, or the box of the centres of the splats with sigmoid(opacity) >= 0.5
 // cut to the cube of half-side 3 x extent about the camera centroid (extent: the scene extent the prune rules use).
@@ -156,9 +172,13 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
     const uint32_t min_bp = (uint32_t)mesh_min_bp();
     bool cleaned = false;
     dvs_mesh_clean_info info{};
-    double normals_ms = 0, clean_ms = 0;
+    double normals_ms = 0, clean_ms = 0, decimate_ms = 0;
+    const int decimate = mesh_decimate();
+    bool decimated = false;
+    dvs_mesh_decimate_info dinfo{};
+    uint32_t dec_v0 = 0, dec_t0 = 0;
     if (nv > 0 && nt > 0) {
-        DevBuf<float> d_xyz, d_nrm, c_xyz, c_nrm; DevBuf<uint8_t> d_rgb, c_rgb; DevBuf<uint32_t> d_tri, c_tri;
+        DevBuf<float> d_xyz, d_nrm, c_xyz, c_nrm, m_xyz, m_nrm; DevBuf<uint8_t> d_rgb, c_rgb, m_rgb; DevBuf<uint32_t> d_tri, c_tri, m_tri;
         d_xyz.alloc((size_t)nv * 3 * sizeof(float)); d_rgb.alloc((size_t)nv * 3); d_tri.alloc((size_t)nt * 3 * sizeof(uint32_t));
         const int rw = dvs_mesh_extract_write(stream.get(), &grid.g, sc, d_xyz.get(), d_rgb.get(), d_tri.get());
         if (rw != DVS_OK) throw std::runtime_error("dvs_mesh_extract_write: status " + std::to_string(rw));
@@ -193,6 +213,32 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
             nv = info.kept_vertices; nt = info.kept_triangles;
             f_xyz = c_xyz.get(); f_rgb = c_rgb.get(); f_tri = c_tri.get(); f_nrm = want_normals ? c_nrm.get() : nullptr;
         }
+        if (decimate > 0) {
+            // last: vertex clustering on the voxel lattice shifted by half a voxel (the grid's own planes, where the vertices of axis
+            // edges lie, are then no cell faces), `decimate` voxels per cell and axis
+            HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+            const auto t_d = std::chrono::steady_clock::now();
+            const float cell = (float)decimate * voxel;
+            float origin[3]; int32_t ncell[3];
+            for (int k = 0; k < 3; ++k) { origin[k] = lo[k] - 0.5f * voxel; ncell[k] = (dims[k] + decimate - 1) / decimate; }
+            DevBuf<void> dscratch;
+            dscratch.alloc(dvs_mesh_decimate_scratch_bytes(nv, nt) + 256);
+            void* const ds = (void*)(((uintptr_t)dscratch.get() + 255) & ~(uintptr_t)255);
+            const int rdc = dvs_mesh_decimate_count(stream.get(), nv, f_xyz, f_tri, nt, origin, cell, ncell, ds, &dinfo);
+            if (rdc != DVS_OK) throw std::runtime_error("dvs_mesh_decimate_count: status " + std::to_string(rdc));
+            m_xyz.alloc(std::max<size_t>(1, dinfo.out_vertices) * 3 * sizeof(float)); m_rgb.alloc(std::max<size_t>(1, dinfo.out_vertices) * 3);
+            m_tri.alloc(std::max<size_t>(1, dinfo.out_triangles) * 3 * sizeof(uint32_t));
+            if (want_normals) m_nrm.alloc(std::max<size_t>(1, dinfo.out_vertices) * 3 * sizeof(float));
+            const int rdw = dvs_mesh_decimate_write(stream.get(), nv, f_xyz, f_rgb, f_nrm, f_tri, nt, ds, m_xyz.get(), m_rgb.get(),
+                                                    want_normals ? m_nrm.get() : nullptr, m_tri.get());
+            if (rdw != DVS_OK) throw std::runtime_error("dvs_mesh_decimate_write: status " + std::to_string(rdw));
+            HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+            decimate_ms = ms_since(t_d);
+            decimated = true;
+            dec_v0 = nv; dec_t0 = nt;
+            nv = dinfo.out_vertices; nt = dinfo.out_triangles;
+            f_xyz = m_xyz.get(); f_rgb = m_rgb.get(); f_tri = m_tri.get(); f_nrm = want_normals ? m_nrm.get() : nullptr;
+        }
         xyz.resize((size_t)nv * 3); rgb.resize((size_t)nv * 3); tri.resize((size_t)nt * 3);
         if (want_normals) nrm.resize((size_t)nv * 3);
         if (nv > 0) {
@@ -203,12 +249,15 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
         if (nt > 0) HIP_OR_THROW(hipMemcpyAsync(tri.data(), f_tri, tri.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, stream.get()));
         HIP_OR_THROW(hipStreamSynchronize(stream.get()));
     } else { nv = 0; nt = 0; }
-    const double extract_ms = ms_since(t_ex) - normals_ms - clean_ms;        // (count, write and the copies to the host, as before)
-    char extras[256] = "";
+    const double extract_ms = ms_since(t_ex) - normals_ms - clean_ms - decimate_ms;        // (count, write and the copies to the host, as before)
+    char extras[512] = "";
     if (cleaned)
         snprintf(extras, sizeof extras, ", cleanup: %u of %u components kept (largest %u triangles, min %g %%), %.2f ms", info.kept_components,
                  info.n_components, info.largest, min_bp / 100.0, clean_ms);
     if (want_normals) snprintf(extras + strlen(extras), sizeof extras - strlen(extras), ", normals %.2f ms", normals_ms);
+    if (decimated)
+        snprintf(extras + strlen(extras), sizeof extras - strlen(extras), ", decimate: %d voxels per cell, %u -> %u vertices, %u -> %u triangles (%u degenerate, "
+                 "%u duplicate), %.2f ms", decimate, dec_v0, nv, dec_t0, nt, dinfo.n_degenerate, dinfo.n_duplicate, decimate_ms);
 
     if (!write_ply(nv, xyz.data(), rgb.data(), nt, tri.data(), want_normals ? nrm.data() : nullptr)) return false;
     logf_("mesh @%d: %u vertices, %u triangles, grid %dx%dx%d, voxel %.9g, bounds %.9g,%.9g,%.9g,%.9g,%.9g,%.9g, trunc %.9g, %d views; render+depth %.2f ms, "

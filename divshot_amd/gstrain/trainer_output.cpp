@@ -41,6 +41,9 @@ void GaussianTrainerScene::Impl::report_config() const {
         logf_("config: mesh clean-up: components with fewer than %g %% of the largest one's triangles are dropped%s, on the device, before the mesh "
               "is written%s", mesh_min_bp() / 100.0, mesh_min_bp() > 0 ? "" : " (off)",
               mesh_normals() ? "; vertex normals nx ny nz from the TSDF gradient" : "");
+    if (const int F = mesh_decimate(); F > 0)
+        logf_("config: mesh decimation: vertex clustering on cells of %d voxels of the extraction grid per axis (mean position, colour and normal per "
+              "cell; collapsed and repeated triangles dropped), on the device, last before the mesh is written", F);
     if (const int P = importance_prune(); P > 0) {
         const int asked = env_int("DVS_IMPORTANCE_PRUNE", cfg.importancePrune);
         if (asked > 90) logf_("config: importancePrune %d clamped to 90", asked);

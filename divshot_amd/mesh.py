@@ -6,11 +6,12 @@ torch supplies device buffers and the HIP stream; all compute runs in libdvsrast
     xyz, rgb, tri = grid.extract()                      # numpy: float32 [nv,3], uint8 [nv,3], uint32 [nt,3]
     xyz, rgb, tri, nrm = grid.extract(normals=True)     # ... and the TSDF gradient's unit normals, float32 [nv,3]
     xyz, rgb, tri, nrm, info = clean_mesh(xyz, rgb, tri, min_bp=100, normals=nrm)   # components below 1 % of the largest dropped
+    xyz, rgb, tri, nrm, info = decimate_mesh(xyz, rgb, tri, origin, cell, (cx, cy, cz), normals=nrm)   # one vertex per lattice cell
 """
 import ctypes as C
 import numpy as np
 import torch
-from ._lib import lib, Camera, Opts, TsdfGridDesc, MeshCleanInfo, check, DvsError, write_mesh_ply  # noqa: F401
+from ._lib import lib, Camera, Opts, TsdfGridDesc, MeshCleanInfo, MeshDecimateInfo, check, DvsError, write_mesh_ply  # noqa: F401
 from .raster import _stream_ptr
 
 
@@ -156,3 +157,43 @@ def clean_mesh(xyz, rgb, tri, min_bp, normals=None, device=0):
         torch.cuda.synchronize()
     return (o_xyz[:kv].cpu().numpy(), o_rgb[:kv].cpu().numpy(), o_tri[:kt].cpu().numpy().view(np.uint32),
             None if o_nrm is None else o_nrm[:kv].cpu().numpy(), {name: getattr(info, name) for name, _ in MeshCleanInfo._fields_})
+
+
+def decimate_mesh(xyz, rgb, tri, origin, cell, ncell, normals=None, device=0):
+    """dvs_mesh_decimate_count / _write on numpy arrays: vertex clustering on the lattice of ncell = (cx, cy, cz) cubic cells of edge
+    `cell` from `origin` — every occupied cell's vertices become one vertex (mean position, colour, renormalised normal), collapsed and
+    repeated triangles and unused clusters are dropped -> (xyz, rgb, tri, normals or None, info) with info a dict of dvs_mesh_decimate_info"""
+    tdev = torch.device("cuda", device)
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    rgb = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+    nv = len(xyz)
+    if len(rgb) != nv or (normals is not None and len(normals) != nv):
+        raise DvsError("decimate_mesh: xyz, rgb and normals differ in length")
+    tri, d_tri = _tri_to_device(tri, tdev)
+
+    def up(a, dtype):
+        d = torch.empty((max(nv, 1), 3), dtype=dtype, device=tdev)
+        if nv:
+            d[:nv].copy_(torch.from_numpy(a))
+        return d
+    d_xyz, d_rgb = up(xyz, torch.float32), up(rgb, torch.uint8)
+    d_nrm = None if normals is None else up(np.ascontiguousarray(normals, np.float32).reshape(-1, 3), torch.float32)
+    scratch = torch.empty(lib.dvs_mesh_decimate_scratch_bytes(nv, len(tri)) + 256, dtype=torch.uint8, device=tdev)
+    sp = (scratch.data_ptr() + 255) & ~255
+    info = MeshDecimateInfo()
+    c_origin = (C.c_float * 3)(*[float(v) for v in origin])
+    c_ncell = (C.c_int32 * 3)(*[int(v) for v in ncell])
+    with torch.cuda.device(tdev):
+        check(lib.dvs_mesh_decimate_count(_stream_ptr(), nv, d_xyz.data_ptr(), d_tri.data_ptr(), len(tri), c_origin, float(cell), c_ncell, sp,
+                                          C.byref(info)), "dvs_mesh_decimate_count")
+        ov, ot = info.out_vertices, info.out_triangles
+        o_xyz = torch.empty((max(ov, 1), 3), dtype=torch.float32, device=tdev)
+        o_rgb = torch.empty((max(ov, 1), 3), dtype=torch.uint8, device=tdev)
+        o_nrm = None if d_nrm is None else torch.empty((max(ov, 1), 3), dtype=torch.float32, device=tdev)
+        o_tri = torch.empty((max(ot, 1), 3), dtype=torch.int32, device=tdev)
+        check(lib.dvs_mesh_decimate_write(_stream_ptr(), nv, d_xyz.data_ptr(), d_rgb.data_ptr(), None if d_nrm is None else d_nrm.data_ptr(),
+                                          d_tri.data_ptr(), len(tri), sp, o_xyz.data_ptr(), o_rgb.data_ptr(),
+                                          None if o_nrm is None else o_nrm.data_ptr(), o_tri.data_ptr()), "dvs_mesh_decimate_write")
+        torch.cuda.synchronize()
+    return (o_xyz[:ov].cpu().numpy(), o_rgb[:ov].cpu().numpy(), o_tri[:ot].cpu().numpy().view(np.uint32),
+            None if o_nrm is None else o_nrm[:ov].cpu().numpy(), {name: getattr(info, name) for name, _ in MeshDecimateInfo._fields_})

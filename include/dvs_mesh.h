@@ -1,7 +1,8 @@
 /*
  * dvs_mesh.h — C-ABI of surface extraction from a trained model: truncated-signed-distance (TSDF) fusion of rendered depth maps
  * (dvs_raster_depth_views, dvs_raster.h) into a voxel grid, marching tetrahedra over that grid into a welded, indexed mesh, and what
- * is done to that mesh before it is written: vertex normals from the grid, removal of small connected components.
+ * is done to that mesh before it is written: vertex normals from the grid, removal of small connected components, decimation by vertex
+ * clustering.
  *
  * Conventions of dvs_train.h: `stream` is a hipStream_t, arrays are DEVICE pointers unless marked HOST, calls are asynchronous unless
  * they say otherwise and return a DVS_* status (dvs_raster.h); the current HIP device is the caller's. The only atomics are integer
@@ -128,6 +129,49 @@ int dvs_mesh_clean_count(void* stream, uint32_t n_vertices, const uint32_t* tri,
 int dvs_mesh_clean_write(void* stream, uint32_t n_vertices, const float* xyz, const uint8_t* rgb, const float* normals /*or NULL*/,
                          const uint32_t* tri, uint32_t n_triangles, const void* scratch, float* out_xyz, uint8_t* out_rgb,
                          float* out_normals /*or NULL*/, uint32_t* out_tri);
+
+/* Decimation by vertex clustering (Rossignac-Borrel), the last stage before the mesh is written: a lattice of ncell[0] x ncell[1] x
+ * ncell[2] cubic cells of edge `cell` from `origin`; all vertices of a cell become ONE vertex with their mean position, colour and
+ * normal, triangles are re-indexed, collapsed and repeated triangles are dropped, and so are the clusters no surviving triangle uses.
+ * Defined bit for bit (tests/mesh_decimate_ref.py restates it):
+ * Cell of a vertex, per axis a: q = (x_a - origin_a) / cell (one fp32 subtraction, one fp32 IEEE division); i_a = 0 if !(q >= 0) (a NaN
+ *   too), ncell_a - 1 if q >= (float) ncell_a, else (uint32) q; key = (i_z * ncell_y + i_y) * ncell_x + i_x < 2^30.
+ * Clusters: the (key, vertex index) pairs in a stable sort by key; a sorted position is a cluster's head iff it is the first or its key
+ *   differs from its predecessor's; the exclusive scan of the heads numbers the clusters in key order (n_clusters of them); the members
+ *   of a cluster are in ascending vertex index.
+ * Triangles: one with an index >= n_vertices is bad — counted in n_bad, dropped, never dereferenced. Otherwise its corners are replaced
+ *   by their cluster numbers; it is degenerate — counted, dropped — if two of the three are equal. Two survivors are duplicates if their
+ *   cluster triples are equal after each is rotated so that its smallest number comes first; the winding is kept, so (a, b, c),
+ *   (b, c, a) and (c, a, b) are one triangle and (a, c, b), which faces the other way, is another. Of a set of duplicates the one with the
+ *   smallest triangle index is kept and the others are counted in n_duplicate. (Found by stable LSD sorts of (word, triangle index)
+ *   over the three rotated words, last word first, and an equal-to-predecessor test: no hashing, nothing that depends on order.)
+ * Output: the kept triangles in their old order and their old corner order (not the rotated one); the vertices are the clusters some
+ *   kept triangle uses, in key order; indices are remapped through exclusive scans.
+ * Attributes of an output vertex, over its cluster's members m0 < m1 < ... (vertex indices), count of them:
+ *   xyz per component: s = x[m0]; s = s + x[m1]; ... (serial, fp32), then s / (float) count;
+ *   rgb per channel: the integer sum, then (2 * sum + count) / (2 * count) in integers (the mean, rounded half up);
+ *   normals: the same serial fp32 sums n, no division by count; l2 = (n.x * n.x + n.y * n.y) + n.z * n.z; (0, 0, 0) when l2 < 1e-30,
+ *   else each component divided by sqrtf(l2) — the rule of dvs_mesh_extract_normals.
+ * dvs_mesh_decimate_count runs the key, sort, scan and marking passes into `scratch` (dvs_mesh_decimate_scratch_bytes bytes, 256-byte
+ * aligned, no initialisation) and synchronises the stream ONCE to fill *info. dvs_mesh_decimate_write (asynchronous) then writes out_xyz /
+ * out_rgb / out_normals [out_vertices][3] and out_tri [out_triangles][3] from the same scratch and the unchanged inputs; it gathers the
+ * vertex records in sorted order into a part of the scratch that is its own workspace, and leaves what _count put there unchanged, so it
+ * may be called again. normals and out_normals are both given or both NULL.
+ * DVS_ERR_INVALID, before any device work: scratch NULL or not 256-byte aligned; info, origin or ncell NULL; cell <= 0 or not finite; an
+ * ncell outside 1..1024; normals without out_normals or the reverse. DVS_ERR_CAPACITY for more than 2^31 - 1 vertices or triangles.
+ * n_vertices == 0 (every triangle is bad) and n_triangles == 0 are legal and give empty outputs. The only atomics are integer sums. */
+typedef struct dvs_mesh_decimate_info {
+    uint32_t out_vertices, out_triangles;   /* what dvs_mesh_decimate_write will produce */
+    uint32_t n_clusters;                    /* occupied cells, before unused ones are dropped */
+    uint32_t n_degenerate, n_duplicate, n_bad;
+} dvs_mesh_decimate_info;
+size_t dvs_mesh_decimate_scratch_bytes(uint32_t n_vertices, uint32_t n_triangles);
+int dvs_mesh_decimate_count(void* stream, uint32_t n_vertices, const float* xyz, const uint32_t* tri, uint32_t n_triangles,
+                            const float origin[3] /*HOST*/, float cell, const int32_t ncell[3] /*HOST, each 1..1024*/, void* scratch,
+                            dvs_mesh_decimate_info* info /*HOST*/);
+int dvs_mesh_decimate_write(void* stream, uint32_t n_vertices, const float* xyz, const uint8_t* rgb, const float* normals /*or NULL*/,
+                            const uint32_t* tri, uint32_t n_triangles, const void* scratch, float* out_xyz, uint8_t* out_rgb,
+                            float* out_normals /*or NULL*/, uint32_t* out_tri);
 
 #ifdef __cplusplus
 }

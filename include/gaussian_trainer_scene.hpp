@@ -127,6 +127,10 @@ public:
     // decimals count; 0 = off) of the largest component's triangles are dropped before the mesh is written, and `normals` adds the
     // TSDF gradient's unit normals nx ny nz to the file. Wins over DVS_MESH_MIN_COMPONENT / DVS_MESH_NORMALS once called.
     void setMeshCleanup(float minComponentPercent, bool normals);
+    // mesh decimation (extension of this build; INTEGRATION.md "Mesh export"): factor 2..16 merges, last before the mesh is written, all
+    // vertices inside a cell of factor^3 voxels of the extraction grid into one (vertex clustering on the device); 0 = off, any other
+    // value is reported and counts as 0. Wins over DVS_MESH_DECIMATE once called.
+    void setMeshDecimate(int factor);
     void exportSparsePointCloud(const std::string& path);   // editor.cpp:3535 — writes the splat centres as an ASCII PLY point cloud
     void saveCameraDatas(const std::string& path);          // editor.cpp:3512 — one line per camera: centre, view matrix, intrinsics
     bool isTrain() const;
