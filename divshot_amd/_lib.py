@@ -188,7 +188,22 @@ class SpzLayout(C.Structure):          # dvs_spz_layout: positions, alphas, colo
     _fields_ = [("off", C.c_uint64 * 6), ("bytes", C.c_uint64 * 6), ("total", C.c_uint64)]
 
 
+class ReducedLayout(C.Structure):      # dvs_reduced_layout: the four per-degree vertex blocks, then the codebook table
+    _fields_ = [("count", C.c_uint64 * 4), ("off", C.c_uint64 * 4), ("stride", C.c_uint64 * 4), ("table_off", C.c_uint64), ("total", C.c_uint64),
+                ("half", C.c_int32), ("_pad", C.c_int32)]
+
+
 _EXPORT_PROTOS = {
+    "dvs_reduced_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "dvs_sh_degree_select": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
+    "dvs_codebooks_build": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_reduced_degree_counts": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_reduced_layout_for": (C.c_int, [C.POINTER(C.c_uint32), C.c_int, C.POINTER(ReducedLayout)]),
+    "dvs_pack_reduced": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.POINTER(ReducedLayout), C.c_void_p]),
+    "dvs_unpack_reduced": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(ReducedLayout), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dvs_pack_scratch_bytes": (C.c_size_t, [C.c_int]),
     "dvs_pack_compressed": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),

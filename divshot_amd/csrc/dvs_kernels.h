@@ -185,6 +185,9 @@ hipError_t dvs_launch_morton_order(hipStream_t st, int n, const float* pos, void
 // block sums itself: bsum [nb] -> exclusive offsets in place (32-bit words), *total = the sum in 64 bits; nb = 0 leaves *total = 0.
 #define DVS_SCAN_TILE 2048
 hipError_t dvs_launch_scan_u32(hipStream_t st, uint32_t* v, size_t n, uint32_t* bsum, unsigned long long* total);
+// the INCLUSIVE scan, in place, of n > 0 64-bit words (sums wrap modulo 2^64, so int64 addends scan as themselves); bsum = ceil(n /
+// DVS_SCAN_TILE) 64-bit words of scratch
+hipError_t dvs_launch_scan_incl_u64(hipStream_t st, uint64_t* v, size_t n, uint64_t* bsum);
 __attribute__((visibility("hidden"))) hipError_t dvs_launch_block_sums_excl(hipStream_t st, uint32_t* bsum, uint32_t nb, unsigned long long* total);
 // mesh.hip — for mesh_clean.hip: the byte offsets, inside the scratch of dvs_mesh_extract_count, of vert_off [voxels] (uint32) and
 // flags [voxels] (uint8); false for dims the extraction refuses.

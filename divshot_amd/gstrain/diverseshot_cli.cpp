@@ -40,6 +40,10 @@ static std::map<std::string, std::string> g_opts = {
     // extension of this build: a switch, every save also writes <outputPath>_<it>.spz (the compact format that keeps the SH bands above 0;
     // with --eval its decoded model is scored on the held-out views too); also on when --outputPath itself ends in .spz
     {"exportSpz", "0"},
+    // extension of this build: --exportFormat also takes reduced (<outputPath>_<it>.reduced.ply: per-splat SH degree, k-means codebooks; also
+    // on when --outputPath ends in .reduced.ply). --cullSH 1 lets a splat drop the SH bands that change its colour by at most
+    // --cullSHThreshold (default 0.01) from every training camera; --reducedHalf 1 writes half-float positions
+    {"cullSH", "0"}, {"cullSHThreshold", "0.01"}, {"reducedHalf", "0"},
     // the config fields pruneScale3d / pruneScale2d (the reference's CLI has no flag for them): after the first opacity reset a refinement
     // also prunes splats larger than this fraction of the scene extent / whose screen radius exceeds this fraction of the image size
     {"pruneScale3d", "0.1"}, {"pruneScale2d", "0.15"},
@@ -122,6 +126,16 @@ int main(int argc, const char* argv[]) {
         if (!(f == 0 || (f >= 2 && f <= 16))) { std::cout << "Command Line Error: --meshDecimate takes 0 (off) or an integer 2..16, not '" << v << "'\n"; return 1; }
         setenv("DVS_MESH_DECIMATE", v.c_str(), 1);                          // before the plugin is loaded
     }
+    for (const char* flag : {"cullSH", "reducedHalf"})
+        if (g_opts[flag] != "0" && g_opts[flag] != "1") { std::cout << "Command Line Error: --" << flag << " takes 0 or 1, not '" << g_opts[flag] << "'\n"; return 1; }
+    if (g_given.count("reducedHalf")) setenv("DVS_REDUCED_HALF", g_opts["reducedHalf"].c_str(), 1);      // before the plugin is loaded
+    if (g_given.count("cullSHThreshold")) {
+        const std::string& v = g_opts["cullSHThreshold"];
+        char* end = nullptr;
+        const float t = strtof(v.c_str(), &end);
+        if (v.empty() || *end || !(t >= 0.0f)) { std::cout << "Command Line Error: --cullSHThreshold takes a number >= 0, not '" << v << "'\n"; return 1; }
+        setenv("DVS_SH_CULL_THRESHOLD", v.c_str(), 1);
+    }
     if (g_opts["enableBg"] != "0" && g_opts["enableBg"] != "1") { std::cout << "Command Line Error: --enableBg takes 0 or 1, not '" << g_opts["enableBg"] << "'\n"; return 1; }
     if (g_given.count("skyResolution")) {
         const std::string& v = g_opts["skyResolution"];
@@ -195,10 +209,12 @@ int main(int argc, const char* argv[]) {
         const std::string tok = v.substr(at, comma - at);
         if (tok == "compressed") train_config.exportFormats |= 1;
         else if (tok == "splat") train_config.exportFormats |= 2;
-        else { std::cout << "Command Line Error: --exportFormat takes compressed, splat or compressed,splat, not '" << tok << "'\n"; return 1; }
+        else if (tok == "reduced") train_config.exportFormats |= 8;
+        else { std::cout << "Command Line Error: --exportFormat takes compressed, splat, reduced or a comma-separated list of them, not '" << tok << "'\n"; return 1; }
         at = comma + 1;
     }
     if (as_bool(g_opts["exportSpz"])) train_config.exportFormats |= 4;
+    train_config.cullSH = as_bool(g_opts["cullSH"]);
     {
         const std::string &rv = g_opts["renderViews"], &rs = g_opts["renderSampling"];
         const int q = atoi(g_opts["renderQuality"].c_str());

@@ -142,7 +142,7 @@ void GaussianTrainerScene::saveGaussianModel() {
         logf_("export @%d: ply %d splats, %llu bytes, %.2f ms", m.step, m.n, (unsigned long long)(fec ? 0 : ply_bytes), ms_since(t_save));
     }
     if (m.rank == 0)
-        for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT, (int)Impl::EXPORT_SPZ})
+        for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT, (int)Impl::EXPORT_SPZ, (int)Impl::EXPORT_REDUCED})
             if (m.export_formats() & format) m.export_model(format);
     m.evaluate(true);                                                       // <modelPath>_<it>_eval.json beside the PLY (rank 0, evaluation on)
     m.render_at_save();                                                     // <modelPath>_<it>_renders/*.jpg (rank 0, renderViews on)
@@ -170,6 +170,11 @@ void GaussianTrainerScene::setMeshDecimate(int factor) {
     Impl& m = *impl_;
     if (factor != 0 && (factor < 2 || factor > 16)) { logf_("setMeshDecimate: %d is not 0 (off) or a factor 2..16: decimation is off", factor); factor = 0; }
     m.mesh_decimate_set = factor;
+}
+void GaussianTrainerScene::setReducedExport(float shCullThreshold, bool halfFloat) {
+    Impl& m = *impl_;
+    if (!(shCullThreshold >= 0.0f)) { logf_("setReducedExport: the threshold %g is not a number >= 0: 0.01 is used", (double)shCullThreshold); shCullThreshold = 0.01f; }
+    m.reduced_set = true; m.reduced_thr_set = shCullThreshold; m.reduced_half_set = halfFloat;
 }
 void GaussianTrainerScene::exportSparsePointCloud(const std::string& path) {
     Impl& m = *impl_;

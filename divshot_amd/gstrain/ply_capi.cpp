@@ -25,6 +25,14 @@ __attribute__((visibility("default"))) int gstrain_write_spz(const char* path, u
     if (err_out && err_cap > 0) { const size_t k = std::min<size_t>(err.size(), (size_t)err_cap - 1); memcpy(err_out, err.data(), k); err_out[k] = 0; }
     return 1;
 }
+// `payload`: the payload_bytes bytes that follow end_header (dvs_pack_reduced); layout or payload may be NULL: refused with a message
+__attribute__((visibility("default"))) int gstrain_write_reduced_ply(const char* path, const dvs_reduced_layout* layout, const uint8_t* payload,
+                                                                      uint64_t payload_bytes, char* err_out, uint64_t err_cap) {
+    std::string err;
+    if (gsply::write_reduced_ply(path, layout, payload, payload_bytes, &err)) return 0;
+    if (err_out && err_cap > 0) { const size_t k = std::min<size_t>(err.size(), (size_t)err_cap - 1); memcpy(err_out, err.data(), k); err_out[k] = 0; }
+    return 1;
+}
 __attribute__((visibility("default"))) int gstrain_write_mesh_ply(const char* path, uint64_t n_vertices, const float* xyz, const uint8_t* rgb,
                                                                    uint64_t n_triangles, const uint32_t* tri, char* err_out, uint64_t err_cap) {
     std::string err;

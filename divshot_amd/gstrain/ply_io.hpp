@@ -26,6 +26,12 @@ bool write_splat(const std::string& path, size_t n, const uint8_t* bytes, std::s
 // gzclose); without it the call fails with a message naming the library or the symbol.
 bool write_spz(const std::string& path, size_t n, int sh_degree, bool antialiased, const uint8_t* packed, const dvs_spz_layout& layout,
                std::string* err);
+// .reduced.ply, quantised (tiny_gsplat.cpp save_reduced_ply with quantised = true, read by load_reduced_ply): the header — `element
+// vertex <count>` four times, one block per SH degree 0..3, each with `property float|f16 x y z` and its `property u8` ids (f_dc_0..2,
+// f_rest_0..3 coeffs - 1, opacity, scale_0..2, rot_0..3), then `element cook_center 256` with the 20 float columns — and the payload
+// dvs_pack_reduced filled, layout->total bytes. An empty block keeps its header lines. Refused, with a message and nothing written: a
+// NULL layout or payload, a layout that is not the one its counts and half imply, no splats, payload_bytes != layout->total.
+bool write_reduced_ply(const std::string& path, const dvs_reduced_layout* layout, const uint8_t* payload, uint64_t payload_bytes, std::string* err);
 // The extracted surface (include/dvs_mesh.h): binary_little_endian PLY, `element vertex` x y z float + red green blue uchar (15 bytes),
 // `element face` with `property list uchar uint vertex_indices` (13 bytes per triangle). An empty mesh is a valid file with zero
 // elements. Refused, with a message, when an index is >= n_vertices (nothing is written then). With `normals` ([n_vertices][3]) the

@@ -167,6 +167,16 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     GrowBuf<float> d_decoded[6];
     double spz_mean[4] = {NAN, NAN, NAN, NAN};                               // {mse, l1, ssim, psnr} means of the decoded model ...
     int spz_it = -1;                                                         // ... at this iteration (-1: none)
+    // the .reduced.ply export (EXPORT_REDUCED): per-splat degrees, the camera centres, centres / iteration counts / block counts on the
+    // device (one small buffer), and the decoded model's means like the .spz ones. Nothing is allocated until the first such export.
+    GrowBuf<uint8_t> d_red_degree, d_red_small;
+    double reduced_mean[4] = {NAN, NAN, NAN, NAN};
+    int reduced_it = -1;
+    // DVS_SH_CULL_THRESHOLD (colour units, default 0.01: chosen without measurement) and DVS_REDUCED_HALF (0 | 1), or what setReducedExport
+    // said (reduced_set: it was called)
+    bool reduced_set = false; float reduced_thr_set = 0.01f; bool reduced_half_set = false;
+    float sh_cull_threshold() const;
+    bool reduced_half() const;
 
     // rendered views as JPEG files (cfg.renderViews / renderQuality / renderSampling and their DVS_RENDER_* overrides, read at load): at
     // every save rank 0 renders the selected cameras through eval_ctx (for_each_eval_pass: what `eval @it` scored), turns each pass
@@ -341,14 +351,16 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         return cfg.modelPath.size() >= k && cfg.modelPath.compare(cfg.modelPath.size() - k, k, suffix) == 0;
     }
     // EXPORT_* bits of the compact formats a save writes; decided at every use, since the editor sets modelPath after construction
-    enum { EXPORT_COMPRESSED = 1, EXPORT_SPLAT = 2, EXPORT_SPZ = 4 };
+    enum { EXPORT_COMPRESSED = 1, EXPORT_SPLAT = 2, EXPORT_SPZ = 4, EXPORT_REDUCED = 8 };
     int suffix_formats() const {
-        return model_path_ends(".compressed.ply") ? EXPORT_COMPRESSED : model_path_ends(".splat") ? EXPORT_SPLAT : model_path_ends(".spz") ? EXPORT_SPZ : 0;
+        return model_path_ends(".compressed.ply") ? EXPORT_COMPRESSED : model_path_ends(".splat") ? EXPORT_SPLAT : model_path_ends(".spz") ? EXPORT_SPZ :
+               model_path_ends(".reduced.ply") ? EXPORT_REDUCED : 0;
     }
     int asked_formats() const { return env_int("DVS_EXPORT_FORMATS", cfg.exportFormats); }   // 0: the suffix of modelPath decides
-    int export_formats() const { return (asked_formats() ? asked_formats() : suffix_formats()) & (EXPORT_COMPRESSED | EXPORT_SPLAT | EXPORT_SPZ); }
+    int export_formats() const { return (asked_formats() ? asked_formats() : suffix_formats()) & (EXPORT_COMPRESSED | EXPORT_SPLAT | EXPORT_SPZ | EXPORT_REDUCED); }
     void export_model(int format);
     void export_spz();
+    void export_reduced();
     // the tail of both: `bytes` of d_export_out to the host, the file through `write`, the `export @` line (unknown_size: the byte
     // count it prints when the file's size cannot be read). -> false when the file could not be written (logged)
     bool write_export(std::chrono::steady_clock::time_point t_start, size_t bytes, const std::string& file, const char* word, size_t unknown_size,

@@ -24,10 +24,17 @@ void GaussianTrainerScene::Impl::report_config() const {
               "%dx%d (targets box-filtered per step, cameras of dvs_camera_downscale); full resolution from iteration %d; evaluation always at full size",
               res_every, res_levels, res_levels, res_every, W, H, res_levels * res_every + 1);
     if (const int fmts = export_formats())
-        logf_("config: exportFormats %d: every save also writes%s%s%s beside the full PLY, packed on the device%s%s", fmts,
+        logf_("config: exportFormats %d: every save also writes%s%s%s%s beside the full PLY, packed on the device%s%s", fmts,
               (fmts & EXPORT_COMPRESSED) ? " <modelPath>_<it>.compressed.ply" : "", (fmts & EXPORT_SPLAT) ? " <modelPath>_<it>.splat" : "",
-              (fmts & EXPORT_SPZ) ? " <modelPath>_<it>.spz" : "", asked_formats() == 0 ? " (turned on by the suffix of modelPath)" : "",
+              (fmts & EXPORT_SPZ) ? " <modelPath>_<it>.spz" : "", (fmts & EXPORT_REDUCED) ? " <modelPath>_<it>.reduced.ply" : "", asked_formats() == 0 ? " (turned on by the suffix of modelPath)" : "",
               (fmts & EXPORT_SPZ) && !test_idx.empty() ? "; the .spz payload is decoded on the device and scored on the held-out views" : "");
+    if (export_formats() & EXPORT_REDUCED)
+        logf_("config: reduced export: twenty 256-entry k-means codebooks (at most 100 iterations each), %s positions; cullSH %d: %s%s",
+              reduced_half() ? "half-float" : "float", (int)cfg.cullSH,
+              cfg.cullSH ? ("every splat gets the smallest SH degree that loses at most " + std::to_string(sh_cull_threshold()) +
+                            " of colour from any training camera's centre (no visibility test; the 0.01 default was chosen without measurement)").c_str()
+                         : "every splat keeps the model's SH degree",
+              !test_idx.empty() ? "; the payload is decoded on the device and scored on the held-out views" : "");
     if (render_views)
         logf_("config: renderViews %d: every save also writes the %s cameras as JPEG files (quality %d, %s) to <modelPath>_<it>_renders/, rendered with the "
               "evaluation's options; transform on the device, entropy coding on the host%s", render_views,
@@ -64,7 +71,6 @@ void GaussianTrainerScene::Impl::report_config() const {
               (double)focus_trs[6], (double)focus_trs[7], (double)focus_trs[8]);
     std::string ign;
     if (cfg.modelType != 0) ign += " modelType(only 3DGS)";
-    if (cfg.cullSH) ign += " cullSH";
     if (cfg.pixelGradScale) ign += " pixelGradScale";
     if (cfg.bestQuality) ign += " bestQuality";
     if (cfg.normalConsistencyLoss) ign += " normalConsistencyLoss(2DGS)";
@@ -163,8 +169,15 @@ void GaussianTrainerScene::Impl::write_eval_json() const {
                 v + 1 < nt ? "," : "");
     }
     fprintf(f, "  ],\n  \"mean\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}", eval_mean[3], eval_mean[2], eval_mean[1], eval_mean[0]);
-    if (spz_it == step)                                                      // the decoded .spz model's means, scored by this save's export
-        fprintf(f, ",\n  \"exports\": {\"spz\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}}", spz_mean[3], spz_mean[2], spz_mean[1], spz_mean[0]);
+    if (spz_it == step || reduced_it == step) {                              // the decoded models' means, scored by this save's exports
+        fprintf(f, ",\n  \"exports\": {");
+        if (spz_it == step)
+            fprintf(f, "\"spz\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}", spz_mean[3], spz_mean[2], spz_mean[1], spz_mean[0]);
+        if (reduced_it == step)
+            fprintf(f, "%s\"reduced\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}", spz_it == step ? ", " : "", reduced_mean[3],
+                    reduced_mean[2], reduced_mean[1], reduced_mean[0]);
+        fprintf(f, "}");
+    }
     fprintf(f, "\n}\n");
     fclose(f);
 }
@@ -232,6 +245,7 @@ bool GaussianTrainerScene::Impl::write_export(std::chrono::steady_clock::time_po
 // does not matter), the packed payload alone copied to the host and written to <modelPath>_<step>.compressed.ply / .splat.
 void GaussianTrainerScene::Impl::export_model(int format) {
     if (format == EXPORT_SPZ) { export_spz(); return; }
+    if (format == EXPORT_REDUCED) { export_reduced(); return; }
     const auto t_start = std::chrono::steady_clock::now();
     const bool compressed = format == EXPORT_COMPRESSED;
     const size_t n_chunks = ((size_t)n + 255) / 256;
@@ -283,4 +297,92 @@ void GaussianTrainerScene::Impl::export_spz() {
     score_views(splats_of(d_decoded, n), res, spz_mean);
     spz_it = step;
     logf_("export @%d: spz decoded model: PSNR %.17g dB (full model %.17g dB), SSIM %.17g, L1 %.17g", step, spz_mean[3], eval_mean[3], spz_mean[2], spz_mean[1]);
+}
+
+float GaussianTrainerScene::Impl::sh_cull_threshold() const {
+    if (reduced_set) return reduced_thr_set;
+    const char* e = getenv("DVS_SH_CULL_THRESHOLD");
+    if (!e) return 0.01f;
+    char* end = nullptr;
+    const float t = strtof(e, &end);
+    if (end == e || *end || !(t >= 0.0f)) {
+        static bool said = false;
+        if (!said) { logf_("DVS_SH_CULL_THRESHOLD='%s' is not a number >= 0: 0.01 is used", e); said = true; }
+        return 0.01f;
+    }
+    return t;
+}
+bool GaussianTrainerScene::Impl::reduced_half() const { return reduced_set ? reduced_half_set : env_int("DVS_REDUCED_HALF", 0) == 1; }
+
+// The .reduced.ply export (include/dvs_export.h, last section): per-splat degrees — dvs_sh_degree_select over the training cameras'
+// centres with cullSH, else the model's SH degree (sh_max) for every splat —, the twenty codebooks, the block counts (16 bytes to the host, for
+// the layout), the payload; only the payload with its 20 KB table crosses to the host. Rank 0, on the training stream. With evaluation
+// on, the device payload is decoded into the second parameter set and scored like the .spz one.
+void GaussianTrainerScene::Impl::export_reduced() {
+    auto t0 = std::chrono::steady_clock::now();
+    const int D = sh_max, half = reduced_half() ? 1 : 0;   // the degree the full PLY stores and the evaluation renders (as the .spz export)
+    const std::vector<int> tc = training_cameras();
+    const size_t o_iters = (size_t)DVS_REDUCED_BOOKS * DVS_REDUCED_ENTRIES * sizeof(float), o_counts = o_iters + 96, o_cams = o_counts + 16;
+    d_export_scratch.reserve(dvs_reduced_scratch_bytes(n));
+    d_red_degree.reserve(((size_t)n + 15) & ~(size_t)15);
+    d_red_small.reserve(o_cams + ((tc.size() * 3 * sizeof(float) + 15) & ~(size_t)15));
+    uint8_t* const small = d_red_small.get();
+    float* const centres = (float*)small;
+    int32_t* const iters = (int32_t*)(small + o_iters);
+    uint32_t* const counts = (uint32_t*)(small + o_counts);
+    const float *pos = d_param[P_POS].get(), *sh0 = d_param[P_SH0].get(), *shN = d_param[P_SHN].get(), *opa = d_param[P_OPA].get(),
+                *scale = d_param[P_SCALE].get(), *rot = d_param[P_ROT].get();
+    const auto check = [](int status, const char* what) { if (status != DVS_OK) throw std::runtime_error(std::string(what) + ": status " + std::to_string(status)); };
+    if (cfg.cullSH && D > 0) {
+        std::vector<float> centre(tc.size() * 3);
+        for (size_t k = 0; k < tc.size(); ++k) for (int a = 0; a < 3; ++a) centre[3 * k + a] = cams[(size_t)tc[k]].campos[a];
+        HIP_OR_THROW(hipMemcpyAsync(small + o_cams, centre.data(), centre.size() * sizeof(float), hipMemcpyHostToDevice, stream.get()));
+        check(dvs_sh_degree_select(stream.get(), n, D, pos, shN, DVS_SHN_TILED, (const float*)(small + o_cams), (int)tc.size(), sh_cull_threshold(),
+                                   d_red_degree.get()), "dvs_sh_degree_select");
+        HIP_OR_THROW(hipStreamSynchronize(stream.get()));                    // (also: `centre` leaves scope)
+    } else {
+        HIP_OR_THROW(hipMemsetAsync(d_red_degree.get(), D, (size_t)n, stream.get()));
+        HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    }
+    const double ms_select = ms_since(t0);
+    auto t1 = std::chrono::steady_clock::now();
+    check(dvs_codebooks_build(stream.get(), n, sh0, shN, DVS_SHN_TILED, opa, scale, rot, d_red_degree.get(), 100, d_export_scratch.get(), centres, iters),
+          "dvs_codebooks_build");
+    check(dvs_reduced_degree_counts(stream.get(), n, d_red_degree.get(), d_export_scratch.get(), counts), "dvs_reduced_degree_counts");
+    int32_t h_iters[DVS_REDUCED_BOOKS];
+    uint32_t h_counts[4];
+    HIP_OR_THROW(hipMemcpyAsync(h_iters, iters, sizeof h_iters, hipMemcpyDeviceToHost, stream.get()));
+    HIP_OR_THROW(hipMemcpyAsync(h_counts, counts, sizeof h_counts, hipMemcpyDeviceToHost, stream.get()));
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    const double ms_books = ms_since(t1);
+    auto t2 = std::chrono::steady_clock::now();
+    dvs_reduced_layout layout;
+    check(dvs_reduced_layout_for(h_counts, half, &layout), "dvs_reduced_layout_for");
+    const size_t bytes = (size_t)layout.total;
+    d_export_out.reserve(bytes);
+    check(dvs_pack_reduced(stream.get(), n, pos, sh0, shN, DVS_SHN_TILED, opa, scale, rot, d_red_degree.get(), centres, d_export_scratch.get(), &layout,
+                           d_export_out.get()), "dvs_pack_reduced");
+    if (export_host.size() < bytes) export_host.resize(bytes);
+    HIP_OR_THROW(hipMemcpyAsync(export_host.data(), d_export_out.get(), bytes, hipMemcpyDeviceToHost, stream.get()));
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    const double ms_pack = ms_since(t2);
+    const std::string file = cfg.modelPath + "_" + std::to_string(step) + ".reduced.ply";
+    std::string err;
+    if (!gsply::write_reduced_ply(file, &layout, export_host.data(), bytes, &err)) { logf_("export @%d: %s", step, err.c_str()); return; }
+    std::error_code ec;
+    const auto file_bytes = std::filesystem::file_size(file, ec);
+    int most = 0;
+    for (int it : h_iters) most = std::max(most, it);
+    logf_("export @%d: reduced %d splats (%u/%u/%u/%u by degree), %llu bytes, degree select %.2f ms, codebooks %.2f ms (%d iterations at most), pack %.2f ms",
+          step, n, h_counts[0], h_counts[1], h_counts[2], h_counts[3], (unsigned long long)(ec ? bytes : file_bytes), ms_select, ms_books, most, ms_pack);
+    if (test_idx.empty() || rank != 0) return;
+    for (int g = 0; g < 6; ++g) d_decoded[g].reserve(dev_floats_for(g, n) * sizeof(float) + 16);
+    check(dvs_unpack_reduced(stream.get(), n, d_export_out.get(), &layout, d_decoded[P_POS].get(), d_decoded[P_SH0].get(), d_decoded[P_SHN].get(),
+                             DVS_SHN_TILED, d_decoded[P_OPA].get(), d_decoded[P_SCALE].get(), d_decoded[P_ROT].get(), nullptr), "dvs_unpack_reduced");
+    if (eval_it != step) run_evaluation();                                  // the full model of the same parameters: the comparison
+    std::vector<double> res;
+    score_views(splats_of(d_decoded, n), res, reduced_mean);
+    reduced_it = step;
+    logf_("export @%d: reduced decoded model: PSNR %.17g dB (full model %.17g dB), SSIM %.17g, L1 %.17g", step, reduced_mean[3], eval_mean[3],
+          reduced_mean[2], reduced_mean[1]);
 }

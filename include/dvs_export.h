@@ -6,6 +6,8 @@
  *   .splat           one 32-byte record per splat                                       tiny_gsplat.cpp:243-291
  *   .spz             version 3: six byte sections, 20 + 3 dim B per splat, gzipped      spz/src/load-spz.cc (packGaussians,
  *                    by the host writer; the one compact format with the SH bands above 0       unpackGaussians), tiny_gsplat.cpp:1232-1272
+ *   .reduced.ply     quantised: four per-degree vertex blocks of codebook ids + twenty           tiny_gsplat.cpp:398-630 (save), :817-992 (load);
+ *                    256-entry k-means codebooks, 17..68 B per splat (last section below)        the producing side is defined in this header
  * Only the packed payload has to cross to the host (16.2 B / 32 B / 65 B per splat instead of the 236 B of the full PLY). The first two
  * never read the SH bands above 0 (neither format has them), so the layout of shN does not matter to them; .spz reads either layout.
  *
@@ -101,6 +103,85 @@ int dvs_pack_spz(void* stream, int n, int sh_degree, const float* pos, const flo
  * shN may be NULL at degree 0 (nothing is written for it). Same DVS_ERR_INVALID rules as dvs_pack_spz. */
 int dvs_unpack_spz(void* stream, int n, int sh_degree, const uint8_t* packed, float* pos, float* sh0, float* shN, int shn_layout,
                    float* opacity, float* scale, float* rot);
+
+/* ---- .reduced.ply, the quantised variant (tiny_gsplat.cpp save_reduced_ply / load_reduced_ply with quantised = true) -----------------
+ * Four vertex blocks, one per SH degree 0..3, then a table of twenty 256-entry scalar codebooks. The reference defines the container
+ * and its reader; it has no caller that chooses degrees or builds codebooks, so the producing side is defined HERE, bit for bit
+ * (tests/reduced_ply_ref.py restates it in numpy).
+ * Codebook columns, in the file's order: 0 f_dc, 1..15 f_rest_0..14, 16 opacity, 17 scale, 18 rot_re, 19 rot_im. */
+#define DVS_REDUCED_BOOKS 20
+#define DVS_REDUCED_ENTRIES 256
+#define DVS_REDUCED_MAX_VALUES (1 << 25)      /* values of one codebook: 3 n <= 2^25 */
+
+/* Bytes of scratch the three calls below that take `scratch` need for n splats (0 for n <= 0). No initialisation needed. */
+size_t dvs_reduced_scratch_bytes(int n);
+
+/* degree[i] = the smallest SH degree k <= D that loses at most t of colour from any of the C camera centres (the cullSH rule).
+ * For camera c: v = pos_i - o_c, len = sqrt((v_x^2 + v_y^2) + v_z^2), d = v / len; a camera with len == 0 or not finite is skipped.
+ * err_k(i) = max over cameras and the three channels of |sum over the coefficients l of the bands k < band <= D of Y_l(d) shN[i][l][ch]|,
+ * Y_l the basis of the rasterizer's forward (dvs_device.h constants); err_D = 0. degree[i] = the smallest k with err_k(i) <= t; an
+ * err_k that is not finite exceeds t. fp32 without contraction; per channel the band sums are taken coefficient by coefficient in
+ * ascending order and the bands added from the highest down (the result is a tolerance-level quantity: only its order of magnitude
+ * matters). Every given camera counts and no visibility test is made: a camera that never sees the splat can only RAISE its degree,
+ * so the rule is conservative. One lane per splat, no atomics.
+ *   cams   DEVICE [C][3] camera centres         degree  DEVICE [n] bytes
+ * DVS_ERR_INVALID for n <= 0, D outside 0..3, C <= 0, t negative or NaN, an unknown layout, a NULL pointer (shN: only above D = 0), a
+ * pointer off a 16-byte boundary; nothing is launched then. */
+int dvs_sh_degree_select(void* stream, int n, int D, const float* pos, const float* shN, int shn_layout, const float* cams, int C, float t,
+                         uint8_t* degree);
+
+/* The twenty codebooks of a model whose per-splat degrees are degree[] (each 0..3; a larger byte counts as 3).
+ * Value sets (the STORED parameters, not activated): f_dc the 3 n sh0 values; f_rest_j the 3 channels of coefficient j of every splat
+ * whose degree stores coefficient j (j < (degree + 1)^2 - 1); opacity the n logits; scale the 3 n log scales; rot_re / rot_im the w /
+ * the x, y, z of rot normalised as dvs_pack_spz normalises it (squared norm 0 or not finite: (1, 0, 0, 0)). A value that is not finite
+ * is clustered as 0, and -0 as +0.
+ * Per codebook, with V the multiset of its m values — the result does not depend on the order of V:
+ *   1. m = 0, or A = max |v| = 0: all 256 centres are 0 (0 iterations).
+ *   2. e = the exponent with A < 2^e <= 2 A (frexp); k(v) = (int64)rint(ldexp((double)v, 36 - e)), ties to even.
+ *   3. s[0..m) = V ascending; c_j = s[((2 j + 1) m) / 512] (integer division), j = 0..255.
+ *   4. One iteration: b_j = ((double)c_j + (double)c_{j+1}) * 0.5, j = 0..254; the cluster of v is #{j : b_j < (double)v} (a value on a
+ *      boundary goes below it); c_q = (float)ldexp((double)S_q / (double)N_q, e - 36) with S_q the exact int64 sum of k(v) over cluster q
+ *      and N_q its size; an empty cluster keeps its centre.
+ *   5. Iterate until an iteration would assign every value as the one before it did (that iteration is not run or counted), at most
+ *      max_iters iterations. iters[b] = the iterations run.
+ *   6. The id of a value (dvs_pack_reduced) = its cluster by rule 4 under the FINAL centres.
+ * Implementation: one stable radix sort of the order-preserving keys per codebook, an inclusive int64 prefix sum of k over s[], then all
+ * iterations in ONE launch of ONE 256-lane workgroup (lane j owns centre j: 255 binary searches into s[] and prefix differences per
+ * iteration). No float atomics, no host round trip; two calls give identical bytes. The codebooks are processed one after another.
+ *   centres DEVICE [20][256] floats (book-major)     iters DEVICE [20] int32     scratch dvs_reduced_scratch_bytes(n) bytes
+ * DVS_ERR_INVALID for n <= 0, 3 n > DVS_REDUCED_MAX_VALUES, max_iters < 1, an unknown layout, a NULL pointer (shN included), a pointer
+ * off a 16-byte boundary; nothing is launched then. */
+int dvs_codebooks_build(void* stream, int n, const float* sh0, const float* shN, int shn_layout, const float* opacity, const float* scale,
+                        const float* rot, const uint8_t* degree, int max_iters, void* scratch, float* centres, int32_t* iters);
+
+/* counts[d] (DEVICE, 4 words) = the number of splats of degree d (a byte above 3 counts as 3): what dvs_reduced_layout_for needs. */
+int dvs_reduced_degree_counts(void* stream, int n, const uint8_t* degree, void* scratch, uint32_t* counts);
+
+/* The payload = the file's bytes after end_header: block d at off[d] holds count[d] records of stride[d] = xyz + 3 + 3 coeffs + 8 bytes
+ * (xyz = 12, or 6 with half; coeffs = (d + 1)^2 - 1), blocks back to back; the codebook table at table_off = off[3] + count[3] *
+ * stride[3] is [256][20] floats (row = entry); total = table_off + 20480. */
+typedef struct dvs_reduced_layout { uint64_t count[4], off[4], stride[4], table_off, total; int32_t half, _pad; } dvs_reduced_layout;
+/* Host only. DVS_ERR_INVALID for counts == NULL, out == NULL, a sum of counts that is 0 or above INT32_MAX, half outside 0..1. */
+int dvs_reduced_layout_for(const uint32_t counts[4], int half, dvs_reduced_layout* out);
+
+/* The payload of L into `out` (L->total bytes). The record of a degree-d splat: xyz as 3 floats, or (L->half) as 3 halves — round to
+ * nearest even, |x| >= 65520 (infinities included) saturates to +-65504, NaN -> 0; the 3 f_dc ids; the 3 coeffs f_rest ids, coefficient-
+ * major and channel-minor; then opacity id, 3 scale ids, rot_re id, 3 rot_im ids. Ids by rule 6 above (binary search over the 255
+ * boundaries of each codebook, held in LDS). Within a block the splats keep the model's order (a stable 4-way partition). L->count must
+ * be the counts of degree[]: a record that would fall outside its block is not written. A workgroup stages its 256 splats' four runs
+ * in LDS and stores them as 16-byte words wherever a run covers one.
+ * DVS_ERR_INVALID for n <= 0 or n != the sum of L->count, an unknown layout, a NULL pointer (shN included), a pointer off a 16-byte
+ * boundary; nothing is launched then. */
+int dvs_pack_reduced(void* stream, int n, const float* pos, const float* sh0, const float* shN, int shn_layout, const float* opacity,
+                     const float* scale, const float* rot, const uint8_t* degree, const float* centres /*[20][256]*/, void* scratch,
+                     const dvs_reduced_layout* L, uint8_t* out);
+
+/* What load_reduced_ply reconstructs from that payload, into a parameter set: the splats in BLOCK order (all of degree 0, then 1, ...),
+ * every value the centre its id names (rot = (rot_re centre, three rot_im centres)), the coefficients above a splat's degree 0, and in
+ * DVS_SHN_TILED so are the three pad floats and the lanes of the last tile past n (whole tiles are written). degree (nullable) [n]
+ * receives each output splat's degree. Same DVS_ERR_INVALID rules as dvs_pack_reduced. */
+int dvs_unpack_reduced(void* stream, int n, const uint8_t* packed, const dvs_reduced_layout* L, float* pos, float* sh0, float* shN,
+                       int shn_layout, float* opacity, float* scale, float* rot, uint8_t* degree);
 
 #ifdef __cplusplus
 }

@@ -87,8 +87,9 @@ struct GaussianTrainConfig {
     // format): 1 = <modelPath>_<it>.compressed.ply (chunked, quantised: 16 B per splat + 48 B per 256), 2 = <modelPath>_<it>.splat
     // (32 B per splat), 4 = <modelPath>_<it>.spz (version 3, gzipped, 20 + 3 dim B per splat: keeps the SH bands above 0). Packed on the
     // device from the trained arrays (include/dvs_export.h); only the packed payload crosses to the host.
+    // 8 = <modelPath>_<it>.reduced.ply (per-splat SH degree with cullSH, twenty 256-entry k-means codebooks, 17..68 B per splat).
     // The editor passes its "Splat Format" choice only as the suffix of modelPath (editor.cpp:1886-1904, 2024): while this field is 0 a
-    // modelPath ending in ".compressed.ply" / ".splat" / ".spz" turns on the matching bit. DVS_EXPORT_FORMATS overrides the field.
+    // modelPath ending in ".compressed.ply" / ".splat" / ".spz" / ".reduced.ply" turns on the matching bit. DVS_EXPORT_FORMATS overrides the field.
     int exportFormats = 0;
     // extension of this build, appended the same way (0 = the reference's behaviour: a save writes no picture). renderViews: bit 1 = the
     // test cameras (evalHoldout), bit 2 = the training cameras; at every saveGaussianModel() they are rendered with the evaluation's
@@ -131,6 +132,10 @@ public:
     // vertices inside a cell of factor^3 voxels of the extraction grid into one (vertex clustering on the device); 0 = off, any other
     // value is reported and counts as 0. Wins over DVS_MESH_DECIMATE once called.
     void setMeshDecimate(int factor);
+    // the .reduced.ply export (extension of this build; exportFormats bit 8, INTEGRATION.md "Compact exports"): the colour a splat may lose
+    // when cullSH lowers its SH degree (>= 0, default 0.01) and whether positions are written as half floats. Once called it wins over
+    // DVS_SH_CULL_THRESHOLD / DVS_REDUCED_HALF.
+    void setReducedExport(float shCullThreshold, bool halfFloat);
     void exportSparsePointCloud(const std::string& path);   // editor.cpp:3535 — writes the splat centres as an ASCII PLY point cloud
     void saveCameraDatas(const std::string& path);          // editor.cpp:3512 — one line per camera: centre, view matrix, intrinsics
     bool isTrain() const;
