@@ -889,12 +889,10 @@ int dvs_sort_pairs_u32(dvs_ctx* c, void* stream, uint32_t* keys, uint32_t* vals,
     int cur = 0;
     // (partition offsets are 32-bit: the last partition's element indices must not wrap — ADVICE r05)
     if (n > (1ull << 32) - 4097ull) return fail(DVS_ERR_CAPACITY, "dvs_sort_pairs_u32", "n must be at most 2^32 - 4097");
-    TRY(c->fe.hist.ensure(dvs_fe_hist_words(n, 1, 512) * 4));
-    const uint32_t part = dvs_fe_part_for(n);
-    HIPCHECK(dvs_launch_seg_init(st, (int)n, 1, 0, c->fe.seg_all));      // one segment: [0, n)
-    invalidate(c, DROP_SEGS);
-    HIPCHECK(dvs_launch_seg_sort(st, 1, k[0], v[0], k[1], v[1], c->fe.seg_all, bit_lo, bit_hi - bit_lo, n, part, (uint32_t)(n / part) + 3u,
-                                 c->fe.hist.as<uint32_t>(), c->fe.totals, 0u, &cur, nullptr, 1, 0, c->fe.rank_atomic));
+    TRY(c->fe.hist.ensure(dvs_pair_sort_hist_bytes(n)));
+    invalidate(c, DROP_SEGS);                                            // the sort writes its one segment over the context's descriptors
+    HIPCHECK(dvs_launch_pair_sort(st, n, k[0], v[0], k[1], v[1], bit_lo, bit_hi - bit_lo,
+                                  DvsPairSortWs{c->fe.seg_all, c->fe.totals, c->fe.hist.as<uint32_t>()}, c->fe.rank_atomic, &cur));
     if (cur == 1) {
         HIPCHECK(hipMemcpyAsync(keys, k[1], n * 4, hipMemcpyDeviceToDevice, st));
         HIPCHECK(hipMemcpyAsync(vals, v[1], n * 4, hipMemcpyDeviceToDevice, st));

@@ -79,6 +79,9 @@ template <class T> __device__ __forceinline__ T dvs_karg(size_t byte_offset) {
 __device__ __forceinline__ int64_t dvs_shn_index(int layout, int i, int e) {
     return layout == DVS_SHN_TILED ? ((((int64_t)(i >> 6) * 12 + (e >> 2)) * 64 + (i & 63)) * 4 + (e & 3)) : ((int64_t)i * 45 + e);
 }
+// The same address in the DVS_SHN_TILED layout for a whole 16-byte chunk: the float4 index of chunk c (elements 4 c .. 4 c + 3, c < 12) of
+// splat i, for the export kernels that move a splat's shN as float4 words (dvs_shn_index(TILED, i, e) = 4 * this(i, e >> 2) + (e & 3)).
+__device__ __forceinline__ int64_t dvs_shn_tiled_chunk(int64_t i, int c) { return ((i >> 6) * 12 + c) * 64 + (i & 63); }
 // counter-based RNG: one 32-bit hash per (seed, index, draw), and the uniform in (0, 1) of its high 24 bits
 __device__ __forceinline__ uint32_t dvs_hash3(uint32_t a, uint32_t b, uint32_t c) {
     uint32_t h = a * 0x9E3779B1u ^ (b + 0x7F4A7C15u) * 0x85EBCA77u ^ (c + 0x165667B1u) * 0xC2B2AE3Du;

@@ -106,6 +106,16 @@ hipError_t dvs_launch_seg_sort(hipStream_t st, int V, uint32_t* keys0, uint32_t*
                                uint64_t grid_elems, uint32_t part, uint32_t nbtot, uint32_t* hist, uint32_t* totals, uint32_t key_add_per_view,
                                int* result_in, uint32_t* ranges_enc = nullptr /*A6 fused into the last pass: tile ranges as (~start, end), see k_seg_scatter*/,
                                int write_last_keys = 1, int first_keys16 = 0 /*keys0 holds 16-bit keys (A4's tile ids)*/, int rank_atomic = 0);
+// The same sort for ONE segment [0, n): what every user outside the multi-view front end calls (the packers' Morton order, the codebooks,
+// the mesh decimation, dvs_sort_pairs_u32). Buffers 0 hold the input, *cur says which hold the result; bits <= 0 launches nothing and
+// leaves *cur = 0. The workspace, never initialised: dvs_pair_sort_ws_bytes(n) bytes carved by dvs_pair_sort_ws_at into {descriptor,
+// totals, histogram} on 256-byte boundaries, or three parts the caller owns (hist: dvs_pair_sort_hist_bytes(n), totals: DVS_FE_MAXBINS
+// words). rank_atomic = 0 is the ballot ranking: correct by construction, no probe of the device needed.
+struct DvsPairSortWs { DvsSeg* seg; uint32_t* totals; uint32_t* hist; };
+size_t dvs_pair_sort_hist_bytes(uint64_t n), dvs_pair_sort_ws_bytes(uint64_t n);
+DvsPairSortWs dvs_pair_sort_ws_at(void* base);
+hipError_t dvs_launch_pair_sort(hipStream_t st, uint64_t n, uint32_t* keys0, uint32_t* vals0, uint32_t* keys1, uint32_t* vals1, int bit_lo, int bits,
+                                const DvsPairSortWs& ws, int rank_atomic, int* cur);
 // runs the two in-wave rankings of k_seg_scatter side by side on synthetic digits; *bad_dev (zeroed) counts disagreements (frontend.hip)
 hipError_t dvs_fe_probe_rank_atomic(hipStream_t st, uint32_t* bad_dev);
 // stage 0 = A3 (tile counts in depth order, block / super sums) + the views' instance ranges (seg_tile, total_dev); stage 1 = A4

@@ -761,6 +761,26 @@ hipError_t dvs_launch_seg_init(hipStream_t st, int n, int V, uint32_t rows_per_v
     return hipGetLastError();
 }
 
+// ---- the one-segment stable pair sort (dvs_kernels.h): the three relations its users depend on, stated once ----------------------------
+// hist: the kernels address hist[digit * nbtot + row] with digit < 512 (digits are at most FE_REORDER_BITS = 9 wide) and row < nbtot.
+// dvs_fe_hist_words sizes for the SMALLER partition: ceil(n / 2048) + 7 rows, and dvs_fe_part_for returns 2048 keys or more, so the
+// nbtot = n / part + 3 rows always fit. totals: k_seg_rowscan writes totals[view * DVS_FE_MAXBINS + digit], and there is one view.
+static const size_t FE_PS_TOTALS = dvs_align256(sizeof(DvsSeg)), FE_PS_HIST = FE_PS_TOTALS + dvs_align256((size_t)DVS_FE_MAXBINS * sizeof(uint32_t));
+size_t dvs_pair_sort_hist_bytes(uint64_t n) { return dvs_fe_hist_words(n, 1, 512) * sizeof(uint32_t); }
+size_t dvs_pair_sort_ws_bytes(uint64_t n) { return FE_PS_HIST + dvs_align256(dvs_pair_sort_hist_bytes(n)); }
+DvsPairSortWs dvs_pair_sort_ws_at(void* base) { return {(DvsSeg*)base, (uint32_t*)((char*)base + FE_PS_TOTALS), (uint32_t*)((char*)base + FE_PS_HIST)}; }
+hipError_t dvs_launch_pair_sort(hipStream_t st, uint64_t n, uint32_t* keys0, uint32_t* vals0, uint32_t* keys1, uint32_t* vals1, int bit_lo, int bits,
+                                const DvsPairSortWs& ws, int rank_atomic, int* cur) {
+    *cur = 0;
+    if (bits <= 0) return hipSuccess;
+    // nbtot: the segment's rows are its ceil(n / part) <= n / part + 1 partitions, counted from pstart = 0 (the launch's one spare
+    // workgroup per view finds no partition left and writes nothing); + 3 keeps the margin the table is sized with
+    const uint32_t part = dvs_fe_part_for(n), nbtot = (uint32_t)(n / part) + 3u;
+    const hipError_t e = dvs_launch_seg_init(st, (int)n, 1, 0, ws.seg);
+    if (e != hipSuccess) return e;
+    return dvs_launch_seg_sort(st, 1, keys0, vals0, keys1, vals1, ws.seg, bit_lo, bits, n, part, nbtot, ws.hist, ws.totals, 0u, cur, nullptr, 1, 0, rank_atomic);
+}
+
 // ---- A6 as its own kernel: only with DVS_FE_NO_FUSE_A6=1 (a cross-check switch of the parity tests);
 // normally the tile sort's last pass builds the ranges (k_seg_scatter) ---------------------------------------------------------------
 __global__ void __launch_bounds__(FE_BLOCK)

@@ -23,6 +23,7 @@
 #include <cmath>
 #include "dvs_device.h"
 #include "dvs_kernels.h"
+#include "export_common.h"
 #include "../../include/dvs_raster.h"
 #include "../../include/dvs_init.h"
 
@@ -158,7 +159,7 @@ k_init_from_points(int n, const uint8_t* __restrict__ rgb, const float* __restri
 
 struct KnnScratch { size_t morton, rec, box, total; };
 KnnScratch knn_layout(int n) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const auto up = dvs_align256;
     KnnScratch L;
     size_t o = 0;
     L.morton = o; o += up(dvs_morton_scratch_bytes(n));
@@ -167,7 +168,6 @@ KnnScratch knn_layout(int n) {
     L.total = o;
     return L;
 }
-bool off16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
 
 int knn_run(hipStream_t st, int n, const float* pos, void* scratch, float* dist2, unsigned long long* visited) {
     const KnnScratch L = knn_layout(n);
@@ -187,21 +187,18 @@ int knn_run(hipStream_t st, int n, const float* pos, void* scratch, float* dist2
 extern "C" size_t dvs_knn_scratch_bytes(int n) { return n > 0 ? knn_layout(n).total : 0; }
 
 extern "C" int dvs_knn_mean_dist2(void* stream, int n, const float* pos, void* scratch, float* dist2) {
-    if (n <= 0 || !pos || !scratch || !dist2) return DVS_ERR_INVALID;
-    if (off16(pos) || off16(scratch) || off16(dist2)) return DVS_ERR_INVALID;
+    if (n <= 0 || dvs_bad_args({pos, scratch, dist2})) return DVS_ERR_INVALID;
     return knn_run((hipStream_t)stream, n, pos, scratch, dist2, nullptr);
 }
 
 extern "C" int dvs_knn_mean_dist2_stats(void* stream, int n, const float* pos, void* scratch, float* dist2, uint64_t* boxes_streamed) {
-    if (n <= 0 || !pos || !scratch || !dist2 || !boxes_streamed) return DVS_ERR_INVALID;
-    if (off16(pos) || off16(scratch) || off16(dist2) || off16(boxes_streamed)) return DVS_ERR_INVALID;
+    if (n <= 0 || dvs_bad_args({pos, scratch, dist2, boxes_streamed})) return DVS_ERR_INVALID;
     return knn_run((hipStream_t)stream, n, pos, scratch, dist2, (unsigned long long*)boxes_streamed);
 }
 
 extern "C" int dvs_init_from_points(void* stream, int n, const float* pos, const uint8_t* rgb, const float* dist2, float* sh0, float* opacity,
                                     float* scale, float* rot) {
-    if (n <= 0 || !pos || !rgb || !dist2 || !sh0 || !opacity || !scale || !rot) return DVS_ERR_INVALID;
-    if (off16(pos) || off16(rgb) || off16(dist2) || off16(sh0) || off16(opacity) || off16(scale) || off16(rot)) return DVS_ERR_INVALID;
+    if (n <= 0 || dvs_bad_args({pos, rgb, dist2, sh0, opacity, scale, rot})) return DVS_ERR_INVALID;
     const float opacity0 = (float)std::log((double)(0.1f / 0.9f));          // the logit of 0.1, rounded once
     const unsigned nblocks = (unsigned)(((int64_t)n + KN_BLOCK - 1) / KN_BLOCK);
     hipLaunchKernelGGL(k_init_from_points, dim3(nblocks), dim3(KN_BLOCK), 0, (hipStream_t)stream, n, rgb, dist2, opacity0, sh0, opacity, scale,

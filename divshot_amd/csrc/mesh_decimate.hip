@@ -51,7 +51,7 @@ struct DecBlock {
 static_assert(sizeof(DecBlock) == 64, "one block of words");
 
 struct DecLayout {
-    size_t seg, totals, hist;                                          // the sort's workspace, shared by the vertex and the triangle sorts
+    size_t sort_ws;                                                    // the pair sort's workspace, shared by the vertex and the triangle sorts
     size_t vkey[2], vval[2], cex, bsum_v, vclu, cstart, used, coff;    // per vertex
     size_t rec, recn;                                                  // the gathered records (written by dvs_mesh_decimate_write)
     size_t w[3], tkey[2], tval[2], keep, toff, bsum_t;                 // per triangle
@@ -62,9 +62,7 @@ DecLayout dec_layout(uint32_t nv, uint32_t nt) {
     const size_t v = nv ? nv : 1, t = nt ? nt : 1, big = v > t ? v : t;
     size_t o = 0;
     auto part = [&o](size_t bytes) { const size_t at = o; o = dvs_align256(o + bytes); return at; };
-    L.seg = part(sizeof(DvsSeg));
-    L.totals = part((size_t)DVS_FE_MAXBINS * sizeof(uint32_t));
-    L.hist = part(dvs_fe_hist_words((uint64_t)big, 1, 512) * sizeof(uint32_t));
+    L.sort_ws = part(dvs_pair_sort_ws_bytes((uint64_t)big));
     for (int k = 0; k < 2; ++k) { L.vkey[k] = part(v * 4); L.vval[k] = part(v * 4); }
     L.cex = part(v * 4);
     L.bsum_v = part(((v + DVS_SCAN_TILE - 1) / DVS_SCAN_TILE) * 4);
@@ -269,16 +267,6 @@ k_dec_write_t(uint32_t nv, const uint32_t* __restrict__ tri, uint32_t nt, const 
 
 // bits of the largest value a word can take: the cluster numbers are below min(n_vertices, cells)
 int bits_for(uint64_t max_value) { int b = 0; while (b < 32 && (max_value >> b)) ++b; return b; }
-
-// one stable sort of n (key, value) pairs over the low `bits` key bits: buffers 0 hold the input, *cur says where the result is
-hipError_t dec_sort(hipStream_t st, const DecLayout& L, char* base, uint32_t n, uint32_t* key[2], uint32_t* val[2], int bits, int* cur) {
-    const uint32_t part = dvs_fe_part_for((uint64_t)n);
-    hipError_t e = dvs_launch_seg_init(st, (int)n, 1, 0, (DvsSeg*)(base + L.seg));
-    if (e != hipSuccess) return e;
-    // one segment [0, n); ballot ranking (rank_atomic = 0), as dvs_launch_morton_order calls it
-    return dvs_launch_seg_sort(st, 1, key[0], val[0], key[1], val[1], (DvsSeg*)(base + L.seg), 0, bits, (uint64_t)n, part, n / part + 3u,
-                               (uint32_t*)(base + L.hist), (uint32_t*)(base + L.totals), 0u, cur, nullptr, 1, 0, 0);
-}
 }  // namespace
 
 extern "C" size_t dvs_mesh_decimate_scratch_bytes(uint32_t n_vertices, uint32_t n_triangles) { return dec_layout(n_vertices, n_triangles).total; }
@@ -309,7 +297,8 @@ extern "C" int dvs_mesh_decimate_count(void* stream, uint32_t n_vertices, const 
     uint32_t* vval[2] = {(uint32_t*)(base + L.vval[0]), (uint32_t*)(base + L.vval[1])};
     hipLaunchKernelGGL(k_dec_keys, gv, block, 0, st, nv, xyz, g, vkey[0], vval[0]);
     int vc = 0;
-    if (dec_sort(st, L, base, nv, vkey, vval, 30, &vc) != hipSuccess) return DVS_ERR_HIP;
+    const DvsPairSortWs ws = dvs_pair_sort_ws_at(base + L.sort_ws);
+    if (dvs_launch_pair_sort(st, nv, vkey[0], vval[0], vkey[1], vval[1], 0, 30, ws, 0, &vc) != hipSuccess) return DVS_ERR_HIP;      // ballot ranking
     // the write call looks for the sorted order in buffers 0 (where the four passes of 30 bits leave it)
     if (vc != 0 && (hipMemcpyAsync(vkey[0], vkey[1], (size_t)nv * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
                     hipMemcpyAsync(vval[0], vval[1], (size_t)nv * 4, hipMemcpyDeviceToDevice, st) != hipSuccess))
@@ -334,7 +323,7 @@ extern "C" int dvs_mesh_decimate_count(void* stream, uint32_t n_vertices, const 
         for (int word = 2; word >= 0; --word) {
             if (word < 2) hipLaunchKernelGGL(k_dec_regather, gt, block, 0, st, nt, (const uint32_t*)tval[0], (const uint32_t*)w[word], tkey[0]);
             int c = 0;
-            if (dec_sort(st, L, base, nt, tkey, tval, bits, &c) != hipSuccess) return DVS_ERR_HIP;
+            if (dvs_launch_pair_sort(st, nt, tkey[0], tval[0], tkey[1], tval[1], 0, bits, ws, 0, &c) != hipSuccess) return DVS_ERR_HIP;
             if (c) { std::swap(tkey[0], tkey[1]); std::swap(tval[0], tval[1]); }       // buffers 0: the order so far
         }
         hipLaunchKernelGGL(k_dec_dups, gt, block, 0, st, nt, (const uint32_t*)tval[0], (const uint32_t*)w[0], (const uint32_t*)w[1], (const uint32_t*)w[2],

@@ -5,7 +5,7 @@
 //   (a) k_pack_bounds / k_pack_bounds_final: min / max of pos per axis. Every workgroup writes its partial result to its own slot, one
 //       small workgroup combines the slots: no float atomics, the result does not depend on the schedule.
 //   (b) k_pack_morton: one 30-bit Morton key (10 bits per axis over the model's box) and the splat index per splat.
-//   (c) the stable segmented LSD radix sort of frontend.hip (dvs_launch_seg_sort, one segment, four passes, ballot ranking): equal
+//   (c) the stable one-segment pair sort of frontend.hip (dvs_launch_pair_sort, 30 bits in four passes, ballot ranking): equal
 //       keys stay in index order.
 //   (d) k_pack_chunks: one workgroup of 256 lanes per chunk of 256 consecutive sorted entries (the last may be partial). A lane gathers
 //       its splat by sorted index; the chunk's bounds of pos and of the raw scale are taken over the chunk's OWN members (the reference's
@@ -19,6 +19,7 @@
 #include <cstdint>
 #include "dvs_device.h"
 #include "dvs_kernels.h"
+#include "export_common.h"
 #include "../../include/dvs_raster.h"
 #include "../../include/dvs_export.h"
 
@@ -126,16 +127,9 @@ __device__ __forceinline__ uint32_t pk_unorm(float v, int bits) {
 }
 __device__ __forceinline__ uint32_t pk_111011(float x, float y, float z) { return pk_unorm(x, 11) << 21 | pk_unorm(y, 10) << 11 | pk_unorm(z, 11); }
 
-// q = rot / |rot| with correctly rounded sqrt and divisions; a squared norm of 0 or not finite gives (1, 0, 0, 0)
-__device__ __forceinline__ void pk_quat(const float4 r, float q[4]) {
-    const float ss = ((r.x * r.x + r.y * r.y) + r.z * r.z) + r.w * r.w;
-    if (!(ss > 0.0f) || !(ss < __builtin_inff())) { q[0] = 1.0f; q[1] = q[2] = q[3] = 0.0f; return; }
-    const float len = dvs_sqrt_rn(ss);
-    q[0] = r.x / len; q[1] = r.y / len; q[2] = r.z / len; q[3] = r.w / len;
-}
 __device__ __forceinline__ uint32_t pk_rot(const float4 r) {
     float q[4];
-    pk_quat(r, q);
+    dvs_unit_quat(r, q);
     int largest = 0;
     float ql = q[0];
 #pragma unroll
@@ -191,7 +185,7 @@ k_pack_splat32(int n, const float* __restrict__ pos, const float* __restrict__ s
     const int64_t i = (int64_t)blockIdx.x * PK_BLOCK + threadIdx.x;
     if (i >= n) return;
     float q[4];
-    pk_quat(reinterpret_cast<const float4*>(rot)[i], q);
+    dvs_unit_quat(reinterpret_cast<const float4*>(rot)[i], q);
     uint4 a, b;
     a.x = __float_as_uint(pos[3 * i]); a.y = __float_as_uint(pos[3 * i + 1]); a.z = __float_as_uint(pos[3 * i + 2]);
     a.w = __float_as_uint(dvs_exp_det(scale[3 * i]));
@@ -212,7 +206,6 @@ k_pack_splat32(int n, const float* __restrict__ pos, const float* __restrict__ s
 // section). The last, partial tile goes byte by byte. alphas (one byte per lane, 64 contiguous bytes per wave) and rotations (one dword
 // per lane, 256 contiguous bytes) are whole records per lane and are stored directly. DVS_SHN_ROWS input is read as dwords, lane after
 // lane through the tile's rows, into the same image. The decoder is the mirror image.
-struct SpzOff { uint64_t a[6]; };                          // byte offsets of positions, alphas, colors, scales, rotations, sh
 constexpr int SPZ_POS = 64 * 9, SPZ_VEC3 = 64 * 3;         // bytes of one tile in positions / in colors and scales
 template <int DIM> constexpr int spz_image_bytes() { return 64 * 3 * DIM + SPZ_POS + 2 * SPZ_VEC3; }
 
@@ -247,7 +240,8 @@ template <int B> __device__ __forceinline__ uint8_t spz_sh(float x) {
     q = (q + B / 2) / B * B;
     return (uint8_t)min(max(q, 0), 255);
 }
-// packQuaternionSmallestThree (load-spz.cc:216-255) of the repository's (w, x, y, z)
+// packQuaternionSmallestThree (load-spz.cc:216-255) of the repository's (w, x, y, z). Its normalisation is NOT dvs_unit_quat: the squares
+// are summed in the format's (x, y, z, w) order, w last, as the format's reference does, so the two sums can differ in the last bit.
 __device__ __forceinline__ uint32_t spz_rot(const float4 r) {
     float q[4] = {r.y, r.z, r.w, r.x};                                     // the format's (x, y, z, w)
     const float ss = ((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3];
@@ -274,7 +268,7 @@ __device__ __forceinline__ uint32_t spz_rot(const float4 r) {
 
 template <int DIM>
 __global__ void __launch_bounds__(PK_BLOCK)
-k_pack_spz(int n, SpzOff off, const float* __restrict__ pos, const float* __restrict__ sh0, const float* __restrict__ shN, int tiled,
+k_pack_spz(int n, dvs_spz_layout L /*off[]: positions, alphas, colors, scales, rotations, sh*/, const float* __restrict__ pos, const float* __restrict__ sh0, const float* __restrict__ shN, int tiled,
            const float* __restrict__ opacity, const float* __restrict__ scale, const float* __restrict__ rot, uint8_t* __restrict__ out) {
     constexpr int SHB = 3 * DIM, IMG16 = spz_image_bytes<DIM>() / 16;
     __shared__ uint4 lds[PK_WAVES * IMG16];
@@ -294,14 +288,14 @@ k_pack_spz(int n, SpzOff off, const float* __restrict__ pos, const float* __rest
             img_scl[lane * 3 + k] = (uint8_t)spz_u8((scale[3 * i + k] + 10.0f) * 16.0f);
         }
         const float o = opacity[i];
-        out[off.a[1] + i] = (uint8_t)(o == o ? spz_u8(dvs_sigmoid_det(o) * 255.0f) : 0u);         // a NaN logit: alpha 0
-        reinterpret_cast<uint32_t*>(out + off.a[4])[i] = spz_rot(reinterpret_cast<const float4*>(rot)[i]);
+        out[L.off[1] + i] = (uint8_t)(o == o ? spz_u8(dvs_sigmoid_det(o) * 255.0f) : 0u);         // a NaN logit: alpha 0
+        reinterpret_cast<uint32_t*>(out + L.off[4])[i] = spz_rot(reinterpret_cast<const float4*>(rot)[i]);
     }
     if (DIM > 0 && count > 0) {
         if (tiled) {                                                       // (whole tiles are allocated: every lane's chunk is in bounds)
 #pragma unroll
             for (int c = 0; c < (SHB + 3) / 4; ++c) {
-                const float4 v = reinterpret_cast<const float4*>(shN)[(tile * 12 + c) * 64 + lane];
+                const float4 v = reinterpret_cast<const float4*>(shN)[dvs_shn_tiled_chunk(i, c)];
                 const float e4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
@@ -317,16 +311,16 @@ k_pack_spz(int n, SpzOff off, const float* __restrict__ pos, const float* __rest
     }
     __syncthreads();
     if (count == 0) return;
-    if (DIM > 0) spz_store_slice(img_sh, out + off.a[5] + (size_t)tile * (64 * SHB), 64 * SHB, count * SHB, lane);
-    spz_store_slice(img_pos, out + off.a[0] + (size_t)tile * SPZ_POS, SPZ_POS, count * 9, lane);
-    spz_store_slice(img_col, out + off.a[2] + (size_t)tile * SPZ_VEC3, SPZ_VEC3, count * 3, lane);
-    spz_store_slice(img_scl, out + off.a[3] + (size_t)tile * SPZ_VEC3, SPZ_VEC3, count * 3, lane);
+    if (DIM > 0) spz_store_slice(img_sh, out + L.off[5] + (size_t)tile * (64 * SHB), 64 * SHB, count * SHB, lane);
+    spz_store_slice(img_pos, out + L.off[0] + (size_t)tile * SPZ_POS, SPZ_POS, count * 9, lane);
+    spz_store_slice(img_col, out + L.off[2] + (size_t)tile * SPZ_VEC3, SPZ_VEC3, count * 3, lane);
+    spz_store_slice(img_scl, out + L.off[3] + (size_t)tile * SPZ_VEC3, SPZ_VEC3, count * 3, lane);
 }
 
 // unpackGaussians (load-spz.cc:467-531): shN == nullptr skips the higher bands (degree 0 only)
 template <int DIM>
 __global__ void __launch_bounds__(PK_BLOCK)
-k_unpack_spz(int n, SpzOff off, const uint8_t* __restrict__ in, float* __restrict__ pos, float* __restrict__ sh0, float* __restrict__ shN, int tiled,
+k_unpack_spz(int n, dvs_spz_layout L /*off[]: positions, alphas, colors, scales, rotations, sh*/, const uint8_t* __restrict__ in, float* __restrict__ pos, float* __restrict__ sh0, float* __restrict__ shN, int tiled,
              float* __restrict__ opacity, float* __restrict__ scale, float* __restrict__ rot) {
     constexpr int SHB = 3 * DIM, IMG16 = spz_image_bytes<DIM>() / 16;
     __shared__ uint4 lds[PK_WAVES * IMG16];
@@ -338,10 +332,10 @@ k_unpack_spz(int n, SpzOff off, const uint8_t* __restrict__ in, float* __restric
     uint8_t* const img_col = img_pos + SPZ_POS;
     uint8_t* const img_scl = img_col + SPZ_VEC3;
     if (count > 0) {
-        if (DIM > 0) spz_load_slice(img_sh, in + off.a[5] + (size_t)tile * (64 * SHB), 64 * SHB, count * SHB, lane);
-        spz_load_slice(img_pos, in + off.a[0] + (size_t)tile * SPZ_POS, SPZ_POS, count * 9, lane);
-        spz_load_slice(img_col, in + off.a[2] + (size_t)tile * SPZ_VEC3, SPZ_VEC3, count * 3, lane);
-        spz_load_slice(img_scl, in + off.a[3] + (size_t)tile * SPZ_VEC3, SPZ_VEC3, count * 3, lane);
+        if (DIM > 0) spz_load_slice(img_sh, in + L.off[5] + (size_t)tile * (64 * SHB), 64 * SHB, count * SHB, lane);
+        spz_load_slice(img_pos, in + L.off[0] + (size_t)tile * SPZ_POS, SPZ_POS, count * 9, lane);
+        spz_load_slice(img_col, in + L.off[2] + (size_t)tile * SPZ_VEC3, SPZ_VEC3, count * 3, lane);
+        spz_load_slice(img_scl, in + L.off[3] + (size_t)tile * SPZ_VEC3, SPZ_VEC3, count * 3, lane);
     }
     __syncthreads();
     if (count == 0) return;
@@ -355,9 +349,9 @@ k_unpack_spz(int n, SpzOff off, const uint8_t* __restrict__ in, float* __restric
             sh0[3 * i + k] = (((float)img_col[lane * 3 + k] / 255.0f) - 0.5f) / 0.15f;
             scale[3 * i + k] = (float)img_scl[lane * 3 + k] / 16.0f - 10.0f;
         }
-        const float a = (float)in[off.a[1] + i] / 255.0f;
+        const float a = (float)in[L.off[1] + i] / 255.0f;
         opacity[i] = logf(a / (1.0f - a));                                 // bytes 0 / 255: -inf / +inf
-        uint32_t comp = reinterpret_cast<const uint32_t*>(in + off.a[4])[i];
+        uint32_t comp = reinterpret_cast<const uint32_t*>(in + L.off[4])[i];
         const int largest = (int)(comp >> 30);
         float q[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sum = 0.0f;                 // (x, y, z, w)
 #pragma unroll
@@ -380,7 +374,7 @@ k_unpack_spz(int n, SpzOff off, const uint8_t* __restrict__ in, float* __restric
             float e4[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) e4[k] = (4 * c + k < SHB && valid) ? ((float)img_sh[lane * SHB + 4 * c + k] - 128.0f) / 128.0f : 0.0f;
-            reinterpret_cast<float4*>(shN)[(tile * 12 + c) * 64 + lane] = make_float4(e4[0], e4[1], e4[2], e4[3]);
+            reinterpret_cast<float4*>(shN)[dvs_shn_tiled_chunk(i, c)] = make_float4(e4[0], e4[1], e4[2], e4[3]);
         }
     } else {
         for (int idx = lane; idx < count * 45; idx += 64) {
@@ -391,21 +385,18 @@ k_unpack_spz(int n, SpzOff off, const uint8_t* __restrict__ in, float* __restric
 }
 
 // the scratch of dvs_pack_compressed: byte offsets of its parts, each on a 256-byte boundary
-struct PackScratch { size_t slots, bounds, seg, totals, hist, key[2], val[2], total; };
+struct PackScratch { size_t slots, bounds, sort_ws, key[2], val[2], total; };
 PackScratch pack_layout(int n) {
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const auto up = dvs_align256;
     PackScratch L;
     size_t o = 0;
     L.slots = o; o += up((size_t)PK_BOUNDS_BLOCKS * 6 * sizeof(float));
     L.bounds = o; o += up(6 * sizeof(float));
-    L.seg = o; o += up(sizeof(DvsSeg));
-    L.totals = o; o += up((size_t)DVS_FE_MAXBINS * sizeof(uint32_t));
-    L.hist = o; o += up(dvs_fe_hist_words((uint64_t)n, 1, 512) * sizeof(uint32_t));
+    L.sort_ws = o; o += dvs_pair_sort_ws_bytes((uint64_t)n);
     for (int k = 0; k < 2; ++k) { L.key[k] = o; o += up((size_t)n * 4); L.val[k] = o; o += up((size_t)n * 4); }
     L.total = o;
     return L;
 }
-bool off16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
 }  // namespace
 
 extern "C" size_t dvs_pack_scratch_bytes(int n) { return n > 0 ? pack_layout(n).total : 0; }
@@ -416,7 +407,6 @@ hipError_t dvs_launch_morton_order(hipStream_t st, int n, const float* pos, void
     char* const base = (char*)scratch;
     float* const slots = (float*)(base + L.slots);
     float* const bounds = (float*)(base + L.bounds);
-    DvsSeg* const seg = (DvsSeg*)(base + L.seg);
     uint32_t* key[2] = {(uint32_t*)(base + L.key[0]), (uint32_t*)(base + L.key[1])};
     uint32_t* val[2] = {(uint32_t*)(base + L.val[0]), (uint32_t*)(base + L.val[1])};
     const unsigned nblocks = (unsigned)(((int64_t)n + PK_BLOCK - 1) / PK_BLOCK);
@@ -426,12 +416,8 @@ hipError_t dvs_launch_morton_order(hipStream_t st, int n, const float* pos, void
     hipLaunchKernelGGL(k_pack_morton, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, pos, (const float*)bounds, key[0], val[0]);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    // one segment [0, n); ballot ranking (rank_atomic = 0): correct by construction, no probe of the device needed
-    const uint32_t part = dvs_fe_part_for((uint64_t)n);
-    int cur = 0;
-    if ((e = dvs_launch_seg_init(st, n, 1, 0, seg)) != hipSuccess) return e;
-    if ((e = dvs_launch_seg_sort(st, 1, key[0], val[0], key[1], val[1], seg, 0, 30, (uint64_t)n, part, (uint32_t)((uint32_t)n / part) + 3u,
-                                 (uint32_t*)(base + L.hist), (uint32_t*)(base + L.totals), 0u, &cur, nullptr, 1, 0, 0)) != hipSuccess)
+    int cur = 0;                                                           // ballot ranking: no probe of the device needed
+    if ((e = dvs_launch_pair_sort(st, (uint64_t)n, key[0], val[0], key[1], val[1], 0, 30, dvs_pair_sort_ws_at(base + L.sort_ws), 0, &cur)) != hipSuccess)
         return e;
     *sorted = val[cur];
     if (bounds_out) *bounds_out = bounds;
@@ -441,9 +427,7 @@ size_t dvs_morton_scratch_bytes(int n) { return n > 0 ? pack_layout(n).total : 0
 
 extern "C" int dvs_pack_compressed(void* stream, int n, const float* pos, const float* sh0, const float* opacity, const float* scale,
                                    const float* rot, void* scratch, float* chunks, uint32_t* verts, uint32_t* order) {
-    if (n <= 0 || !pos || !sh0 || !opacity || !scale || !rot || !scratch || !chunks || !verts) return DVS_ERR_INVALID;
-    if (off16(pos) || off16(sh0) || off16(opacity) || off16(scale) || off16(rot) || off16(scratch) || off16(chunks) || off16(verts) || off16(order))
-        return DVS_ERR_INVALID;
+    if (n <= 0 || dvs_bad_args({pos, sh0, opacity, scale, rot, scratch, chunks, verts}, {order})) return DVS_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t* sorted = nullptr;
     if (dvs_launch_morton_order(st, n, pos, scratch, &sorted, nullptr) != hipSuccess) return DVS_ERR_HIP;
@@ -455,8 +439,7 @@ extern "C" int dvs_pack_compressed(void* stream, int n, const float* pos, const 
 
 extern "C" int dvs_pack_splat32(void* stream, int n, const float* pos, const float* sh0, const float* opacity, const float* scale,
                                 const float* rot, uint8_t* out) {
-    if (n <= 0 || !pos || !sh0 || !opacity || !scale || !rot || !out) return DVS_ERR_INVALID;
-    if (off16(pos) || off16(sh0) || off16(opacity) || off16(scale) || off16(rot) || off16(out)) return DVS_ERR_INVALID;
+    if (n <= 0 || dvs_bad_args({pos, sh0, opacity, scale, rot, out})) return DVS_ERR_INVALID;
     const unsigned nblocks = (unsigned)(((int64_t)n + PK_BLOCK - 1) / PK_BLOCK);
     hipLaunchKernelGGL(k_pack_splat32, dim3(nblocks), dim3(PK_BLOCK), 0, (hipStream_t)stream, n, pos, sh0, opacity, scale, rot, (uint4*)out);
     return dvs_launch_status();
@@ -473,50 +456,42 @@ extern "C" int dvs_spz_layout_for(int n, int sh_degree, dvs_spz_layout* out) {
 }
 
 namespace {
-bool spz_args_ok(int n, int sh_degree, int shn_layout, const void* const* ptrs, int n_ptrs, const void* shN) {
-    if (n <= 0 || sh_degree < 0 || sh_degree > 3 || (shn_layout != DVS_SHN_ROWS && shn_layout != DVS_SHN_TILED)) return false;
-    for (int k = 0; k < n_ptrs; ++k) if (!ptrs[k] || off16(ptrs[k])) return false;
-    return !off16(shN) && (shN || sh_degree == 0);
-}
-SpzOff spz_offsets(int n, int sh_degree) {
-    dvs_spz_layout L;
-    (void)dvs_spz_layout_for(n, sh_degree, &L);
-    SpzOff o;
-    for (int k = 0; k < 6; ++k) o.a[k] = L.off[k];
-    return o;
+// the six required pointers of dvs_pack_spz / dvs_unpack_spz; shN may be null at degree 0 only
+bool spz_bad_args(int n, int sh_degree, int shn_layout, std::initializer_list<const void*> required, const void* shN) {
+    return n <= 0 || sh_degree < 0 || sh_degree > 3 || (!shN && sh_degree > 0) || dvs_bad_args(required, {shN}, shn_layout);
 }
 }  // namespace
 
 extern "C" int dvs_pack_spz(void* stream, int n, int sh_degree, const float* pos, const float* sh0, const float* shN, int shn_layout,
                             const float* opacity, const float* scale, const float* rot, uint8_t* out) {
-    const void* const ptrs[6] = {pos, sh0, opacity, scale, rot, out};
-    if (!spz_args_ok(n, sh_degree, shn_layout, ptrs, 6, shN)) return DVS_ERR_INVALID;
-    const SpzOff off = spz_offsets(n, sh_degree);
+    if (spz_bad_args(n, sh_degree, shn_layout, {pos, sh0, opacity, scale, rot, out}, shN)) return DVS_ERR_INVALID;
+    dvs_spz_layout L;
+    (void)dvs_spz_layout_for(n, sh_degree, &L);                           // (the arguments were checked above)
     const unsigned nblocks = (unsigned)(((int64_t)n + PK_BLOCK - 1) / PK_BLOCK);
     hipStream_t st = (hipStream_t)stream;
     const int tiled = shn_layout == DVS_SHN_TILED;
     switch (sh_degree) {
-        case 0: hipLaunchKernelGGL(k_pack_spz<0>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
-        case 1: hipLaunchKernelGGL(k_pack_spz<3>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
-        case 2: hipLaunchKernelGGL(k_pack_spz<8>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
-        default: hipLaunchKernelGGL(k_pack_spz<15>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
+        case 0: hipLaunchKernelGGL(k_pack_spz<0>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, L, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
+        case 1: hipLaunchKernelGGL(k_pack_spz<3>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, L, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
+        case 2: hipLaunchKernelGGL(k_pack_spz<8>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, L, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
+        default: hipLaunchKernelGGL(k_pack_spz<15>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, L, pos, sh0, shN, tiled, opacity, scale, rot, out); break;
     }
     return dvs_launch_status();
 }
 
 extern "C" int dvs_unpack_spz(void* stream, int n, int sh_degree, const uint8_t* packed, float* pos, float* sh0, float* shN, int shn_layout,
                               float* opacity, float* scale, float* rot) {
-    const void* const ptrs[6] = {packed, pos, sh0, opacity, scale, rot};
-    if (!spz_args_ok(n, sh_degree, shn_layout, ptrs, 6, shN)) return DVS_ERR_INVALID;
-    const SpzOff off = spz_offsets(n, sh_degree);
+    if (spz_bad_args(n, sh_degree, shn_layout, {packed, pos, sh0, opacity, scale, rot}, shN)) return DVS_ERR_INVALID;
+    dvs_spz_layout L;
+    (void)dvs_spz_layout_for(n, sh_degree, &L);                           // (the arguments were checked above)
     const unsigned nblocks = (unsigned)(((int64_t)n + PK_BLOCK - 1) / PK_BLOCK);
     hipStream_t st = (hipStream_t)stream;
     const int tiled = shn_layout == DVS_SHN_TILED;
     switch (sh_degree) {
-        case 0: hipLaunchKernelGGL(k_unpack_spz<0>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
-        case 1: hipLaunchKernelGGL(k_unpack_spz<3>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
-        case 2: hipLaunchKernelGGL(k_unpack_spz<8>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
-        default: hipLaunchKernelGGL(k_unpack_spz<15>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, off, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
+        case 0: hipLaunchKernelGGL(k_unpack_spz<0>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, L, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
+        case 1: hipLaunchKernelGGL(k_unpack_spz<3>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, L, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
+        case 2: hipLaunchKernelGGL(k_unpack_spz<8>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, L, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
+        default: hipLaunchKernelGGL(k_unpack_spz<15>, dim3(nblocks), dim3(PK_BLOCK), 0, st, n, L, packed, pos, sh0, shN, tiled, opacity, scale, rot); break;
     }
     return dvs_launch_status();
 }

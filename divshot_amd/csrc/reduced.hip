@@ -4,7 +4,7 @@
 //   (a) k_sh_degree<D>: one lane per splat, its 3 ((D + 1)^2 - 1) coefficients in registers, a loop over the camera centres (read through
 //       wave-uniform addresses: scalar loads). No atomics, no LDS.
 //   (b) per codebook: k_rd_keys (value -> order-preserving uint32 key; a value outside the book's set -> 0xFFFFFFFF, which no finite
-//       float maps to and which sorts last), the stable radix sort of frontend.hip (one segment, four 8-bit passes), k_rd_info (m = the
+//       float maps to and which sorts last), the stable pair sort of frontend.hip (dvs_launch_pair_sort, four 8-bit passes), k_rd_info (m = the
 //       keys below the sentinel, the scaling exponent e), k_rd_fixed (k(v) as int64), the inclusive 64-bit scan of scan.hip, and
 //       k_rd_lloyd: ONE workgroup of 256 lanes runs every iteration, lane j owning centre j.
 //   (c) k_rd_count + the 32-bit scan of scan.hip over the [4][tiles] degree counts: a stable 4-way partition. k_pack_reduced: one workgroup
@@ -17,6 +17,7 @@
 #include "dvs_device.h"
 #include "dvs_kernels.h"
 #include "block_scan.h"
+#include "export_common.h"
 #include "../../include/dvs_raster.h"
 #include "../../include/dvs_export.h"
 
@@ -39,13 +40,6 @@ __device__ __forceinline__ uint32_t rd_key(float clean) {
     return b & 0x80000000u ? ~b : b | 0x80000000u;
 }
 __device__ __forceinline__ float rd_unkey(uint32_t k) { return __uint_as_float(k & 0x80000000u ? k & 0x7FFFFFFFu : ~k); }
-// dvs_pack_spz's normalisation of (w, x, y, z)
-__device__ __forceinline__ void rd_quat(const float4 r, float q[4]) {
-    const float ss = ((r.x * r.x + r.y * r.y) + r.z * r.z) + r.w * r.w;
-    if (!(ss > 0.0f) || !(ss < __builtin_inff())) { q[0] = 1.0f; q[1] = q[2] = q[3] = 0.0f; return; }
-    const float len = dvs_sqrt_rn(ss);
-    q[0] = r.x / len; q[1] = r.y / len; q[2] = r.z / len; q[3] = r.w / len;
-}
 
 // ---- (a) ------------------------------------------------------------------------------------------------------------------------------
 template <int D>
@@ -59,7 +53,7 @@ k_sh_degree(int n, const float* __restrict__ pos, const float* __restrict__ shN,
     if (layout == DVS_SHN_TILED) {
 #pragma unroll
         for (int c = 0; c < (3 * NC + 3) / 4; ++c) {
-            const float4 v = reinterpret_cast<const float4*>(shN)[((int64_t)(i >> 6) * 12 + c) * 64 + (i & 63)];
+            const float4 v = reinterpret_cast<const float4*>(shN)[dvs_shn_tiled_chunk(i, c)];
             const float e4[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) if (4 * c + k < 3 * NC) sh[4 * c + k] = e4[k];
@@ -126,7 +120,7 @@ k_rd_keys(int book, int n, uint32_t M, const float* __restrict__ sh0, const floa
     else {
         const int i = book == 18 ? (int)q : (int)(q / 3u);
         float qn[4];
-        rd_quat(reinterpret_cast<const float4*>(rot)[i], qn);
+        dvs_unit_quat(reinterpret_cast<const float4*>(rot)[i], qn);
         const int comp = book == 18 ? 0 : 1 + (int)(q - 3u * (uint32_t)i);
         v = comp == 0 ? qn[0] : comp == 1 ? qn[1] : comp == 2 ? qn[2] : qn[3];
     }
@@ -338,7 +332,7 @@ k_pack_reduced(int n, RdLayout L, const float* __restrict__ pos, const float* __
 #pragma unroll
         for (int k = 0; k < 3; ++k) *r++ = (uint8_t)rd_id(bnd + 17 * RD_K, scale[3 * i + k]);
         float q[4];
-        rd_quat(reinterpret_cast<const float4*>(rot)[i], q);
+        dvs_unit_quat(reinterpret_cast<const float4*>(rot)[i], q);
         *r++ = (uint8_t)rd_id(bnd + 18 * RD_K, q[0]);
 #pragma unroll
         for (int k = 1; k < 4; ++k) *r++ = (uint8_t)rd_id(bnd + 19 * RD_K, q[k]);
@@ -414,7 +408,7 @@ k_unpack_reduced(int n, RdLayout L, const uint8_t* __restrict__ in, float* __res
                 const int e = 4 * c + k;
                 e4[k] = e < ne ? rd_load_f32(tb + ((size_t)ids[e] * RD_BOOKS + 1 + e / 3) * 4) : 0.0f;
             }
-            reinterpret_cast<float4*>(shN)[((g >> 6) * 12 + c) * 64 + (g & 63)] = make_float4(e4[0], e4[1], e4[2], e4[3]);
+            reinterpret_cast<float4*>(shN)[dvs_shn_tiled_chunk(g, c)] = make_float4(e4[0], e4[1], e4[2], e4[3]);
         }
     } else {
         for (int e = 0; e < 45; ++e) shN[g * 45 + e] = e < ne ? rd_load_f32(tb + ((size_t)ids[e] * RD_BOOKS + 1 + e / 3) * 4) : 0.0f;
@@ -422,15 +416,13 @@ k_unpack_reduced(int n, RdLayout L, const uint8_t* __restrict__ in, float* __res
 }
 
 // the scratch: byte offsets of its parts, each on a 256-byte boundary
-struct RdScratch { size_t seg, totals, hist, key[2], val[2], P, bsum64, info, cnt, bsum32, total32, total; };
+struct RdScratch { size_t sort_ws, key[2], val[2], P, bsum64, info, cnt, bsum32, total32, total; };
 RdScratch rd_scratch(int n) {
     RdScratch S;
     const size_t M = 3 * (size_t)n, tiles = ((size_t)n + RD_BLOCK - 1) / RD_BLOCK;
     size_t o = 0;
     auto take = [&o](size_t bytes) { const size_t at = o; o += dvs_align256(bytes); return at; };
-    S.seg = take(sizeof(DvsSeg));
-    S.totals = take((size_t)DVS_FE_MAXBINS * sizeof(uint32_t));
-    S.hist = take(dvs_fe_hist_words((uint64_t)M, 1, 512) * sizeof(uint32_t));
+    S.sort_ws = take(dvs_pair_sort_ws_bytes((uint64_t)M));
     for (int k = 0; k < 2; ++k) { S.key[k] = take(M * 4); S.val[k] = take(M * 4); }
     S.P = take(M * 8);
     S.bsum64 = take(((M + DVS_SCAN_TILE - 1) / DVS_SCAN_TILE) * 8);
@@ -441,12 +433,6 @@ RdScratch rd_scratch(int n) {
     S.total = o;
     return S;
 }
-bool off16(const void* p) { return ((uintptr_t)p & 15u) != 0; }
-bool bad_ptrs(const void* const* p, int count) {
-    for (int k = 0; k < count; ++k) if (!p[k] || off16(p[k])) return true;
-    return false;
-}
-bool bad_layout(int l) { return l != DVS_SHN_ROWS && l != DVS_SHN_TILED; }
 
 // degree[] -> the scanned [4][tiles] table in scratch (base[d][tile] = the block-order index of the tile's first splat of degree d)
 hipError_t rd_partition(hipStream_t st, int n, const uint8_t* degree, char* scratch, const RdScratch& S, uint32_t tiles) {
@@ -481,9 +467,8 @@ extern "C" size_t dvs_reduced_scratch_bytes(int n) { return n > 0 ? rd_scratch(n
 
 extern "C" int dvs_sh_degree_select(void* stream, int n, int D, const float* pos, const float* shN, int shn_layout, const float* cams, int C,
                                     float t, uint8_t* degree) {
-    if (n <= 0 || D < 0 || D > 3 || C <= 0 || !(t >= 0.0f) || bad_layout(shn_layout)) return DVS_ERR_INVALID;
-    const void* const ptrs[3] = {pos, cams, degree};
-    if (bad_ptrs(ptrs, 3) || off16(shN) || (!shN && D > 0)) return DVS_ERR_INVALID;
+    if (n <= 0 || D < 0 || D > 3 || C <= 0 || !(t >= 0.0f) || (!shN && D > 0)) return DVS_ERR_INVALID;
+    if (dvs_bad_args({pos, cams, degree}, {shN}, shn_layout)) return DVS_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const unsigned nblocks = (unsigned)(((int64_t)n + RD_BLOCK - 1) / RD_BLOCK);
     switch (D) {
@@ -498,13 +483,11 @@ extern "C" int dvs_sh_degree_select(void* stream, int n, int D, const float* pos
 extern "C" int dvs_codebooks_build(void* stream, int n, const float* sh0, const float* shN, int shn_layout, const float* opacity,
                                    const float* scale, const float* rot, const uint8_t* degree, int max_iters, void* scratch, float* centres,
                                    int32_t* iters) {
-    if (n <= 0 || 3 * (int64_t)n > DVS_REDUCED_MAX_VALUES || max_iters < 1 || bad_layout(shn_layout)) return DVS_ERR_INVALID;
-    const void* const ptrs[9] = {sh0, shN, opacity, scale, rot, degree, scratch, centres, iters};
-    if (bad_ptrs(ptrs, 9)) return DVS_ERR_INVALID;
+    if (n <= 0 || 3 * (int64_t)n > DVS_REDUCED_MAX_VALUES || max_iters < 1) return DVS_ERR_INVALID;
+    if (dvs_bad_args({sh0, shN, opacity, scale, rot, degree, scratch, centres, iters}, {}, shn_layout)) return DVS_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const RdScratch S = rd_scratch(n);
     char* const base = (char*)scratch;
-    DvsSeg* const seg = (DvsSeg*)(base + S.seg);
     uint32_t* key[2] = {(uint32_t*)(base + S.key[0]), (uint32_t*)(base + S.key[1])};
     uint32_t* val[2] = {(uint32_t*)(base + S.val[0]), (uint32_t*)(base + S.val[1])};
     uint64_t* const P = (uint64_t*)(base + S.P);
@@ -514,12 +497,8 @@ extern "C" int dvs_codebooks_build(void* stream, int n, const float* sh0, const 
         const unsigned nblocks = (M + RD_BLOCK - 1) / RD_BLOCK;
         hipLaunchKernelGGL(k_rd_keys, dim3(nblocks), dim3(RD_BLOCK), 0, st, book, n, M, sh0, shN, shn_layout, opacity, scale, rot, degree, key[0]);
         if (hipGetLastError() != hipSuccess) return DVS_ERR_HIP;
-        // one segment [0, M), all 32 key bits; ballot ranking (rank_atomic = 0): correct by construction. The values ride along unread.
-        const uint32_t part = dvs_fe_part_for((uint64_t)M);
-        int cur = 0;
-        if (dvs_launch_seg_init(st, (int)M, 1, 0, seg) != hipSuccess) return DVS_ERR_HIP;
-        if (dvs_launch_seg_sort(st, 1, key[0], val[0], key[1], val[1], seg, 0, 32, (uint64_t)M, part, M / part + 3u, (uint32_t*)(base + S.hist),
-                                (uint32_t*)(base + S.totals), 0u, &cur, nullptr, 1, 0, 0) != hipSuccess)
+        int cur = 0;                                       // all 32 key bits, ballot ranking. The values ride along uninitialised and unread.
+        if (dvs_launch_pair_sort(st, M, key[0], val[0], key[1], val[1], 0, 32, dvs_pair_sort_ws_at(base + S.sort_ws), 0, &cur) != hipSuccess)
             return DVS_ERR_HIP;
         const uint32_t* const s = key[cur];
         hipLaunchKernelGGL(k_rd_info, dim3(1), dim3(64), 0, st, s, M, info);
@@ -533,8 +512,7 @@ extern "C" int dvs_codebooks_build(void* stream, int n, const float* sh0, const 
 }
 
 extern "C" int dvs_reduced_degree_counts(void* stream, int n, const uint8_t* degree, void* scratch, uint32_t* counts) {
-    const void* const ptrs[3] = {degree, scratch, counts};
-    if (n <= 0 || bad_ptrs(ptrs, 3)) return DVS_ERR_INVALID;
+    if (n <= 0 || dvs_bad_args({degree, scratch, counts})) return DVS_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const RdScratch S = rd_scratch(n);
     const uint32_t tiles = (uint32_t)(((int64_t)n + RD_BLOCK - 1) / RD_BLOCK);
@@ -564,9 +542,7 @@ extern "C" int dvs_reduced_layout_for(const uint32_t counts[4], int half, dvs_re
 extern "C" int dvs_pack_reduced(void* stream, int n, const float* pos, const float* sh0, const float* shN, int shn_layout, const float* opacity,
                                 const float* scale, const float* rot, const uint8_t* degree, const float* centres, void* scratch,
                                 const dvs_reduced_layout* L, uint8_t* out) {
-    if (n <= 0 || bad_layout(shn_layout) || !layout_ok(L, n)) return DVS_ERR_INVALID;
-    const void* const ptrs[10] = {pos, sh0, shN, opacity, scale, rot, degree, centres, scratch, out};
-    if (bad_ptrs(ptrs, 10)) return DVS_ERR_INVALID;
+    if (n <= 0 || !layout_ok(L, n) || dvs_bad_args({pos, sh0, shN, opacity, scale, rot, degree, centres, scratch, out}, {}, shn_layout)) return DVS_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     const RdScratch S = rd_scratch(n);
     const uint32_t tiles = (uint32_t)(((int64_t)n + RD_BLOCK - 1) / RD_BLOCK);
@@ -579,9 +555,7 @@ extern "C" int dvs_pack_reduced(void* stream, int n, const float* pos, const flo
 
 extern "C" int dvs_unpack_reduced(void* stream, int n, const uint8_t* packed, const dvs_reduced_layout* L, float* pos, float* sh0, float* shN,
                                   int shn_layout, float* opacity, float* scale, float* rot, uint8_t* degree) {
-    if (n <= 0 || bad_layout(shn_layout) || !layout_ok(L, n)) return DVS_ERR_INVALID;
-    const void* const ptrs[7] = {packed, pos, sh0, shN, opacity, scale, rot};
-    if (bad_ptrs(ptrs, 7) || off16(degree)) return DVS_ERR_INVALID;
+    if (n <= 0 || !layout_ok(L, n) || dvs_bad_args({packed, pos, sh0, shN, opacity, scale, rot}, {degree}, shn_layout)) return DVS_ERR_INVALID;
     const int64_t lanes = shn_layout == DVS_SHN_TILED ? ((int64_t)n + 63) / 64 * 64 : (int64_t)n;
     const unsigned nblocks = (unsigned)((lanes + RD_BLOCK - 1) / RD_BLOCK);
     hipLaunchKernelGGL(k_unpack_reduced, dim3(nblocks), dim3(RD_BLOCK), 0, (hipStream_t)stream, n, rd_layout(L), packed, pos, sh0, shN, shn_layout,

@@ -162,16 +162,19 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     // packed payload on the device and its host copy. Nothing is allocated until a save exports.
     GrowBuf<void> d_export_scratch; GrowBuf<uint8_t> d_export_out;
     std::vector<uint8_t> export_host;
-    // the .spz export's fidelity score (evaluation on, rank 0): the packed payload decoded on the device into a second parameter set
-    // in the tiled layout, rendered and scored on the test cameras like the full model. Allocated at the first such export.
+    // the fidelity score of the .spz and .reduced.ply exports (evaluation on, rank 0): the packed payload decoded on the device into a
+    // second parameter set in the tiled layout, rendered and scored on the test cameras like the full model. Allocated at the first
+    // such export. One record per scored format, in the eval JSON's order: the decoded model's means {mse, l1, ssim, psnr} at iteration `it`.
     GrowBuf<float> d_decoded[6];
-    double spz_mean[4] = {NAN, NAN, NAN, NAN};                               // {mse, l1, ssim, psnr} means of the decoded model ...
-    int spz_it = -1;                                                         // ... at this iteration (-1: none)
+    enum { SCORED_SPZ = 0, SCORED_REDUCED = 1 };
+    struct DecodedScore { const char* name; double mean[4] = {NAN, NAN, NAN, NAN}; int it = -1; /*-1: none*/ };
+    DecodedScore decoded_score[2] = {{"spz"}, {"reduced"}};
+    // the ending both exports share: reserves d_decoded, `unpack` decodes into it (-> status; `unpacker` names it in the exception), the
+    // full model is evaluated unless this step's already is, the decoded one scored and logged. Nothing without test cameras.
+    void score_decoded(int format, const char* unpacker, const std::function<int()>& unpack);
     // the .reduced.ply export (EXPORT_REDUCED): per-splat degrees, the camera centres, centres / iteration counts / block counts on the
-    // device (one small buffer), and the decoded model's means like the .spz ones. Nothing is allocated until the first such export.
+    // device (one small buffer). Nothing is allocated until the first such export.
     GrowBuf<uint8_t> d_red_degree, d_red_small;
-    double reduced_mean[4] = {NAN, NAN, NAN, NAN};
-    int reduced_it = -1;
     // DVS_SH_CULL_THRESHOLD (colour units, default 0.01: chosen without measurement) and DVS_REDUCED_HALF (0 | 1), or what setReducedExport
     // said (reduced_set: it was called)
     bool reduced_set = false; float reduced_thr_set = 0.01f; bool reduced_half_set = false;
@@ -201,7 +204,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     // allocated until the first mesh. The grid and the extraction scratch live for one extraction.
     GrowBuf<float> d_mesh_depth, d_mesh_alpha;
     int mesh_resolution() const;
-    std::string mesh_file(int it) const { return cfg.modelPath + "_" + std::to_string(it) + "_mesh.ply"; }
+    std::string mesh_file(int it) const { return save_path(it, "_mesh.ply"); }
     bool mesh_bounds(float lo[3], float hi[3]);
     bool extract_mesh(const std::string& path, int resolution);
     // what happens to the mesh before it is written: DVS_MESH_MIN_COMPONENT (percent of the largest component's triangles, at most two
@@ -230,7 +233,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     DevBuf<float> d_sky, d_sky_m, d_sky_v, d_sky_grad, d_sky_rgb;
     size_t sky_floats() const { return (size_t)sky_h * 2 * sky_h * 3; }
     dvs_sky sky() const { dvs_sky s{}; s.tex = d_sky.get(); s.width = 2 * sky_h; s.height = sky_h; return s; }
-    std::string sky_file(int it) const { return cfg.modelPath + "_" + std::to_string(it) + ".sky"; }
+    std::string sky_file(int it) const { return save_path(it, ".sky"); }
     void setup_sky(bool resumed);
     void step_sky(const Step& s);
     void save_sky();
@@ -345,7 +348,8 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         return s;
     }
     dvs_splats splats() const { return splats_of(d_param, n); }
-    std::string model_file(int it) const { return cfg.modelPath + "_" + std::to_string(it) + ".ply"; }
+    std::string save_path(int it, const char* suffix) const { return cfg.modelPath + "_" + std::to_string(it) + suffix; }   // every file a save writes
+    std::string model_file(int it) const { return save_path(it, ".ply"); }
     bool model_path_ends(const char* suffix) const {
         const size_t k = strlen(suffix);
         return cfg.modelPath.size() >= k && cfg.modelPath.compare(cfg.modelPath.size() - k, k, suffix) == 0;
@@ -361,8 +365,10 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     void export_model(int format);
     void export_spz();
     void export_reduced();
-    // the tail of both: `bytes` of d_export_out to the host, the file through `write`, the `export @` line (unknown_size: the byte
-    // count it prints when the file's size cannot be read). -> false when the file could not be written (logged)
+    // the tail of every export: `bytes` of d_export_out to the host (stream synchronised), then the file through `write`. -> the file's
+    // size (unknown_size when it cannot be read), or -1 when the file could not be written (logged)
+    long long write_payload(size_t bytes, const std::string& file, size_t unknown_size, const std::function<bool(std::string*)>& write);
+    // write_payload, then the `export @` line of the simple formats (its time includes the write). -> false: not written
     bool write_export(std::chrono::steady_clock::time_point t_start, size_t bytes, const std::string& file, const char* word, size_t unknown_size,
                       const std::function<bool(std::string*)>& write);
     void fetch_host();

@@ -159,7 +159,7 @@ void GaussianTrainerScene::Impl::score_views(const dvs_splats& sp, std::vector<d
 // <modelPath>_<it>_eval.json: the last evaluation, every double with 17 significant digits (they read back bit for bit)
 void GaussianTrainerScene::Impl::write_eval_json() const {
     const int nt = (int)test_idx.size();
-    const std::string file = cfg.modelPath + "_" + std::to_string(step) + "_eval.json";
+    const std::string file = save_path(step, "_eval.json");
     FILE* f = fopen(file.c_str(), "w");
     if (!f) { logf_("evaluation: cannot write %s", file.c_str()); return; }
     fprintf(f, "{\n  \"iteration\": %d,\n  \"n_splats\": %d,\n  \"sh_degree\": %d,\n  \"holdout\": %d,\n  \"views\": [\n", step, n, sh_max, eval_holdout);
@@ -169,15 +169,14 @@ void GaussianTrainerScene::Impl::write_eval_json() const {
                 v + 1 < nt ? "," : "");
     }
     fprintf(f, "  ],\n  \"mean\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}", eval_mean[3], eval_mean[2], eval_mean[1], eval_mean[0]);
-    if (spz_it == step || reduced_it == step) {                              // the decoded models' means, scored by this save's exports
-        fprintf(f, ",\n  \"exports\": {");
-        if (spz_it == step)
-            fprintf(f, "\"spz\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}", spz_mean[3], spz_mean[2], spz_mean[1], spz_mean[0]);
-        if (reduced_it == step)
-            fprintf(f, "%s\"reduced\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}", spz_it == step ? ", " : "", reduced_mean[3],
-                    reduced_mean[2], reduced_mean[1], reduced_mean[0]);
-        fprintf(f, "}");
+    bool any = false;                                                       // the decoded models' means, scored by this save's exports
+    for (const DecodedScore& s : decoded_score) {
+        if (s.it != step) continue;
+        fprintf(f, "%s\"%s\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}", any ? ", " : ",\n  \"exports\": {", s.name, s.mean[3],
+                s.mean[2], s.mean[1], s.mean[0]);
+        any = true;
     }
+    if (any) fprintf(f, "}");
     fprintf(f, "\n}\n");
     fclose(f);
 }
@@ -227,18 +226,36 @@ void GaussianTrainerScene::Impl::fetch_host() {
     host_valid = true;
 }
 
-// The tail of a compact export, after its packer: the payload to the host, the file, the log line.
-bool GaussianTrainerScene::Impl::write_export(std::chrono::steady_clock::time_point t_start, size_t bytes, const std::string& file, const char* word,
-                                              size_t unknown_size, const std::function<bool(std::string*)>& write) {
+// The tail of a compact export, after its packer: the payload to the host, the file ...
+long long GaussianTrainerScene::Impl::write_payload(size_t bytes, const std::string& file, size_t unknown_size, const std::function<bool(std::string*)>& write) {
     if (export_host.size() < bytes) export_host.resize(bytes);
     HIP_OR_THROW(hipMemcpyAsync(export_host.data(), d_export_out.get(), bytes, hipMemcpyDeviceToHost, stream.get()));
     HIP_OR_THROW(hipStreamSynchronize(stream.get()));
     std::string err;
-    if (!write(&err)) { logf_("export @%d: %s", step, err.c_str()); return false; }
+    if (!write(&err)) { logf_("export @%d: %s", step, err.c_str()); return -1; }
     std::error_code ec;
     const auto file_bytes = std::filesystem::file_size(file, ec);
-    logf_("export @%d: %s %d splats, %llu bytes, %.2f ms", step, word, n, (unsigned long long)(ec ? unknown_size : file_bytes), ms_since(t_start));
-    return true;
+    return (long long)(ec ? unknown_size : file_bytes);
+}
+// ... and the log line of the simple formats
+bool GaussianTrainerScene::Impl::write_export(std::chrono::steady_clock::time_point t_start, size_t bytes, const std::string& file, const char* word,
+                                              size_t unknown_size, const std::function<bool(std::string*)>& write) {
+    const long long on_disk = write_payload(bytes, file, unknown_size, write);
+    if (on_disk >= 0) logf_("export @%d: %s %d splats, %llu bytes, %.2f ms", step, word, n, (unsigned long long)on_disk, ms_since(t_start));
+    return on_disk >= 0;
+}
+// The ending of an export whose payload can be decoded (trainer.hpp): what the compact file costs in dB. The score is reported beside
+// the full model's (log line, "exports" in the eval JSON) and never replaces it.
+void GaussianTrainerScene::Impl::score_decoded(int format, const char* unpacker, const std::function<int()>& unpack) {
+    if (test_idx.empty() || rank != 0) return;
+    for (int g = 0; g < 6; ++g) d_decoded[g].reserve(dev_floats_for(g, n) * sizeof(float) + 16);
+    if (const int rc = unpack(); rc != DVS_OK) throw std::runtime_error(std::string(unpacker) + ": status " + std::to_string(rc));
+    if (eval_it != step) run_evaluation();                                  // the full model of the same parameters: the comparison
+    DecodedScore& s = decoded_score[format];
+    std::vector<double> res;
+    score_views(splats_of(d_decoded, n), res, s.mean);
+    s.it = step;
+    logf_("export @%d: %s decoded model: PSNR %.17g dB (full model %.17g dB), SSIM %.17g, L1 %.17g", step, s.name, s.mean[3], eval_mean[3], s.mean[2], s.mean[1]);
 }
 
 // One compact export of the current model: packed on the training stream from the device arrays (shN is not read, so its tiled layout
@@ -262,7 +279,7 @@ void GaussianTrainerScene::Impl::export_model(int format) {
         status = dvs_pack_splat32(stream.get(), n, pos, sh0, opa, scale, rot, out);
     }
     if (status != DVS_OK) throw std::runtime_error(std::string(compressed ? "dvs_pack_compressed" : "dvs_pack_splat32") + ": status " + std::to_string(status));
-    const std::string file = cfg.modelPath + "_" + std::to_string(step) + (compressed ? ".compressed.ply" : ".splat");
+    const std::string file = save_path(step, compressed ? ".compressed.ply" : ".splat");
     write_export(t_start, bytes, file, compressed ? "compressed.ply" : "splat", bytes, [&](std::string* err) {
         return compressed ? gsply::write_compressed_ply(file, (size_t)n, (const float*)export_host.data(),
                                                         (const uint32_t*)(export_host.data() + chunk_bytes), cfg.mipAntiliased, err)
@@ -272,8 +289,7 @@ void GaussianTrainerScene::Impl::export_model(int format) {
 
 // The .spz export: the six sections packed from the tiled arrays at the model's sh_max (the one compact format that keeps the
 // higher SH bands), layout.total bytes copied to the host, gzipped into <modelPath>_<step>.spz. With evaluation on, the device payload
-// is then decoded into a second parameter set and scored on the test cameras: what the compact file costs in dB. That score is
-// reported beside the full model's (log line, "exports" in the eval JSON) and never replaces it.
+// is then decoded into a second parameter set and scored on the test cameras (score_decoded).
 void GaussianTrainerScene::Impl::export_spz() {
     const auto t_start = std::chrono::steady_clock::now();
     dvs_spz_layout layout;
@@ -283,20 +299,14 @@ void GaussianTrainerScene::Impl::export_spz() {
     const int status = dvs_pack_spz(stream.get(), n, sh_max, d_param[P_POS].get(), d_param[P_SH0].get(), d_param[P_SHN].get(), DVS_SHN_TILED,
                                     d_param[P_OPA].get(), d_param[P_SCALE].get(), d_param[P_ROT].get(), d_export_out.get());
     if (status != DVS_OK) throw std::runtime_error("dvs_pack_spz: status " + std::to_string(status));
-    const std::string file = cfg.modelPath + "_" + std::to_string(step) + ".spz";
+    const std::string file = save_path(step, ".spz");
     if (!write_export(t_start, bytes, file, "spz", 0, [&](std::string* err) {
             return gsply::write_spz(file, (size_t)n, sh_max, cfg.mipAntiliased, export_host.data(), layout, err);
         })) return;
-    if (test_idx.empty() || rank != 0) return;
-    for (int g = 0; g < 6; ++g) d_decoded[g].reserve(dev_floats_for(g, n) * sizeof(float) + 16);
-    const int rc = dvs_unpack_spz(stream.get(), n, sh_max, d_export_out.get(), d_decoded[P_POS].get(), d_decoded[P_SH0].get(), d_decoded[P_SHN].get(),
-                                  DVS_SHN_TILED, d_decoded[P_OPA].get(), d_decoded[P_SCALE].get(), d_decoded[P_ROT].get());
-    if (rc != DVS_OK) throw std::runtime_error("dvs_unpack_spz: status " + std::to_string(rc));
-    if (eval_it != step) run_evaluation();                                  // the full model of the same parameters: the comparison
-    std::vector<double> res;
-    score_views(splats_of(d_decoded, n), res, spz_mean);
-    spz_it = step;
-    logf_("export @%d: spz decoded model: PSNR %.17g dB (full model %.17g dB), SSIM %.17g, L1 %.17g", step, spz_mean[3], eval_mean[3], spz_mean[2], spz_mean[1]);
+    score_decoded(SCORED_SPZ, "dvs_unpack_spz", [&] {
+        return dvs_unpack_spz(stream.get(), n, sh_max, d_export_out.get(), d_decoded[P_POS].get(), d_decoded[P_SH0].get(), d_decoded[P_SHN].get(),
+                              DVS_SHN_TILED, d_decoded[P_OPA].get(), d_decoded[P_SCALE].get(), d_decoded[P_ROT].get());
+    });
 }
 
 float GaussianTrainerScene::Impl::sh_cull_threshold() const {
@@ -362,27 +372,19 @@ void GaussianTrainerScene::Impl::export_reduced() {
     d_export_out.reserve(bytes);
     check(dvs_pack_reduced(stream.get(), n, pos, sh0, shN, DVS_SHN_TILED, opa, scale, rot, d_red_degree.get(), centres, d_export_scratch.get(), &layout,
                            d_export_out.get()), "dvs_pack_reduced");
-    if (export_host.size() < bytes) export_host.resize(bytes);
-    HIP_OR_THROW(hipMemcpyAsync(export_host.data(), d_export_out.get(), bytes, hipMemcpyDeviceToHost, stream.get()));
-    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
-    const double ms_pack = ms_since(t2);
-    const std::string file = cfg.modelPath + "_" + std::to_string(step) + ".reduced.ply";
-    std::string err;
-    if (!gsply::write_reduced_ply(file, &layout, export_host.data(), bytes, &err)) { logf_("export @%d: %s", step, err.c_str()); return; }
-    std::error_code ec;
-    const auto file_bytes = std::filesystem::file_size(file, ec);
+    const std::string file = save_path(step, ".reduced.ply");
+    double ms_pack = 0.0;
+    const long long on_disk = write_payload(bytes, file, bytes, [&](std::string* err) {
+        ms_pack = ms_since(t2);                                             // the payload is on the host: the pack time ends before the file is written
+        return gsply::write_reduced_ply(file, &layout, export_host.data(), bytes, err);
+    });
+    if (on_disk < 0) return;
     int most = 0;
     for (int it : h_iters) most = std::max(most, it);
     logf_("export @%d: reduced %d splats (%u/%u/%u/%u by degree), %llu bytes, degree select %.2f ms, codebooks %.2f ms (%d iterations at most), pack %.2f ms",
-          step, n, h_counts[0], h_counts[1], h_counts[2], h_counts[3], (unsigned long long)(ec ? bytes : file_bytes), ms_select, ms_books, most, ms_pack);
-    if (test_idx.empty() || rank != 0) return;
-    for (int g = 0; g < 6; ++g) d_decoded[g].reserve(dev_floats_for(g, n) * sizeof(float) + 16);
-    check(dvs_unpack_reduced(stream.get(), n, d_export_out.get(), &layout, d_decoded[P_POS].get(), d_decoded[P_SH0].get(), d_decoded[P_SHN].get(),
-                             DVS_SHN_TILED, d_decoded[P_OPA].get(), d_decoded[P_SCALE].get(), d_decoded[P_ROT].get(), nullptr), "dvs_unpack_reduced");
-    if (eval_it != step) run_evaluation();                                  // the full model of the same parameters: the comparison
-    std::vector<double> res;
-    score_views(splats_of(d_decoded, n), res, reduced_mean);
-    reduced_it = step;
-    logf_("export @%d: reduced decoded model: PSNR %.17g dB (full model %.17g dB), SSIM %.17g, L1 %.17g", step, reduced_mean[3], eval_mean[3],
-          reduced_mean[2], reduced_mean[1]);
+          step, n, h_counts[0], h_counts[1], h_counts[2], h_counts[3], (unsigned long long)on_disk, ms_select, ms_books, most, ms_pack);
+    score_decoded(SCORED_REDUCED, "dvs_unpack_reduced", [&] {
+        return dvs_unpack_reduced(stream.get(), n, d_export_out.get(), &layout, d_decoded[P_POS].get(), d_decoded[P_SH0].get(), d_decoded[P_SHN].get(),
+                                  DVS_SHN_TILED, d_decoded[P_OPA].get(), d_decoded[P_SCALE].get(), d_decoded[P_ROT].get(), nullptr);
+    });
 }

@@ -106,7 +106,7 @@ void GaussianTrainerScene::Impl::render_at_save() {
         if (render_views & (test ? RENDER_TEST : RENDER_TRAIN)) which.push_back(c);
     }
     if (which.empty()) { logf_("render @%d: 0 views (renderViews %d selects no camera: nothing is held out)", step, render_views); return; }
-    const std::string dir = cfg.modelPath + "_" + std::to_string(step) + "_renders";
+    const std::string dir = save_path(step, "_renders");
     std::error_code ec;
     std::filesystem::create_directories(dir, ec);
     if (ec) { logf_("render @%d: cannot create %s: %s", step, dir.c_str(), ec.message().c_str()); return; }

@@ -133,8 +133,9 @@ int dvs_sh_degree_select(void* stream, int n, int D, const float* pos, const flo
 /* The twenty codebooks of a model whose per-splat degrees are degree[] (each 0..3; a larger byte counts as 3).
  * Value sets (the STORED parameters, not activated): f_dc the 3 n sh0 values; f_rest_j the 3 channels of coefficient j of every splat
  * whose degree stores coefficient j (j < (degree + 1)^2 - 1); opacity the n logits; scale the 3 n log scales; rot_re / rot_im the w /
- * the x, y, z of rot normalised as dvs_pack_spz normalises it (squared norm 0 or not finite: (1, 0, 0, 0)). A value that is not finite
- * is clustered as 0, and -0 as +0.
+ * the x, y, z of rot normalised as dvs_pack_compressed normalises it: divided by sqrt(((w^2 + x^2) + y^2) + z^2), squared norm 0 or not
+ * finite: (1, 0, 0, 0). (dvs_pack_spz sums w^2 last; the two can differ in the last bit.) A value that is not finite is clustered as 0,
+ * and -0 as +0.
  * Per codebook, with V the multiset of its m values — the result does not depend on the order of V:
  *   1. m = 0, or A = max |v| = 0: all 256 centres are 0 (0 iterations).
  *   2. e = the exponent with A < 2^e <= 2 A (frexp); k(v) = (int64)rint(ldexp((double)v, 36 - e)), ties to even.

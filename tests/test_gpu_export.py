@@ -120,6 +120,31 @@ def test_null_order_and_repeatability(gpu_device, reference):
     _compare(model, c, want)
 
 
+def test_morton_order_users_do_not_share_state(gpu_device):
+    """dvs_pack_compressed and dvs_knn_mean_dist2 both sort through dvs_launch_morton_order, each in its own scratch: run one after the
+    other (and the packer once more after the search) on the same 2049 positions, a third of them repeated — past one 2048-key sort
+    partition, with ties —, each equals its restatement whatever the other left behind."""
+    import torch
+    import knn_ref as K
+    from divshot_amd._lib import lib
+    n = 2049
+    model = R.random_model(n, seed=77)
+    rng = np.random.default_rng(78)
+    pos = np.array(model["pos"], np.float32).reshape(n, 3)
+    pos[rng.integers(0, n, n // 3)] = pos[0]
+    model["pos"] = pos
+    want = R.encode(model)
+    _compare(model, _pack(gpu_device, model), want)
+    d_pos = torch.from_numpy(pos.reshape(-1).copy()).to(gpu_device)
+    scratch = torch.empty(lib.dvs_knn_scratch_bytes(n), dtype=torch.uint8, device=gpu_device)
+    dist2 = _guarded(gpu_device, n)
+    st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    assert lib.dvs_knn_mean_dist2(st, n, d_pos.data_ptr(), scratch.data_ptr(), dist2.data_ptr() + 4 * GUARD) == 0
+    torch.cuda.synchronize()
+    assert np.array_equal(_payload(dist2, n), K.mean_dist2(pos).view(np.uint32)), "dist2 differs from the all-pairs restatement"
+    _compare(model, _pack(gpu_device, model), want)
+
+
 def test_invalid_arguments(gpu_device):
     import torch
     from divshot_amd._lib import lib

@@ -639,6 +639,22 @@ def test_sort_pairs(rast):
         order = np.argsort(keys & mask, kind="stable")
         np.testing.assert_array_equal(k_d.cpu().numpy().view(np.uint32), keys[order])
         np.testing.assert_array_equal(v_d.cpu().numpy().view(np.uint32), vals[order])
+    # odd pass counts and none: one pass (9 bits) and three (27 bits) leave the result in the second buffers, so the copy back into the
+    # caller's arrays runs; zero bits launch nothing and leave keys and values untouched. Below, at and above one 2048-key partition, and
+    # three partitions and one.
+    for n in (1, 2047, 2048, 2049, 6145):
+        for lo, hi in ((0, 9), (3, 30), (5, 5)):
+            keys = rng.integers(0, 2**32, size=n, dtype=np.uint64).astype(np.uint32)
+            if n > 10:
+                keys[rng.integers(0, n, n // 3)] = keys[0]
+            vals = np.arange(n, dtype=np.uint32)
+            k_d = torch.from_numpy(keys.view(np.int32).copy()).to(rast.tdev)
+            v_d = torch.from_numpy(vals.view(np.int32).copy()).to(rast.tdev)
+            rast.sort_pairs(k_d, v_d, lo, hi)
+            torch.cuda.synchronize()
+            order = np.argsort(keys & np.uint32(((1 << (hi - lo)) - 1) << lo), kind="stable")       # (zero bits: the identity)
+            np.testing.assert_array_equal(k_d.cpu().numpy().view(np.uint32), keys[order], err_msg=f"keys n={n} bits [{lo}, {hi})")
+            np.testing.assert_array_equal(v_d.cpu().numpy().view(np.uint32), vals[order], err_msg=f"values n={n} bits [{lo}, {hi})")
     # all keys equal, and already-sorted / reverse-sorted inputs
     for keys in (np.full(5000, 7, np.uint32), np.arange(5000, dtype=np.uint32), np.arange(5000, dtype=np.uint32)[::-1].copy()):
         vals = np.arange(keys.size, dtype=np.uint32)
