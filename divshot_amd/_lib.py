@@ -193,7 +193,17 @@ class ReducedLayout(C.Structure):      # dvs_reduced_layout: the four per-degree
                 ("half", C.c_int32), ("_pad", C.c_int32)]
 
 
+class Similarity(C.Structure):         # dvs_similarity: p' = s R p + t, R row-major
+    _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("s", C.c_float)]
+
+
 _EXPORT_PROTOS = {
+    "dvs_similarity_from_trs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(Similarity)]),
+    "dvs_similarity_inverse": (C.c_int, [C.POINTER(Similarity), C.POINTER(Similarity)]),
+    "dvs_sh_rotation": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "dvs_transform_splats": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Similarity), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_transform_points": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Similarity), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dvs_reduced_scratch_bytes": (C.c_size_t, [C.c_int]),
     "dvs_sh_degree_select": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_void_p]),
     "dvs_codebooks_build": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
@@ -333,6 +343,11 @@ _MESH_HOST_PROTOS = {
     "gstrain_write_mesh_ply": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64]),
     "gstrain_write_mesh_ply_normals": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64]),
 }
+# ... and the export frame's orientation from the training cameras (export_frame.hpp)
+_FRAME_HOST_PROTOS = {
+    "gstrain_host_read_ply": (C.c_int64, [C.c_char_p] + [C.c_void_p] * 6 + [C.c_uint64]),
+    "gstrain_export_orientation": (C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64]),
+}
 _host_lib = None
 
 
@@ -344,7 +359,7 @@ def host_lib():
         if not os.path.exists(path):
             raise ImportError(f"{path} is missing: build it with `make -C divshot_amd/gstrain`")
         h = C.CDLL(path)
-        for name, (res, args) in list(_JPEG_HOST_PROTOS.items()) + list(_MESH_HOST_PROTOS.items()):
+        for name, (res, args) in list(_JPEG_HOST_PROTOS.items()) + list(_MESH_HOST_PROTOS.items()) + list(_FRAME_HOST_PROTOS.items()):
             f = getattr(h, name)
             f.restype = res
             f.argtypes = args
@@ -374,6 +389,19 @@ def write_mesh_ply(path, xyz, rgb, tri, normals=None):
                                               tri.ctypes.data, err, 1024)
     if rc != 0:
         raise DvsError(err.value.decode(errors="replace"))
+
+
+def read_ply(path):
+    """gsply::read_ply through libgsplyio.so -> dict of float32 arrays pos [n,3], sh0 [n,3], shN [n,45], opacity [n], scale [n,3], rot [n,4]"""
+    import numpy as np
+    h = host_lib()
+    n = h.gstrain_host_read_ply(os.fsencode(path), None, None, None, None, None, None, 0)
+    if n < 0:
+        raise DvsError(f"read_ply: {path} is not a splat PLY this build reads")
+    out = {k: np.zeros((n, w), np.float32) for k, w in (("pos", 3), ("sh0", 3), ("shN", 45), ("opacity", 1), ("scale", 3), ("rot", 4))}
+    h.gstrain_host_read_ply(os.fsencode(path), *[out[k].ctypes.data for k in ("pos", "sh0", "shN", "opacity", "scale", "rot")], n)
+    out["opacity"] = out["opacity"].reshape(-1)
+    return out
 
 
 def jpeg_encode_desc(width, height, sampling, quality):

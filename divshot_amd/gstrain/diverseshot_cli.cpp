@@ -71,7 +71,13 @@ static std::map<std::string, std::string> g_opts = {
     // trains only the splats inside an oriented box. --focusRegion x0,y0,z0,x1,y1,z1 is the box (default: the bounds of the initial splat
     // centres), --focusRotation rx,ry,rz turns it about the origin (Euler angles in radians, as the editor's). The config struct has no room
     // left: the two are handed to the plugin as DVS_FOCUS_REGION / DVS_FOCUS_ROTATION.
-    {"enableFocusRegion", "0"}, {"focusRegion", ""}, {"focusRotation", ""}};
+    {"enableFocusRegion", "0"}, {"focusRegion", ""}, {"focusRotation", ""},
+    // extension of this build (the editor's "export apply transform"): every file a save writes but the resume PLY, and the mesh, in a chosen
+    // frame. --exportTransform tx,ty,tz,rx,ry,rz,s: p' = s R p + t, Euler angles in radians (R = Rz Ry Rx), s > 0. --exportOrient +y (or -y,
+    // +x, -x, +z, -z): turn the cameras' mean up vector onto that axis and centre their centroid. One of the two at most. --exportFormat
+    // takes `transformed` with either: <outputPath>_<it>.transformed.ply, the full PLY in that frame (implied when no other format is
+    // selected). The config struct has no room left: they are handed to the plugin as DVS_EXPORT_TRANSFORM / DVS_EXPORT_ORIENT.
+    {"exportTransform", ""}, {"exportOrient", ""}};
 static std::map<std::string, bool> g_given;
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
@@ -157,6 +163,29 @@ int main(int argc, const char* argv[]) {
         if (sscanf(v.c_str(), "%f,%f,%f%c", &r[0], &r[1], &r[2], &tail) != 3) { std::cout << "Command Line Error: --focusRotation takes rx,ry,rz (radians), not '" << v << "'\n"; return 1; }
         setenv("DVS_FOCUS_ROTATION", v.c_str(), 1);
     }
+    if (g_given.count("exportTransform") && g_given.count("exportOrient")) { std::cout << "Command Line Error: --exportTransform and --exportOrient exclude each other\n"; return 1; }
+    if (g_given.count("exportTransform")) {
+        const std::string& v = g_opts["exportTransform"];
+        float f[7]; char tail = 0;
+        bool ok = sscanf(v.c_str(), "%f,%f,%f,%f,%f,%f,%f%c", &f[0], &f[1], &f[2], &f[3], &f[4], &f[5], &f[6], &tail) == 7 && f[6] > 0.0f;
+        for (int k = 0; ok && k < 7; ++k) ok = f[k] - f[k] == 0.0f;          // (finite)
+        if (!ok) { std::cout << "Command Line Error: --exportTransform takes tx,ty,tz,rx,ry,rz,s (seven numbers, angles in radians, s > 0), not '" << v << "'\n"; return 1; }
+        setenv("DVS_EXPORT_TRANSFORM", v.c_str(), 1);                       // before the plugin is loaded
+    }
+    if (g_given.count("exportOrient")) {
+        const std::string& v = g_opts["exportOrient"];
+        if (v.size() != 2 || (v[0] != '+' && v[0] != '-') || v[1] < 'x' || v[1] > 'z') { std::cout << "Command Line Error: --exportOrient takes +x, -x, +y, -y, +z or -z, not '" << v << "'\n"; return 1; }
+        setenv("DVS_EXPORT_ORIENT", v.c_str(), 1);
+    }
+    const bool export_frame = g_given.count("exportTransform") || g_given.count("exportOrient");
+    for (size_t at = 0; at < g_opts["exportFormat"].size();) {               // (the token is checked again where the formats are collected)
+        const std::string& v = g_opts["exportFormat"];
+        const size_t comma = std::min(v.find(',', at), v.size());
+        if (v.substr(at, comma - at) == "transformed" && !export_frame) {
+            std::cout << "Command Line Error: --exportFormat transformed needs --exportTransform or --exportOrient\n"; return 1;
+        }
+        at = comma + 1;
+    }
     // plugin: "libgstrain.so" next to the executable (plugin.cpp:74 builds parent_path / "lib<name>.so")
     std::error_code ec;
     auto exe = std::filesystem::read_symlink("/proc/self/exe", ec);
@@ -210,7 +239,8 @@ int main(int argc, const char* argv[]) {
         if (tok == "compressed") train_config.exportFormats |= 1;
         else if (tok == "splat") train_config.exportFormats |= 2;
         else if (tok == "reduced") train_config.exportFormats |= 8;
-        else { std::cout << "Command Line Error: --exportFormat takes compressed, splat, reduced or a comma-separated list of them, not '" << tok << "'\n"; return 1; }
+        else if (tok == "transformed") train_config.exportFormats |= 16;     // (refused above without an export frame)
+        else { std::cout << "Command Line Error: --exportFormat takes compressed, splat, reduced, transformed or a comma-separated list of them, not '" << tok << "'\n"; return 1; }
         at = comma + 1;
     }
     if (as_bool(g_opts["exportSpz"])) train_config.exportFormats |= 4;

@@ -141,9 +141,12 @@ void GaussianTrainerScene::saveGaussianModel() {
         const auto ply_bytes = std::filesystem::file_size(file, fec);
         logf_("export @%d: ply %d splats, %llu bytes, %.2f ms", m.step, m.n, (unsigned long long)(fec ? 0 : ply_bytes), ms_since(t_save));
     }
-    if (m.rank == 0)
-        for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT, (int)Impl::EXPORT_SPZ, (int)Impl::EXPORT_REDUCED})
+    if (m.rank == 0 && m.export_formats()) {
+        struct Done { bool& filled; ~Done() { filled = false; } } done{m.xf_filled};      // the transformed set belongs to this save alone
+        if (m.xf_set) m.fill_transformed();                                  // (an export transform is set: the exports below pack from it)
+        for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT, (int)Impl::EXPORT_SPZ, (int)Impl::EXPORT_REDUCED, (int)Impl::EXPORT_TRANSFORMED})
             if (m.export_formats() & format) m.export_model(format);
+    }
     m.evaluate(true);                                                       // <modelPath>_<it>_eval.json beside the PLY (rank 0, evaluation on)
     m.render_at_save();                                                     // <modelPath>_<it>_renders/*.jpg (rank 0, renderViews on)
     if (m.rank == 0 && m.mesh_resolution() > 0 && m.status == TrainingStatus::Training_Done)
@@ -176,6 +179,31 @@ void GaussianTrainerScene::setReducedExport(float shCullThreshold, bool halfFloa
     if (!(shCullThreshold >= 0.0f)) { logf_("setReducedExport: the threshold %g is not a number >= 0: 0.01 is used", (double)shCullThreshold); shCullThreshold = 0.01f; }
     m.reduced_set = true; m.reduced_thr_set = shCullThreshold; m.reduced_half_set = halfFloat;
 }
+// The editor's "export apply transform": what DVS_EXPORT_TRANSFORM / DVS_EXPORT_ORIENT set for the CLI. The last call wins.
+bool GaussianTrainerScene::setExportTransform(const dvs_types::Vec3& position, const dvs_types::Vec3& rotationEulerRad, float scale) {
+    Impl& m = *impl_;
+    const float t[3] = {position.x, position.y, position.z}, e[3] = {rotationEulerRad.x, rotationEulerRad.y, rotationEulerRad.z};
+    dvs_similarity sim;
+    if (dvs_similarity_from_trs(t, e, scale, &sim) != DVS_OK) {
+        logf_("setExportTransform: position (%g, %g, %g), rotation (%g, %g, %g), scale %g refused (finite numbers, scale > 0): the export frame stays as it was",
+              (double)t[0], (double)t[1], (double)t[2], (double)e[0], (double)e[1], (double)e[2], (double)scale);
+        return false;
+    }
+    char how[200];
+    snprintf(how, sizeof how, "setExportTransform(T(%g, %g, %g) R(%g, %g, %g rad, Rz Ry Rx) S(%g))", (double)t[0], (double)t[1], (double)t[2], (double)e[0],
+             (double)e[1], (double)e[2], (double)scale);
+    if (!m.set_export_transform(sim, how)) return false;
+    m.report_export_transform();
+    return true;
+}
+bool GaussianTrainerScene::setExportOrientation(const std::string& axis) {
+    Impl& m = *impl_;
+    if (m.cams.empty()) { logf_("setExportOrientation before loadTrainData: there are no cameras yet"); return false; }
+    if (!m.set_export_orientation(axis.c_str(), "setExportOrientation")) return false;
+    m.report_export_transform();
+    return true;
+}
+void GaussianTrainerScene::clearExportTransform() { impl_->xf_set = false; }
 void GaussianTrainerScene::exportSparsePointCloud(const std::string& path) {
     Impl& m = *impl_;
     m.fetch_host();

@@ -5,6 +5,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <vector>
 #include "ply_io.hpp"
 
 extern "C" {
@@ -48,5 +49,19 @@ __attribute__((visibility("default"))) int gstrain_write_mesh_ply_normals(const 
     if (gsply::write_mesh_ply(path, (size_t)n_vertices, xyz, rgb, (size_t)n_triangles, tri, &err, normals)) return 0;
     if (err_out && err_cap > 0) { const size_t k = std::min<size_t>(err.size(), (size_t)err_cap - 1); memcpy(err_out, err.data(), k); err_out[k] = 0; }
     return 1;
+}
+// gsply::read_ply of a full PLY (the resume file, .transformed.ply): -> the splat count, or -1 when the file is refused; the six arrays are
+// filled (shN coefficient-major [n][45]) when pos is given and n <= capacity
+__attribute__((visibility("default"))) int64_t gstrain_host_read_ply(const char* path, float* pos, float* sh0, float* shN, float* opacity, float* scale,
+                                                                      float* rot, uint64_t capacity) {
+    std::vector<float> a, b, c, d, e, f;
+    std::string err;
+    if (!gsply::read_ply(path, a, b, c, d, e, f, &err)) return -1;
+    const uint64_t n = d.size();
+    if (pos && n <= capacity) {
+        memcpy(pos, a.data(), a.size() * 4); memcpy(sh0, b.data(), b.size() * 4); memcpy(shN, c.data(), c.size() * 4);
+        memcpy(opacity, d.data(), d.size() * 4); memcpy(scale, e.data(), e.size() * 4); memcpy(rot, f.data(), f.size() * 4);
+    }
+    return (int64_t)n;
 }
 }

@@ -24,6 +24,7 @@
 #include "device_mem.hpp"
 #include "ply_io.hpp"
 #include "dataset_io.hpp"
+#include "export_frame.hpp"
 
 namespace {
 const int kWidth[6] = {3, 3, 45, 1, 3, 4};          // pos sh0 shN opacity scale rot
@@ -180,6 +181,23 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     bool reduced_set = false; float reduced_thr_set = 0.01f; bool reduced_half_set = false;
     float sh_cull_threshold() const;
     bool reduced_half() const;
+
+    // export frame (INTEGRATION.md "Export frame"): a similarity p' = s R p + t every export but the resume PLY is written in — what
+    // DVS_EXPORT_TRANSFORM / DVS_EXPORT_ORIENT said at load, or setExportTransform / setExportOrientation since. At a save rank 0 fills a
+    // second set of pos, shN, scale, rot (sh0 and opacity are invariant: the training arrays) with ONE dvs_transform_splats call on the
+    // training stream and the packers read that set (ex()); a decoded payload is taken back by the inverse before it is scored, so the
+    // evaluation cameras stay as they are. Nothing is allocated, launched, written or logged while no transform is set.
+    bool xf_set = false; dvs_similarity xf{}, xf_inv{}; float xf_D[83] = {}, xf_inv_D[83] = {}; std::string xf_how;
+    bool xf_filled = false;                                                  // this save's set is in d_xf
+    GrowBuf<float> d_xf[4], d_xf_rows;                                       // pos, shN (tiled), scale, rot; shN as rows for the .transformed.ply
+    static int xf_slot(int g) { return g == P_POS ? 0 : g == P_SHN ? 1 : g == P_SCALE ? 2 : g == P_ROT ? 3 : -1; }
+    const float* ex(int g) const { return xf_filled && xf_slot(g) >= 0 ? d_xf[xf_slot(g)].get() : d_param[g].get(); }   // what an export packs from
+    bool set_export_transform(const dvs_similarity& m, const std::string& how);
+    bool set_export_orientation(const char* axis, const char* from);
+    void setup_export_transform();
+    void report_export_transform() const;
+    void fill_transformed();
+    void export_transformed();
 
     // rendered views as JPEG files (cfg.renderViews / renderQuality / renderSampling and their DVS_RENDER_* overrides, read at load): at
     // every save rank 0 renders the selected cameras through eval_ctx (for_each_eval_pass: what `eval @it` scored), turns each pass
@@ -355,13 +373,18 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         return cfg.modelPath.size() >= k && cfg.modelPath.compare(cfg.modelPath.size() - k, k, suffix) == 0;
     }
     // EXPORT_* bits of the compact formats a save writes; decided at every use, since the editor sets modelPath after construction
-    enum { EXPORT_COMPRESSED = 1, EXPORT_SPLAT = 2, EXPORT_SPZ = 4, EXPORT_REDUCED = 8 };
+    // EXPORT_TRANSFORMED: <modelPath>_<it>.transformed.ply, the full PLY in the export frame; counts only while a transform is set, and is
+    // implied when one is set and no other format is selected (a set transform is never a silent no-op)
+    enum { EXPORT_COMPRESSED = 1, EXPORT_SPLAT = 2, EXPORT_SPZ = 4, EXPORT_REDUCED = 8, EXPORT_TRANSFORMED = 16 };
     int suffix_formats() const {
         return model_path_ends(".compressed.ply") ? EXPORT_COMPRESSED : model_path_ends(".splat") ? EXPORT_SPLAT : model_path_ends(".spz") ? EXPORT_SPZ :
                model_path_ends(".reduced.ply") ? EXPORT_REDUCED : 0;
     }
     int asked_formats() const { return env_int("DVS_EXPORT_FORMATS", cfg.exportFormats); }   // 0: the suffix of modelPath decides
-    int export_formats() const { return (asked_formats() ? asked_formats() : suffix_formats()) & (EXPORT_COMPRESSED | EXPORT_SPLAT | EXPORT_SPZ | EXPORT_REDUCED); }
+    int export_formats() const {
+        const int f = (asked_formats() ? asked_formats() : suffix_formats()) & (EXPORT_COMPRESSED | EXPORT_SPLAT | EXPORT_SPZ | EXPORT_REDUCED | (xf_set ? EXPORT_TRANSFORMED : 0));
+        return f == 0 && xf_set ? (int)EXPORT_TRANSFORMED : f;
+    }
     void export_model(int format);
     void export_spz();
     void export_reduced();

@@ -243,6 +243,7 @@ void GaussianTrainerScene::Impl::finish_load(const std::function<void(std::vecto
     for (int g = 0; g < 6; ++g) { upload(g, init[g]); init_host[g] = init[g]; }
     setup_sky(resumed);
     setup_region();
+    setup_export_transform();                                               // (DVS_EXPORT_TRANSFORM / DVS_EXPORT_ORIENT; needs the cameras)
     report_config();
     describe(resumed);
     if (cfg.enableFocusRegion) prune_region(step);

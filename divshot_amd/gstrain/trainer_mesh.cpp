@@ -241,6 +241,10 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
         }
         xyz.resize((size_t)nv * 3); rgb.resize((size_t)nv * 3); tri.resize((size_t)nt * 3);
         if (want_normals) nrm.resize((size_t)nv * 3);
+        if (nv > 0 && xf_set) {                                              // the export frame, in place on the final arrays (they are this call's own): the model files' frame
+            const int rt = dvs_transform_points(stream.get(), (int)nv, &xf, f_xyz, f_nrm, const_cast<float*>(f_xyz), const_cast<float*>(f_nrm));
+            if (rt != DVS_OK) throw std::runtime_error("dvs_transform_points: status " + std::to_string(rt));
+        }
         if (nv > 0) {
             HIP_OR_THROW(hipMemcpyAsync(xyz.data(), f_xyz, xyz.size() * sizeof(float), hipMemcpyDeviceToHost, stream.get()));
             HIP_OR_THROW(hipMemcpyAsync(rgb.data(), f_rgb, rgb.size(), hipMemcpyDeviceToHost, stream.get()));
@@ -261,8 +265,9 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
 
     if (!write_ply(nv, xyz.data(), rgb.data(), nt, tri.data(), want_normals ? nrm.data() : nullptr)) return false;
     logf_("mesh @%d: %u vertices, %u triangles, grid %dx%dx%d, voxel %.9g, bounds %.9g,%.9g,%.9g,%.9g,%.9g,%.9g, trunc %.9g, %d views; render+depth %.2f ms, "
-          "fusion %.2f ms, extraction %.2f ms%s -> %s", step, nv, nt, dims[0], dims[1], dims[2], (double)voxel, (double)lo[0], (double)lo[1], (double)lo[2],
+          "fusion %.2f ms, extraction %.2f ms%s%s -> %s", step, nv, nt, dims[0], dims[1], dims[2], (double)voxel, (double)lo[0], (double)lo[1], (double)lo[2],
           (double)(lo[0] + (dims[0] - 1) * voxel), (double)(lo[1] + (dims[1] - 1) * voxel), (double)(lo[2] + (dims[2] - 1) * voxel), (double)trunc,
-          (int)which.size(), render_ms, fuse_ms, extract_ms, extras, path.c_str());
+          (int)which.size(), render_ms, fuse_ms, extract_ms, extras,
+          xf_set ? "; grid, voxel and bounds are those of the extraction, in the training frame: the vertices and normals are written in the export frame" : "", path.c_str());
     return true;
 }

@@ -24,10 +24,13 @@ void GaussianTrainerScene::Impl::report_config() const {
               "%dx%d (targets box-filtered per step, cameras of dvs_camera_downscale); full resolution from iteration %d; evaluation always at full size",
               res_every, res_levels, res_levels, res_every, W, H, res_levels * res_every + 1);
     if (const int fmts = export_formats())
-        logf_("config: exportFormats %d: every save also writes%s%s%s%s beside the full PLY, packed on the device%s%s", fmts,
+        logf_("config: exportFormats %d: every save also writes%s%s%s%s%s beside the full PLY, packed on the device%s%s", fmts,
               (fmts & EXPORT_COMPRESSED) ? " <modelPath>_<it>.compressed.ply" : "", (fmts & EXPORT_SPLAT) ? " <modelPath>_<it>.splat" : "",
-              (fmts & EXPORT_SPZ) ? " <modelPath>_<it>.spz" : "", (fmts & EXPORT_REDUCED) ? " <modelPath>_<it>.reduced.ply" : "", asked_formats() == 0 ? " (turned on by the suffix of modelPath)" : "",
+              (fmts & EXPORT_SPZ) ? " <modelPath>_<it>.spz" : "", (fmts & EXPORT_REDUCED) ? " <modelPath>_<it>.reduced.ply" : "",
+              (fmts & EXPORT_TRANSFORMED) ? " <modelPath>_<it>.transformed.ply (the full PLY in the export frame)" : "",
+              asked_formats() == 0 ? ((fmts & ~EXPORT_TRANSFORMED) ? " (turned on by the suffix of modelPath)" : " (implied by the export transform)") : "",
               (fmts & EXPORT_SPZ) && !test_idx.empty() ? "; the .spz payload is decoded on the device and scored on the held-out views" : "");
+    report_export_transform();
     if (export_formats() & EXPORT_REDUCED)
         logf_("config: reduced export: twenty 256-entry k-means codebooks (at most 100 iterations each), %s positions; cullSH %d: %s%s",
               reduced_half() ? "half-float" : "float", (int)cfg.cullSH,
@@ -250,6 +253,12 @@ void GaussianTrainerScene::Impl::score_decoded(int format, const char* unpacker,
     if (test_idx.empty() || rank != 0) return;
     for (int g = 0; g < 6; ++g) d_decoded[g].reserve(dev_floats_for(g, n) * sizeof(float) + 16);
     if (const int rc = unpack(); rc != DVS_OK) throw std::runtime_error(std::string(unpacker) + ": status " + std::to_string(rc));
+    if (xf_filled) {                                                        // the payload is in the export frame: back, in place, to the cameras' frame
+        const int rc = dvs_transform_splats(stream.get(), n, sh_max, &xf_inv, xf_inv_D, d_decoded[P_POS].get(), d_decoded[P_SHN].get(), DVS_SHN_TILED,
+                                            d_decoded[P_SCALE].get(), d_decoded[P_ROT].get(), d_decoded[P_POS].get(), d_decoded[P_SHN].get(),
+                                            d_decoded[P_SCALE].get(), d_decoded[P_ROT].get());
+        if (rc != DVS_OK) throw std::runtime_error("dvs_transform_splats (inverse): status " + std::to_string(rc));
+    }
     if (eval_it != step) run_evaluation();                                  // the full model of the same parameters: the comparison
     DecodedScore& s = decoded_score[format];
     std::vector<double> res;
@@ -263,13 +272,14 @@ void GaussianTrainerScene::Impl::score_decoded(int format, const char* unpacker,
 void GaussianTrainerScene::Impl::export_model(int format) {
     if (format == EXPORT_SPZ) { export_spz(); return; }
     if (format == EXPORT_REDUCED) { export_reduced(); return; }
+    if (format == EXPORT_TRANSFORMED) { export_transformed(); return; }
     const auto t_start = std::chrono::steady_clock::now();
     const bool compressed = format == EXPORT_COMPRESSED;
     const size_t n_chunks = ((size_t)n + 255) / 256;
     const size_t chunk_bytes = n_chunks * 12 * sizeof(float);              // (a multiple of 16: the vertex records follow on a 16-byte boundary)
     const size_t bytes = compressed ? chunk_bytes + (size_t)n * 16 : (size_t)n * 32;
     d_export_out.reserve(bytes);
-    const float *pos = d_param[P_POS].get(), *sh0 = d_param[P_SH0].get(), *opa = d_param[P_OPA].get(), *scale = d_param[P_SCALE].get(), *rot = d_param[P_ROT].get();
+    const float *pos = ex(P_POS), *sh0 = ex(P_SH0), *opa = ex(P_OPA), *scale = ex(P_SCALE), *rot = ex(P_ROT);
     uint8_t* const out = d_export_out.get();
     int status;
     if (compressed) {
@@ -296,8 +306,8 @@ void GaussianTrainerScene::Impl::export_spz() {
     if (dvs_spz_layout_for(n, sh_max, &layout) != DVS_OK) throw std::runtime_error("dvs_spz_layout_for: invalid arguments");
     const size_t bytes = (size_t)layout.total;
     d_export_out.reserve(bytes);
-    const int status = dvs_pack_spz(stream.get(), n, sh_max, d_param[P_POS].get(), d_param[P_SH0].get(), d_param[P_SHN].get(), DVS_SHN_TILED,
-                                    d_param[P_OPA].get(), d_param[P_SCALE].get(), d_param[P_ROT].get(), d_export_out.get());
+    const int status = dvs_pack_spz(stream.get(), n, sh_max, ex(P_POS), ex(P_SH0), ex(P_SHN), DVS_SHN_TILED, ex(P_OPA), ex(P_SCALE), ex(P_ROT),
+                                    d_export_out.get());
     if (status != DVS_OK) throw std::runtime_error("dvs_pack_spz: status " + std::to_string(status));
     const std::string file = save_path(step, ".spz");
     if (!write_export(t_start, bytes, file, "spz", 0, [&](std::string* err) {
@@ -340,14 +350,15 @@ void GaussianTrainerScene::Impl::export_reduced() {
     float* const centres = (float*)small;
     int32_t* const iters = (int32_t*)(small + o_iters);
     uint32_t* const counts = (uint32_t*)(small + o_counts);
-    const float *pos = d_param[P_POS].get(), *sh0 = d_param[P_SH0].get(), *shN = d_param[P_SHN].get(), *opa = d_param[P_OPA].get(),
-                *scale = d_param[P_SCALE].get(), *rot = d_param[P_ROT].get();
+    // (with an export transform: degrees are selected on the model as trained, against the real camera centres; codebooks and payload
+    // come from the transformed set)
+    const float *pos = ex(P_POS), *sh0 = ex(P_SH0), *shN = ex(P_SHN), *opa = ex(P_OPA), *scale = ex(P_SCALE), *rot = ex(P_ROT);
     const auto check = [](int status, const char* what) { if (status != DVS_OK) throw std::runtime_error(std::string(what) + ": status " + std::to_string(status)); };
     if (cfg.cullSH && D > 0) {
         std::vector<float> centre(tc.size() * 3);
         for (size_t k = 0; k < tc.size(); ++k) for (int a = 0; a < 3; ++a) centre[3 * k + a] = cams[(size_t)tc[k]].campos[a];
         HIP_OR_THROW(hipMemcpyAsync(small + o_cams, centre.data(), centre.size() * sizeof(float), hipMemcpyHostToDevice, stream.get()));
-        check(dvs_sh_degree_select(stream.get(), n, D, pos, shN, DVS_SHN_TILED, (const float*)(small + o_cams), (int)tc.size(), sh_cull_threshold(),
+        check(dvs_sh_degree_select(stream.get(), n, D, d_param[P_POS].get(), d_param[P_SHN].get(), DVS_SHN_TILED, (const float*)(small + o_cams), (int)tc.size(), sh_cull_threshold(),
                                    d_red_degree.get()), "dvs_sh_degree_select");
         HIP_OR_THROW(hipStreamSynchronize(stream.get()));                    // (also: `centre` leaves scope)
     } else {
@@ -387,4 +398,107 @@ void GaussianTrainerScene::Impl::export_reduced() {
         return dvs_unpack_reduced(stream.get(), n, d_export_out.get(), &layout, d_decoded[P_POS].get(), d_decoded[P_SH0].get(), d_decoded[P_SHN].get(),
                                   DVS_SHN_TILED, d_decoded[P_OPA].get(), d_decoded[P_SCALE].get(), d_decoded[P_ROT].get(), nullptr);
     });
+}
+
+// ---- export frame (trainer.hpp; INTEGRATION.md "Export frame") ------------------------------------------------------------------------
+// Accepts a similarity: its band matrices and its inverse (with the inverse's matrices) are made once, here. -> false (logged, the
+// previous state stays) when the host helpers refuse it.
+bool GaussianTrainerScene::Impl::set_export_transform(const dvs_similarity& m, const std::string& how) {
+    dvs_similarity inv;
+    float D[83], Di[83];
+    if (dvs_similarity_inverse(&m, &inv) != DVS_OK || dvs_sh_rotation(m.R, D) != DVS_OK || dvs_sh_rotation(inv.R, Di) != DVS_OK) {
+        logf_("exportTransform: %s is not a similarity (a rotation, a finite translation, a scale > 0; non-uniform scale and shear cannot be "
+              "represented by splats): ignored", how.c_str());
+        return false;
+    }
+    xf = m; xf_inv = inv; xf_how = how; xf_set = true;
+    memcpy(xf_D, D, sizeof D); memcpy(xf_inv_D, Di, sizeof Di);
+    return true;
+}
+// R, t from the training cameras (export_frame.hpp), s = 1. -> false (logged, exports stay untransformed) when it is refused.
+bool GaussianTrainerScene::Impl::set_export_orientation(const char* axis, const char* from) {
+    double a[3], R[9], t[3], up[3];
+    if (!gsframe::parse_axis(axis, a)) { logf_("exportTransform: %s '%s' is not one of +x -x +y -y +z -z: ignored", from, axis ? axis : ""); return false; }
+    const std::vector<int> tc = training_cameras();
+    std::vector<float> views(tc.size() * 16), centres(tc.size() * 3);
+    for (size_t k = 0; k < tc.size(); ++k) {
+        memcpy(&views[16 * k], cams[(size_t)tc[k]].view, 16 * sizeof(float));
+        memcpy(&centres[3 * k], cams[(size_t)tc[k]].campos, 3 * sizeof(float));
+    }
+    std::string err;
+    if (!gsframe::orientation(tc.size(), views.data(), centres.data(), a, R, t, up, &err)) {
+        logf_("exportTransform: %s %s refused: %s; exports stay in the training frame", from, axis, err.c_str());
+        return false;
+    }
+    dvs_similarity m;
+    for (int k = 0; k < 9; ++k) m.R[k] = (float)R[k];
+    for (int k = 0; k < 3; ++k) m.t[k] = (float)t[k];
+    m.s = 1.0f;
+    char how[256];
+    snprintf(how, sizeof how, "%s %s: the mean image-up vector (%.6g, %.6g, %.6g) of %zu training cameras turned onto the axis by the shortest arc, "
+             "their centroid moved to the origin", from, axis, up[0], up[1], up[2], tc.size());
+    return set_export_transform(m, how);
+}
+// DVS_EXPORT_TRANSFORM="tx,ty,tz,rx,ry,rz,s" (Euler angles in radians, R = Rz Ry Rx) / DVS_EXPORT_ORIENT="+y": read at load
+void GaussianTrainerScene::Impl::setup_export_transform() {
+    const char *et = getenv("DVS_EXPORT_TRANSFORM"), *eo = getenv("DVS_EXPORT_ORIENT");
+    if (et && *et) {
+        if (eo && *eo) logf_("exportTransform: DVS_EXPORT_TRANSFORM and DVS_EXPORT_ORIENT are both set: DVS_EXPORT_TRANSFORM is used");
+        float v[7]; char tail = 0;
+        dvs_similarity m;
+        if (sscanf(et, "%f,%f,%f,%f,%f,%f,%f%c", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &tail) != 7 ||
+            dvs_similarity_from_trs(v, v + 3, v[6], &m) != DVS_OK) {
+            logf_("exportTransform: DVS_EXPORT_TRANSFORM='%s' is not tx,ty,tz,rx,ry,rz,s with finite numbers and s > 0: ignored", et);
+            return;
+        }
+        set_export_transform(m, std::string("DVS_EXPORT_TRANSFORM=") + et + " (T R S, R = Rz Ry Rx, radians)");
+    } else if (eo && *eo) {
+        set_export_orientation(eo, "DVS_EXPORT_ORIENT");
+    }
+}
+void GaussianTrainerScene::Impl::report_export_transform() const {
+    if (!xf_set || rank != 0) return;
+    logf_("config: exportTransform p' = s R p + t with R = [%.9g %.9g %.9g; %.9g %.9g %.9g; %.9g %.9g %.9g], t = (%.9g, %.9g, %.9g), s = %.9g, from %s: "
+          "every export but the resume PLY <modelPath>_<it>.ply is written in this frame (positions, scales, rotations and the SH bands above 0 "
+          "transformed on the device)%s; decoded payloads are taken back by the inverse before they are scored; the mesh shares the frame",
+          (double)xf.R[0], (double)xf.R[1], (double)xf.R[2], (double)xf.R[3], (double)xf.R[4], (double)xf.R[5], (double)xf.R[6], (double)xf.R[7],
+          (double)xf.R[8], (double)xf.t[0], (double)xf.t[1], (double)xf.t[2], (double)xf.s, xf_how.c_str(),
+          (export_formats() & EXPORT_TRANSFORMED) ? "; <modelPath>_<it>.transformed.ply is the full PLY in it" : "");
+    if (cfg.enableBg) logf_("config: exportTransform: the sky texture <modelPath>_<it>.sky is written in the TRAINING frame (resampling it is out of scope)");
+}
+// this save's transformed set: one launch on the training stream at the model's SH degree
+void GaussianTrainerScene::Impl::fill_transformed() {
+    const auto t_start = std::chrono::steady_clock::now();
+    for (int g : {(int)P_POS, (int)P_SHN, (int)P_SCALE, (int)P_ROT}) d_xf[xf_slot(g)].reserve(dev_floats_for(g, n) * sizeof(float) + 16);
+    const int rc = dvs_transform_splats(stream.get(), n, sh_max, &xf, xf_D, d_param[P_POS].get(), d_param[P_SHN].get(), DVS_SHN_TILED,
+                                        d_param[P_SCALE].get(), d_param[P_ROT].get(), d_xf[0].get(), d_xf[1].get(), d_xf[2].get(), d_xf[3].get());
+    if (rc != DVS_OK) throw std::runtime_error("dvs_transform_splats: status " + std::to_string(rc));
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    xf_filled = true;
+    logf_("export @%d: transform %d splats, %.2f ms", step, n, ms_since(t_start));
+}
+// <modelPath>_<it>.transformed.ply: the full PLY's wire format from the transformed set (sh0 and opacity: the host copies of the save)
+void GaussianTrainerScene::Impl::export_transformed() {
+    const auto t_start = std::chrono::steady_clock::now();
+    fetch_host();
+    std::vector<float> h[4];
+    const size_t rows = (size_t)n * 45;
+    d_xf_rows.reserve(rows * sizeof(float) + 16);
+    DVS_OR_THROW(dvs_shn_relayout(ctx.get(), stream.get(), n, d_xf[1].get(), d_xf_rows.get(), 0));
+    const float* src[4] = {d_xf[0].get(), d_xf_rows.get(), d_xf[2].get(), d_xf[3].get()};
+    const size_t floats[4] = {(size_t)n * 3, rows, (size_t)n * 3, (size_t)n * 4};
+    for (int k = 0; k < 4; ++k) {
+        h[k].resize(floats[k]);
+        HIP_OR_THROW(hipMemcpyAsync(h[k].data(), src[k], floats[k] * sizeof(float), hipMemcpyDeviceToHost, stream.get()));
+    }
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    const std::string file = save_path(step, ".transformed.ply");
+    std::string err;
+    if (!gsply::write_ply(file, (size_t)n, h[0].data(), host[P_SH0].data(), h[1].data(), host[P_OPA].data(), h[2].data(), h[3].data(), cfg.mipAntiliased, &err)) {
+        logf_("export @%d: %s", step, err.c_str());
+        return;
+    }
+    std::error_code ec;
+    const auto bytes = std::filesystem::file_size(file, ec);
+    logf_("export @%d: transformed.ply %d splats, %llu bytes, %.2f ms", step, n, (unsigned long long)(ec ? 0 : bytes), ms_since(t_start));
 }

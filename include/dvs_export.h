@@ -184,6 +184,48 @@ int dvs_pack_reduced(void* stream, int n, const float* pos, const float* sh0, co
 int dvs_unpack_reduced(void* stream, int n, const uint8_t* packed, const dvs_reduced_layout* L, float* pos, float* sh0, float* shN,
                        int shn_layout, float* opacity, float* scale, float* rot, uint8_t* degree);
 
+/* ---- export in a chosen frame: a similarity transform of the model (csrc/transform.hip; tests/transform_ref.py restates it) ------------
+ * p' = s R p + t, R row-major. A splat under it: the position moves, the log scale gains log s, the quaternion is composed with R's,
+ * the 45 higher SH floats are rotated band by band; sh0 and opacity are invariant. Non-uniform scale and shear cannot be represented
+ * by a splat and have no entry here. */
+typedef struct dvs_similarity { float R[9]; float t[3]; float s; } dvs_similarity;
+
+/* HOST helpers: pure functions, no device, no statics. Each returns DVS_ERR_INVALID (nothing is written) for a NULL pointer, a
+ * non-finite input, s <= 0, or an R that is not a rotation: ||R R^T - I||_inf (the largest absolute row sum) > 1e-4 or det < 0.
+ *   dvs_similarity_from_trs  R = Rz(euler[2]) Ry(euler[1]) Rx(euler[0]), radians: the convention of dvs_region_from_trs (dvs_region.h),
+ *                            formed in fp64 through the same half-angle quaternion and rounded once.
+ *   dvs_similarity_inverse   s' = 1 / s, R' = R^T, t' = -(R^T t) / s, in fp64, rounded once.
+ *   dvs_sh_rotation          D = the three band matrices 3x3, 5x5, 7x7, row-major, one after the other (9 + 25 + 49 = 83 floats), of THIS
+ *                            library's real SH basis (dvs_sh_basis of the rasterizer's forward, its signs included): for every unit d and
+ *                            every band, sum_k (D c)_k Y_k(R d) = sum_k c_k Y_k(d). Solved in fp64 by projection over a fixed set of
+ *                            directions and rounded once to fp32. */
+int dvs_similarity_from_trs(const float t[3], const float euler_rad[3], float s, dvs_similarity* out);
+int dvs_similarity_inverse(const dvs_similarity* in, dvs_similarity* out);
+int dvs_sh_rotation(const float R[9], float D[83]);
+
+/* The model under a similarity, ONE launch. Every result is defined operation by operation in fp32 without contraction:
+ *   pos'    row k: (((R[3k] x + R[3k+1] y) + R[3k+2] z) * s) + t[k]
+ *   scale'  scale + ls, ls = (float)log((double)s), taken once on the host
+ *   rot'    a (x) q, the Hamilton product in the stored (w, x, y, z) order, a = the unit quaternion of R (formed on the host in fp64 by the
+ *           largest-diagonal branch, sign w >= 0 where w is the pivot, rounded once), q the splat's own quaternion, NOT normalised:
+ *             w' = ((aw qw - ax qx) - ay qy) - az qz        x' = ((aw qx + ax qw) + ay qz) - az qy
+ *             y' = ((aw qy - ax qz) + ay qw) + az qx        z' = ((aw qz + ax qy) - ay qx) + az qw
+ *   shN'    per band l = 1..sh_degree and colour channel c, coefficient j of the band (element (first_l + j) * 3 + c, first_l = 0, 3, 8):
+ *           D_l[j][0] v_0 + D_l[j][1] v_1 + ... summed left to right over v_k = element (first_l + k) * 3 + c. Bands above sh_degree are
+ *           copied. In DVS_SHN_TILED whole tiles are written: the three pad floats and the lanes past n are 0 (the rule of dvs_unpack_spz).
+ * In place is allowed: any *_out may equal its input (a lane touches only its own splat); other overlaps are not. D as dvs_sh_rotation
+ * returns it for sim->R (it is not checked against R). shN / shN_out may be NULL at degree 0 (shN is then not touched). One wavefront
+ * per 64-splat tile; sim and D are wave-uniform kernel arguments.
+ * DVS_ERR_INVALID for n <= 0, a degree outside 0..3, an unknown layout, a NULL pointer (shN, shN_out: only above degree 0), a pointer
+ * off a 16-byte boundary, a sim the host helpers would refuse; nothing is launched then. */
+int dvs_transform_splats(void* stream, int n, int sh_degree, const dvs_similarity* sim, const float D[83], const float* pos, const float* shN,
+                         int shn_layout, const float* scale, const float* rot, float* pos_out, float* shN_out, float* scale_out, float* rot_out);
+
+/* Mesh vertices under the same similarity: xyz by the position rule; normals (nullable, then normals_out is ignored) by R alone,
+ * ((R[3k] x + R[3k+1] y) + R[3k+2] z), not renormalised. [n][3] fp32 arrays of natural alignment; in place is allowed.
+ * DVS_ERR_INVALID for n <= 0, NULL sim / xyz / xyz_out, normals without normals_out, a sim the host helpers would refuse. */
+int dvs_transform_points(void* stream, int n, const dvs_similarity* sim, const float* xyz, const float* normals, float* xyz_out, float* normals_out);
+
 #ifdef __cplusplus
 }
 #endif

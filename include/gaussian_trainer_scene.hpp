@@ -136,6 +136,15 @@ public:
     // when cullSH lowers its SH degree (>= 0, default 0.01) and whether positions are written as half floats. Once called it wins over
     // DVS_SH_CULL_THRESHOLD / DVS_REDUCED_HALF.
     void setReducedExport(float shCullThreshold, bool halfFloat);
+    // export frame (extension of this build, the editor's "export apply transform"; INTEGRATION.md "Export frame"): every file a save writes
+    // but the resume PLY <modelPath>_<it>.ply, and the mesh, are written under p' = scale R p + position, R = Rz Ry Rx of rotationEulerRad
+    // (radians; the focus region's convention). setExportOrientation("+y" | "-y" | "+x" | ...) derives R and the translation from the
+    // training cameras instead: their mean image-up vector turned onto the axis, their centroid moved to the origin, scale 1 (after
+    // loadTrainData). false = refused with a log line, the frame stays as it was. The last call wins, also over DVS_EXPORT_TRANSFORM /
+    // DVS_EXPORT_ORIENT; clearExportTransform() goes back to the training frame.
+    bool setExportTransform(const dvs_types::Vec3& position, const dvs_types::Vec3& rotationEulerRad, float scale);
+    bool setExportOrientation(const std::string& axis);
+    void clearExportTransform();
     void exportSparsePointCloud(const std::string& path);   // editor.cpp:3535 — writes the splat centres as an ASCII PLY point cloud
     void saveCameraDatas(const std::string& path);          // editor.cpp:3512 — one line per camera: centre, view matrix, intrinsics
     bool isTrain() const;
