@@ -197,7 +197,17 @@ class Similarity(C.Structure):         # dvs_similarity: p' = s R p + t, R row-m
     _fields_ = [("R", C.c_float * 9), ("t", C.c_float * 3), ("s", C.c_float)]
 
 
+class LodLattice(C.Structure):         # dvs_lod_lattice: the cells the LOD merge clusters by
+    _fields_ = [("origin", C.c_float * 3), ("cell", C.c_float), ("dims", C.c_int32 * 3)]
+
+
 _EXPORT_PROTOS = {
+    "dvs_lod_lattice_for": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(LodLattice)]),
+    "dvs_lod_scratch_bytes": (C.c_size_t, [C.c_int]),
+    "dvs_lod_merge_count": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LodLattice), C.c_void_p,
+                                      C.POINTER(C.c_uint32)]),
+    "dvs_lod_merge_write": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "dvs_similarity_from_trs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.POINTER(Similarity)]),
     "dvs_similarity_inverse": (C.c_int, [C.POINTER(Similarity), C.POINTER(Similarity)]),
     "dvs_sh_rotation": (C.c_int, [C.c_void_p, C.c_void_p]),

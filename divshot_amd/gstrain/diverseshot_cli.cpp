@@ -77,7 +77,11 @@ static std::map<std::string, std::string> g_opts = {
     // +x, -x, +z, -z): turn the cameras' mean up vector onto that axis and centre their centroid. One of the two at most. --exportFormat
     // takes `transformed` with either: <outputPath>_<it>.transformed.ply, the full PLY in that frame (implied when no other format is
     // selected). The config struct has no room left: they are handed to the plugin as DVS_EXPORT_TRANSFORM / DVS_EXPORT_ORIENT.
-    {"exportTransform", ""}, {"exportOrient", ""}};
+    {"exportTransform", ""}, {"exportOrient", ""},
+    // extension of this build: --exportLod L (0 = off .. 4): every save also writes <outputPath>_<it>.lod<k>.ply, k = 1..L, the model with the
+    // splats of every cell of a lattice merged into one (moment-matched, on the GPU); --lodResolution R (32..1024) is level 1's cell count
+    // along the longest side, level k has R >> (k - 1). Handed to the plugin as DVS_EXPORT_LOD / DVS_LOD_RESOLUTION, like the mesh flags.
+    {"exportLod", "0"}, {"lodResolution", "256"}};
 static std::map<std::string, bool> g_given;
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
@@ -131,6 +135,18 @@ int main(int argc, const char* argv[]) {
         const int f = digits ? atoi(v.c_str()) : -1;
         if (!(f == 0 || (f >= 2 && f <= 16))) { std::cout << "Command Line Error: --meshDecimate takes 0 (off) or an integer 2..16, not '" << v << "'\n"; return 1; }
         setenv("DVS_MESH_DECIMATE", v.c_str(), 1);                          // before the plugin is loaded
+    }
+    for (const char* flag : {"exportLod", "lodResolution"}) {
+        if (!g_given.count(flag)) continue;
+        const bool levels = std::string(flag) == "exportLod";
+        const std::string& v = g_opts[flag];
+        const bool digits = !v.empty() && v.size() <= 4 && v.find_first_not_of("0123456789") == std::string::npos;
+        const int f = digits ? atoi(v.c_str()) : -1;
+        if (levels ? !(f >= 0 && f <= 4) : !(f >= 32 && f <= 1024)) {
+            std::cout << "Command Line Error: --" << flag << (levels ? " takes a number of levels 0 (off) .. 4, not '" : " takes a resolution 32..1024, not '") << v << "'\n";
+            return 1;
+        }
+        setenv(levels ? "DVS_EXPORT_LOD" : "DVS_LOD_RESOLUTION", v.c_str(), 1);      // before the plugin is loaded
     }
     for (const char* flag : {"cullSH", "reducedHalf"})
         if (g_opts[flag] != "0" && g_opts[flag] != "1") { std::cout << "Command Line Error: --" << flag << " takes 0 or 1, not '" << g_opts[flag] << "'\n"; return 1; }

@@ -147,6 +147,7 @@ void GaussianTrainerScene::saveGaussianModel() {
         for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT, (int)Impl::EXPORT_SPZ, (int)Impl::EXPORT_REDUCED, (int)Impl::EXPORT_TRANSFORMED})
             if (m.export_formats() & format) m.export_model(format);
     }
+    if (m.rank == 0 && m.lod_levels() > 0) m.export_lod();                  // <modelPath>_<it>.lod<k>.ply (DVS_EXPORT_LOD / setLodExport)
     m.evaluate(true);                                                       // <modelPath>_<it>_eval.json beside the PLY (rank 0, evaluation on)
     m.render_at_save();                                                     // <modelPath>_<it>_renders/*.jpg (rank 0, renderViews on)
     if (m.rank == 0 && m.mesh_resolution() > 0 && m.status == TrainingStatus::Training_Done)
@@ -173,6 +174,14 @@ void GaussianTrainerScene::setMeshDecimate(int factor) {
     Impl& m = *impl_;
     if (factor != 0 && (factor < 2 || factor > 16)) { logf_("setMeshDecimate: %d is not 0 (off) or a factor 2..16: decimation is off", factor); factor = 0; }
     m.mesh_decimate_set = factor;
+}
+// The editor's switch for what DVS_EXPORT_LOD / DVS_LOD_RESOLUTION set for the CLI: once called it wins over the environment.
+void GaussianTrainerScene::setLodExport(int levels, int resolution) {
+    Impl& m = *impl_;
+    if (levels < 0 || levels > 4) { logf_("setLodExport: %d is not a number of levels 0 (off) .. 4: LOD export is off", levels); levels = 0; }
+    if (resolution < 32 || resolution > 1024) { logf_("setLodExport: %d is not a resolution 32..1024: 256 is used", resolution); resolution = 256; }
+    m.lod_levels_set = levels; m.lod_resolution_set = resolution;
+    if (levels > 0 && m.rank == 0) logf_("config: lodExport %d levels, resolution %d (setLodExport)", levels, resolution);
 }
 void GaussianTrainerScene::setReducedExport(float shCullThreshold, bool halfFloat) {
     Impl& m = *impl_;

@@ -199,6 +199,19 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     void fill_transformed();
     void export_transformed();
 
+    // level-of-detail export (INTEGRATION.md "LOD export"; trainer_lod.cpp): DVS_EXPORT_LOD = L (0 = off .. 4) and DVS_LOD_RESOLUTION = R
+    // (32..1024, default 256), or what setLodExport said (-1: it was not called). At a save rank 0 merges the FULL model on a lattice of
+    // R >> (k - 1) cells along the longest side of the finite centres' box, for k = 1..L (include/dvs_export.h, last section), scores each
+    // level on the held-out views when evaluation is on and writes <modelPath>_<it>.lod<k>.ply in the full PLY's layout (in the export
+    // frame when one is set). Nothing is allocated, launched, written or logged while L is 0.
+    int lod_levels_set = -1, lod_resolution_set = -1;
+    int lod_levels() const;
+    int lod_resolution() const;
+    GrowBuf<void> d_lod_scratch; GrowBuf<float> d_lod[6], d_lod_rows;       // a level's merged set (shN tiled), its shN as rows for the file
+    struct LodScore { int it = -1, m = 0; double mean[4] = {NAN, NAN, NAN, NAN}; };     // it = -1: none
+    LodScore lod_score[4];
+    void export_lod();
+
     // rendered views as JPEG files (cfg.renderViews / renderQuality / renderSampling and their DVS_RENDER_* overrides, read at load): at
     // every save rank 0 renders the selected cameras through eval_ctx (for_each_eval_pass: what `eval @it` scored), turns each pass
     // into quantised DCT coefficients with ONE dvs_jpeg_encode_views launch, copies them to the host and Huffman-codes them on up to

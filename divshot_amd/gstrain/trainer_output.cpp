@@ -54,6 +54,11 @@ void GaussianTrainerScene::Impl::report_config() const {
     if (const int F = mesh_decimate(); F > 0)
         logf_("config: mesh decimation: vertex clustering on cells of %d voxels of the extraction grid per axis (mean position, colour and normal per "
               "cell; collapsed and repeated triangles dropped), on the device, last before the mesh is written", F);
+    if (const int L = lod_levels(); L > 0)
+        logf_("config: lodExport %d levels, resolution %d: every save also writes <modelPath>_<it>.lod<k>.ply, k = 1..%d — the full model's splats merged "
+              "per cell of a lattice of %d >> (k - 1) cells along the longest side of the finite centres' box (weighted mean, moment-matched "
+              "covariance, weight-preserving opacity), on the device%s", L, lod_resolution(), L, lod_resolution(),
+              !test_idx.empty() ? "; every level is scored on the held-out views" : "");
     if (const int P = importance_prune(); P > 0) {
         const int asked = env_int("DVS_IMPORTANCE_PRUNE", cfg.importancePrune);
         if (asked > 90) logf_("config: importancePrune %d clamped to 90", asked);
@@ -177,6 +182,15 @@ void GaussianTrainerScene::Impl::write_eval_json() const {
         if (s.it != step) continue;
         fprintf(f, "%s\"%s\": {\"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}", any ? ", " : ",\n  \"exports\": {", s.name, s.mean[3],
                 s.mean[2], s.mean[1], s.mean[0]);
+        any = true;
+    }
+    if (any) fprintf(f, "}");
+    any = false;                                                            // the LOD levels of this save (LOD export on)
+    for (int k = 0; k < 4; ++k) {
+        const LodScore& s = lod_score[k];
+        if (s.it != step) continue;
+        fprintf(f, "%s\"%d\": {\"n_splats\": %d, \"psnr\": %.17g, \"ssim\": %.17g, \"l1\": %.17g, \"mse\": %.17g}", any ? ", " : ",\n  \"lod\": {", k + 1, s.m,
+                s.mean[3], s.mean[2], s.mean[1], s.mean[0]);
         any = true;
     }
     if (any) fprintf(f, "}");

@@ -226,6 +226,52 @@ int dvs_transform_splats(void* stream, int n, int sh_degree, const dvs_similarit
  * DVS_ERR_INVALID for n <= 0, NULL sim / xyz / xyz_out, normals without normals_out, a sim the host helpers would refuse. */
 int dvs_transform_points(void* stream, int n, const dvs_similarity* sim, const float* xyz, const float* normals, float* xyz_out, float* normals_out);
 
+/* ---- level of detail: moment-matched merging of the splats of every cell of a lattice (csrc/lod.hip; tests/lod_ref.py restates it) -------
+ * A model with fewer splats that still covers the whole scene. The lattice: cell (ix, iy, iz) of a centre p is, per axis,
+ * q = (p_a - origin_a) / cell (one subtraction, one IEEE division), 0 when !(q >= 0) (negative, NaN), dims_a - 1 when q >= dims_a, else
+ * (uint32)q — the rule of dvs_mesh_decimate; key = (iz dims_y + iy) dims_x + ix < 2^30.
+ *   dropped   a splat whose centre, opacity, scale or rotation holds a non-finite value (counted in n_dropped)
+ *   weight    w_i = alpha_i (sigma0 sigma1 sigma2)^(2/3), formed as sigmoid(opacity) * exp(((s0 + s1) + s2) * (2/3)): opacity times a mean
+ *             cross-section
+ *   cluster   the surviving splats of one cell, in ascending splat index; every sum below is the serial sum in that order, from 0
+ *   one member      its six rows are copied bit for bit (every SH band, whatever sh_degree)
+ *   more members    W = sum w_i; !(W > 0): the cluster is dropped, its members counted in n_dropped. Else, in two passes,
+ *             mu     = (sum w_i p_i) / W
+ *             Sigma' = (sum w_i (Sigma_i + (p_i - mu)(p_i - mu)^T)) / W, Sigma_i = R_i diag(sigma_i^2) R_i^T of the unit quaternion
+ *                      (dvs_unit_quat) as the rasterizer forms it, six components; a term is w_i * (Sigma_i[ab] + d_a * d_b)
+ *             sh0, and every shN element of the bands <= sh_degree: (sum w_i c_i) / W; the bands above sh_degree: 0
+ *             Sigma' = V diag(lambda) V^T by cyclic Jacobi sweeps (0,1), (0,2), (1,2) in fp32, at most 12, ended early only when the three
+ *                      off-diagonal elements are exactly 0; lambda_k floored at 1e-7 max(lambda); scale'_k = 0.5 log(lambda_k)
+ *             rot'   = the unit quaternion (w, x, y, z), w >= 0, of V with its third column negated when det V < 0
+ *             alpha' = min(0.99, W / (lambda0 lambda1 lambda2)^(1/3)): the merged splat keeps the cluster's total weight; stored as its logit
+ *   output    the live clusters in ascending cell key; m of them. A DVS_SHN_TILED output has zero pads and zero lanes past m.
+ * Two calls, as the mesh decimation: _count sorts (ballot ranking), finds the clusters and returns counts = {m, n_dropped} (it
+ * synchronises the stream); the caller allocates m rows (whole 64-splat tiles of shN for DVS_SHN_TILED); _write fills them from the same
+ * scratch and inputs. exp and log are the device library's (a few ulp from libm's); nothing else is approximated. The only atomics are
+ * integer additions to a counter: two runs return identical bytes. */
+typedef struct dvs_lod_lattice { float origin[3]; float cell; int32_t dims[3]; } dvs_lod_lattice;
+
+/* HOST: the lattice over a box bounds = {min xyz, max xyz} with `resolution` cells along its longest side: cell = (float)(longest * (1 +
+ * 1e-5) / resolution) (the margin keeps the largest coordinate's quotient below `resolution`: it lands inside the last cell), origin =
+ * the box's minimum, dims_a = ceil(side_a / cell), at least 1. DVS_ERR_INVALID (nothing is written) for a NULL pointer, a resolution
+ * outside 4..1024, a non-finite bound, max < min on an axis, or a box without extent. */
+int dvs_lod_lattice_for(const float bounds[6], int resolution, dvs_lod_lattice* out);
+
+/* Bytes of scratch for n splats (256-byte aligned parts, no initialisation): the sort's workspace and arrays, the cluster tables, the
+ * weights and the 48-byte records of dvs_lod_merge_write. */
+size_t dvs_lod_scratch_bytes(int n);
+
+/* counts = {m, n_dropped}. n = 0 gives {0, 0} and launches nothing. DVS_ERR_INVALID for n < 0, a NULL or misaligned pointer (16 bytes;
+ * scratch: 256), a cell that is not a finite number > 0, a dims entry outside 1..1024, a non-finite origin. */
+int dvs_lod_merge_count(void* stream, int n, const float* pos, const float* opacity, const float* scale, const float* rot,
+                        const dvs_lod_lattice* lattice, void* scratch, uint32_t counts[2]);
+
+/* The m merged splats, after dvs_lod_merge_count on the same n, inputs and scratch. The outputs must not overlap the inputs. n = 0
+ * launches nothing. DVS_ERR_INVALID for a degree outside 0..3, an unknown layout, a NULL or misaligned pointer. */
+int dvs_lod_merge_write(void* stream, int n, int sh_degree, const float* pos, const float* sh0, const float* shN, const float* opacity,
+                        const float* scale, const float* rot, int shn_layout_in, const void* scratch, float* pos_out, float* sh0_out,
+                        float* shN_out, float* opacity_out, float* scale_out, float* rot_out, int shn_layout_out);
+
 #ifdef __cplusplus
 }
 #endif

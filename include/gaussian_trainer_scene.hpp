@@ -132,6 +132,11 @@ public:
     // vertices inside a cell of factor^3 voxels of the extraction grid into one (vertex clustering on the device); 0 = off, any other
     // value is reported and counts as 0. Wins over DVS_MESH_DECIMATE once called.
     void setMeshDecimate(int factor);
+    // level-of-detail export (extension of this build; INTEGRATION.md "LOD export"): levels = L in 1..4 makes every save also write
+    // <modelPath>_<it>.lod<k>.ply, k = 1..L — the full model's splats merged per cell of a lattice with resolution >> (k - 1) cells
+    // (resolution 32..1024) along the longest side of the model's box, moment-matched on the device; 0 = off. A value outside these
+    // ranges is reported and counts as 0 / 256. Wins over DVS_EXPORT_LOD / DVS_LOD_RESOLUTION once called.
+    void setLodExport(int levels, int resolution);
     // the .reduced.ply export (extension of this build; exportFormats bit 8, INTEGRATION.md "Compact exports"): the colour a splat may lose
     // when cullSH lowers its SH degree (>= 0, default 0.01) and whether positions are written as half floats. Once called it wins over
     // DVS_SH_CULL_THRESHOLD / DVS_REDUCED_HALF.
