@@ -12,6 +12,15 @@
 static inline int dvs_launch_status() { return hipGetLastError() == hipSuccess ? DVS_OK : DVS_ERR_HIP; }
 // scratch carving: parts start on 256-byte boundaries
 static inline size_t dvs_align256(size_t v) { return (v + 255) & ~(size_t)255; }
+// the next part of a scratch layout: `bytes` at the running offset o, which moves on to the next boundary
+static inline size_t dvs_carve(size_t& o, size_t bytes) { const size_t at = o; o = dvs_align256(o + bytes); return at; }
+// workgroups of 256 lanes for n work items (the mesh files, lod.hip, cell_cluster.hip)
+static inline unsigned dvs_blocks256(size_t n) { return (unsigned)((n + 255) / 256); }
+// the end of a count call: the block of words the passes left on the device, read after everything queued on st
+template <class B> int dvs_fetch_block(hipStream_t st, const B* dev, B* host) {
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(host, dev, sizeof(B), hipMemcpyDeviceToHost, st) != hipSuccess) return DVS_ERR_HIP;
+    return hipStreamSynchronize(st) == hipSuccess ? DVS_OK : DVS_ERR_HIP;
+}
 
 #define DVS_TILE 16
 #define DVS_ALPHA_MIN (1.0f / 255.0f)
@@ -113,6 +122,14 @@ __device__ __forceinline__ float dvs_exp_det(float x) {
 // ROCm 7.2 is the raw 1-ulp v_sqrt_f32 and breaks bit-exactness against the CPU oracle.
 __device__ __forceinline__ float dvs_sqrt_rn(float x) { return sqrtf(x); }
 __device__ __forceinline__ float dvs_sigmoid_det(float x) { return 1.0f / (1.0f + dvs_exp_det(-x)); }
+// The unit-normal rule of the mesh line (include/dvs_mesh.h): a vector whose squared length (x x + y y) + z z is below 1e-30 becomes
+// zero, any other is divided, component by component, by the square root of that sum.
+__device__ __forceinline__ void dvs_unit_or_zero(float& x, float& y, float& z) {
+    const float l2 = (x * x + y * y) + z * z;
+    if (l2 < 1e-30f) { x = y = z = 0.0f; return; }
+    const float len = sqrtf(l2);
+    x /= len; y /= len; z /= len;
+}
 
 // Deterministic natural logarithm for x > 0 (normal numbers): a fixed sequence of IEEE-exact operations, like dvs_exp_det — it feeds an
 // integer decision (which tiles a splat is binned into with DVS_TILES_TIGHT), so the CPU oracle must reproduce it bit for bit.

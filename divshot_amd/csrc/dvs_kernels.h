@@ -107,7 +107,7 @@ hipError_t dvs_launch_seg_sort(hipStream_t st, int V, uint32_t* keys0, uint32_t*
                                int* result_in, uint32_t* ranges_enc = nullptr /*A6 fused into the last pass: tile ranges as (~start, end), see k_seg_scatter*/,
                                int write_last_keys = 1, int first_keys16 = 0 /*keys0 holds 16-bit keys (A4's tile ids)*/, int rank_atomic = 0);
 // The same sort for ONE segment [0, n): what every user outside the multi-view front end calls (the packers' Morton order, the codebooks,
-// the mesh decimation, dvs_sort_pairs_u32). Buffers 0 hold the input, *cur says which hold the result; bits <= 0 launches nothing and
+// the cell clustering and the mesh decimation's triangle words, dvs_sort_pairs_u32). Buffers 0 hold the input, *cur says which hold the result; bits <= 0 launches nothing and
 // leaves *cur = 0. The workspace, never initialised: dvs_pair_sort_ws_bytes(n) bytes carved by dvs_pair_sort_ws_at into {descriptor,
 // totals, histogram} on 256-byte boundaries, or three parts the caller owns (hist: dvs_pair_sort_hist_bytes(n), totals: DVS_FE_MAXBINS
 // words). rank_atomic = 0 is the ballot ranking: correct by construction, no probe of the device needed.
@@ -199,6 +199,19 @@ hipError_t dvs_launch_scan_u32(hipStream_t st, uint32_t* v, size_t n, uint32_t* 
 // DVS_SCAN_TILE) 64-bit words of scratch
 hipError_t dvs_launch_scan_incl_u64(hipStream_t st, uint64_t* v, size_t n, uint64_t* bsum);
 __attribute__((visibility("hidden"))) hipError_t dvs_launch_block_sums_excl(hipStream_t st, uint32_t* bsum, uint32_t nb, unsigned long long* total);
+// cell_cluster.hip — elements grouped by the lattice cell they fall into (mesh_decimate.hip, lod.hip; device side: cell_cluster.h).
+// dvs_cell_lattice fills *g; false for a null pointer, a cell that is not > 0 and finite, a dim outside 1 .. 1024 (the origin is the
+// caller's to judge). dvs_cluster_layout carves the shared parts of a scratch for n > 0 elements from offset 0 (sort_ws sized for the
+// largest sort the caller runs in it, sort_n elements if that is more than n); the caller's own parts follow from `end` (dvs_carve).
+struct DvsCellLattice;
+bool dvs_cell_lattice(const float origin[3], float cell, const int32_t dims[3], DvsCellLattice* g);
+struct DvsClusterLayout { size_t sort_ws, key[2], val[2], cex, bsum, cstart, end; };
+DvsClusterLayout dvs_cluster_layout(size_t n, size_t sort_n = 0);
+// key[0] / val[0] hold (dvs_cell_key or DVS_CELL_NONE, i) for i < n: sorts them over `bits` key bits and leaves in key[0] / val[0] the
+// sorted keys and indices (equal keys in index order, DVS_CELL_NONE last), in cstart[0 .. n_clusters] the first sorted position of every
+// cluster and the end of the last, in *n_clusters_dev their number, in cluster_of [n] (nullable) the cluster of every element.
+hipError_t dvs_launch_cell_clusters(hipStream_t st, uint32_t n, int bits, void* base, const DvsClusterLayout& L, uint32_t* cluster_of,
+                                    unsigned long long* n_clusters_dev);
 // mesh.hip — for mesh_clean.hip: the byte offsets, inside the scratch of dvs_mesh_extract_count, of vert_off [voxels] (uint32) and
 // flags [voxels] (uint8); false for dims the extraction refuses.
 bool dvs_mesh_scratch_parts(const int32_t dims[3], size_t* vert_off, size_t* flags);

@@ -3,12 +3,9 @@
 // counterpart of mesh_decimate.hip, whose two-call shape it shares.
 //
 // Counting (dvs_lod_merge_count):
-//   k_lod_keys        key[i] = the cell of splat i (30 bits; a splat with a non-finite centre, opacity, scale or rotation: LOD_DROPPED, bit
-//                     30 alone, counted), val[i] = i, wgt[i] = alpha (sigma0 sigma1 sigma2)^(2/3)
-//   sort              the one-segment pair sort, ballot ranking: (key, splat index) over 31 bits; the dropped splats end up last
-//   k_lod_heads       head[i] = the sorted position i starts a run of equal keys of surviving splats
-//   scan              head -> exclusive: a head's value is its cluster's number in key order; the total is n_clusters
-//   k_lod_starts      first sorted position of every cluster (and the end of the last)
+//   k_lod_keys        key[i] = the cell of splat i (30 bits; a splat with a non-finite centre, opacity, scale or rotation: DVS_CELL_NONE,
+//                     counted), val[i] = i, wgt[i] = alpha (sigma0 sigma1 sigma2)^(2/3)
+//   clustering        cell_cluster.hip: the splats sorted by (cell, index) over 31 bits, the dropped ones last; first sorted position of every cluster
 //   k_lod_alive       one lane per cluster: a cluster of one member lives; a larger one lives when W = the serial sum of its members'
 //                     weights is > 0, else its members are counted as dropped
 //   scan              alive -> exclusive: the output index of a live cluster; the total is m
@@ -26,19 +23,14 @@
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <stdint.h>
-#include "dvs_kernels.h"
+#include "cell_cluster.h"
 #include "export_common.h"
 #include "../../include/dvs_export.h"
 
 #define LB 256
-#define LOD_DROPPED 0x40000000u
 #define LOD_SWEEPS 12                                                       /* cyclic Jacobi on 3 x 3 in fp32 converges in 4 - 6 */
 
 namespace {
-unsigned lblocks(size_t n) { return (unsigned)((n + LB - 1) / LB); }
-
-struct LodLattice { float o[3]; float cell; uint32_t n[3]; };
-
 // the words the passes share and the host reads (one 64-byte block at the end of the scratch)
 struct LodBlock {
     unsigned long long n_clusters, m;                                     // the scans' totals
@@ -47,33 +39,22 @@ struct LodBlock {
 static_assert(sizeof(LodBlock) == 64, "one block of words");
 
 struct LodLayout {
-    size_t sort_ws, key[2], val[2], cex, bsum, cstart, wgt, coff, rec[3], block, total;
+    DvsClusterLayout c;
+    size_t wgt, coff, rec[3], block, total;
 };
 LodLayout lod_layout(uint32_t n_in) {
     LodLayout L{};
     const size_t n = n_in ? n_in : 1;
-    size_t o = 0;
-    auto part = [&o](size_t bytes) { const size_t at = o; o = dvs_align256(o + bytes); return at; };
-    L.sort_ws = part(dvs_pair_sort_ws_bytes((uint64_t)n));
-    for (int k = 0; k < 2; ++k) { L.key[k] = part(n * 4); L.val[k] = part(n * 4); }
-    L.cex = part(n * 4);
-    L.bsum = part(((n + DVS_SCAN_TILE - 1) / DVS_SCAN_TILE) * 4);
-    L.cstart = part((n + 1) * 4);
-    L.wgt = part(n * 4);
-    L.coff = part(n * 4);
-    for (int k = 0; k < 3; ++k) L.rec[k] = part(n * 16);
-    L.block = part(sizeof(LodBlock));
+    L.c = dvs_cluster_layout(n);
+    size_t o = L.c.end;
+    L.wgt = dvs_carve(o, n * 4);
+    L.coff = dvs_carve(o, n * 4);
+    for (int k = 0; k < 3; ++k) L.rec[k] = dvs_carve(o, n * 16);
+    L.block = dvs_carve(o, sizeof(LodBlock));
     L.total = o;
     return L;
 }
 
-// the cell of a coordinate along one axis: the rule of mesh_decimate.hip's dec_axis
-__device__ __forceinline__ uint32_t lod_axis(float x, float o, float cell, uint32_t n) {
-    const float q = (x - o) / cell;
-    if (!(q >= 0.0f)) return 0u;
-    if (q >= (float)n) return n - 1u;
-    return (uint32_t)q;
-}
 __device__ __forceinline__ bool lod_finite(float x) { return fabsf(x) < __builtin_inff(); }
 
 __global__ void k_lod_init(LodBlock* blk) { blk->n_clusters = 0; blk->m = 0; blk->n_dropped = 0; }
@@ -81,7 +62,7 @@ __global__ void k_lod_init(LodBlock* blk) { blk->n_clusters = 0; blk->m = 0; blk
 // One thread per splat. No lane leaves early: the wave's leader adds the wave's count.
 __global__ void __launch_bounds__(LB)
 k_lod_keys(uint32_t n, const float* __restrict__ pos, const float* __restrict__ opacity, const float* __restrict__ scale, const float* __restrict__ rot,
-           LodLattice g, uint32_t* __restrict__ key, uint32_t* __restrict__ val, float* __restrict__ wgt, LodBlock* blk) {
+           DvsCellLattice g, uint32_t* __restrict__ key, uint32_t* __restrict__ val, float* __restrict__ wgt, LodBlock* blk) {
     const size_t i = (size_t)blockIdx.x * LB + threadIdx.x;
     bool dropped = false;
     if (i < n) {
@@ -91,11 +72,10 @@ k_lod_keys(uint32_t n, const float* __restrict__ pos, const float* __restrict__ 
         const bool fin = lod_finite(x) && lod_finite(y) && lod_finite(z) && lod_finite(o) && lod_finite(s0) && lod_finite(s1) && lod_finite(s2) &&
                          lod_finite(r.x) && lod_finite(r.y) && lod_finite(r.z) && lod_finite(r.w);
         dropped = !fin;
-        uint32_t k = LOD_DROPPED;
+        uint32_t k = DVS_CELL_NONE;
         float w = 0.0f;
         if (fin) {
-            const uint32_t ix = lod_axis(x, g.o[0], g.cell, g.n[0]), iy = lod_axis(y, g.o[1], g.cell, g.n[1]), iz = lod_axis(z, g.o[2], g.cell, g.n[2]);
-            k = (iz * g.n[1] + iy) * g.n[0] + ix;                            // < 1024^3 = 2^30
+            k = dvs_cell_key(x, y, z, g);
             const float alpha = 1.0f / (1.0f + expf(-o));
             w = alpha * expf(((s0 + s1) + s2) * 0.6666666666666666f);      // (sigma0 sigma1 sigma2)^(2/3)
         }
@@ -104,25 +84,6 @@ k_lod_keys(uint32_t n, const float* __restrict__ pos, const float* __restrict__ 
     const uint32_t nd = (uint32_t)__popcll(__ballot(dropped));
     if ((threadIdx.x & 63u) == 0u && nd) atomicAdd(&blk->n_dropped, nd);
 }
-__global__ void __launch_bounds__(LB) k_lod_heads(uint32_t n, const uint32_t* __restrict__ skey, uint32_t* __restrict__ head) {
-    const size_t i = (size_t)blockIdx.x * LB + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t k = skey[i];
-    head[i] = (k != LOD_DROPPED && (i == 0 || k != skey[i - 1])) ? 1u : 0u;
-}
-// cex = the exclusive scan of the heads: a head's value is its cluster's number. The survivors are the sorted positions [0, ns): the
-// last of them closes the last cluster.
-__global__ void __launch_bounds__(LB)
-k_lod_starts(uint32_t n, const uint32_t* __restrict__ skey, const uint32_t* __restrict__ cex, uint32_t* __restrict__ cstart) {
-    const size_t i = (size_t)blockIdx.x * LB + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t k = skey[i];
-    if (k == LOD_DROPPED) return;
-    const bool head = i == 0 || k != skey[i - 1];
-    const uint32_t c = head ? cex[i] : cex[i] - 1u;                          // (a follower has a head before it: cex >= 1)
-    if (head) cstart[c] = (uint32_t)i;
-    if (i + 1 == n || skey[i + 1] == LOD_DROPPED) cstart[c + 1u] = (uint32_t)(i + 1);      // c + 1 = n_clusters <= n: inside the n + 1 words
-}
 // One lane per cluster: alive[c] = 1 when the cluster is written. W is the serial sum in ascending splat index, the same sum
 // k_lod_geometry forms from the records (which hold these very words).
 __global__ void __launch_bounds__(LB)
@@ -130,13 +91,10 @@ k_lod_alive(uint32_t n, LodBlock* blk, const uint32_t* __restrict__ cstart, cons
             uint32_t* __restrict__ alive) {
     const size_t c = (size_t)blockIdx.x * LB + threadIdx.x;
     if (c >= n) return;
-    uint32_t a = 0u;
-    if (c < blk->n_clusters) {
-        const uint32_t first = cstart[c];
-        uint32_t end = cstart[c + 1];
-        if (end > n) end = n;                                                // the loop's bound comes from the input
+    uint32_t a = 0u, first, end;
+    if (dvs_cluster_run(c, n, blk->n_clusters, cstart, &first, &end)) {
         if (first + 1u == end) a = 1u;
-        else if (first < end) {
+        else {
             float W = 0.0f;
             for (uint32_t m = first; m < end; ++m) { const uint32_t v = sidx[m]; W = W + (v < n ? wgt[v] : 0.0f); }
             if (W > 0.0f) a = 1u;
@@ -151,7 +109,7 @@ __global__ void __launch_bounds__(LB)
 k_lod_gather(uint32_t n, const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sidx, const float* __restrict__ pos, const float* __restrict__ scale,
              const float* __restrict__ rot, const float* __restrict__ wgt, float4* __restrict__ rec0, float4* __restrict__ rec1, float4* __restrict__ rec2) {
     const size_t i = (size_t)blockIdx.x * LB + threadIdx.x;
-    if (i >= n || skey[i] == LOD_DROPPED) return;
+    if (i >= n || skey[i] == DVS_CELL_NONE) return;
     const size_t v = sidx[i];
     if (v >= n) return;                                                      // (never: sidx is a permutation of [0, n))
     float q[4], R[9], cov[6];
@@ -195,11 +153,8 @@ k_lod_geometry(uint32_t n, const LodBlock* __restrict__ blk, const uint32_t* __r
                const float* __restrict__ pos, const float* __restrict__ opacity, const float* __restrict__ scale, const float* __restrict__ rot,
                float* __restrict__ pos_out, float* __restrict__ opacity_out, float* __restrict__ scale_out, float* __restrict__ rot_out) {
     const size_t c = (size_t)blockIdx.x * LB + threadIdx.x;
-    if (c >= n || c >= blk->n_clusters || !alive[c]) return;
-    const uint32_t first = cstart[c];
-    uint32_t end = cstart[c + 1];
-    if (end > n) end = n;
-    if (first >= end) return;                                                // (never: a cluster has a member)
+    uint32_t first, end;
+    if (!dvs_cluster_run(c, n, blk->n_clusters, cstart, &first, &end) || !alive[c]) return;
     const size_t o = coff[c];                                                // < m <= n
     if (first + 1u == end) {                                                 // one member: its rows, bit for bit
         const size_t v = sidx[first];
@@ -284,11 +239,8 @@ k_lod_colour(uint32_t n, int limit, const LodBlock* __restrict__ blk, const uint
              const float* __restrict__ shN, int tiled_in, float* __restrict__ sh0_out, float* __restrict__ shN_out, int tiled_out) {
     const size_t c = (size_t)blockIdx.x * LB + threadIdx.x;
     const int ch = (int)blockIdx.y;
-    if (c >= n || c >= blk->n_clusters || !alive[c]) return;
-    const uint32_t first = cstart[c];
-    uint32_t end = cstart[c + 1];
-    if (end > n) end = n;
-    if (first >= end) return;
+    uint32_t first, end;
+    if (!dvs_cluster_run(c, n, blk->n_clusters, cstart, &first, &end) || !alive[c]) return;
     const size_t o = coff[c];
     float4 r;
     if (first + 1u == end) {
@@ -338,7 +290,7 @@ extern "C" int dvs_lod_lattice_for(const float bounds[6], int resolution, dvs_lo
         side[k] = (double)bounds[3 + k] - (double)bounds[k];
         longest = std::fmax(longest, side[k]);
     }
-    // 1e-5 of the side is some hundred ulps of any coordinate quotient: the largest coordinate's (x - o) / cell stays below `resolution`
+    // 1e-5 of the side is some hundred ulps of any coordinate quotient: the largest coordinate's quotient in dvs_cell_key stays below `resolution`
     const float cell = (float)(longest * (1.0 + 1e-5) / (double)resolution);
     if (!(cell > 0.0f) || !std::isfinite(cell)) return DVS_ERR_INVALID;     // an empty box (or one whose cell is not an fp32 number)
     dvs_lod_lattice g;
@@ -356,9 +308,10 @@ extern "C" size_t dvs_lod_scratch_bytes(int n) { return lod_layout(n > 0 ? (uint
 
 extern "C" int dvs_lod_merge_count(void* stream, int n, const float* pos, const float* opacity, const float* scale, const float* rot,
                                    const dvs_lod_lattice* lattice, void* scratch, uint32_t counts[2]) {
-    if (n < 0 || !lattice || !counts || !scratch || ((uintptr_t)scratch & 255u) || !(lattice->cell > 0.0f) || !std::isfinite(lattice->cell))
+    DvsCellLattice g;
+    if (n < 0 || !lattice || !counts || !scratch || ((uintptr_t)scratch & 255u) || !dvs_cell_lattice(lattice->origin, lattice->cell, lattice->dims, &g))
         return DVS_ERR_INVALID;
-    for (int k = 0; k < 3; ++k) if (lattice->dims[k] < 1 || lattice->dims[k] > 1024 || !std::isfinite(lattice->origin[k])) return DVS_ERR_INVALID;
+    for (int k = 0; k < 3; ++k) if (!std::isfinite(lattice->origin[k])) return DVS_ERR_INVALID;
     counts[0] = 0; counts[1] = 0;
     if (n == 0) return DVS_OK;
     if (dvs_bad_args({pos, opacity, scale, rot})) return DVS_ERR_INVALID;
@@ -367,34 +320,18 @@ extern "C" int dvs_lod_merge_count(void* stream, int n, const float* pos, const 
     const LodLayout L = lod_layout(un);
     char* const base = (char*)scratch;
     LodBlock* const blk = (LodBlock*)(base + L.block);
-    const dim3 grid(lblocks(un)), block(LB);
-    LodLattice g;
-    for (int k = 0; k < 3; ++k) { g.o[k] = lattice->origin[k]; g.n[k] = (uint32_t)lattice->dims[k]; }
-    g.cell = lattice->cell;
-    uint32_t* key[2] = {(uint32_t*)(base + L.key[0]), (uint32_t*)(base + L.key[1])};
-    uint32_t* val[2] = {(uint32_t*)(base + L.val[0]), (uint32_t*)(base + L.val[1])};
+    const dim3 grid(dvs_blocks256(un)), block(LB);
+    uint32_t *sidx = (uint32_t*)(base + L.c.val[0]), *cex = (uint32_t*)(base + L.c.cex), *coff = (uint32_t*)(base + L.coff);
     float* const wgt = (float*)(base + L.wgt);
     hipLaunchKernelGGL(k_lod_init, dim3(1), dim3(1), 0, st, blk);
-    hipLaunchKernelGGL(k_lod_keys, grid, block, 0, st, un, pos, opacity, scale, rot, g, key[0], val[0], wgt, blk);
-    int cur = 0;
-    if (dvs_launch_pair_sort(st, un, key[0], val[0], key[1], val[1], 0, 31, dvs_pair_sort_ws_at(base + L.sort_ws), 0, &cur) != hipSuccess) return DVS_ERR_HIP;   // ballot ranking
-    // the write call looks for the sorted order in buffers 0
-    if (cur != 0 && (hipMemcpyAsync(key[0], key[1], (size_t)un * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                     hipMemcpyAsync(val[0], val[1], (size_t)un * 4, hipMemcpyDeviceToDevice, st) != hipSuccess))
-        return DVS_ERR_HIP;
-    const uint32_t *skey = key[0], *sidx = val[0];
-    uint32_t *cex = (uint32_t*)(base + L.cex), *bsum = (uint32_t*)(base + L.bsum), *cstart = (uint32_t*)(base + L.cstart), *coff = (uint32_t*)(base + L.coff);
-    hipLaunchKernelGGL(k_lod_heads, grid, block, 0, st, un, skey, cex);
-    if (dvs_launch_scan_u32(st, cex, un, bsum, &blk->n_clusters) != hipSuccess) return DVS_ERR_HIP;
-    hipLaunchKernelGGL(k_lod_starts, grid, block, 0, st, un, skey, (const uint32_t*)cex, cstart);
-    hipLaunchKernelGGL(k_lod_alive, grid, block, 0, st, un, blk, (const uint32_t*)cstart, sidx, (const float*)wgt, coff);
+    hipLaunchKernelGGL(k_lod_keys, grid, block, 0, st, un, pos, opacity, scale, rot, g, (uint32_t*)(base + L.c.key[0]), sidx, wgt, blk);
+    if (dvs_launch_cell_clusters(st, un, 31, base, L.c, nullptr, &blk->n_clusters) != hipSuccess) return DVS_ERR_HIP;
+    hipLaunchKernelGGL(k_lod_alive, grid, block, 0, st, un, blk, (const uint32_t*)(base + L.c.cstart), (const uint32_t*)sidx, (const float*)wgt, coff);
     // (alive stays in cex's place for the write call: the scan below turns coff into offsets)
     if (hipMemcpyAsync(cex, coff, (size_t)un * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return DVS_ERR_HIP;
-    if (dvs_launch_scan_u32(st, coff, un, bsum, &blk->m) != hipSuccess) return DVS_ERR_HIP;
-    if (hipGetLastError() != hipSuccess) return DVS_ERR_HIP;
+    if (dvs_launch_scan_u32(st, coff, un, (uint32_t*)(base + L.c.bsum), &blk->m) != hipSuccess) return DVS_ERR_HIP;
     LodBlock host{};
-    if (hipMemcpyAsync(&host, blk, sizeof host, hipMemcpyDeviceToHost, st) != hipSuccess) return DVS_ERR_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return DVS_ERR_HIP;
+    if (dvs_fetch_block(st, blk, &host) != DVS_OK) return DVS_ERR_HIP;
     counts[0] = (uint32_t)host.m; counts[1] = host.n_dropped;
     return DVS_OK;
 }
@@ -411,19 +348,19 @@ extern "C" int dvs_lod_merge_write(void* stream, int n, int sh_degree, const flo
     const LodLayout L = lod_layout(un);
     const char* const base = (const char*)scratch;
     const LodBlock* blk = (const LodBlock*)(base + L.block);
-    const uint32_t *skey = (const uint32_t*)(base + L.key[0]), *sidx = (const uint32_t*)(base + L.val[0]), *alive = (const uint32_t*)(base + L.cex),
-                   *cstart = (const uint32_t*)(base + L.cstart), *coff = (const uint32_t*)(base + L.coff);
+    const uint32_t *skey = (const uint32_t*)(base + L.c.key[0]), *sidx = (const uint32_t*)(base + L.c.val[0]), *alive = (const uint32_t*)(base + L.c.cex),
+                   *cstart = (const uint32_t*)(base + L.c.cstart), *coff = (const uint32_t*)(base + L.coff);
     const float* wgt = (const float*)(base + L.wgt);
     // the record area is this call's workspace inside the scratch; what dvs_lod_merge_count left there is read only
     float4* rec[3];
     for (int k = 0; k < 3; ++k) rec[k] = (float4*)const_cast<char*>(base + L.rec[k]);
-    const dim3 grid(lblocks(un)), block(LB);
+    const dim3 grid(dvs_blocks256(un)), block(LB);
     static const int limit[4] = {0, 9, 24, 45};
     const int tin = shn_layout_in == DVS_SHN_TILED ? 1 : 0, tout = shn_layout_out == DVS_SHN_TILED ? 1 : 0;
     hipLaunchKernelGGL(k_lod_gather, grid, block, 0, st, un, skey, sidx, pos, scale, rot, wgt, rec[0], rec[1], rec[2]);
     hipLaunchKernelGGL(k_lod_geometry, grid, block, 0, st, un, blk, cstart, alive, coff, sidx, (const float4*)rec[0], (const float4*)rec[1], (const float4*)rec[2],
                        pos, opacity, scale, rot, pos_out, opacity_out, scale_out, rot_out);
-    hipLaunchKernelGGL(k_lod_colour, dim3(lblocks(un), 12), block, 0, st, un, limit[sh_degree], blk, cstart, alive, coff, sidx, (const float4*)rec[0], sh0, shN,
+    hipLaunchKernelGGL(k_lod_colour, dim3(dvs_blocks256(un), 12), block, 0, st, un, limit[sh_degree], blk, cstart, alive, coff, sidx, (const float4*)rec[0], sh0, shN,
                        tin, sh0_out, shN_out, tout);
     if (tout) hipLaunchKernelGGL(k_lod_pads, dim3(3), block, 0, st, un, blk, shN_out);
     return dvs_launch_status();

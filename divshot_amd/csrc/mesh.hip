@@ -24,7 +24,6 @@ struct GridDims { int dx, dy, dz; };
 __host__ __device__ inline size_t grid_voxels(const GridDims& g) { return (size_t)g.dx * g.dy * g.dz; }
 bool dims_ok(const int32_t d[3]) { return d && d[0] >= 2 && d[1] >= 2 && d[2] >= 2 && d[0] <= DVS_TSDF_MAX_DIM && d[1] <= DVS_TSDF_MAX_DIM && d[2] <= DVS_TSDF_MAX_DIM; }
 bool grid_ok(const dvs_tsdf_grid* g) { return g && dims_ok(g->dims) && g->voxel > 0.f && g->tsdf && g->weight && g->rgb; }
-unsigned blocks_for(size_t n) { return (unsigned)((n + MB - 1) / MB); }
 
 // ---- the 16-case table of the six tetrahedra, derived at compile time -------------------------------------------------------------
 // Tetrahedron t has the cell corners c[0] = 0, c[1] = 1 << p0, c[2] = c[1] | 1 << p1, c[3] = 7 for the t-th permutation (p0, p1, p2) of
@@ -279,7 +278,7 @@ extern "C" size_t dvs_tsdf_bytes(const int32_t dims[3]) { return dims_ok(dims) ?
 extern "C" int dvs_tsdf_clear(void* stream, const dvs_tsdf_grid* grid) {
     if (!grid_ok(grid)) return DVS_ERR_INVALID;
     const size_t nv = (size_t)grid->dims[0] * grid->dims[1] * grid->dims[2];
-    hipLaunchKernelGGL(k_tsdf_clear, dim3(blocks_for(nv)), dim3(MB), 0, (hipStream_t)stream, nv, grid->tsdf, grid->weight, grid->rgb);
+    hipLaunchKernelGGL(k_tsdf_clear, dim3(dvs_blocks256(nv)), dim3(MB), 0, (hipStream_t)stream, nv, grid->tsdf, grid->weight, grid->rgb);
     return dvs_launch_status();
 }
 
@@ -320,7 +319,7 @@ extern "C" int dvs_tsdf_integrate(void* stream, const dvs_tsdf_grid* grid, const
     TsdfViews views{};
     for (int v = 0; v < n_views; ++v) { memcpy(&views.cams.c[v], &cams[v], sizeof(DvsCam)); views.mask[v] = masks ? masks[v] : nullptr; }
     const GridDims g{grid->dims[0], grid->dims[1], grid->dims[2]};
-    hipLaunchKernelGGL(k_tsdf_integrate, dim3(blocks_for(grid_voxels(g))), dim3(MB), 0, (hipStream_t)stream, views, n_views, g, grid->origin[0],
+    hipLaunchKernelGGL(k_tsdf_integrate, dim3(dvs_blocks256(grid_voxels(g))), dim3(MB), 0, (hipStream_t)stream, views, n_views, g, grid->origin[0],
                        grid->origin[1], grid->origin[2], grid->voxel, grid->tsdf, grid->weight, grid->rgb, depth, alpha, rgb, W, H, trunc);
     return dvs_launch_status();
 }
@@ -337,7 +336,7 @@ extern "C" int dvs_mesh_extract_count(void* stream, const dvs_tsdf_grid* grid, v
     uint32_t *vert_off = (uint32_t*)(base + L.vert_off), *tri_off = (uint32_t*)(base + L.tri_off);
     uint8_t *flags = (uint8_t*)(base + L.flags), *cell_ok = (uint8_t*)(base + L.cell_ok);
     unsigned long long* totals = (unsigned long long*)(base + L.totals);
-    const dim3 grid_dim(blocks_for(nv)), block(MB);
+    const dim3 grid_dim(dvs_blocks256(nv)), block(MB);
     hipLaunchKernelGGL(k_mesh_cells, grid_dim, block, 0, st, g, (const float*)grid->weight, cell_ok);
     hipLaunchKernelGGL(k_mesh_edges, grid_dim, block, 0, st, g, (const float*)grid->tsdf, (const uint8_t*)cell_ok, flags, vert_off);
     if (dvs_launch_scan_u32(st, vert_off, nv, (uint32_t*)(base + L.bsum_v), totals) != hipSuccess) return DVS_ERR_HIP;
@@ -361,7 +360,7 @@ extern "C" int dvs_mesh_extract_write(void* stream, const dvs_tsdf_grid* grid, c
     const char* const base = (const char*)scratch;
     const uint32_t *vert_off = (const uint32_t*)(base + L.vert_off), *tri_off = (const uint32_t*)(base + L.tri_off);
     const uint8_t *flags = (const uint8_t*)(base + L.flags), *cell_ok = (const uint8_t*)(base + L.cell_ok);
-    const dim3 grid_dim(blocks_for(nv)), block(MB);
+    const dim3 grid_dim(dvs_blocks256(nv)), block(MB);
     hipLaunchKernelGGL(k_mesh_verts, grid_dim, block, 0, st, g, grid->origin[0], grid->origin[1], grid->origin[2], grid->voxel, (const float*)grid->tsdf,
                        (const float*)grid->rgb, flags, vert_off, xyz, rgb);
     hipLaunchKernelGGL(k_mesh_tris, grid_dim, block, 0, st, g, (const float*)grid->tsdf, cell_ok, flags, vert_off, tri_off, tri);

@@ -32,8 +32,6 @@
 namespace {
 __device__ uint32_t g_mesh_err;        // != 0: a capped loop ran out (one word per device)
 
-unsigned cblocks(size_t n) { return (unsigned)((n + CB - 1) / CB); }
-
 __device__ __forceinline__ uint32_t ld_relaxed(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // The root of x while links are still being made. parent[x] <= x for every x at every moment (initially equal, and every later write is
@@ -244,9 +242,7 @@ k_mesh_normals(NDims g, const float* __restrict__ tsdf, const float* __restrict_
         const float s = 1.0f - t;
 #pragma unroll
         for (int c = 0; c < 3; ++c) nrm[c] = s * gp[c] + t * gq[c];
-        const float len2 = nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2];
-        if (len2 < 1e-30f) { nrm[0] = nrm[1] = nrm[2] = 0.f; }
-        else { const float len = sqrtf(len2); nrm[0] /= len; nrm[1] /= len; nrm[2] /= len; }
+        dvs_unit_or_zero(nrm[0], nrm[1], nrm[2]);
         normals[3 * id] = nrm[0]; normals[3 * id + 1] = nrm[1]; normals[3 * id + 2] = nrm[2];
         ++id;
     }
@@ -257,10 +253,10 @@ extern "C" int dvs_mesh_components(void* stream, uint32_t n_vertices, const uint
     if ((n_vertices > 0 && !label) || (n_triangles > 0 && !tri)) return DVS_ERR_INVALID;
     hipStream_t st = (hipStream_t)stream;
     if (n_bad && hipMemsetAsync(n_bad, 0, sizeof(uint32_t), st) != hipSuccess) return DVS_ERR_HIP;
-    if (n_vertices > 0) hipLaunchKernelGGL(k_cc_init, dim3(cblocks(n_vertices)), dim3(CB), 0, st, n_vertices, label);
+    if (n_vertices > 0) hipLaunchKernelGGL(k_cc_init, dim3(dvs_blocks256(n_vertices)), dim3(CB), 0, st, n_vertices, label);
     // (with no vertex every triangle is bad: the union pass still counts them, and dereferences nothing but tri)
-    if (n_triangles > 0) hipLaunchKernelGGL(k_cc_union, dim3(cblocks(n_triangles)), dim3(CB), 0, st, n_vertices, tri, n_triangles, label, n_bad);
-    if (n_vertices > 0 && n_triangles > 0) hipLaunchKernelGGL(k_cc_flatten, dim3(cblocks(n_vertices)), dim3(CB), 0, st, n_vertices, label);
+    if (n_triangles > 0) hipLaunchKernelGGL(k_cc_union, dim3(dvs_blocks256(n_triangles)), dim3(CB), 0, st, n_vertices, tri, n_triangles, label, n_bad);
+    if (n_vertices > 0 && n_triangles > 0) hipLaunchKernelGGL(k_cc_flatten, dim3(dvs_blocks256(n_vertices)), dim3(CB), 0, st, n_vertices, label);
     return dvs_launch_status();
 }
 
@@ -274,7 +270,7 @@ extern "C" int dvs_mesh_clean_count(void* stream, uint32_t n_vertices, const uin
     char* const base = (char*)scratch;
     uint32_t *label = (uint32_t*)(base + L.label), *cnt = (uint32_t*)(base + L.cnt), *voff = (uint32_t*)(base + L.voff), *toff = (uint32_t*)(base + L.toff);
     CleanBlock* blk = (CleanBlock*)(base + L.block);
-    const dim3 gv(cblocks(n_vertices)), gt(cblocks(n_triangles)), block(CB);
+    const dim3 gv(dvs_blocks256(n_vertices)), gt(dvs_blocks256(n_triangles)), block(CB);
     hipLaunchKernelGGL(k_clean_init, dim3(1), dim3(1), 0, st, blk, min_bp);
     const int rc = dvs_mesh_components(stream, n_vertices, tri, n_triangles, label, &blk->n_bad);
     if (rc != DVS_OK) return rc;
@@ -291,10 +287,8 @@ extern "C" int dvs_mesh_clean_count(void* stream, uint32_t n_vertices, const uin
         }
     }
     hipLaunchKernelGGL(k_clean_finish, dim3(1), dim3(1), 0, st, blk);
-    if (hipGetLastError() != hipSuccess) return DVS_ERR_HIP;
     CleanBlock host{};
-    if (hipMemcpyAsync(&host, blk, sizeof host, hipMemcpyDeviceToHost, st) != hipSuccess) return DVS_ERR_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return DVS_ERR_HIP;
+    if (dvs_fetch_block(st, blk, &host) != DVS_OK) return DVS_ERR_HIP;
     info->n_components = host.n_components; info->largest = host.largest; info->kept_components = host.kept_components;
     info->kept_vertices = (uint32_t)host.kept_vertices; info->kept_triangles = (uint32_t)host.kept_triangles; info->n_bad = host.n_bad;
     return host.err ? DVS_ERR_STATE : DVS_OK;
@@ -311,9 +305,9 @@ extern "C" int dvs_mesh_clean_write(void* stream, uint32_t n_vertices, const flo
     const uint32_t *label = (const uint32_t*)(base + L.label), *cnt = (const uint32_t*)(base + L.cnt), *voff = (const uint32_t*)(base + L.voff),
                    *toff = (const uint32_t*)(base + L.toff);
     const CleanBlock* blk = (const CleanBlock*)(base + L.block);
-    hipLaunchKernelGGL(k_clean_write_v, dim3(cblocks(n_vertices)), dim3(CB), 0, st, n_vertices, xyz, rgb, normals, label, cnt, voff, blk, out_xyz, out_rgb,
+    hipLaunchKernelGGL(k_clean_write_v, dim3(dvs_blocks256(n_vertices)), dim3(CB), 0, st, n_vertices, xyz, rgb, normals, label, cnt, voff, blk, out_xyz, out_rgb,
                        out_normals);
-    hipLaunchKernelGGL(k_clean_write_t, dim3(cblocks(n_triangles)), dim3(CB), 0, st, n_vertices, tri, n_triangles, label, cnt, voff, toff, blk, out_tri);
+    hipLaunchKernelGGL(k_clean_write_t, dim3(dvs_blocks256(n_triangles)), dim3(CB), 0, st, n_vertices, tri, n_triangles, label, cnt, voff, toff, blk, out_tri);
     return dvs_launch_status();
 }
 
@@ -325,7 +319,7 @@ extern "C" int dvs_mesh_extract_normals(void* stream, const dvs_tsdf_grid* grid,
     const NDims g{grid->dims[0], grid->dims[1], grid->dims[2]};
     const size_t nv = (size_t)g.dx * g.dy * g.dz;
     const char* const base = (const char*)scratch;
-    hipLaunchKernelGGL(k_mesh_normals, dim3(cblocks(nv)), dim3(CB), 0, (hipStream_t)stream, g, (const float*)grid->tsdf, (const float*)grid->weight,
+    hipLaunchKernelGGL(k_mesh_normals, dim3(dvs_blocks256(nv)), dim3(CB), 0, (hipStream_t)stream, g, (const float*)grid->tsdf, (const float*)grid->weight,
                        (const uint8_t*)(base + flags_off), (const uint32_t*)(base + vert_off_off), normals);
     return dvs_launch_status();
 }

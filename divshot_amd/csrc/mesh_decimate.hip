@@ -5,16 +5,13 @@
 //
 // Vertices (dvs_mesh_decimate_count):
 //   k_dec_keys        key[v] = the cell of v (30 bits), val[v] = v
-//   sort              the stable segmented LSD sort of frontend.hip, one segment, ballot ranking: (key, vertex index) over 30 bits
-//   k_dec_heads       head[i] = the sorted position i starts a run of equal keys
-//   scan              head -> exclusive: a head's value is its cluster number in key order; the total is n_clusters
-//   k_dec_assign      cluster_of[vertex], first sorted position of every cluster (and the end of the last)
+//   clustering        cell_cluster.hip: the vertices sorted by (cell, index), cluster_of[vertex], first sorted position of every cluster
 // Triangles:
 //   k_dec_canon       bad / degenerate triangles counted and given the words (0, 0, 0); the others their three cluster numbers rotated so
 //                     that the smallest comes first (winding kept) -> w0, w1, w2
-//   sort x 3          stable LSD sorts of (word, triangle id) over w2, then w1, then w0 (k_dec_regather loads the next word in the
-//                     order the last sort left), each over the bits min(n_vertices, cells) - 1 needs — the host's bound on
-//                     n_clusters - 1, known without waiting for the device
+//   sort x 3          the one-segment pair sort of frontend.hip (stable, ballot ranking) of (word, triangle id) over w2, then w1, then w0
+//                     (k_dec_regather loads the next word in the order the last sort left), each over the bits min(n_vertices, cells) - 1
+//                     needs — the host's bound on n_clusters - 1, known without waiting for the device
 //   k_dec_dups        a surviving triangle whose three words equal its predecessor's in that order repeats it: the run's first member
 //                     is the one with the smallest triangle index (the sorts are stable), the others are counted and dropped
 //   scan              keep -> exclusive: the new index of a kept triangle
@@ -30,19 +27,14 @@
 // The only atomics are integer additions to three counters (one per wave), whose sums do not depend on order. No kernel waits for
 // another workgroup: phases are launches. Every device loop is bounded by n_vertices. No scratch memory, no inline assembly.
 #include <hip/hip_runtime.h>
-#include <cmath>
 #include <stdint.h>
 #include <utility>
 #include "../../include/dvs_mesh.h"
-#include "dvs_kernels.h"
+#include "cell_cluster.h"
 
 #define MB 256
 
 namespace {
-unsigned mblocks(size_t n) { return (unsigned)((n + MB - 1) / MB); }
-
-struct DecLattice { float o[3]; float cell; uint32_t n[3]; };
-
 // the words the passes share and the host reads (one 64-byte block at the end of the scratch)
 struct DecBlock {
     unsigned long long n_clusters, out_vertices, out_triangles;       // the scans' totals
@@ -51,43 +43,30 @@ struct DecBlock {
 static_assert(sizeof(DecBlock) == 64, "one block of words");
 
 struct DecLayout {
-    size_t sort_ws;                                                    // the pair sort's workspace, shared by the vertex and the triangle sorts
-    size_t vkey[2], vval[2], cex, bsum_v, vclu, cstart, used, coff;    // per vertex
+    DvsClusterLayout c;                                                // the vertex clusters; its sort workspace also serves the triangle sorts
+    size_t vclu, used, coff;                                           // per vertex
     size_t rec, recn;                                                  // the gathered records (written by dvs_mesh_decimate_write)
     size_t w[3], tkey[2], tval[2], keep, toff, bsum_t;                 // per triangle
     size_t block, total;
 };
 DecLayout dec_layout(uint32_t nv, uint32_t nt) {
     DecLayout L{};
-    const size_t v = nv ? nv : 1, t = nt ? nt : 1, big = v > t ? v : t;
-    size_t o = 0;
-    auto part = [&o](size_t bytes) { const size_t at = o; o = dvs_align256(o + bytes); return at; };
-    L.sort_ws = part(dvs_pair_sort_ws_bytes((uint64_t)big));
-    for (int k = 0; k < 2; ++k) { L.vkey[k] = part(v * 4); L.vval[k] = part(v * 4); }
-    L.cex = part(v * 4);
-    L.bsum_v = part(((v + DVS_SCAN_TILE - 1) / DVS_SCAN_TILE) * 4);
-    L.vclu = part(v * 4);
-    L.cstart = part((v + 1) * 4);
-    L.used = part(v);
-    L.coff = part(v * 4);
-    L.rec = part(v * 16);
-    L.recn = part(v * 16);
-    for (int k = 0; k < 3; ++k) L.w[k] = part(t * 4);
-    for (int k = 0; k < 2; ++k) { L.tkey[k] = part(t * 4); L.tval[k] = part(t * 4); }
-    L.keep = part(t);
-    L.toff = part(t * 4);
-    L.bsum_t = part(((t + DVS_SCAN_TILE - 1) / DVS_SCAN_TILE) * 4);
-    L.block = part(sizeof(DecBlock));
+    const size_t v = nv ? nv : 1, t = nt ? nt : 1;
+    L.c = dvs_cluster_layout(v, t);
+    size_t o = L.c.end;
+    L.vclu = dvs_carve(o, v * 4);
+    L.used = dvs_carve(o, v);
+    L.coff = dvs_carve(o, v * 4);
+    L.rec = dvs_carve(o, v * 16);
+    L.recn = dvs_carve(o, v * 16);
+    for (int k = 0; k < 3; ++k) L.w[k] = dvs_carve(o, t * 4);
+    for (int k = 0; k < 2; ++k) { L.tkey[k] = dvs_carve(o, t * 4); L.tval[k] = dvs_carve(o, t * 4); }
+    L.keep = dvs_carve(o, t);
+    L.toff = dvs_carve(o, t * 4);
+    L.bsum_t = dvs_carve(o, ((t + DVS_SCAN_TILE - 1) / DVS_SCAN_TILE) * 4);
+    L.block = dvs_carve(o, sizeof(DecBlock));
     L.total = o;
     return L;
-}
-
-// the cell of a coordinate along one axis: one subtraction, one IEEE division; !(q >= 0) also catches NaN
-__device__ __forceinline__ uint32_t dec_axis(float x, float o, float cell, uint32_t n) {
-    const float q = (x - o) / cell;
-    if (!(q >= 0.0f)) return 0u;
-    if (q >= (float)n) return n - 1u;
-    return (uint32_t)q;
 }
 
 __global__ void k_dec_init(DecBlock* blk) {
@@ -95,32 +74,11 @@ __global__ void k_dec_init(DecBlock* blk) {
     blk->n_degenerate = 0; blk->n_duplicate = 0; blk->n_bad = 0;
 }
 __global__ void __launch_bounds__(MB)
-k_dec_keys(uint32_t nv, const float* __restrict__ xyz, DecLattice g, uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
+k_dec_keys(uint32_t nv, const float* __restrict__ xyz, DvsCellLattice g, uint32_t* __restrict__ key, uint32_t* __restrict__ val) {
     const size_t v = (size_t)blockIdx.x * MB + threadIdx.x;
     if (v >= nv) return;
-    const uint32_t ix = dec_axis(xyz[3 * v], g.o[0], g.cell, g.n[0]);
-    const uint32_t iy = dec_axis(xyz[3 * v + 1], g.o[1], g.cell, g.n[1]);
-    const uint32_t iz = dec_axis(xyz[3 * v + 2], g.o[2], g.cell, g.n[2]);
-    key[v] = (iz * g.n[1] + iy) * g.n[0] + ix;                          // < 1024^3 = 2^30
+    key[v] = dvs_cell_key(xyz[3 * v], xyz[3 * v + 1], xyz[3 * v + 2], g);
     val[v] = (uint32_t)v;
-}
-__global__ void __launch_bounds__(MB) k_dec_heads(uint32_t nv, const uint32_t* __restrict__ skey, uint32_t* __restrict__ head) {
-    const size_t i = (size_t)blockIdx.x * MB + threadIdx.x;
-    if (i >= nv) return;
-    head[i] = (i == 0 || skey[i] != skey[i - 1]) ? 1u : 0u;
-}
-// cex = the exclusive scan of the heads: a head's value is its cluster's number, a follower's is that number + 1
-__global__ void __launch_bounds__(MB)
-k_dec_assign(uint32_t nv, const uint32_t* __restrict__ skey, const uint32_t* __restrict__ sidx, const uint32_t* __restrict__ cex,
-             uint32_t* __restrict__ vclu, uint32_t* __restrict__ cstart) {
-    const size_t i = (size_t)blockIdx.x * MB + threadIdx.x;
-    if (i >= nv) return;
-    const bool head = i == 0 || skey[i] != skey[i - 1];
-    const uint32_t c = head ? cex[i] : cex[i] - 1u;                      // (a follower has a head before it: cex >= 1)
-    const uint32_t v = sidx[i];
-    if (v < nv) vclu[v] = c;                                             // (the sort permutes [0, nv): always true)
-    if (head) cstart[c] = (uint32_t)i;
-    if (i + 1 == nv) cstart[c + 1u] = nv;                               // c + 1 = n_clusters <= nv: inside the nv + 1 words
 }
 
 // One thread per triangle. No lane leaves early: the wave's leader adds the wave's counts.
@@ -218,11 +176,8 @@ k_dec_walk(uint32_t nv, const DecBlock* __restrict__ blk, const uint32_t* __rest
            const uint32_t* __restrict__ coff, const float4* __restrict__ rec, const float4* __restrict__ recn, float* __restrict__ out_xyz,
            uint8_t* __restrict__ out_rgb, float* __restrict__ out_normals) {
     const size_t c = (size_t)blockIdx.x * MB + threadIdx.x;
-    if (c >= nv || c >= blk->n_clusters || !used[c]) return;
-    const uint32_t first = cstart[c];
-    uint32_t end = cstart[c + 1];
-    if (end > nv) end = nv;                                              // the loop's bound comes from the input
-    if (first >= end) return;                                            // (never: a cluster has a member)
+    uint32_t first, end;
+    if (!dvs_cluster_run(c, nv, blk->n_clusters, cstart, &first, &end) || !used[c]) return;
     const size_t o = coff[c];                                            // < out_vertices
     float4 r = rec[first];
     float sx = r.x, sy = r.y, sz = r.z;
@@ -248,9 +203,7 @@ k_dec_walk(uint32_t nv, const DecBlock* __restrict__ blk, const uint32_t* __rest
             q = recn[m];
             nx = nx + q.x; ny = ny + q.y; nz = nz + q.z;
         }
-        const float l2 = (nx * nx + ny * ny) + nz * nz;
-        if (l2 < 1e-30f) { nx = ny = nz = 0.0f; }                      // the rule of dvs_mesh_extract_normals
-        else { const float len = sqrtf(l2); nx /= len; ny /= len; nz /= len; }
+        dvs_unit_or_zero(nx, ny, nz);
         out_normals[3 * o] = nx; out_normals[3 * o + 1] = ny; out_normals[3 * o + 2] = nz;
     }
 }
@@ -273,8 +226,8 @@ extern "C" size_t dvs_mesh_decimate_scratch_bytes(uint32_t n_vertices, uint32_t 
 
 extern "C" int dvs_mesh_decimate_count(void* stream, uint32_t n_vertices, const float* xyz, const uint32_t* tri, uint32_t n_triangles, const float origin[3],
                                        float cell, const int32_t ncell[3], void* scratch, dvs_mesh_decimate_info* info) {
-    if (!scratch || ((uintptr_t)scratch & 255u) || !info || !origin || !ncell || !(cell > 0.0f) || !std::isfinite(cell)) return DVS_ERR_INVALID;
-    for (int k = 0; k < 3; ++k) if (ncell[k] < 1 || ncell[k] > DVS_TSDF_MAX_DIM) return DVS_ERR_INVALID;
+    DvsCellLattice g;
+    if (!scratch || ((uintptr_t)scratch & 255u) || !info || !dvs_cell_lattice(origin, cell, ncell, &g)) return DVS_ERR_INVALID;
     if ((n_vertices > 0 && !xyz) || (n_triangles > 0 && !tri)) return DVS_ERR_INVALID;
     if (n_vertices > 0x7FFFFFFFu || n_triangles > 0x7FFFFFFFu) return DVS_ERR_CAPACITY;      // the sort counts in int
     *info = dvs_mesh_decimate_info{};
@@ -287,28 +240,13 @@ extern "C" int dvs_mesh_decimate_count(void* stream, uint32_t n_vertices, const 
     const DecLayout L = dec_layout(nv, nt);
     char* const base = (char*)scratch;
     DecBlock* const blk = (DecBlock*)(base + L.block);
-    const dim3 gv(mblocks(nv)), gt(mblocks(nt)), block(MB);
-    DecLattice g;
-    for (int k = 0; k < 3; ++k) { g.o[k] = origin[k]; g.n[k] = (uint32_t)ncell[k]; }
-    g.cell = cell;
+    const dim3 gv(dvs_blocks256(nv)), gt(dvs_blocks256(nt)), block(MB);
+    uint32_t *vclu = (uint32_t*)(base + L.vclu), *coff = (uint32_t*)(base + L.coff);
+    uint8_t* used = (uint8_t*)(base + L.used);
 
     hipLaunchKernelGGL(k_dec_init, dim3(1), dim3(1), 0, st, blk);
-    uint32_t* vkey[2] = {(uint32_t*)(base + L.vkey[0]), (uint32_t*)(base + L.vkey[1])};
-    uint32_t* vval[2] = {(uint32_t*)(base + L.vval[0]), (uint32_t*)(base + L.vval[1])};
-    hipLaunchKernelGGL(k_dec_keys, gv, block, 0, st, nv, xyz, g, vkey[0], vval[0]);
-    int vc = 0;
-    const DvsPairSortWs ws = dvs_pair_sort_ws_at(base + L.sort_ws);
-    if (dvs_launch_pair_sort(st, nv, vkey[0], vval[0], vkey[1], vval[1], 0, 30, ws, 0, &vc) != hipSuccess) return DVS_ERR_HIP;      // ballot ranking
-    // the write call looks for the sorted order in buffers 0 (where the four passes of 30 bits leave it)
-    if (vc != 0 && (hipMemcpyAsync(vkey[0], vkey[1], (size_t)nv * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-                    hipMemcpyAsync(vval[0], vval[1], (size_t)nv * 4, hipMemcpyDeviceToDevice, st) != hipSuccess))
-        return DVS_ERR_HIP;
-    const uint32_t *skey = vkey[0], *sidx = vval[0];
-    uint32_t *cex = (uint32_t*)(base + L.cex), *vclu = (uint32_t*)(base + L.vclu), *cstart = (uint32_t*)(base + L.cstart), *coff = (uint32_t*)(base + L.coff);
-    uint8_t* used = (uint8_t*)(base + L.used);
-    hipLaunchKernelGGL(k_dec_heads, gv, block, 0, st, nv, skey, cex);
-    if (dvs_launch_scan_u32(st, cex, nv, (uint32_t*)(base + L.bsum_v), &blk->n_clusters) != hipSuccess) return DVS_ERR_HIP;
-    hipLaunchKernelGGL(k_dec_assign, gv, block, 0, st, nv, skey, sidx, (const uint32_t*)cex, vclu, cstart);
+    hipLaunchKernelGGL(k_dec_keys, gv, block, 0, st, nv, xyz, g, (uint32_t*)(base + L.c.key[0]), (uint32_t*)(base + L.c.val[0]));
+    if (dvs_launch_cell_clusters(st, nv, 30, base, L.c, vclu, &blk->n_clusters) != hipSuccess) return DVS_ERR_HIP;
     hipLaunchKernelGGL(k_dec_zero_used, gv, block, 0, st, nv, used, coff);
 
     if (nt > 0) {
@@ -318,6 +256,7 @@ extern "C" int dvs_mesh_decimate_count(void* stream, uint32_t n_vertices, const 
         uint8_t* keep = (uint8_t*)(base + L.keep);
         uint32_t* toff = (uint32_t*)(base + L.toff);
         hipLaunchKernelGGL(k_dec_canon, gt, block, 0, st, nv, tri, nt, (const uint32_t*)vclu, w[0], w[1], w[2], tkey[0], tval[0], blk);
+        const DvsPairSortWs ws = dvs_pair_sort_ws_at(base + L.c.sort_ws);
         const uint64_t cells = (uint64_t)g.n[0] * g.n[1] * g.n[2];
         const int bits = bits_for((cells < nv ? cells : (uint64_t)nv) - 1u);          // 0 when there can be one cluster only: nothing to sort
         for (int word = 2; word >= 0; --word) {
@@ -331,11 +270,9 @@ extern "C" int dvs_mesh_decimate_count(void* stream, uint32_t n_vertices, const 
         if (dvs_launch_scan_u32(st, toff, nt, (uint32_t*)(base + L.bsum_t), &blk->out_triangles) != hipSuccess) return DVS_ERR_HIP;
         hipLaunchKernelGGL(k_dec_mark_used, gt, block, 0, st, nv, tri, nt, (const uint8_t*)keep, (const uint32_t*)vclu, used, coff);
     }
-    if (dvs_launch_scan_u32(st, coff, nv, (uint32_t*)(base + L.bsum_v), &blk->out_vertices) != hipSuccess) return DVS_ERR_HIP;
-    if (hipGetLastError() != hipSuccess) return DVS_ERR_HIP;
+    if (dvs_launch_scan_u32(st, coff, nv, (uint32_t*)(base + L.c.bsum), &blk->out_vertices) != hipSuccess) return DVS_ERR_HIP;
     DecBlock host{};
-    if (hipMemcpyAsync(&host, blk, sizeof host, hipMemcpyDeviceToHost, st) != hipSuccess) return DVS_ERR_HIP;
-    if (hipStreamSynchronize(st) != hipSuccess) return DVS_ERR_HIP;
+    if (dvs_fetch_block(st, blk, &host) != DVS_OK) return DVS_ERR_HIP;
     info->out_vertices = (uint32_t)host.out_vertices; info->out_triangles = (uint32_t)host.out_triangles; info->n_clusters = (uint32_t)host.n_clusters;
     info->n_degenerate = host.n_degenerate; info->n_duplicate = host.n_duplicate; info->n_bad = host.n_bad;
     return DVS_OK;
@@ -352,12 +289,12 @@ extern "C" int dvs_mesh_decimate_write(void* stream, uint32_t n_vertices, const 
     const DecLayout L = dec_layout(nv, nt);
     const char* const base = (const char*)scratch;
     const DecBlock* blk = (const DecBlock*)(base + L.block);
-    const uint32_t *sidx = (const uint32_t*)(base + L.vval[0]), *vclu = (const uint32_t*)(base + L.vclu), *cstart = (const uint32_t*)(base + L.cstart),
+    const uint32_t *sidx = (const uint32_t*)(base + L.c.val[0]), *vclu = (const uint32_t*)(base + L.vclu), *cstart = (const uint32_t*)(base + L.c.cstart),
                    *coff = (const uint32_t*)(base + L.coff), *toff = (const uint32_t*)(base + L.toff);
     const uint8_t *used = (const uint8_t*)(base + L.used), *keep = (const uint8_t*)(base + L.keep);
     // the record area is this call's workspace inside the scratch; what dvs_mesh_decimate_count left there is read only
     float4 *rec = (float4*)const_cast<char*>(base + L.rec), *recn = (float4*)const_cast<char*>(base + L.recn);
-    const dim3 gv(mblocks(nv)), gt(mblocks(nt)), block(MB);
+    const dim3 gv(dvs_blocks256(nv)), gt(dvs_blocks256(nt)), block(MB);
     hipLaunchKernelGGL(k_dec_gather, gv, block, 0, st, nv, sidx, xyz, rgb, normals, rec, recn);
     hipLaunchKernelGGL(k_dec_walk, gv, block, 0, st, nv, blk, cstart, used, coff, (const float4*)rec, (const float4*)recn, out_xyz, out_rgb, out_normals);
     hipLaunchKernelGGL(k_dec_write_t, gt, block, 0, st, nv, tri, nt, keep, toff, vclu, coff, out_tri);

@@ -2,7 +2,7 @@
 // reduce-then-scan. Block sums of DVS_SCAN_TILE elements, one workgroup scans the block sums with a 64-bit carry, the blocks rescan their
 // elements from their offset. The three kernels are templates over the word; the 32-bit instances are what they always were.
 // Integer only; no atomics: every output word has exactly one writer. Users: mesh.hip (vertex and triangle offsets), mesh_clean.hip
-// (compaction), mesh_decimate.hip (cluster numbers, compaction), region.hip (the middle step alone, over its own block counts),
+// (compaction), cell_cluster.hip (cluster numbers), mesh_decimate.hip and lod.hip (compaction), region.hip (the middle step alone, over its own block counts),
 // reduced.hip (degree block offsets; the int64 prefix sums of the codebooks' sorted values).
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -79,6 +79,41 @@ def test_finest_lattice_merges_nothing(gpu_device):
     assert info["out_triangles"] == len(canon) and info["n_duplicate"] == len(tri) - len(canon)
 
 
+def highest_cell_fixture():
+    """1024^3 cells of 2^-10 again (q is exact): 294 vertices alone in cells spread over the lattice, among them the two neighbours of the
+    last cell in key order, and six in the last cell (1023, 1023, 1023), whose key 2^30 - 1 has every one of the 30 bits set — one of the
+    six on the far corner, clamped into it. Every triangle has a corner in the last cell. -> xyz, rgb, nrm, tri, cell"""
+    rng = np.random.default_rng(4)
+    top = 1024 ** 3 - 1
+    cells = np.concatenate([rng.choice(top - 2, 292, replace=False), [top - 2, top - 1]])
+    ijk = np.stack([cells % 1024, (cells // 1024) % 1024, cells // (1024 * 1024)], -1)
+    cell = np.float32(2.0 ** -10)
+    inside = 1023 + np.array([[0.5, 0.5, 0.5], [0.125, 0.75, 0.25], [0.875, 0.0, 0.625], [0.0, 0.0, 0.0], [0.25, 0.5, 0.875]])
+    xyz = np.concatenate([(ijk + 0.5) * float(cell), inside * float(cell), [[1.0, 1.0, 1.0]]]).astype(np.float32)
+    perm = rng.permutation(300)                                          # the six are not the last six indices
+    xyz = xyz[perm]
+    members = np.nonzero(np.isin(perm, np.arange(294, 300)))[0]
+    others = np.nonzero(~np.isin(perm, np.arange(294, 300)))[0]
+    rgb = rng.integers(0, 256, (300, 3), dtype=np.uint8)
+    nrm = rng.standard_normal((300, 3)).astype(np.float32)
+    tri = np.stack([rng.choice(members, 200), rng.choice(others, 200), rng.choice(others, 200)], -1)
+    tri = np.concatenate([tri, tri[:20, [1, 2, 0]], [[members[0], members[1], others[0]]]]).astype(np.uint32)      # rotations repeat, one collapses
+    return xyz, rgb, nrm, tri, cell
+
+
+def test_highest_cell_is_a_cell(gpu_device):
+    """a full 30-bit key sits next to the bit that marks "no cell" in the shared clustering (cell_cluster.hip): the last cell's vertices
+    form a cluster like any other, the last one, and its triangles survive"""
+    xyz, rgb, nrm, tri, cell = highest_cell_fixture()
+    dims = (1024, 1024, 1024)
+    keys = DR.cell_keys(xyz, (0.0, 0.0, 0.0), cell, dims)
+    assert keys.max() == 2 ** 30 - 1 and (keys == 2 ** 30 - 1).sum() == 6 and len(np.unique(keys)) == 295
+    oxyz, _, otri, _, info = check(xyz, rgb, tri, (0.0, 0.0, 0.0), cell, dims, normals=nrm)
+    assert info["n_clusters"] == 295 and info["n_bad"] == 0 and info["n_degenerate"] >= 1 and info["n_duplicate"] >= 20
+    assert info["out_triangles"] > 100 and DR.cell_keys(oxyz, (0.0, 0.0, 0.0), cell, dims)[-1] == 2 ** 30 - 1
+    assert (otri == info["out_vertices"] - 1).any(1).all(), "every kept triangle has a corner in the last cluster"
+
+
 def test_member_order_of_a_large_cell(gpu_device):
     """3000 vertices in one cell whose fp32 sums depend on the order of the additions (magnitudes over five decades, mixed signs for the
     normals), walked by one lane; two more cells so that triangles survive"""
