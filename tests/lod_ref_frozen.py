@@ -1,4 +1,8 @@
-"""numpy restatement of the level-of-detail merge (include/dvs_export.h, last section; csrc/lod.hip).
+"""tests/lod_ref.py as it stood before merge() recorded its branch census and took a `defect`, kept verbatim below this paragraph and never
+edited: tests/test_lod_ref.py holds lod_ref.merge() to it byte for byte. (A digest of the outputs cannot do that: numpy's exp and log
+differ in the last place between CPUs, so the bytes are only comparable within one process.)
+
+numpy restatement of the level-of-detail merge (include/dvs_export.h, last section; csrc/lod.hip).
 
 merge(params, origin, cell, dims, D, dtype): dtype float64 is the yardstick; float32 restates the device's arithmetic operation by
 operation, in its order (the device's exp and log differ from numpy's by a few ulp, and nothing else). The cell of a splat and the
@@ -17,31 +21,15 @@ The definition. Lattice: origin o[3], cell edge c > 0, dims[3] (1..1024 each).
             scale' = log(lambda) / 2; rot' = the unit quaternion, w >= 0, of the eigenvectors made a proper rotation;
             alpha' = min(0.99, W / (lambda0 lambda1 lambda2)^(1/3)), stored as its logit
   output    clusters in ascending key
-
-The branch census. merge() records in info["census"], per multi-member cluster that is written (in output order, beside info["census_row"],
-the cluster's output row), which way the decomposition went: "quat" the branch of quat_of_rotation (0 trace, 1 V00, 2 V11, 3 V22), "flip"
-det < 0 negated the third column, "sweeps" the Jacobi sweeps started (0: Sigma' was diagonal as summed), "skips" the rotations passed over for an
-off-diagonal element of exactly 0, "floored" the eigenvalues the floor raised, "capped" alpha' was cut to 0.99, "negated" the quaternion
-came out with w < 0 and was negated. Recording changes no number.
-
-DEFECTS names deliberate departures from the definition, one at a time through merge(..., defect=name): what a subtly wrong kernel would
-compute. They exist for tests/test_lod_ref.py, which proves that the comparisons of tests/test_gpu_lod.py reject each of them.
 """
 import numpy as np
 
 SWEEPS = 12
 LIMIT = (0, 9, 24, 45)          # shN elements of the bands <= D
 KEYS = ("pos", "sh0", "shN", "opacity", "scale", "rot")
-DEFECTS = ("d1_zero_from_8",       # degree 1 keeps 8 shN elements, not 9
-           "d1_zero_from_12",      # degree 1 keeps chunk 2 whole
-           "strides_swapped",      # key = (iz dims_x + iy) dims_y + ix
-           "one_pass_moment",      # Sigma' = E[Sigma_i + p p^T] - mu mu^T
-           "no_alpha_cap",         # alpha' = W / (lambda0 lambda1 lambda2)^(1/3), uncut
-           "no_quat_sign",         # the quaternion is left with w < 0
-           "clamp_to_n")           # a coordinate at or past the far face gets the cell dims, not dims - 1
 
 
-def cell_keys(pos, origin, cell, dims, defect=None):
+def cell_keys(pos, origin, cell, dims):
     """float32 [n,3] -> int64 [n], the rule of dec_axis per axis"""
     pos = np.asarray(pos, np.float32).reshape(-1, 3)
     o = np.asarray(origin, np.float32)
@@ -54,11 +42,9 @@ def cell_keys(pos, origin, cell, dims, defect=None):
             inside = q >= 0                                  # (False for NaN)
             high = inside & (q >= np.float32(dims[a]))
             low = inside & ~high
-            i[high] = dims[a] if defect == "clamp_to_n" else dims[a] - 1
+            i[high] = dims[a] - 1
             i[low] = q[low].astype(np.int64)
             idx.append(i)
-    if defect == "strides_swapped":
-        return (idx[2] * int(dims[0]) + idx[1]) * int(dims[1]) + idx[0]
     return (idx[2] * int(dims[1]) + idx[1]) * int(dims[0]) + idx[0]
 
 
@@ -107,22 +93,18 @@ def sym3(c6):
     return np.array([[c6[0], c6[1], c6[2]], [c6[1], c6[3], c6[4]], [c6[2], c6[4], c6[5]]], c6.dtype)
 
 
-def jacobi(A, dt, census=None):
-    """cyclic Jacobi sweeps (0,1), (0,2), (1,2) -> (diagonal [3], V [3,3] with A = V diag V^T); census: a dict that receives "sweeps"
-    and "skips" (see the module's head)"""
+def jacobi(A, dt):
+    """cyclic Jacobi sweeps (0,1), (0,2), (1,2) -> (diagonal [3], V [3,3] with A = V diag V^T)"""
     A = np.array(A, dt)
     V = np.eye(3, dtype=dt)
     one, two = dt(1), dt(2)
-    sweeps = skips = 0
     with np.errstate(all="ignore"):
         for _ in range(SWEEPS):
             if A[0, 1] == 0 and A[0, 2] == 0 and A[1, 2] == 0:
                 break
-            sweeps += 1
             for p, q in ((0, 1), (0, 2), (1, 2)):
                 apq = A[p, q]
                 if apq == 0:
-                    skips += 1
                     continue
                 r = 3 - p - q
                 theta = (A[q, q] - A[p, p]) / (two * apq)
@@ -139,48 +121,35 @@ def jacobi(A, dt, census=None):
                     vp, vq = V[k, p], V[k, q]
                     V[k, p] = c * vp - s * vq
                     V[k, q] = s * vp + c * vq
-    if census is not None:
-        census["sweeps"], census["skips"] = sweeps, skips
     return np.array([A[0, 0], A[1, 1], A[2, 2]], dt), V
 
 
-def quat_of_rotation(V, dt, census=None, defect=None):
-    """the branch of the largest of trace, V00, V11, V22 (the first of equal ones), unit, w >= 0; census: a dict that receives "quat"
-    and "negated" (see the module's head)"""
+def quat_of_rotation(V, dt):
+    """the branch of the largest of trace, V00, V11, V22 (the first of equal ones), unit, w >= 0"""
     one, two, quarter = dt(1), dt(2), dt(0.25)
     tr = (V[0, 0] + V[1, 1]) + V[2, 2]
     if tr >= V[0, 0] and tr >= V[1, 1] and tr >= V[2, 2]:
-        branch = 0
         S = np.sqrt(tr + one) * two
         q = [quarter * S, (V[2, 1] - V[1, 2]) / S, (V[0, 2] - V[2, 0]) / S, (V[1, 0] - V[0, 1]) / S]
     elif V[0, 0] >= V[1, 1] and V[0, 0] >= V[2, 2]:
-        branch = 1
         S = np.sqrt(((one + V[0, 0]) - V[1, 1]) - V[2, 2]) * two
         q = [(V[2, 1] - V[1, 2]) / S, quarter * S, (V[0, 1] + V[1, 0]) / S, (V[0, 2] + V[2, 0]) / S]
     elif V[1, 1] >= V[2, 2]:
-        branch = 2
         S = np.sqrt(((one + V[1, 1]) - V[0, 0]) - V[2, 2]) * two
         q = [(V[0, 2] - V[2, 0]) / S, (V[0, 1] + V[1, 0]) / S, quarter * S, (V[1, 2] + V[2, 1]) / S]
     else:
-        branch = 3
         S = np.sqrt(((one + V[2, 2]) - V[0, 0]) - V[1, 1]) * two
         q = [(V[1, 0] - V[0, 1]) / S, (V[0, 2] + V[2, 0]) / S, (V[1, 2] + V[2, 1]) / S, quarter * S]
     q = np.array(q, dt)
     q = q / np.sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3])
-    if census is not None:
-        census["quat"], census["negated"] = branch, bool(q[0] < 0)
-    return -q if q[0] < 0 and defect != "no_quat_sign" else q
+    return -q if q[0] < 0 else q
 
 
-def merge(params, origin, cell, dims, D, dtype=np.float64, defect=None):
+def merge(params, origin, cell, dims, D, dtype=np.float64):
     """params: float32 arrays pos [n,3], sh0 [n,3], shN [n,45], opacity [n], scale [n,3], rot [n,4].
     -> (out, info): out = the six arrays of m rows in `dtype` (rows of single-member clusters hold the float32 inputs exactly);
     info = {"m", "n_dropped", "keys" [m], "single" bool [m], "members" list of index arrays, "cov" [m,6] = Sigma' before the
-    decomposition (NaN rows for single members), "W" [m], "census" and "census_row" (the module's head), "n_clusters" the clusters
-    before the weightless ones leave, "number" [m] the written clusters' numbers among those, "dead" the weightless ones' numbers,
-    "runs" [n_clusters, 2] every cluster's first and past-the-last position in the sorted order}.
-    defect: None, or one of DEFECTS."""
-    assert defect is None or defect in DEFECTS
+    decomposition (NaN rows for single members), "W" [m]}"""
     dt = np.dtype(dtype).type
     p32 = {k: np.asarray(params[k], np.float32) for k in KEYS}
     p32 = {"pos": p32["pos"].reshape(-1, 3), "sh0": p32["sh0"].reshape(-1, 3), "shN": p32["shN"].reshape(-1, 45), "opacity": p32["opacity"].reshape(-1),
@@ -188,7 +157,7 @@ def merge(params, origin, cell, dims, D, dtype=np.float64, defect=None):
     n = len(p32["opacity"])
     ok = finite_rows(p32)
     n_dropped = int((~ok).sum())
-    keys = cell_keys(p32["pos"], origin, cell, dims, defect)
+    keys = cell_keys(p32["pos"], origin, cell, dims)
     alive = np.nonzero(ok)[0]
     order = alive[np.argsort(keys[alive], kind="stable")]                    # by (key, splat index)
     skeys = keys[order]
@@ -199,11 +168,10 @@ def merge(params, origin, cell, dims, D, dtype=np.float64, defect=None):
     cov_all = np.zeros((n, 6), dt)
     cov_all[ok] = covariances(p32["scale"][ok], p32["rot"][ok], dt)
     rows = {k: [] for k in KEYS}
-    info = {"keys": [], "single": [], "members": [], "cov": [], "W": [], "census": [], "census_row": [], "number": [], "dead": []}
+    info = {"keys": [], "single": [], "members": [], "cov": [], "W": []}
     zero = dt(0)
-    limit = {"d1_zero_from_8": 8, "d1_zero_from_12": 12}.get(defect, LIMIT[D]) if D == 1 else LIMIT[D]
     with np.errstate(all="ignore"):
-        for number, (a, b) in enumerate(zip(starts, ends)):
+        for a, b in zip(starts, ends):
             mem = order[a:b]
             if len(mem) == 1:
                 v = mem[0]
@@ -218,7 +186,6 @@ def merge(params, origin, cell, dims, D, dtype=np.float64, defect=None):
                     s = s + w_all[v] * P["pos"][v]
                 if not W > 0:
                     n_dropped += len(mem)
-                    info["dead"].append(number)
                     continue
                 mu = s / W
                 c6 = np.zeros(6, dt)
@@ -230,42 +197,28 @@ def merge(params, origin, cell, dims, D, dtype=np.float64, defect=None):
                     a0 = a0 + w_all[v] * P["sh0"][v]
                     aN = aN + w_all[v] * P["shN"][v]
                 c6 = c6 / W
-                if defect == "one_pass_moment":
-                    c6 = np.zeros(6, dt)
-                    for v in mem:
-                        q = P["pos"][v]
-                        c6 = c6 + w_all[v] * (cov_all[v] + np.array([q[0] * q[0], q[0] * q[1], q[0] * q[2], q[1] * q[1], q[1] * q[2], q[2] * q[2]], dt))
-                    c6 = c6 / W - np.array([mu[0] * mu[0], mu[0] * mu[1], mu[0] * mu[2], mu[1] * mu[1], mu[1] * mu[2], mu[2] * mu[2]], dt)
-                census = {}
-                lam, V = jacobi(sym3(c6), dt, census)
+                lam, V = jacobi(sym3(c6), dt)
                 lmax = max(max(lam[0], lam[1]), lam[2])
-                census["floored"] = int((lam < dt(np.float32(1e-7)) * lmax).sum())
                 lam = np.maximum(lam, dt(np.float32(1e-7)) * lmax)
                 l = np.log(lam)
                 det = (V[0, 0] * (V[1, 1] * V[2, 2] - V[1, 2] * V[2, 1]) - V[0, 1] * (V[1, 0] * V[2, 2] - V[1, 2] * V[2, 0])) + \
                     V[0, 2] * (V[1, 0] * V[2, 1] - V[1, 1] * V[2, 0])
-                census["flip"] = bool(det < 0)
                 if det < 0:
                     V[:, 2] = -V[:, 2]
                 gm = np.exp(((l[0] + l[1]) + l[2]) / dt(3))
-                census["capped"] = bool(W / gm > dt(np.float32(0.99)))
-                alpha = W / gm if defect == "no_alpha_cap" else min(dt(np.float32(0.99)), W / gm)
+                alpha = min(dt(np.float32(0.99)), W / gm)
                 shN = aN / W
-                shN[limit:] = 0
+                shN[LIMIT[D]:] = 0
                 rows["pos"].append(mu); rows["sh0"].append(a0 / W); rows["shN"].append(shN)
                 rows["opacity"].append(np.log(alpha / (dt(1) - alpha)))
-                rows["scale"].append(dt(0.5) * l); rows["rot"].append(quat_of_rotation(V, dt, census, defect))
+                rows["scale"].append(dt(0.5) * l); rows["rot"].append(quat_of_rotation(V, dt))
                 info["cov"].append(c6); info["W"].append(W)
-                info["census"].append(census); info["census_row"].append(len(info["keys"]))
-            info["number"].append(number)
             info["keys"].append(int(skeys[a])); info["single"].append(len(mem) == 1); info["members"].append(mem)
     m = len(info["keys"])
     width = {"pos": 3, "sh0": 3, "shN": 45, "opacity": 0, "scale": 3, "rot": 4}
     out = {k: (np.array(rows[k], dt).reshape((m, width[k]) if width[k] else (m,))) for k in KEYS}
     info = {"m": m, "n_dropped": n_dropped, "keys": np.array(info["keys"], np.int64), "single": np.array(info["single"], bool),
-            "members": info["members"], "cov": np.array(info["cov"], dt).reshape(m, 6), "W": np.array(info["W"], dt),
-            "census": info["census"], "census_row": np.array(info["census_row"], np.int64), "n_clusters": len(starts),
-            "number": np.array(info["number"], np.int64), "dead": np.array(info["dead"], np.int64), "runs": np.stack([starts, ends], 1).astype(np.int64)}
+            "members": info["members"], "cov": np.array(info["cov"], dt).reshape(m, 6), "W": np.array(info["W"], dt)}
     return out, info
 
 

@@ -12,7 +12,36 @@ The bounds. The float32 restatement (numpy, the device's operation order) was ru
 cases below (both degrees); MEASURED_* are its worst errors, and the device is allowed 4 x that: its exp, log and division differ from
 numpy's by a few ulp and nothing else does. Units: mu relative to the largest coordinate of the finite centres (a mean's rounding
 error scales with the size of the coordinates, not with the cell); SH absolute (the rows are O(1)); alpha' absolute; geometry relative
-Frobenius."""
+Frobenius.
+
+The paths those cases left unrun (NEW_RUNS; tests/test_lod_ref.py proves on the CPU that each of lod_ref.DEFECTS passes the cases above
+and fails one of these):
+  n65, mix at D = 1, 2    D = 1 is the one degree whose limit (9) lies inside a 16-byte chunk: element 8 stays, 9 .. 11 are zeroed
+  box                     a lattice of 16 x 4 x 5 cells through lattice_for: the key's strides and the origin's axes are told apart
+  corners                 1024^3 cells: keys 0 and 2^30 - 1, the eight corner cells, cells one bit of one sort digit apart, six dropped
+                          splats; the 31-bit sort has set bits in every digit and a live key beside DVS_CELL_NONE in the top one
+  outside                 finite centres up to 12 cells beyond every face (clamped into the face cells and merged there), centres exactly
+                          on every interior face and on the far faces (float32 quotients that are integers, asserted where they are built)
+  many                    4918 splats, 4300 clusters, m = 4288: three scan tiles of clusters, twelve weightless clusters with numbers on
+                          both sides of 2048 and of 4096 (coff[c] != c across the tile edges), a live cluster across sorted position 2048
+  branches                eight built clusters, one per branch of k_lod_geometry that random splats do not take: Sigma' diagonal as summed
+                          (no sweep), a repeated eigenvalue off the axes, quaternion branches 2 and 3 with and without the w >= 0
+                          negation, alpha' capped and not, a floored eigenvalue that is 1e-16 of the largest in every precision
+facts() asserts on the float64 restatement that each case holds what it was built for, and test_every_branch_is_compared that over all
+runs every branch of lod_ref's census is taken by a compared cluster.
+
+Two branches no input reaches, and the kernel keeps them: `det < 0` (Jacobi starts from I and applies proper rotations) and quaternion
+branch 1 (V00 the largest of trace, V00, V11, V22). Searched with the float64 Jacobi of lod_ref over 1 200 000 symmetric positive definite
+matrices: M M^T of normal M; random eigenvectors with eigenvalues over eight decades; random eigenvectors with eigenvalues 1 + 1e-6 .. 1e-1;
+eigenvectors near signed permutations; the matrices found for branches 2 and 3 under all index permutations, perturbed; eigenvectors a
+rotation by 90 .. 180 degrees about an axis near x. Branch 0: 98 %, branch 3: 2 %, branch 2: 0.02 %, branch 1 and det < 0: never.
+BRANCH_MATRICES are four of the finds that keep their branch in float32 and under 1e-5 relative perturbations.
+
+The bounds of these cases follow the same protocol. Where the float32 restatement's worst error over a case stays at or below MEASURED_*
+the case has the bounds above (n65, mix, branches); where it does not, the case has its own figure for that quantity (MEASURED_OWN), 4 x
+again: alpha' at box 8.741e-07, corners 8.995e-07, outside 1.100e-06, many 1.127e-06; SH at many 6.407e-07; geometry at many 8.006e-07.
+(corners stays at 5.4e-07 in the geometry although its cells are 2^-9 wide at coordinates near 1: the error of mu shifts every p - mu
+alike, and sum w (p - mu) = 0 cancels it to first order in the two-pass moment.)"""
 import functools
 import numpy as np
 import pytest
@@ -23,6 +52,9 @@ pytestmark = pytest.mark.gpu
 # worst over the cases (mu at mix, the others at n2049 with its 461 merged clusters; the 300-member and the thin cluster stay below them)
 MEASURED_MU, MEASURED_SH, MEASURED_ALPHA, MEASURED_COV = 2.148e-07, 6.383e-07, 7.768e-07, 6.878e-07
 BOUND_MU, BOUND_SH, BOUND_ALPHA, BOUND_COV = 4 * MEASURED_MU, 4 * MEASURED_SH, 4 * MEASURED_ALPHA, 4 * MEASURED_COV
+# the cases added later whose float32 restatement errs more than that in some quantity: their own worst figures there, the ones above elsewhere
+MEASURED_OWN = {"box": (MEASURED_MU, MEASURED_SH, 8.741e-07, MEASURED_COV), "corners": (MEASURED_MU, MEASURED_SH, 8.995e-07, MEASURED_COV),
+                "outside": (MEASURED_MU, MEASURED_SH, 1.100e-06, MEASURED_COV), "many": (MEASURED_MU, 6.407e-07, 1.127e-06, 8.006e-07)}
 
 
 def random_splats(n, seed, lo=-1.0, hi=1.0):
@@ -79,16 +111,181 @@ def case(name):
         q0 = L.quat_of_rotation(R, np.float64)
         p["rot"] = ((q0 + r.normal(0, 1e-5, (40, 4))) * r.uniform(0.5, 2.0, (40, 1))).astype(np.float32)
         return p, lattice(-1.0, 1.0, 4)
+    if name == "box":                                                        # every axis its own count of cells
+        lo, hi = [-1.0, -0.2, 0.0], [1.0, 0.2, 0.55]
+        o, c, d = L.lattice_for(lo + hi, 16)
+        assert len(set(d)) == 3, d
+        p = random_splats(1500, 20)
+        p["pos"] = np.random.default_rng(21).uniform(lo, hi, (1500, 3)).astype(np.float32)
+        return p, (o, c, d)
+    if name == "corners":                                                    # 1024^3 cells of 2^-9: keys up to 2^30 - 1
+        o, c, d = np.full(3, -1.0, np.float32), np.float32(2.0 ** -9), [1024, 1024, 1024]
+        r = np.random.default_rng(22)
+        full = [(z << 20) | (y << 10) | x for z in (0, 1023) for y in (0, 1023) for x in (0, 1023)]          # the eight corner cells
+        digits = [CORNERS_BASE] + [CORNERS_BASE ^ (1 << b) for b in (3, 11, 19, 27)]                         # one bit of one 8-bit digit apart
+        want = np.repeat(full + digits, [2 + i % 4 for i in range(13)])                                     # 2 - 5 members each
+        idx = np.stack([want & 1023, (want >> 10) & 1023, want >> 20], 1)
+        grouped = (-1.0 + (idx + r.uniform(0.1, 0.9, idx.shape)) * 2.0 ** -9).astype(np.float32)
+        assert np.array_equal(L.cell_keys(grouped, o, c, d), want)
+        n = len(want) + 250 + 6
+        p = random_splats(n, 23)
+        p["pos"][:len(want)] = grouped                                       # (the 250 after them: anywhere, nearly all alone in their cells)
+        p["pos"][np.arange(n - 6, n), [0, 1, 2, 0, 1, 2]] = np.array([np.nan, np.inf, -np.inf, np.inf, np.nan, -np.inf], np.float32)
+        p["scale"] = r.normal(np.log(2.0 ** -9) - 1.5, 0.3, (n, 3)).astype(np.float32)                       # splats the size of their cell
+        return shuffled(p, 24), (o, c, d)
+    if name == "outside":                                                    # a lattice of 8 x 5 x 3 cells of 1/4; centres beyond it and on its faces
+        o, c, d = np.array([-1.0, -0.5, 0.25], np.float32), np.float32(0.25), [8, 5, 3]
+        r = np.random.default_rng(25)
+        top = o + np.array(d, np.float32) * c
+        inside = lambda k: r.uniform(o + 0.01, top - 0.01, (k, 3))
+        rows = [inside(300)]
+        faces = []
+        for a in range(3):
+            for off in (0.01, 0.6, 3.0):                                     # beyond the near and the far face: up to 12 cells away
+                lo_, hi_ = inside(2), inside(2)
+                lo_[:, a] = o[a] - off; hi_[:, a] = top[a] + off
+                rows += [lo_, hi_]
+            for k in range(1, d[a] + 1):                                     # on every interior face, and on the far face itself
+                f = inside(2)
+                f[:, a] = np.float32(o[a] + np.float32(k) * c)
+                faces.append(f)
+        corner = np.stack([top, top, o, o - 3.0, top + 3.0]).astype(np.float64)
+        faces.append(corner[:3])
+        pos = np.concatenate(rows + faces + [corner[3:]]).astype(np.float32)
+        nf = sum(len(f) for f in faces)
+        onface = pos[len(pos) - 2 - nf:len(pos) - 2]
+        q = (onface - o) / c                                                 # float32, as dvs_cell_axis forms it
+        assert q.dtype == np.float32 and ((q == np.round(q)).sum(1) >= 1).all() and (q[-3:] == np.round(q[-3:])).all()
+        p = random_splats(len(pos), 26)
+        p["pos"] = pos
+        return shuffled(p, 27), (o, c, d)
+    if name == "many":                                                       # 4300 clusters in 20 x 16 x 15 cells: three scan tiles of clusters
+        o, c, d = np.array([-2.0, 1.0, 0.5], np.float32), np.float32(0.1), [20, 16, 15]
+        r = np.random.default_rng(28)
+        cells = np.sort(r.choice(20 * 16 * 15, 4300, replace=False))         # cluster number -> cell key
+        count = 1 + np.bincount(r.integers(0, 4300, 600), minlength=4300)
+        count[list(MANY_DEAD)] = np.maximum(count[list(MANY_DEAD)], 2)
+        at = int(np.searchsorted(np.cumsum(count), 2047, side="right"))      # the cluster that holds sorted position 2047 ...
+        if np.cumsum(count)[at] == 2048:
+            count[at] += 1                                                   # ... reaches over 2048
+        want = np.repeat(cells, count)
+        idx = np.stack([want % 20, (want // 20) % 16, want // 320], 1)
+        pos = (o.astype(np.float64) + (idx + r.uniform(0.1, 0.9, idx.shape)) * 0.1).astype(np.float32)
+        assert np.array_equal(L.cell_keys(pos, o, c, d), want)
+        n = len(want) + 8
+        p = random_splats(n, 29)
+        p["pos"][:len(want)] = pos
+        p["pos"][-8:, 1] = np.nan
+        p["scale"] = r.normal(-4.0, 0.3, (n, 3)).astype(np.float32)
+        p["scale"][:len(want)][np.isin(want, cells[list(MANY_DEAD)])] = -1000.0                               # W = 0
+        return shuffled(p, 30), (o, c, d)
+    if name == "branches":                                                   # one built cluster per cell of 16 x 1 x 1, cell edge 1
+        o, c, d = np.zeros(3, np.float32), np.float32(1.0), [16, 1, 1]
+        r = np.random.default_rng(31)
+        pos, opacity, scale, rot = [], [], [], []
+        def cluster(cell, offsets, op, sc, q):
+            k = len(offsets)
+            pos.append(np.array([cell + 0.5, 0.5, 0.5]) + np.asarray(offsets, np.float64).reshape(k, 3))
+            opacity.append(np.broadcast_to(op, (k,))); scale.append(np.broadcast_to(sc, (k, 3))); rot.append(np.broadcast_to(q, (k, 4)))
+        # 0: Sigma' diagonal as summed. w = 1/2 exactly (opacity 0, scale 0), Sigma_i = I exactly, offsets +-1/8 and 0 on x: every product and sum is exact
+        cluster(0, [[-0.125, 0, 0], [0, 0, 0], [0.125, 0, 0]], 0.0, 0.0, [1, 0, 0, 0])
+        # 1: a repeated eigenvalue off the axes: isotropic members along (1, 1, 1); Sigma' = s^2 I + v (1,1,1)(1,1,1)^T
+        cluster(1, np.outer([-0.2, -0.05, 0.1, 0.25], [1, 1, 1]), r.normal(0, 1, 4), np.full((4, 3), -2.0) + r.normal(0, 0.2, (4, 1)), r.normal(0, 1, (4, 4)))
+        # 2 - 5: two coincident members of covariance A, for the A of BRANCH_MATRICES (found by search: see the module's head); alpha' = 0.09, not capped
+        for i, A in enumerate(BRANCH_MATRICES):
+            lam, Q = np.linalg.eigh(np.array(A))
+            Q = Q * np.sign(np.linalg.det(Q))
+            cluster(2 + i, np.zeros((2, 3)), [-3.0, -2.5], 0.5 * np.log(lam), L.quat_of_rotation(Q, np.float64))
+        # 6: alpha' capped: two coincident opaque members
+        cluster(6, np.zeros((2, 3)), 3.0, r.normal(-2, 0.3, 3), r.normal(0, 1, 4))
+        # 7: the floor raises lambda_z. Discs of sigma_z = e^-20 turned about z only, all at z = 1/2: Sigma' has xz = yz = 0 exactly and
+        # zz = e^-40 in every precision (mu_z = (W / 2) / W = 1/2: halving commutes with rounding), 1e-16 of the largest
+        ang = r.uniform(0, np.pi, 5)
+        cluster(7, np.c_[r.uniform(-0.3, 0.3, (5, 2)), np.zeros(5)], r.normal(-1, 0.5, 5), np.c_[r.normal(-3, 0.3, (5, 2)), np.full(5, -20.0)],
+                np.c_[np.cos(ang), np.zeros(5), np.zeros(5), np.sin(ang)])
+        pos = np.concatenate(pos)
+        p = random_splats(len(pos), 32)
+        p.update(pos=pos.astype(np.float32), opacity=np.concatenate(opacity).astype(np.float32), scale=np.concatenate(scale).astype(np.float32),
+                 rot=np.concatenate(rot).astype(np.float32))
+        return p, (o, c, d)
     raise KeyError(name)
 
 
+def shuffled(p, seed):
+    """the splats in a random order: the sort has work to do"""
+    perm = np.random.default_rng(seed).permutation(len(p["opacity"]))
+    return {k: np.ascontiguousarray(v[perm]) for k, v in p.items()}
+
+
 CASES = ("n1", "n64", "n65", "n2049", "one_cell", "alone", "mix", "thin")
+OLD_RUNS = tuple((name, D, lin, lout) for D, lin, lout in ((3, 0, 0), (0, 1, 1)) for name in CASES) + \
+    tuple((name, 3, lin, lout) for lin, lout in ((0, 1), (1, 0)) for name in ("n65", "mix"))
+NEW_RUNS = tuple(("n65", D, lin, lout) for D in (1, 2) for lin in (0, 1) for lout in (0, 1)) + \
+    tuple(("mix", D, l, l) for D in (1, 2) for l in (0, 1)) + \
+    (("box", 2, 0, 1), ("box", 1, 1, 0), ("corners", 3, 0, 0), ("corners", 1, 1, 1), ("outside", 3, 0, 0), ("outside", 2, 1, 1),
+     ("many", 1, 0, 1), ("many", 3, 1, 0), ("branches", 3, 0, 0), ("branches", 1, 1, 1))
+
+CORNERS_BASE = 0x2B4D96A7                                                    # a cell of `corners` with set and clear bits in each of the four digits
+MANY_DEAD = (5, 2040, 2046, 2047, 2048, 2049, 2055, 4090, 4095, 4096, 4097, 4100)        # the cluster numbers of `many` that are weightless
+# Sigma' whose Jacobi eigenvectors leave quat_of_rotation's first branch: (branch, negated for w >= 0) = (2, no), (2, yes), (3, no), (3, yes)
+BRANCH_MATRICES = (((0.508939, 0.128332, 0.127018), (0.128332, 0.381485, -0.273018), (0.127018, -0.273018, 0.587979)),
+                   ((1.532862, -0.634663, 0.764866), (-0.634663, 1.683177, -1.162123), (0.764866, -1.162123, 1.020918)),
+                   ((0.109757, -0.039863, 0.068991), (-0.039863, 0.109796, -0.129169), (0.068991, -0.129169, 0.278253)),
+                   ((3.586384, 1.315451, 1.177846), (1.315451, 4.465809, 3.932243), (1.177846, 3.932243, 5.603361)))
+# the census branches no input reaches (the module's head says what was searched)
+UNREACHABLE = ("flip", "quat 1")
+
+
+def census_of(info):
+    """the branches of lod_ref's census that the multi-member clusters of one reference run take -> {branch name: clusters}"""
+    C = info["census"]
+    count = lambda f: sum(1 for x in C if f(x))
+    got = {f"quat {b}": count(lambda x: x["quat"] == b) for b in range(4)}
+    got.update({"flip": count(lambda x: x["flip"]), "negated": count(lambda x: x["negated"]), "sweeps 0": count(lambda x: x["sweeps"] == 0),
+                "early break": count(lambda x: 0 < x["sweeps"] < L.SWEEPS), "apq 0 skipped": count(lambda x: x["skips"] > 0),
+                "floored": count(lambda x: x["floored"] > 0), "capped": count(lambda x: x["capped"]), "not capped": count(lambda x: not x["capped"])})
+    return got
+
+
+def facts(name, p, info):
+    """what a case was built for, asserted on the float64 restatement's own clustering"""
+    if name == "corners":
+        assert info["keys"].max() == 2 ** 30 - 1 and info["keys"].min() == 0 and info["n_dropped"] == 6
+        assert ((info["keys"] & 0x3F000000) == 0x3F000000).any(), "a live key with bits 24..29 set"
+        multi = set(info["keys"][~info["single"]].tolist())
+        assert all(CORNERS_BASE ^ bit in multi for bit in (0, 1 << 3, 1 << 11, 1 << 19, 1 << 27))
+    if name == "outside":
+        o, c, d = case(name)[1]
+        top, q = o + np.array(d, np.float32) * c, (p["pos"] - o) / c
+        merged = np.zeros(len(q), bool)
+        merged[np.concatenate([m for m, s in zip(info["members"], info["single"]) if not s])] = True
+        beyond, face = ((p["pos"] < o) | (p["pos"] >= top)).any(1), (q == np.round(q)).any(1)
+        assert (beyond & merged).sum() >= 40 and (face & merged).sum() >= 40, "the centres beyond the lattice and on faces merge with members of their cells"
+    if name == "many":
+        dead = info["dead"]
+        assert info["n_clusters"] == 4300 and info["m"] == 4300 - len(MANY_DEAD) > 2048 and sorted(dead.tolist()) == list(MANY_DEAD)
+        assert (dead < 2048).any() and ((dead >= 2048) & (dead < 4096)).any() and (dead >= 4096).any()
+        runs = info["runs"][info["number"][~info["single"]]]                 # the live multi-member clusters' sorted runs
+        assert ((runs[:, 0] < 2048) & (runs[:, 1] > 2048)).any(), "a live cluster's run lies across sorted position 2048"
+    if name == "branches":
+        want = [dict(sweeps=0, quat=0), dict(flip=False), dict(quat=2, negated=False), dict(quat=2, negated=True), dict(quat=3, negated=False),
+                dict(quat=3, negated=True), dict(capped=True), dict(floored=1, capped=False)]
+        o, c, d = case(name)[1]
+        for dtype in (np.float64, np.float32):                               # the float32 restatement goes the same way: no cluster sits on a branch's edge
+            C = info["census"] if dtype is np.float64 else L.merge(p, o, c, d, 3, dtype)[1]["census"]
+            assert len(C) == len(want) and all(C[i][k] == v for i, w in enumerate(want) for k, v in w.items()), C
+        assert not any(C[i]["capped"] for i in (2, 3, 4, 5))
+        lam = np.linalg.eigvalsh(L.sym3(info["cov"][1]))
+        assert lam[1] - lam[0] <= 1e-12 * lam[2] < 0.1 * (lam[2] - lam[1]) and abs(info["cov"][1][1]) > 0.1 * lam[2], "a repeated eigenvalue, not diagonal"
 
 
 @functools.lru_cache(maxsize=None)
 def reference(name, D, dtype=np.float64):
     p, (o, c, d) = case(name)
-    return L.merge(p, o, c, d, D, dtype)
+    out, info = L.merge(p, o, c, d, D, dtype)
+    if dtype is np.float64:
+        facts(name, p, info)
+    return out, info
 
 
 def extent(pos):
@@ -143,23 +340,38 @@ def run(dev, name, D, lin, lout):
 
 
 def check(dev, name, D, lin, lout):
-    ref, info = reference(name, D)
     got, counts = run(dev, name, D, lin, lout)
+    compare(name, D, got, counts, f"in={lin} out={lout}")
+
+
+def bounds(name):
+    """(mu, SH, alpha, cov): 4 x what the float32 restatement measured"""
+    return tuple(4 * e for e in MEASURED_OWN[name]) if name in MEASURED_OWN else (BOUND_MU, BOUND_SH, BOUND_ALPHA, BOUND_COV)
+
+
+def compare(name, D, got, counts, label=""):
+    """every comparison of a result (float32 rows, shN as [m,45]; counts = {"m", "n_dropped"}) with the float64 restatement of case
+    `name` at degree D: the device's result in check(), a restatement's in tests/test_lod_ref.py"""
+    ref, info = reference(name, D)
     assert counts == {"m": info["m"], "n_dropped": info["n_dropped"]}, (counts, info["m"], info["n_dropped"])
     p, (o, c, d) = case(name)
     single = info["single"]
+    B = bounds(name)
     for k in L.KEYS:                                                         # single members, bit for bit: this also pins the clusters' order
         want = ref[k][single].astype(np.float32)
         assert np.array_equal(got[k][single].view(np.uint32), want.view(np.uint32)), (name, k)
     assert np.array_equal(L.cell_keys(got["pos"], o, c, d), info["keys"]), "clusters in ascending cell key, each mean inside its cell"
     assert (got["shN"][~single][:, L.LIMIT[D]:] == 0).all(), "the bands above D are written as 0"
+    if D == 1 and not single.all():                                          # the one limit inside a 16-byte chunk: element 8 stays, 9 .. 11 go
+        assert (got["shN"][~single][:, 8] != 0).any() and (got["shN"][~single][:, 9:] == 0).all()
     assert np.isfinite(np.concatenate([got[k][~single].reshape(-1) for k in L.KEYS])).all()
     q = got["rot"][~single].astype(np.float64)
     assert (np.abs(np.linalg.norm(q, axis=1) - 1.0) <= 1e-6).all() and (q[:, 0] >= 0).all()
     e = errors(got, ref, info, extent(p["pos"]))
-    print(f"{name} D={D} in={lin} out={lout}: n={len(p['opacity'])} m={counts['m']} dropped={counts['n_dropped']} multi={int((~single).sum())} "
-          f"mu {e[0]:.3e} (<= {BOUND_MU:.3e}) sh {e[1]:.3e} (<= {BOUND_SH:.3e}) alpha {e[2]:.3e} (<= {BOUND_ALPHA:.3e}) cov {e[3]:.3e} (<= {BOUND_COV:.3e})")
-    assert e[0] <= BOUND_MU and e[1] <= BOUND_SH and e[2] <= BOUND_ALPHA and e[3] <= BOUND_COV, e
+    print(f"{name} D={D} {label}: n={len(p['opacity'])} m={counts['m']} dropped={counts['n_dropped']} multi={int((~single).sum())} "
+          f"mu {e[0]:.3e} (<= {B[0]:.3e}) sh {e[1]:.3e} (<= {B[1]:.3e}) alpha {e[2]:.3e} (<= {B[2]:.3e}) cov {e[3]:.3e} (<= {B[3]:.3e})")
+    assert e[0] <= B[0] and e[1] <= B[1] and e[2] <= B[2] and e[3] <= B[3], e
+    return e
 
 
 def test_no_splats(gpu_device):
@@ -180,6 +392,23 @@ def test_merge_matches_the_restatement(gpu_device, name, D, lin, lout):
 def test_layouts_cross(gpu_device, lin, lout):
     check(gpu_device, "n65", 3, lin, lout)
     check(gpu_device, "mix", 3, lin, lout)
+
+
+@pytest.mark.parametrize("name,D,lin,lout", NEW_RUNS)
+def test_untested_paths_match_the_restatement(gpu_device, name, D, lin, lout):
+    check(gpu_device, name, D, lin, lout)
+
+
+def test_every_branch_is_compared():
+    """Over the runs above (check() compares every multi-member cluster of a run's reference), each branch of the census is taken by some
+    cluster, except the ones no input reaches."""
+    total = {}
+    for name, D in sorted({(name, D) for name, D, _, _ in OLD_RUNS + NEW_RUNS}):
+        for k, v in census_of(reference(name, D)[1]).items():
+            total[k] = total.get(k, 0) + v
+    print(total)
+    assert all(total[k] == 0 for k in UNREACHABLE), total
+    assert all(v > 0 for k, v in total.items() if k not in UNREACHABLE), total
 
 
 def test_every_splat_alone_is_the_input_in_key_order(gpu_device):

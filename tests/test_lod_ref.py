@@ -1,9 +1,12 @@
 """The level-of-detail merge's restatement (tests/lod_ref.py) against what merging must do, without a GPU: a single member is the
 identity, two coincident copies merge to themselves with twice the weight, Sigma' is symmetric positive semi-definite, mu is the
 weighted centroid, and the written quaternion and scale reproduce Sigma'."""
+import functools
 import numpy as np
 import pytest
 import lod_ref as L
+import lod_ref_frozen as F
+import test_gpu_lod as G
 
 ORIGIN, CELL, DIMS = np.zeros(3, np.float32), np.float32(1.0), [4, 4, 4]
 
@@ -93,6 +96,58 @@ def test_dropped_splats_and_weightless_clusters():
     for dtype in (np.float32, np.float64):
         out, info = L.merge(p, ORIGIN, CELL, DIMS, 3, dtype)
         assert info["m"] == 0 and info["n_dropped"] == 12
+
+
+def test_the_census_changes_no_byte_of_the_earlier_cases():
+    for name in G.CASES:
+        p, (o, c, d) = G.case(name)
+        for D in (0, 3):
+            for dtype in (np.float32, np.float64):
+                (a, ia), (b, ib) = L.merge(p, o, c, d, D, dtype), F.merge(p, o, c, d, D, dtype)
+                for k in L.KEYS:
+                    assert a[k].dtype == b[k].dtype and a[k].tobytes() == b[k].tobytes(), (name, D, dtype, k)
+                for k in ("keys", "single", "cov", "W"):
+                    assert ia[k].tobytes() == ib[k].tobytes(), (name, D, dtype, k)
+                assert (ia["m"], ia["n_dropped"]) == (ib["m"], ib["n_dropped"])
+                assert len(ia["census"]) == int((~ia["single"]).sum()) and np.array_equal(ia["census_row"], np.nonzero(~ia["single"])[0])
+
+
+@functools.lru_cache(maxsize=None)
+def restated(name, D, defect):
+    """the float32 restatement of a case of tests/test_gpu_lod.py as the device's result would arrive: float32 rows and the two counts"""
+    p, (o, c, d) = G.case(name)
+    out, info = L.merge(p, o, c, d, D, np.float32, defect)
+    return {k: v.astype(np.float32) for k, v in out.items()}, {"m": info["m"], "n_dropped": info["n_dropped"]}
+
+
+def rejected(runs, defect):
+    """the (name, D) of `runs` at which test_gpu_lod.compare() refuses the float32 restatement with `defect`"""
+    bad = []
+    for name, D in sorted({(name, D) for name, D, _, _ in runs}):
+        try:
+            G.compare(name, D, *restated(name, D, defect))
+        except AssertionError:
+            bad.append((name, D))
+    return bad
+
+
+def test_the_float32_restatement_passes_every_comparison_of_the_gpu_test():
+    """(this is also where the bounds of test_gpu_lod come from: run with -s for the figures)"""
+    assert rejected(G.OLD_RUNS + G.NEW_RUNS, None) == []
+
+
+# the defects the earlier cases already refused, and one case that did (the one-pass moment: every earlier case with a merged cluster but
+# `thin`, whose cluster lies near the origin; the missing cap: the four with a capped cluster, n2049, one_cell, mix and thin)
+ALREADY_REJECTED = {"one_pass_moment": ("n2049", 3), "no_alpha_cap": ("one_cell", 3)}
+
+
+@pytest.mark.parametrize("defect", L.DEFECTS)
+def test_a_defect_is_rejected_by_a_new_case_and_was_not_before(defect):
+    """The gap the new cases close: each of lod_ref.DEFECTS went through every comparison of the earlier cases (but for the ones
+    ALREADY_REJECTED records), and is refused by at least one of the cases added with the census."""
+    assert rejected(G.NEW_RUNS, defect), defect
+    before = rejected(G.OLD_RUNS, defect)
+    assert ALREADY_REJECTED[defect] in before if defect in ALREADY_REJECTED else before == [], before
 
 
 def test_lattice_for():
