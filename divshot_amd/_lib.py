@@ -252,7 +252,16 @@ class UndistortDesc(C.Structure):      # dvs_undistort_desc
     _fields_ = [("width", C.c_int32), ("height", C.c_int32)] + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "ifx", "ify", "k1", "k2", "p1", "p2")]
 
 
+class PngDesc(C.Structure):            # dvs_png_desc
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("bit_depth", C.c_int32), ("color_type", C.c_int32), ("has_key", C.c_int32),
+                ("key", C.c_uint16 * 3), ("palette", (C.c_uint8 * 4) * 256)]
+
+
 _IMAGE_PROTOS = {
+    "dvs_png_band_rows": (C.c_int, []),
+    "dvs_png_filtered_bytes": (C.c_size_t, [C.POINTER(PngDesc)]),
+    "dvs_png_reconstruct": (C.c_int, [C.c_void_p, C.POINTER(PngDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_mask_combine": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dvs_jpeg_reconstruct": (C.c_int, [C.c_void_p, C.POINTER(JpegDesc), C.c_void_p, C.c_void_p]),
     "dvs_jpeg_encode_desc": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JpegDesc)]),
     "dvs_jpeg_encode_coef_count": (C.c_size_t, [C.POINTER(JpegDesc)]),
@@ -348,6 +357,14 @@ _JPEG_HOST_PROTOS = {
     "gstrain_jpeg_encoded_bytes": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gstrain_jpeg_encoded_free": (None, [C.c_void_p]),
 }
+# ... the PNG host half (png_io.hpp: chunk parsing and inflate, file -> filtered scanlines)
+_PNG_HOST_PROTOS = {
+    "gstrain_png_open": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_int]),
+    "gstrain_png_open_memory": (C.c_void_p, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_int]),
+    "gstrain_png_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gstrain_png_filtered": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gstrain_png_close": (None, [C.c_void_p]),
+}
 # ... and the mesh file writer (ply_io.hpp write_mesh_ply)
 _MESH_HOST_PROTOS = {
     "gstrain_write_mesh_ply": (C.c_int, [C.c_char_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64]),
@@ -369,7 +386,7 @@ def host_lib():
         if not os.path.exists(path):
             raise ImportError(f"{path} is missing: build it with `make -C divshot_amd/gstrain`")
         h = C.CDLL(path)
-        for name, (res, args) in list(_JPEG_HOST_PROTOS.items()) + list(_MESH_HOST_PROTOS.items()) + list(_FRAME_HOST_PROTOS.items()):
+        for name, (res, args) in list(_JPEG_HOST_PROTOS.items()) + list(_PNG_HOST_PROTOS.items()) + list(_MESH_HOST_PROTOS.items()) + list(_FRAME_HOST_PROTOS.items()):
             f = getattr(h, name)
             f.restype = res
             f.argtypes = args
@@ -444,6 +461,31 @@ def jpeg_encode_coefficients(desc, coef):
         return out.tobytes()
     finally:
         h.gstrain_jpeg_encoded_free(e)
+
+
+def png_decode_filtered(path):
+    """-> (PngDesc, uint8 numpy array): gspng::decode_filtered of a file (or of `bytes` in memory): the descriptor and the filtered
+    scanlines dvs_png_reconstruct takes; DvsError with the decoder's message when the file is refused"""
+    import numpy as np
+    h = host_lib()
+    err = C.create_string_buffer(1024)
+    if isinstance(path, (bytes, bytearray)):
+        f = h.gstrain_png_open_memory(bytes(path), len(path), err, 1024)
+    else:
+        f = h.gstrain_png_open(os.fsencode(path), err, 1024)
+    if not f:
+        raise DvsError(err.value.decode(errors="replace"))
+    try:
+        desc = PngDesc()
+        ints = (C.c_int32 * 5)()
+        size = C.c_uint64()
+        check(h.gstrain_png_info(f, ints, C.addressof(desc.key), C.addressof(desc.palette), C.byref(size)), "gstrain_png_info")
+        desc.width, desc.height, desc.bit_depth, desc.color_type, desc.has_key = list(ints)
+        filtered = np.zeros(size.value, np.uint8)
+        check(h.gstrain_png_filtered(f, filtered.ctypes.data), "gstrain_png_filtered")
+        return desc, filtered
+    finally:
+        h.gstrain_png_close(f)
 
 
 def jpeg_decode_coefficients(path):

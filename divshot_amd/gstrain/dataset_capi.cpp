@@ -87,6 +87,30 @@ GSDATA_API int gstrain_dataset_resolve_image(const void* h, uint64_t index, char
     *is_jpeg = jpeg ? 1 : 0;
     return 0;
 }
+// the same with the kind told apart: *kind = 0 PPM, 1 JPEG, 2 PNG (gsdata::resolve_image_kind)
+GSDATA_API int gstrain_dataset_resolve_image_kind(const void* h, uint64_t index, char* file, int file_cap, int* kind, char* err, int cap) {
+    const gsdata::Dataset* d = (const gsdata::Dataset*)h;
+    if (!d || !file || file_cap <= 0 || !kind) return report(false, "NULL argument", err, cap);
+    std::string path, msg;
+    gsdata::ImageKind k = gsdata::ImageKind::PPM;
+    if (!gsdata::resolve_image_kind(*d, (size_t)index, &path, &k, &msg)) return report(false, msg, err, cap);
+    if (path.size() + 1 > (size_t)file_cap) return report(false, "path longer than the buffer", err, cap);
+    memcpy(file, path.c_str(), path.size() + 1);
+    *kind = (int)k;
+    return 0;
+}
+// the mask file of image `index` under --useMask: *kind = 0 none (file = ""), 1 PGM, 2 PNG (gsdata::resolve_mask)
+GSDATA_API int gstrain_dataset_resolve_mask(const void* h, uint64_t index, char* file, int file_cap, int* kind, char* err, int cap) {
+    const gsdata::Dataset* d = (const gsdata::Dataset*)h;
+    if (!d || !file || file_cap <= 0 || !kind) return report(false, "NULL argument", err, cap);
+    std::string path, msg;
+    gsdata::MaskKind k = gsdata::MaskKind::NONE;
+    if (!gsdata::resolve_mask(*d, (size_t)index, &path, &k, &msg)) return report(false, msg, err, cap);
+    if (path.size() + 1 > (size_t)file_cap) return report(false, "path longer than the buffer", err, cap);
+    memcpy(file, path.c_str(), path.size() + 1);
+    *kind = (int)k;
+    return 0;
+}
 // rgb [H][W][3] of the image's camera size; mask (nullable) [H][W] in {0, 1}
 GSDATA_API int gstrain_dataset_read_image(const void* h, uint64_t index, uint8_t* rgb, uint8_t* mask, char* err, int cap) {
     const gsdata::Dataset* d = (const gsdata::Dataset*)h;

@@ -350,27 +350,53 @@ void rotation_of(const Image& im, float R[9]) {
     for (int k = 0; k < 9; ++k) R[k] = (float)r[k];
 }
 
-bool resolve_image(const Dataset& d, size_t index, std::string* file, bool* is_jpeg, std::string* err) {
+bool resolve_image_kind(const Dataset& d, size_t index, std::string* file, ImageKind* kind, std::string* err) {
     if (index >= d.images.size()) return fail(err, "image index out of range");
     const fs::path named = fs::path(d.root) / "images" / d.images[index].name;
-    *is_jpeg = false;
+    *kind = ImageKind::PPM;
     if (path_exists(named)) {
         std::string ext = named.extension().string();
         for (char& c : ext) c = (char)tolower((unsigned char)c);
-        *is_jpeg = ext == ".jpg" || ext == ".jpeg";
+        if (ext == ".jpg" || ext == ".jpeg") *kind = ImageKind::JPEG;
+        else if (ext == ".png") *kind = ImageKind::PNG;
         *file = named.string();
         return true;
     }
-    for (const char* ext : {".ppm", ".jpg", ".jpeg", ".JPG", ".JPEG"}) {
+    for (const char* ext : {".ppm", ".jpg", ".jpeg", ".JPG", ".JPEG", ".png", ".PNG"}) {
         fs::path alt = named;
         alt.replace_extension(ext);
-        if (path_exists(alt)) { *is_jpeg = ext[1] != 'p'; *file = alt.string(); return true; }
+        if (path_exists(alt)) { *kind = ext[1] == 'p' && ext[2] == 'p' ? ImageKind::PPM : (ext[1] == 'j' || ext[1] == 'J') ? ImageKind::JPEG : ImageKind::PNG; *file = alt.string(); return true; }
     }
     fs::path ppm = named;
     ppm.replace_extension(".ppm");
     const std::string stem = named.stem().string();
     return fail(err, "image " + named.string() + " does not exist (nor " + ppm.filename().string() + "); JPEG and PNG are not decoded here, convert the images to PPM" +
-                         " — nor is there a JPEG for the loader to decode under " + stem + ".jpg, " + stem + ".jpeg, " + stem + ".JPG or " + stem + ".JPEG");
+                         " — nor is there a JPEG for the loader to decode under " + stem + ".jpg, " + stem + ".jpeg, " + stem + ".JPG or " + stem + ".JPEG" +
+                         ", nor a PNG under " + stem + ".png or " + stem + ".PNG");
+}
+
+// the resolver from before PNG was read: a PNG file is reported as it always was, as a file that is not a JPEG
+bool resolve_image(const Dataset& d, size_t index, std::string* file, bool* is_jpeg, std::string* err) {
+    ImageKind kind = ImageKind::PPM;
+    *is_jpeg = false;
+    if (!resolve_image_kind(d, index, file, &kind, err)) return false;
+    *is_jpeg = kind == ImageKind::JPEG;
+    return true;
+}
+
+bool resolve_mask(const Dataset& d, size_t index, std::string* file, MaskKind* kind, std::string* err) {
+    if (index >= d.images.size()) return fail(err, "image index out of range");
+    const std::string& name = d.images[index].name;
+    fs::path pgm = fs::path(d.root) / "masks" / name, png = pgm;
+    pgm.replace_extension(".pgm");
+    png.replace_extension(".png");
+    const fs::path full = fs::path(d.root) / "masks" / (name + ".png");
+    file->clear();
+    *kind = MaskKind::NONE;
+    if (path_exists(pgm)) { *kind = MaskKind::PGM; *file = pgm.string(); }
+    else if (path_exists(png)) { *kind = MaskKind::PNG; *file = png.string(); }
+    else if (path_exists(full)) { *kind = MaskKind::PNG; *file = full.string(); }
+    return true;
 }
 
 bool read_image(const Dataset& d, size_t index, std::vector<uint8_t>* rgb, std::string* err) {

@@ -3,9 +3,11 @@
 // never an allocation sized by an unchecked count field.
 //   <path>/sparse/0/ (tried first) or <path>/sparse/: cameras, images, points3D as .bin (preferred) or .txt
 //   <path>/images/<name>: binary PPM (P6, maxval 255), or baseline JPEG when the file's extension is .jpg / .jpeg in any case (decoded by
-//                         jpeg_io.hpp + dvs_jpeg_reconstruct, not here); a name whose file is absent is retried with its extension replaced
-//                         by .ppm, then .jpg, .jpeg, .JPG, .JPEG
-//   <path>/masks/<stem>.pgm (P5, maxval 255): > 127 is trainable; a missing file means all ones
+//                         jpeg_io.hpp + dvs_jpeg_reconstruct, not here), or PNG when it is .png in any case (png_io.hpp +
+//                         dvs_png_reconstruct, not here); a name whose file is absent is retried with its extension replaced
+//                         by .ppm, then .jpg, .jpeg, .JPG, .JPEG, .png, .PNG
+//   <path>/masks/<stem>.pgm (P5, maxval 255): > 127 is trainable; then masks/<stem>.png, then masks/<image name>.png (gray or gray+alpha,
+//                         read by the trainer's loader, not here); no file means all ones
 // Camera models: SIMPLE_PINHOLE and PINHOLE by default — anything else is refused with the hint to undistort the capture first (the
 // lineage's own requirement). With ReadOptions::accept_distorted also SIMPLE_RADIAL, RADIAL and OPENCV, whose coefficients come back
 // in Camera::dist: the trainer's loader undistorts their views on the device (include/dvs_image.h: dvs_undistort_view). The fisheye
@@ -53,6 +55,14 @@ bool read_dataset(const std::string& path, const ReadOptions& opt, Dataset* out,
 // the file of image `index` and whether it is a JPEG: an existing <name> is a JPEG by its extension (.jpg / .jpeg, any case) and a PPM
 // otherwise; an absent one is retried as <stem>.ppm, then <stem>.jpg, .jpeg, .JPG, .JPEG
 bool resolve_image(const Dataset& d, size_t index, std::string* file, bool* is_jpeg, std::string* err);
+// the same with PNG told apart (resolve_image is a wrapper over this one and calls a PNG "not a JPEG", as it always did): an existing
+// <name> is a PNG when its extension is .png in any case; an absent one is retried in the order above, then as <stem>.png, <stem>.PNG
+enum class ImageKind { PPM = 0, JPEG = 1, PNG = 2 };
+bool resolve_image_kind(const Dataset& d, size_t index, std::string* file, ImageKind* kind, std::string* err);
+// the mask file of image `index`, the first that exists of masks/<stem>.pgm, masks/<stem>.png, masks/<image name>.png (COLMAP's own
+// convention); NONE with an empty `file` when there is none, which means all ones
+enum class MaskKind { NONE = 0, PGM = 1, PNG = 2 };
+bool resolve_mask(const Dataset& d, size_t index, std::string* file, MaskKind* kind, std::string* err);
 // image `index` as interleaved 8-bit RGB [H][W][3]; its size must equal its camera's (PPM only: <name>, else <stem>.ppm)
 bool read_image(const Dataset& d, size_t index, std::vector<uint8_t>* rgb, std::string* err);
 // its mask as [H][W] bytes in {0, 1}; all ones when <root>/masks/<stem>.pgm does not exist

@@ -4,6 +4,7 @@
 #include <mutex>
 #include <thread>
 #include "jpeg_io.hpp"
+#include "png_io.hpp"
 #include "../../include/dvs_image.h"
 
 namespace {
@@ -12,16 +13,18 @@ __global__ void k_pack_u8(const float* __restrict__ src, uint8_t* __restrict__ d
     if (i < n) dst[i] = (uint8_t)fminf(255.f, fmaxf(0.f, rintf(src[i] * 255.f)));
 }
 
-// Host threads that entropy-decode the JPEG images of a capture ahead of the loader: entropy decoding is the serial cost of a JPEG, so up
-// to `threads` files are decoded at once, never more than `window` images beyond the one the loader has taken (the memory held is
-// bounded by the window, not by the capture). take() hands the images out strictly in order, so nothing depends on the thread count.
-class JpegAhead {
+// Host threads that run the serial half of the compressed files of a capture ahead of the loader: entropy decoding is the serial cost of
+// a JPEG and inflate that of a PNG (pictures and masks alike), so up to `threads` files are decoded at once, never more than `window`
+// files beyond the one the loader has taken (the memory held is bounded by the window, not by the capture). take() hands the files out
+// strictly in order, so nothing depends on the thread count.
+class DecodeAhead {
 public:
-    struct Result { gsjpeg::Frame frame; std::string err; bool ok = false, done = false; };
-    JpegAhead(std::vector<std::string> files, int threads) : files_(std::move(files)), slots_(files_.size()), window_(2 * (size_t)threads) {
-        for (int t = 0; t < threads && (size_t)t < files_.size(); ++t) workers_.emplace_back([this] { work(); });
+    struct Job { std::string file; bool png = false; };
+    struct Result { gsjpeg::Frame frame; gspng::Frame png; std::string err; bool ok = false, done = false; };
+    DecodeAhead(std::vector<Job> jobs, int threads) : jobs_(std::move(jobs)), slots_(jobs_.size()), window_(2 * (size_t)threads) {
+        for (int t = 0; t < threads && (size_t)t < jobs_.size(); ++t) workers_.emplace_back([this] { work(); });
     }
-    ~JpegAhead() {
+    ~DecodeAhead() {
         { std::lock_guard<std::mutex> lock(m_); stop_ = true; }
         cv_.notify_all();
         for (std::thread& t : workers_) t.join();
@@ -36,44 +39,55 @@ public:
         cv_.notify_all();
         return r;
     }
-    double wall_ms() {                                       // wall time during which at least one thread was decoding: waits on a full window are not in it
+    const std::string& file(size_t i) const { return jobs_[i].file; }
+    double wall_ms(bool png) {                               // wall time during which at least one thread was decoding a file of that format: waits on a full window are not in it
         std::lock_guard<std::mutex> lock(m_);
-        return busy_ms_;
+        return busy_ms_[png ? 1 : 0];
     }
 
 private:
     void work() {
         for (;;) {
             size_t i;
+            int k;
             {
                 std::unique_lock<std::mutex> lock(m_);
-                cv_.wait(lock, [&] { return stop_ || next_ >= files_.size() || next_ < taken_ + window_; });
-                if (stop_ || next_ >= files_.size()) return;
+                cv_.wait(lock, [&] { return stop_ || next_ >= jobs_.size() || next_ < taken_ + window_; });
+                if (stop_ || next_ >= jobs_.size()) return;
                 i = next_++;
-                if (busy_++ == 0) busy_since_ = std::chrono::steady_clock::now();
+                k = jobs_[i].png ? 1 : 0;
+                if (busy_[k]++ == 0) busy_since_[k] = std::chrono::steady_clock::now();
             }
             Result r;
-            r.ok = gsjpeg::decode_coefficients(files_[i], &r.frame, &r.err);
+            r.ok = k ? gspng::decode_filtered(jobs_[i].file, &r.png, &r.err) : gsjpeg::decode_coefficients(jobs_[i].file, &r.frame, &r.err);
             r.done = true;
             {
                 std::lock_guard<std::mutex> lock(m_);
                 slots_[i] = std::move(r);
-                if (--busy_ == 0) busy_ms_ += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - busy_since_).count();
+                if (--busy_[k] == 0) busy_ms_[k] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - busy_since_[k]).count();
             }
             cv_.notify_all();
         }
     }
-    std::vector<std::string> files_;
+    const std::vector<Job> jobs_;
     std::vector<Result> slots_;
     size_t window_, next_ = 0, taken_ = 0;
     bool stop_ = false;
-    int busy_ = 0;                                           // threads inside a decode
-    double busy_ms_ = 0;
-    std::chrono::steady_clock::time_point busy_since_;
+    int busy_[2] = {0, 0};                                   // threads inside a decode, per format (0 JPEG, 1 PNG)
+    double busy_ms_[2] = {0, 0};
+    std::chrono::steady_clock::time_point busy_since_[2];
     std::mutex m_;
     std::condition_variable cv_;
     std::vector<std::thread> workers_;
 };
+
+dvs_png_desc png_desc_of(const gspng::Frame& f) {
+    dvs_png_desc d{};
+    d.width = f.width; d.height = f.height; d.bit_depth = f.bit_depth; d.color_type = f.color_type; d.has_key = f.has_key ? 1 : 0;
+    for (int k = 0; k < 3; ++k) d.key[k] = f.key[k];
+    memcpy(d.palette, f.palette, sizeof d.palette);
+    return d;
+}
 
 struct Lcg {       // tiny deterministic noise source for the synthetic initialisation
     uint64_t s;
@@ -316,9 +330,11 @@ bool GaussianTrainerScene::Impl::load_synthetic(const std::string& spec_str) {
     return true;
 }
 
-// A capture directory: a COLMAP sparse model and its images, binary PPM or baseline JPEG (dataset_io.hpp). A JPEG is entropy-decoded
-// on the host (jpeg_io.hpp, ahead of the loop by JpegAhead) and reconstructed on the device (dvs_jpeg_reconstruct) into the same planar
-// bytes a PPM is uploaded as. The view of a SIMPLE_RADIAL / RADIAL / OPENCV camera is then remapped on the device into the view of the
+// A capture directory: a COLMAP sparse model and its images, binary PPM, baseline JPEG or PNG (dataset_io.hpp). A JPEG is entropy-decoded
+// on the host (jpeg_io.hpp, ahead of the loop by DecodeAhead) and reconstructed on the device (dvs_jpeg_reconstruct) into the same planar
+// bytes a PPM is uploaded as; a PNG is inflated on the host (png_io.hpp, by the same threads) and unfiltered and expanded on the device
+// (dvs_png_reconstruct) into those bytes too. Under useMask a PNG mask (masks/<stem>.png, masks/<name>.png; gray or gray+alpha) goes the
+// same way and a picture's alpha is ANDed into its mask on the device (dvs_mask_combine); without useMask the alpha is ignored. The view of a SIMPLE_RADIAL / RADIAL / OPENCV camera is then remapped on the device into the view of the
 // pinhole camera with the same fx, fy, cx, cy and size (dvs_undistort_view); the pixels without a source are blank and masked out, not
 // cropped, so a capture with one such camera carries a mask on every view. Everything after that is one path. The views go up as bytes and are box-filtered
 // on the device when maxImageWidth / maxImageHeight ask for it; the splats start from the sparse points (include/dvs_init.h).
@@ -371,27 +387,44 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
     const size_t P = (size_t)W * H, img = 3 * P;
     std::vector<uint8_t> px, planar, mk;
     std::vector<float> mkf;
-    // which file each image is read from; the JPEGs among them are decoded ahead by DVS_LOAD_THREADS host threads (default 8, 1..16:
-    // never sized from the machine's CPU count)
-    std::vector<std::string> jpeg_files, jpeg_names;
-    std::vector<char> is_jpeg(ds.images.size(), 0);
+    // which file each image, and under useMask its mask, is read from; the JPEGs and PNGs among them are decoded ahead by DVS_LOAD_THREADS
+    // host threads (default 8, 1..16: never sized from the machine's CPU count), in the order the loop below takes them
+    std::vector<DecodeAhead::Job> jobs;
+    std::vector<gsdata::ImageKind> kind(ds.images.size(), gsdata::ImageKind::PPM);
+    std::vector<gsdata::MaskKind> mask_kind(ds.images.size(), gsdata::MaskKind::NONE);
+    size_t n_jpeg = 0, n_png = 0, n_png_masks = 0, n_alpha = 0;
     for (size_t i = 0; i < ds.images.size(); ++i) {
         std::string file;
-        bool jpeg = false;
-        if (!gsdata::resolve_image(ds, i, &file, &jpeg, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-        is_jpeg[i] = jpeg ? 1 : 0;
-        if (jpeg) jpeg_files.push_back(file);
+        if (!gsdata::resolve_image_kind(ds, i, &file, &kind[i], &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
+        if (kind[i] == gsdata::ImageKind::JPEG) { jobs.push_back({file, false}); ++n_jpeg; }
+        if (kind[i] == gsdata::ImageKind::PNG) { jobs.push_back({file, true}); ++n_png; }
+        if (cfg.useMask) {
+            if (!gsdata::resolve_mask(ds, i, &file, &mask_kind[i], &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
+            if (mask_kind[i] == gsdata::MaskKind::PNG) { jobs.push_back({file, true}); ++n_png_masks; }
+        }
     }
-    jpeg_names = jpeg_files;
-    const size_t n_jpeg = jpeg_files.size();
     const int load_threads = std::max(1, std::min(env_int("DVS_LOAD_THREADS", 8), 16));
-    JpegAhead ahead(std::move(jpeg_files), load_threads);
+    DecodeAhead ahead(std::move(jobs), load_threads);
     Event ev_j0, ev_j1;
-    if (n_jpeg) {
+    if (n_jpeg + n_png + n_png_masks) {
         for (Event* e : {&ev_j0, &ev_j1}) { hipEvent_t ev = nullptr; HIP_OR_THROW(hipEventCreate(&ev)); e->reset(ev); }
     }
-    double recon_ms = 0;
-    size_t jpeg_at = 0;
+    double recon_ms = 0, png_ms = 0;
+    size_t job_at = 0;
+    // a PNG from the ahead-decoder onto the device: rgb (planar, 3 p0 bytes) and, when the file has one and `alpha` is given, its alpha plane
+    const auto png_to_device = [&](const gspng::Frame& f, uint8_t* rgb, DevBuf<uint8_t>* alpha) {
+        const dvs_png_desc desc = png_desc_of(f);
+        DevBuf<uint8_t> d_filtered(f.filtered.size());
+        HIP_OR_THROW(hipMemcpy(d_filtered.get(), f.filtered.data(), f.filtered.size(), hipMemcpyHostToDevice));
+        if (alpha && gspng::has_alpha(f)) alpha->alloc((size_t)f.width * f.height);
+        HIP_OR_THROW(hipEventRecord(ev_j0.get(), stream.get()));
+        DVS_OR_THROW(dvs_png_reconstruct(stream.get(), &desc, d_filtered.get(), rgb, alpha ? alpha->get() : nullptr));
+        HIP_OR_THROW(hipEventRecord(ev_j1.get(), stream.get()));
+        HIP_OR_THROW(hipEventSynchronize(ev_j1.get()));              // the scanlines are freed at the end of this scope
+        float ms = 0;
+        HIP_OR_THROW(hipEventElapsedTime(&ms, ev_j0.get(), ev_j1.get()));
+        png_ms += ms;
+    };
     // the undistortion's events and the count of pixels without a source, summed over the distorted views on the device
     Event ev_u0, ev_u1;
     DevBuf<uint32_t> d_invalid;
@@ -412,12 +445,13 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
         // bytes are the view as they are; 3. its mask. The owners free whatever an early return or a throw leaves behind.
         DevBuf<uint8_t> full8(3 * p0);
         DevBuf<float> t, mask;
-        if (is_jpeg[i]) {
-            JpegAhead::Result r = ahead.take(jpeg_at++);
+        DevBuf<uint8_t> alpha8;                                 // a PNG picture's alpha plane, kept only where a mask is asked for
+        if (kind[i] == gsdata::ImageKind::JPEG) {
+            DecodeAhead::Result r = ahead.take(job_at++);
             if (!r.ok) { logf_("load_train_data('%s'): %s", path.c_str(), r.err.c_str()); return false; }
             const gsjpeg::Frame& f = r.frame;
             if (f.width != w || f.height != h) {
-                logf_("load_train_data('%s'): %s is %dx%d but its camera %u is %dx%d", path.c_str(), jpeg_names[jpeg_at - 1].c_str(), f.width, f.height, c.id, w, h);
+                logf_("load_train_data('%s'): %s is %dx%d but its camera %u is %dx%d", path.c_str(), ahead.file(job_at - 1).c_str(), f.width, f.height, c.id, w, h);
                 return false;
             }
             dvs_jpeg_desc desc{};
@@ -433,11 +467,50 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
             float ms = 0;
             HIP_OR_THROW(hipEventElapsedTime(&ms, ev_j0.get(), ev_j1.get()));
             recon_ms += ms;
+        } else if (kind[i] == gsdata::ImageKind::PNG) {
+            DecodeAhead::Result r = ahead.take(job_at++);
+            if (!r.ok) { logf_("load_train_data('%s'): %s", path.c_str(), r.err.c_str()); return false; }
+            const gspng::Frame& f = r.png;
+            if (f.width != w || f.height != h) {
+                logf_("load_train_data('%s'): %s is %dx%d but its camera %u is %dx%d", path.c_str(), ahead.file(job_at - 1).c_str(), f.width, f.height, c.id, w, h);
+                return false;
+            }
+            if (gspng::has_alpha(f)) ++n_alpha;
+            png_to_device(f, full8.get(), cfg.useMask ? &alpha8 : nullptr);
         } else {
             if (!gsdata::read_image(ds, i, &px, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
             planar.resize(3 * p0);                              // the file is [H][W][3], the trainer's views are planar [3][H][W]
             for (size_t q = 0; q < p0; ++q) for (int k = 0; k < 3; ++k) planar[(size_t)k * p0 + q] = px[3 * q + k];
             HIP_OR_THROW(hipMemcpy(full8.get(), planar.data(), 3 * p0, hipMemcpyHostToDevice));
+        }
+        // under useMask, a PNG mask and / or a picture's alpha are combined on the device into mask8, bytes in {0, 1} (dvs_mask_combine);
+        // a PGM mask or none beside a picture without alpha stays on the path it always took
+        DevBuf<uint8_t> mask8;
+        if (cfg.useMask && (mask_kind[i] == gsdata::MaskKind::PNG || alpha8)) {
+            mask8.alloc(p0);
+            if (mask_kind[i] == gsdata::MaskKind::PNG) {
+                DecodeAhead::Result r = ahead.take(job_at++);
+                if (!r.ok) { logf_("load_train_data('%s'): %s", path.c_str(), r.err.c_str()); return false; }
+                const gspng::Frame& f = r.png;
+                const std::string& file = ahead.file(job_at - 1);
+                if (f.color_type != 0 && f.color_type != 4) {
+                    logf_("load_train_data('%s'): mask %s has colour type %d; a PNG mask must be grayscale or grayscale with alpha (types 0 and 4)", path.c_str(), file.c_str(), f.color_type);
+                    return false;
+                }
+                if (f.width != w || f.height != h) {
+                    logf_("load_train_data('%s'): %s is %dx%d but its camera is %dx%d", path.c_str(), file.c_str(), f.width, f.height, w, h);
+                    return false;
+                }
+                DevBuf<uint8_t> gray3(3 * p0), mask_alpha;
+                png_to_device(f, gray3.get(), &mask_alpha);
+                DVS_OR_THROW(dvs_mask_combine(stream.get(), p0, gray3.get(), mask_alpha.get(), nullptr, mask8.get(), nullptr));
+                if (alpha8) DVS_OR_THROW(dvs_mask_combine(stream.get(), p0, alpha8.get(), nullptr, mask8.get(), mask8.get(), nullptr));
+                HIP_OR_THROW(hipStreamSynchronize(stream.get()));    // gray3 and mask_alpha are freed at the end of this scope
+            } else {
+                if (!gsdata::read_mask(ds, i, &mk, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
+                HIP_OR_THROW(hipMemcpy(mask8.get(), mk.data(), p0, hipMemcpyHostToDevice));
+                DVS_OR_THROW(dvs_mask_combine(stream.get(), p0, alpha8.get(), nullptr, mask8.get(), mask8.get(), nullptr));
+            }
         }
         if (is_distorted(c)) {                                  // full8 := the pinhole camera's view; mask := valid and, with useMask, trainable
             const double prm[8] = {c.fx, c.fy, c.cx, c.cy, c.dist[0], c.dist[1], c.dist[2], c.dist[3]};      // the camera in OPENCV's order (absent coefficients are 0)
@@ -447,7 +520,8 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
                 return false;
             }
             DevBuf<uint8_t> pinhole(3 * p0), d_mk;
-            if (cfg.useMask) {
+            if (mask8) d_mk = std::move(mask8);
+            else if (cfg.useMask) {
                 if (!gsdata::read_mask(ds, i, &mk, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
                 d_mk.alloc(p0);
                 HIP_OR_THROW(hipMemcpy(d_mk.get(), mk.data(), p0, hipMemcpyHostToDevice));
@@ -469,7 +543,11 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
             DVS_OR_THROW(dvs_downsample_views(stream.get(), &dv, 1, 3, w, h, d, 1));
         }
         if (masked) {                                           // > 127 trains; a level mask keeps the box filter's fractional weights
-            if (!is_distorted(c)) {                             // (a distorted view's mask came out of the undistortion)
+            if (!is_distorted(c) && mask8) {                    // the device's mask as the floats a view keeps
+                mask.alloc(p0 * sizeof(float));
+                DVS_OR_THROW(dvs_mask_combine(stream.get(), p0, nullptr, nullptr, mask8.get(), nullptr, mask.get()));
+                HIP_OR_THROW(hipStreamSynchronize(stream.get()));    // mask8 is freed at the end of the iteration
+            } else if (!is_distorted(c)) {                      // (a distorted view's mask came out of the undistortion)
                 if (cfg.useMask) {
                     if (!gsdata::read_mask(ds, i, &mk, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
                     mkf.assign(mk.begin(), mk.end());
@@ -509,7 +587,12 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
               W0, H0, lvl, n_pts, ds.dropped);
         if (n_jpeg)
             logf_("dataset: jpeg: %zu of %zu images, entropy decode %.3f ms (host, %d threads, wall), reconstruction %.3f ms (device, events)", n_jpeg,
-                  ds.images.size(), ahead.wall_ms(), load_threads, recon_ms);
+                  ds.images.size(), ahead.wall_ms(false), load_threads, recon_ms);
+        if (n_png + n_png_masks)
+            logf_("dataset: png: %zu of %zu images, %zu masks, inflate %.3f ms (host, %d threads, wall), reconstruction %.3f ms (device, events)", n_png,
+                  ds.images.size(), n_png_masks, ahead.wall_ms(true), load_threads, png_ms);
+        if (n_alpha && !cfg.useMask)
+            logf_("dataset: png: %zu of %zu images have alpha; it is ignored without useMask (with it, alpha > 127 is ANDed into the mask)", n_alpha, ds.images.size());
         if (undistorted) {
             uint32_t invalid = 0;
             HIP_OR_THROW(hipMemcpy(&invalid, d_invalid.get(), sizeof invalid, hipMemcpyDeviceToHost));

@@ -1,7 +1,7 @@
 /*
  * dvs_image.h — C-ABI of the image work on the device: the parallel half of baseline JPEG decoding (below), the parallel half of
- * baseline JPEG encoding (dvs_jpeg_encode_views, after it) and the undistortion of a view taken through a distorted COLMAP camera
- * (dvs_undistort_view, at the end).
+ * baseline JPEG encoding (dvs_jpeg_encode_views, after it), the undistortion of a view taken through a distorted COLMAP camera
+ * (dvs_undistort_view) and the parallel half of PNG decoding with the mask rule (dvs_png_reconstruct, dvs_mask_combine, at the end).
  *
  * JPEG: quantised DCT coefficients (gstrain/jpeg_io.hpp decodes them on
  * the host) -> planar 8-bit RGB on the device, in one kernel: dequantisation, 8x8 inverse DCT, chroma upsampling, YCbCr -> RGB.
@@ -131,6 +131,52 @@ int dvs_undistort_desc_from_colmap(int model, const double* params, int width, i
  * DVS_ERR_INVALID for a NULL desc / src / dst, planes outside 1..4, a side outside 1..65536, dst overlapping src. */
 int dvs_undistort_view(void* stream, const dvs_undistort_desc* desc, int planes, const uint8_t* src, const uint8_t* mask_src,
                        uint8_t* dst, float* mask_dst, uint32_t* invalid_count);
+
+/* ---- PNG: filtered scanlines (gstrain/png_io.hpp inflates them on the host) -> planar 8-bit RGB and, when asked, alpha. Two launches:
+ * the five filters undone in place, then sample expansion. No scratch, no atomics: two calls on the same inputs return identical bytes.
+ * The result is defined bit for bit; tests/png_ref.py restates it:
+ *   stream       per row one filter byte and rowbytes = ceil(W * channels * depth / 8) bytes; channels = 1 (types 0, 3), 2 (4), 3 (2), 4 (6)
+ *   unfiltering  bpp = max(1, channels * depth / 8); x = the filtered byte, a = the byte bpp to the left, b = the byte above, c = the byte
+ *                above a; bytes left of the row and the row above the first read as 0; every sum is taken modulo 256:
+ *                0 None x | 1 Sub x + a | 2 Up x + b | 3 Average x + ((a + b) >> 1) (the 9-bit sum) |
+ *                4 Paeth x + (p = a + b - c; pa = |p - a|, pb = |p - b|, pc = |p - c|; a if pa <= pb and pa <= pc, else b if pb <= pc, else c)
+ *                a filter byte above 4 counts as None (the host half refuses such files)
+ *   samples      depths 1, 2, 4: packed MSB first, each row padded to a byte, scaled by 255, 85, 17; depth 16: big-endian,
+ *                byte = (v * 255 + 32895) >> 16; a palette index (type 3) goes through the 256-entry table
+ *   colour       gray is written to all three planes; colour is stored as it is in the file, not premultiplied
+ *   alpha        the alpha channel (types 4, 6), the palette table's alpha (type 3), or the colour key (types 0 and 2 with has_key):
+ *                0 where every sample equals its key at the file's full depth (the key's bits above the depth are ignored), else 255;
+ *                255 everywhere otherwise */
+#define DVS_PNG_BAND 512               /* rows of one band of the unfiltering wavefront (the kernel's workgroup size) */
+typedef struct dvs_png_desc {
+    int32_t width, height;          /* 1 .. 65500 */
+    int32_t bit_depth, color_type;  /* a legal PNG pair: type 0 at 1/2/4/8/16, 2 at 8/16, 3 at 1/2/4/8, 4 at 8/16, 6 at 8/16 */
+    int32_t has_key;                /* 0 or 1; 1 only with types 0 (key[0]) and 2 (key[0..2]) */
+    uint16_t key[3];
+    uint8_t palette[256][4];        /* RGBA, read for type 3 only */
+} dvs_png_desc;
+
+/* host only: the value of DVS_PNG_BAND the library was built with */
+int dvs_png_band_rows(void);
+
+/* host only: bytes of the filtered stream, height * (1 + rowbytes); 0 for a desc dvs_png_reconstruct refuses */
+size_t dvs_png_filtered_bytes(const dvs_png_desc* desc);
+
+/* rgb (and alpha) = the image of `filtered`. `desc` is a HOST pointer, read before the call returns; `filtered` is a DEVICE pointer to
+ * dvs_png_filtered_bytes(desc) bytes with no alignment requirement, OVERWRITTEN with the unfiltered scanlines (no scratch buffer is
+ * needed); `rgb` is a DEVICE pointer to planar [3][height][width] bytes, the layout dvs_jpeg_reconstruct writes; `alpha` is a nullable
+ * DEVICE pointer to [height][width] bytes; neither may overlap `filtered`. The same rgb with or without alpha.
+ * DVS_ERR_INVALID for a NULL desc, filtered or rgb, an illegal type / depth pair, or a desc that contradicts itself (a side outside
+ * 1..65500, has_key outside {0, 1} or set beside an alpha channel or a palette). */
+int dvs_png_reconstruct(void* stream, const dvs_png_desc* desc, uint8_t* filtered, uint8_t* rgb, uint8_t* alpha);
+
+/* ---- the mask rule on the device, so that decoded pixels never travel back to the host: m[i] = gray[i] > 127, AND alpha[i] > 127 when
+ * alpha is given, AND other[i] != 0 when other is given (a plane of bytes in {0, 1}, such as an earlier result); written as bytes in
+ * {0, 1} to out_u8 and as 0.0f / 1.0f to out_f32, whichever of the two is not NULL (the loader feeds the bytes to dvs_undistort_view
+ * and keeps the floats as the view's mask). With gray NULL and other given the call is the converter of a {0, 1} plane to those floats.
+ * All pointers are DEVICE pointers to n elements; out_u8 may be one of the inputs (element i is read before it is written).
+ * DVS_ERR_INVALID for gray and other both NULL, both outputs NULL, n = 0. */
+int dvs_mask_combine(void* stream, size_t n, const uint8_t* gray, const uint8_t* alpha, const uint8_t* other, uint8_t* out_u8, float* out_f32);
 
 #ifdef __cplusplus
 }
