@@ -262,6 +262,8 @@ _IMAGE_PROTOS = {
     "dvs_png_filtered_bytes": (C.c_size_t, [C.POINTER(PngDesc)]),
     "dvs_png_reconstruct": (C.c_int, [C.c_void_p, C.POINTER(PngDesc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "dvs_mask_combine": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_png_encode_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "dvs_png_encode_views": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int]),
     "dvs_jpeg_reconstruct": (C.c_int, [C.c_void_p, C.POINTER(JpegDesc), C.c_void_p, C.c_void_p]),
     "dvs_jpeg_encode_desc": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(JpegDesc)]),
     "dvs_jpeg_encode_coef_count": (C.c_size_t, [C.POINTER(JpegDesc)]),
@@ -364,6 +366,8 @@ _PNG_HOST_PROTOS = {
     "gstrain_png_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gstrain_png_filtered": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gstrain_png_close": (None, [C.c_void_p]),
+    "gstrain_png_write": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_int, C.c_void_p, C.c_uint64,
+                                    C.POINTER(C.c_uint64), C.c_char_p, C.c_int]),
 }
 # ... and the mesh file writer (ply_io.hpp write_mesh_ply)
 _MESH_HOST_PROTOS = {
@@ -486,6 +490,23 @@ def png_decode_filtered(path):
         return desc, filtered
     finally:
         h.gstrain_png_close(f)
+
+
+def png_write(width, height, bit_depth, color_type, filtered, level=6, text=None):
+    """-> bytes: gspng::write_png of a filtered stream (uint8 array or bytes; what dvs_png_encode_views writes) at zlib `level`, with one
+    tEXt chunk per (keyword, text) pair of `text` (str as Latin-1, or bytes); DvsError with the writer's message when it refuses"""
+    import numpy as np
+    h = host_lib()
+    stream = np.ascontiguousarray(np.frombuffer(bytes(filtered), np.uint8) if isinstance(filtered, (bytes, bytearray)) else filtered, np.uint8)
+    pairs = [tuple(s if isinstance(s, bytes) else s.encode("latin-1") for s in kv) for kv in (text or [])]
+    keys, texts = (C.c_char_p * max(1, len(pairs)))(*[k for k, _ in pairs]), (C.c_char_p * max(1, len(pairs)))(*[t for _, t in pairs])
+    ints = (C.c_int32 * 5)(int(width), int(height), int(bit_depth), int(color_type), int(level))
+    err, size = C.create_string_buffer(1024), C.c_uint64()
+    cap = stream.size + stream.size // 1000 + 4096 + sum(len(k) + len(t) + 16 for k, t in pairs)      # above deflate's worst case and the chunk frames
+    out = np.zeros(cap, np.uint8)
+    if h.gstrain_png_write(ints, stream.ctypes.data, stream.size, keys, texts, len(pairs), out.ctypes.data, cap, C.byref(size), err, 1024) != 0:
+        raise DvsError(err.value.decode(errors="replace"))
+    return out[:size.value].tobytes()
 
 
 def jpeg_decode_coefficients(path):

@@ -10,6 +10,7 @@
 #include <dlfcn.h>
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -50,6 +51,11 @@ static std::map<std::string, std::string> g_opts = {
     // extension of this build: every save also writes rendered views as JPEG files to <outputPath>_<it>_renders/: --renderViews test (the
     // held-out cameras of --eval) | train | all; --renderQuality 1..100; --renderSampling 420 | 444
     {"renderViews", ""}, {"renderQuality", "90"}, {"renderSampling", "420"},
+    // extension of this build: --renderFormat jpg | png writes those views as lossless PNG files instead; with png, --renderLayers
+    // color[,depth][,alpha] adds <name>_depth.png (16-bit gray: depth x --renderDepthScale, 0 = no depth) and <name>_alpha.png (8-bit
+    // gray). The config struct has no room left: when given they are handed to the plugin as DVS_RENDER_FORMAT / DVS_RENDER_LAYERS (the
+    // sum of 1 color, 2 depth, 4 alpha) / DVS_RENDER_DEPTH_SCALE.
+    {"renderFormat", "jpg"}, {"renderLayers", "color"}, {"renderDepthScale", "1000"},
     // the reference's config field meshResolution (its CLI has no flag for it): > 0 = the final save also writes <outputPath>_<it>_mesh.ply,
     // the surface extracted on a grid of that many voxels along its longest side (16..1024). --exportMesh keeps the reference's meaning.
     {"meshResolution", "0"},
@@ -135,6 +141,35 @@ int main(int argc, const char* argv[]) {
         const int f = digits ? atoi(v.c_str()) : -1;
         if (!(f == 0 || (f >= 2 && f <= 16))) { std::cout << "Command Line Error: --meshDecimate takes 0 (off) or an integer 2..16, not '" << v << "'\n"; return 1; }
         setenv("DVS_MESH_DECIMATE", v.c_str(), 1);                          // before the plugin is loaded
+    }
+    {
+        const std::string &fmt = g_opts["renderFormat"], &lay = g_opts["renderLayers"], &ds = g_opts["renderDepthScale"];
+        if (fmt != "jpg" && fmt != "png") { std::cout << "Command Line Error: --renderFormat takes jpg or png, not '" << fmt << "'\n"; return 1; }
+        int bits = 0;
+        bool ok = !lay.empty();
+        for (size_t at = 0; ok && at <= lay.size();) {                      // color[,depth][,alpha]: each name once, in this order, color first
+            const size_t comma = std::min(lay.find(',', at), lay.size());
+            const std::string name = lay.substr(at, comma - at);
+            const int bit = name == "color" ? 1 : name == "depth" ? 2 : name == "alpha" ? 4 : 0;
+            ok = bit > bits;                                                 // (unknown: 0; repeated or out of order: not above what came before)
+            bits |= bit;
+            at = comma + 1;
+        }
+        ok = ok && (bits & 1);
+        if (!ok) { std::cout << "Command Line Error: --renderLayers takes color[,depth][,alpha], not '" << lay << "'\n"; return 1; }
+        if (bits != 1 && fmt != "png") {
+            std::cout << "Command Line Error: --renderLayers takes depth or alpha only with --renderFormat png (JPEG files carry colour alone), not '" << lay << "'\n";
+            return 1;
+        }
+        char* end = nullptr;
+        const double s = strtod(ds.c_str(), &end);
+        if (ds.empty() || *end || !std::isfinite(s) || !(s > 0) || !std::isfinite((float)s) || !((float)s > 0.f)) {
+            std::cout << "Command Line Error: --renderDepthScale takes a finite number > 0, not '" << ds << "'\n";
+            return 1;
+        }
+        if (g_given.count("renderFormat")) setenv("DVS_RENDER_FORMAT", fmt.c_str(), 1);        // before the plugin is loaded
+        if (g_given.count("renderLayers")) setenv("DVS_RENDER_LAYERS", std::to_string(bits).c_str(), 1);
+        if (g_given.count("renderDepthScale")) setenv("DVS_RENDER_DEPTH_SCALE", ds.c_str(), 1);
     }
     for (const char* flag : {"exportLod", "lodResolution"}) {
         if (!g_given.count(flag)) continue;

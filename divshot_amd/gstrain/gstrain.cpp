@@ -392,6 +392,22 @@ bool GaussianTrainerScene::renderCameraToJpeg(int camera, const std::string& pat
     }
     return false;
 }
+bool GaussianTrainerScene::renderCameraToPng(int camera, const std::string& path, int layer) {
+    Impl& m = *impl_;
+    try {
+        if (!m.ctx || camera < 0 || camera >= (int)m.cams.size() || path.empty()) return false;
+        if (layer != Impl::LAYER_COLOR && layer != Impl::LAYER_DEPTH && layer != Impl::LAYER_ALPHA) return false;
+        HIP_OR_THROW(hipSetDevice(m.device));
+        std::vector<std::string> files[3];
+        files[layer == Impl::LAYER_COLOR ? 0 : layer == Impl::LAYER_DEPTH ? 1 : 2] = {path};
+        return m.render_to_png({camera}, files, nullptr);
+    } catch (const std::exception& e) {
+        logf_("renderCameraToPng(%d, '%s', %d) failed: %s", camera, path.c_str(), layer, e.what());
+    } catch (...) {
+        logf_("renderCameraToPng(%d, '%s', %d) failed: unknown exception", camera, path.c_str(), layer);
+    }
+    return false;
+}
 const std::vector<float>& GaussianTrainerScene::getGaussianPositionCpu() { impl_->fetch_host(); return impl_->host[P_POS]; }
 const std::vector<float>& GaussianTrainerScene::getGaussianSH0Cpu() { impl_->fetch_host(); return impl_->host[P_SH0]; }
 const std::vector<float>& GaussianTrainerScene::getGaussianSHNCpu() { impl_->fetch_host(); return impl_->host[P_SHN]; }

@@ -200,6 +200,89 @@ bool decode_filtered(const uint8_t* data, size_t size, const std::string& name, 
     return true;
 }
 
+namespace {
+void put_u32(std::string* s, uint32_t v) { const char b[4] = {(char)(v >> 24), (char)(v >> 16), (char)(v >> 8), (char)v}; s->append(b, 4); }
+// one chunk appended to *s: length, type, body, CRC over type and body
+void put_chunk(std::string* s, const char type[4], const uint8_t* body, size_t n) {
+    put_u32(s, (uint32_t)n);
+    const size_t at = s->size();
+    s->append(type, 4);
+    if (n) s->append((const char*)body, n);
+    put_u32(s, crc32((const uint8_t*)s->data() + at, n + 4));
+}
+bool keyword_ok(const std::string& k) {
+    if (k.empty() || k.size() > 79 || k.front() == ' ' || k.back() == ' ') return false;
+    for (size_t i = 0; i < k.size(); ++i) {
+        const uint8_t ch = (uint8_t)k[i];
+        if (!((ch >= 32 && ch <= 126) || ch >= 161)) return false;
+        if (ch == ' ' && k[i + 1] == ' ') return false;                      // (the last character is no space: i + 1 is inside)
+    }
+    return true;
+}
+}  // namespace
+
+bool write_png(int width, int height, int bit_depth, int color_type, const uint8_t* filtered, size_t size, int level, const TextPairs* text,
+               std::string* out, std::string* err) {
+    if (!out) return fail(err, "write_png: NULL output");
+    out->clear();
+    if (!filtered) return fail(err, "write_png: NULL filtered stream");
+    if (!legal_pair(color_type, bit_depth)) return fail(err, "write_png: illegal colour type / bit depth pair " + std::to_string(color_type) + " / " + std::to_string(bit_depth));
+    if (width < 1 || height < 1 || (uint32_t)width > kMaxSide || (uint32_t)height > kMaxSide)
+        return fail(err, "write_png: image size " + std::to_string(width) + "x" + std::to_string(height) + " (a side must be 1.." + std::to_string(kMaxSide) + ")");
+    const size_t rowbytes = row_bytes(width, bit_depth, color_type);
+    const uint64_t expected = (uint64_t)height * (1 + (uint64_t)rowbytes);
+    if ((uint64_t)size != expected) return fail(err, "write_png: a filtered stream of " + std::to_string(size) + " bytes, the image takes " + std::to_string(expected));
+    for (int y = 0; y < height; ++y)
+        if (filtered[(size_t)y * (1 + rowbytes)] > 4) return fail(err, "write_png: scanline " + std::to_string(y) + " has the unknown filter type " + std::to_string(filtered[(size_t)y * (1 + rowbytes)]));
+    if (level < 0 || level > 9) return fail(err, "write_png: zlib level " + std::to_string(level) + " (0..9)");
+    if (text)
+        for (const auto& kv : *text) {
+            if (!keyword_ok(kv.first)) return fail(err, "write_png: a tEXt keyword must be 1..79 Latin-1 characters without leading, trailing or doubled spaces");
+            if (kv.second.find('\0') != std::string::npos) return fail(err, "write_png: the tEXt text of '" + kv.first + "' holds a NUL");
+        }
+    const gszlib::Api& z = gszlib::api();
+    if (!z.err.empty()) return fail(err, "write_png: PNG needs zlib: " + z.err);
+
+    std::string file;
+    static const char kSig[8] = {(char)0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+    file.append(kSig, 8);
+    const uint32_t w = (uint32_t)width, h = (uint32_t)height;
+    const uint8_t ihdr[13] = {(uint8_t)(w >> 24), (uint8_t)(w >> 16), (uint8_t)(w >> 8), (uint8_t)w, (uint8_t)(h >> 24), (uint8_t)(h >> 16), (uint8_t)(h >> 8),
+                              (uint8_t)h, (uint8_t)bit_depth, (uint8_t)color_type, 0, 0, 0};
+    put_chunk(&file, "IHDR", ihdr, 13);
+    if (text)
+        for (const auto& kv : *text) {
+            std::string body = kv.first;
+            body.push_back('\0');
+            body += kv.second;
+            put_chunk(&file, "tEXt", (const uint8_t*)body.data(), body.size());
+        }
+    gszlib::Stream s;
+    memset(&s, 0, sizeof s);
+    if (z.deflateInit_(&s, level, z.zlibVersion(), (int)sizeof s) != gszlib::kOk) return fail(err, "write_png: deflateInit failed");
+    std::vector<uint8_t> part(kMaxIdat);                                     // one IDAT body at a time
+    size_t in_at = 0;
+    int rc = gszlib::kOk;
+    for (;;) {
+        const size_t in_part = std::min<size_t>(size - in_at, 1u << 30);
+        const bool last = in_at + in_part == size;
+        s.next_in = filtered + in_at; s.avail_in = (unsigned)in_part;
+        s.next_out = part.data(); s.avail_out = (unsigned)part.size();
+        rc = z.deflate(&s, last ? gszlib::kFinish : gszlib::kNoFlush);
+        in_at += in_part - s.avail_in;
+        const size_t made = part.size() - s.avail_out;
+        if (rc != gszlib::kOk && rc != gszlib::kStreamEnd && rc != gszlib::kBufError) break;
+        if (made) put_chunk(&file, "IDAT", part.data(), made);
+        if (rc == gszlib::kStreamEnd) break;
+        if (made == 0 && in_part - s.avail_in == 0) break;                   // no progress
+    }
+    z.deflateEnd(&s);
+    if (rc != gszlib::kStreamEnd) return fail(err, "write_png: deflate error " + std::to_string(rc));
+    put_chunk(&file, "IEND", nullptr, 0);
+    out->swap(file);
+    return true;
+}
+
 void unfilter_host(const Frame& f, uint8_t* filtered) {
     const size_t rb = row_bytes(f.width, f.bit_depth, f.color_type), stride = rb + 1;
     const size_t bpp = std::max<size_t>(1, (size_t)channels_of(f.color_type) * (size_t)f.bit_depth / 8);

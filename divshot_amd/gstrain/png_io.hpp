@@ -1,4 +1,4 @@
-// png_io.hpp — the serial half of PNG decoding: chunk parsing and inflate, file -> FILTERED scanlines (the inflated IDAT stream exactly
+// png_io.hpp — the serial halves of PNG decoding and (write_png, further down) encoding. Decoding: chunk parsing and inflate, file -> FILTERED scanlines (the inflated IDAT stream exactly
 // as stored: per row one filter byte and rowbytes = ceil(W * channels * depth / 8) bytes). Host only, no GPU dependency; a pure function
 // without mutable globals, so any number of threads may decode different files at once. The parallel half (the five filters, sample
 // expansion, palette, transparency) is dvs_png_reconstruct (include/dvs_image.h); tests/png_ref.py restates both.
@@ -19,6 +19,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace gspng {
@@ -43,6 +44,18 @@ bool has_alpha(const Frame& f);
 bool decode_filtered(const std::string& file, Frame* out, std::string* err);
 // the same over bytes already in memory; `name` prefixes the messages
 bool decode_filtered(const uint8_t* data, size_t size, const std::string& name, Frame* out, std::string* err);
+
+// The serial half of PNG ENCODING, the mirror image of decode_filtered: a filtered stream (what dvs_png_encode_views writes: per row one
+// filter byte 0..4 and rowbytes bytes) -> a whole PNG file in *out: the signature, IHDR, one tEXt chunk per (keyword, text) pair of
+// `text` (nullable), the zlib stream of `filtered` at `level` 0..9 in IDAT chunks of at most kMaxIdat bytes, IEND; CRCs from this
+// file's table, deflate through zlib_dl.hpp. A pure function without statics: any number of threads may write different files at once.
+// Refused with a message in *err and *out left empty: a NULL filtered or out, an illegal type / depth pair, a side outside 1..kMaxSide,
+// a size other than height * (1 + rowbytes), a filter byte above 4, a level outside 0..9, a keyword that is not 1..79 Latin-1
+// characters (32..126 and 161..255, no space at either end, no two spaces in a row) or a text with a NUL in it, zlib missing.
+constexpr size_t kMaxIdat = 1u << 20;
+using TextPairs = std::vector<std::pair<std::string, std::string>>;
+bool write_png(int width, int height, int bit_depth, int color_type, const uint8_t* filtered, size_t size, int level, const TextPairs* text,
+               std::string* out, std::string* err);
 
 // the five filters undone in place by a plain loop, one thread: what the device half replaces (png_check times it)
 void unfilter_host(const Frame& f, uint8_t* filtered);

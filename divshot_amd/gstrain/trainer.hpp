@@ -130,6 +130,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     //   caller            cameras             sky   masks
     //   score_views       test_idx            yes   view_mask x region_masks (enableFocusRegion), made in per_pass: only the metric reads them
     //   render_to_jpeg    what is asked for   yes   none
+    //   render_to_png     what is asked for   yes   none
     //   extract_mesh      training_cameras()  no    view_mask
     //   prune_importance  training_cameras()  no    view_mask
     struct EvalPass { int first, nb; const int* cam; const dvs_camera* cams; const float* images; };   // views which[first .. first + nb): their indices
@@ -230,6 +231,20 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     void ensure_eval_ctx();
     bool render_to_jpeg(const std::vector<int>& which, const std::vector<std::string>& files, RenderStats* stats);
     void render_at_save();
+    // the same views as PNG files (DVS_RENDER_FORMAT=png; INTEGRATION.md "Rendered views"): the layers of DVS_RENDER_LAYERS — colour
+    // <name>.png (RGB8, scale 255: the JPEG's quantisation), depth <name>_depth.png (GRAY16 of depth x DVS_RENDER_DEPTH_SCALE, 0 = no
+    // depth, a tEXt chunk depth_scale) and alpha <name>_alpha.png (GRAY8, scale 255). Depth and alpha are one dvs_raster_depth_views call
+    // per pass on eval_ctx (the sky composite only adds to the image: the saved forward state stays valid; the sky is in neither).
+    // Per pass one dvs_png_encode_views launch per layer, one copy of the filtered streams and the saturation counts, then the host
+    // threads deflate (DVS_RENDER_PNG_LEVEL) and write one file each. Nothing is allocated until the first PNG render.
+    enum { LAYER_COLOR = 1, LAYER_DEPTH = 2, LAYER_ALPHA = 4 };
+    bool render_png = false; int render_layers = LAYER_COLOR, render_png_level = 6; float render_depth_scale = 1000.f;
+    GrowBuf<uint8_t> d_render_png;                                           // 64 bytes of saturation counts, then per layer [views of the pass][stream]
+    std::vector<uint8_t> render_png_host;
+    GrowBuf<float> d_render_depth, d_render_alpha;                           // [eval_views][H][W]
+    struct PngStats { size_t views = 0, files = 0, bytes = 0, saturated = 0; double filter_ms = 0, deflate_ms = 0; int threads = 0; };
+    // files[l] (l = 0 colour, 1 depth, 2 alpha): one path per camera of `which`, or empty when the layer is not asked for
+    bool render_to_png(const std::vector<int>& which, const std::vector<std::string> (&files)[3], PngStats* stats);
 
     // mesh export (cfg.meshResolution / DVS_MESH_RESOLUTION; trainer_mesh.cpp): the depth and alpha maps of a pass of eval_ctx. Nothing is
     // allocated until the first mesh. The grid and the extraction scratch live for one extraction.

@@ -38,7 +38,14 @@ void GaussianTrainerScene::Impl::report_config() const {
                             " of colour from any training camera's centre (no visibility test; the 0.01 default was chosen without measurement)").c_str()
                          : "every splat keeps the model's SH degree",
               !test_idx.empty() ? "; the payload is decoded on the device and scored on the held-out views" : "");
-    if (render_views)
+    if (render_views && render_png)
+        logf_("config: renderViews %d: every save also writes the %s cameras as PNG files (layers %s%s%s, depth x %.9g as 16-bit gray with 0 = no depth, "
+              "zlib level %d) to <modelPath>_<it>_renders/, rendered with the evaluation's options; samples and the per-row filter choice on the device, "
+              "deflate on the host%s", render_views, render_views == RENDER_TEST ? "test" : render_views == RENDER_TRAIN ? "training" : "test and training",
+              (render_layers & LAYER_COLOR) ? "color" : "", (render_layers & LAYER_DEPTH) ? ((render_layers & LAYER_COLOR) ? ",depth" : "depth") : "",
+              (render_layers & LAYER_ALPHA) ? ((render_layers & (LAYER_COLOR | LAYER_DEPTH)) ? ",alpha" : "alpha") : "", (double)render_depth_scale, render_png_level,
+              (render_views & RENDER_TEST) && test_idx.empty() ? " (no camera is held out: every camera is a training camera)" : "");
+    else if (render_views)
         logf_("config: renderViews %d: every save also writes the %s cameras as JPEG files (quality %d, %s) to <modelPath>_<it>_renders/, rendered with the "
               "evaluation's options; transform on the device, entropy coding on the host%s", render_views,
               render_views == RENDER_TEST ? "test" : render_views == RENDER_TRAIN ? "training" : "test and training", render_quality,

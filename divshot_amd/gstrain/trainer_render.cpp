@@ -1,15 +1,42 @@
 // trainer_render.cpp — rendered views as JPEG files: the selected cameras through the evaluation context, the forward DCT and
-// quantisation on the device (dvs_jpeg_encode_views), the entropy coder on host threads (jpeg_write.hpp).
+// quantisation on the device (dvs_jpeg_encode_views), the entropy coder on host threads (jpeg_write.hpp). And as PNG files (colour,
+// 16-bit depth, alpha): sample conversion and the per-row filter choice on the device (dvs_png_encode_views), deflate on host threads
+// (png_io.hpp write_png).
 #include "trainer.hpp"
 #include <atomic>
 #include <thread>
 #include "jpeg_write.hpp"
+#include "png_io.hpp"
 #include "../../include/dvs_image.h"
 
 void GaussianTrainerScene::Impl::setup_render() {
     render_views = env_int("DVS_RENDER_VIEWS", cfg.renderViews) & (RENDER_TEST | RENDER_TRAIN);
     render_quality = std::max(1, std::min(env_int("DVS_RENDER_QUALITY", cfg.renderQuality), 100));
     render_sampling = env_int("DVS_RENDER_SAMPLING", cfg.renderSampling) == 1 ? DVS_JPEG_SAMPLING_444 : DVS_JPEG_SAMPLING_420;
+    // the PNG settings travel as environment variables (the config struct has no room left); a bad value is reported once, here, and ignored
+    if (const char* e = getenv("DVS_RENDER_FORMAT")) {
+        if (std::string_view(e) == "png") render_png = true;
+        else if (std::string_view(e) != "jpg") logf_("render: DVS_RENDER_FORMAT='%s' is not jpg or png: ignored", e);
+    }
+    if (const char* e = getenv("DVS_RENDER_LAYERS")) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end == e || *end || v < 1 || v > 7) logf_("render: DVS_RENDER_LAYERS='%s' is not a sum 1..7 of 1 (color), 2 (depth), 4 (alpha): ignored", e);
+        else if (!render_png && v != LAYER_COLOR) logf_("render: DVS_RENDER_LAYERS='%s' asks for depth or alpha, which JPEG files do not carry (DVS_RENDER_FORMAT=png does): ignored", e);
+        else render_layers = (int)v;
+    }
+    if (const char* e = getenv("DVS_RENDER_DEPTH_SCALE")) {
+        char* end = nullptr;
+        const double v = strtod(e, &end);
+        if (end == e || *end || !std::isfinite(v) || !(v > 0) || !std::isfinite((float)v) || !((float)v > 0.f)) logf_("render: DVS_RENDER_DEPTH_SCALE='%s' is not a finite number > 0: ignored", e);
+        else render_depth_scale = (float)v;
+    }
+    if (const char* e = getenv("DVS_RENDER_PNG_LEVEL")) {
+        char* end = nullptr;
+        const long v = strtol(e, &end, 10);
+        if (end == e || *end || v < 0 || v > 9) logf_("render: DVS_RENDER_PNG_LEVEL='%s' is not a zlib level 0..9: ignored", e);
+        else render_png_level = (int)v;
+    }
     // file names: the image stems when every camera has one and they are unique, cam_%04d otherwise (a synthetic scene). cam_names is
     // filled in step with cams by both loaders.
     std::map<std::string, int> seen;
@@ -96,6 +123,106 @@ bool GaussianTrainerScene::Impl::render_to_jpeg(const std::vector<int>& which, c
     return all_ok;
 }
 
+// the PNG counterpart of render_to_jpeg: the layers whose files[l] is not empty. -> false when a file could not be deflated or written.
+bool GaussianTrainerScene::Impl::render_to_png(const std::vector<int>& which, const std::vector<std::string> (&files)[3], PngStats* stats) {
+    ensure_eval_ctx();
+    static const int kKind[3] = {DVS_PNG_KIND_RGB8, DVS_PNG_KIND_GRAY16, DVS_PNG_KIND_GRAY8};
+    static const int kType[3] = {2, 0, 0}, kDepth[3] = {8, 16, 8};
+    const float scales[3] = {255.f, render_depth_scale, 255.f};
+    constexpr size_t kCounts = DVS_PNG_ENCODE_MAX_VIEWS * sizeof(uint32_t);   // the saturation counts lead the buffer: one copy brings both
+    size_t bytes_of[3] = {0, 0, 0}, per_view = 0;
+    int n_layers = 0, asked[3] = {0, 0, 0};                                  // the layers asked for, in file order
+    for (int l = 0; l < 3; ++l) {
+        if (files[l].empty()) continue;
+        if (files[l].size() != which.size()) throw std::runtime_error("render_to_png: a layer's file list does not match the cameras");
+        bytes_of[l] = dvs_png_encode_bytes(kKind[l], W, H);
+        if (!bytes_of[l]) throw std::runtime_error("dvs_png_encode_bytes: invalid arguments");
+        per_view += bytes_of[l];
+        asked[n_layers++] = l;
+    }
+    if (!n_layers) return true;
+    const bool maps = !files[1].empty() || !files[2].empty();
+    const size_t img = 3 * (size_t)W * H, map = (size_t)W * H;
+    d_render_png.reserve(kCounts + (size_t)eval_views * per_view);
+    if (render_png_host.size() < kCounts + (size_t)eval_views * per_view) render_png_host.resize(kCounts + (size_t)eval_views * per_view);
+    if (maps) { d_render_depth.reserve((size_t)eval_views * map * sizeof(float)); d_render_alpha.reserve((size_t)eval_views * map * sizeof(float)); }
+    if (!ev_render0)
+        for (Event* e : {&ev_render0, &ev_render1}) { hipEvent_t ev = nullptr; HIP_OR_THROW(hipEventCreate(&ev)); e->reset(ev); }
+    const int load_threads = std::max(1, std::min(env_int("DVS_LOAD_THREADS", 8), 16));     // never the machine's CPU count
+    const dvs_opts opts = eval_opts();
+    char scale_text[32];
+    snprintf(scale_text, sizeof scale_text, "%.9g", (double)render_depth_scale);
+    const gspng::TextPairs depth_text = {{"depth_scale", scale_text}};
+    bool all_ok = true;
+    for_each_eval_pass(splats(), which, true, [&](const EvalPass& p) {
+        const int first = p.first, nb = p.nb;
+        if (maps) DVS_OR_THROW(dvs_raster_depth_views(eval_ctx.get(), stream.get(), &opts, d_render_depth.get(), d_render_alpha.get()));
+        HIP_OR_THROW(hipMemsetAsync(d_render_png.get(), 0, kCounts, stream.get()));
+        size_t layer_at[3] = {0, 0, 0}, at = kCounts;
+        HIP_OR_THROW(hipEventRecord(ev_render0.get(), stream.get()));
+        for (int l = 0; l < 3; ++l) {
+            if (files[l].empty()) continue;
+            layer_at[l] = at;
+            const float* images[DVS_PNG_ENCODE_MAX_VIEWS];
+            uint8_t* outs[DVS_PNG_ENCODE_MAX_VIEWS];
+            for (int k = 0; k < nb; ++k) {
+                images[k] = l == 0 ? p.images + (size_t)k * img : (l == 1 ? d_render_depth.get() : d_render_alpha.get()) + (size_t)k * map;
+                outs[k] = d_render_png.get() + at + (size_t)k * bytes_of[l];
+            }
+            DVS_OR_THROW(dvs_png_encode_views(stream.get(), kKind[l], W, H, scales[l], images, outs, l == 1 ? (uint32_t*)d_render_png.get() : nullptr, nb));
+            at += (size_t)nb * bytes_of[l];
+        }
+        HIP_OR_THROW(hipEventRecord(ev_render1.get(), stream.get()));
+        HIP_OR_THROW(hipMemcpyAsync(render_png_host.data(), d_render_png.get(), at, hipMemcpyDeviceToHost, stream.get()));
+        HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+        float ms = 0;
+        HIP_OR_THROW(hipEventElapsedTime(&ms, ev_render0.get(), ev_render1.get()));
+        const auto t_host = std::chrono::steady_clock::now();
+        const int tasks = nb * n_layers;                                     // task t: view t / n_layers, layer asked[t % n_layers]
+        std::vector<size_t> bytes((size_t)tasks, 0);
+        std::vector<std::string> errs((size_t)tasks);
+        std::atomic<int> next{0};
+        const auto work = [&]() noexcept {                                   // files are handed out one at a time: any number of threads finishes them all
+            for (int t = next++; t < tasks; t = next++) {
+                try {
+                    const int k = t / n_layers, l = asked[t % n_layers];
+                    std::string out;
+                    const std::string& file = files[l][(size_t)(first + k)];
+                    if (!gspng::write_png(W, H, kDepth[l], kType[l], render_png_host.data() + layer_at[l] + (size_t)k * bytes_of[l], bytes_of[l], render_png_level,
+                                          l == 1 ? &depth_text : nullptr, &out, &errs[(size_t)t])) continue;
+                    FILE* f = fopen(file.c_str(), "wb");
+                    if (!f || fwrite(out.data(), 1, out.size(), f) != out.size()) errs[(size_t)t] = "cannot write " + file;
+                    else bytes[(size_t)t] = out.size();
+                    if (f && fclose(f) != 0) { errs[(size_t)t] = "cannot write " + file; bytes[(size_t)t] = 0; }
+                } catch (...) {
+                    try { errs[(size_t)t] = "out of memory while writing the view"; } catch (...) {}
+                }
+            }
+        };
+        std::vector<std::thread> workers;
+        try {                                                                // a thread that cannot be started is not needed: this one works too
+            workers.reserve((size_t)load_threads);
+            for (int t = 1; t < std::min(load_threads, tasks); ++t) workers.emplace_back(work);
+        } catch (...) {}
+        const int nthreads = (int)workers.size() + 1;
+        work();
+        for (std::thread& t : workers) t.join();
+        const double host_ms = ms_since(t_host);
+        for (int k = 0; k < nb; ++k) {
+            bool view_ok = true;
+            for (int j = 0; j < n_layers; ++j) {
+                const size_t t = (size_t)(k * n_layers + j);
+                if (!errs[t].empty()) { logf_("render @%d: camera %d: %s", step, which[(size_t)(first + k)], errs[t].c_str()); all_ok = view_ok = false; }
+                else if (stats) { stats->files += 1; stats->bytes += bytes[t]; }
+            }
+            if (stats && view_ok) stats->views += 1;
+            if (stats && !files[1].empty()) { uint32_t c; memcpy(&c, render_png_host.data() + (size_t)k * sizeof c, sizeof c); stats->saturated += c; }
+        }
+        if (stats) { stats->filter_ms += ms; stats->deflate_ms += host_ms; stats->threads = std::max(stats->threads, nthreads); }
+    });
+    return all_ok;
+}
+
 // at a save, rank 0: the cameras cfg.renderViews selects, into <modelPath>_<step>_renders/
 void GaussianTrainerScene::Impl::render_at_save() {
     if (!render_views || rank != 0 || !ctx) return;
@@ -110,6 +237,17 @@ void GaussianTrainerScene::Impl::render_at_save() {
     std::error_code ec;
     std::filesystem::create_directories(dir, ec);
     if (ec) { logf_("render @%d: cannot create %s: %s", step, dir.c_str(), ec.message().c_str()); return; }
+    if (render_png) {
+        static const char* const kSuffix[3] = {".png", "_depth.png", "_alpha.png"};
+        std::vector<std::string> layers[3];
+        for (int l = 0; l < 3; ++l)
+            if (render_layers & (1 << l)) for (int c : which) layers[l].push_back(dir + "/" + camera_name(c) + kSuffix[l]);
+        PngStats st;
+        render_to_png(which, layers, &st);
+        logf_("render @%d: %zu views, %zu files, %zu bytes, filtering %.3f ms (device, events), deflate %.3f ms (host, %d threads, wall), %zu depth samples saturated",
+              step, st.views, st.files, st.bytes, st.filter_ms, st.deflate_ms, st.threads, st.saturated);
+        return;
+    }
     std::vector<std::string> files;
     for (int c : which) files.push_back(dir + "/" + camera_name(c) + ".jpg");
     RenderStats st;

@@ -1,7 +1,7 @@
 /*
  * dvs_image.h — C-ABI of the image work on the device: the parallel half of baseline JPEG decoding (below), the parallel half of
  * baseline JPEG encoding (dvs_jpeg_encode_views, after it), the undistortion of a view taken through a distorted COLMAP camera
- * (dvs_undistort_view) and the parallel half of PNG decoding with the mask rule (dvs_png_reconstruct, dvs_mask_combine, at the end).
+ * (dvs_undistort_view) and the parallel half of PNG decoding with the mask rule (dvs_png_reconstruct, dvs_mask_combine, at the end) and, right after that decoder, the parallel half of PNG encoding (dvs_png_encode_views).
  *
  * JPEG: quantised DCT coefficients (gstrain/jpeg_io.hpp decodes them on
  * the host) -> planar 8-bit RGB on the device, in one kernel: dequantisation, 8x8 inverse DCT, chroma upsampling, YCbCr -> RGB.
@@ -169,6 +169,42 @@ size_t dvs_png_filtered_bytes(const dvs_png_desc* desc);
  * DVS_ERR_INVALID for a NULL desc, filtered or rgb, an illegal type / depth pair, or a desc that contradicts itself (a side outside
  * 1..65500, has_key outside {0, 1} or set beside an alpha channel or a palette). */
 int dvs_png_reconstruct(void* stream, const dvs_png_desc* desc, uint8_t* filtered, uint8_t* rgb, uint8_t* alpha);
+
+/* ---- PNG encoding: fp32 planes (what dvs_raster_forward_views and dvs_raster_depth_views write) -> filtered scanlines, the mirror image
+ * of the above; gstrain/png_io.hpp (write_png) deflates them on the host. One launch takes up to DVS_PNG_ENCODE_MAX_VIEWS views of one
+ * size and kind. No scratch; a view's output does not depend on the other views of the call, and two calls return identical bytes and
+ * counts. The result is defined bit for bit; after the first step it is integer arithmetic; tests/png_enc_ref.py restates it:
+ *   sample       M = 255 (RGB8, GRAY8) or 65535 (GRAY16); s = (int)min(M, max(0, rint(x * scale))): the fp32 product rounded to the
+ *                nearest integer, ties to even; NaN -> 0, +inf -> M, -inf -> 0. With scale = 255 this is dvs_jpeg_encode_views' float to
+ *                byte rule (PackF32ToU8): a PNG and a JPEG of one render are quantised alike. A sample counts as SATURATED iff
+ *                rint(x * scale) > M before the clamp: +inf counts, a NaN does not.
+ *   raw scanline RGB8: R G B per pixel, interleaved; GRAY8: one byte per pixel; GRAY16: two, the high byte first
+ *   filters      x = the raw byte, a = the raw byte bpp to the left, b = the raw byte above, c = the raw byte above a (as the decoder's
+ *                comment above defines them); bytes left of the row and the row above the first read as 0; every difference is taken
+ *                modulo 256:   0 None x | 1 Sub x - a | 2 Up x - b | 3 Average x - ((a + b) >> 1) | 4 Paeth x - predictor, the
+ *                predictor with the decoder's own tie order (a if pa <= pb and pa <= pc, else b if pb <= pc, else c)
+ *   choice       the cost of filter f on a row = the sum over its rowbytes filtered bytes v of (v < 128 ? v : 256 - v), the "minimum sum
+ *                of absolute differences" heuristic; an int32 (at most 196 500 * 128). The row gets the filter of the smallest cost, on
+ *                a tie the smallest f: a row of zeros gets 0.
+ *   output row   the filter byte, then the row filtered with it; rows follow one another at y * (1 + rowbytes) */
+#define DVS_PNG_ENCODE_MAX_VIEWS 16
+#define DVS_PNG_KIND_RGB8   0   /* images[v]: planar [3][H][W] fp32 -> colour type 2, depth 8  (rowbytes 3W, bpp 3) */
+#define DVS_PNG_KIND_GRAY8  1   /* images[v]: [H][W] fp32          -> colour type 0, depth 8  (rowbytes  W, bpp 1) */
+#define DVS_PNG_KIND_GRAY16 2   /* images[v]: [H][W] fp32          -> colour type 0, depth 16 (rowbytes 2W, bpp 2, big-endian) */
+
+/* host only: bytes of one view's filtered stream, height * (1 + rowbytes); 0 for a kind or size dvs_png_encode_views refuses */
+size_t dvs_png_encode_bytes(int kind, int width, int height);
+
+/* filtered[v] = the filtered stream of images[v], v < n_views, in the layout dvs_png_reconstruct reads. `images` and `filtered` are HOST
+ * arrays of DEVICE pointers, read before the call returns; images[v] needs a float's alignment only; filtered[v] points to
+ * dvs_png_encode_bytes(kind, width, height) bytes with no alignment requirement: where a lane's four bytes fall on a dword of the
+ * output they leave as one dword store, as single bytes otherwise, the same bytes either way. `saturated`: nullable DEVICE
+ * uint32[n_views], INCREMENTED by the number of saturated samples of each view (the caller zeroes it; one atomic per wavefront that
+ * has any — an integer sum, so the count does not depend on their order).
+ * DVS_ERR_INVALID, before anything touches the device, for a NULL images / filtered / images[v] / filtered[v], n_views outside 1..16,
+ * an unknown kind, a side outside 1..65500, a scale that is not finite or not > 0, an images[v] off a 4-byte boundary. */
+int dvs_png_encode_views(void* stream, int kind, int width, int height, float scale, const float* const* images,
+                         uint8_t* const* filtered, uint32_t* saturated, int n_views);
 
 /* ---- the mask rule on the device, so that decoded pixels never travel back to the host: m[i] = gray[i] > 127, AND alpha[i] > 127 when
  * alpha is given, AND other[i] != 0 when other is given (a plane of bytes in {0, 1}, such as an earlier result); written as bytes in

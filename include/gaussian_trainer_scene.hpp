@@ -196,6 +196,10 @@ public:
     // evaluation's options and written to `path` as a baseline JPEG at the config's renderQuality / renderSampling; synchronises.
     // false for a bad index, before loadTrainData, or when the file cannot be written; nothing is thrown.
     bool renderCameraToJpeg(int camera, const std::string& path);
+    // the same as a PNG file (INTEGRATION.md "Rendered views"): layer 1 = colour (8-bit RGB, lossless: the JPEG's quantisation of the
+    // render), 2 = depth (16-bit gray, depth x DVS_RENDER_DEPTH_SCALE, default 1000; 0 = no depth; a tEXt chunk depth_scale), 4 = alpha
+    // (8-bit gray); the sky is in neither of the last two. Same contract; false also for another layer value.
+    bool renderCameraToPng(int camera, const std::string& path, int layer);
     // trainer -> viewer hand-off (editor.cpp:1459-1473 -> GaussianModel::update_from_cpu, gaussian_model.cpp:43-68)
     const std::vector<float>& getGaussianPositionCpu();
     const std::vector<float>& getGaussianSH0Cpu();
