@@ -1,8 +1,9 @@
 // trainer.hpp — GaussianTrainerScene::Impl, the state behind `libgstrain.so`, and what its source files share. The members are defined
-// in trainer_load.cpp (loaders, allocation), trainer_step.cpp (one trainStep), trainer_refine.cpp (densification, pruning),
-// trainer_output.cpp (configuration report, the evaluation context and its pass loop, evaluation, export), trainer_render.cpp (rendered
-// views as JPEG files) and trainer_mesh.cpp (mesh export); the focus region's members sit beside the code they feed (trainer_step.cpp,
-// trainer_refine.cpp); gstrain.cpp holds the GaussianTrainerScene members and the C symbols.
+// in trainer_load.cpp (allocation, what the loaders share, the synthetic loader), trainer_dataset.cpp (the capture loader), trainer_step.cpp
+// (one trainStep), trainer_refine.cpp (densification, pruning), trainer_output.cpp (configuration report, the evaluation context and its
+// pass loop, evaluation, export), trainer_render.cpp (rendered views as JPEG and PNG files) and trainer_mesh.cpp (mesh export); the focus
+// region's members sit beside the code they feed (trainer_step.cpp, trainer_refine.cpp); gstrain.cpp holds the GaussianTrainerScene
+// members and the C symbols.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -47,6 +48,22 @@ inline int env_int(const char* name, int fallback) { const char* e = getenv(name
 inline bool env_is(const char* name, const char* value) { const char* e = getenv(name); return e && std::string_view(e) == value; }
 inline double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
 }  // namespace
+
+// Two timing events, created at the first use: how long the device took over what a stream was given between begin() and end(). run() is
+// the whole sequence (record, launch, record, wait for the second event). A caller that queues more behind end() and then waits for the
+// stream itself (the renders' copy) takes the two steps and asks for ms() after its wait.
+struct TimedPair {
+    Event e0, e1;
+    void begin(hipStream_t s) {
+        for (Event* e : {&e0, &e1})
+            if (!*e) { hipEvent_t h = nullptr; HIP_OR_THROW(hipEventCreate(&h)); e->reset(h); }
+        HIP_OR_THROW(hipEventRecord(e0.get(), s));
+    }
+    void end(hipStream_t s) { HIP_OR_THROW(hipEventRecord(e1.get(), s)); }
+    float ms() const { float v = 0; HIP_OR_THROW(hipEventElapsedTime(&v, e0.get(), e1.get())); return v; }
+    template <class F>
+    float run(hipStream_t s, F&& launch) { begin(s); launch(); end(s); HIP_OR_THROW(hipEventSynchronize(e1.get())); return ms(); }
+};
 
 struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     // the class is exported (GSTRAIN_API), its implementation is not
     GaussianTrainConfig cfg;
@@ -216,7 +233,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     // rendered views as JPEG files (cfg.renderViews / renderQuality / renderSampling and their DVS_RENDER_* overrides, read at load): at
     // every save rank 0 renders the selected cameras through eval_ctx (for_each_eval_pass: what `eval @it` scored), turns each pass
     // into quantised DCT coefficients with ONE dvs_jpeg_encode_views launch, copies them to the host and Huffman-codes them on up to
-    // DVS_LOAD_THREADS threads into <modelPath>_<it>_renders/<name>.jpg. Nothing is allocated until the first render. The training
+    // load_threads() threads (write_files) into <modelPath>_<it>_renders/<name>.jpg. Nothing is allocated until the first render. The training
     // context, its pending rows and its prepared projection are never touched.
     enum { RENDER_TEST = 1, RENDER_TRAIN = 2 };
     int render_views = 0, render_quality = 90, render_sampling = 0;
@@ -224,7 +241,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     bool cam_names_ok = false;                                               // every camera has a stem and they are unique (else the files are cam_%04d)
     GrowBuf<int16_t> d_render_coef;                                          // [eval_views][coefficients of a view]
     std::vector<int16_t> render_coef_host;
-    Event ev_render0, ev_render1;
+    TimedPair render_timer;                                                  // a pass's encode launches, both formats
     struct RenderStats { size_t views = 0, bytes = 0; double transform_ms = 0, entropy_ms = 0; int threads = 0; };
     void setup_render();
     std::string camera_name(int c) const;
@@ -235,7 +252,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     // <name>.png (RGB8, scale 255: the JPEG's quantisation), depth <name>_depth.png (GRAY16 of depth x DVS_RENDER_DEPTH_SCALE, 0 = no
     // depth, a tEXt chunk depth_scale) and alpha <name>_alpha.png (GRAY8, scale 255). Depth and alpha are one dvs_raster_depth_views call
     // per pass on eval_ctx (the sky composite only adds to the image: the saved forward state stays valid; the sky is in neither).
-    // Per pass one dvs_png_encode_views launch per layer, one copy of the filtered streams and the saturation counts, then the host
+    // Per pass one dvs_png_encode_views launch per layer, one copy of the filtered streams and the saturation counts, then the same host
     // threads deflate (DVS_RENDER_PNG_LEVEL) and write one file each. Nothing is allocated until the first PNG render.
     enum { LAYER_COLOR = 1, LAYER_DEPTH = 2, LAYER_ALPHA = 4 };
     bool render_png = false; int render_layers = LAYER_COLOR, render_png_level = 6; float render_depth_scale = 1000.f;
@@ -430,5 +447,9 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     void finish_load(const std::function<void(std::vector<float> (&)[6])>& fresh_init, const char* fresh_name,
                      const std::function<void(bool)>& describe);
     bool load_synthetic(const std::string& spec_str);
+    struct CaptureLoad;                                                      // load_dataset's plan, loop state and stages (trainer_dataset.cpp)
     bool load_dataset(const std::string& path);
+    // host threads of the capture loader's decode-ahead and of the render writers (DVS_LOAD_THREADS, default 8, 1..16: never sized from
+    // the machine's CPU count)
+    int load_threads() const { return std::max(1, std::min(env_int("DVS_LOAD_THREADS", 8), 16)); }
 };

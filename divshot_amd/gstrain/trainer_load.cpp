@@ -1,92 +1,11 @@
-// trainer_load.cpp — load_train_data: the synthetic-scene and capture-directory loaders and the allocations they share.
+// trainer_load.cpp — load_train_data: the allocations and the set-up both loaders share (create_context, store_view, setup_*, finish_load) and
+// the synthetic-scene loader. The capture-directory loader is trainer_dataset.cpp.
 #include "trainer.hpp"
-#include <condition_variable>
-#include <mutex>
-#include <thread>
-#include "jpeg_io.hpp"
-#include "png_io.hpp"
-#include "../../include/dvs_image.h"
 
 namespace {
 __global__ void k_pack_u8(const float* __restrict__ src, uint8_t* __restrict__ dst, size_t n) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) dst[i] = (uint8_t)fminf(255.f, fmaxf(0.f, rintf(src[i] * 255.f)));
-}
-
-// Host threads that run the serial half of the compressed files of a capture ahead of the loader: entropy decoding is the serial cost of
-// a JPEG and inflate that of a PNG (pictures and masks alike), so up to `threads` files are decoded at once, never more than `window`
-// files beyond the one the loader has taken (the memory held is bounded by the window, not by the capture). take() hands the files out
-// strictly in order, so nothing depends on the thread count.
-class DecodeAhead {
-public:
-    struct Job { std::string file; bool png = false; };
-    struct Result { gsjpeg::Frame frame; gspng::Frame png; std::string err; bool ok = false, done = false; };
-    DecodeAhead(std::vector<Job> jobs, int threads) : jobs_(std::move(jobs)), slots_(jobs_.size()), window_(2 * (size_t)threads) {
-        for (int t = 0; t < threads && (size_t)t < jobs_.size(); ++t) workers_.emplace_back([this] { work(); });
-    }
-    ~DecodeAhead() {
-        { std::lock_guard<std::mutex> lock(m_); stop_ = true; }
-        cv_.notify_all();
-        for (std::thread& t : workers_) t.join();
-    }
-    Result take(size_t i) {                                  // i = 0, 1, 2, ... in this order
-        std::unique_lock<std::mutex> lock(m_);
-        cv_.wait(lock, [&] { return slots_[i].done; });
-        Result r = std::move(slots_[i]);
-        slots_[i] = Result();
-        taken_ = i + 1;
-        lock.unlock();
-        cv_.notify_all();
-        return r;
-    }
-    const std::string& file(size_t i) const { return jobs_[i].file; }
-    double wall_ms(bool png) {                               // wall time during which at least one thread was decoding a file of that format: waits on a full window are not in it
-        std::lock_guard<std::mutex> lock(m_);
-        return busy_ms_[png ? 1 : 0];
-    }
-
-private:
-    void work() {
-        for (;;) {
-            size_t i;
-            int k;
-            {
-                std::unique_lock<std::mutex> lock(m_);
-                cv_.wait(lock, [&] { return stop_ || next_ >= jobs_.size() || next_ < taken_ + window_; });
-                if (stop_ || next_ >= jobs_.size()) return;
-                i = next_++;
-                k = jobs_[i].png ? 1 : 0;
-                if (busy_[k]++ == 0) busy_since_[k] = std::chrono::steady_clock::now();
-            }
-            Result r;
-            r.ok = k ? gspng::decode_filtered(jobs_[i].file, &r.png, &r.err) : gsjpeg::decode_coefficients(jobs_[i].file, &r.frame, &r.err);
-            r.done = true;
-            {
-                std::lock_guard<std::mutex> lock(m_);
-                slots_[i] = std::move(r);
-                if (--busy_[k] == 0) busy_ms_[k] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - busy_since_[k]).count();
-            }
-            cv_.notify_all();
-        }
-    }
-    const std::vector<Job> jobs_;
-    std::vector<Result> slots_;
-    size_t window_, next_ = 0, taken_ = 0;
-    bool stop_ = false;
-    int busy_[2] = {0, 0};                                   // threads inside a decode, per format (0 JPEG, 1 PNG)
-    double busy_ms_[2] = {0, 0};
-    std::chrono::steady_clock::time_point busy_since_[2];
-    std::mutex m_;
-    std::condition_variable cv_;
-    std::vector<std::thread> workers_;
-};
-
-dvs_png_desc png_desc_of(const gspng::Frame& f) {
-    dvs_png_desc d{};
-    d.width = f.width; d.height = f.height; d.bit_depth = f.bit_depth; d.color_type = f.color_type; d.has_key = f.has_key ? 1 : 0;
-    for (int k = 0; k < 3; ++k) d.key[k] = f.key[k];
-    memcpy(d.palette, f.palette, sizeof d.palette);
-    return d;
 }
 
 struct Lcg {       // tiny deterministic noise source for the synthetic initialisation
@@ -327,306 +246,5 @@ bool GaussianTrainerScene::Impl::load_synthetic(const std::string& spec_str) {
     }, "synthetic", [&](bool resumed) {
         if (cfg.verbose) logf_("synthetic scene: %d splats, %d cameras @ %dx%d, SH degree %d%s", spec.n, spec.n_cams, W, H, sh_max, resumed ? " (resumed)" : "");
     });
-    return true;
-}
-
-// A capture directory: a COLMAP sparse model and its images, binary PPM, baseline JPEG or PNG (dataset_io.hpp). A JPEG is entropy-decoded
-// on the host (jpeg_io.hpp, ahead of the loop by DecodeAhead) and reconstructed on the device (dvs_jpeg_reconstruct) into the same planar
-// bytes a PPM is uploaded as; a PNG is inflated on the host (png_io.hpp, by the same threads) and unfiltered and expanded on the device
-// (dvs_png_reconstruct) into those bytes too. Under useMask a PNG mask (masks/<stem>.png, masks/<name>.png; gray or gray+alpha) goes the
-// same way and a picture's alpha is ANDed into its mask on the device (dvs_mask_combine); without useMask the alpha is ignored. The view of a SIMPLE_RADIAL / RADIAL / OPENCV camera is then remapped on the device into the view of the
-// pinhole camera with the same fx, fy, cx, cy and size (dvs_undistort_view); the pixels without a source are blank and masked out, not
-// cropped, so a capture with one such camera carries a mask on every view. Everything after that is one path. The views go up as bytes and are box-filtered
-// on the device when maxImageWidth / maxImageHeight ask for it; the splats start from the sparse points (include/dvs_init.h).
-bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) {
-    gsdata::Dataset ds;
-    std::string err;
-    gsdata::ReadOptions read_opt;
-    read_opt.accept_distorted = true;
-    if (!gsdata::read_dataset(path, read_opt, &ds, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-    const int n_pts = (int)std::min<size_t>(ds.xyz.size() / 3, (size_t)0x7FFFFFFF);
-    if (n_pts <= 0) {
-        logf_("load_train_data('%s'): the sparse model has no usable points (%zu dropped); initialisation without a point cloud is out of scope", path.c_str(), ds.dropped);
-        return false;
-    }
-    // the smallest factor of {1, 2, 4, 8} that fits each image into maxImageWidth x maxImageHeight; one size per run
-    const int max_w = cfg.maxImageWidth > 0 ? cfg.maxImageWidth : 0x7FFFFFFF, max_h = cfg.maxImageHeight > 0 ? cfg.maxImageHeight : 0x7FFFFFFF;
-    std::vector<int> factor(ds.images.size(), 1);
-    int W0 = 0, H0 = 0, model = -1;
-    bool one_model = true;
-    const auto is_distorted = [](const gsdata::Camera& c) { return c.model >= 2 && c.model <= 4; };
-    size_t n_distorted = 0;
-    bool distorted_models[5] = {false, false, false, false, false};
-    undistorted = false;
-    for (size_t i = 0; i < ds.images.size(); ++i) {
-        const gsdata::Camera& c = ds.cameras[ds.images[i].camera];
-        if (is_distorted(c)) { ++n_distorted; distorted_models[c.model] = true; undistorted = true; }
-        const int w = (int)c.width, h = (int)c.height;
-        int d = 1;
-        while (d <= 8 && (w / d > max_w || h / d > max_h)) d *= 2;
-        if (d > 8 || w / d <= 0 || h / d <= 0) {
-            logf_("load_train_data('%s'): image %s is %dx%d; even 1/8 of it does not fit maxImageWidth / maxImageHeight %dx%d", path.c_str(),
-                  ds.images[i].name.c_str(), w, h, cfg.maxImageWidth, cfg.maxImageHeight);
-            return false;
-        }
-        factor[i] = d;
-        if (i == 0) { W0 = w; H0 = h; W = w / d; H = h / d; model = c.model; }
-        else if (w / d != W || h / d != H) {
-            logf_("load_train_data('%s'): image %s ends up %dx%d but %s ends up %dx%d; this trainer takes one image size per run", path.c_str(),
-                  ds.images[i].name.c_str(), w / d, h / d, ds.images[0].name.c_str(), W, H);
-            return false;
-        }
-        one_model = one_model && c.model == model;
-    }
-    sh_max = 3;
-    const int capacity = std::max(n_pts, cfg.capMax);
-    std::vector<float> zero[6];
-    for (int g = 0; g < 6; ++g) zero[g].assign((size_t)n_pts * kWidth[g], 0.f);
-    create_context(n_pts, capacity, zero);
-    const bool u8 = views_u8();
-    const size_t P = (size_t)W * H, img = 3 * P;
-    std::vector<uint8_t> px, planar, mk;
-    std::vector<float> mkf;
-    // which file each image, and under useMask its mask, is read from; the JPEGs and PNGs among them are decoded ahead by DVS_LOAD_THREADS
-    // host threads (default 8, 1..16: never sized from the machine's CPU count), in the order the loop below takes them
-    std::vector<DecodeAhead::Job> jobs;
-    std::vector<gsdata::ImageKind> kind(ds.images.size(), gsdata::ImageKind::PPM);
-    std::vector<gsdata::MaskKind> mask_kind(ds.images.size(), gsdata::MaskKind::NONE);
-    size_t n_jpeg = 0, n_png = 0, n_png_masks = 0, n_alpha = 0;
-    for (size_t i = 0; i < ds.images.size(); ++i) {
-        std::string file;
-        if (!gsdata::resolve_image_kind(ds, i, &file, &kind[i], &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-        if (kind[i] == gsdata::ImageKind::JPEG) { jobs.push_back({file, false}); ++n_jpeg; }
-        if (kind[i] == gsdata::ImageKind::PNG) { jobs.push_back({file, true}); ++n_png; }
-        if (cfg.useMask) {
-            if (!gsdata::resolve_mask(ds, i, &file, &mask_kind[i], &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-            if (mask_kind[i] == gsdata::MaskKind::PNG) { jobs.push_back({file, true}); ++n_png_masks; }
-        }
-    }
-    const int load_threads = std::max(1, std::min(env_int("DVS_LOAD_THREADS", 8), 16));
-    DecodeAhead ahead(std::move(jobs), load_threads);
-    Event ev_j0, ev_j1;
-    if (n_jpeg + n_png + n_png_masks) {
-        for (Event* e : {&ev_j0, &ev_j1}) { hipEvent_t ev = nullptr; HIP_OR_THROW(hipEventCreate(&ev)); e->reset(ev); }
-    }
-    double recon_ms = 0, png_ms = 0;
-    size_t job_at = 0;
-    // a PNG from the ahead-decoder onto the device: rgb (planar, 3 p0 bytes) and, when the file has one and `alpha` is given, its alpha plane
-    const auto png_to_device = [&](const gspng::Frame& f, uint8_t* rgb, DevBuf<uint8_t>* alpha) {
-        const dvs_png_desc desc = png_desc_of(f);
-        DevBuf<uint8_t> d_filtered(f.filtered.size());
-        HIP_OR_THROW(hipMemcpy(d_filtered.get(), f.filtered.data(), f.filtered.size(), hipMemcpyHostToDevice));
-        if (alpha && gspng::has_alpha(f)) alpha->alloc((size_t)f.width * f.height);
-        HIP_OR_THROW(hipEventRecord(ev_j0.get(), stream.get()));
-        DVS_OR_THROW(dvs_png_reconstruct(stream.get(), &desc, d_filtered.get(), rgb, alpha ? alpha->get() : nullptr));
-        HIP_OR_THROW(hipEventRecord(ev_j1.get(), stream.get()));
-        HIP_OR_THROW(hipEventSynchronize(ev_j1.get()));              // the scanlines are freed at the end of this scope
-        float ms = 0;
-        HIP_OR_THROW(hipEventElapsedTime(&ms, ev_j0.get(), ev_j1.get()));
-        png_ms += ms;
-    };
-    // the undistortion's events and the count of pixels without a source, summed over the distorted views on the device
-    Event ev_u0, ev_u1;
-    DevBuf<uint32_t> d_invalid;
-    double undistort_ms = 0;
-    uint64_t undistort_pixels = 0;
-    if (undistorted) {
-        for (Event* e : {&ev_u0, &ev_u1}) { hipEvent_t ev = nullptr; HIP_OR_THROW(hipEventCreate(&ev)); e->reset(ev); }
-        d_invalid.alloc(sizeof(uint32_t));
-        HIP_OR_THROW(hipMemset(d_invalid.get(), 0, sizeof(uint32_t)));
-    }
-    const bool masked = cfg.useMask || undistorted;           // (a capture of pinhole cameras only: cfg.useMask, as ever)
-    for (size_t i = 0; i < ds.images.size(); ++i) {
-        const gsdata::Image& im = ds.images[i];
-        const gsdata::Camera& c = ds.cameras[im.camera];
-        const int w = (int)c.width, h = (int)c.height, d = factor[i];
-        const size_t p0 = (size_t)w * h;
-        // 1. the view as bytes; 2. box-filtered by the image's factor (rounded back to 8 bits when the views are kept as bytes) unless the
-        // bytes are the view as they are; 3. its mask. The owners free whatever an early return or a throw leaves behind.
-        DevBuf<uint8_t> full8(3 * p0);
-        DevBuf<float> t, mask;
-        DevBuf<uint8_t> alpha8;                                 // a PNG picture's alpha plane, kept only where a mask is asked for
-        if (kind[i] == gsdata::ImageKind::JPEG) {
-            DecodeAhead::Result r = ahead.take(job_at++);
-            if (!r.ok) { logf_("load_train_data('%s'): %s", path.c_str(), r.err.c_str()); return false; }
-            const gsjpeg::Frame& f = r.frame;
-            if (f.width != w || f.height != h) {
-                logf_("load_train_data('%s'): %s is %dx%d but its camera %u is %dx%d", path.c_str(), ahead.file(job_at - 1).c_str(), f.width, f.height, c.id, w, h);
-                return false;
-            }
-            dvs_jpeg_desc desc{};
-            desc.width = f.width; desc.height = f.height; desc.components = f.components; desc.hs = f.hs[0]; desc.vs = f.vs[0];
-            for (int k = 0; k < 3; ++k) { desc.blocks_w[k] = f.blocks_w[k]; desc.blocks_h[k] = f.blocks_h[k]; desc.offset[k] = f.offset[k]; }
-            memcpy(desc.quant, f.quant, sizeof desc.quant);
-            DevBuf<int16_t> d_coef(f.coef.size() * sizeof(int16_t));
-            HIP_OR_THROW(hipMemcpy(d_coef.get(), f.coef.data(), f.coef.size() * sizeof(int16_t), hipMemcpyHostToDevice));
-            HIP_OR_THROW(hipEventRecord(ev_j0.get(), stream.get()));
-            DVS_OR_THROW(dvs_jpeg_reconstruct(stream.get(), &desc, d_coef.get(), full8.get()));
-            HIP_OR_THROW(hipEventRecord(ev_j1.get(), stream.get()));
-            HIP_OR_THROW(hipEventSynchronize(ev_j1.get()));          // the coefficients are freed at the end of this scope
-            float ms = 0;
-            HIP_OR_THROW(hipEventElapsedTime(&ms, ev_j0.get(), ev_j1.get()));
-            recon_ms += ms;
-        } else if (kind[i] == gsdata::ImageKind::PNG) {
-            DecodeAhead::Result r = ahead.take(job_at++);
-            if (!r.ok) { logf_("load_train_data('%s'): %s", path.c_str(), r.err.c_str()); return false; }
-            const gspng::Frame& f = r.png;
-            if (f.width != w || f.height != h) {
-                logf_("load_train_data('%s'): %s is %dx%d but its camera %u is %dx%d", path.c_str(), ahead.file(job_at - 1).c_str(), f.width, f.height, c.id, w, h);
-                return false;
-            }
-            if (gspng::has_alpha(f)) ++n_alpha;
-            png_to_device(f, full8.get(), cfg.useMask ? &alpha8 : nullptr);
-        } else {
-            if (!gsdata::read_image(ds, i, &px, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-            planar.resize(3 * p0);                              // the file is [H][W][3], the trainer's views are planar [3][H][W]
-            for (size_t q = 0; q < p0; ++q) for (int k = 0; k < 3; ++k) planar[(size_t)k * p0 + q] = px[3 * q + k];
-            HIP_OR_THROW(hipMemcpy(full8.get(), planar.data(), 3 * p0, hipMemcpyHostToDevice));
-        }
-        // under useMask, a PNG mask and / or a picture's alpha are combined on the device into mask8, bytes in {0, 1} (dvs_mask_combine);
-        // a PGM mask or none beside a picture without alpha stays on the path it always took
-        DevBuf<uint8_t> mask8;
-        if (cfg.useMask && (mask_kind[i] == gsdata::MaskKind::PNG || alpha8)) {
-            mask8.alloc(p0);
-            if (mask_kind[i] == gsdata::MaskKind::PNG) {
-                DecodeAhead::Result r = ahead.take(job_at++);
-                if (!r.ok) { logf_("load_train_data('%s'): %s", path.c_str(), r.err.c_str()); return false; }
-                const gspng::Frame& f = r.png;
-                const std::string& file = ahead.file(job_at - 1);
-                if (f.color_type != 0 && f.color_type != 4) {
-                    logf_("load_train_data('%s'): mask %s has colour type %d; a PNG mask must be grayscale or grayscale with alpha (types 0 and 4)", path.c_str(), file.c_str(), f.color_type);
-                    return false;
-                }
-                if (f.width != w || f.height != h) {
-                    logf_("load_train_data('%s'): %s is %dx%d but its camera is %dx%d", path.c_str(), file.c_str(), f.width, f.height, w, h);
-                    return false;
-                }
-                DevBuf<uint8_t> gray3(3 * p0), mask_alpha;
-                png_to_device(f, gray3.get(), &mask_alpha);
-                DVS_OR_THROW(dvs_mask_combine(stream.get(), p0, gray3.get(), mask_alpha.get(), nullptr, mask8.get(), nullptr));
-                if (alpha8) DVS_OR_THROW(dvs_mask_combine(stream.get(), p0, alpha8.get(), nullptr, mask8.get(), mask8.get(), nullptr));
-                HIP_OR_THROW(hipStreamSynchronize(stream.get()));    // gray3 and mask_alpha are freed at the end of this scope
-            } else {
-                if (!gsdata::read_mask(ds, i, &mk, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-                HIP_OR_THROW(hipMemcpy(mask8.get(), mk.data(), p0, hipMemcpyHostToDevice));
-                DVS_OR_THROW(dvs_mask_combine(stream.get(), p0, alpha8.get(), nullptr, mask8.get(), mask8.get(), nullptr));
-            }
-        }
-        if (is_distorted(c)) {                                  // full8 := the pinhole camera's view; mask := valid and, with useMask, trainable
-            const double prm[8] = {c.fx, c.fy, c.cx, c.cy, c.dist[0], c.dist[1], c.dist[2], c.dist[3]};      // the camera in OPENCV's order (absent coefficients are 0)
-            dvs_undistort_desc desc;
-            if (dvs_undistort_desc_from_colmap(4, prm, w, h, &desc) != DVS_OK) {
-                logf_("load_train_data('%s'): the parameters of camera %u (%s) do not round to finite fp32 values", path.c_str(), c.id, gsdata::model_name(c.model));
-                return false;
-            }
-            DevBuf<uint8_t> pinhole(3 * p0), d_mk;
-            if (mask8) d_mk = std::move(mask8);
-            else if (cfg.useMask) {
-                if (!gsdata::read_mask(ds, i, &mk, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-                d_mk.alloc(p0);
-                HIP_OR_THROW(hipMemcpy(d_mk.get(), mk.data(), p0, hipMemcpyHostToDevice));
-            }
-            mask.alloc(p0 * sizeof(float));
-            HIP_OR_THROW(hipEventRecord(ev_u0.get(), stream.get()));
-            DVS_OR_THROW(dvs_undistort_view(stream.get(), &desc, 3, full8.get(), d_mk.get(), pinhole.get(), mask.get(), d_invalid.get()));
-            HIP_OR_THROW(hipEventRecord(ev_u1.get(), stream.get()));
-            HIP_OR_THROW(hipEventSynchronize(ev_u1.get()));          // the source bytes and the source mask are freed below
-            float ms = 0;
-            HIP_OR_THROW(hipEventElapsedTime(&ms, ev_u0.get(), ev_u1.get()));
-            undistort_ms += ms;
-            undistort_pixels += p0;
-            full8 = std::move(pinhole);
-        }
-        if (!(u8 && d == 1)) {
-            t.alloc(img * sizeof(float));
-            const dvs_downsample_view dv{full8.get(), t.get()};
-            DVS_OR_THROW(dvs_downsample_views(stream.get(), &dv, 1, 3, w, h, d, 1));
-        }
-        if (masked) {                                           // > 127 trains; a level mask keeps the box filter's fractional weights
-            if (!is_distorted(c) && mask8) {                    // the device's mask as the floats a view keeps
-                mask.alloc(p0 * sizeof(float));
-                DVS_OR_THROW(dvs_mask_combine(stream.get(), p0, nullptr, nullptr, mask8.get(), nullptr, mask.get()));
-                HIP_OR_THROW(hipStreamSynchronize(stream.get()));    // mask8 is freed at the end of the iteration
-            } else if (!is_distorted(c)) {                      // (a distorted view's mask came out of the undistortion)
-                if (cfg.useMask) {
-                    if (!gsdata::read_mask(ds, i, &mk, &err)) { logf_("load_train_data('%s'): %s", path.c_str(), err.c_str()); return false; }
-                    mkf.assign(mk.begin(), mk.end());
-                } else {
-                    mkf.assign(p0, 1.f);                        // a pinhole view beside distorted ones, no mask files asked for
-                }
-                mask.alloc(p0 * sizeof(float));
-                HIP_OR_THROW(hipMemcpy(mask.get(), mkf.data(), p0 * sizeof(float), hipMemcpyHostToDevice));
-            }
-            if (d > 1) {
-                DevBuf<float> md(P * sizeof(float));
-                const dvs_downsample_view dv{mask.get(), md.get()};
-                DVS_OR_THROW(dvs_downsample_views(stream.get(), &dv, 1, 1, w, h, d, 0));
-                HIP_OR_THROW(hipStreamSynchronize(stream.get()));
-                mask = std::move(md);
-            }
-        }
-        if (t) {
-            store_view(std::move(t), std::move(mask));
-            if (!u8) HIP_OR_THROW(hipStreamSynchronize(stream.get()));       // (u8: store_view has synchronised) full8 was read until here
-        } else {
-            views.push_back(View{DevBuf<float>(), std::move(full8), std::move(mask)});
-        }
-        float R[9];
-        gsdata::rotation_of(im, R);
-        const float t3[3] = {(float)im.t[0], (float)im.t[1], (float)im.t[2]};
-        dvs_camera cam, camd;
-        DVS_OR_THROW(dvs_make_camera_intrinsics(R, t3, c.fx, c.fy, c.cx, c.cy, w, h, &cam));
-        DVS_OR_THROW(dvs_camera_downscale(&cam, d, &camd));
-        cams.push_back(camd);
-        cam_names.push_back(std::filesystem::path(im.name).stem().string());
-    }
-    if (rank == 0) {
-        char lvl[64] = "";
-        if (factor[0] > 1) snprintf(lvl, sizeof lvl, " -> %dx%d (1/%d)", W, H, factor[0]);
-        logf_("dataset: %zu cameras (%s), %dx%d%s, %d points (%zu dropped)", ds.images.size(), one_model ? gsdata::model_name(model) : undistorted ? "mixed models" : "mixed pinhole models",
-              W0, H0, lvl, n_pts, ds.dropped);
-        if (n_jpeg)
-            logf_("dataset: jpeg: %zu of %zu images, entropy decode %.3f ms (host, %d threads, wall), reconstruction %.3f ms (device, events)", n_jpeg,
-                  ds.images.size(), ahead.wall_ms(false), load_threads, recon_ms);
-        if (n_png + n_png_masks)
-            logf_("dataset: png: %zu of %zu images, %zu masks, inflate %.3f ms (host, %d threads, wall), reconstruction %.3f ms (device, events)", n_png,
-                  ds.images.size(), n_png_masks, ahead.wall_ms(true), load_threads, png_ms);
-        if (n_alpha && !cfg.useMask)
-            logf_("dataset: png: %zu of %zu images have alpha; it is ignored without useMask (with it, alpha > 127 is ANDed into the mask)", n_alpha, ds.images.size());
-        if (undistorted) {
-            uint32_t invalid = 0;
-            HIP_OR_THROW(hipMemcpy(&invalid, d_invalid.get(), sizeof invalid, hipMemcpyDeviceToHost));
-            std::string names;
-            for (int m = 2; m <= 4; ++m) if (distorted_models[m]) names += std::string(names.empty() ? "" : ", ") + gsdata::model_name(m);
-            logf_("dataset: undistort: %zu of %zu images (%s), %.3f ms (device, events), %u of %llu pixels have no source and are masked out", n_distorted,
-                  ds.images.size(), names.c_str(), undistort_ms, invalid, (unsigned long long)undistort_pixels);
-        }
-    }
-    // 4. the points, 5. their 3-NN scales and the initial parameters, straight into the parameter arrays
-    {
-        DevBuf<uint8_t> d_rgb((size_t)n_pts * 3 + 16);
-        DevBuf<float> d_dist2((size_t)n_pts * sizeof(float) + 16);
-        DevBuf<void> d_knn(dvs_knn_scratch_bytes(n_pts));
-        float* const pos = d_param[P_POS].get();
-        HIP_OR_THROW(hipMemcpy(pos, ds.xyz.data(), (size_t)n_pts * 3 * sizeof(float), hipMemcpyHostToDevice));
-        HIP_OR_THROW(hipMemcpy(d_rgb.get(), ds.rgb.data(), (size_t)n_pts * 3, hipMemcpyHostToDevice));
-        const auto t_init = std::chrono::steady_clock::now();
-        DVS_OR_THROW(dvs_knn_mean_dist2(stream.get(), n_pts, pos, d_knn.get(), d_dist2.get()));
-        DVS_OR_THROW(dvs_init_from_points(stream.get(), n_pts, pos, d_rgb.get(), d_dist2.get(), d_param[P_SH0].get(), d_param[P_OPA].get(),
-                                          d_param[P_SCALE].get(), d_param[P_ROT].get()));
-        HIP_OR_THROW(hipStreamSynchronize(stream.get()));
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_init).count();
-        if (rank == 0) logf_("init: 3-NN scales for %d points: %.3f ms", n_pts, ms);
-    }
-    finish_load([&](std::vector<float> (&init)[6]) {          // the device's initialisation, kept on the host too (resetGaussian, getPoints3D)
-        for (int g = 0; g < 6; ++g) {
-            init[g].assign((size_t)n_pts * kWidth[g], 0.f);
-            if (g != P_SHN) HIP_OR_THROW(hipMemcpy(init[g].data(), d_param[g].get(), init[g].size() * sizeof(float), hipMemcpyDeviceToHost));
-        }
-    }, "point-cloud", [&](bool resumed) {
-        if (cfg.verbose && rank == 0)
-            logf_("dataset scene: %d splats, %zu cameras @ %dx%d, SH degree %d%s", n, cams.size(), W, H, sh_max, resumed ? " (resumed; cameras and images from the dataset)" : "");
-    });
-    evaluate(false);                                            // where the point-cloud start stands on the held-out views (evaluation on, rank 0)
     return true;
 }

@@ -1,13 +1,59 @@
 // trainer_render.cpp — rendered views as JPEG files: the selected cameras through the evaluation context, the forward DCT and
 // quantisation on the device (dvs_jpeg_encode_views), the entropy coder on host threads (jpeg_write.hpp). And as PNG files (colour,
 // 16-bit depth, alpha): sample conversion and the per-row filter choice on the device (dvs_png_encode_views), deflate on host threads
-// (png_io.hpp write_png).
+// (png_io.hpp write_png). Both formats hand their files to write_files, the one host-thread fan-out.
 #include "trainer.hpp"
 #include <atomic>
 #include <thread>
 #include "jpeg_write.hpp"
 #include "png_io.hpp"
 #include "../../include/dvs_image.h"
+
+namespace {
+bool write_file(const std::string& file, const std::string& data) {
+    FILE* f = fopen(file.c_str(), "wb");
+    bool ok = f && fwrite(data.data(), 1, data.size(), f) == data.size();
+    if (f && fclose(f) != 0) ok = false;
+    return ok;
+}
+
+// Files written by host threads. code(task, &out, &err) -> bool produces task's bytes, file_of(task) names its file; the tasks are handed
+// out one at a time, so any number of threads finishes them all: up to min(limit, tasks), the calling thread among them, and a thread
+// that cannot be started is not needed. A worker never throws: a failed allocation inside a task becomes that task's error, `oom`.
+// -> per task the bytes written (0 with its error set), the threads used and the wall time of it all.
+struct Written { std::vector<size_t> bytes; std::vector<std::string> errs; int threads = 1; double host_ms = 0; };
+template <class Code, class FileOf>
+Written write_files(int tasks, int limit, const char* oom, const Code& code, const FileOf& file_of) {
+    const auto t_host = std::chrono::steady_clock::now();
+    Written w;
+    w.bytes.assign((size_t)tasks, 0);
+    w.errs.resize((size_t)tasks);
+    std::atomic<int> next{0};
+    const auto work = [&]() noexcept {
+        for (int t = next++; t < tasks; t = next++) {
+            try {
+                std::string out;
+                if (!code(t, &out, &w.errs[(size_t)t])) continue;
+                const std::string& file = file_of(t);
+                if (write_file(file, out)) w.bytes[(size_t)t] = out.size();
+                else w.errs[(size_t)t] = "cannot write " + file;
+            } catch (...) {
+                try { w.errs[(size_t)t] = oom; } catch (...) {}
+            }
+        }
+    };
+    std::vector<std::thread> workers;
+    try {
+        workers.reserve((size_t)limit);
+        for (int t = 1; t < std::min(limit, tasks); ++t) workers.emplace_back(work);
+    } catch (...) {}
+    w.threads = (int)workers.size() + 1;
+    work();
+    for (std::thread& t : workers) t.join();
+    w.host_ms = ms_since(t_host);
+    return w;
+}
+}  // namespace
 
 void GaussianTrainerScene::Impl::setup_render() {
     render_views = env_int("DVS_RENDER_VIEWS", cfg.renderViews) & (RENDER_TEST | RENDER_TRAIN);
@@ -52,8 +98,8 @@ std::string GaussianTrainerScene::Impl::camera_name(int c) const {
 }
 
 // cameras `which` rendered from the current parameters and written to `files`: per pass of for_each_eval_pass (the sky composited),
-// ONE encode launch (timed by events), one copy of the coefficients, then up to DVS_LOAD_THREADS host threads that code one
-// view each at a time and write its file. Synchronous. -> false when a file could not be coded or written (the others are still written).
+// ONE encode launch (timed by events), one copy of the coefficients, then write_files codes one view per task.
+// Synchronous. -> false when a file could not be coded or written (the others are still written).
 bool GaussianTrainerScene::Impl::render_to_jpeg(const std::vector<int>& which, const std::vector<std::string>& files, RenderStats* stats) {
     ensure_eval_ctx();
     dvs_jpeg_desc desc;
@@ -61,14 +107,7 @@ bool GaussianTrainerScene::Impl::render_to_jpeg(const std::vector<int>& which, c
     const size_t count = dvs_jpeg_encode_coef_count(&desc), img = 3 * (size_t)W * H;
     d_render_coef.reserve((size_t)eval_views * count * sizeof(int16_t));
     if (render_coef_host.size() < (size_t)eval_views * count) render_coef_host.resize((size_t)eval_views * count);
-    if (!ev_render0)
-        for (Event* e : {&ev_render0, &ev_render1}) { hipEvent_t ev = nullptr; HIP_OR_THROW(hipEventCreate(&ev)); e->reset(ev); }
-    const int load_threads = std::max(1, std::min(env_int("DVS_LOAD_THREADS", 8), 16));     // never the machine's CPU count
-    gsjpeg::Frame shape;                                                     // what every view's frame shares
-    shape.width = W; shape.height = H; shape.components = 3;
-    shape.hs[0] = desc.hs; shape.vs[0] = desc.vs;
-    for (int c = 0; c < 3; ++c) { shape.blocks_w[c] = desc.blocks_w[c]; shape.blocks_h[c] = desc.blocks_h[c]; shape.offset[c] = desc.offset[c]; }
-    memcpy(shape.quant, desc.quant, sizeof shape.quant);
+    const int hs[3] = {desc.hs, 1, 1}, vs[3] = {desc.vs, 1, 1};             // (the chroma components are sampled 1x1)
     bool all_ok = true;
     for_each_eval_pass(splats(), which, true, [&](const EvalPass& p) {
         const int first = p.first, nb = p.nb;
@@ -78,47 +117,20 @@ bool GaussianTrainerScene::Impl::render_to_jpeg(const std::vector<int>& which, c
             images[k] = p.images + (size_t)k * img;
             coefs[k] = d_render_coef.get() + (size_t)k * count;
         }
-        HIP_OR_THROW(hipEventRecord(ev_render0.get(), stream.get()));
+        render_timer.begin(stream.get());
         DVS_OR_THROW(dvs_jpeg_encode_views(stream.get(), &desc, images, coefs, nb));
-        HIP_OR_THROW(hipEventRecord(ev_render1.get(), stream.get()));
+        render_timer.end(stream.get());
         HIP_OR_THROW(hipMemcpyAsync(render_coef_host.data(), d_render_coef.get(), (size_t)nb * count * sizeof(int16_t), hipMemcpyDeviceToHost, stream.get()));
         HIP_OR_THROW(hipStreamSynchronize(stream.get()));
-        float ms = 0;
-        HIP_OR_THROW(hipEventElapsedTime(&ms, ev_render0.get(), ev_render1.get()));
-        const auto t_host = std::chrono::steady_clock::now();
-        std::vector<size_t> bytes((size_t)nb, 0);
-        std::vector<std::string> errs((size_t)nb);
-        std::atomic<int> next{0};
-        const auto work = [&]() noexcept {                                   // views are handed out one at a time: any number of threads finishes them all
-            for (int k = next++; k < nb; k = next++) {
-                try {
-                    std::string out;
-                    const std::string& file = files[(size_t)(first + k)];
-                    if (!gsjpeg::encode_coefficients(W, H, 3, shape.hs, shape.vs, shape.quant, shape.blocks_w, shape.blocks_h, shape.offset,
-                                                     render_coef_host.data() + (size_t)k * count, count, &out, &errs[(size_t)k])) continue;
-                    FILE* f = fopen(file.c_str(), "wb");
-                    if (!f || fwrite(out.data(), 1, out.size(), f) != out.size()) errs[(size_t)k] = "cannot write " + file;
-                    else bytes[(size_t)k] = out.size();
-                    if (f && fclose(f) != 0) { errs[(size_t)k] = "cannot write " + file; bytes[(size_t)k] = 0; }
-                } catch (...) {
-                    try { errs[(size_t)k] = "out of memory while coding the view"; } catch (...) {}
-                }
-            }
-        };
-        std::vector<std::thread> workers;
-        try {                                                                // a thread that cannot be started is not needed: this one works too
-            workers.reserve((size_t)load_threads);
-            for (int t = 1; t < std::min(load_threads, nb); ++t) workers.emplace_back(work);
-        } catch (...) {}
-        const int nthreads = (int)workers.size() + 1;
-        work();
-        for (std::thread& t : workers) t.join();
-        const double host_ms = ms_since(t_host);
+        const float ms = render_timer.ms();
+        const Written w = write_files(nb, load_threads(), "out of memory while coding the view", [&](int k, std::string* out, std::string* err) {
+            return gsjpeg::encode_coefficients(W, H, 3, hs, vs, desc.quant, desc.blocks_w, desc.blocks_h, desc.offset, render_coef_host.data() + (size_t)k * count, count, out, err);
+        }, [&](int k) -> const std::string& { return files[(size_t)(first + k)]; });
         for (int k = 0; k < nb; ++k) {
-            if (!errs[(size_t)k].empty()) { logf_("render @%d: camera %d: %s", step, which[(size_t)(first + k)], errs[(size_t)k].c_str()); all_ok = false; }
-            else if (stats) { stats->views += 1; stats->bytes += bytes[(size_t)k]; }
+            if (!w.errs[(size_t)k].empty()) { logf_("render @%d: camera %d: %s", step, which[(size_t)(first + k)], w.errs[(size_t)k].c_str()); all_ok = false; }
+            else if (stats) { stats->views += 1; stats->bytes += w.bytes[(size_t)k]; }
         }
-        if (stats) { stats->transform_ms += ms; stats->entropy_ms += host_ms; stats->threads = std::max(stats->threads, nthreads); }
+        if (stats) { stats->transform_ms += ms; stats->entropy_ms += w.host_ms; stats->threads = std::max(stats->threads, w.threads); }
     });
     return all_ok;
 }
@@ -146,9 +158,6 @@ bool GaussianTrainerScene::Impl::render_to_png(const std::vector<int>& which, co
     d_render_png.reserve(kCounts + (size_t)eval_views * per_view);
     if (render_png_host.size() < kCounts + (size_t)eval_views * per_view) render_png_host.resize(kCounts + (size_t)eval_views * per_view);
     if (maps) { d_render_depth.reserve((size_t)eval_views * map * sizeof(float)); d_render_alpha.reserve((size_t)eval_views * map * sizeof(float)); }
-    if (!ev_render0)
-        for (Event* e : {&ev_render0, &ev_render1}) { hipEvent_t ev = nullptr; HIP_OR_THROW(hipEventCreate(&ev)); e->reset(ev); }
-    const int load_threads = std::max(1, std::min(env_int("DVS_LOAD_THREADS", 8), 16));     // never the machine's CPU count
     const dvs_opts opts = eval_opts();
     char scale_text[32];
     snprintf(scale_text, sizeof scale_text, "%.9g", (double)render_depth_scale);
@@ -159,7 +168,7 @@ bool GaussianTrainerScene::Impl::render_to_png(const std::vector<int>& which, co
         if (maps) DVS_OR_THROW(dvs_raster_depth_views(eval_ctx.get(), stream.get(), &opts, d_render_depth.get(), d_render_alpha.get()));
         HIP_OR_THROW(hipMemsetAsync(d_render_png.get(), 0, kCounts, stream.get()));
         size_t layer_at[3] = {0, 0, 0}, at = kCounts;
-        HIP_OR_THROW(hipEventRecord(ev_render0.get(), stream.get()));
+        render_timer.begin(stream.get());
         for (int l = 0; l < 3; ++l) {
             if (files[l].empty()) continue;
             layer_at[l] = at;
@@ -172,53 +181,27 @@ bool GaussianTrainerScene::Impl::render_to_png(const std::vector<int>& which, co
             DVS_OR_THROW(dvs_png_encode_views(stream.get(), kKind[l], W, H, scales[l], images, outs, l == 1 ? (uint32_t*)d_render_png.get() : nullptr, nb));
             at += (size_t)nb * bytes_of[l];
         }
-        HIP_OR_THROW(hipEventRecord(ev_render1.get(), stream.get()));
+        render_timer.end(stream.get());
         HIP_OR_THROW(hipMemcpyAsync(render_png_host.data(), d_render_png.get(), at, hipMemcpyDeviceToHost, stream.get()));
         HIP_OR_THROW(hipStreamSynchronize(stream.get()));
-        float ms = 0;
-        HIP_OR_THROW(hipEventElapsedTime(&ms, ev_render0.get(), ev_render1.get()));
-        const auto t_host = std::chrono::steady_clock::now();
-        const int tasks = nb * n_layers;                                     // task t: view t / n_layers, layer asked[t % n_layers]
-        std::vector<size_t> bytes((size_t)tasks, 0);
-        std::vector<std::string> errs((size_t)tasks);
-        std::atomic<int> next{0};
-        const auto work = [&]() noexcept {                                   // files are handed out one at a time: any number of threads finishes them all
-            for (int t = next++; t < tasks; t = next++) {
-                try {
-                    const int k = t / n_layers, l = asked[t % n_layers];
-                    std::string out;
-                    const std::string& file = files[l][(size_t)(first + k)];
-                    if (!gspng::write_png(W, H, kDepth[l], kType[l], render_png_host.data() + layer_at[l] + (size_t)k * bytes_of[l], bytes_of[l], render_png_level,
-                                          l == 1 ? &depth_text : nullptr, &out, &errs[(size_t)t])) continue;
-                    FILE* f = fopen(file.c_str(), "wb");
-                    if (!f || fwrite(out.data(), 1, out.size(), f) != out.size()) errs[(size_t)t] = "cannot write " + file;
-                    else bytes[(size_t)t] = out.size();
-                    if (f && fclose(f) != 0) { errs[(size_t)t] = "cannot write " + file; bytes[(size_t)t] = 0; }
-                } catch (...) {
-                    try { errs[(size_t)t] = "out of memory while writing the view"; } catch (...) {}
-                }
-            }
-        };
-        std::vector<std::thread> workers;
-        try {                                                                // a thread that cannot be started is not needed: this one works too
-            workers.reserve((size_t)load_threads);
-            for (int t = 1; t < std::min(load_threads, tasks); ++t) workers.emplace_back(work);
-        } catch (...) {}
-        const int nthreads = (int)workers.size() + 1;
-        work();
-        for (std::thread& t : workers) t.join();
-        const double host_ms = ms_since(t_host);
+        const float ms = render_timer.ms();
+        // task t: view t / n_layers, layer asked[t % n_layers]
+        const Written w = write_files(nb * n_layers, load_threads(), "out of memory while writing the view", [&](int t, std::string* out, std::string* err) {
+            const int k = t / n_layers, l = asked[t % n_layers];
+            return gspng::write_png(W, H, kDepth[l], kType[l], render_png_host.data() + layer_at[l] + (size_t)k * bytes_of[l], bytes_of[l], render_png_level,
+                                    l == 1 ? &depth_text : nullptr, out, err);
+        }, [&](int t) -> const std::string& { return files[asked[t % n_layers]][(size_t)(first + t / n_layers)]; });
         for (int k = 0; k < nb; ++k) {
             bool view_ok = true;
             for (int j = 0; j < n_layers; ++j) {
                 const size_t t = (size_t)(k * n_layers + j);
-                if (!errs[t].empty()) { logf_("render @%d: camera %d: %s", step, which[(size_t)(first + k)], errs[t].c_str()); all_ok = view_ok = false; }
-                else if (stats) { stats->files += 1; stats->bytes += bytes[t]; }
+                if (!w.errs[t].empty()) { logf_("render @%d: camera %d: %s", step, which[(size_t)(first + k)], w.errs[t].c_str()); all_ok = view_ok = false; }
+                else if (stats) { stats->files += 1; stats->bytes += w.bytes[t]; }
             }
             if (stats && view_ok) stats->views += 1;
             if (stats && !files[1].empty()) { uint32_t c; memcpy(&c, render_png_host.data() + (size_t)k * sizeof c, sizeof c); stats->saturated += c; }
         }
-        if (stats) { stats->filter_ms += ms; stats->deflate_ms += host_ms; stats->threads = std::max(stats->threads, nthreads); }
+        if (stats) { stats->filter_ms += ms; stats->deflate_ms += w.host_ms; stats->threads = std::max(stats->threads, w.threads); }
     });
     return all_ok;
 }

@@ -9,7 +9,8 @@ writer with the row filters cycling 0..4:
 PNG is lossless and the loader reconstructs what png_ref defines, so nothing past the loader can tell a PNG capture from the PPM one:
 `gaussian_train` runs for a few steps with DVS_LOSS_EVERY=1 and every comparison is `==` on the log lines, with and without --useMask,
 at factor 1 and at --maxImageWidth 20 (factor 2). One OPENCV variant takes a PNG picture with a PNG mask through the undistortion; a
-truncated PNG stops the load with its message; one load thread gives the same lines as the default."""
+truncated PNG stops the load with its message; one load thread gives the same lines as the default. RGBA8 pictures beside PGM masks train
+as the PPM capture whose masks are the product of the alpha and the PGM."""
 import os
 import re
 import shutil
@@ -172,6 +173,33 @@ def test_opencv_camera_png_picture_and_png_mask_through_the_undistortion(gpu_dev
     png, ppm = run(a, MASK), run(b, MASK)
     assert "dataset: undistort: 3 of 3 images (OPENCV)" in png[3] and "dataset: png: 3 of 3 images, 3 masks" in png[3]
     _compare(png, ppm, False)
+    png, ppm = run(a, MASK + HALF), run(b, MASK + HALF)
+    _compare(png, ppm, True)
+
+
+def test_a_pgm_mask_is_anded_with_the_picture_alpha(gpu_device, captures, tmp_path, run):
+    """RGBA8 pictures whose alpha is 255 x the block masks AND masks/<stem>.pgm with other blocks, against the PPM capture whose PGM masks are
+    the product of the two"""
+    pictures, alpha = _pictures(), _masks()
+    files = []
+    for k in range(3):
+        m = np.ones((H, W), np.uint8)
+        m[5 + 2 * k:20 - k, 1 + 5 * k:12 + 6 * k] = 0
+        files.append(m)
+        both = alpha[k] & m
+        assert (both != alpha[k]).any() and (both != m).any() and both.any()
+    cameras, images, points = _sparse()
+    a, b = str(tmp_path / "png"), str(tmp_path / "ppm")
+    CR.write_dataset(a, cameras, images, points, {})
+    _write_variant(a, "rgba8", pictures, alpha)
+    os.makedirs(os.path.join(a, "masks"), exist_ok=True)
+    for k in range(3):
+        CR.write_pgm(os.path.join(a, "masks", f"view_{k}.pgm"), files[k] * 255)
+    CR.write_dataset(b, cameras, images, points, {f"view_{k}.png": pictures[k] for k in range(3)}, masks={f"view_{k}.png": (alpha[k] & files[k]) * 255 for k in range(3)})
+    png, ppm = run(a, MASK), run(b, MASK)
+    assert "dataset: png: 3 of 3 images, 0 masks" in png[3] and "have alpha" not in png[3]
+    _compare(png, ppm, False)
+    assert (png[0], png[1][0]) != (run(captures["ppm"], MASK)[0], run(captures["ppm"], MASK)[1][0])       # the alpha alone is another mask
     png, ppm = run(a, MASK + HALF), run(b, MASK + HALF)
     _compare(png, ppm, True)
 

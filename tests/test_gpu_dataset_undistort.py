@@ -7,7 +7,8 @@ pictures of smooth random content, 300 points, `gaussian_train` for 20 steps wit
 The loader undistorts A on the device into what undistort_ref defines, so nothing past the loader can tell A from B when both run with
 --useMask 1: every comparison is `==` on the log lines. A without --useMask gives the same `eval @0` (it has no mask files: the mask
 is the validity either way) and its log carries the restatement's invalid count. With source-space mask files on two views of A and the
-restatement's warped masks in B the lines are identical again. An OPENCV_FISHEYE camera stops the load with a message that names it."""
+restatement's warped masks in B the lines are identical again. Pinhole views beside a distorted one, without --useMask, train as they
+do with all-255 mask files under --useMask. An OPENCV_FISHEYE camera stops the load with a message that names it."""
 import os
 import re
 import shutil
@@ -65,19 +66,19 @@ def captures(tmp_path_factory):
 
 @pytest.fixture(scope="module")
 def run(tmp_path_factory):
-    """run(capture, extra args) -> (eval @0 line, [20 loss lines], eval @20 line, stderr), each distinct run made once"""
+    """run(capture, extra args, steps) -> (eval @0 line, [the loss lines], the last eval line, stderr), each distinct run made once"""
     cache = {}
 
-    def go(capture, extra=()):
-        key = (capture, tuple(extra))
+    def go(capture, extra=(), steps=STEPS):
+        key = (capture, tuple(extra), steps)
         if key not in cache:
             out = str(tmp_path_factory.mktemp("out") / "iteration")
-            p = subprocess.run([DRIVER, "--inputPath", capture, "--maxIteration", str(STEPS), "--eval", "--outputPath", out] + list(extra),
+            p = subprocess.run([DRIVER, "--inputPath", capture, "--maxIteration", str(steps), "--eval", "--outputPath", out] + list(extra),
                                capture_output=True, text=True, timeout=300, env=dict(os.environ, DVS_LOSS_EVERY="1"))
             assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
-            ev0, ev20 = re.findall(r"eval @0: .*", p.stderr), re.findall(rf"eval @{STEPS}: .*", p.stderr)
+            ev0, ev20 = re.findall(r"eval @0: .*", p.stderr), re.findall(rf"eval @{steps}: .*", p.stderr)
             losses = re.findall(r"Iteraions \d+, loss : [-\d.enaif+]+", p.stderr)
-            assert len(ev0) == 1 and len(ev20) == 1 and len(losses) == STEPS, p.stderr[-3000:]
+            assert len(ev0) == 1 and len(ev20) == 1 and len(losses) == steps, p.stderr[-3000:]
             assert all("nan" not in l and "inf" not in l for l in losses)
             cache[key] = (ev0[0], losses, ev20[0], p.stderr)
         return cache[key]
@@ -128,6 +129,27 @@ def test_source_masks_are_warped_with_the_view(gpu_device, captures, run):
     assert ev_a != run(captures()[0], MASK)[0]                               # the held-out view's mask file counts
     ev_h, loss_h, end_h, _ = run(a, MASK + HALF)
     assert (ev_h, loss_h, end_h) == run(b, MASK + HALF)[:3]
+
+
+def test_a_pinhole_view_beside_a_distorted_one_trains_everywhere(gpu_device, tmp_path, run):
+    """without --useMask a capture with one distorted camera carries a mask on every view, all ones on its pinhole views: the same
+    capture with an all-255 masks/<stem>.pgm on the pinhole views and --useMask gives the same lines (4 steps)"""
+    r = np.random.default_rng(12)
+    models = [("PINHOLE", [36.0, 35.0, 20.0, 12.0]), MODELS[1], ("PINHOLE", [34.0, 36.0, 19.5, 12.5])]
+    cams = [dict(id=k + 1, model=m, width=W, height=H, params=p) for k, (m, p) in enumerate(models)]
+    images = [dict(id=k + 1, q=np.array([1.0, 0.0, 0.0, 0.0]), t=np.array([0.3 * (k - 1), 0.05 * k, 0.0]), camera_id=k + 1, name=f"view_{k}.ppm") for k in range(3)]
+    points = [dict(id=k + 1, xyz=np.array([r.uniform(-1.5, 1.5), r.uniform(-1.0, 1.0), r.uniform(2.5, 4.0)]), rgb=r.integers(0, 256, 3)) for k in range(300)]
+    pixels = {f"view_{k}.ppm": U.smooth_image(W, H, 3, seed=40 + k).transpose(1, 2, 0) for k in range(3)}
+    a, b = str(tmp_path / "plain"), str(tmp_path / "ones")
+    CR.write_dataset(a, cams, images, points, pixels)
+    CR.write_dataset(b, cams, images, points, pixels, masks={f"view_{k}.ppm": np.full((H, W), 255, np.uint8) for k in (0, 2)})
+    for extra in ((), HALF):
+        ev_a, loss_a, end_a, log_a = run(a, extra, 4)
+        ev_b, loss_b, end_b, _ = run(b, MASK + extra, 4)
+        assert "dataset: 3 cameras (mixed models)" in log_a and "dataset: undistort: 1 of 3 images (RADIAL)" in log_a, log_a[-3000:]
+        assert ev_a == ev_b and loss_a[0] == loss_b[0] and len(set(loss_a)) > 1
+        if extra:                                                            # 20x12: the whole trajectory is reproducible
+            assert loss_a == loss_b and end_a == end_b
 
 
 def test_a_fisheye_camera_stops_the_load_with_its_name(gpu_device, captures, tmp_path):
