@@ -614,11 +614,18 @@ int dvs_get_view_state(dvs_ctx* c, int view, dvs_fwd_state* out) {
     return DVS_OK;
 }
 
+// What every pass over the saved lists (depth, importance, sky) checks first: the context holds a forward, of n_views views unless n_views < 0
+static int need_forward(const dvs_ctx* c, const char* who, int n_views = -1) {
+    if (c->fwd.have && (n_views < 0 || n_views == c->fwd.n_views)) return DVS_OK;
+    return fail(DVS_ERR_STATE, who, n_views < 0 ? "no forward on this context (valid after dvs_raster_forward / _views until the next forward)"
+                                                : "no matching forward on this context (valid after dvs_raster_forward / _views until the next forward)");
+}
+
 // Depth and alpha maps of the last forward: a forward-only pass over the saved lists (depth.hip); reads the state, changes none of it
 int dvs_raster_depth_views(dvs_ctx* c, void* stream, const dvs_opts* opts, float* out_depth, float* out_alpha) {
     const char* const who = "dvs_raster_depth_views";
     if (!c || !opts || !out_depth || !out_alpha) return fail(DVS_ERR_INVALID, who, "null argument");
-    if (!c->fwd.have) return fail(DVS_ERR_STATE, who, "no forward on this context (valid after dvs_raster_forward / _views until the next forward)");
+    TRY(need_forward(c, who));
     HIPCHECK(hipSetDevice(c->device));
     const dvs_fwd_state& s = c->fwd.st;
     HIPCHECK(dvs_launch_depth_views((hipStream_t)stream, s.width, s.height, s.tiles_x, s.tiles_y, c->fwd.n_views, s.ranges, s.sorted_splat, s.splat2d,
@@ -632,7 +639,7 @@ int dvs_raster_importance_views(dvs_ctx* c, void* stream, const dvs_opts* opts, 
     const char* const who = "dvs_raster_importance_views";
     if (!c || !opts || !score_sum) return fail(DVS_ERR_INVALID, who, "null argument");
     if (((uintptr_t)score_sum | (uintptr_t)score_max | (uintptr_t)hits) & 15u) return fail(DVS_ERR_INVALID, who, "score arrays must be 16-byte aligned");
-    if (!c->fwd.have) return fail(DVS_ERR_STATE, who, "no forward on this context (valid after dvs_raster_forward / _views until the next forward)");
+    TRY(need_forward(c, who));
     HIPCHECK(hipSetDevice(c->device));
     const dvs_fwd_state& s = c->fwd.st;
     HIPCHECK(dvs_launch_importance_views((hipStream_t)stream, s.width, s.height, s.tiles_x, s.tiles_y, c->fwd.n_views, s.n, s.ranges, s.sorted_splat,
@@ -670,8 +677,7 @@ static int check_sky(dvs_ctx* c, const dvs_camera* cams, int n_views, const dvs_
             return fail(DVS_ERR_INVALID, who, "cams[v].bg must be zero: the sky texture is the background (never both)");
         if (!dvs_pixel_ray_matrix(&cams[v], minv + 9 * v)) return fail(DVS_ERR_INVALID, who, "cams[v].proj is singular: no ray per pixel");
     }
-    if (!c->fwd.have || n_views != c->fwd.n_views)
-        return fail(DVS_ERR_STATE, who, "no matching forward on this context (valid after dvs_raster_forward / _views until the next forward)");
+    TRY(need_forward(c, who, n_views));
     for (int v = 0; v < n_views; ++v)
         if (c->fwd.st.width != cams[v].width || c->fwd.st.height != cams[v].height)
             return fail(DVS_ERR_STATE, who, "a camera's image size is not that of the last forward on this context");

@@ -32,8 +32,8 @@ struct __attribute__((aligned(16))) FwdLds {
 };
 // cs = (-0.5 log2e a, -log2e b, -0.5 log2e c): exp(power) = exp2(cs.x dx^2 + cs.y dx dy + cs.z dy^2)
 __device__ __forceinline__ void lds_put(FwdLds& L, int t, float2 xy, float4 co, float3 col) {
-    L.a[t] = make_float4(xy.x, xy.y, -0.72134752044448170f * co.x, -1.4426950408889634f * co.y);
-    L.b[t] = make_float4(-0.72134752044448170f * co.z, co.w, col.x, col.y);
+    L.a[t] = make_float4(xy.x, xy.y, DVS_CS_SQ * co.x, DVS_CS_XY * co.y);
+    L.b[t] = make_float4(DVS_CS_SQ * co.z, co.w, col.x, col.y);
     L.c[t].x = col.z;
 }
 
@@ -246,7 +246,7 @@ hipError_t dvs_launch_render_fwd(hipStream_t st, int W, int H, int tiles_x, int 
                                  uint32_t* n_contrib, uint32_t* live_splat, uint32_t* live_pos, uint64_t* take_masks, uint64_t take_cap, uint32_t* ranges_out) {
     const int tiles_pv = tiles_x * tiles_y, num_tiles = tiles_pv * n_views;
     if (num_tiles <= 0) return hipSuccess;
-    const int grid = ((num_tiles + 7) >> 3) << 3;
+    const int grid = replay_grid(num_tiles);
     if (take_masks)
         hipLaunchKernelGGL(k_render_fwd<true>, dim3(grid), dim3(RB), 0, st, make_view_bg(n_views, bgs), W, H, tiles_x, tiles_pv, num_tiles,
                            (const uint2*)ranges, (uint2*)ranges_out, sorted_splat, (const float4*)splat2d, out_color, final_T, n_contrib, live_splat, live_pos, take_masks, take_cap);

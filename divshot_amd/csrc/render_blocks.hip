@@ -66,8 +66,8 @@ __device__ __forceinline__ void stage_blocks(BlockLds& L, const uint32_t* __rest
         const float bl = splat2d[4 * (size_t)id + 2].x;
         const float a = r0.z, b = r0.w, c = r1.x, op = r1.y;
         if (sub == 0) {
-            L.xyc[e] = make_float4(r0.x, r0.y, -0.72134752044448170f * a, -1.4426950408889634f * b);
-            L.zoir[e] = make_float4(-0.72134752044448170f * c, op, bl, r1.z);
+            L.xyc[e] = make_float4(r0.x, r0.y, DVS_CS_SQ * a, DVS_CS_XY * b);
+            L.zoir[e] = make_float4(DVS_CS_SQ * c, op, bl, r1.z);
             L.cog[e] = make_float4(a, b, c, r1.w);
             L.id[e] = id;
         }
@@ -321,7 +321,7 @@ hipError_t dvs_launch_render_bwd_blocks(hipStream_t st, int W, int H, int tiles_
                                         const uint32_t* n_contrib, const float* dL_dout, float* grad_rows, int absgrad, int grad_mode) {
     const int tiles_pv = tiles_x * tiles_y, num_tiles = tiles_pv * n_views;
     if (num_tiles <= 0) return hipSuccess;
-    const int grid = ((num_tiles + 7) >> 3) << 3;
+    const int grid = replay_grid(num_tiles);
     const int lineage = grad_mode == 1 ? 1 : 0;
 #define DVS_RBB(KERNEL)                                                                                                     \
     hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(RB), 0, st, make_view_bg(n_views, bgs), W, H, tiles_x, tiles_pv, num_tiles, \

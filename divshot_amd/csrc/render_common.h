@@ -1,4 +1,4 @@
-// render_common.h — device helpers shared by the composite kernels (render.hip, render_blocks.hip, render_tr.hip).
+// render_common.h — device helpers shared by the composite kernels (render.hip, render_blocks.hip, render_tr.hip) and the replay passes (replay_walk.h).
 #pragma once
 #include "dvs_device.h"
 
@@ -25,6 +25,12 @@ __device__ __forceinline__ int tile_of_block(int b, int num_tiles) {
     const int chunk = (num_tiles + 7) >> 3;
     return (b & 7) * chunk + (b >> 3);
 }
+// ... and the grid that goes with it: eight bands of equal length (workgroups with tile_of_block() >= num_tiles have no tile)
+static inline int replay_grid(int num_tiles) { return ((num_tiles + 7) >> 3) << 3; }
+
+// The staged conic: exp(-0.5 (a dx^2 + c dy^2) - b dx dy) = exp2(cs.x dx^2 + cs.y dx dy + cs.z dy^2), cs = (CS_SQ a, CS_XY b, CS_SQ c)
+constexpr float DVS_CS_SQ = -0.72134752044448170f;      // -0.5 log2(e)
+constexpr float DVS_CS_XY = -1.4426950408889634f;       // -log2(e)
 
 // The gfx950 packing swaps behind the composite backwards' cross-lane sums: two registers of per-lane partials become one.
 // v_permlane32_swap: lanes 32-63 of A <-> lanes 0-31 of B; v_permlane16_swap: odd 16-lane rows of A <-> even rows of B.

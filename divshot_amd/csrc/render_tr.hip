@@ -80,8 +80,8 @@ __device__ __forceinline__ void tr_stage(TrLds<BK>& L, const float4* __restrict_
         const float4 r0 = splat2d[4 * (size_t)id], r1 = splat2d[4 * (size_t)id + 1], r2 = splat2d[4 * (size_t)id + 2], r3 = splat2d[4 * (size_t)id + 3];
         const float a = r0.z, b = r0.w, c = r1.x, op = r1.y;
         if (sub == 0) {
-            L.ea[e] = make_float4(r0.x, r0.y, -0.72134752044448170f * a, -1.4426950408889634f * b);
-            L.eb[e] = make_float4(-0.72134752044448170f * c, op, r1.z, r1.w);
+            L.ea[e] = make_float4(r0.x, r0.y, DVS_CS_SQ * a, DVS_CS_XY * b);
+            L.eb[e] = make_float4(DVS_CS_SQ * c, op, r1.z, r1.w);
             L.ec[e] = make_float4(r2.x, a, b, c);
             L.idop[parity][e] = make_uint2(id, __float_as_uint(op));
         }
@@ -369,7 +369,7 @@ hipError_t dvs_launch_render_bwd_tr(hipStream_t st, int W, int H, int tiles_x, i
                                     const uint32_t* live_splat, const uint32_t* live_pos) {
     const int tiles_pv = tiles_x * tiles_y, num_tiles = tiles_pv * n_views;
     if (num_tiles <= 0) return hipSuccess;
-    const int grid = ((num_tiles + 7) >> 3) << 3;
+    const int grid = replay_grid(num_tiles);
     const int lineage = grad_mode == 1 ? 1 : 0;
 #define DVS_TR(A, LN, BKV)                                                                                                              \
     hipLaunchKernelGGL((k_render_bwd_tr<A, LN, BKV>), dim3(grid), dim3(RB), 0, st, make_view_bg(n_views, bgs), W, H, tiles_x, tiles_pv, \

@@ -20,16 +20,13 @@
 //                        dL/dalpha_i -= h final_T / (1 - alpha_i), chained exactly as k_render_bwd_tr chains its own dL/dalpha:
 //                        v5 = G dL/dalpha, gated by the 0.99 cap unless DVS_GRAD_LINEAGE, the moments of v5 about the splat's mean with
 //                        d = mean - pixel times the opacity into row columns 0..4, the plain sum into column 5 (dvs_get_bwd_intermediates).
-//                        This is the term the constant-bg path forms inside the composite backward from bg_dot. Shaped like
-//                        importance.hip: one 256-thread workgroup per (view, tile), entries staged through LDS in batches of 256, alpha
-//                        formed by the operations of k_render_fwd in its order; no back-to-front T: final_T is saved and alpha_i is
-//                        recomputed. Per (wave, entry): ballot first, then the six sums over the wave (four DPP steps per 16-lane row,
-//                        four v_readlane), lane 0 stores them in the wave's LDS slot; after the batch thread j folds the four waves'
-//                        slots of entry j and issues at most one non-returning atomic per value. Columns 9, 10 (abs-grad) are NOT
-//                        touched: the densification statistic stays that of the colour path. Pixels with n_contrib == 0 or h == 0 walk nothing.
+//                        This is the term the constant-bg path forms inside the composite backward from bg_dot. A replay pass
+//                        (replay_walk.h) that accumulates six sums per entry the way importance.hip accumulates its three; no
+//                        back-to-front T: final_T is saved and alpha_i is recomputed. Columns 9, 10 (abs-grad) are NOT touched: the
+//                        densification statistic stays that of the colour path. Pixels with n_contrib == 0 or h == 0 walk nothing.
 #include "dvs_device.h"
 #include "dvs_kernels.h"
-#include "render_common.h"
+#include "replay_walk.h"
 #include "pixel_ray.h"
 
 typedef PixelRays SkyRays;
@@ -78,17 +75,12 @@ k_sky_forward(SkyRays rays_arg /* MUST stay the first parameter: read through sk
     }
 }
 
-template <int CTRL> __device__ __forceinline__ float sky_dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));       // (a source outside the 16-lane row reads 0)
-}
-template <int CTRL> __device__ __forceinline__ int sky_dpp_i(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-
 // one step of the segmented inclusive scan inside a 16-lane row: lane l adds lane l - D unless a run starts between them
 template <int D> __device__ __forceinline__ void sky_scan_step(float (&val)[12], int& stop) {
-    const int ostop = sky_dpp_i<0x110 + D>(stop);               // row_shr:D
+    const int ostop = wave_dpp<0x110 + D>(stop);               // row_shr:D
 #pragma unroll
     for (int k = 0; k < 12; ++k) {
-        const float o = sky_dpp<0x110 + D>(val[k]);
+        const float o = wave_dpp<0x110 + D>(val[k]);
         val[k] = stop ? val[k] : val[k] + o;
     }
     stop |= ostop;                                              // (lanes l < D of the row already hold the stop of the row's first lane)
@@ -120,7 +112,7 @@ k_sky_backward_tex(SkyRays rays_arg /* MUST stay the first parameter */, int W, 
         }
     }
     const int lane16 = threadIdx.x & 15;
-    const int prev = sky_dpp_i<0x111>(key), next = sky_dpp_i<0x101>(key);          // row_shr:1, row_shl:1
+    const int prev = wave_dpp<0x111>(key), next = wave_dpp<0x101>(key);          // row_shr:1, row_shl:1
     int stop = (lane16 == 0 || prev != key) ? 1 : 0;            // a run starts here
     const bool last = lane16 == 15 || next != key;              // ... and ends here
     sky_scan_step<1>(val, stop);
@@ -139,21 +131,9 @@ k_sky_backward_tex(SkyRays rays_arg /* MUST stay the first parameter */, int W, 
 }
 
 struct __attribute__((aligned(16))) SkyRowsLds {
-    float4 a[RB];       // mean x, mean y, cs.x, cs.y        (as importance.hip)
-    float4 b[RB];       // cs.z, opacity, -, -
-    float acc[RB / 64][6][RB];                                  // [wave][value][entry of the batch]
-    uint32_t wmax[RB / 64];
+    ReplayLds walk;
+    float acc[6][RB / 64][RB];                                  // [value][wave][entry of the batch]
 };
-
-__device__ __forceinline__ float sky_wave_sum(float v) {        // all 64 lanes active; the result is wave-uniform
-    v += sky_dpp<0xB1>(v);            // quad_perm [1,0,3,2]
-    v += sky_dpp<0x4E>(v);            // quad_perm [2,3,0,1]
-    v += sky_dpp<0x141>(v);           // row_half_mirror
-    v += sky_dpp<0x140>(v);           // row_mirror
-    const int b = __float_as_int(v);
-    return (__int_as_float(__builtin_amdgcn_readlane(b, 0)) + __int_as_float(__builtin_amdgcn_readlane(b, 16))) +
-           (__int_as_float(__builtin_amdgcn_readlane(b, 32)) + __int_as_float(__builtin_amdgcn_readlane(b, 48)));
-}
 
 template <bool LINEAGE>
 __global__ void __launch_bounds__(RB)
@@ -162,77 +142,59 @@ k_sky_backward_rows(int W, int H, int tiles_x, int tiles_per_view, int num_tiles
                     const uint32_t* __restrict__ n_contrib, const float* __restrict__ dL_dout /*[views,3,H,W]*/,
                     const float* __restrict__ sky_rgb /*[views,3,H,W]*/, float* __restrict__ grow /*[views,n,12]*/) {
     __shared__ SkyRowsLds L;
-    const int tile_g = tile_of_block(blockIdx.x, num_tiles);
-    if (tile_g >= num_tiles) return;                                       // (whole workgroup: no barrier is skipped by a part of it)
-    const int view = tile_g / tiles_per_view, tile = tile_g - view * tiles_per_view;
-    const int tx = tile % tiles_x, ty = tile / tiles_x;
+    const ReplayTile rt = replay_tile(W, H, tiles_x, tiles_per_view, num_tiles, ranges);
+    if (rt.none) return;
     const int t = threadIdx.x, wave = t >> 6;
-    const int px = tx * DVS_TILE + (t & 15), py = ty * DVS_TILE + (t >> 4);
-    const bool inside = px < W && py < H;
     const size_t P = (size_t)W * H;
-    const size_t pix = (size_t)py * W + px;
     float c5 = 0.f;                                                        // -h final_T: dL/dalpha_i = c5 / (1 - alpha_i)
-    if (inside) {
-        const float* const g = dL_dout + (size_t)view * 3 * P + pix;
-        const float* const s = sky_rgb + (size_t)view * 3 * P + pix;
+    if (rt.inside) {
+        const float* const g = dL_dout + (size_t)rt.view * 3 * P + rt.pix;
+        const float* const s = sky_rgb + (size_t)rt.view * 3 * P + rt.pix;
         const float h = (s[0] * g[0] + s[P] * g[P]) + s[2 * P] * g[2 * P];
-        c5 = -(final_T[(size_t)view * P + pix] * h);
+        c5 = -(final_T[rt.gpix] * h);
     }
-    const uint2 range = ranges[tile_g];
-    const uint32_t total = range.y - range.x;
-    const uint32_t mine = (inside && c5 != 0.f) ? min(n_contrib[(size_t)view * P + pix], total) : 0u;   // entries this pixel walks; never more than the tile's list holds
-    uint32_t wm = mine;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) wm = max(wm, (uint32_t)__shfl_xor((int)wm, d, 64));
-    if ((t & 63) == 0) L.wmax[wave] = wm;
-    __syncthreads();
-    const uint32_t need = max(max(L.wmax[0], L.wmax[1]), max(L.wmax[2], L.wmax[3]));   // entries the workgroup stages
+    const uint32_t mine = replay_mine(rt, rt.inside && c5 != 0.f, n_contrib);
+    uint32_t wm;
+    const uint32_t need = replay_need(L.walk, mine, &wm);
 
-    const float pxf = (float)px, pyf = (float)py;
+    const float pxf = (float)rt.px, pyf = (float)rt.py;
     for (uint32_t base = 0; base < need; base += RB) {
         const uint32_t cnt = min((uint32_t)RB, need - base);
         uint32_t id = 0;
         float op = 0.f;
         if ((uint32_t)t < cnt) {
-            id = sorted_splat[range.x + base + t];                         // batch-wide value: view * n + splat, the record's and the row's index
-            const float4 r0 = splat2d[4 * (size_t)id], r1 = splat2d[4 * (size_t)id + 1];
+            id = sorted_splat[rt.range.x + base + t];                      // batch-wide value: view * n + splat, the record's and the row's index
+            const float4 r1 = splat2d[4 * (size_t)id + 1];
             op = r1.y;
-            L.a[t] = make_float4(r0.x, r0.y, -0.72134752044448170f * r0.z, -1.4426950408889634f * r0.w);
-            L.b[t] = make_float4(-0.72134752044448170f * r1.x, r1.y, 0.f, 0.f);
+            replay_stage(L.walk, t, splat2d[4 * (size_t)id], r1, 0.f);
 #pragma unroll
-            for (int w = 0; w < RB / 64; ++w)
+            for (int k = 0; k < 6; ++k)
 #pragma unroll
-                for (int k = 0; k < 6; ++k) L.acc[w][k][t] = 0.f;
+                for (int w = 0; w < RB / 64; ++w) L.acc[k][w][t] = 0.f;
         }
         __syncthreads();
-        const uint32_t stop = mine > base ? min(cnt, mine - base) : 0u;
-        const uint32_t wave_stop = wm > base ? min(cnt, wm - base) : 0u;   // wave-uniform: the cross-lane steps below run with all 64 lanes
+        const uint32_t stop = replay_stop(mine, base, cnt);
+        const uint32_t wave_stop = replay_stop(wm, base, cnt);             // wave-uniform: the cross-lane steps below run with all 64 lanes
         for (uint32_t j = 0; j < wave_stop; ++j) {
-            const float4 A = L.a[j], B = L.b[j];
-            const float dx = A.x - pxf, dy = A.y - pyf;                    // d = mean - pixel
-            const float p2 = __builtin_fmaf(B.x * dy, dy, __builtin_fmaf(A.w, dy, A.z * dx) * dx);
-            const float G = __builtin_amdgcn_exp2f(p2);
-            const float oa = B.y * G;
-            const float alpha = fminf(DVS_ALPHA_MAX, oa);
-            const bool take = j < stop && !(p2 > 0.f || alpha < DVS_ALPHA_MIN);
+            const ReplayEntry e = replay_entry(L.walk.a[j], L.walk.b[j], pxf, pyf);
+            const bool take = j < stop && e.take;
             // DVS_GRAD_TRUE: the 0.99 clamp blocks the gradient; DVS_GRAD_LINEAGE: it passes as if alpha = opacity * G (k_render_bwd_tr)
-            const bool gate = LINEAGE ? take : (take && !(oa > DVS_ALPHA_MAX));
+            const bool gate = LINEAGE ? take : (take && !(e.oa > DVS_ALPHA_MAX));
             if (__ballot(gate) == 0ull) continue;
-            const float v5 = gate ? G * (c5 * __builtin_amdgcn_rcpf(1.f - alpha)) : 0.f;
-            const float vx = v5 * dx, vy = v5 * dy;
-            const float s0 = sky_wave_sum(vx), s1 = sky_wave_sum(vy), s2 = sky_wave_sum(vx * dx), s3 = sky_wave_sum(vx * dy),
-                        s4 = sky_wave_sum(vy * dy), s5 = sky_wave_sum(v5);
+            const float v5 = gate ? e.G * (c5 * __builtin_amdgcn_rcpf(1.f - e.alpha)) : 0.f;
+            const float vx = v5 * e.dx, vy = v5 * e.dy;
+            const float s[6] = {wave_sum_f32(vx), wave_sum_f32(vy), wave_sum_f32(vx * e.dx), wave_sum_f32(vx * e.dy), wave_sum_f32(vy * e.dy), wave_sum_f32(v5)};
             if ((t & 63) == 0) {
-                L.acc[wave][0][j] = s0; L.acc[wave][1][j] = s1; L.acc[wave][2][j] = s2; L.acc[wave][3][j] = s3; L.acc[wave][4][j] = s4;
-                L.acc[wave][5][j] = s5;
+#pragma unroll
+                for (int k = 0; k < 6; ++k) L.acc[k][wave][j] = s[k];
             }
         }
         __syncthreads();
-        if ((uint32_t)t < cnt && id - (uint32_t)view * (uint32_t)n < (uint32_t)n) {
+        if ((uint32_t)t < cnt && replay_owns(id, rt.view, n)) {
             float* const row = grow + (size_t)id * 12;
 #pragma unroll
             for (int k = 0; k < 6; ++k) {
-                const float v = (L.acc[0][k][t] + L.acc[1][k][t]) + (L.acc[2][k][t] + L.acc[3][k][t]);
+                const float v = replay_fold_sum(L.acc[k], t);
                 // the moment sums were taken over v5 = G dL/dalpha; the row contract wants them over opacity * v5 (column 5 is dL/dopacity itself)
                 if (v != 0.f) atomicAdd(&row[k], k == 5 ? v : v * op);
             }
@@ -268,7 +230,7 @@ hipError_t dvs_launch_sky_backward_rows(hipStream_t st, int W, int H, int tiles_
                                         const float* dL_dout, const float* sky_rgb, float* grad_rows, int grad_mode) {
     const int tiles_pv = tiles_x * tiles_y, num_tiles = tiles_pv * n_views;
     if (num_tiles <= 0 || n <= 0) return hipSuccess;
-    const int grid = ((num_tiles + 7) >> 3) << 3;
+    const int grid = replay_grid(num_tiles);
 #define DVS_SKY_ROWS(LN)                                                                                                                       \
     hipLaunchKernelGGL((k_sky_backward_rows<LN>), dim3(grid), dim3(RB), 0, st, W, H, tiles_x, tiles_pv, num_tiles, n, (const uint2*)ranges,   \
                        sorted_splat, (const float4*)splat2d, final_T, n_contrib, dL_dout, sky_rgb, grad_rows)

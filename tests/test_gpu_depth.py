@@ -1,6 +1,6 @@
 """dvs_raster_depth_views against the fp64 restatement tests/depth_ref.py on the exported forward state.
 
-Scene: two views of 50x37 (4x3 tiles, neither size a multiple of 16), 700 splats: 370 small ones spread over pixels x < 40, y < 28 (so
+Scene (tests/replay_scene.py, seed 11): two views of 50x37 (4x3 tiles, neither size a multiple of 16), 700 splats: 370 small ones spread over pixels x < 40, y < 28 (so
 tile (3, 2) stays empty), 300 faint ones (opacity about 0.03) crowded into tile (1, 0) — more than one 256-entry staging batch, and faint
 enough that its pixels walk past entry 256 — and a stack of 30 opaque ones over pixel (10, 20), which saturates the pixels under it (the forward ends such a pixel before the entry that would take T below 1e-4, so its
 final_T stays at about 1e-4 and n_contrib stops short of the list end).
@@ -12,53 +12,19 @@ import numpy as np
 import pytest
 import torch
 import divshot_amd as dv
-from divshot_amd import _lib, mesh
+from divshot_amd import mesh
 from divshot_amd.raster import Rasterizer, params_to_device
 import depth_ref as DR
+from replay_scene import W, H, cameras, scene_params, export_view
 
 pytestmark = pytest.mark.gpu
-W, H, N = 50, 37, 700
-
-
-def cameras():
-    cams = []
-    for tx in (0.0, 0.08):
-        cam = dv.Camera()
-        R = np.eye(3, dtype=np.float32); t = np.array([tx, -0.02 * (tx > 0), 0.0], np.float32)
-        _lib.check(dv.lib.dvs_make_camera(R.ctypes.data, t.ctypes.data, 60.0, W, H, C.byref(cam)), "dvs_make_camera")
-        cams.append(cam)
-    return cams
-
-
-def scene_params():
-    r = np.random.default_rng(11)
-    fx = W / (2 * np.tan(np.radians(30.0))); fy = fx            # (tan_fovy = tan_fovx H / W)
-    px = np.concatenate([r.uniform(2, 38, 370), r.uniform(20, 27, 300), 10 + r.normal(0, 0.4, 30)])
-    py = np.concatenate([r.uniform(2, 26, 370), r.uniform(4, 11, 300), 20 + r.normal(0, 0.4, 30)])
-    z = np.concatenate([r.uniform(3, 6, 370), r.uniform(3, 6, 300), np.linspace(2.5, 5.5, 30)])
-    pos = np.stack([(px - (W - 1) / 2) * z / fx, (py - (H - 1) / 2) * z / fy, z], 1)
-    sig = np.concatenate([r.uniform(0.06, 0.14, 370), r.uniform(0.08, 0.16, 300), np.full(30, 0.3)])
-    P = {"pos": pos, "sh0": r.normal(0, 1, (N, 3)), "shN": np.zeros((N, 15, 3)),
-         "opacity": np.concatenate([r.normal(0, 1.5, 370), r.normal(-3.4, 0.2, 300), np.full(30, 5.0)]),
-         "scale": np.log(sig)[:, None] + r.normal(0, 0.15, (N, 3)), "rot": r.normal(0, 1, (N, 4))}
-    return {k: np.ascontiguousarray(v, np.float32) for k, v in P.items()}
-
-
-def export_view(r, v, V):
-    st = _lib.FwdState()
-    _lib.check(dv.lib.dvs_get_view_state(r.ctx, v, C.byref(st)), "dvs_get_view_state")
-    st0 = _lib.FwdState()
-    _lib.check(dv.lib.dvs_get_view_state(r.ctx, 0, C.byref(st0)), "dvs_get_view_state")
-    tiles = st.tiles_x * st.tiles_y
-    return dict(splat2d=r._d2h(st0.splat2d, (V * st.n, 16), np.float32), ranges=r._d2h(st.ranges, (tiles, 2), np.uint32),
-                sorted_splat=r._d2h(st0.sorted_splat, (int(r.num_rendered),), np.uint32), n_contrib=r._d2h(st.n_contrib, (H, W), np.uint32),
-                final_T=r._d2h(st.final_T, (H, W), np.float32))
+SEED = 11
 
 
 @pytest.fixture(scope="module")
 def runs(gpu_device):
     """the two-view forward's maps, exported state and reference (computed once); the single-view maps"""
-    P = params_to_device(scene_params(), gpu_device)
+    P = params_to_device(scene_params(SEED), gpu_device)
     cams = cameras()
     r2 = Rasterizer(0, max_splats=1024, max_w=W, max_h=H, max_views=2)
     assert dv.lib.dvs_raster_depth_views(r2.ctx, None, C.byref(dv.Opts()), 1, 1) == 4          # DVS_ERR_STATE before any forward
@@ -113,7 +79,7 @@ def test_two_view_slices_equal_single_view_runs_bit_for_bit(runs):
 
 def test_async_and_tight_tiles(gpu_device):
     """asynchronous mode and DVS_TILES_TIGHT: the same maps to 1e-4 (the lists differ, the contributing entries do not)"""
-    P = params_to_device(scene_params(), gpu_device)
+    P = params_to_device(scene_params(SEED), gpu_device)
     cam = cameras()[0]
     r = Rasterizer(0, max_splats=1024, max_w=W, max_h=H)
     r.forward(P, cam, sh_degree=0)

@@ -1,7 +1,6 @@
 """dvs_raster_importance_views against the fp64 restatement tests/importance_ref.py on the exported forward state.
 
-The scene is tests/test_gpu_depth.py's (its cameras and export imported, its scene_params restated below line by line with the seed as
-an argument): two views of 50x37 (neither size a multiple of 16), 700 splats, an empty tile, a tile with more than 256 faint entries
+The scene is tests/replay_scene.py's, as in tests/test_gpu_depth.py but for the seed: two views of 50x37 (neither size a multiple of 16), 700 splats, an empty tile, a tile with more than 256 faint entries
 (its pixels walk past one staging batch) and a saturating opaque stack (n_contrib stops short of the list) — the shapes at which this
 kernel can go wrong; test_scene_has_the_cases asserts them.
 A splat is excluded when, in some pixel, an entry at or before its own falls into depth_ref's threshold bands (1e-5 wide; the reference
@@ -22,26 +21,11 @@ import divshot_amd as dv
 from divshot_amd import mesh, prune
 from divshot_amd.raster import Rasterizer, params_to_device
 import importance_ref as IR
-from test_gpu_depth import W, H, N, cameras, export_view
+from replay_scene import W, H, N, cameras, scene_params, export_view
 
 pytestmark = pytest.mark.gpu
 Q = 16777216.0
 SEED = 12
-
-
-def scene_params(seed=SEED):
-    """test_gpu_depth.scene_params with the seed as an argument"""
-    r = np.random.default_rng(seed)
-    fx = W / (2 * np.tan(np.radians(30.0))); fy = fx            # (tan_fovy = tan_fovx H / W)
-    px = np.concatenate([r.uniform(2, 38, 370), r.uniform(20, 27, 300), 10 + r.normal(0, 0.4, 30)])
-    py = np.concatenate([r.uniform(2, 26, 370), r.uniform(4, 11, 300), 20 + r.normal(0, 0.4, 30)])
-    z = np.concatenate([r.uniform(3, 6, 370), r.uniform(3, 6, 300), np.linspace(2.5, 5.5, 30)])
-    pos = np.stack([(px - (W - 1) / 2) * z / fx, (py - (H - 1) / 2) * z / fy, z], 1)
-    sig = np.concatenate([r.uniform(0.06, 0.14, 370), r.uniform(0.08, 0.16, 300), np.full(30, 0.3)])
-    P = {"pos": pos, "sh0": r.normal(0, 1, (N, 3)), "shN": np.zeros((N, 15, 3)),
-         "opacity": np.concatenate([r.normal(0, 1.5, 370), r.normal(-3.4, 0.2, 300), np.full(30, 5.0)]),
-         "scale": np.log(sig)[:, None] + r.normal(0, 0.15, (N, 3)), "rot": r.normal(0, 1, (N, 4))}
-    return {k: np.ascontiguousarray(v, np.float32) for k, v in P.items()}
 
 
 def to_np(triple):
@@ -52,7 +36,7 @@ def to_np(triple):
 @pytest.fixture(scope="module")
 def runs(gpu_device):
     """the two-view pass (scores, depth pass alpha, exported state, reference, masked variant); per-view single passes"""
-    P = params_to_device(scene_params(), gpu_device)
+    P = params_to_device(scene_params(SEED), gpu_device)
     cams = cameras()
     r2 = Rasterizer(0, max_splats=1024, max_w=W, max_h=H, max_views=2)
     z = torch.zeros(N, dtype=torch.int64, device=gpu_device)
@@ -143,7 +127,7 @@ def test_mask_zeroes_the_left_half_of_view_0(runs):
 
 
 def test_async_and_tight_tiles_bit_for_bit(gpu_device):
-    P = params_to_device(scene_params(), gpu_device)
+    P = params_to_device(scene_params(SEED), gpu_device)
     cam = cameras()[0]
     r = Rasterizer(0, max_splats=1024, max_w=W, max_h=H)
     r.forward(P, cam, sh_degree=0)

@@ -24,7 +24,7 @@ from divshot_amd import _lib
 from divshot_amd.raster import Rasterizer, params_to_device
 from util import KEYS, rel_close
 import sky_ref as SR
-import test_gpu_depth as TD
+import replay_scene as RS
 from test_sky_ref import intrinsics_camera, rot_xyz
 
 pytestmark = pytest.mark.gpu
@@ -229,9 +229,8 @@ def test_varying_texture_matches_the_reference(gpu_device, mode):
 # ---- (d) ---------------------------------------------------------------------------------------------------------------------------
 def test_long_lists_empty_tiles_and_saturated_pixels(gpu_device):
     """tests/test_gpu_depth.py's scene with the importance test's seed: a tile with more than 256 walked entries (a second LDS batch), an empty tile, a saturating stack"""
-    from test_gpu_importance import scene_params
     tex = np.random.default_rng(22).uniform(0, 1, (HS, WS, 3)).astype(np.float32)
-    facts, _, _ = run_against_reference(gpu_device, colourless(scene_params()), TD.cameras(), tex, what="depth-test scene:")
+    facts, _, _ = run_against_reference(gpu_device, colourless(RS.scene_params(12)), RS.cameras(), tex, what="depth-test scene:")
     for f in facts:
         e = f["e"]
         length = e["ranges"][:, 1].astype(np.int64) - e["ranges"][:, 0]
