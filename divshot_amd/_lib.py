@@ -85,6 +85,7 @@ _PROTOS = {
     "dvs_raster_forward_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Splats), C.POINTER(Camera), C.c_int, C.POINTER(Opts), C.c_void_p]),
     "dvs_raster_depth_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p]),
     "dvs_raster_importance_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Opts), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_raster_foreground_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Opts), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p]),
     "dvs_sky_forward_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.c_int, C.POINTER(Sky), C.c_void_p, C.c_void_p]),
     "dvs_sky_backward_views": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Camera), C.c_int, C.POINTER(Opts), C.POINTER(Sky), C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
@@ -169,6 +170,7 @@ _PROTOS = {
     "dvs_densify_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DensifyParams), C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "dvs_importance_scratch_bytes": (C.c_size_t, [C.c_int]),
     "dvs_importance_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dvs_foreground_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "dvs_reset_opacity": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]),
     "dvs_adam_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float,
                                 C.c_float, C.c_float, C.c_int]),

@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 #include "../../include/dvs_raster.h"
+#include "../../include/dvs_train.h"
 #include "dvs_kernels.h"
 
 static thread_local std::string g_last_error;
@@ -644,6 +645,31 @@ int dvs_raster_importance_views(dvs_ctx* c, void* stream, const dvs_opts* opts, 
     const dvs_fwd_state& s = c->fwd.st;
     HIPCHECK(dvs_launch_importance_views((hipStream_t)stream, s.width, s.height, s.tiles_x, s.tiles_y, c->fwd.n_views, s.n, s.ranges, s.sorted_splat,
                                          s.splat2d, s.n_contrib, masks, score_sum, score_max, hits));
+    return DVS_OK;
+}
+
+// Where those blend weights landed, on foreground or on background pixels (foreground.hip); reads the state, changes none of it
+int dvs_raster_foreground_views(dvs_ctx* c, void* stream, const dvs_opts* opts, const float* const* fg_masks, const float* const* valid_masks,
+                                uint64_t* fg_sum, uint64_t* bg_sum) {
+    const char* const who = "dvs_raster_foreground_views";
+    if (!c || !opts || !fg_sum || !bg_sum) return fail(DVS_ERR_INVALID, who, "null argument");
+    if (((uintptr_t)fg_sum | (uintptr_t)bg_sum) & 15u) return fail(DVS_ERR_INVALID, who, "vote arrays must be 16-byte aligned");
+    TRY(need_forward(c, who));
+    HIPCHECK(hipSetDevice(c->device));
+    const dvs_fwd_state& s = c->fwd.st;
+    HIPCHECK(dvs_launch_foreground_views((hipStream_t)stream, s.width, s.height, s.tiles_x, s.tiles_y, c->fwd.n_views, s.n, s.ranges, s.sorted_splat,
+                                         s.splat2d, s.n_contrib, fg_masks, valid_masks, fg_sum, bg_sum));
+    return DVS_OK;
+}
+// The plan over the votes (dvs_train.h; kernels in foreground.hip). Here because its refusals name themselves in dvs_last_error()
+int dvs_foreground_plan(void* stream, int n, const uint64_t* fg, const uint64_t* bg, int percent, uint8_t* action, uint32_t* offsets, uint32_t* scratch,
+                        uint64_t* new_count) {
+    const char* const who = "dvs_foreground_plan";
+    if (n <= 0) return fail(DVS_ERR_INVALID, who, "n must be > 0");
+    if (percent < 1 || percent > 100) return fail(DVS_ERR_INVALID, who, "percent must be in [1, 100]");
+    if (!fg || !bg || !action || !offsets || !scratch || !new_count) return fail(DVS_ERR_INVALID, who, "null argument");
+    if ((uintptr_t)new_count & 7u) return fail(DVS_ERR_INVALID, who, "new_count must be 8-byte aligned");
+    HIPCHECK(dvs_launch_foreground_plan((hipStream_t)stream, n, fg, bg, percent, action, offsets, scratch, new_count));
     return DVS_OK;
 }
 

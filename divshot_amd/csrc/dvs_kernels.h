@@ -149,6 +149,14 @@ hipError_t dvs_launch_depth_views(hipStream_t st, int W, int H, int tiles_x, int
 hipError_t dvs_launch_importance_views(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, int n, const uint32_t* ranges /*canonical (start, end)*/,
                                        const uint32_t* sorted_splat, const float* splat2d, const uint32_t* n_contrib, const float* const* masks,
                                        uint64_t* score_sum, uint32_t* score_max, uint32_t* hits);
+// foreground.hip — where the blend weight of the saved forward state landed, all n_views views in one launch: accumulates into fg_sum [n] and
+// bg_sum [n] (uint64); fg_masks / valid_masks = HOST arrays [n_views] of DEVICE [H,W] pointers, or null, entries may be null. And the plan over
+// the two sums: three launches (flags + block sums | scan.hip's block-sum scan | offsets), scratch = (n / 256 + 2) words
+hipError_t dvs_launch_foreground_views(hipStream_t st, int W, int H, int tiles_x, int tiles_y, int n_views, int n, const uint32_t* ranges /*canonical (start, end)*/,
+                                       const uint32_t* sorted_splat, const float* splat2d, const uint32_t* n_contrib, const float* const* fg_masks,
+                                       const float* const* valid_masks, uint64_t* fg_sum, uint64_t* bg_sum);
+hipError_t dvs_launch_foreground_plan(hipStream_t st, int n, const uint64_t* fg, const uint64_t* bg, int percent, uint8_t* action, uint32_t* offsets,
+                                      uint32_t* scratch, uint64_t* new_count);
 // sky.hip — the sky texture behind the splats, all n_views views in one launch each. minv = HOST [n_views][9]: per view the inverse of rows
 // 0, 1, 3 of proj's 3x3 part, row-major (world ray of a pixel = minv (ndc_x, ndc_y, 1)); tex = DEVICE [Hs][Ws][3].
 // forward: out_rgb += final_T s in place (null: skipped), s -> sky_rgb (null: skipped); both are [n_views][3][H][W]

@@ -87,7 +87,11 @@ static std::map<std::string, std::string> g_opts = {
     // extension of this build: --exportLod L (0 = off .. 4): every save also writes <outputPath>_<it>.lod<k>.ply, k = 1..L, the model with the
     // splats of every cell of a lattice merged into one (moment-matched, on the GPU); --lodResolution R (32..1024) is level 1's cell count
     // along the longest side, level k has R >> (k - 1). Handed to the plugin as DVS_EXPORT_LOD / DVS_LOD_RESOLUTION, like the mesh flags.
-    {"exportLod", "0"}, {"lodResolution", "256"}};
+    {"exportLod", "0"}, {"lodResolution", "256"},
+    // extension of this build: --maskCarve T (0 = off .. 100) removes, at every prune occasion and before every save, the splats whose blend
+    // weight over the training views landed on background pixels of the masks (--useMask 1): a splat stays iff fg > 0 and
+    // fg (100 - T) >= bg T. The config struct has no room left: it is handed to the plugin as DVS_MASK_CARVE.
+    {"maskCarve", "0"}};
 static std::map<std::string, bool> g_given;
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
@@ -182,6 +186,12 @@ int main(int argc, const char* argv[]) {
             return 1;
         }
         setenv(levels ? "DVS_EXPORT_LOD" : "DVS_LOD_RESOLUTION", v.c_str(), 1);      // before the plugin is loaded
+    }
+    if (g_given.count("maskCarve")) {
+        const std::string& v = g_opts["maskCarve"];
+        const bool digits = !v.empty() && v.size() <= 3 && v.find_first_not_of("0123456789") == std::string::npos;
+        if (!digits || atoi(v.c_str()) > 100) { std::cout << "Command Line Error: --maskCarve takes an integer 0..100, not '" << v << "'\n"; return 1; }
+        setenv("DVS_MASK_CARVE", v.c_str(), 1);                             // before the plugin is loaded
     }
     for (const char* flag : {"cullSH", "reducedHalf"})
         if (g_opts[flag] != "0" && g_opts[flag] != "1") { std::cout << "Command Line Error: --" << flag << " takes 0 or 1, not '" << g_opts[flag] << "'\n"; return 1; }

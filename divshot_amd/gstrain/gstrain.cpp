@@ -103,6 +103,7 @@ void GaussianTrainerScene::trainStep() {
         DVS_OR_THROW(dvs_reset_opacity(m.stream.get(), m.n, m.d_param[P_OPA].get(), 0.01f, m.d_m[P_OPA].get(), m.d_v[P_OPA].get()));
     if (s.prune_now) {
         if (m.cfg.enableFocusRegion) m.prune_region(s.it);
+        m.prune_mask_carve(s.it);                                            // (nothing when maskCarve is 0)
         m.prune_light(s.it);
         m.prune_importance(s.it);                                            // (nothing when importancePrune is 0)
         pruenIteraions.push_back(s.it);
@@ -120,6 +121,7 @@ void GaussianTrainerScene::trainStep() {
 void GaussianTrainerScene::saveGaussianModel() {
     Impl& m = *impl_;
     if (m.cfg.enableFocusRegion && m.ctx) m.prune_region(m.step);           // what is written holds inside splats only (every rank: the replicas stay identical)
+    if (m.ctx) m.prune_mask_carve(m.step);                                  // (nothing when maskCarve is 0; every rank, like the region prune)
     // the replicas are identical: one file — unless DVS_SAVE_ALL_RANKS=1 asks every rank for its own (<model>_<it>.ply.rank<r>), which
     // is how the two-rank test checks that they ARE identical, bit for bit
     static const bool all_ranks = env_is("DVS_SAVE_ALL_RANKS", "1");
@@ -182,6 +184,13 @@ void GaussianTrainerScene::setLodExport(int levels, int resolution) {
     if (resolution < 32 || resolution > 1024) { logf_("setLodExport: %d is not a resolution 32..1024: 256 is used", resolution); resolution = 256; }
     m.lod_levels_set = levels; m.lod_resolution_set = resolution;
     if (levels > 0 && m.rank == 0) logf_("config: lodExport %d levels, resolution %d (setLodExport)", levels, resolution);
+}
+// The editor's switch for what DVS_MASK_CARVE sets for the CLI: once called it wins over the environment.
+void GaussianTrainerScene::setMaskCarve(int percent) {
+    Impl& m = *impl_;
+    if (percent < 0 || percent > 100) { logf_("setMaskCarve: %d is not a percentage 0 (off) .. 100: the mask carve is off", percent); percent = 0; }
+    m.mask_carve_set = percent;
+    m.report_mask_carve("setMaskCarve");
 }
 void GaussianTrainerScene::setReducedExport(float shCullThreshold, bool halfFloat) {
     Impl& m = *impl_;

@@ -104,7 +104,9 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     // loss), and the camera's mask when useMask was on at load time or the capture had a distorted camera (`undistorted`: the views of
     // SIMPLE_RADIAL / RADIAL / OPENCV cameras were remapped to pinhole views at load time and their pixels without a source are masked
     // out; every view of such a capture carries a mask, a pinhole view's being its file mask or all ones)
-    struct View { DevBuf<float> f32; DevBuf<uint8_t> u8; DevBuf<float> mask; };
+    // `valid`: only for an undistorted view loaded with useMask while maskCarve was on — the undistortion's validity alone (the mask is
+    // "valid AND trainable"), so that the carve can tell a blank pixel from a background pixel
+    struct View { DevBuf<float> f32; DevBuf<uint8_t> u8; DevBuf<float> mask, valid; };
     std::vector<View> views;
     std::vector<dvs_camera> cams;
     DevBuf<float> d_target_f32;
@@ -150,6 +152,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     //   render_to_png     what is asked for   yes   none
     //   extract_mesh      training_cameras()  no    view_mask
     //   prune_importance  training_cameras()  no    view_mask
+    //   prune_mask_carve  training_cameras()  no    view_mask as the foreground, the view's validity plane when it has one
     struct EvalPass { int first, nb; const int* cam; const dvs_camera* cams; const float* images; };   // views which[first .. first + nb): their indices
                                                                              // (&which[first]), their cameras [nb], d_eval_out [nb][3][H][W]
     void for_each_eval_pass(const dvs_splats& sp, const std::vector<int>& which, bool with_sky, const std::function<void(const EvalPass&)>& per_pass);
@@ -285,6 +288,18 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     DevBuf<uint64_t> d_imp_score; DevBuf<void> d_imp_scratch;
     int importance_prune() const { return std::min(90, std::max(0, env_int("DVS_IMPORTANCE_PRUNE", cfg.importancePrune))); }   // percent, 0 = off
     void prune_importance(int it);
+
+    // mask carve (DVS_MASK_CARVE = T in 1..100, 0 = off, or what setMaskCarve said, -1: it was not called; trainer_refine.cpp,
+    // INTEGRATION.md "Mask carve"): at every prune occasion and before every save the splats whose blend weight over the training views
+    // landed on background pixels of the views' masks go (dvs_raster_foreground_views per pass of eval_ctx, dvs_foreground_plan). Inactive
+    // when no training view has a mask. Nothing is allocated, launched, written or logged while T is 0.
+    int mask_carve_set = -1;
+    int mask_carve() const;
+    bool carve_has_masks() const;                                            // some training view has a mask
+    bool carve_has_valid() const;                                            // ... and some view kept its validity plane
+    DevBuf<uint64_t> d_carve_votes;                                          // [2][cap rounded up to even]: foreground, background
+    void prune_mask_carve(int it);
+    void report_mask_carve(const char* by) const;
 
     // sky model (cfg.enableBg, the reference's "Create Sky Model"; trainer_output.cpp): an equirectangular fp32 texture [sky_h][2 sky_h][3]
     // behind the splats (dvs_sky_forward_views / dvs_sky_backward_views, dvs_raster.h), initialised to zero, its own Adam state, the

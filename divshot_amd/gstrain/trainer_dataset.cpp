@@ -286,8 +286,9 @@ struct GaussianTrainerScene::Impl::CaptureLoad {
         return out;
     }
 
-    // -> the pinhole camera's view; *mask := valid and, with a source mask, trainable
-    DevBuf<uint8_t> undistort(const ViewLoad& v, DevBuf<uint8_t> full8, DevBuf<uint8_t> mask8, DevBuf<float>* mask) {
+    // -> the pinhole camera's view; *mask := valid and, with a source mask, trainable; *valid := valid alone, kept only when there is a
+    // source mask and maskCarve is on (one more pass without the source mask, whose one plane of pixels is overwritten right after)
+    DevBuf<uint8_t> undistort(const ViewLoad& v, DevBuf<uint8_t> full8, DevBuf<uint8_t> mask8, DevBuf<float>* mask, DevBuf<float>* valid) {
         const gsdata::Camera& c = v.c;
         const double prm[8] = {c.fx, c.fy, c.cx, c.cy, c.dist[0], c.dist[1], c.dist[2], c.dist[3]};      // the camera in OPENCV's order (absent coefficients are 0)
         dvs_undistort_desc desc;
@@ -295,6 +296,10 @@ struct GaussianTrainerScene::Impl::CaptureLoad {
             refuse("the parameters of camera %u (%s) do not round to finite fp32 values", c.id, gsdata::model_name(c.model));
         DevBuf<uint8_t> pinhole(3 * v.p0);
         mask->alloc(v.p0 * sizeof(float));
+        if (mask8 && m.mask_carve() > 0) {
+            valid->alloc(v.p0 * sizeof(float));
+            DVS_OR_THROW(dvs_undistort_view(m.stream.get(), &desc, 1, full8.get(), nullptr, pinhole.get(), valid->get(), nullptr));
+        }
         undistort_ms += undistort_timer.run(m.stream.get(), [&] {
             DVS_OR_THROW(dvs_undistort_view(m.stream.get(), &desc, 3, full8.get(), mask8.get(), pinhole.get(), mask->get(), d_invalid.get()));
         });
@@ -304,7 +309,7 @@ struct GaussianTrainerScene::Impl::CaptureLoad {
 
     // box-filtered by the image's factor (rounded back to 8 bits when the views are kept as bytes) unless the bytes are the view as they
     // are; the mask as the floats a view keeps (> 127 trains; a level mask keeps the box filter's fractional weights)
-    void store(const ViewLoad& v, DevBuf<uint8_t> full8, ViewMask vm, DevBuf<float> mask) {
+    void store(const ViewLoad& v, DevBuf<uint8_t> full8, ViewMask vm, DevBuf<float> mask, DevBuf<float> valid) {
         const bool u8 = m.views_u8();
         const size_t P = (size_t)m.W * m.H;
         DevBuf<float> t;
@@ -328,12 +333,20 @@ struct GaussianTrainerScene::Impl::CaptureLoad {
             HIP_OR_THROW(hipStreamSynchronize(m.stream.get()));
             mask = std::move(md);
         }
+        if (valid && v.d > 1) {                                  // (the validity plane of the mask carve: filtered like the mask)
+            DevBuf<float> vd(P * sizeof(float));
+            const dvs_downsample_view dv{valid.get(), vd.get()};
+            DVS_OR_THROW(dvs_downsample_views(m.stream.get(), &dv, 1, 1, v.w, v.h, v.d, 0));
+            HIP_OR_THROW(hipStreamSynchronize(m.stream.get()));
+            valid = std::move(vd);
+        }
         if (t) {
             m.store_view(std::move(t), std::move(mask));
             if (!u8) HIP_OR_THROW(hipStreamSynchronize(m.stream.get()));         // (u8: store_view has synchronised) full8 was read until here
         } else {
-            m.views.push_back(View{DevBuf<float>(), std::move(full8), std::move(mask)});
+            m.views.push_back(View{DevBuf<float>(), std::move(full8), std::move(mask), DevBuf<float>()});
         }
+        m.views.back().valid = std::move(valid);
     }
 
     void camera(const ViewLoad& v) {
@@ -407,9 +420,9 @@ bool GaussianTrainerScene::Impl::load_dataset(const std::string& path) try {
         DevBuf<uint8_t> alpha8;                                 // (read by the mask's launches until the view is stored)
         DevBuf<uint8_t> full8 = L.picture(v, &alpha8);
         ViewMask vm = L.mask(v, alpha8);
-        DevBuf<float> mask;
-        if (v.distorted) full8 = L.undistort(v, std::move(full8), std::move(vm.bytes), &mask);
-        L.store(v, std::move(full8), std::move(vm), std::move(mask));
+        DevBuf<float> mask, valid;
+        if (v.distorted) full8 = L.undistort(v, std::move(full8), std::move(vm.bytes), &mask, &valid);
+        L.store(v, std::move(full8), std::move(vm), std::move(mask), std::move(valid));
         L.camera(v);
     }
     L.report();

@@ -73,6 +73,7 @@ void GaussianTrainerScene::Impl::report_config() const {
               "summed over the %zu training cameras are removed (scored and selected on the device, every rank for itself)", P,
               cfg.pruneStrategy > 0 ? "" : " (none: pruneStrategy is 0)", P, train_idx.empty() ? cams.size() : train_idx.size());
     }
+    report_mask_carve(nullptr);
     if (sky_on)
         logf_("config: skyModel %dx%d: enableBg — an equirectangular fp32 texture behind the splats, looked up along each pixel's ray and trained with "
               "them (Adam, lr %g); every save also writes <modelPath>_<it>.sky; evaluation and written renders composite it; mesh export, the "
@@ -95,6 +96,25 @@ void GaussianTrainerScene::Impl::report_config() const {
     if (!cfg.cameraPosePath.empty() || !cfg.pointCloudPath.empty()) ign += " cameraPosePath/pointCloudPath(dataset ingestion)";
     if (cfg.visibleAdam && world > 1) ign += " visibleAdam(off with WORLD_SIZE > 1: the visible set differs per rank)";
     if (!ign.empty()) logf_("config: IGNORED by this build:%s", ign.c_str());
+}
+
+// the maskCarve line of report_config(), and of setMaskCarve (`by`); nothing while it is off
+void GaussianTrainerScene::Impl::report_mask_carve(const char* by) const {
+    const int T = mask_carve();
+    if (T <= 0 || rank != 0) return;
+    const std::string who = by ? std::string(" (") + by + ")" : std::string();
+    if (cams.empty()) { logf_("config: maskCarve %d%s: decided when the training views are loaded", T, who.c_str()); return; }
+    if (!carve_has_masks()) {
+        logf_("config: maskCarve %d%s: inactive: no training view has a mask (%s)", T, who.c_str(),
+              cfg.useMask ? "the capture was loaded without masks" : "useMask is off");
+        return;
+    }
+    logf_("config: maskCarve %d%s: at every prune occasion%s before the light prune, and before every save, a splat stays only while its blend weight "
+          "over the %zu training cameras landed on foreground pixels of their masks: fg > 0 and fg x %d >= bg x %d (voted and planned on the "
+          "device, every rank for itself)%s", T, who.c_str(), cfg.pruneStrategy > 0 ? "" : " (none: pruneStrategy is 0)",
+          train_idx.empty() ? cams.size() : train_idx.size(), 100 - T, T,
+          !undistorted ? "" : carve_has_valid() ? "; the blank pixels of the undistorted views vote for nothing"
+                                                : "; the blank pixels of the undistorted views count as background (their validity was not kept at load)");
 }
 
 // Held-out evaluation, on the training stream: the test cameras rendered from the current parameters at the full SH degree (what a

@@ -1,5 +1,5 @@
 // trainer_refine.cpp — what changes the number of splats between two iterations: ADC / ADC+ densification, MCMC relocation, light prune,
-// importance prune, focus-region prune.
+// importance prune, focus-region prune, mask carve.
 #include "trainer.hpp"
 
 // data parallel: the densification statistics are per-view sums / maxima — make them global before a refinement decision
@@ -185,5 +185,90 @@ void GaussianTrainerScene::Impl::prune_importance(int it) {
               never, score_ms, ms_since(t0_));
     n = new_n;
     host_valid = false;
+    pruning = false;
+}
+
+// maskCarve = T > 0 (DVS_MASK_CARVE, setMaskCarve): the splats the views' masks call background go. Every training camera is rendered
+// through the evaluation context (for_each_eval_pass, without the sky) and dvs_raster_foreground_views splits each splat's blend weight
+// alpha T by where it landed: on pixels with a nonzero mask (foreground) or on the others (background); a view without a mask counts as
+// foreground throughout, a pixel an undistortion left blank votes for nothing when the view kept its validity plane.
+// dvs_foreground_plan keeps splat i iff fg > 0 and fg (100 - T) >= bg T, the existing apply path compacts the parameters and the
+// moments, the gradients and the densification statistics start again as after an importance prune. Called at every prune occasion
+// before the light prune and before every save, after the focus-region prune in both places. A plan that would leave no splat is
+// logged and not applied. Every rank scores all training cameras itself: integer votes, an exact rule, no communication — the
+// replicas stay bit-identical.
+int GaussianTrainerScene::Impl::mask_carve() const {
+    if (mask_carve_set >= 0) return mask_carve_set;
+    const char* e = getenv("DVS_MASK_CARVE");
+    if (!e) return 0;
+    int v = 0, nd = 0;
+    const char* c = e;
+    for (; *c >= '0' && *c <= '9' && nd < 4; ++c, ++nd) v = v * 10 + (*c - '0');
+    if (*c || nd == 0 || v > 100) {
+        static bool said = false;
+        if (!said) logf_("mask carve: DVS_MASK_CARVE='%s' is not a percentage 0 (off) .. 100: ignored", e);
+        said = true;
+        return 0;
+    }
+    return v;
+}
+bool GaussianTrainerScene::Impl::carve_has_masks() const {
+    for (int c : training_cameras()) if (view_mask((size_t)c)) return true;
+    return false;
+}
+bool GaussianTrainerScene::Impl::carve_has_valid() const {
+    for (int c : training_cameras()) if (views[(size_t)c].valid) return true;
+    return false;
+}
+void GaussianTrainerScene::Impl::prune_mask_carve(int it) {
+    const int T = mask_carve();
+    if (T <= 0 || n <= 0 || !carve_has_masks()) return;
+    pruning = true;
+    ensure_eval_ctx();
+    const size_t half = ((size_t)cap + 1) & ~(size_t)1;                     // (an even count: both arrays on a 16-byte boundary)
+    if (!d_carve_votes) d_carve_votes.alloc(2 * half * sizeof(uint64_t) + 16);
+    uint64_t* const d_fg = d_carve_votes.get();
+    uint64_t* const d_bg = d_fg + half;
+    const std::vector<int> which = training_cameras();
+    const dvs_opts opts = eval_opts();
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    auto t0_ = std::chrono::steady_clock::now();
+    HIP_OR_THROW(hipMemsetAsync(d_fg, 0, (size_t)n * sizeof(uint64_t), stream.get()));
+    HIP_OR_THROW(hipMemsetAsync(d_bg, 0, (size_t)n * sizeof(uint64_t), stream.get()));
+    for_each_eval_pass(splats(), which, false, [&](const EvalPass& p) {
+        std::vector<const float*> fg((size_t)p.nb), valid((size_t)p.nb);
+        for (int k = 0; k < p.nb; ++k) { fg[(size_t)k] = view_mask((size_t)p.cam[k]); valid[(size_t)k] = views[(size_t)p.cam[k]].valid.get(); }
+        DVS_OR_THROW(dvs_raster_foreground_views(eval_ctx.get(), stream.get(), &opts, fg.data(), valid.data(), d_fg, d_bg));
+    });
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    const double votes_ms = ms_since(t0_);
+    size_t never = 0;                                                        // (for the log line only: nothing below depends on the host copy)
+    if (cfg.verbose && rank == 0) {
+        std::vector<uint64_t> hf((size_t)n), hb((size_t)n);
+        HIP_OR_THROW(hipMemcpy(hf.data(), d_fg, hf.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        HIP_OR_THROW(hipMemcpy(hb.data(), d_bg, hb.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < hf.size(); ++i) never += (hf[i] | hb[i]) == 0;
+    }
+    t0_ = std::chrono::steady_clock::now();
+    uint64_t new_n = 0;
+    DVS_OR_THROW(dvs_foreground_plan(stream.get(), n, d_fg, d_bg, T, d_action.get(), d_offsets.get(), d_dscratch.get(), d_newcount.get()));
+    HIP_OR_THROW(hipMemcpyAsync(&new_n, d_newcount.get(), 8, hipMemcpyDeviceToHost, stream.get()));
+    HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    if (new_n == 0) {
+        if (rank == 0) logf_("mask carve @%d: none of the %d splats has its blend weight on the foreground (threshold %d %%): nothing removed", it, n, T);
+        pruning = false;
+        return;
+    }
+    if (new_n < (uint64_t)n) {
+        apply_plan(plan_params(it), (int)new_n, false);
+        HIP_OR_THROW(hipMemsetAsync(d_grad_flat.get(), 0, grad_floats * sizeof(float), stream.get()));
+        reset_stats();
+        (void)dvs_raster_forward_cancel_prepared(ctx.get());               // (a pipelined step may have projected the next iteration's splats already)
+        HIP_OR_THROW(hipStreamSynchronize(stream.get()));
+    }
+    if (cfg.verbose && rank == 0)
+        logf_("mask carve @%d: %d -> %llu splats, %d views, %zu never taken, votes %.2f ms, plan+compact %.2f ms", it, n, (unsigned long long)new_n,
+              (int)which.size(), never, votes_ms, ms_since(t0_));
+    if (new_n < (uint64_t)n) { n = (int)new_n; host_valid = false; }
     pruning = false;
 }

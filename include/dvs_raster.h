@@ -290,6 +290,22 @@ int dvs_raster_depth_views(dvs_ctx* ctx, void* stream, const dvs_opts* opts, flo
 int dvs_raster_importance_views(dvs_ctx* ctx, void* stream, const dvs_opts* opts, const float* const* masks, uint64_t* score_sum,
                                 uint32_t* score_max, uint32_t* hits);
 
+/* Foreground votes of the last forward on the context — per splat, where its blend weight landed: on foreground pixels or on background
+ * pixels of the views' masks. The score of the mask carve (dvs_foreground_plan, dvs_train.h). Validity, state rules and alignment are
+ * those of dvs_raster_importance_views, and so is the pass: a separate forward-only walk over the saved state with the forward's rules
+ * and operations. Every entry a pixel takes gives q = (uint32_t)rintf(alpha T * 2^24), that call's quantisation on purpose, and per
+ * splat i the pass ACCUMULATES INTO two DEVICE arrays of n uint64, 16-byte aligned, which the caller zeroes:
+ *   fg_sum[i] += q   when the pixel's fg value is nonzero, or the view has no fg plane
+ *   bg_sum[i] += q   otherwise
+ * fg_masks, valid_masks: HOST arrays [n_views] of DEVICE [H,W] float pointers (read before the call returns), or NULL, and so may each
+ * entry. A pixel whose valid value is 0 walks nothing (the blank pixels an undistortion leaves); every other pixel inside the image
+ * walks its list exactly as the forward did. fg_sum + bg_sum is therefore, bit for bit, the score_sum of
+ * dvs_raster_importance_views called with masks = valid_masks; integer sums, so both arrays are bit-reproducible from run to run and
+ * identical on every rank. DVS_ERR_STATE without a forward; DVS_ERR_INVALID for a NULL ctx, opts, fg_sum or bg_sum and for misaligned
+ * arrays. `opts` are those of that forward. Asynchronous, on `stream`. */
+int dvs_raster_foreground_views(dvs_ctx* ctx, void* stream, const dvs_opts* opts, const float* const* fg_masks,
+                                const float* const* valid_masks, uint64_t* fg_sum, uint64_t* bg_sum);
+
 /* Sky model: a learned equirectangular RGB texture behind the splats, instead of the constant dvs_camera.bg. fp32 values used as they
  * are (no activation). Two separate passes over the state the forward saved; the composite kernels run with bg = 0 and are untouched.
  *   tex     DEVICE [height][width][3], 16-byte aligned, width == 2 * height, height >= 2; texel centres at integer (u, v).

@@ -180,6 +180,19 @@ int dvs_densify_apply(void* stream, int n, const uint8_t* action, const uint32_t
 size_t dvs_importance_scratch_bytes(int n);
 int dvs_importance_plan(void* stream, int n, const uint64_t* score, uint32_t keep, uint8_t* action, uint32_t* offsets, void* scratch,
                         uint64_t* new_count);
+/* Mask carve: which splats the foreground voted for, from the two sums of dvs_raster_foreground_views (dvs_raster.h) accumulated over the
+ * training views, in the form dvs_region_plan leaves, so that dvs_densify_apply (modes 0 and 1) compacts from it:
+ *   action[i]   DVS_DENSIFY_KEEP iff fg[i] > 0 and fg[i] * (100 - percent) >= bg[i] * percent, else DVS_DENSIFY_PRUNE. The products are
+ *               formed in 128 bits: the rule holds for every 64-bit input. A splat that no valid pixel of any view took (fg = bg = 0)
+ *               goes: it is in no training view. percent = 100 keeps only the splats that never landed on a background pixel.
+ *   offsets[i]  the exclusive scan of the kept splats;  *new_count (DEVICE uint64) = their number (0 when none stays)
+ * Three launches (flags + block sums | one workgroup scans the block sums, with a running carry | offsets); no host round trip.
+ * Integers only, no atomics: two calls on the same inputs return identical bytes. Asynchronous on `stream`.
+ *   scratch  at least (n / 256 + 2) uint32, contents irrelevant (as dvs_densify_plan's)
+ * DVS_ERR_INVALID, before anything touches the device, for n <= 0, a percent outside 1..100, a NULL pointer, or a new_count that is
+ * not 8-byte aligned; dvs_last_error() names the call. */
+int dvs_foreground_plan(void* stream, int n, const uint64_t* fg, const uint64_t* bg, int percent /*1..100*/, uint8_t* action,
+                        uint32_t* offsets, uint32_t* scratch, uint64_t* new_count);
 /* opacity reset (--resetAlphaEvery): opacity = min(opacity, logit(max_opacity)); zeroes the matching Adam moments if given. */
 int dvs_reset_opacity(void* stream, int n, float* opacity, float max_opacity, float* adam_m, float* adam_v);
 

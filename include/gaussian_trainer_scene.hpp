@@ -137,6 +137,12 @@ public:
     // (resolution 32..1024) along the longest side of the model's box, moment-matched on the device; 0 = off. A value outside these
     // ranges is reported and counts as 0 / 256. Wins over DVS_EXPORT_LOD / DVS_LOD_RESOLUTION once called.
     void setLodExport(int levels, int resolution);
+    // mask carve (extension of this build; INTEGRATION.md "Mask carve"): percent = T in 1..100 removes, at every prune occasion and before
+    // every save, the splats whose blend weight over the training views landed on background pixels of the views' masks: a splat stays
+    // iff fg > 0 and fg (100 - T) >= bg T, with fg / bg its weight on pixels with a nonzero / zero mask. Needs views loaded with useMask;
+    // 0 = off, any other value is reported and counts as 0. Wins over DVS_MASK_CARVE once called. Turned on after the load of a capture
+    // with distorted cameras, the pixels the undistortion left blank count as background (at load their validity is kept apart).
+    void setMaskCarve(int percent);
     // the .reduced.ply export (extension of this build; exportFormats bit 8, INTEGRATION.md "Compact exports"): the colour a splat may lose
     // when cullSH lowers its SH degree (>= 0, default 0.01) and whether positions are written as half floats. Once called it wins over
     // DVS_SH_CULL_THRESHOLD / DVS_REDUCED_HALF.
