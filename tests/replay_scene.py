@@ -38,7 +38,7 @@ def export_view(r, v, V):
     _lib.check(dv.lib.dvs_get_view_state(r.ctx, v, C.byref(st)), "dvs_get_view_state")
     st0 = _lib.FwdState()
     _lib.check(dv.lib.dvs_get_view_state(r.ctx, 0, C.byref(st0)), "dvs_get_view_state")
-    tiles = st.tiles_x * st.tiles_y
+    tiles, hw = st.tiles_x * st.tiles_y, (st.height, st.width)       # (the view's own size: tests/test_gpu_list_seams.py exports other scenes)
     return dict(splat2d=r._d2h(st0.splat2d, (V * st.n, 16), np.float32), ranges=r._d2h(st.ranges, (tiles, 2), np.uint32),
-                sorted_splat=r._d2h(st0.sorted_splat, (int(r.num_rendered),), np.uint32), n_contrib=r._d2h(st.n_contrib, (H, W), np.uint32),
-                final_T=r._d2h(st.final_T, (H, W), np.float32))
+                sorted_splat=r._d2h(st0.sorted_splat, (int(r.num_rendered),), np.uint32), n_contrib=r._d2h(st.n_contrib, hw, np.uint32),
+                final_T=r._d2h(st.final_T, hw, np.float32))

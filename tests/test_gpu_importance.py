@@ -75,7 +75,8 @@ def test_scene_has_the_cases(runs):
         assert sat.any() and (e["n_contrib"][sat] < tile_len[sat]).any(), "no saturated pixel that stops short of its list"
 
 
-def check_against(got, ref, what):
+def check_against(got, ref, what, min_taken=100, min_wmax=0.5):
+    """min_taken, min_wmax: what the scene must exercise (this file's scene by default; tests/test_gpu_list_seams.py gives its scenes' own)"""
     s, m, h = got
     wsum, wmax, hits, excl = ref
     print(f"{what}: excluded {int(excl.sum())} of {excl.size} splats; taken splats {int((hits > 0).sum())}, hits {int(hits.sum())}")
@@ -88,7 +89,7 @@ def check_against(got, ref, what):
     print(f"{what}: sum err max {s_err[k].max():.3e} (worst ratio to its bound {np.max(s_err[k] / np.maximum(bound[k], 1e-300)):.3e}), max err {m_err[k].max():.3e}")
     assert (s_err[k] <= bound[k]).all()
     assert (m_err[k] <= 1e-4).all()
-    assert (hits[k] > 0).sum() > 100 and wmax[k].max() > 0.5
+    assert (hits[k] > 0).sum() > min_taken and wmax[k].max() > min_wmax
 
 
 @pytest.mark.parametrize("view", [0, 1])
