@@ -381,6 +381,10 @@ _FRAME_HOST_PROTOS = {
     "gstrain_host_read_ply": (C.c_int64, [C.c_char_p] + [C.c_void_p] * 6 + [C.c_uint64]),
     "gstrain_export_orientation": (C.c_int, [C.c_uint64, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_uint64]),
 }
+# ... and the extension options' table (ext_options.hpp): one row's grammar and messages
+_OPTION_HOST_PROTOS = {
+    "gstrain_ext_option_check": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(C.c_double), C.c_char_p, C.c_int]),
+}
 _host_lib = None
 
 
@@ -392,12 +396,24 @@ def host_lib():
         if not os.path.exists(path):
             raise ImportError(f"{path} is missing: build it with `make -C divshot_amd/gstrain`")
         h = C.CDLL(path)
-        for name, (res, args) in list(_JPEG_HOST_PROTOS.items()) + list(_PNG_HOST_PROTOS.items()) + list(_MESH_HOST_PROTOS.items()) + list(_FRAME_HOST_PROTOS.items()):
+        for name, (res, args) in list(_JPEG_HOST_PROTOS.items()) + list(_PNG_HOST_PROTOS.items()) + list(_MESH_HOST_PROTOS.items()) + list(_FRAME_HOST_PROTOS.items()) + list(_OPTION_HOST_PROTOS.items()):
             f = getattr(h, name)
             f.restype = res
             f.argtypes = args
         _host_lib = h
     return _host_lib
+
+
+def ext_option_check(name_or_var, text):
+    """gstrain_ext_option_check: `text` against the extension option's table row, found by its flag name (no dashes; the text is then the
+    flag's spelling) or by its variable name -> (True, [8 floats], "") when it is of the row's grammar, (False, None, message) when it is
+    not — the CLI's message for a flag, the plugin's log line for a variable; DvsError when there is no such row"""
+    out = (C.c_double * 8)()
+    err = C.create_string_buffer(1024)
+    status = host_lib().gstrain_ext_option_check(name_or_var.encode(), text.encode(), out, err, 1024)
+    if status < 0:
+        raise DvsError(f"no extension option is called {name_or_var!r}")
+    return (True, list(out), "") if status == 0 else (False, None, err.value.decode())
 
 
 def write_mesh_ply(path, xyz, rgb, tri, normals=None):

@@ -19,6 +19,7 @@
 #include <map>
 #include <string>
 #include "../../include/gaussian_trainer_scene.hpp"
+#include "ext_options.hpp"
 
 static std::map<std::string, std::string> g_opts = {
     // flag -> default (main.cpp:12-70)
@@ -124,129 +125,28 @@ int main(int argc, const char* argv[]) {
         g_opts[a] = val;
         g_given[a] = true;
     }
-    if (g_given.count("meshMinComponent")) {
-        const std::string& v = g_opts["meshMinComponent"];
-        const size_t dot = v.find('.');
-        const std::string whole = v.substr(0, dot), frac = dot == std::string::npos ? "" : v.substr(dot + 1);
-        const bool ok = !whole.empty() && whole.size() <= 3 && whole.find_first_not_of("0123456789") == std::string::npos && frac.size() <= 2 &&
-                        frac.find_first_not_of("0123456789") == std::string::npos &&
-                        atoi(whole.c_str()) * 100 + atoi((frac + "00").substr(0, 2).c_str()) <= 10000;
-        if (!ok) { std::cout << "Command Line Error: --meshMinComponent takes a percentage 0..100 with at most two decimals, not '" << v << "'\n"; return 1; }
-        setenv("DVS_MESH_MIN_COMPONENT", v.c_str(), 1);                     // before the plugin is loaded
+    // the extension options the config struct has no room for (ext_options.hpp): a given flag's value is checked against its table row
+    // and handed to the plugin in the row's environment variable, before the plugin is loaded
+    int layers = gsopt::LAYER_COLOR;
+    for (int id = 0; id < gsopt::N_OPTIONS; ++id) {
+        const gsopt::Row& r = gsopt::row((gsopt::Id)id);
+        if (!r.flag || !g_given.count(r.flag)) continue;
+        std::string v = g_opts[r.flag];
+        double parsed[8];
+        if ((r.flag_to_var && !r.flag_to_var(v, &v)) || !gsopt::parse(r, v.c_str(), parsed)) { std::cout << gsopt::cli_error(r, g_opts[r.flag]) << "\n"; return 1; }
+        setenv(r.var, v.c_str(), 1);
+        if (id == gsopt::RENDER_LAYERS) layers = (int)parsed[0];
     }
-    if (g_given.count("meshNormals")) {
-        const std::string& v = g_opts["meshNormals"];
-        if (v != "0" && v != "1") { std::cout << "Command Line Error: --meshNormals takes 0 or 1, not '" << v << "'\n"; return 1; }
-        setenv("DVS_MESH_NORMALS", v.c_str(), 1);
-    }
-    if (g_given.count("meshDecimate")) {
-        const std::string& v = g_opts["meshDecimate"];
-        const bool digits = !v.empty() && v.size() <= 2 && v.find_first_not_of("0123456789") == std::string::npos;
-        const int f = digits ? atoi(v.c_str()) : -1;
-        if (!(f == 0 || (f >= 2 && f <= 16))) { std::cout << "Command Line Error: --meshDecimate takes 0 (off) or an integer 2..16, not '" << v << "'\n"; return 1; }
-        setenv("DVS_MESH_DECIMATE", v.c_str(), 1);                          // before the plugin is loaded
-    }
-    {
-        const std::string &fmt = g_opts["renderFormat"], &lay = g_opts["renderLayers"], &ds = g_opts["renderDepthScale"];
-        if (fmt != "jpg" && fmt != "png") { std::cout << "Command Line Error: --renderFormat takes jpg or png, not '" << fmt << "'\n"; return 1; }
-        int bits = 0;
-        bool ok = !lay.empty();
-        for (size_t at = 0; ok && at <= lay.size();) {                      // color[,depth][,alpha]: each name once, in this order, color first
-            const size_t comma = std::min(lay.find(',', at), lay.size());
-            const std::string name = lay.substr(at, comma - at);
-            const int bit = name == "color" ? 1 : name == "depth" ? 2 : name == "alpha" ? 4 : 0;
-            ok = bit > bits;                                                 // (unknown: 0; repeated or out of order: not above what came before)
-            bits |= bit;
-            at = comma + 1;
-        }
-        ok = ok && (bits & 1);
-        if (!ok) { std::cout << "Command Line Error: --renderLayers takes color[,depth][,alpha], not '" << lay << "'\n"; return 1; }
-        if (bits != 1 && fmt != "png") {
-            std::cout << "Command Line Error: --renderLayers takes depth or alpha only with --renderFormat png (JPEG files carry colour alone), not '" << lay << "'\n";
-            return 1;
-        }
-        char* end = nullptr;
-        const double s = strtod(ds.c_str(), &end);
-        if (ds.empty() || *end || !std::isfinite(s) || !(s > 0) || !std::isfinite((float)s) || !((float)s > 0.f)) {
-            std::cout << "Command Line Error: --renderDepthScale takes a finite number > 0, not '" << ds << "'\n";
-            return 1;
-        }
-        if (g_given.count("renderFormat")) setenv("DVS_RENDER_FORMAT", fmt.c_str(), 1);        // before the plugin is loaded
-        if (g_given.count("renderLayers")) setenv("DVS_RENDER_LAYERS", std::to_string(bits).c_str(), 1);
-        if (g_given.count("renderDepthScale")) setenv("DVS_RENDER_DEPTH_SCALE", ds.c_str(), 1);
-    }
-    for (const char* flag : {"exportLod", "lodResolution"}) {
-        if (!g_given.count(flag)) continue;
-        const bool levels = std::string(flag) == "exportLod";
-        const std::string& v = g_opts[flag];
-        const bool digits = !v.empty() && v.size() <= 4 && v.find_first_not_of("0123456789") == std::string::npos;
-        const int f = digits ? atoi(v.c_str()) : -1;
-        if (levels ? !(f >= 0 && f <= 4) : !(f >= 32 && f <= 1024)) {
-            std::cout << "Command Line Error: --" << flag << (levels ? " takes a number of levels 0 (off) .. 4, not '" : " takes a resolution 32..1024, not '") << v << "'\n";
-            return 1;
-        }
-        setenv(levels ? "DVS_EXPORT_LOD" : "DVS_LOD_RESOLUTION", v.c_str(), 1);      // before the plugin is loaded
-    }
-    if (g_given.count("maskCarve")) {
-        const std::string& v = g_opts["maskCarve"];
-        const bool digits = !v.empty() && v.size() <= 3 && v.find_first_not_of("0123456789") == std::string::npos;
-        if (!digits || atoi(v.c_str()) > 100) { std::cout << "Command Line Error: --maskCarve takes an integer 0..100, not '" << v << "'\n"; return 1; }
-        setenv("DVS_MASK_CARVE", v.c_str(), 1);                             // before the plugin is loaded
-    }
-    for (const char* flag : {"cullSH", "reducedHalf"})
+    for (const char* flag : {"cullSH", "enableBg", "enableFocusRegion"})
         if (g_opts[flag] != "0" && g_opts[flag] != "1") { std::cout << "Command Line Error: --" << flag << " takes 0 or 1, not '" << g_opts[flag] << "'\n"; return 1; }
-    if (g_given.count("reducedHalf")) setenv("DVS_REDUCED_HALF", g_opts["reducedHalf"].c_str(), 1);      // before the plugin is loaded
-    if (g_given.count("cullSHThreshold")) {
-        const std::string& v = g_opts["cullSHThreshold"];
-        char* end = nullptr;
-        const float t = strtof(v.c_str(), &end);
-        if (v.empty() || *end || !(t >= 0.0f)) { std::cout << "Command Line Error: --cullSHThreshold takes a number >= 0, not '" << v << "'\n"; return 1; }
-        setenv("DVS_SH_CULL_THRESHOLD", v.c_str(), 1);
-    }
-    if (g_opts["enableBg"] != "0" && g_opts["enableBg"] != "1") { std::cout << "Command Line Error: --enableBg takes 0 or 1, not '" << g_opts["enableBg"] << "'\n"; return 1; }
-    if (g_given.count("skyResolution")) {
-        const std::string& v = g_opts["skyResolution"];
-        if (v.empty() || v.size() > 5 || v.find_first_not_of("0123456789") != std::string::npos) { std::cout << "Command Line Error: --skyResolution takes a texture height (16..1024), not '" << v << "'\n"; return 1; }
-        setenv("DVS_SKY_RESOLUTION", v.c_str(), 1);                         // before the plugin is loaded
-    }
-    if (g_opts["enableFocusRegion"] != "0" && g_opts["enableFocusRegion"] != "1") { std::cout << "Command Line Error: --enableFocusRegion takes 0 or 1, not '" << g_opts["enableFocusRegion"] << "'\n"; return 1; }
-    if (g_given.count("focusRegion")) {
-        const std::string& v = g_opts["focusRegion"];
-        float b[6]; char tail = 0;
-        if (sscanf(v.c_str(), "%f,%f,%f,%f,%f,%f%c", &b[0], &b[1], &b[2], &b[3], &b[4], &b[5], &tail) != 6 || !(b[3] > b[0] && b[4] > b[1] && b[5] > b[2])) {
-            std::cout << "Command Line Error: --focusRegion takes x0,y0,z0,x1,y1,z1 with x1 > x0, y1 > y0, z1 > z0, not '" << v << "'\n"; return 1;
-        }
-        setenv("DVS_FOCUS_REGION", v.c_str(), 1);                           // before the plugin is loaded
-    }
-    if (g_given.count("focusRotation")) {
-        const std::string& v = g_opts["focusRotation"];
-        float r[3]; char tail = 0;
-        if (sscanf(v.c_str(), "%f,%f,%f%c", &r[0], &r[1], &r[2], &tail) != 3) { std::cout << "Command Line Error: --focusRotation takes rx,ry,rz (radians), not '" << v << "'\n"; return 1; }
-        setenv("DVS_FOCUS_ROTATION", v.c_str(), 1);
-    }
-    if (g_given.count("exportTransform") && g_given.count("exportOrient")) { std::cout << "Command Line Error: --exportTransform and --exportOrient exclude each other\n"; return 1; }
-    if (g_given.count("exportTransform")) {
-        const std::string& v = g_opts["exportTransform"];
-        float f[7]; char tail = 0;
-        bool ok = sscanf(v.c_str(), "%f,%f,%f,%f,%f,%f,%f%c", &f[0], &f[1], &f[2], &f[3], &f[4], &f[5], &f[6], &tail) == 7 && f[6] > 0.0f;
-        for (int k = 0; ok && k < 7; ++k) ok = f[k] - f[k] == 0.0f;          // (finite)
-        if (!ok) { std::cout << "Command Line Error: --exportTransform takes tx,ty,tz,rx,ry,rz,s (seven numbers, angles in radians, s > 0), not '" << v << "'\n"; return 1; }
-        setenv("DVS_EXPORT_TRANSFORM", v.c_str(), 1);                       // before the plugin is loaded
-    }
-    if (g_given.count("exportOrient")) {
-        const std::string& v = g_opts["exportOrient"];
-        if (v.size() != 2 || (v[0] != '+' && v[0] != '-') || v[1] < 'x' || v[1] > 'z') { std::cout << "Command Line Error: --exportOrient takes +x, -x, +y, -y, +z or -z, not '" << v << "'\n"; return 1; }
-        setenv("DVS_EXPORT_ORIENT", v.c_str(), 1);
+    // the rules across options
+    if (gsopt::layers_need_png(layers, g_opts["renderFormat"] == "png")) {
+        std::cout << "Command Line Error: --renderLayers takes depth or alpha only with --renderFormat png (JPEG files carry colour alone), not '" << g_opts["renderLayers"] << "'\n";
+        return 1;
     }
     const bool export_frame = g_given.count("exportTransform") || g_given.count("exportOrient");
-    for (size_t at = 0; at < g_opts["exportFormat"].size();) {               // (the token is checked again where the formats are collected)
-        const std::string& v = g_opts["exportFormat"];
-        const size_t comma = std::min(v.find(',', at), v.size());
-        if (v.substr(at, comma - at) == "transformed" && !export_frame) {
-            std::cout << "Command Line Error: --exportFormat transformed needs --exportTransform or --exportOrient\n"; return 1;
-        }
-        at = comma + 1;
-    }
+    if (gsopt::two_export_frames(g_given.count("exportTransform"), g_given.count("exportOrient"))) { std::cout << "Command Line Error: --exportTransform and --exportOrient exclude each other\n"; return 1; }
+    if (gsopt::transformed_needs_frame(g_opts["exportFormat"], export_frame)) { std::cout << "Command Line Error: --exportFormat transformed needs --exportTransform or --exportOrient\n"; return 1; }
     // plugin: "libgstrain.so" next to the executable (plugin.cpp:74 builds parent_path / "lib<name>.so")
     std::error_code ec;
     auto exe = std::filesystem::read_symlink("/proc/self/exe", ec);

@@ -24,6 +24,7 @@ GaussianTrainerScene::GaussianTrainerScene(const GaussianTrainConfig& cfg, int l
     Impl& m = *impl_;
     m.cfg = cfg;
     m.loadItr = loadItr;
+    m.opt = gsopt::read_env([](const std::string& line) { logf_("%s", line.c_str()); });     // before any setter can be called: a setter wins
     m.device = env_int("LOCAL_RANK", 0);
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
@@ -149,7 +150,7 @@ void GaussianTrainerScene::saveGaussianModel() {
         for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT, (int)Impl::EXPORT_SPZ, (int)Impl::EXPORT_REDUCED, (int)Impl::EXPORT_TRANSFORMED})
             if (m.export_formats() & format) m.export_model(format);
     }
-    if (m.rank == 0 && m.lod_levels() > 0) m.export_lod();                  // <modelPath>_<it>.lod<k>.ply (DVS_EXPORT_LOD / setLodExport)
+    if (m.rank == 0 && m.opt.i(gsopt::EXPORT_LOD) > 0) m.export_lod();                  // <modelPath>_<it>.lod<k>.ply (DVS_EXPORT_LOD / setLodExport)
     m.evaluate(true);                                                       // <modelPath>_<it>_eval.json beside the PLY (rank 0, evaluation on)
     m.render_at_save();                                                     // <modelPath>_<it>_renders/*.jpg (rank 0, renderViews on)
     if (m.rank == 0 && m.mesh_resolution() > 0 && m.status == TrainingStatus::Training_Done)
@@ -164,38 +165,36 @@ void GaussianTrainerScene::exportMesh(const std::string& path) {
     if (path.empty() && res <= 0) { logf_("export_mesh: mesh extraction is outside this build's scope"); return; }
     m.extract_mesh(path.empty() ? m.mesh_file(m.step) : path, res > 0 ? res : 256);
 }
-// The editor's switch for what DVS_MESH_MIN_COMPONENT / DVS_MESH_NORMALS set for the CLI: once called it wins over the environment.
+// The editor's switches for what the extension variables set for the CLI (ext_options.hpp): they write the fields the environment
+// filled when the scene was made, so once called they win over it; an argument outside the row's bounds is reported and replaced.
 void GaussianTrainerScene::setMeshCleanup(float minComponentPercent, bool normals) {
     Impl& m = *impl_;
     const float p = std::isfinite(minComponentPercent) ? std::min(100.0f, std::max(0.0f, minComponentPercent)) : 0.0f;
-    m.mesh_min_bp_set = (int)std::lround((double)p * 100.0);
-    m.mesh_normals_set = normals ? 1 : 0;
+    m.opt.set(gsopt::MESH_MIN_COMPONENT, (double)std::lround((double)p * 100.0));
+    m.opt.set(gsopt::MESH_NORMALS, normals);
 }
-// The editor's switch for what DVS_MESH_DECIMATE sets for the CLI: once called it wins over the environment.
 void GaussianTrainerScene::setMeshDecimate(int factor) {
     Impl& m = *impl_;
-    if (factor != 0 && (factor < 2 || factor > 16)) { logf_("setMeshDecimate: %d is not 0 (off) or a factor 2..16: decimation is off", factor); factor = 0; }
-    m.mesh_decimate_set = factor;
+    if (!gsopt::admits(gsopt::MESH_DECIMATE, factor)) { logf_("setMeshDecimate: %d is not 0 (off) or a factor 2..16: decimation is off", factor); factor = 0; }
+    m.opt.set(gsopt::MESH_DECIMATE, factor);
 }
-// The editor's switch for what DVS_EXPORT_LOD / DVS_LOD_RESOLUTION set for the CLI: once called it wins over the environment.
 void GaussianTrainerScene::setLodExport(int levels, int resolution) {
     Impl& m = *impl_;
-    if (levels < 0 || levels > 4) { logf_("setLodExport: %d is not a number of levels 0 (off) .. 4: LOD export is off", levels); levels = 0; }
-    if (resolution < 32 || resolution > 1024) { logf_("setLodExport: %d is not a resolution 32..1024: 256 is used", resolution); resolution = 256; }
-    m.lod_levels_set = levels; m.lod_resolution_set = resolution;
+    if (!gsopt::admits(gsopt::EXPORT_LOD, levels)) { logf_("setLodExport: %d is not a number of levels 0 (off) .. 4: LOD export is off", levels); levels = 0; }
+    if (!gsopt::admits(gsopt::LOD_RESOLUTION, resolution)) { logf_("setLodExport: %d is not a resolution 32..1024: 256 is used", resolution); resolution = 256; }
+    m.opt.set(gsopt::EXPORT_LOD, levels); m.opt.set(gsopt::LOD_RESOLUTION, resolution);
     if (levels > 0 && m.rank == 0) logf_("config: lodExport %d levels, resolution %d (setLodExport)", levels, resolution);
 }
-// The editor's switch for what DVS_MASK_CARVE sets for the CLI: once called it wins over the environment.
 void GaussianTrainerScene::setMaskCarve(int percent) {
     Impl& m = *impl_;
-    if (percent < 0 || percent > 100) { logf_("setMaskCarve: %d is not a percentage 0 (off) .. 100: the mask carve is off", percent); percent = 0; }
-    m.mask_carve_set = percent;
+    if (!gsopt::admits(gsopt::MASK_CARVE, percent)) { logf_("setMaskCarve: %d is not a percentage 0 (off) .. 100: the mask carve is off", percent); percent = 0; }
+    m.opt.set(gsopt::MASK_CARVE, percent);
     m.report_mask_carve("setMaskCarve");
 }
 void GaussianTrainerScene::setReducedExport(float shCullThreshold, bool halfFloat) {
     Impl& m = *impl_;
-    if (!(shCullThreshold >= 0.0f)) { logf_("setReducedExport: the threshold %g is not a number >= 0: 0.01 is used", (double)shCullThreshold); shCullThreshold = 0.01f; }
-    m.reduced_set = true; m.reduced_thr_set = shCullThreshold; m.reduced_half_set = halfFloat;
+    if (!gsopt::admits(gsopt::SH_CULL_THRESHOLD, shCullThreshold)) { logf_("setReducedExport: the threshold %g is not a number >= 0: 0.01 is used", (double)shCullThreshold); shCullThreshold = 0.01f; }
+    m.opt.set(gsopt::SH_CULL_THRESHOLD, shCullThreshold); m.opt.set(gsopt::REDUCED_HALF, halfFloat);
 }
 // The editor's "export apply transform": what DVS_EXPORT_TRANSFORM / DVS_EXPORT_ORIENT set for the CLI. The last call wins.
 bool GaussianTrainerScene::setExportTransform(const dvs_types::Vec3& position, const dvs_types::Vec3& rotationEulerRad, float scale) {
@@ -405,10 +404,10 @@ bool GaussianTrainerScene::renderCameraToPng(int camera, const std::string& path
     Impl& m = *impl_;
     try {
         if (!m.ctx || camera < 0 || camera >= (int)m.cams.size() || path.empty()) return false;
-        if (layer != Impl::LAYER_COLOR && layer != Impl::LAYER_DEPTH && layer != Impl::LAYER_ALPHA) return false;
+        if (layer != gsopt::LAYER_COLOR && layer != gsopt::LAYER_DEPTH && layer != gsopt::LAYER_ALPHA) return false;
         HIP_OR_THROW(hipSetDevice(m.device));
         std::vector<std::string> files[3];
-        files[layer == Impl::LAYER_COLOR ? 0 : layer == Impl::LAYER_DEPTH ? 1 : 2] = {path};
+        files[layer == gsopt::LAYER_COLOR ? 0 : layer == gsopt::LAYER_DEPTH ? 1 : 2] = {path};
         return m.render_to_png({camera}, files, nullptr);
     } catch (const std::exception& e) {
         logf_("renderCameraToPng(%d, '%s', %d) failed: %s", camera, path.c_str(), layer, e.what());

@@ -26,6 +26,7 @@
 #include "ply_io.hpp"
 #include "dataset_io.hpp"
 #include "export_frame.hpp"
+#include "ext_options.hpp"
 
 namespace {
 const int kWidth[6] = {3, 3, 45, 1, 3, 4};          // pos sh0 shN opacity scale rot
@@ -67,6 +68,10 @@ struct TimedPair {
 
 struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     // the class is exported (GSTRAIN_API), its implementation is not
     GaussianTrainConfig cfg;
+    // the extension options the config struct has no room for (ext_options.hpp, INTEGRATION.md "Extension options"): read from the
+    // environment once, when the scene is constructed (a bad value is reported there and leaves the default); the set... methods of
+    // GaussianTrainerScene write the same fields, so a setter called at any time wins over the environment
+    gsopt::ExtOptions opt;
     int loadItr = -1;
     TrainingStatus status = TrainingStatus::Loading_Prepare;
     bool training = true;
@@ -197,11 +202,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     // the .reduced.ply export (EXPORT_REDUCED): per-splat degrees, the camera centres, centres / iteration counts / block counts on the
     // device (one small buffer). Nothing is allocated until the first such export.
     GrowBuf<uint8_t> d_red_degree, d_red_small;
-    // DVS_SH_CULL_THRESHOLD (colour units, default 0.01: chosen without measurement) and DVS_REDUCED_HALF (0 | 1), or what setReducedExport
-    // said (reduced_set: it was called)
-    bool reduced_set = false; float reduced_thr_set = 0.01f; bool reduced_half_set = false;
-    float sh_cull_threshold() const;
-    bool reduced_half() const;
+    // opt: SH_CULL_THRESHOLD (colour units, default 0.01: chosen without measurement) and REDUCED_HALF, or what setReducedExport said
 
     // export frame (INTEGRATION.md "Export frame"): a similarity p' = s R p + t every export but the resume PLY is written in — what
     // DVS_EXPORT_TRANSFORM / DVS_EXPORT_ORIENT said at load, or setExportTransform / setExportOrientation since. At a save rank 0 fills a
@@ -220,14 +221,11 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     void fill_transformed();
     void export_transformed();
 
-    // level-of-detail export (INTEGRATION.md "LOD export"; trainer_lod.cpp): DVS_EXPORT_LOD = L (0 = off .. 4) and DVS_LOD_RESOLUTION = R
-    // (32..1024, default 256), or what setLodExport said (-1: it was not called). At a save rank 0 merges the FULL model on a lattice of
+    // level-of-detail export (INTEGRATION.md "LOD export"; trainer_lod.cpp): opt's EXPORT_LOD = L (0 = off .. 4) and LOD_RESOLUTION = R
+    // (32..1024, default 256), or what setLodExport said. At a save rank 0 merges the FULL model on a lattice of
     // R >> (k - 1) cells along the longest side of the finite centres' box, for k = 1..L (include/dvs_export.h, last section), scores each
     // level on the held-out views when evaluation is on and writes <modelPath>_<it>.lod<k>.ply in the full PLY's layout (in the export
     // frame when one is set). Nothing is allocated, launched, written or logged while L is 0.
-    int lod_levels_set = -1, lod_resolution_set = -1;
-    int lod_levels() const;
-    int lod_resolution() const;
     GrowBuf<void> d_lod_scratch; GrowBuf<float> d_lod[6], d_lod_rows;       // a level's merged set (shN tiled), its shN as rows for the file
     struct LodScore { int it = -1, m = 0; double mean[4] = {NAN, NAN, NAN, NAN}; };     // it = -1: none
     LodScore lod_score[4];
@@ -257,8 +255,6 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     // per pass on eval_ctx (the sky composite only adds to the image: the saved forward state stays valid; the sky is in neither).
     // Per pass one dvs_png_encode_views launch per layer, one copy of the filtered streams and the saturation counts, then the same host
     // threads deflate (DVS_RENDER_PNG_LEVEL) and write one file each. Nothing is allocated until the first PNG render.
-    enum { LAYER_COLOR = 1, LAYER_DEPTH = 2, LAYER_ALPHA = 4 };
-    bool render_png = false; int render_layers = LAYER_COLOR, render_png_level = 6; float render_depth_scale = 1000.f;
     GrowBuf<uint8_t> d_render_png;                                           // 64 bytes of saturation counts, then per layer [views of the pass][stream]
     std::vector<uint8_t> render_png_host;
     GrowBuf<float> d_render_depth, d_render_alpha;                           // [eval_views][H][W]
@@ -273,15 +269,9 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     std::string mesh_file(int it) const { return save_path(it, "_mesh.ply"); }
     bool mesh_bounds(float lo[3], float hi[3]);
     bool extract_mesh(const std::string& path, int resolution);
-    // what happens to the mesh before it is written: DVS_MESH_MIN_COMPONENT (percent of the largest component's triangles, at most two
-    // decimals; kept here in 1/100 percent) and DVS_MESH_NORMALS (0 | 1), or what setMeshCleanup said (-1: it was not called)
-    int mesh_min_bp_set = -1, mesh_normals_set = -1;
-    int mesh_min_bp() const;
-    bool mesh_normals() const;
-    // decimation of the mesh, last before it is written: DVS_MESH_DECIMATE (0 = off, or 2..16 voxels of the extraction grid per cell and
-    // axis), or what setMeshDecimate said (-1: it was not called)
-    int mesh_decimate_set = -1;
-    int mesh_decimate() const;
+    // what happens to the mesh before it is written, from opt: MESH_MIN_COMPONENT (of the largest component's triangles, in 1/100 percent)
+    // and MESH_NORMALS, or what setMeshCleanup said; then MESH_DECIMATE (0 = off, or 2..16 voxels of the extraction grid per cell and
+    // axis), or what setMeshDecimate said
 
     // importance prune (cfg.importancePrune / DVS_IMPORTANCE_PRUNE; trainer_refine.cpp): the per-splat score summed over the training views
     // and the selection's scratch. Nothing is allocated until the first such prune.
@@ -289,12 +279,10 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     int importance_prune() const { return std::min(90, std::max(0, env_int("DVS_IMPORTANCE_PRUNE", cfg.importancePrune))); }   // percent, 0 = off
     void prune_importance(int it);
 
-    // mask carve (DVS_MASK_CARVE = T in 1..100, 0 = off, or what setMaskCarve said, -1: it was not called; trainer_refine.cpp,
+    // mask carve (opt's MASK_CARVE = T in 1..100, 0 = off, or what setMaskCarve said; trainer_refine.cpp,
     // INTEGRATION.md "Mask carve"): at every prune occasion and before every save the splats whose blend weight over the training views
     // landed on background pixels of the views' masks go (dvs_raster_foreground_views per pass of eval_ctx, dvs_foreground_plan). Inactive
     // when no training view has a mask. Nothing is allocated, launched, written or logged while T is 0.
-    int mask_carve_set = -1;
-    int mask_carve() const;
     bool carve_has_masks() const;                                            // some training view has a mask
     bool carve_has_valid() const;                                            // ... and some view kept its validity plane
     DevBuf<uint64_t> d_carve_votes;                                          // [2][cap rounded up to even]: foreground, background
@@ -304,10 +292,10 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     // sky model (cfg.enableBg, the reference's "Create Sky Model"; trainer_output.cpp): an equirectangular fp32 texture [sky_h][2 sky_h][3]
     // behind the splats (dvs_sky_forward_views / dvs_sky_backward_views, dvs_raster.h), initialised to zero, its own Adam state, the
     // step's gradient, and the lookup the forward leaves for the backward. Every camera of the trainer has bg = 0 (the loaders set
-    // none). Nothing is allocated, launched or written while enableBg is off. DVS_SKY_RESOLUTION (--skyResolution; 128, clamped to
-    // 16..1024) and DVS_SKY_LR (0.01) are read at load.
+    // none). Nothing is allocated, launched or written while enableBg is off. opt's SKY_RESOLUTION (128, clamped to 16..1024 at load)
+    // and SKY_LR (0.01).
     struct Step;
-    bool sky_on = false; int sky_h = 0; float sky_lr = 0.01f;
+    bool sky_on = false; int sky_h = 0;
     DevBuf<float> d_sky, d_sky_m, d_sky_v, d_sky_grad, d_sky_rgb;
     size_t sky_floats() const { return (size_t)sky_h * 2 * sky_h * 3; }
     dvs_sky sky() const { dvs_sky s{}; s.tex = d_sky.get(); s.width = 2 * sky_h; s.height = sky_h; return s; }

@@ -296,7 +296,7 @@ struct GaussianTrainerScene::Impl::CaptureLoad {
             refuse("the parameters of camera %u (%s) do not round to finite fp32 values", c.id, gsdata::model_name(c.model));
         DevBuf<uint8_t> pinhole(3 * v.p0);
         mask->alloc(v.p0 * sizeof(float));
-        if (mask8 && m.mask_carve() > 0) {
+        if (mask8 && m.opt.i(gsopt::MASK_CARVE) > 0) {
             valid->alloc(v.p0 * sizeof(float));
             DVS_OR_THROW(dvs_undistort_view(m.stream.get(), &desc, 1, full8.get(), nullptr, pinhole.get(), valid->get(), nullptr));
         }

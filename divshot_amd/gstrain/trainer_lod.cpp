@@ -4,36 +4,8 @@
 // Rank 0, on the training stream; the training arrays and the training context are never touched.
 #include "trainer.hpp"
 
-namespace {
-// digits alone, lo..hi -> the value; anything else is reported once (said) and gives `fallback`
-int lod_env(const char* name, int lo, int hi, int fallback, const char* what, bool* said) {
-    const char* e = getenv(name);
-    if (!e) return fallback;
-    int v = 0, nd = 0;
-    const char* c = e;
-    for (; *c >= '0' && *c <= '9' && nd < 5; ++c, ++nd) v = v * 10 + (*c - '0');
-    if (*c || nd == 0 || nd > 4 || v < lo || v > hi) {
-        if (!*said) logf_("lod: %s='%s' is not %s: ignored", name, e, what);
-        *said = true;
-        return fallback;
-    }
-    return v;
-}
-}  // namespace
-
-int GaussianTrainerScene::Impl::lod_levels() const {
-    if (lod_levels_set >= 0) return lod_levels_set;
-    static bool said = false;
-    return lod_env("DVS_EXPORT_LOD", 0, 4, 0, "a number of levels 0 (off) .. 4", &said);
-}
-int GaussianTrainerScene::Impl::lod_resolution() const {
-    if (lod_resolution_set >= 0) return lod_resolution_set;
-    static bool said = false;
-    return lod_env("DVS_LOD_RESOLUTION", 32, 1024, 256, "a resolution 32..1024", &said);
-}
-
 void GaussianTrainerScene::Impl::export_lod() {
-    const int L = lod_levels(), R = lod_resolution();
+    const int L = opt.i(gsopt::EXPORT_LOD), R = opt.i(gsopt::LOD_RESOLUTION);
     if (L <= 0 || rank != 0 || !ctx || n <= 0) return;
     HIP_OR_THROW(hipSetDevice(device));
     // the box of the finite centres, from the save's host copy: a centre with a non-finite coordinate is dropped by the merge and must

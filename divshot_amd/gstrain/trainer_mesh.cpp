@@ -14,52 +14,12 @@ struct GridGuard {                                                           // 
 
 int GaussianTrainerScene::Impl::mesh_resolution() const { return env_int("DVS_MESH_RESOLUTION", cfg.meshResolution); }
 
-// DVS_MESH_MIN_COMPONENT: digits with at most two decimals, 0..100 -> 1/100 percent; anything else is reported once and ignored
-int GaussianTrainerScene::Impl::mesh_min_bp() const {
-    if (mesh_min_bp_set >= 0) return mesh_min_bp_set;
-    const char* e = getenv("DVS_MESH_MIN_COMPONENT");
-    if (!e) return 0;
-    int whole = 0, frac = 0, nw = 0, nf = 0;
-    const char* c = e;
-    for (; *c >= '0' && *c <= '9' && nw < 4; ++c, ++nw) whole = whole * 10 + (*c - '0');
-    if (*c == '.') for (++c; *c >= '0' && *c <= '9' && nf < 3; ++c, ++nf) frac = frac * 10 + (*c - '0');
-    const int bp = whole * 100 + (nf == 1 ? frac * 10 : frac);
-    if (*c || nw == 0 || nw > 3 || nf > 2 || bp > 10000) {
-        static bool said = false;
-        if (!said) logf_("mesh: DVS_MESH_MIN_COMPONENT='%s' is not a percentage 0..100 with at most two decimals: ignored", e);
-        said = true;
-        return 0;
-    }
-    return bp;
-}
-bool GaussianTrainerScene::Impl::mesh_normals() const { return mesh_normals_set >= 0 ? mesh_normals_set != 0 : env_is("DVS_MESH_NORMALS", "1"); }
-// DVS_MESH_DECIMATE: one or two digits, 0 (off) or 2..16; anything else is reported once and ignored
-int GaussianTrainerScene::Impl::mesh_decimate() const {
-    if (mesh_decimate_set >= 0) return mesh_decimate_set;
-    const char* e = getenv("DVS_MESH_DECIMATE");
-    if (!e) return 0;
-    int f = 0, nd = 0;
-    const char* c = e;
-    for (; *c >= '0' && *c <= '9' && nd < 3; ++c, ++nd) f = f * 10 + (*c - '0');
-    if (*c || nd == 0 || nd > 2 || !(f == 0 || (f >= 2 && f <= 16))) {
-        static bool said = false;
-        if (!said) logf_("mesh: DVS_MESH_DECIMATE='%s' is not 0 (off) or an integer 2..16: ignored", e);
-        said = true;
-        return 0;
-    }
-    return f;
-}
-
 // The box the grid covers: DVS_MESH_BOUNDS=x0,y0,z0,x1,y1,z1, or with enableFocusRegion the focus region's world bounds, or the box of the centres of the splats with sigmoid(opacity) >= 0.5
 // cut to the cube of half-side 3 x extent about the camera centroid (extent: the scene extent the prune rules use).
 bool GaussianTrainerScene::Impl::mesh_bounds(float lo[3], float hi[3]) {
-    if (const char* e = getenv("DVS_MESH_BOUNDS")) {
-        float v[6];
-        if (sscanf(e, "%f,%f,%f,%f,%f,%f", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5]) == 6 && v[3] > v[0] && v[4] > v[1] && v[5] > v[2]) {
-            for (int k = 0; k < 3; ++k) { lo[k] = v[k]; hi[k] = v[3 + k]; }
-            return true;
-        }
-        logf_("mesh: DVS_MESH_BOUNDS='%s' is not x0,y0,z0,x1,y1,z1 with x1 > x0, y1 > y0, z1 > z0: ignored", e);
+    if (opt.given[gsopt::MESH_BOUNDS]) {
+        for (int k = 0; k < 3; ++k) { lo[k] = opt.f(gsopt::MESH_BOUNDS, k); hi[k] = opt.f(gsopt::MESH_BOUNDS, 3 + k); }
+        return true;
     }
     if (cfg.enableFocusRegion) {            // the world axis-aligned bounds of the region's eight corners
         for (int k = 0; k < 3; ++k) { lo[k] = INFINITY; hi[k] = -INFINITY; }
@@ -115,7 +75,7 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
     if (!mesh_bounds(lo, hi)) {
         // nothing opaque inside the cube: the empty mesh, a valid file with zero elements, and the same log line
         static const float no_normals[3] = {0, 0, 0};                     // (zero vertices: only the header's nx ny nz)
-        if (!write_ply(0, nullptr, nullptr, 0, nullptr, mesh_normals() ? no_normals : nullptr)) return false;
+        if (!write_ply(0, nullptr, nullptr, 0, nullptr, opt.on(gsopt::MESH_NORMALS) ? no_normals : nullptr)) return false;
         logf_("mesh @%d: 0 vertices, 0 triangles, grid 0x0x0, voxel 0, bounds %.9g,%.9g,%.9g,%.9g,%.9g,%.9g (no splat with opacity >= 0.5 within 3 x extent "
               "= %.9g of the cameras' centroid; DVS_MESH_BOUNDS sets the box), trunc 0, 0 views; render+depth 0.00 ms, fusion 0.00 ms, extraction 0.00 ms -> %s",
               step, (double)lo[0], (double)lo[1], (double)lo[2], (double)hi[0], (double)hi[1], (double)hi[2], 3.0 * (double)extent, path.c_str());
@@ -125,9 +85,7 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
     const float voxel = longest / (float)res;
     int32_t dims[3];
     for (int k = 0; k < 3; ++k) dims[k] = std::min(DVS_TSDF_MAX_DIM, std::max(2, (int)std::ceil((hi[k] - lo[k]) / voxel) + 1));
-    const char* tv = getenv("DVS_MESH_TRUNC_VOXELS");
-    const float trunc_voxels = tv && atof(tv) > 0.0 ? (float)atof(tv) : 4.0f;
-    const float trunc = trunc_voxels * voxel;
+    const float trunc = opt.f(gsopt::MESH_TRUNC_VOXELS) * voxel;                  // (DVS_MESH_TRUNC_VOXELS, default 4)
 
     GridGuard grid;
     const int rc = dvs_tsdf_create(lo, voxel, dims, &grid.g);
@@ -168,12 +126,12 @@ bool GaussianTrainerScene::Impl::extract_mesh(const std::string& path, int resol
     std::vector<float> xyz, nrm;
     std::vector<uint8_t> rgb;
     std::vector<uint32_t> tri;
-    const bool want_normals = mesh_normals();
-    const uint32_t min_bp = (uint32_t)mesh_min_bp();
+    const bool want_normals = opt.on(gsopt::MESH_NORMALS);
+    const uint32_t min_bp = (uint32_t)opt.i(gsopt::MESH_MIN_COMPONENT);
     bool cleaned = false;
     dvs_mesh_clean_info info{};
     double normals_ms = 0, clean_ms = 0, decimate_ms = 0;
-    const int decimate = mesh_decimate();
+    const int decimate = opt.i(gsopt::MESH_DECIMATE);
     bool decimated = false;
     dvs_mesh_decimate_info dinfo{};
     uint32_t dec_v0 = 0, dec_t0 = 0;

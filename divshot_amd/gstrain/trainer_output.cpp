@@ -33,17 +33,19 @@ void GaussianTrainerScene::Impl::report_config() const {
     report_export_transform();
     if (export_formats() & EXPORT_REDUCED)
         logf_("config: reduced export: twenty 256-entry k-means codebooks (at most 100 iterations each), %s positions; cullSH %d: %s%s",
-              reduced_half() ? "half-float" : "float", (int)cfg.cullSH,
-              cfg.cullSH ? ("every splat gets the smallest SH degree that loses at most " + std::to_string(sh_cull_threshold()) +
+              opt.on(gsopt::REDUCED_HALF) ? "half-float" : "float", (int)cfg.cullSH,
+              cfg.cullSH ? ("every splat gets the smallest SH degree that loses at most " + std::to_string(opt.f(gsopt::SH_CULL_THRESHOLD)) +
                             " of colour from any training camera's centre (no visibility test; the 0.01 default was chosen without measurement)").c_str()
                          : "every splat keeps the model's SH degree",
               !test_idx.empty() ? "; the payload is decoded on the device and scored on the held-out views" : "");
-    if (render_views && render_png)
+    const int render_layers = opt.i(gsopt::RENDER_LAYERS);
+    if (render_views && opt.on(gsopt::RENDER_FORMAT))
         logf_("config: renderViews %d: every save also writes the %s cameras as PNG files (layers %s%s%s, depth x %.9g as 16-bit gray with 0 = no depth, "
               "zlib level %d) to <modelPath>_<it>_renders/, rendered with the evaluation's options; samples and the per-row filter choice on the device, "
               "deflate on the host%s", render_views, render_views == RENDER_TEST ? "test" : render_views == RENDER_TRAIN ? "training" : "test and training",
-              (render_layers & LAYER_COLOR) ? "color" : "", (render_layers & LAYER_DEPTH) ? ((render_layers & LAYER_COLOR) ? ",depth" : "depth") : "",
-              (render_layers & LAYER_ALPHA) ? ((render_layers & (LAYER_COLOR | LAYER_DEPTH)) ? ",alpha" : "alpha") : "", (double)render_depth_scale, render_png_level,
+              (render_layers & gsopt::LAYER_COLOR) ? "color" : "", (render_layers & gsopt::LAYER_DEPTH) ? ((render_layers & gsopt::LAYER_COLOR) ? ",depth" : "depth") : "",
+              (render_layers & gsopt::LAYER_ALPHA) ? ((render_layers & (gsopt::LAYER_COLOR | gsopt::LAYER_DEPTH)) ? ",alpha" : "alpha") : "",
+              (double)opt.f(gsopt::RENDER_DEPTH_SCALE), opt.i(gsopt::RENDER_PNG_LEVEL),
               (render_views & RENDER_TEST) && test_idx.empty() ? " (no camera is held out: every camera is a training camera)" : "");
     else if (render_views)
         logf_("config: renderViews %d: every save also writes the %s cameras as JPEG files (quality %d, %s) to <modelPath>_<it>_renders/, rendered with the "
@@ -54,17 +56,17 @@ void GaussianTrainerScene::Impl::report_config() const {
         logf_("config: meshResolution %d: a save of the finished model and export_mesh() also write <modelPath>_<it>_mesh.ply — the training cameras' "
               "depth maps fused into a TSDF grid of %d voxels along the longest side, marching tetrahedra, all on the device", res,
               std::min(1024, std::max(16, res)));
-    if (mesh_min_bp() > 0 || mesh_normals())
+    if (const int bp = opt.i(gsopt::MESH_MIN_COMPONENT); bp > 0 || opt.on(gsopt::MESH_NORMALS))
         logf_("config: mesh clean-up: components with fewer than %g %% of the largest one's triangles are dropped%s, on the device, before the mesh "
-              "is written%s", mesh_min_bp() / 100.0, mesh_min_bp() > 0 ? "" : " (off)",
-              mesh_normals() ? "; vertex normals nx ny nz from the TSDF gradient" : "");
-    if (const int F = mesh_decimate(); F > 0)
+              "is written%s", bp / 100.0, bp > 0 ? "" : " (off)",
+              opt.on(gsopt::MESH_NORMALS) ? "; vertex normals nx ny nz from the TSDF gradient" : "");
+    if (const int F = opt.i(gsopt::MESH_DECIMATE); F > 0)
         logf_("config: mesh decimation: vertex clustering on cells of %d voxels of the extraction grid per axis (mean position, colour and normal per "
               "cell; collapsed and repeated triangles dropped), on the device, last before the mesh is written", F);
-    if (const int L = lod_levels(); L > 0)
+    if (const int L = opt.i(gsopt::EXPORT_LOD), R = opt.i(gsopt::LOD_RESOLUTION); L > 0)
         logf_("config: lodExport %d levels, resolution %d: every save also writes <modelPath>_<it>.lod<k>.ply, k = 1..%d — the full model's splats merged "
               "per cell of a lattice of %d >> (k - 1) cells along the longest side of the finite centres' box (weighted mean, moment-matched "
-              "covariance, weight-preserving opacity), on the device%s", L, lod_resolution(), L, lod_resolution(),
+              "covariance, weight-preserving opacity), on the device%s", L, R, L, R,
               !test_idx.empty() ? "; every level is scored on the held-out views" : "");
     if (const int P = importance_prune(); P > 0) {
         const int asked = env_int("DVS_IMPORTANCE_PRUNE", cfg.importancePrune);
@@ -77,7 +79,7 @@ void GaussianTrainerScene::Impl::report_config() const {
     if (sky_on)
         logf_("config: skyModel %dx%d: enableBg — an equirectangular fp32 texture behind the splats, looked up along each pixel's ray and trained with "
               "them (Adam, lr %g); every save also writes <modelPath>_<it>.sky; evaluation and written renders composite it; mesh export, the "
-              "importance score and the depth pass do not see it", 2 * sky_h, sky_h, (double)sky_lr);
+              "importance score and the depth pass do not see it", 2 * sky_h, sky_h, (double)opt.f(gsopt::SKY_LR));
     if (cfg.enableFocusRegion)
         logf_("config: focusRegion box %.9g,%.9g,%.9g .. %.9g,%.9g,%.9g under F = T(%g,%g,%g) R(%g,%g,%g rad, Rz Ry Rx) S(%g,%g,%g): a splat stays while "
               "its centre p has lo <= F^-1 p <= hi (faces included, extents not considered; pruned after load, when the region changes, before every "
@@ -100,7 +102,7 @@ void GaussianTrainerScene::Impl::report_config() const {
 
 // the maskCarve line of report_config(), and of setMaskCarve (`by`); nothing while it is off
 void GaussianTrainerScene::Impl::report_mask_carve(const char* by) const {
-    const int T = mask_carve();
+    const int T = opt.i(gsopt::MASK_CARVE);
     if (T <= 0 || rank != 0) return;
     const std::string who = by ? std::string(" (") + by + ")" : std::string();
     if (cams.empty()) { logf_("config: maskCarve %d%s: decided when the training views are loaded", T, who.c_str()); return; }
@@ -230,8 +232,7 @@ void GaussianTrainerScene::Impl::write_eval_json() const {
 void GaussianTrainerScene::Impl::setup_sky(bool resumed) {
     sky_on = cfg.enableBg;
     if (!sky_on) return;
-    sky_h = std::min(1024, std::max(16, env_int("DVS_SKY_RESOLUTION", 128)));
-    if (const char* e = getenv("DVS_SKY_LR")) { const float v = (float)atof(e); if (v > 0.f && std::isfinite(v)) sky_lr = v; }
+    sky_h = std::min(1024, std::max(16, opt.i(gsopt::SKY_RESOLUTION)));
     const size_t bytes = sky_floats() * sizeof(float);
     for (DevBuf<float>* b : {&d_sky, &d_sky_m, &d_sky_v, &d_sky_grad}) { b->alloc(bytes); HIP_OR_THROW(hipMemset(b->get(), 0, bytes)); }
     d_sky_rgb.alloc((size_t)vpi * 3 * (size_t)W * H * sizeof(float));
@@ -360,28 +361,13 @@ void GaussianTrainerScene::Impl::export_spz() {
     });
 }
 
-float GaussianTrainerScene::Impl::sh_cull_threshold() const {
-    if (reduced_set) return reduced_thr_set;
-    const char* e = getenv("DVS_SH_CULL_THRESHOLD");
-    if (!e) return 0.01f;
-    char* end = nullptr;
-    const float t = strtof(e, &end);
-    if (end == e || *end || !(t >= 0.0f)) {
-        static bool said = false;
-        if (!said) { logf_("DVS_SH_CULL_THRESHOLD='%s' is not a number >= 0: 0.01 is used", e); said = true; }
-        return 0.01f;
-    }
-    return t;
-}
-bool GaussianTrainerScene::Impl::reduced_half() const { return reduced_set ? reduced_half_set : env_int("DVS_REDUCED_HALF", 0) == 1; }
-
 // The .reduced.ply export (include/dvs_export.h, last section): per-splat degrees — dvs_sh_degree_select over the training cameras'
 // centres with cullSH, else the model's SH degree (sh_max) for every splat —, the twenty codebooks, the block counts (16 bytes to the host, for
 // the layout), the payload; only the payload with its 20 KB table crosses to the host. Rank 0, on the training stream. With evaluation
 // on, the device payload is decoded into the second parameter set and scored like the .spz one.
 void GaussianTrainerScene::Impl::export_reduced() {
     auto t0 = std::chrono::steady_clock::now();
-    const int D = sh_max, half = reduced_half() ? 1 : 0;   // the degree the full PLY stores and the evaluation renders (as the .spz export)
+    const int D = sh_max, half = opt.on(gsopt::REDUCED_HALF) ? 1 : 0;   // the degree the full PLY stores and the evaluation renders (as the .spz export)
     const std::vector<int> tc = training_cameras();
     const size_t o_iters = (size_t)DVS_REDUCED_BOOKS * DVS_REDUCED_ENTRIES * sizeof(float), o_counts = o_iters + 96, o_cams = o_counts + 16;
     d_export_scratch.reserve(dvs_reduced_scratch_bytes(n));
@@ -399,7 +385,7 @@ void GaussianTrainerScene::Impl::export_reduced() {
         std::vector<float> centre(tc.size() * 3);
         for (size_t k = 0; k < tc.size(); ++k) for (int a = 0; a < 3; ++a) centre[3 * k + a] = cams[(size_t)tc[k]].campos[a];
         HIP_OR_THROW(hipMemcpyAsync(small + o_cams, centre.data(), centre.size() * sizeof(float), hipMemcpyHostToDevice, stream.get()));
-        check(dvs_sh_degree_select(stream.get(), n, D, d_param[P_POS].get(), d_param[P_SHN].get(), DVS_SHN_TILED, (const float*)(small + o_cams), (int)tc.size(), sh_cull_threshold(),
+        check(dvs_sh_degree_select(stream.get(), n, D, d_param[P_POS].get(), d_param[P_SHN].get(), DVS_SHN_TILED, (const float*)(small + o_cams), (int)tc.size(), opt.f(gsopt::SH_CULL_THRESHOLD),
                                    d_red_degree.get()), "dvs_sh_degree_select");
         HIP_OR_THROW(hipStreamSynchronize(stream.get()));                    // (also: `centre` leaves scope)
     } else {
@@ -480,21 +466,19 @@ bool GaussianTrainerScene::Impl::set_export_orientation(const char* axis, const 
              "their centroid moved to the origin", from, axis, up[0], up[1], up[2], tc.size());
     return set_export_transform(m, how);
 }
-// DVS_EXPORT_TRANSFORM="tx,ty,tz,rx,ry,rz,s" (Euler angles in radians, R = Rz Ry Rx) / DVS_EXPORT_ORIENT="+y": read at load
+// opt's EXPORT_TRANSFORM = tx,ty,tz,rx,ry,rz,s (Euler angles in radians, R = Rz Ry Rx) / EXPORT_ORIENT, as the environment gave them: taken
+// at load, once the cameras are there
 void GaussianTrainerScene::Impl::setup_export_transform() {
-    const char *et = getenv("DVS_EXPORT_TRANSFORM"), *eo = getenv("DVS_EXPORT_ORIENT");
-    if (et && *et) {
-        if (eo && *eo) logf_("exportTransform: DVS_EXPORT_TRANSFORM and DVS_EXPORT_ORIENT are both set: DVS_EXPORT_TRANSFORM is used");
-        float v[7]; char tail = 0;
+    const bool et = opt.given[gsopt::EXPORT_TRANSFORM], eo = opt.given[gsopt::EXPORT_ORIENT];
+    if (gsopt::two_export_frames(et, eo)) logf_("exportTransform: DVS_EXPORT_TRANSFORM and DVS_EXPORT_ORIENT are both set: DVS_EXPORT_TRANSFORM is used");
+    if (et) {
+        float v[7];
+        for (int k = 0; k < 7; ++k) v[k] = opt.f(gsopt::EXPORT_TRANSFORM, k);
         dvs_similarity m;
-        if (sscanf(et, "%f,%f,%f,%f,%f,%f,%f%c", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &v[6], &tail) != 7 ||
-            dvs_similarity_from_trs(v, v + 3, v[6], &m) != DVS_OK) {
-            logf_("exportTransform: DVS_EXPORT_TRANSFORM='%s' is not tx,ty,tz,rx,ry,rz,s with finite numbers and s > 0: ignored", et);
-            return;
-        }
-        set_export_transform(m, std::string("DVS_EXPORT_TRANSFORM=") + et + " (T R S, R = Rz Ry Rx, radians)");
-    } else if (eo && *eo) {
-        set_export_orientation(eo, "DVS_EXPORT_ORIENT");
+        DVS_OR_THROW(dvs_similarity_from_trs(v, v + 3, v[6], &m));          // (finite, s > 0: the row's grammar)
+        set_export_transform(m, "DVS_EXPORT_TRANSFORM=" + opt.text[gsopt::EXPORT_TRANSFORM] + " (T R S, R = Rz Ry Rx, radians)");
+    } else if (eo) {
+        set_export_orientation(opt.text[gsopt::EXPORT_ORIENT].c_str(), "DVS_EXPORT_ORIENT");
     }
 }
 void GaussianTrainerScene::Impl::report_export_transform() const {

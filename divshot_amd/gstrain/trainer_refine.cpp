@@ -197,21 +197,6 @@ void GaussianTrainerScene::Impl::prune_importance(int it) {
 // before the light prune and before every save, after the focus-region prune in both places. A plan that would leave no splat is
 // logged and not applied. Every rank scores all training cameras itself: integer votes, an exact rule, no communication — the
 // replicas stay bit-identical.
-int GaussianTrainerScene::Impl::mask_carve() const {
-    if (mask_carve_set >= 0) return mask_carve_set;
-    const char* e = getenv("DVS_MASK_CARVE");
-    if (!e) return 0;
-    int v = 0, nd = 0;
-    const char* c = e;
-    for (; *c >= '0' && *c <= '9' && nd < 4; ++c, ++nd) v = v * 10 + (*c - '0');
-    if (*c || nd == 0 || v > 100) {
-        static bool said = false;
-        if (!said) logf_("mask carve: DVS_MASK_CARVE='%s' is not a percentage 0 (off) .. 100: ignored", e);
-        said = true;
-        return 0;
-    }
-    return v;
-}
 bool GaussianTrainerScene::Impl::carve_has_masks() const {
     for (int c : training_cameras()) if (view_mask((size_t)c)) return true;
     return false;
@@ -221,7 +206,7 @@ bool GaussianTrainerScene::Impl::carve_has_valid() const {
     return false;
 }
 void GaussianTrainerScene::Impl::prune_mask_carve(int it) {
-    const int T = mask_carve();
+    const int T = opt.i(gsopt::MASK_CARVE);
     if (T <= 0 || n <= 0 || !carve_has_masks()) return;
     pruning = true;
     ensure_eval_ctx();

@@ -59,29 +59,9 @@ void GaussianTrainerScene::Impl::setup_render() {
     render_views = env_int("DVS_RENDER_VIEWS", cfg.renderViews) & (RENDER_TEST | RENDER_TRAIN);
     render_quality = std::max(1, std::min(env_int("DVS_RENDER_QUALITY", cfg.renderQuality), 100));
     render_sampling = env_int("DVS_RENDER_SAMPLING", cfg.renderSampling) == 1 ? DVS_JPEG_SAMPLING_444 : DVS_JPEG_SAMPLING_420;
-    // the PNG settings travel as environment variables (the config struct has no room left); a bad value is reported once, here, and ignored
-    if (const char* e = getenv("DVS_RENDER_FORMAT")) {
-        if (std::string_view(e) == "png") render_png = true;
-        else if (std::string_view(e) != "jpg") logf_("render: DVS_RENDER_FORMAT='%s' is not jpg or png: ignored", e);
-    }
-    if (const char* e = getenv("DVS_RENDER_LAYERS")) {
-        char* end = nullptr;
-        const long v = strtol(e, &end, 10);
-        if (end == e || *end || v < 1 || v > 7) logf_("render: DVS_RENDER_LAYERS='%s' is not a sum 1..7 of 1 (color), 2 (depth), 4 (alpha): ignored", e);
-        else if (!render_png && v != LAYER_COLOR) logf_("render: DVS_RENDER_LAYERS='%s' asks for depth or alpha, which JPEG files do not carry (DVS_RENDER_FORMAT=png does): ignored", e);
-        else render_layers = (int)v;
-    }
-    if (const char* e = getenv("DVS_RENDER_DEPTH_SCALE")) {
-        char* end = nullptr;
-        const double v = strtod(e, &end);
-        if (end == e || *end || !std::isfinite(v) || !(v > 0) || !std::isfinite((float)v) || !((float)v > 0.f)) logf_("render: DVS_RENDER_DEPTH_SCALE='%s' is not a finite number > 0: ignored", e);
-        else render_depth_scale = (float)v;
-    }
-    if (const char* e = getenv("DVS_RENDER_PNG_LEVEL")) {
-        char* end = nullptr;
-        const long v = strtol(e, &end, 10);
-        if (end == e || *end || v < 0 || v > 9) logf_("render: DVS_RENDER_PNG_LEVEL='%s' is not a zlib level 0..9: ignored", e);
-        else render_png_level = (int)v;
+    if (gsopt::layers_need_png(opt.i(gsopt::RENDER_LAYERS), opt.on(gsopt::RENDER_FORMAT))) {     // (the PNG settings themselves: opt)
+        logf_("render: DVS_RENDER_LAYERS='%s' asks for depth or alpha, which JPEG files do not carry (DVS_RENDER_FORMAT=png does): ignored", opt.text[gsopt::RENDER_LAYERS].c_str());
+        opt.v[gsopt::RENDER_LAYERS][0] = gsopt::LAYER_COLOR;
     }
     // file names: the image stems when every camera has one and they are unique, cam_%04d otherwise (a synthetic scene). cam_names is
     // filled in step with cams by both loaders.
@@ -140,7 +120,7 @@ bool GaussianTrainerScene::Impl::render_to_png(const std::vector<int>& which, co
     ensure_eval_ctx();
     static const int kKind[3] = {DVS_PNG_KIND_RGB8, DVS_PNG_KIND_GRAY16, DVS_PNG_KIND_GRAY8};
     static const int kType[3] = {2, 0, 0}, kDepth[3] = {8, 16, 8};
-    const float scales[3] = {255.f, render_depth_scale, 255.f};
+    const float scales[3] = {255.f, opt.f(gsopt::RENDER_DEPTH_SCALE), 255.f};
     constexpr size_t kCounts = DVS_PNG_ENCODE_MAX_VIEWS * sizeof(uint32_t);   // the saturation counts lead the buffer: one copy brings both
     size_t bytes_of[3] = {0, 0, 0}, per_view = 0;
     int n_layers = 0, asked[3] = {0, 0, 0};                                  // the layers asked for, in file order
@@ -160,7 +140,7 @@ bool GaussianTrainerScene::Impl::render_to_png(const std::vector<int>& which, co
     if (maps) { d_render_depth.reserve((size_t)eval_views * map * sizeof(float)); d_render_alpha.reserve((size_t)eval_views * map * sizeof(float)); }
     const dvs_opts opts = eval_opts();
     char scale_text[32];
-    snprintf(scale_text, sizeof scale_text, "%.9g", (double)render_depth_scale);
+    snprintf(scale_text, sizeof scale_text, "%.9g", (double)opt.f(gsopt::RENDER_DEPTH_SCALE));
     const gspng::TextPairs depth_text = {{"depth_scale", scale_text}};
     bool all_ok = true;
     for_each_eval_pass(splats(), which, true, [&](const EvalPass& p) {
@@ -188,7 +168,7 @@ bool GaussianTrainerScene::Impl::render_to_png(const std::vector<int>& which, co
         // task t: view t / n_layers, layer asked[t % n_layers]
         const Written w = write_files(nb * n_layers, load_threads(), "out of memory while writing the view", [&](int t, std::string* out, std::string* err) {
             const int k = t / n_layers, l = asked[t % n_layers];
-            return gspng::write_png(W, H, kDepth[l], kType[l], render_png_host.data() + layer_at[l] + (size_t)k * bytes_of[l], bytes_of[l], render_png_level,
+            return gspng::write_png(W, H, kDepth[l], kType[l], render_png_host.data() + layer_at[l] + (size_t)k * bytes_of[l], bytes_of[l], opt.i(gsopt::RENDER_PNG_LEVEL),
                                     l == 1 ? &depth_text : nullptr, out, err);
         }, [&](int t) -> const std::string& { return files[asked[t % n_layers]][(size_t)(first + t / n_layers)]; });
         for (int k = 0; k < nb; ++k) {
@@ -220,11 +200,11 @@ void GaussianTrainerScene::Impl::render_at_save() {
     std::error_code ec;
     std::filesystem::create_directories(dir, ec);
     if (ec) { logf_("render @%d: cannot create %s: %s", step, dir.c_str(), ec.message().c_str()); return; }
-    if (render_png) {
+    if (opt.on(gsopt::RENDER_FORMAT)) {
         static const char* const kSuffix[3] = {".png", "_depth.png", "_alpha.png"};
         std::vector<std::string> layers[3];
         for (int l = 0; l < 3; ++l)
-            if (render_layers & (1 << l)) for (int c : which) layers[l].push_back(dir + "/" + camera_name(c) + kSuffix[l]);
+            if (opt.i(gsopt::RENDER_LAYERS) & (1 << l)) for (int c : which) layers[l].push_back(dir + "/" + camera_name(c) + kSuffix[l]);
         PngStats st;
         render_to_png(which, layers, &st);
         logf_("render @%d: %zu views, %zu files, %zu bytes, filtering %.3f ms (device, events), deflate %.3f ms (host, %d threads, wall), %zu depth samples saturated",

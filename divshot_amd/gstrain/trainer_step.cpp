@@ -125,8 +125,7 @@ void GaussianTrainerScene::Impl::loss_of_view(const Step& s, int v) {
 
 // ---- focus region ----
 // The box of the region: DVS_FOCUS_REGION=x0,y0,z0,x1,y1,z1 (--focusRegion), or the axis-aligned bounds of the initial centres; the
-// initial rotation DVS_FOCUS_ROTATION=rx,ry,rz (--focusRotation; radians, as updateFocusRegion's). Malformed values are reported once
-// (this runs once, at load) and ignored.
+// initial rotation DVS_FOCUS_ROTATION=rx,ry,rz (--focusRotation; radians, as updateFocusRegion's), both from opt.
 void GaussianTrainerScene::Impl::setup_region() {
     for (int k = 0; k < 3; ++k) { focus_lo[k] = INFINITY; focus_hi[k] = -INFINITY; }
     const std::vector<float>& p = init_host[P_POS];
@@ -135,20 +134,9 @@ void GaussianTrainerScene::Impl::setup_region() {
         for (int k = 0; k < 3; ++k) { focus_lo[k] = std::min(focus_lo[k], p[i + k]); focus_hi[k] = std::max(focus_hi[k], p[i + k]); }
     }
     for (int k = 0; k < 3; ++k) if (!(focus_hi[k] >= focus_lo[k])) focus_lo[k] = focus_hi[k] = 0.f;      // (no finite centre)
-    if (const char* e = getenv("DVS_FOCUS_REGION")) {
-        float v[6]; char tail = 0;
-        if (sscanf(e, "%f,%f,%f,%f,%f,%f%c", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5], &tail) == 6 && v[3] > v[0] && v[4] > v[1] && v[5] > v[2] &&
-            std::all_of(v, v + 6, [](float f) { return std::isfinite(f); }))
-            for (int k = 0; k < 3; ++k) { focus_lo[k] = v[k]; focus_hi[k] = v[3 + k]; }
-        else logf_("focus region: DVS_FOCUS_REGION='%s' is not x0,y0,z0,x1,y1,z1 with x1 > x0, y1 > y0, z1 > z0: ignored", e);
-    }
-    float rot[3] = {0.f, 0.f, 0.f};
-    if (const char* e = getenv("DVS_FOCUS_ROTATION")) {
-        float v[3]; char tail = 0;
-        if (sscanf(e, "%f,%f,%f%c", &v[0], &v[1], &v[2], &tail) == 3 && std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]))
-            for (int k = 0; k < 3; ++k) rot[k] = v[k];
-        else logf_("focus region: DVS_FOCUS_ROTATION='%s' is not rx,ry,rz (radians): ignored", e);
-    }
+    if (opt.given[gsopt::FOCUS_REGION])
+        for (int k = 0; k < 3; ++k) { focus_lo[k] = opt.f(gsopt::FOCUS_REGION, k); focus_hi[k] = opt.f(gsopt::FOCUS_REGION, 3 + k); }
+    const float rot[3] = {opt.f(gsopt::FOCUS_ROTATION, 0), opt.f(gsopt::FOCUS_ROTATION, 1), opt.f(gsopt::FOCUS_ROTATION, 2)};
     const float zero[3] = {0.f, 0.f, 0.f}, one[3] = {1.f, 1.f, 1.f};
     set_region(zero, rot, one);
     region_flag_seen = cfg.enableFocusRegion;
@@ -275,7 +263,7 @@ void GaussianTrainerScene::Impl::render_backward(Step& s) {
 void GaussianTrainerScene::Impl::step_sky(const Step& s) {
     if (!sky_on) return;
     if (comm) DVS_OR_THROW(dvs_comm_all_reduce_sum_f32(comm.get(), stream.get(), d_sky_grad.get(), sky_floats()));
-    DVS_OR_THROW(dvs_adam_step(stream.get(), d_sky.get(), d_sky_grad.get(), d_sky_m.get(), d_sky_v.get(), sky_floats(), sky_lr, kAdamBeta1, kAdamBeta2,
+    DVS_OR_THROW(dvs_adam_step(stream.get(), d_sky.get(), d_sky_grad.get(), d_sky_m.get(), d_sky_v.get(), sky_floats(), opt.f(gsopt::SKY_LR), kAdamBeta1, kAdamBeta2,
                                kAdamEps, s.it));
 }
 
