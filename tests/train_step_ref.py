@@ -14,8 +14,8 @@ this build's plugin defines (divshot_amd/gstrain/gstrain.cpp trainStep) from ind
 Options of the step, each off by default (the host flags of gstrain/trainer_step.cpp plan_step / loss_of_view and gstrain.cpp trainStep): start_step (a resume
 through --load_itr), progressive (SH degree min(sh, step // 1000)), antialias, pack_u8 (8-bit training views), mask (the synthetic
 inscribed-ellipse mask on the photometric gradient), reset_alpha_every (the opacity reset inside the step), train_cams (the training
-cameras of a hold-out), the light prune (prune_decisions / apply_prune) and the importance prune (importance_scores /
-importance_decisions).
+cameras of a hold-out), the light prune (prune_decisions / apply_prune), the importance prune (importance_scores /
+importance_decisions) and sky (--enableBg 1: the learned texture behind the splats, its own section of TrainStepRef).
 
 dtype float32 mirrors the arithmetic the plugin performs; float64 is the ground truth of the same recurrences. The parity test compares
 the plugin with the float64 trajectory on every element where the float32 restatement itself stays within tolerance of it: Adam with
@@ -121,7 +121,7 @@ def scene_extent(cams):
 class TrainStepRef:
     def __init__(self, oracle_cls, cams, targets, init, sh_degree, num_iters, dtype=np.float32, views_per_step=1, world=1, lr=None,
                  ssim_weight=0.0, mcmc_reg=None, start_step=0, progressive=False, antialias=False, pack_u8=False, mask=False,
-                 reset_alpha_every=0, train_cams=None):
+                 reset_alpha_every=0, train_cams=None, sky=None):
         """ssim_weight: w of L = (1 - w) mean|x - y| + w (1 - mean SSIM) (--ssim, main.cpp:24: 0.2; 0 = L1 only).
         mcmc_reg: (opacity_reg, scale_reg) of densifyStrategy 1 (gstrain/trainer_step.cpp finish_range: 0.01, 0.01), added to the summed gradients once per step.
         start_step: a resume through --load_itr — the step number (Adam bias correction, position-rate schedule, SH degree) starts there,
@@ -130,9 +130,17 @@ class TrainStepRef:
         multiplied by ellipse_mask. reset_alpha_every: --resetAlphaEvery, applied after the Adam step of iterations it % r == 0.
         train_cams: --evalHoldout h, the indices i with i % h != 0 in order — a draw is train_cams[xorshift % len(train_cams)] (gstrain/
         trainer.hpp draw_cameras: held-out cameras are never trained on); None = every camera, cams[xorshift % len(cams)]. The extent
-        stays that of ALL cameras (trainer_load.cpp finish_load)."""
+        stays that of ALL cameras (trainer_load.cpp finish_load).
+        sky: --enableBg 1, dict(tex=[Hs, 2 Hs, 3], lr=DVS_SKY_LR) — the texture a resume reads from <model>_<it>.sky (see the sky
+        section below); None = no sky, nothing of it runs."""
         self.w_ssim, self.mcmc_reg = float(ssim_weight), mcmc_reg
         self.dt = np.dtype(dtype)
+        self.sky = None
+        if sky is not None:
+            tex = np.array(sky["tex"], self.dt)
+            assert tex.ndim == 3 and tex.shape[1] == 2 * tex.shape[0] and tex.shape[2] == 3, tex.shape
+            self.sky = dict(tex=tex, m=np.zeros_like(tex), v=np.zeros_like(tex), lr=float(sky["lr"]))
+            self._taps = {}
         self.orc = oracle_cls(self.dt)
         self.progressive, self.antialias, self.reset_every = bool(progressive), bool(antialias), int(reset_alpha_every)
         self.cams, self.targets = cams, [np.asarray(pack_unpack_u8(t) if pack_u8 else t, self.dt) for t in targets]
@@ -171,9 +179,14 @@ class TrainStepRef:
         draws = self.order[k * n_views:(k + 1) * n_views]
         G = {k: np.zeros_like(v) for k, v in self.P.items()}
         loss = 0.0
+        self.tex_grads = []                                    # per view of the step, all ranks' (sky only)
         for ci in draws:
             cam, tgt = self.cams[ci], self.targets[ci]
             out = self.orc.forward(self.P, cam, sh_degree=self.degree(), antialias=self.antialias, absgrad=True, grad_mode=1)
+            if self.sky is not None:                           # out = C + final_T s; the loss below is taken on it
+                C, T = out, self.orc.get("final_T").copy()
+                s = self.sky_lookup(cam)
+                out = self.loss_image(C, T, s)
             d = out - tgt
             scale = f(1.0) / f(d.size)
             w = f(self.w_ssim)
@@ -196,6 +209,11 @@ class TrainStepRef:
             self.grad_accum_mean2d += np.where(vis, np.hypot(gm[:, 0] * f(0.5 * W), gm[:, 1] * f(0.5 * H)), 0).astype(self.dt)
             self.denom += vis.astype(self.dt)
             self.max_radii = np.maximum(self.max_radii, np.where(vis, radii, 0))
+            if self.sky is not None:                       # (after the statistics: they are the colour path's, sky.hip leaves columns 9, 10 alone)
+                self.tex_grads.append(self.sky_tex_gradient(cam, T, dL))
+                gT = self.final_T_gradient(cam, dL, s)
+                for k in KEYS:
+                    G[k] += gT[k].reshape(G[k].shape)
         self.losses.append(loss / len(draws))
         if self.mcmc_reg is not None:            # dvs_mcmc_regularize: d/dlogit of wo mean(sigmoid), d/dlog s of ws mean(exp(log s))
             wo, ws = self.mcmc_reg
@@ -226,6 +244,8 @@ class TrainStepRef:
     def train_step(self):
         G = self.gradients()
         self.adam(G)
+        if self.sky is not None:
+            self.sky_adam(self.tex_gradient())
         self.step += 1
         if self.reset_every > 0 and self.step % self.reset_every == 0:      # trainStep reset_now -> dvs_reset_opacity(0.01)
             f = self.dt.type
@@ -233,6 +253,77 @@ class TrainStepRef:
             self.M["opacity"][:] = 0
             self.V["opacity"][:] = 0
         return G
+
+    # ---- sky model (--enableBg 1; gstrain/trainer_step.cpp render_backward / step_sky, csrc/sky.hip) -----------------------------------------
+    # The oracle knows a constant cam.bg only. A background that varies per pixel, out = C + final_T s, is restated from it by linearity:
+    # the oracle's backward is linear in dL and, through the one term bg . dL it hands to dL/dalpha, in bg — so the gradient through
+    # final_T of sum_p final_T(p) h(p), h = s . dL, is backward(dL' = (h, 0, 0); bg = (1, 0, 0)) - backward(dL'; bg = 0): the colour
+    # path of dL' is in both and cancels. Each piece is its own method so that a test can restate the step WRONGLY in one place.
+    def _sky_taps(self, cam):
+        """-> (texel indices [H,W,4], bilinear weights [H,W,4] in the run's dtype) of the camera's pixels: tests/sky_ref.py's rays and taps"""
+        import sky_ref as SR
+        key = (cam.width, cam.height, tuple(cam.proj))
+        if key not in self._taps:
+            Hs, Ws, _ = self.sky["tex"].shape
+            idx, w = SR.taps(SR.rays(cam.proj[:], cam.width, cam.height), Ws, Hs)
+            self._taps[key] = (idx, w.astype(self.dt))
+        return self._taps[key]
+
+    def sky_lookup(self, cam):
+        """s [3,H,W]: sky_ref.lookup in the run's dtype"""
+        idx, w = self._sky_taps(cam)
+        flat = self.sky["tex"].reshape(-1, 3)
+        return np.ascontiguousarray(np.moveaxis((flat[idx] * w[..., None]).sum(-2), -1, 0), self.dt)
+
+    def loss_image(self, C, T, s):
+        """the image the loss and its gradient are formed from"""
+        return (C + T[None] * s).astype(self.dt)
+
+    def sky_tex_gradient(self, cam, T, dL):
+        """dL/dtex [Hs,Ws,3] of one view: sky_ref.sky_backward_tex (the same sums in the same order) in the run's dtype"""
+        idx, w = self._sky_taps(cam)
+        Hs, Ws, _ = self.sky["tex"].shape
+        tg = np.moveaxis(T[None] * dL, 0, -1)
+        out = np.zeros((Hs * Ws, 3), self.dt)
+        for k in range(4):
+            np.add.at(out, idx[..., k].reshape(-1), (w[..., k, None] * tg).reshape(-1, 3))
+        return out.reshape(Hs, Ws, 3)
+
+    def final_T_gradient(self, cam, dL, s):
+        """the gradient of sum_p final_T(p) (s(p) . dL(p)) in the six groups (DVS_GRAD_LINEAGE, like the colour path). Leaves the oracle
+        in the state of another forward: read what the step needs of the colour-path state before."""
+        assert cam.bg[0] == 0 and cam.bg[1] == 0 and cam.bg[2] == 0, "the sky texture is the background (never both)"
+        dLh = np.zeros_like(dL)
+        dLh[0] = (s * dL).sum(0)
+        kw = dict(sh_degree=self.degree(), antialias=self.antialias, absgrad=True, grad_mode=1)
+        g = []
+        for b in (1.0, 0.0):
+            cam.bg[0] = b
+            try:
+                self.orc.forward(self.P, cam, **kw)
+                g.append(self.orc.backward(dLh, grad_mode=1))
+            finally:
+                cam.bg[0] = 0.0
+        return {k: g[0][k] - g[1][k] for k in KEYS}
+
+    def tex_gradient(self):
+        """the step's texture gradient: the sum over its views, all ranks' (step_sky's all-reduce)"""
+        return sum(self.tex_grads[1:], self.tex_grads[0])
+
+    def sky_step_number(self):
+        """what step_sky hands dvs_adam_step for the bias correction: Step::it = step + 1, the resumed step number included"""
+        return self.step + 1
+
+    def sky_adam(self, g):
+        """plain Adam on every texel, betas and eps of the other groups, rate DVS_SKY_LR; the moments start from zero"""
+        f = self.dt.type
+        it = self.sky_step_number()
+        b1, b2, eps = f(0.9), f(0.999), f(1e-15)
+        bc1, bc2 = f(1.0) / (f(1.0) - b1 ** f(it)), f(1.0) / (f(1.0) - b2 ** f(it))
+        S = self.sky
+        S["m"] = b1 * S["m"] + (f(1.0) - b1) * g
+        S["v"] = b2 * S["v"] + (f(1.0) - b2) * g * g
+        S["tex"] = (S["tex"] - f(S["lr"]) * (S["m"] * bc1) / (np.sqrt(S["v"] * bc2) + eps)).astype(self.dt)
 
     # ---- light prune of gstrain/trainer_refine.cpp prune_light() (pruneStrategy > 0, after refinement has stopped) ----------------------------------
     def prune_decisions(self, prune_opacity=0.005, min_opacity=0.005, prune_scale3d=0.1):
