@@ -92,7 +92,13 @@ static std::map<std::string, std::string> g_opts = {
     // extension of this build: --maskCarve T (0 = off .. 100) removes, at every prune occasion and before every save, the splats whose blend
     // weight over the training views landed on background pixels of the masks (--useMask 1): a splat stays iff fg > 0 and
     // fg (100 - T) >= bg T. The config struct has no room left: it is handed to the plugin as DVS_MASK_CARVE.
-    {"maskCarve", "0"}};
+    {"maskCarve", "0"},
+    // extension of this build: --mipFilter3d 1 trains with the 3D smoothing filter of Mip-Splatting: every splat is low-pass filtered in world
+    // space by the highest rate at which a training camera samples it (recomputed at load, after every change of the splat set, and every 100
+    // steps). Independent of --mipAntiliased, the method's 2D half; the paper's configuration is both. Every file a save writes but the resume
+    // PLY holds the fused (filtered) model; --exportFormat takes `fused` with it: <outputPath>_<it>.fused.ply, the full PLY of that model (implied
+    // when no other format is selected). The config struct has no room left: it is handed to the plugin as DVS_MIP_FILTER3D.
+    {"mipFilter3d", "0"}};
 static std::map<std::string, bool> g_given;
 
 static bool as_bool(const std::string& v) { return v == "1" || v == "true" || v == "True" || v == "on"; }
@@ -147,6 +153,7 @@ int main(int argc, const char* argv[]) {
     const bool export_frame = g_given.count("exportTransform") || g_given.count("exportOrient");
     if (gsopt::two_export_frames(g_given.count("exportTransform"), g_given.count("exportOrient"))) { std::cout << "Command Line Error: --exportTransform and --exportOrient exclude each other\n"; return 1; }
     if (gsopt::transformed_needs_frame(g_opts["exportFormat"], export_frame)) { std::cout << "Command Line Error: --exportFormat transformed needs --exportTransform or --exportOrient\n"; return 1; }
+    if (gsopt::fused_needs_filter(g_opts["exportFormat"], g_opts["mipFilter3d"] == "1")) { std::cout << "Command Line Error: --exportFormat fused needs --mipFilter3d 1\n"; return 1; }
     // plugin: "libgstrain.so" next to the executable (plugin.cpp:74 builds parent_path / "lib<name>.so")
     std::error_code ec;
     auto exe = std::filesystem::read_symlink("/proc/self/exe", ec);
@@ -201,7 +208,8 @@ int main(int argc, const char* argv[]) {
         else if (tok == "splat") train_config.exportFormats |= 2;
         else if (tok == "reduced") train_config.exportFormats |= 8;
         else if (tok == "transformed") train_config.exportFormats |= 16;     // (refused above without an export frame)
-        else { std::cout << "Command Line Error: --exportFormat takes compressed, splat, reduced, transformed or a comma-separated list of them, not '" << tok << "'\n"; return 1; }
+        else if (tok == "fused") train_config.exportFormats |= 32;           // (refused above without --mipFilter3d 1)
+        else { std::cout << "Command Line Error: --exportFormat takes compressed, splat, reduced, transformed, fused or a comma-separated list of them, not '" << tok << "'\n"; return 1; }
         at = comma + 1;
     }
     if (as_bool(g_opts["exportSpz"])) train_config.exportFormats |= 4;

@@ -54,6 +54,7 @@ const Row kRows[N_OPTIONS] = {
     {FOCUS_ROTATION,     "focusRotation",    "DVS_FOCUS_ROTATION",     F(3, ANY, false),              0,       "focus region",    "rx,ry,rz (radians)"},
     {EXPORT_TRANSFORM,   "exportTransform",  "DVS_EXPORT_TRANSFORM",   F(7, LAST_GT0, false),         0,       "exportTransform", "tx,ty,tz,rx,ry,rz,s with finite numbers and s > 0"},
     {EXPORT_ORIENT,      "exportOrient",     "DVS_EXPORT_ORIENT",      K(AXIS, nullptr),              0,       "exportTransform", "one of +x -x +y -y +z -z"},
+    {MIP_FILTER3D,       "mipFilter3d",      "DVS_MIP_FILTER3D",       K(BOOL01, nullptr),            0,       "filter3d",        kSwitch},
 };
 #undef U
 #undef F
@@ -162,12 +163,16 @@ ExtOptions read_env(const std::function<void(const std::string&)>& log) {
     return o;
 }
 
-bool transformed_needs_frame(const std::string& formats, bool frame) {
-    for (size_t at = 0; !frame && at < formats.size();) {
+namespace {
+bool lists(const std::string& formats, const char* token) {                  // `token` is one of the comma list's entries
+    for (size_t at = 0; at < formats.size();) {
         const size_t comma = std::min(formats.find(',', at), formats.size());
-        if (formats.compare(at, comma - at, "transformed") == 0) return true;
+        if (formats.compare(at, comma - at, token) == 0) return true;
         at = comma + 1;
     }
     return false;
 }
+}  // namespace
+bool transformed_needs_frame(const std::string& formats, bool frame) { return !frame && lists(formats, "transformed"); }
+bool fused_needs_filter(const std::string& formats, bool filter3d) { return !filter3d && lists(formats, "fused"); }
 }  // namespace gsopt

@@ -12,7 +12,7 @@ enum Id {
     MESH_MIN_COMPONENT, MESH_NORMALS, MESH_DECIMATE, MESH_BOUNDS, MESH_TRUNC_VOXELS,
     RENDER_FORMAT, RENDER_LAYERS, RENDER_DEPTH_SCALE, RENDER_PNG_LEVEL,
     EXPORT_LOD, LOD_RESOLUTION, MASK_CARVE, SH_CULL_THRESHOLD, REDUCED_HALF, SKY_RESOLUTION, SKY_LR,
-    FOCUS_REGION, FOCUS_ROTATION, EXPORT_TRANSFORM, EXPORT_ORIENT, N_OPTIONS
+    FOCUS_REGION, FOCUS_ROTATION, EXPORT_TRANSFORM, EXPORT_ORIENT, MIP_FILTER3D, N_OPTIONS
 };
 // What a value looks like, each parser written once (ext_options.cpp):
 //   UINT     1..digits decimal digits and nothing else, lo..hi or the one extra value `also` (-1: none)          -> out[0]
@@ -66,4 +66,5 @@ enum { LAYER_COLOR = 1, LAYER_DEPTH = 2, LAYER_ALPHA = 4 };               // DVS
 inline bool layers_need_png(int layers, bool png) { return layers != LAYER_COLOR && !png; }     // JPEG files carry colour alone
 inline bool two_export_frames(bool transform, bool orient) { return transform && orient; }       // one export frame at most
 bool transformed_needs_frame(const std::string& export_formats, bool frame);                    // `transformed` in the comma list, no frame
+bool fused_needs_filter(const std::string& export_formats, bool filter3d);                      // `fused` in the comma list, mipFilter3d off
 }  // namespace gsopt

@@ -38,7 +38,7 @@ int main() {
                                    switch_yes = {"0", "1"}, switch_no = {"2", "+1", "-1", "1x", "01", "yes"};
     const std::vector<Probe> probes = {
         {"DVS_MESH_MIN_COMPONENT", {"0", "100", "12.5", "12.", "100.00", "007"}, {"100.01", "101", "+5", "-1", "5x", "1000", "12.345", ".5"}},
-        {"DVS_MESH_NORMALS", switch_yes, switch_no}, {"DVS_REDUCED_HALF", switch_yes, switch_no},
+        {"DVS_MESH_NORMALS", switch_yes, switch_no}, {"DVS_REDUCED_HALF", switch_yes, switch_no}, {"DVS_MIP_FILTER3D", switch_yes, switch_no},
         {"DVS_MESH_DECIMATE", {"0", "2", "16", "8", "02"}, {"1", "17", "+2", "-2", "2x", "016"}},
         {"DVS_MESH_BOUNDS", box_yes, box_no}, {"DVS_FOCUS_REGION", box_yes, box_no},
         {"DVS_MESH_TRUNC_VOXELS", rate_yes, rate_no}, {"DVS_SKY_LR", rate_yes, rate_no}, {"DVS_RENDER_DEPTH_SCALE", rate_yes, rate_no},
@@ -103,7 +103,8 @@ int main() {
     expect(o.i(MASK_CARVE) == 50 && o.f(MESH_BOUNDS, 3) == 1.0f && o.f(EXPORT_TRANSFORM, 6) == 2.5f && o.f(EXPORT_ORIENT, 2) == -1.0f && o.on(RENDER_FORMAT), "read_env", "values");
     expect(layers_need_png(3, false) && !layers_need_png(3, true) && !layers_need_png(1, false) && two_export_frames(true, true) && !two_export_frames(true, false) &&
            transformed_needs_frame("splat,transformed", false) && !transformed_needs_frame("splat,transformed", true) && !transformed_needs_frame("splat,transformedx", false) &&
-           !transformed_needs_frame("", false) && transformed_needs_frame(std::string(1000, ',') + "transformed", false), "rules", "across options");
+           !transformed_needs_frame("", false) && transformed_needs_frame(std::string(1000, ',') + "transformed", false) && fused_needs_filter("splat,fused", false) &&
+           !fused_needs_filter("splat,fused", true) && !fused_needs_filter("fusedx", false) && !fused_needs_filter("", false), "rules", "across options");
     printf("ext_options_check: %s (%d failed)\n", failures ? "FAILED" : "ok", failures);
     return failures ? 1 : 0;
 }

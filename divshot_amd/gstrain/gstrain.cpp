@@ -123,6 +123,8 @@ void GaussianTrainerScene::saveGaussianModel() {
     Impl& m = *impl_;
     if (m.cfg.enableFocusRegion && m.ctx) m.prune_region(m.step);           // what is written holds inside splats only (every rank: the replicas stay identical)
     if (m.ctx) m.prune_mask_carve(m.step);                                  // (nothing when maskCarve is 0; every rank, like the region prune)
+    struct SaveSet { bool& in_use; ~SaveSet() { in_use = false; } } save_set{m.f3d_save};      // the save's own fused set belongs to this save alone
+    if (m.ctx) m.filter3d_for_save();                                       // (nothing when mipFilter3d is 0: the exports below pack the model fused at the saved positions)
     // the replicas are identical: one file — unless DVS_SAVE_ALL_RANKS=1 asks every rank for its own (<model>_<it>.ply.rank<r>), which
     // is how the two-rank test checks that they ARE identical, bit for bit
     static const bool all_ranks = env_is("DVS_SAVE_ALL_RANKS", "1");
@@ -147,7 +149,7 @@ void GaussianTrainerScene::saveGaussianModel() {
     if (m.rank == 0 && m.export_formats()) {
         struct Done { bool& filled; ~Done() { filled = false; } } done{m.xf_filled};      // the transformed set belongs to this save alone
         if (m.xf_set) m.fill_transformed();                                  // (an export transform is set: the exports below pack from it)
-        for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT, (int)Impl::EXPORT_SPZ, (int)Impl::EXPORT_REDUCED, (int)Impl::EXPORT_TRANSFORMED})
+        for (int format : {(int)Impl::EXPORT_COMPRESSED, (int)Impl::EXPORT_SPLAT, (int)Impl::EXPORT_SPZ, (int)Impl::EXPORT_REDUCED, (int)Impl::EXPORT_TRANSFORMED, (int)Impl::EXPORT_FUSED})
             if (m.export_formats() & format) m.export_model(format);
     }
     if (m.rank == 0 && m.opt.i(gsopt::EXPORT_LOD) > 0) m.export_lod();                  // <modelPath>_<it>.lod<k>.ply (DVS_EXPORT_LOD / setLodExport)
@@ -190,6 +192,11 @@ void GaussianTrainerScene::setMaskCarve(int percent) {
     if (!gsopt::admits(gsopt::MASK_CARVE, percent)) { logf_("setMaskCarve: %d is not a percentage 0 (off) .. 100: the mask carve is off", percent); percent = 0; }
     m.opt.set(gsopt::MASK_CARVE, percent);
     m.report_mask_carve("setMaskCarve");
+}
+void GaussianTrainerScene::setMipFilter3d(bool on) {
+    Impl& m = *impl_;
+    m.opt.set(gsopt::MIP_FILTER3D, on);
+    if (m.rank == 0) logf_("config: mipFilter3d %d (setMipFilter3d): in force from the next loadTrainData / resetGaussian", (int)on);
 }
 void GaussianTrainerScene::setReducedExport(float shCullThreshold, bool halfFloat) {
     Impl& m = *impl_;
@@ -262,6 +269,7 @@ void GaussianTrainerScene::resetGaussian() {
     m.step = 0; curIteration = 0; pruenIteraions.clear();
     m.eval_it = -1;
     m.region_dirty = true;                                                  // (the initial splats are all back: the next step prunes them again)
+    m.setup_filter3d();                                                     // (what setMipFilter3d said since; on: the filter of the initial splats at the next use)
     m.cur_level = -1; m.lw = m.W; m.lh = m.H;
     m.host_valid = false;
     (void)dvs_raster_forward_cancel_prepared(m.ctx.get());          // (a pipelined step may have projected the next iteration's splats already)

@@ -213,7 +213,7 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     bool xf_filled = false;                                                  // this save's set is in d_xf
     GrowBuf<float> d_xf[4], d_xf_rows;                                       // pos, shN (tiled), scale, rot; shN as rows for the .transformed.ply
     static int xf_slot(int g) { return g == P_POS ? 0 : g == P_SHN ? 1 : g == P_SCALE ? 2 : g == P_ROT ? 3 : -1; }
-    const float* ex(int g) const { return xf_filled && xf_slot(g) >= 0 ? d_xf[xf_slot(g)].get() : d_param[g].get(); }   // what an export packs from
+    const float* ex(int g) const { return xf_filled && xf_slot(g) >= 0 ? d_xf[xf_slot(g)].get() : model_ex(g); }   // what an export packs from
     bool set_export_transform(const dvs_similarity& m, const std::string& how);
     bool set_export_orientation(const char* axis, const char* from);
     void setup_export_transform();
@@ -326,6 +326,37 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     void prune_region(int it);
     const float* region_masks(const dvs_camera* bc, const float* const* in, int nb, int w, int h);
 
+    // 3D smoothing filter (opt's MIP_FILTER3D, or what setMipFilter3d said, read at load and at resetGaussian; trainer_filter3d.cpp,
+    // INTEGRATION.md "3D smoothing filter"): d_filter[i] is the world-space standard deviation splat i is smoothed by — the highest rate
+    // at which a full-resolution training camera samples it (dvs_filter3d_compute) — and d_scale_eff / d_opacity_eff are what splats()
+    // hands to every renderer (dvs_filter3d_apply_range). The trained values stay in d_param: the refinement rules, the opacity reset,
+    // MCMC, Adam and the resume PLY read those, and finish_range takes the rasterizer's gradients back to them first
+    // (dvs_filter3d_chain_range). The filter is computed again when f3d_dirty (load, resume, anything that changed the splat set:
+    // apply_plan, MCMC, resetGaussian) and every 100 optimizer steps; the effective arrays again whenever the trained ones changed since
+    // (f3d_fresh). Both happen in filter3d_refresh(), which every reader of splats() calls first; when it does either it cancels a
+    // projection the pipelined step prepared from the arrays it rewrites. A save packs the filter of the positions BEING SAVED: when that
+    // is not the one training holds, filter3d_for_save() computes it and its effective values into a second set (d_save_*) that only the
+    // exports read (model_ex) — training, its schedule and its prepared projection are never touched by a save.
+    // Nothing is allocated, launched, logged or written while the option is 0.
+    bool f3d_on = false, f3d_dirty = false, f3d_fresh = false, f3d_save = false;
+    int f3d_it = 0;                                                          // optimizer steps behind the trained values (= step between two trainSteps)
+    int f3d_step = 0, f3d_cams = 0, f3d_cap = 0;                             // f3d_it at the last computation; training cameras in d_f3d_rows; splats the arrays hold
+    DevBuf<float> d_filter, d_scale_eff, d_opacity_eff, d_f3d_rows; DevBuf<uint32_t> d_f3d_scratch;
+    GrowBuf<float> d_save_filter, d_save_scale, d_save_opacity;              // a save's own set (f3d_save: in use)
+    TimedPair f3d_timer;
+    void setup_filter3d();
+    bool filter3d_due(int optimizer_steps) const { return f3d_on && (f3d_dirty || optimizer_steps - f3d_step >= 100); }
+    void filter3d_compute(float* filter, const char* what);
+    void filter3d_apply(int first, int count);
+    void filter3d_refresh();
+    void filter3d_for_save();
+    void filter3d_chain(int first, int count);
+    void export_fused();
+    // scale / opacity: what a renderer reads (the effective arrays while the filter is on); the other groups: d_param
+    const float* model(int g) const { return f3d_on && g == P_SCALE ? d_scale_eff.get() : f3d_on && g == P_OPA ? d_opacity_eff.get() : d_param[g].get(); }
+    // ... and what an export packs: the save's own set while it is in use
+    const float* model_ex(int g) const { return f3d_save && g == P_SCALE ? d_save_scale.get() : f3d_save && g == P_OPA ? d_save_opacity.get() : model(g); }
+
     ~Impl() { if (device >= 0) (void)hipSetDevice(device); }                // (the members release themselves, after this body)
     // floats of group g on the device: the 45 higher-order SH floats live in the DVS_SHN_TILED layout (48 per splat,
     // whole 64-splat tiles); parameters, gradients and Adam moments share it — the optimizer is element-wise.
@@ -413,7 +444,11 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
         s.scale = p[P_SCALE].get(); s.rot = p[P_ROT].get(); s.n = n;
         return s;
     }
-    dvs_splats splats() const { return splats_of(d_param, n); }
+    dvs_splats splats() const {                                              // what the rasterizer reads (filter3d_refresh() first, outside a step)
+        dvs_splats s = splats_of(d_param, n);
+        s.scale = model(P_SCALE); s.opacity = model(P_OPA);
+        return s;
+    }
     std::string save_path(int it, const char* suffix) const { return cfg.modelPath + "_" + std::to_string(it) + suffix; }   // every file a save writes
     std::string model_file(int it) const { return save_path(it, ".ply"); }
     bool model_path_ends(const char* suffix) const {
@@ -423,15 +458,18 @@ struct __attribute__((visibility("hidden"))) GaussianTrainerScene::Impl {     //
     // EXPORT_* bits of the compact formats a save writes; decided at every use, since the editor sets modelPath after construction
     // EXPORT_TRANSFORMED: <modelPath>_<it>.transformed.ply, the full PLY in the export frame; counts only while a transform is set, and is
     // implied when one is set and no other format is selected (a set transform is never a silent no-op)
-    enum { EXPORT_COMPRESSED = 1, EXPORT_SPLAT = 2, EXPORT_SPZ = 4, EXPORT_REDUCED = 8, EXPORT_TRANSFORMED = 16 };
+    // EXPORT_FUSED: <modelPath>_<it>.fused.ply, the full PLY of the model the 3D smoothing filter fused (in the export frame when one is
+    // set); counts only while the filter is on, and is implied when it is on and no other format is selected
+    enum { EXPORT_COMPRESSED = 1, EXPORT_SPLAT = 2, EXPORT_SPZ = 4, EXPORT_REDUCED = 8, EXPORT_TRANSFORMED = 16, EXPORT_FUSED = 32 };
     int suffix_formats() const {
         return model_path_ends(".compressed.ply") ? EXPORT_COMPRESSED : model_path_ends(".splat") ? EXPORT_SPLAT : model_path_ends(".spz") ? EXPORT_SPZ :
                model_path_ends(".reduced.ply") ? EXPORT_REDUCED : 0;
     }
     int asked_formats() const { return env_int("DVS_EXPORT_FORMATS", cfg.exportFormats); }   // 0: the suffix of modelPath decides
     int export_formats() const {
-        const int f = (asked_formats() ? asked_formats() : suffix_formats()) & (EXPORT_COMPRESSED | EXPORT_SPLAT | EXPORT_SPZ | EXPORT_REDUCED | (xf_set ? EXPORT_TRANSFORMED : 0));
-        return f == 0 && xf_set ? (int)EXPORT_TRANSFORMED : f;
+        const int f = (asked_formats() ? asked_formats() : suffix_formats()) &
+                      (EXPORT_COMPRESSED | EXPORT_SPLAT | EXPORT_SPZ | EXPORT_REDUCED | (xf_set ? EXPORT_TRANSFORMED : 0) | (f3d_on ? EXPORT_FUSED : 0));
+        return f != 0 ? f : (xf_set ? (int)EXPORT_TRANSFORMED : 0) | (f3d_on ? (int)EXPORT_FUSED : 0);
     }
     void export_model(int format);
     void export_spz();

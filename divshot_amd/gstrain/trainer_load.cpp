@@ -57,6 +57,7 @@ void GaussianTrainerScene::Impl::alloc_params(int count, int capacity, const std
 }
 
 void GaussianTrainerScene::Impl::create_context(int count, int capacity, const std::vector<float> init[6]) {
+    f3d_on = false;                                                          // (decided in finish_load: a loader renders through splats() before)
     vpi = std::max(1, std::min(env_int("DVS_VIEWS_PER_ITER", cfg.viewsPerIter), 16));
     sequential_views = env_is("DVS_VIEWS_MODE", "sequential");
     if (vpi > 1 && rank == 0)
@@ -177,10 +178,12 @@ void GaussianTrainerScene::Impl::finish_load(const std::function<void(std::vecto
     setup_sky(resumed);
     setup_region();
     setup_export_transform();                                               // (DVS_EXPORT_TRANSFORM / DVS_EXPORT_ORIENT; needs the cameras)
+    setup_filter3d();                                                       // (DVS_MIP_FILTER3D / setMipFilter3d; needs the split and the cameras)
     report_config();
     describe(resumed);
     if (cfg.enableFocusRegion) prune_region(step);
     region_dirty = false;
+    filter3d_refresh();                                                      // the filter of the loaded or resumed splats, logged at load
     if (exchange_factorised()) setup_exchange();
 }
 

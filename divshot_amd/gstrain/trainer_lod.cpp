@@ -18,8 +18,8 @@ void GaussianTrainerScene::Impl::export_lod() {
         for (int k = 0; k < 3; ++k) { bounds[k] = std::min(bounds[k], p[k]); bounds[3 + k] = std::max(bounds[3 + k], p[k]); }
     }
     d_lod_scratch.reserve(dvs_lod_scratch_bytes(n));
-    const float *pos = d_param[P_POS].get(), *sh0 = d_param[P_SH0].get(), *shN = d_param[P_SHN].get(), *opa = d_param[P_OPA].get(),
-                *scale = d_param[P_SCALE].get(), *rot = d_param[P_ROT].get();
+    const float *pos = d_param[P_POS].get(), *sh0 = d_param[P_SH0].get(), *shN = d_param[P_SHN].get(), *opa = model_ex(P_OPA),
+                *scale = model_ex(P_SCALE), *rot = d_param[P_ROT].get();
     for (int k = 1; k <= L; ++k) {
         const int res = R >> (k - 1);                                        // >= 32 >> 3 = 4: what dvs_lod_lattice_for takes
         dvs_lod_lattice lat;

@@ -24,11 +24,13 @@ void GaussianTrainerScene::Impl::report_config() const {
               "%dx%d (targets box-filtered per step, cameras of dvs_camera_downscale); full resolution from iteration %d; evaluation always at full size",
               res_every, res_levels, res_levels, res_every, W, H, res_levels * res_every + 1);
     if (const int fmts = export_formats())
-        logf_("config: exportFormats %d: every save also writes%s%s%s%s%s beside the full PLY, packed on the device%s%s", fmts,
+        logf_("config: exportFormats %d: every save also writes%s%s%s%s%s%s beside the full PLY, packed on the device%s%s", fmts,
               (fmts & EXPORT_COMPRESSED) ? " <modelPath>_<it>.compressed.ply" : "", (fmts & EXPORT_SPLAT) ? " <modelPath>_<it>.splat" : "",
               (fmts & EXPORT_SPZ) ? " <modelPath>_<it>.spz" : "", (fmts & EXPORT_REDUCED) ? " <modelPath>_<it>.reduced.ply" : "",
               (fmts & EXPORT_TRANSFORMED) ? " <modelPath>_<it>.transformed.ply (the full PLY in the export frame)" : "",
-              asked_formats() == 0 ? ((fmts & ~EXPORT_TRANSFORMED) ? " (turned on by the suffix of modelPath)" : " (implied by the export transform)") : "",
+              (fmts & EXPORT_FUSED) ? " <modelPath>_<it>.fused.ply (the full PLY of the model the 3D smoothing filter fused)" : "",
+              asked_formats() == 0 ? ((fmts & ~(EXPORT_TRANSFORMED | EXPORT_FUSED)) ? " (turned on by the suffix of modelPath)"
+                                      : (fmts & EXPORT_TRANSFORMED) ? " (implied by the export transform)" : " (implied by mipFilter3d)") : "",
               (fmts & EXPORT_SPZ) && !test_idx.empty() ? "; the .spz payload is decoded on the device and scored on the held-out views" : "");
     report_export_transform();
     if (export_formats() & EXPORT_REDUCED)
@@ -148,6 +150,7 @@ void GaussianTrainerScene::Impl::ensure_eval_ctx() {
 void GaussianTrainerScene::Impl::for_each_eval_pass(const dvs_splats& sp, const std::vector<int>& which, bool with_sky,
                                                     const std::function<void(const EvalPass&)>& per_pass) {
     ensure_eval_ctx();
+    filter3d_refresh();                                                      // (mipFilter3d: splats() of the caller reads the effective arrays)
     const dvs_opts opts = eval_opts();
     std::vector<dvs_camera> bc((size_t)eval_views);
     const int total = (int)which.size();
@@ -315,6 +318,7 @@ void GaussianTrainerScene::Impl::export_model(int format) {
     if (format == EXPORT_SPZ) { export_spz(); return; }
     if (format == EXPORT_REDUCED) { export_reduced(); return; }
     if (format == EXPORT_TRANSFORMED) { export_transformed(); return; }
+    if (format == EXPORT_FUSED) { export_fused(); return; }
     const auto t_start = std::chrono::steady_clock::now();
     const bool compressed = format == EXPORT_COMPRESSED;
     const size_t n_chunks = ((size_t)n + 255) / 256;
@@ -496,7 +500,7 @@ void GaussianTrainerScene::Impl::fill_transformed() {
     const auto t_start = std::chrono::steady_clock::now();
     for (int g : {(int)P_POS, (int)P_SHN, (int)P_SCALE, (int)P_ROT}) d_xf[xf_slot(g)].reserve(dev_floats_for(g, n) * sizeof(float) + 16);
     const int rc = dvs_transform_splats(stream.get(), n, sh_max, &xf, xf_D, d_param[P_POS].get(), d_param[P_SHN].get(), DVS_SHN_TILED,
-                                        d_param[P_SCALE].get(), d_param[P_ROT].get(), d_xf[0].get(), d_xf[1].get(), d_xf[2].get(), d_xf[3].get());
+                                        model_ex(P_SCALE), d_param[P_ROT].get(), d_xf[0].get(), d_xf[1].get(), d_xf[2].get(), d_xf[3].get());
     if (rc != DVS_OK) throw std::runtime_error("dvs_transform_splats: status " + std::to_string(rc));
     HIP_OR_THROW(hipStreamSynchronize(stream.get()));
     xf_filled = true;
@@ -519,7 +523,13 @@ void GaussianTrainerScene::Impl::export_transformed() {
     HIP_OR_THROW(hipStreamSynchronize(stream.get()));
     const std::string file = save_path(step, ".transformed.ply");
     std::string err;
-    if (!gsply::write_ply(file, (size_t)n, h[0].data(), host[P_SH0].data(), h[1].data(), host[P_OPA].data(), h[2].data(), h[3].data(), cfg.mipAntiliased, &err)) {
+    std::vector<float> fused_opacity;                                        // mipFilter3d: the exports hold the fused model (the frame leaves opacity alone)
+    if (f3d_on) {
+        fused_opacity.resize((size_t)n);
+        HIP_OR_THROW(hipMemcpy(fused_opacity.data(), ex(P_OPA), fused_opacity.size() * sizeof(float), hipMemcpyDeviceToHost));
+    }
+    const float* const opacity = f3d_on ? fused_opacity.data() : host[P_OPA].data();
+    if (!gsply::write_ply(file, (size_t)n, h[0].data(), host[P_SH0].data(), h[1].data(), opacity, h[2].data(), h[3].data(), cfg.mipAntiliased, &err)) {
         logf_("export @%d: %s", step, err.c_str());
         return;
     }

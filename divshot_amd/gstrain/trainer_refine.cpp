@@ -41,6 +41,7 @@ void GaussianTrainerScene::Impl::apply_plan(const dvs_densify_params& prm, int n
         DVS_OR_THROW(dvs_densify_apply(stream.get(), n, d_action.get(), d_offsets.get(), &prm, set == 0 ? 0 : 1, s6, d6, new_n));
         for (int g = 0; g < 6; ++g) std::swap(src[g], dst[g]);               // (the owners: what was written is now the live set)
     }
+    f3d_dirty = true;                                                        // (mipFilter3d: another splat set, another filter)
 }
 
 // densifyStrategy 1 (MCMC): dead splats are relocated onto live ones drawn ~ opacity, then the model grows by 5 % up to the cap.
@@ -57,6 +58,7 @@ void GaussianTrainerScene::Impl::densify_mcmc(int it) {
         n += n_new;
         HIP_OR_THROW(hipMemsetAsync(d_grad[P_SHN], 0, dev_floats_for(P_SHN, cap) * sizeof(float), stream.get()));   // pad lanes of the new last tile
     }
+    f3d_dirty = true;                                                        // (mipFilter3d: relocated and new splats sit elsewhere)
     host_valid = false;
 }
 

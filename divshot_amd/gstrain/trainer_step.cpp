@@ -172,6 +172,7 @@ const float* GaussianTrainerScene::Impl::region_masks(const dvs_camera* bc, cons
 void GaussianTrainerScene::Impl::render_backward(Step& s) {
     const bool fact = exchange_factorised(), seq = sequential_views;
     const int passes = seq ? vpi : 1, pass_views = seq ? 1 : vpi;
+    filter3d_refresh();                                                      // (mipFilter3d: the effective scale and opacity of this step's parameters)
     const dvs_splats sp = splats();
     const int W = s.Wd, H = s.Hd;                                            // the step's level
     const size_t img = 3 * (size_t)W * H;
@@ -296,6 +297,7 @@ void GaussianTrainerScene::Impl::exchange(const Step& s, bool pipelined) {
 // element-wise, so a range is bit-identical to the whole-array calls.
 void GaussianTrainerScene::Impl::finish_range(const Step& s, int first, int count, const int* groups, int n_groups, const int* gate) {
     float* const opa = d_param[P_OPA].get(); float* const scale = d_param[P_SCALE].get();
+    if (f3d_on) { filter3d_chain(first, count); f3d_fresh = false; f3d_it = s.it; }         // the backward's gradients are those of the effective values; the step below changes the trained ones
     if (s.mcmc)        // opacity and scale regularisers of the MCMC strategy (0.01 each in the published rule): a function of the replicated
                        // parameters, added once (after the exchange) on every rank
         DVS_OR_THROW(dvs_mcmc_regularize_range(stream.get(), n, first, count, opa, scale, d_grad[P_OPA], d_grad[P_SCALE], 0.01f, 0.01f));
@@ -320,7 +322,7 @@ void GaussianTrainerScene::Impl::finish_range(const Step& s, int first, int coun
 // the all-reduces of the chunks before it run under the Adam / A2 of their predecessors. Iterations that refine, reset or prune
 // change the parameters after Adam: no early projection there (the next forward projects everything itself).
 void GaussianTrainerScene::Impl::finish_pipelined(const Step& s) {
-    const bool early = !s.refine_now && !s.reset_now && !s.prune_now && s.it < cfg.numIters;
+    const bool early = !s.refine_now && !s.reset_now && !s.prune_now && s.it < cfg.numIters && !filter3d_due(s.it);     // (a filter due at the next step changes what A2 reads)
     if (early) draw_cameras(next_ci);
     const std::vector<dvs_camera> ncams = early ? rank_cameras(next_ci, level_of(s.it)) : std::vector<dvs_camera>();   // (the NEXT step's level)
     dvs_opts nopts = s.opts;
@@ -330,6 +332,8 @@ void GaussianTrainerScene::Impl::finish_pipelined(const Step& s) {
         const int first = k * s.chunk_per, count = std::min(s.chunk_per, n - first);
         HIP_OR_THROW(hipStreamWaitEvent(stream.get(), ev_ar[(size_t)k].get(), 0));
         finish_range(s, first, count, kGeomGroups, 4, nullptr);        // ungated Adam, unlike the unpipelined tail (s.adam_gate)
+        if (early && f3d_on) filter3d_apply(first, count);              // what A2 of this chunk reads
         if (early) DVS_OR_THROW(dvs_raster_forward_views_prepare(ctx.get(), stream.get(), &sp, ncams.data(), vpi, &nopts, first, count));
     }
+    if (early && f3d_on && s.n_chunks > 0) f3d_fresh = true;               // (the chunks cover every splat)
 }

@@ -10,6 +10,7 @@
 #define DVS_TRAIN_H
 #include <stddef.h>
 #include <stdint.h>
+#include "dvs_raster.h"   /* dvs_camera (the 3D smoothing filter's camera rows) */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -224,6 +225,36 @@ int dvs_mcmc_add_noise_range(void* stream, int n, int first, int count, float* p
                              uint32_t seed);
 int dvs_mcmc_regularize_range(void* stream, int n, int first, int count, const float* opacity, const float* scale, float* g_opacity, float* g_scale,
                               float opacity_reg, float scale_reg);
+
+/* ---- 3D smoothing filter (the world-space half of Mip-Splatting, arXiv 2311.16493; the screen-space half is dvs_opts.antialias) -----------
+ * Every splat is convolved with an isotropic Gaussian of standard deviation filter[i] (world units): the highest rate at which a
+ * training camera samples it, so that no view can see detail finer than any training pixel did. Element-wise kernels AROUND the
+ * rasterizer: it reads the effective scale and opacity that apply writes, and chain takes its gradients back to the trained values.
+ * All arrays DEVICE, fp32, 16-byte aligned; asynchronous on `stream`; DVS_ERR_INVALID for NULL or misaligned pointers, negative counts,
+ * n_cams < 1 or a range outside [0, n).
+ *
+ * pack_cameras (HOST only): host_rows[16 c ..] = the three rows of camera c's world-to-camera transform (from `view`), then focal_x,
+ *   width, height and one pad float. The caller copies the rows to the device.
+ * compute: for camera c and splat i with camera-space (x, y, z), the camera SEES the splat iff z > 0.2, |x/z focal_x| <= 0.65 width and
+ *   |y/z focal_x| <= 0.65 height (the paper code's near bound and 15 % margin; focal_x on both axes, as there). The principal point is
+ *   taken as the image centre: off-centre intrinsics are not modelled, the margin absorbs them.
+ *     filter[i] = sqrt(0.2) min over the seeing cameras of z / focal_x
+ *   A splat no camera sees (a non-finite position never is) takes the maximum filter of the seen splats; 0 everywhere when none is seen.
+ *   scratch: 16 bytes; afterwards scratch[0] = the bits of that maximum, scratch[1] = the number of seen splats.
+ * apply_range: with s_k = exp(scale_k), f = filter[i], r_k = s_k^2 / (s_k^2 + f^2), c = sqrt(r_0 r_1 r_2), for the splats [first, first+count):
+ *     scale_eff_k = 0.5 log(s_k^2 + f^2),   opacity_eff = logit(sigmoid(a) c),
+ *   the logit formed from 1 - o' = sigmoid(-a) + sigmoid(a) (1 - c), finite for a in [-20, 20]. f == 0: bit-for-bit copies.
+ * chain_range: in place, gradients with respect to the effective values -> with respect to the trained ones (scale, opacity: the trained):
+ *     g_scale_k <- g_scale_k r_k + g_opacity (1 - r_k) / (1 - o'),   g_opacity <- g_opacity sigmoid(-a) / (1 - o').   f == 0: the identity.
+ * The forms without _range are the same calls on (0, n); a range is bit-identical to those rows of the whole-array call. */
+int dvs_filter3d_pack_cameras(const dvs_camera* cams, int n_cams, float* host_rows /* HOST [n_cams][16] */);
+int dvs_filter3d_compute(void* stream, int n, const float* pos, const float* dev_cam_rows, int n_cams, float* filter, uint32_t* scratch);
+int dvs_filter3d_apply_range(void* stream, int n, int first, int count, const float* scale, const float* opacity, const float* filter,
+                             float* scale_eff, float* opacity_eff);
+int dvs_filter3d_apply(void* stream, int n, const float* scale, const float* opacity, const float* filter, float* scale_eff, float* opacity_eff);
+int dvs_filter3d_chain_range(void* stream, int n, int first, int count, const float* scale, const float* opacity, const float* filter,
+                             float* g_scale, float* g_opacity);
+int dvs_filter3d_chain(void* stream, int n, const float* scale, const float* opacity, const float* filter, float* g_scale, float* g_opacity);
 
 #ifdef __cplusplus
 }

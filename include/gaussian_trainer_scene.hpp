@@ -143,6 +143,11 @@ public:
     // 0 = off, any other value is reported and counts as 0. Wins over DVS_MASK_CARVE once called. Turned on after the load of a capture
     // with distorted cameras, the pixels the undistortion left blank count as background (at load their validity is kept apart).
     void setMaskCarve(int percent);
+    // 3D smoothing filter (extension of this build; INTEGRATION.md "3D smoothing filter"): the world-space half of Mip-Splatting — the
+    // rasterizer reads every splat convolved with the Gaussian of the highest rate at which a training camera samples it; every file a
+    // save writes but the resume PLY holds that fused model, <modelPath>_<it>.fused.ply (exportFormats bit 32) its full PLY. Takes effect
+    // at the next loadTrainData / resetGaussian. Wins over DVS_MIP_FILTER3D once called. Independent of mipAntiliased, the 2D half.
+    void setMipFilter3d(bool on);
     // the .reduced.ply export (extension of this build; exportFormats bit 8, INTEGRATION.md "Compact exports"): the colour a splat may lose
     // when cullSH lowers its SH degree (>= 0, default 0.01) and whether positions are written as half floats. Once called it wins over
     // DVS_SH_CULL_THRESHOLD / DVS_REDUCED_HALF.
